@@ -16,9 +16,15 @@ merged with one RCCL all-reduce per step (slam_grid_merge_begin / _finish of the
     python bench.py --config 5      # streaming mapper: sliding-window target, periodic merge, PCIe inclusive
 
 Rank 0 prints ONE JSON line.  `value` is registered scan-points/s over the whole job with inputs resident in HBM;
-`grid_cell_updates_per_s` is the second half of BASELINE.json's metric; `value_pcie_inclusive` is the same workload
-fed from pinned host memory through the streaming mapper (SURVEY 8(d) metric (1): H2D of scans + kernels + D2H of
-poses); `model_build_ms` is what 8(d) asks to report separately (the map upload + index build of a match).
+`grid_cell_updates_per_s` is the second half of BASELINE.json's metric; `ms_per_step` is the milliseconds one timed step
+took.  A plain run sets up, warms up, times exactly `--steps` steps (one timed region), writes the last step's arrays
+if --dump-outputs DIR is given, and prints the line.  Everything else moves behind --full (five timed regions, median
+reported): the one-stream steps, per-kernel times and the roofline, the pose and merge checks, `value_pcie_inclusive`
+(the same workload fed from pinned host memory through the streaming mapper: SURVEY 8(d) metric (1), H2D of scans +
+kernels + D2H of poses), `model_build_ms` (what 8(d) asks to report separately: the map upload + index build of a
+match), the other configs' side runs and the CPU baseline.
+
+    python bench.py --full          # the whole record, as the profiles/ and the docs quote it
 """
 import argparse
 import json
@@ -501,6 +507,34 @@ def side_run(argv, keys, timeout=420):
         return {"error": repr(ex)}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays, planes=()):
+    """--dump-outputs: every array as d/<name>.npy, float64 (float32 where the values are bytes or float32).  When the whole
+    exceeds DUMP_BUDGET_BYTES, the `planes` (arrays of one cell count) keep a fixed sample of their cells -- seeded, sorted, the
+    same for every plane and every run of the same arguments -- whose flat indices go beside them as grid_sample_cells.npy."""
+    out = {}
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        out[k] = np.ascontiguousarray(v, np.float32 if v.dtype.itemsize == 1 or v.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BUDGET_BYTES and planes:
+        cells = out[planes[0]].size
+        fixed = total - sum(out[k].nbytes for k in planes)
+        per_cell = sum(out[k].itemsize for k in planes) + 8
+        n = int(min(cells, (DUMP_BUDGET_BYTES - fixed) // per_cell))
+        idx = np.sort(np.random.default_rng(20240917).choice(cells, n, replace=False))
+        for k in planes:
+            out[k] = np.ascontiguousarray(out[k].reshape(-1)[idx])
+        out["grid_sample_cells"] = idx.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BUDGET_BYTES, "outputs exceed the dump budget"
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    log("wrote %d arrays (%.1f MB) to %s" % (len(out), sum(a.nbytes for a in out.values()) / 1e6, d))
+
+
 def main():
     global GRID
     # dmabuf IPC between the ranks' processes (RCCL needs it on this driver); already exported on the boxes, set here for a launcher
@@ -598,9 +632,17 @@ def main():
     ap.add_argument("--no-calibrate", action="store_true",
                     help="N>1 over RCCL: skip the calibration (about 1 700 steps before the warm-up) and run with the one-GPU defaults; recorded "
                          "in the line as config.calibration_skipped, so that a run that was cut short can be told from one that hung")
-    ap.add_argument("--regions", type=int, default=5,
+    ap.add_argument("--regions", type=int, default=None,
                     help="timed regions of `steps` steps each, run back to back behind the one warm-up; the MEDIAN region is reported "
-                         "(ms_per_step_runs lists them all)")
+                         "(ms_per_step_runs lists them all).  Default 1 (exactly `steps` timed steps); 5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: five timed regions, the one-stream steps, per-kernel times and the roofline, "
+                         "the pose and merge checks, the extra legs (model build, PCIe-inclusive stream, single scan, endpoint, config 3, "
+                         "local mapper, point-to-line / config 4 / config 5 / two-rank side runs) and the CPU baseline.  Without it a run "
+                         "sets up, warms up, times `steps` steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (registered poses, per-scan ICP results, the "
+                         "grid's evidence and occupancy planes) as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
     ap.add_argument("--start-stagger-us", type=float, default=125.0,
                     help="pipelined launch: the host waits this long between enqueueing the first registration of a run and the second "
                          "(on the other registration stream), so that the two streams are out of step from the start as they are in "
@@ -618,6 +660,10 @@ def main():
     ap.add_argument("--dry-launch", action="store_true",
                     help="print the launch `python bench.py --gpus N` would make of its N ranks (one JSON line) and exit")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 5 if args.full else 1
+    if args.dump_outputs and args.config == 3:
+        ap.error("--dump-outputs: config 3 is measured by tools/bench_config3.py, which writes no arrays")
     if args.raycast_wg is None:
         args.raycast_wg = 1 if (args.config == 2 and not args.no_pipeline) else 0
     S = args.scans or (1024 if args.config == 4 else N_SCANS)
@@ -637,7 +683,7 @@ def main():
         assert world == 1, "config 3 is a single-GPU sequence"
         from slam_amd import api
         api.set_device(0)
-        out = run_config3(args.clouds, not args.no_cpu_baseline)
+        out = run_config3(args.clouds, args.full and not args.no_cpu_baseline)
         out.update({"n_gpus": 1, "higher_is_better": True, "data": "synthetic", "vs_baseline": None,
                     "dtype": "f64 pose / f32 distance", "device": api.device_info()[0]})
         emit(out)
@@ -1029,157 +1075,170 @@ def main():
     merge_stats = comm.stats() if comm is not None else None
     if upd_per_step is None:      # no warm-up to count them in: the timed steps' own updates, before anything else runs
         upd_per_step = sum(g_.total_updates() for g_ in grids) // max(args.steps * n_regions, 1)
-    live_ms = [a_.elapsed_ms(b_) for a_, b_ in live] if (graph is None and args.steps > 0) else []
-    # How far ahead of the device the enqueue thread ran: registrations k and k + len(SA) share a stream, and that stream never runs
-    # dry as long as the enqueue of the later one has returned before the earlier one ends on the device.  Device end times come
-    # from the launches' own events, placed on the host's clock through ev_ref (read between two host readings just before t0).
-    slack = None
-    if live_ms and launch == "pipeline" and len(live) > len(SA):
-        t_ref = 0.5 * (t_ref0 + t_ref1)
-        end_host = [t_ref + ev_ref.elapsed_ms(b_) * 1e-3 for _, b_ in live]
-        d_ = len(SA)
-        sl_ = [(end_host[k - d_] - t_enq[k]) * 1e3 for k in range(d_, len(live)) if t_enq[k] is not None]
-        if sl_:
-            slack = {"min_ms": float(min(sl_)), "mean_ms": float(np.mean(sl_)), "registrations": len(sl_),
-                     "clock_uncertainty_ms": (t_ref1 - t_ref0) * 0.5e3,
-                     "what": "end of registration k - %d on the device minus the host time at which the enqueue of registration k (same "
-                             "stream) had returned: positive = the launch was in the queue before its predecessor ended, the stream did not "
-                             "run dry; over the first %d registrations of the timed region" % (d_, len(live))}
-    # the same K steps one after the other on one stream (outside the timed region, N=1): what the pipelining buys
-    seq_ms = None
-    if launch == "pipeline" and not multi:
-        run_steps(2, pipelined=False, handle=icp_one)
-        sync()
-        t1 = time.perf_counter()
-        run_steps(args.steps, pipelined=False, handle=icp_one)
-        sync()
-        seq_ms = (time.perf_counter() - t1) / max(args.steps, 1) * 1e3
-    # per-kernel times of the timed region's kernels, each alone on the chip: a few event-bracketed steps run one after
-    # the other on one stream, outside the timed region
-    ev = [[api.Event() for _ in range(5)] for _ in range(min(max(args.steps, 1), 10))]
-    run_steps(len(ev), ev, pipelined=False)
-    sync()
-    d_R, d_t, d_res = pR[(len(ev) - 1) % NB], pt[(len(ev) - 1) % NB], res[(len(ev) - 1) % NB]
-    grid = grids[(len(ev) - 1) % len(grids)]            # the grid of the last step: what the checks below read
-
     if multi:
         cnt = rk.all_reduce(torch.tensor([P, upd_per_step], dtype=torch.int64), what="sum of the ranks' points and updates")
         total_pts, total_upd = int(cnt[0].item()), int(cnt[1].item())
-    if merging:
-        # one more update, merged but not yet folded away (a step ends with finalize_reset, which zeroes the counts): the
-        # merged planes hold every rank's updates of a step, once
-        grid.raycast_scans_dev(d_pts, d_off, S, P, d_R, d_t, sb)
-        comm.merge_begin(grid, sb)
-        merge_rows_seen.append(comm.merge_finish(grid, sb))
-        sync()
-        hits, misses = grid.read_counts()
-        merged = int(hits.astype(np.int64).sum() + misses.astype(np.int64).sum())
-        assert merged == total_upd, "merged planes hold %d updates, the ranks made %d" % (merged, total_upd)
-        grid.finalize_reset(sb)
-        sync()
-    if not multi:
-        total_pts, total_upd = P, upd_per_step
-
-    # per-kernel device time from the HIP events recorded on the launch stream
-    seg = np.array([[e[i].elapsed_ms(e[i + 1]) for i in range(4)] for e in ev]) if len(ev) else np.zeros((1, 4))
-    ms_icp, ms_ray, ms_merge, ms_fin = seg.mean(axis=0)
-
-    # sanity on the result of the last step (not timed): all scans registered
-    res = d_res.download()
-    t_fin = d_t.download()
-    assert (res["iters"] == N_ITERS).all(), "not every scan ran %d iterations" % N_ITERS
-    pose_err = float(np.abs(t_fin - batch.true_poses[:, :2]).max())
-    assert pose_err < 0.05 or args.map_kind != "room", "registered poses are off by %.3f m" % pose_err
-
-    # the storage rows one step's finalize (and count reset) covers: the rows the step's raycast touched -- with N>1 the
-    # rows any rank touched (the merge's united range); read back from the device-tracked range, outside the timed region
-    if merging and merge_rows_seen:
-        rows_lo, rows_hi = merge_rows_seen[-1]
     else:
-        grid.raycast_scans_dev(d_pts, d_off, S, P, d_R, d_t, sa)
+        total_pts, total_upd = P, upd_per_step
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # what the last timed step computed: step k of a region wrote pose / result buffer k % NB and grid k % len(grids) (the
+        # captured graph: buffer 0 and the one grid)
+        k_ = 0 if graph is not None else args.steps - 1
+        g_ = grids[k_ % len(grids)]
+        r_ = res[k_ % NB].download()
+        dump_outputs(args.dump_outputs, {"poses_R": pR[k_ % NB].download(), "poses_t": pt[k_ % NB].download(),
+                                         "icp_iters": r_["iters"], "icp_n_corr": r_["n_corr"], "icp_delta": r_["delta"],
+                                         "grid_evidence": g_.read_num_pts().reshape(g_.size_y, g_.size_x),
+                                         "grid_occupancy": g_.read_occupancy().reshape(g_.size_y, g_.size_x)},
+                     planes=("grid_evidence", "grid_occupancy"))
+    if args.full:
+        live_ms = [a_.elapsed_ms(b_) for a_, b_ in live] if (graph is None and args.steps > 0) else []
+        # How far ahead of the device the enqueue thread ran: registrations k and k + len(SA) share a stream, and that stream never runs
+        # dry as long as the enqueue of the later one has returned before the earlier one ends on the device.  Device end times come
+        # from the launches' own events, placed on the host's clock through ev_ref (read between two host readings just before t0).
+        slack = None
+        if live_ms and launch == "pipeline" and len(live) > len(SA):
+            t_ref = 0.5 * (t_ref0 + t_ref1)
+            end_host = [t_ref + ev_ref.elapsed_ms(b_) * 1e-3 for _, b_ in live]
+            d_ = len(SA)
+            sl_ = [(end_host[k - d_] - t_enq[k]) * 1e3 for k in range(d_, len(live)) if t_enq[k] is not None]
+            if sl_:
+                slack = {"min_ms": float(min(sl_)), "mean_ms": float(np.mean(sl_)), "registrations": len(sl_),
+                         "clock_uncertainty_ms": (t_ref1 - t_ref0) * 0.5e3,
+                         "what": "end of registration k - %d on the device minus the host time at which the enqueue of registration k (same "
+                                 "stream) had returned: positive = the launch was in the queue before its predecessor ended, the stream did not "
+                                 "run dry; over the first %d registrations of the timed region" % (d_, len(live))}
+        # the same K steps one after the other on one stream (outside the timed region, N=1): what the pipelining buys
+        seq_ms = None
+        if launch == "pipeline" and not multi:
+            run_steps(2, pipelined=False, handle=icp_one)
+            sync()
+            t1 = time.perf_counter()
+            run_steps(args.steps, pipelined=False, handle=icp_one)
+            sync()
+            seq_ms = (time.perf_counter() - t1) / max(args.steps, 1) * 1e3
+        # per-kernel times of the timed region's kernels, each alone on the chip: a few event-bracketed steps run one after
+        # the other on one stream, outside the timed region
+        ev = [[api.Event() for _ in range(5)] for _ in range(min(max(args.steps, 1), 10))]
+        run_steps(len(ev), ev, pipelined=False)
         sync()
-        rows_lo, rows_hi = grid.dirty_rows()
-        grid.finalize_reset(sa)
-        sync()
-    rows_cov = max(rows_hi - rows_lo + 1, 0)
+        d_R, d_t, d_res = pR[(len(ev) - 1) % NB], pt[(len(ev) - 1) % NB], res[(len(ev) - 1) % NB]
+        grid = grids[(len(ev) - 1) % len(grids)]            # the grid of the last step: what the checks below read
+
+        if merging:
+            # one more update, merged but not yet folded away (a step ends with finalize_reset, which zeroes the counts): the
+            # merged planes hold every rank's updates of a step, once
+            grid.raycast_scans_dev(d_pts, d_off, S, P, d_R, d_t, sb)
+            comm.merge_begin(grid, sb)
+            merge_rows_seen.append(comm.merge_finish(grid, sb))
+            sync()
+            hits, misses = grid.read_counts()
+            merged = int(hits.astype(np.int64).sum() + misses.astype(np.int64).sum())
+            assert merged == total_upd, "merged planes hold %d updates, the ranks made %d" % (merged, total_upd)
+            grid.finalize_reset(sb)
+            sync()
+
+        # per-kernel device time from the HIP events recorded on the launch stream
+        seg = np.array([[e[i].elapsed_ms(e[i + 1]) for i in range(4)] for e in ev]) if len(ev) else np.zeros((1, 4))
+        ms_icp, ms_ray, ms_merge, ms_fin = seg.mean(axis=0)
+
+        # sanity on the result of the last step (not timed): all scans registered
+        res = d_res.download()
+        t_fin = d_t.download()
+        assert (res["iters"] == N_ITERS).all(), "not every scan ran %d iterations" % N_ITERS
+        pose_err = float(np.abs(t_fin - batch.true_poses[:, :2]).max())
+        assert pose_err < 0.05 or args.map_kind != "room", "registered poses are off by %.3f m" % pose_err
+
+        # the storage rows one step's finalize (and count reset) covers: the rows the step's raycast touched -- with N>1 the
+        # rows any rank touched (the merge's united range); read back from the device-tracked range, outside the timed region
+        if merging and merge_rows_seen:
+            rows_lo, rows_hi = merge_rows_seen[-1]
+        else:
+            grid.raycast_scans_dev(d_pts, d_off, S, P, d_R, d_t, sa)
+            sync()
+            rows_lo, rows_hi = grid.dirty_rows()
+            grid.finalize_reset(sa)
+            sync()
+        rows_cov = max(rows_hi - rows_lo + 1, 0)
 
     if rank == 0:
         info = icp.index_info()
         M = len(m_ga) + len(m_nga)
-        # ALGORITHMIC bytes: ICP per scan 16*T + 8*M + 96, all iterations fused; the halo lists the
-        # library builds for itself are NOT algorithmic bytes (reported beside, as index_bytes_read_per_launch)
-        icp_bytes = 16 * P + S * (8 * M + 96)
-        ray_bytes = 8 * upd_per_step + 16 * P           # 8 B RMW per cell update + 16 B per beam
-        fin_bytes = rows_cov * GRID * 17                # per cell of the rows covered: 2x4 B counts in, 8 B evidence + 1 B occupancy out
-        fused = bool(info.get("two_forms")) and args.lanes == 0
-        paired = fused and (icp is not icp_one or S >= 2 * n_cu)
-        icp_name = "icp_fit_pair_kernel" if paired else ("icp_fit_fused_kernel" if fused else "icp_fit_kernel")
         step_ms = elapsed / max(args.steps, 1) * 1e3
-        # the registration launch as the timed region saw it (HIP events on its own stream around every launch; with two
-        # registration streams two launches share the chip); ms_icp is the same kernel alone on the chip
-        ms_icp_live = float(np.mean(live_ms)) if live_ms else float(ms_icp)
-        ATOMIC_CEILING_GBS = 1300.0   # MI355X_MICROARCH.md, global atomics: ~1.3 TB/s of added bytes
-        kernels = {
-            icp_name: {"ms": ms_icp_live, "ms_alone_on_the_chip": float(ms_icp), "alg_bytes": icp_bytes,
-                       "launches_in_flight": 2 if launch == "pipeline" else 1,
-                       "index_bytes_read_per_launch": (S // 2 if paired else S) * (int(info.get("lds_bytes", 0)) + (int(info.get("list_bytes", 0)) if fused else 0))},
-            "raycast_tiled_kernel (+ beams, work list)": {
-                "ms": float(ms_ray), "alg_bytes": ray_bytes,
-                "global_atomic_ceiling_GBps": ATOMIC_CEILING_GBS,
-                "note": "alg_bytes = 8 B RMW per cell update + 16 B per beam; against the ceiling of one GLOBAL atomic per "
-                        "update (SURVEY 8(d)): the updates are binned in LDS tiles and reach HBM as one atomic per touched "
-                        "cell and segment, which is how the rate can exceed that ceiling"},
-            "finalize_reset_rows_kernel": {"ms": float(ms_fin), "alg_bytes": fin_bytes, "rows_covered": rows_cov, "rows_of_the_grid": GRID,
-                                     "note": "alg_bytes = 17 B x the cells of the storage rows the kernel covers (the touched rows, read "
-                                             "back from the device-tracked range): counts in, evidence + occupancy out; the zeroes it "
-                                             "writes back into the counts it has folded are not counted"},
-        }
-        prof_file, prof = pmc_profile(p2l)
-        for k in kernels.values():
-            k["GBps"] = k["alg_bytes"] / (k["ms"] * 1e-3) / 1e9 if k["ms"] > 0 else 0.0
-            k["frac_of_hbm_peak"] = k["GBps"] / HBM_PEAK_GBS
-        # the raycast's 8 B per cell update never reach HBM (the updates are binned in LDS): its algorithmic rate belongs beside
-        # the global-atomic ceiling, and its HBM fraction comes from the MEASURED traffic of the committed counter passes
-        kr = kernels["raycast_tiled_kernel (+ beams, work list)"]
-        kr["alg_GBps_equivalent"] = kr.pop("GBps")
-        kr["vs_global_atomic_ceiling"] = kr["alg_GBps_equivalent"] / ATOMIC_CEILING_GBS
-        ray_traffic = sum(prof.get(n, {}).get("hbm_bytes_per_launch") or 0.0 for n in ("raycast_tiled_kernel", "beams_from_scans_kernel", "tile_items_wg_kernel"))
-        kr["hbm_bytes_per_launch_measured"] = ray_traffic or None
-        kr["GBps"] = (ray_traffic / (kr["ms"] * 1e-3) / 1e9) if (ray_traffic and kr["ms"] > 0 and (S, GRID) == (256, 2000)) else None
-        kr["frac_of_hbm_peak"] = (kr["GBps"] / HBM_PEAK_GBS) if kr["GBps"] else None
-        dom = max(kernels, key=lambda n: kernels[n]["ms"])
-        pk = prof.get(dom.split(" ")[0], {})
-        busy, lanes = pk.get("valu_busy_frac"), pk.get("valu_active_lane_share")
-        held = min(n_cu, (S + 1) // 2 if paired else S) if dom == icp_name else n_cu
-        roof = {"bound": "hbm", "kernel": dom, "achieved": kernels[dom]["GBps"], "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": kernels[dom]["GBps"] / HBM_PEAK_GBS,
-                "traffic": pk.get("hbm_bytes_per_launch"),
-                "traffic_source": ("%s (rocprofv3 --pmc passes of this command, committed; not measured in this run; the "
-                                   "profiler runs one dispatch at a time, so these are the kernel alone on the chip)" % prof_file)
-                if prof_file else None,
-                "alg_bytes_per_launch": kernels[dom]["alg_bytes"], "avg_launch_ms": kernels[dom]["ms"],
-                "alg_bytes_formula": "16*P + S*(8*M + 96) (SURVEY 8(d)); P=%d points, S=%d scans, M=%d model points" % (P, S, M),
-                "per_step": {"GBps": kernels[dom]["alg_bytes"] / (step_ms * 1e-3) / 1e9,
-                             "frac": kernels[dom]["alg_bytes"] / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                             "what": "alg_bytes_per_launch / ms_per_step: one launch of this kernel per step, whatever overlaps it"},
-                # the bound this kernel actually runs against: the share of the chip's VALU lane-slots that do work
-                "valu": {"bound": "valu", "frac": (busy * lanes) if (busy is not None and lanes is not None) else None,
-                         "busy_frac": busy, "active_lane_share": lanes,
-                         "cus_held_by_one_launch": held,
-                         "frac_on_held_cus": (busy * lanes * n_cu / held) if (busy is not None and lanes is not None) else None,
-                         "source": prof_file,
-                         "profile_csrc_sha256": prof.get("_meta", {}).get("csrc_sha256"),
-                         "run_csrc_sha256": csrc_sha(),
-                         "stale": (prof.get("_meta", {}).get("csrc_sha256") != csrc_sha()) if prof_file else None,
-                         "stale_means": "the committed counter summary was taken from kernel sources other than the ones this run was built "
-                                        "from (sha256 over slam_amd/csrc): the fractions describe that build",
-                         "meaning": "busy_frac = SIMD cycles (all 1024 SIMDs) that issued a VALU instruction; active_lane_share = "
-                                    "SQ_THREAD_CYCLES_VALU / (64 * SQ_ACTIVE_INST_VALU); frac = their product = the share of the "
-                                    "chip's VALU lane-slots that did work during a launch"},
-                "note": "frac = alg_bytes_per_launch / avg_launch_ms / peak, avg_launch_ms = HIP events around every launch of the "
-                        "timed region on its own stream (profiles/: the kernel's AverageNs in the kernel-trace summary of the same "
-                        "command).  The kernel is VALU-issue bound (exact 1-NN search in LDS, DESIGN.md 4.1), not HBM-bound: "
-                        "`valu` is the bound it runs against; the HBM fraction is reported because the contract asks for it."}
+        if args.full:
+            # ALGORITHMIC bytes: ICP per scan 16*T + 8*M + 96, all iterations fused; the halo lists the
+            # library builds for itself are NOT algorithmic bytes (reported beside, as index_bytes_read_per_launch)
+            icp_bytes = 16 * P + S * (8 * M + 96)
+            ray_bytes = 8 * upd_per_step + 16 * P           # 8 B RMW per cell update + 16 B per beam
+            fin_bytes = rows_cov * GRID * 17                # per cell of the rows covered: 2x4 B counts in, 8 B evidence + 1 B occupancy out
+            fused = bool(info.get("two_forms")) and args.lanes == 0
+            paired = fused and (icp is not icp_one or S >= 2 * n_cu)
+            icp_name = "icp_fit_pair_kernel" if paired else ("icp_fit_fused_kernel" if fused else "icp_fit_kernel")
+            # the registration launch as the timed region saw it (HIP events on its own stream around every launch; with two
+            # registration streams two launches share the chip); ms_icp is the same kernel alone on the chip
+            ms_icp_live = float(np.mean(live_ms)) if live_ms else float(ms_icp)
+            ATOMIC_CEILING_GBS = 1300.0   # MI355X_MICROARCH.md, global atomics: ~1.3 TB/s of added bytes
+            kernels = {
+                icp_name: {"ms": ms_icp_live, "ms_alone_on_the_chip": float(ms_icp), "alg_bytes": icp_bytes,
+                           "launches_in_flight": 2 if launch == "pipeline" else 1,
+                           "index_bytes_read_per_launch": (S // 2 if paired else S) * (int(info.get("lds_bytes", 0)) + (int(info.get("list_bytes", 0)) if fused else 0))},
+                "raycast_tiled_kernel (+ beams, work list)": {
+                    "ms": float(ms_ray), "alg_bytes": ray_bytes,
+                    "global_atomic_ceiling_GBps": ATOMIC_CEILING_GBS,
+                    "note": "alg_bytes = 8 B RMW per cell update + 16 B per beam; against the ceiling of one GLOBAL atomic per "
+                            "update (SURVEY 8(d)): the updates are binned in LDS tiles and reach HBM as one atomic per touched "
+                            "cell and segment, which is how the rate can exceed that ceiling"},
+                "finalize_reset_rows_kernel": {"ms": float(ms_fin), "alg_bytes": fin_bytes, "rows_covered": rows_cov, "rows_of_the_grid": GRID,
+                                         "note": "alg_bytes = 17 B x the cells of the storage rows the kernel covers (the touched rows, read "
+                                                 "back from the device-tracked range): counts in, evidence + occupancy out; the zeroes it "
+                                                 "writes back into the counts it has folded are not counted"},
+            }
+            prof_file, prof = pmc_profile(p2l)
+            for k in kernels.values():
+                k["GBps"] = k["alg_bytes"] / (k["ms"] * 1e-3) / 1e9 if k["ms"] > 0 else 0.0
+                k["frac_of_hbm_peak"] = k["GBps"] / HBM_PEAK_GBS
+            # the raycast's 8 B per cell update never reach HBM (the updates are binned in LDS): its algorithmic rate belongs beside
+            # the global-atomic ceiling, and its HBM fraction comes from the MEASURED traffic of the committed counter passes
+            kr = kernels["raycast_tiled_kernel (+ beams, work list)"]
+            kr["alg_GBps_equivalent"] = kr.pop("GBps")
+            kr["vs_global_atomic_ceiling"] = kr["alg_GBps_equivalent"] / ATOMIC_CEILING_GBS
+            ray_traffic = sum(prof.get(n, {}).get("hbm_bytes_per_launch") or 0.0 for n in ("raycast_tiled_kernel", "beams_from_scans_kernel", "tile_items_wg_kernel"))
+            kr["hbm_bytes_per_launch_measured"] = ray_traffic or None
+            kr["GBps"] = (ray_traffic / (kr["ms"] * 1e-3) / 1e9) if (ray_traffic and kr["ms"] > 0 and (S, GRID) == (256, 2000)) else None
+            kr["frac_of_hbm_peak"] = (kr["GBps"] / HBM_PEAK_GBS) if kr["GBps"] else None
+            dom = max(kernels, key=lambda n: kernels[n]["ms"])
+            pk = prof.get(dom.split(" ")[0], {})
+            busy, lanes = pk.get("valu_busy_frac"), pk.get("valu_active_lane_share")
+            held = min(n_cu, (S + 1) // 2 if paired else S) if dom == icp_name else n_cu
+            roof = {"bound": "hbm", "kernel": dom, "achieved": kernels[dom]["GBps"], "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": kernels[dom]["GBps"] / HBM_PEAK_GBS,
+                    "traffic": pk.get("hbm_bytes_per_launch"),
+                    "traffic_source": ("%s (rocprofv3 --pmc passes of this command, committed; not measured in this run; the "
+                                       "profiler runs one dispatch at a time, so these are the kernel alone on the chip)" % prof_file)
+                    if prof_file else None,
+                    "alg_bytes_per_launch": kernels[dom]["alg_bytes"], "avg_launch_ms": kernels[dom]["ms"],
+                    "alg_bytes_formula": "16*P + S*(8*M + 96) (SURVEY 8(d)); P=%d points, S=%d scans, M=%d model points" % (P, S, M),
+                    "per_step": {"GBps": kernels[dom]["alg_bytes"] / (step_ms * 1e-3) / 1e9,
+                                 "frac": kernels[dom]["alg_bytes"] / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                 "what": "alg_bytes_per_launch / ms_per_step: one launch of this kernel per step, whatever overlaps it"},
+                    # the bound this kernel actually runs against: the share of the chip's VALU lane-slots that do work
+                    "valu": {"bound": "valu", "frac": (busy * lanes) if (busy is not None and lanes is not None) else None,
+                             "busy_frac": busy, "active_lane_share": lanes,
+                             "cus_held_by_one_launch": held,
+                             "frac_on_held_cus": (busy * lanes * n_cu / held) if (busy is not None and lanes is not None) else None,
+                             "source": prof_file,
+                             "profile_csrc_sha256": prof.get("_meta", {}).get("csrc_sha256"),
+                             "run_csrc_sha256": csrc_sha(),
+                             "stale": (prof.get("_meta", {}).get("csrc_sha256") != csrc_sha()) if prof_file else None,
+                             "stale_means": "the committed counter summary was taken from kernel sources other than the ones this run was built "
+                                            "from (sha256 over slam_amd/csrc): the fractions describe that build",
+                             "meaning": "busy_frac = SIMD cycles (all 1024 SIMDs) that issued a VALU instruction; active_lane_share = "
+                                        "SQ_THREAD_CYCLES_VALU / (64 * SQ_ACTIVE_INST_VALU); frac = their product = the share of the "
+                                        "chip's VALU lane-slots that did work during a launch"},
+                    "note": "frac = alg_bytes_per_launch / avg_launch_ms / peak, avg_launch_ms = HIP events around every launch of the "
+                            "timed region on its own stream (profiles/: the kernel's AverageNs in the kernel-trace summary of the same "
+                            "command).  The kernel is VALU-issue bound (exact 1-NN search in LDS, DESIGN.md 4.1), not HBM-bound: "
+                            "`valu` is the bound it runs against; the HBM fraction is reported because the contract asks for it."}
         out = {
             "metric": "registered_scan_points_per_s", "value": total_pts * args.steps / elapsed,
             "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1214,19 +1273,22 @@ def main():
             "grid_cell_updates_per_s": total_upd * args.steps / elapsed,
             "cell_updates_per_step": total_upd,
             "point_iterations_per_s": total_pts * N_ITERS * args.steps / elapsed,
-            "one_stream": None if seq_ms is None else
-            {"ms_per_step": seq_ms, "value": total_pts / (seq_ms * 1e-3),
-             "what": "the same steps call by call on ONE stream, one scan per workgroup, nothing overlapped (measured after "
-                     "the timed region)"},
-            "kernel_ms": {"icp": float(ms_icp), "raycast": float(ms_ray), "merge": float(ms_merge),
-                          "finalize": float(ms_fin)},
-            "kernels": kernels,
-            "host_enqueue_slack_ms": slack,
-            "roofline": roof,
-            "max_pose_error_m": pose_err,
             "device": api.device_info()[0],
         }
-        if p2l and world == 1:
+        if args.full:
+            out.update({
+                "one_stream": None if seq_ms is None else
+                {"ms_per_step": seq_ms, "value": total_pts / (seq_ms * 1e-3),
+                 "what": "the same steps call by call on ONE stream, one scan per workgroup, nothing overlapped (measured after "
+                         "the timed region)"},
+                "kernel_ms": {"icp": float(ms_icp), "raycast": float(ms_ray), "merge": float(ms_merge),
+                              "finalize": float(ms_fin)},
+                "kernels": kernels,
+                "host_enqueue_slack_ms": slack,
+                "roofline": roof,
+                "max_pose_error_m": pose_err,
+            })
+        if args.full and p2l and world == 1:
             # the point-to-line handle's own costs: its model build (index + the normals of icpPointToPlane.cpp:279-305, one
             # 10-neighbour scatter matrix per model point, + a normal per halo-list entry) and one scan through the host API
             out["model_build_ms"] = model_build_times(api, synth, m_ga, m_nga, **mode_kw)
@@ -1262,7 +1324,7 @@ def main():
             if merging:
                 out["merge"]["calibration"] = calibration
             out["no_merge"] = bool(args.no_merge)
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # the model build reported separately; metric (1) with the transfers in; the reference's own
             # usage (one scan per match); config 3's match
             out["model_build_ms"] = model_build_times(api, synth, m_ga, m_nga)
@@ -1294,21 +1356,21 @@ def main():
             # with its sliding-window target, PCIe inclusive)
             # the solver north_star names (point-to-line, 3x3 normal equations) on the same workload, same pipelined step, the CPU
             # oracle's point-to-line step timed beside it
-            out["p2l"] = side_run(["--mode", "p2l", "--steps", "30", "--warmup", "5", "--no-extras"],
+            out["p2l"] = side_run(["--full", "--mode", "p2l", "--steps", "30", "--warmup", "5", "--no-extras"],
                                   ("value", "ms_per_step", "icp_step", "grid_cell_updates_per_s", "kernel_ms", "roofline", "one_stream", "model_build_ms", "single_scan",
                                    "max_pose_error_m", "cpu_baseline"))
-            out["config4_share"] = side_run(["--config", "4", "--steps", "12", "--warmup", "3", "--no-extras", "--no-cpu-baseline"],
+            out["config4_share"] = side_run(["--full", "--config", "4", "--steps", "12", "--warmup", "3", "--no-extras", "--no-cpu-baseline"],
                                             ("value", "ms_per_step", "grid_cell_updates_per_s", "cell_updates_per_step", "kernel_ms", "max_pose_error_m"))
             # (the whole 10 240-scan stream of BASELINE config 5: a leg of 4096 scans is 16 chunks, a quarter of them filling and
             # draining the pipeline -- 0.43 ms per chunk where the stream runs at 0.41)
-            out["config5"] = side_run(["--config", "5", "--stream-scans", "10240"],
+            out["config5"] = side_run(["--full", "--config", "5", "--stream-scans", "10240"],
                                       ("value", "ms_per_step", "steps", "grid_cell_updates_per_s", "max_pose_error_m"))
             # the N > 1 path with two ranks on THIS GPU: bench.py launching its own ranks, the library's merge entry points over
             # its host-staged communicator (gloo carries the host buffers; RCCL does not put two ranks on one device).  Not a
             # scaling number -- two ranks share one chip and stage through the host -- but the same code path as --gpus N.
-            out["two_ranks_on_one_gpu"] = side_run(["--gpus", "2", "--backend", "gloo", "--one-device", "--steps", "6", "--warmup", "2",
+            out["two_ranks_on_one_gpu"] = side_run(["--full", "--gpus", "2", "--backend", "gloo", "--one-device", "--steps", "6", "--warmup", "2",
                                                     "--no-cpu-baseline"], ("n_gpus", "value", "ms_per_step", "cell_updates_per_step"))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(m_ga, m_nga, batch, GRID, RES, p2l)
         emit(out)
     if multi:
@@ -1374,6 +1436,13 @@ def run_config5(args, api, synth, m_ga, m_nga, rank, world, comm, rk, sync, barr
     gc.enable()
     upd = mp.grid.total_updates() - upd_warm
     st = mp.stats()
+    if args.dump_outputs and rank == 0:
+        # the last chunk's registered poses (the waits return in push order) and the mapper's grid after its last merge + finalize
+        g_ = mp.grid
+        dump_outputs(args.dump_outputs, {"poses_R": R, "poses_t": t,
+                                         "grid_evidence": g_.read_num_pts().reshape(g_.size_y, g_.size_x),
+                                         "grid_occupancy": g_.read_occupancy().reshape(g_.size_y, g_.size_x)},
+                     planes=("grid_evidence", "grid_occupancy"))
     if rk is not None:
         elapsed = rk.max_over_ranks(elapsed)
     if rank == 0:

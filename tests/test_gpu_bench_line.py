@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_line_contract_and_arithmetic():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--no-extras",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--steps", "6", "--warmup", "2", "--no-extras",
                         "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -55,7 +55,7 @@ def _bench(*argv):
 def test_bench_force_dist_runs_the_n_gt_1_pipeline_over_a_real_rccl_communicator():
     """The N > 1 code path -- RCCL communicator made from an ncclUniqueId, slam_grid_merge_begin / _finish in every pipelined
     step -- with the one rank a one-GPU box has, and the fields a scaling curve is read with."""
-    d = _bench("--force-dist", "--steps", "4", "--warmup", "2", "--no-extras", "--no-cpu-baseline")
+    d = _bench("--full", "--force-dist", "--steps", "4", "--warmup", "2", "--no-extras", "--no-cpu-baseline")
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and d["no_merge"] is False
     m = d["merge"]
     assert m["transport"] == "rccl" and m["rccl_version"] > 20000 and m["ranks"] == 1
@@ -74,7 +74,7 @@ def test_bench_force_dist_runs_the_n_gt_1_pipeline_over_a_real_rccl_communicator
     sl = d["host_enqueue_slack_ms"]
     assert sl is not None and sl["registrations"] >= 1 and sl["min_ms"] <= sl["mean_ms"]
     # ... and the same steps with the merge on the enqueue thread (rounds 2-4), still there behind a switch
-    d0 = _bench("--force-dist", "--merge-thread", "0", "--steps", "4", "--warmup", "2", "--no-extras", "--no-cpu-baseline")
+    d0 = _bench("--full", "--force-dist", "--merge-thread", "0", "--steps", "4", "--warmup", "2", "--no-extras", "--no-cpu-baseline")
     assert d0["config"]["merge_thread"] is False and d0["merge"]["merges_by_helper_thread"] == 0
     assert d0["merge"]["merges_in_timed_region"] == 4 * 5 and d0["config"]["merge_rows"] == d["config"]["merge_rows"]
 
@@ -83,7 +83,7 @@ def test_bench_force_dist_runs_the_n_gt_1_pipeline_over_a_real_rccl_communicator
 def test_bench_calibrates_the_n_gt_1_launch_setting():
     """With more than one rank the bench first times reg-cu-cap 0/1/2/4 x (grid-lag 3/4/6 | early) and keeps the fastest (no
     multi-GPU lease has said which one RCCL's kernels need); --calibrate runs that with the one rank of this box."""
-    d = _bench("--force-dist", "--calibrate", "--steps", "4", "--warmup", "2", "--no-extras", "--no-cpu-baseline")
+    d = _bench("--full", "--force-dist", "--calibrate", "--steps", "4", "--warmup", "2", "--no-extras", "--no-cpu-baseline")
     c = d["merge"]["calibration"]
     assert [(t["reg_cu_cap_per_xcd"], t["grid_lag"], t["merge_order"]) for t in c["tried"]] == \
         [(cap, lag, "late") for cap in (0, 1, 2, 4) for lag in (3, 4, 6)] + [(cap, 0, "early") for cap in (0, 1, 2, 4)]
@@ -95,7 +95,7 @@ def test_bench_calibrates_the_n_gt_1_launch_setting():
     assert all(0.2 < t["ms_per_step"] < 5.0 for t in c["tried"])
     assert d["merge"]["merges_in_timed_region"] == 4 * 5 and d["max_pose_error_m"] < 0.05 and d["merge"]["calibration"]["caps_dropped_unsupported"] == []
     # a setting given on the command line is not calibrated over
-    d = _bench("--force-dist", "--calibrate", "--merge-order", "late", "--grid-lag", "3", "--steps", "4", "--warmup", "2", "--no-extras", "--no-cpu-baseline")
+    d = _bench("--full", "--force-dist", "--calibrate", "--merge-order", "late", "--grid-lag", "3", "--steps", "4", "--warmup", "2", "--no-extras", "--no-cpu-baseline")
     assert [(t["reg_cu_cap_per_xcd"], t["grid_lag"], t["merge_order"]) for t in d["merge"]["calibration"]["tried"]] == \
         [(0, 3, "late"), (1, 3, "late"), (2, 3, "late"), (4, 3, "late")]
 
@@ -104,7 +104,40 @@ def test_bench_calibrates_the_n_gt_1_launch_setting():
 def test_bench_no_merge_and_reserved_cus():
     """--no-merge: the same ranks with the exchange step left out (what the merge costs is the difference to the default
     run); --reg-cu-cap: registration streams that leave CUs of every XCD to the other streams' kernels."""
-    d = _bench("--force-dist", "--no-merge", "--reg-cu-cap", "1", "--steps", "4", "--warmup", "2", "--no-extras", "--no-cpu-baseline")
+    d = _bench("--full", "--force-dist", "--no-merge", "--reg-cu-cap", "1", "--steps", "4", "--warmup", "2", "--no-extras", "--no-cpu-baseline")
     assert d["no_merge"] is True and d["merge"] is None and d["rccl_ranks"] is None
     assert d["config"]["reg_cu_cap_per_xcd"] == 1 and "NO merge" in d["config"]["workload"]
     assert d["max_pose_error_m"] < 0.05 and d["value"] > 1e8
+
+
+DUMPED = ["grid_evidence", "grid_occupancy", "icp_delta", "icp_iters", "icp_n_corr", "poses_R", "poses_t"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run times exactly `steps` steps (one region) and prints the headline without what --full adds; --dump-outputs
+    writes the last timed step's arrays, float32 / float64 within 64 MB, the same from run to run of the same arguments."""
+    import numpy as np
+    from slam_amd import synth
+    arrays = []
+    for k in range(2):
+        d = _bench("--gpus", "1", "--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path / str(k)))
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["metric"] == "registered_scan_points_per_s" and d["unit"] == "points/s" and d["higher_is_better"] is True
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["timed_regions"]["n"] == 1 and d["ms_per_step_runs"] == [d["ms_per_step"]]
+        assert abs(d["value"] - 276242 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        for key in ("roofline", "kernels", "kernel_ms", "one_stream", "cpu_baseline", "config3", "p2l", "value_pcie_inclusive"):
+            assert key not in d, key
+        files = sorted(os.listdir(tmp_path / str(k)))
+        assert files == [n + ".npy" for n in DUMPED]
+        arrays.append({n: np.load(str(tmp_path / str(k) / (n + ".npy"))) for n in DUMPED})
+        assert sum(a.nbytes for a in arrays[-1].values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays[-1].values())
+    for n in DUMPED:
+        assert np.array_equal(arrays[0][n], arrays[1][n]), n
+    a = arrays[0]
+    batch = synth.make_batch(256, n_loop=256)
+    assert a["poses_t"].shape == (256, 2) and np.abs(a["poses_t"] - batch.true_poses[:, :2]).max() < 0.05
+    assert (a["icp_iters"] == 30).all() and (a["icp_n_corr"] > 0).all()
+    assert a["grid_evidence"].shape == (2000, 2000) and np.count_nonzero(a["grid_evidence"]) > 0

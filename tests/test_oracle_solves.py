@@ -74,28 +74,50 @@ def test_normal_matches_reference_svd_column(G):
         assert abs(n @ n - 1.0) < 1e-14
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built")
-def test_live_reference_normals_of_a_model():
-    # the oracle model's own neighbour sets (K = 10) through the compiled reference
+def live_normal_cases():
+    """The oracle model's own neighbour sets (K = 10) of every seventh point of a 2 000-point map: (points, [(i, neighbours)])."""
     from slam_amd import synth
     m_ga, m_nga = synth.make_map(n_points=2000)
-    model = O.IcpModel(m_ga, m_nga, normals_k=10)
-    nrm = model.normals()
     pts = np.concatenate([m_ga, m_nga]).astype(np.float32)
     d2 = ((pts[:, None, :].astype(np.float64) - pts[None, :, :].astype(np.float64)) ** 2).sum(-1)
-    for i in range(0, len(pts), 7):
-        nb = np.argsort(d2[i], kind="stable")[:10]
-        n_ref = O.ref_normal2(pts[nb])
-        sgn = 1.0 if nrm[i] @ n_ref >= 0 else -1.0
-        assert np.abs(nrm[i] - sgn * n_ref).max() < 1e-9, i
+    return (m_ga, m_nga), pts, [(i, np.argsort(d2[i], kind="stable")[:10]) for i in range(0, len(pts), 7)]
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built")
-def test_live_reference_matrix_agrees():
+def live_matrix_cases():
+    """2 000 cross-covariances of noisy point pairs, then the all-zero one."""
     rs = np.random.RandomState(5)
+    Hs = []
     for _ in range(2000):
         q = rs.randn(rs.randint(3, 30), 2) * rs.uniform(0.01, 20, 2)
         qm = q + rs.randn(*q.shape) * 1e-2
-        H = (q - q.mean(0)).T @ (qm - qm.mean(0))
-        assert np.abs(O.p2p_rotation(H) - O.ref_p2p_rotation(H)).max() < 1e-12
-    assert np.array_equal(O.p2p_rotation(np.zeros(4)), O.ref_p2p_rotation(np.zeros(4)))
+        Hs.append((q - q.mean(0)).T @ (qm - qm.mean(0)))
+    return Hs + [np.zeros((2, 2))]
+
+
+@pytest.fixture(scope="module")
+def L(golden_dir):
+    """The compiled reference's answers to the two cases above, recorded by tests/golden/make_live_ref_golden.py: the
+    comparison runs against them everywhere, and against the live library as well where oracle/_ref is built."""
+    return np.load(os.path.join(golden_dir, "live_ref_golden.npz"))
+
+
+def test_live_reference_normals_of_a_model(L):
+    # the oracle model's own neighbour sets (K = 10) through the compiled reference
+    (m_ga, m_nga), pts, cases = live_normal_cases()
+    assert np.array_equal(L["nm_pts"], pts) and len(L["nm_n"]) == len(cases)
+    model = O.IcpModel(m_ga, m_nga, normals_k=10)
+    nrm = model.normals()
+    for (i, nb), n_rec in zip(cases, L["nm_n"]):
+        for n_ref in [n_rec] + ([O.ref_normal2(pts[nb])] if O.ref_available() else []):
+            sgn = 1.0 if nrm[i] @ n_ref >= 0 else -1.0
+            assert np.abs(nrm[i] - sgn * n_ref).max() < 1e-9, i
+
+
+def test_live_reference_matrix_agrees(L):
+    Hs = live_matrix_cases()
+    assert len(L["p2p_R"]) == len(Hs)
+    for H, R_rec in zip(Hs[:-1], L["p2p_R"]):
+        for R_ref in [R_rec] + ([O.ref_p2p_rotation(H)] if O.ref_available() else []):
+            assert np.abs(O.p2p_rotation(H) - R_ref).max() < 1e-12
+    for R_ref in [L["p2p_R"][-1]] + ([O.ref_p2p_rotation(np.zeros(4))] if O.ref_available() else []):
+        assert np.array_equal(O.p2p_rotation(np.zeros(4)), R_ref)

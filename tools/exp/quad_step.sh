@@ -3,7 +3,7 @@
 OUT=gpurun_out/quad_step.txt
 : > $OUT
 run() { # label, env, args
-  v=$(env $2 timeout -k 10 150 python3 bench.py --steps 60 --warmup 8 --no-extras --no-cpu-baseline $3 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.4f ms/step  launch %.4f' % (d['ms_per_step'], d['roofline']['avg_launch_ms']))")
+  v=$(env $2 timeout -k 10 150 python3 bench.py --full --steps 60 --warmup 8 --no-extras --no-cpu-baseline $3 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.4f ms/step  launch %.4f' % (d['ms_per_step'], d['roofline']['avg_launch_ms']))")
   echo "$1: $v" >> $OUT
 }
 for rep in 1 2; do

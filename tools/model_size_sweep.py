@@ -25,7 +25,7 @@ def main():
     steps = sys.argv[1] if len(sys.argv) > 1 else "40"
     rows = []
     for kind, m in (("room", 10000), ("room", 20000), ("room", 39998), ("uniform", 10000), ("uniform", 39998)):
-        common = ["--map-points", str(m), "--map-kind", kind, "--steps", steps, "--warmup", "5", "--no-extras", "--no-cpu-baseline"]
+        common = ["--map-points", str(m), "--map-kind", kind, "--steps", steps, "--warmup", "5", "--no-extras", "--no-cpu-baseline", "--full"]
         d = bench(*common)                                  # pipelined: pairs, two registration launches in flight
         f = bench(*common, "--no-pipeline")                 # one stream: the fused form, one scan per workgroup, alone on the chip
         row = {"map_kind": kind, "map_points": m}

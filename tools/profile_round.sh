@@ -12,7 +12,7 @@ OUT=gpurun_out/profile_$TAG
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 if [[ $PART == *a* ]]; then rm -rf "$OUT"; fi
 mkdir -p "$OUT"
-BENCH="python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras"
+BENCH="python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras"
 if [[ $PART == *a* ]]; then
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH > $OUT/stats.json 2> $OUT/stats.err || echo "stats pass failed"
 i=0
@@ -56,18 +56,18 @@ rm -rf /tmp/c3cpp && SLAM_C3_KEEP_DIR=/tmp/c3cpp python3 tools/bench_config3.py 
 timeout -k 10 300 python3 tools/spread_time.py 20 > $OUT/spread_time.json 2> $OUT/spread.err || echo "spread_time failed"
 SLAM_AMD_MEASURE=1 SLAM_SPREAD_STAMPS=1 timeout -k 10 300 python3 tools/spread_time.py 5 > $OUT/spread_stamps.json 2>> $OUT/spread.err || echo "spread stamps failed (measurement build missing?)"
 [ -x tools/exp/latency_chase ] && ./tools/exp/latency_chase > $OUT/latency_chase.txt 2>&1
-timeout -k 10 600 python3 bench.py --config 3 > $OUT/config3.json 2>> $OUT/config3.err || echo "config 3 failed"
+timeout -k 10 600 python3 bench.py --full --config 3 > $OUT/config3.json 2>> $OUT/config3.err || echo "config 3 failed"
 # the N > 1 path with two ranks on this one GPU (the library's merge over its host-staged communicator, gloo carrying the buffers)
-timeout -k 10 600 python3 bench.py --gpus 2 --backend gloo --one-device --steps 10 --warmup 3 --no-cpu-baseline > $OUT/two_ranks_one_gpu.json 2> $OUT/two_ranks.err || echo "two-rank rehearsal failed"
+timeout -k 10 600 python3 bench.py --full --gpus 2 --backend gloo --one-device --steps 10 --warmup 3 --no-cpu-baseline > $OUT/two_ranks_one_gpu.json 2> $OUT/two_ranks.err || echo "two-rank rehearsal failed"
 # ... and with ONE rank over a real RCCL communicator (the N > 1 pipeline: merge_begin / merge_finish in every step), with and without the merge
-timeout -k 10 600 python3 bench.py --force-dist --steps 50 --warmup 5 --no-extras --no-cpu-baseline > $OUT/force_dist.json 2> $OUT/force_dist.err || echo "force-dist failed"
-timeout -k 10 600 python3 bench.py --force-dist --no-merge --steps 50 --warmup 5 --no-extras --no-cpu-baseline > $OUT/force_dist_no_merge.json 2>> $OUT/force_dist.err || echo "force-dist --no-merge failed"
-timeout -k 10 600 python3 bench.py --force-dist --reg-cu-cap 1 --steps 50 --warmup 5 --no-extras --no-cpu-baseline > $OUT/force_dist_cu_cap1.json 2>> $OUT/force_dist.err || echo "force-dist --reg-cu-cap failed"
-timeout -k 10 600 python3 bench.py --mode p2l --steps 50 --warmup 5 --no-extras > $OUT/p2l.json 2> $OUT/p2l.err || echo "p2l bench failed"
+timeout -k 10 600 python3 bench.py --full --force-dist --steps 50 --warmup 5 --no-extras --no-cpu-baseline > $OUT/force_dist.json 2> $OUT/force_dist.err || echo "force-dist failed"
+timeout -k 10 600 python3 bench.py --full --force-dist --no-merge --steps 50 --warmup 5 --no-extras --no-cpu-baseline > $OUT/force_dist_no_merge.json 2>> $OUT/force_dist.err || echo "force-dist --no-merge failed"
+timeout -k 10 600 python3 bench.py --full --force-dist --reg-cu-cap 1 --steps 50 --warmup 5 --no-extras --no-cpu-baseline > $OUT/force_dist_cu_cap1.json 2>> $OUT/force_dist.err || echo "force-dist --reg-cu-cap failed"
+timeout -k 10 600 python3 bench.py --full --mode p2l --steps 50 --warmup 5 --no-extras > $OUT/p2l.json 2> $OUT/p2l.err || echo "p2l bench failed"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_build -- python3 tools/profile_build.py > $OUT/build.txt 2> $OUT/build.err || echo "build stats failed"
-timeout -k 10 600 python3 bench.py --config 5 > $OUT/config5.json 2> $OUT/config5.err || echo "config 5 failed"
-timeout -k 10 600 python3 bench.py --config 4 --no-extras --no-cpu-baseline > $OUT/config4.json 2> $OUT/config4.err || echo "config 4 failed"
+timeout -k 10 600 python3 bench.py --full --config 5 > $OUT/config5.json 2> $OUT/config5.err || echo "config 5 failed"
+timeout -k 10 600 python3 bench.py --full --config 4 --no-extras --no-cpu-baseline > $OUT/config4.json 2> $OUT/config4.err || echo "config 4 failed"
 # the un-profiled bench line, for reference beside the profiled one
-timeout -k 10 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || echo "bench failed"
+timeout -k 10 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || echo "bench failed"
 fi
 ls $OUT

@@ -1,5 +1,5 @@
 """Device timeline of the pipelined bench from a kernel trace (rocprofv3 --kernel-trace --output-format csv -d DIR -- python3
-bench.py --steps K ...): the registration launches of the timed region (the last K pair launches before the one-stream
+bench.py --full --steps K ...): the registration launches of the timed region (the last K pair launches before the one-stream
 comparison), their gaps per stream, and the span from the first to the end of the last grid kernel.
     python tools/step_timeline.py DIR K W      (K timed steps after W warm-up steps)"""
 import csv
