@@ -384,6 +384,57 @@ int slam_grid_dirty_rows_dev(slam_grid_t *g, int32_t **d_range);
 int slam_grid_enable_accumulator(slam_grid_t *g);
 int slam_grid_fold(slam_grid_t *g, int row_lo, int row_hi, slam_stream_t stream);
 
+/* ------------------------------------------------------------ height-cluster map
+ * Stands for class MLS in its non-rolling, height-cluster mode (mls.h:154-237, mls.cpp:18-53, 152-402, 481-556):
+ * graph_slam's global map (graph_slam.cpp:71).  Every cell holds up to `capacity` z clusters (mean x, y, z, cov_zz,
+ * num_pts), a drivable state, a drivability byte, an `updated` flag and the points still pending for it
+ * (docs/MLS_MAP.md).  Arithmetic is the reference's: double, float inputs widened, no contraction. */
+typedef struct slam_mls slam_mls_t;
+
+typedef struct {
+    double max_range;              /* mls.h:161 (75) */
+    int    update_dist;            /* cells (mls.h:162); -1 = (int)fmin((int)max_range/res, size_x/2), resolved at create */
+    int    max_clusters;           /* mls.h:163 (50); at most the capacity fixed at create */
+    int    max_cluster_points;     /* mls.h:164 (200) */
+    int    min_cluster_points;     /* mls.h:165 (10) */
+    double normal_threshold;       /* mls.h:177 (0.15) */
+    double height_threshold;       /* mls.h:178 (0.4) */
+    double cluster_sigma_factor;   /* mls.h:180 (3) */
+    double cluster_dist_threshold; /* mls.h:181 (0.5) */
+    double cluster_combine_dist;   /* mls.h:182 (0.2) */
+    double drive_dist_threshold;   /* mls.h:183 (1.0) */
+    double robot_height;           /* mls.h:184: robot_size (1.45); also the start pad's height at create (mls.h:195) */
+} slam_mls_params;
+
+void slam_mls_default_params(slam_mls_params *p);
+/* MLS(size_x, size_y, res, false, robot_height), mls.h:154-205: the start pad of (2*(int)(1/res)+1)^2 cells, each
+ * with one cluster (i*res, j*res, -robot_height), num_pts = min_cluster_points, cov_zz 0.01; drivability bytes 0.
+ * Cluster capacity per cell = params->max_clusters (dense: 48 bytes per slot). */
+int  slam_mls_create(int size_x, int size_y, double resolution, const slam_mls_params *params, slam_mls_t **out);
+void slam_mls_destroy(slam_mls_t *m);
+int  slam_mls_clear(slam_mls_t *m, slam_stream_t stream);                         /* MLS::clearMap, mls.cpp:18-31 */
+int  slam_mls_set_pose(slam_mls_t *m, double x, double y);                         /* mls.cpp:408-414: stores the pose */
+/* the setters of mls.h:223-237; update_dist < 0 keeps the current value; max_clusters above the capacity: E_INVALID */
+int  slam_mls_set_params(slam_mls_t *m, const slam_mls_params *p);
+/* MLS::addToMap(cloud) non-rolling, mls.cpp:345-402 -> updateCell :152-342, at the pose last set.  Points are `stride`
+ * floats apart (x, y, z first).  Enqueues on `stream` without a host wait (the host form copies the cloud first);
+ * the device points are borrowed until the stream reaches the call.  SLAM_E_NOMEM when the pending store cannot grow. */
+int  slam_mls_add_cloud(slam_mls_t *m, const float *xyz, int n, int stride);
+int  slam_mls_add_cloud_dev(slam_mls_t *m, const float *d_xyz, int n, int stride, slam_stream_t stream);
+int  slam_mls_offset_z(slam_mls_t *m, double dz, slam_stream_t stream);           /* MLS::offsetMap's clusters, mls.cpp:481-491 */
+int  slam_mls_read_drivability(slam_mls_t *m, int8_t *data);                      /* MLS::getDrivability()->data: size_x*size_y bytes */
+/* MLS::getSegmentedClouds, mls.cpp:520-556: x, y, z floats per point in the reference's order.  The counts are always
+ * returned; SLAM_E_NOMEM (nothing copied) when a capacity is short.  Synchronous. */
+int  slam_mls_segmented_clouds(slam_mls_t *m, float *obstacle, int obstacle_cap, int *n_obstacle, float *ground,
+                               int ground_cap, int *n_ground);
+/* For n cells (linear x + size_x*y): cluster count, clusters[i*capacity + c] = (mean x, y, z, cov_zz, num_pts),
+ * drivable, byte, updated flag and pending point count.  Host arrays (any may be NULL); synchronous. */
+int  slam_mls_read_cells(slam_mls_t *m, const int32_t *cells, int n, int32_t *n_clusters, double *clusters, int8_t *drivable,
+                         int8_t *bytes, uint8_t *updated, int32_t *pending);
+/* sizes, cluster capacity, resolved parameters and the points pending now (synchronous); any pointer may be NULL */
+int  slam_mls_info(slam_mls_t *m, int *size_x, int *size_y, double *resolution, int *capacity, slam_mls_params *p,
+                   int *pending_points);
+
 /* ------------------------------------------------------ ground segmentation
  * Stands for class groundSegmentation (ground_segmentation/include/ground_segmentation/
  * groundSegmentation.h:67-128), the GP-INSAC pre-filter both halves of the path run first

@@ -63,6 +63,14 @@ class GsegParams(C.Structure):
                 ("seeding_maxrange", C.c_double), ("seeding_maxheight", C.c_double)]
 
 
+class MlsParams(C.Structure):
+    _fields_ = [("max_range", C.c_double), ("update_dist", C.c_int), ("max_clusters", C.c_int),
+                ("max_cluster_points", C.c_int), ("min_cluster_points", C.c_int), ("normal_threshold", C.c_double),
+                ("height_threshold", C.c_double), ("cluster_sigma_factor", C.c_double),
+                ("cluster_dist_threshold", C.c_double), ("cluster_combine_dist", C.c_double),
+                ("drive_dist_threshold", C.c_double), ("robot_height", C.c_double)]
+
+
 GSEG_DROPPED, GSEG_GROUND, GSEG_OBSTACLE, GSEG_OVERHEAD = 0, 1, 2, 3
 
 RESULT_DTYPE = np.dtype([("iters", np.int32), ("n_corr", np.int32), ("delta", np.float64)])
@@ -103,6 +111,9 @@ EXPORTS = [
     "slam_mapper_default_params", "slam_mapper_create", "slam_mapper_destroy", "slam_mapper_next_slot", "slam_mapper_slots",
     "slam_mapper_chunk_buffers", "slam_mapper_push", "slam_mapper_wait", "slam_mapper_finish", "slam_mapper_grid",
     "slam_mapper_target", "slam_mapper_stats", "slam_mapper_set_merge",
+    "slam_mls_default_params", "slam_mls_create", "slam_mls_destroy", "slam_mls_clear", "slam_mls_set_pose",
+    "slam_mls_set_params", "slam_mls_add_cloud", "slam_mls_add_cloud_dev", "slam_mls_offset_z",
+    "slam_mls_read_drivability", "slam_mls_segmented_clouds", "slam_mls_read_cells", "slam_mls_info",
 ]
 
 
@@ -258,6 +269,22 @@ def lib():
     L.slam_mapper_stats.argtypes = [_vp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_double),
                                     C.POINTER(C.c_int)]
     L.slam_mapper_set_merge.argtypes = [_vp, _vp, _vp, _vp]
+    L.slam_mls_default_params.restype = None
+    L.slam_mls_default_params.argtypes = [C.POINTER(MlsParams)]
+    L.slam_mls_create.argtypes = [C.c_int, C.c_int, C.c_double, C.POINTER(MlsParams), C.POINTER(_vp)]
+    L.slam_mls_destroy.restype = None
+    L.slam_mls_destroy.argtypes = [_vp]
+    L.slam_mls_clear.argtypes = [_vp, _vp]
+    L.slam_mls_set_pose.argtypes = [_vp, C.c_double, C.c_double]
+    L.slam_mls_set_params.argtypes = [_vp, C.POINTER(MlsParams)]
+    L.slam_mls_add_cloud.argtypes = [_vp, _vp, C.c_int, C.c_int]
+    L.slam_mls_add_cloud_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp]
+    L.slam_mls_offset_z.argtypes = [_vp, C.c_double, _vp]
+    L.slam_mls_read_drivability.argtypes = [_vp, _vp]
+    L.slam_mls_segmented_clouds.argtypes = [_vp, _vp, C.c_int, C.POINTER(C.c_int), _vp, C.c_int, C.POINTER(C.c_int)]
+    L.slam_mls_read_cells.argtypes = [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.slam_mls_info.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                C.POINTER(MlsParams), C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -762,6 +789,104 @@ class Grid:
             self.close()
         except Exception:
             pass
+
+
+def mls_default_params(**kw):
+    p = MlsParams()
+    lib().slam_mls_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+class MlsMap:
+    """The height-cluster MLS map (class MLS, non-rolling: mls.h:154-237) over the C-ABI: graph_slam's global map."""
+
+    def __init__(self, size_x, size_y, resolution, params=None, **kw):
+        self.size_x, self.size_y, self.resolution = int(size_x), int(size_y), float(resolution)
+        p = params or mls_default_params(**kw)
+        h = _vp()
+        check(lib().slam_mls_create(self.size_x, self.size_y, self.resolution, C.byref(p), C.byref(h)))
+        self.h = h.value
+        self.cells = self.size_x * self.size_y
+        self.capacity = self.info()["capacity"]
+
+    def close(self):
+        if self.h:
+            lib().slam_mls_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        sx, sy, cap, pend = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        res = C.c_double()
+        p = MlsParams()
+        check(lib().slam_mls_info(self.h, C.byref(sx), C.byref(sy), C.byref(res), C.byref(cap), C.byref(p), C.byref(pend)))
+        return {"size_x": sx.value, "size_y": sy.value, "resolution": res.value, "capacity": cap.value, "params": p,
+                "pending_points": pend.value}
+
+    @property
+    def params(self):
+        return self.info()["params"]
+
+    def set_params(self, **kw):
+        p = self.params
+        for k, v in kw.items():
+            setattr(p, k, v)
+        check(lib().slam_mls_set_params(self.h, C.byref(p)))
+
+    def clear(self, stream=None):
+        check(lib().slam_mls_clear(self.h, _sp(stream)))
+
+    def set_pose(self, x, y):
+        check(lib().slam_mls_set_pose(self.h, float(x), float(y)))
+
+    def add_cloud(self, xyz, pose=None):
+        """MLS::addToMap(cloud[, pose]) with the cloud already in the map frame; pose = (x, y) sets the pose first."""
+        if pose is not None:
+            self.set_pose(pose[0], pose[1])
+        a = np.ascontiguousarray(xyz, dtype=np.float32)
+        if a.ndim == 1:
+            a = a.reshape(-1, 3)
+        check(lib().slam_mls_add_cloud(self.h, _ptr(a), len(a), a.shape[1] if a.size else 3))
+
+    def add_cloud_dev(self, d_xyz, n, stride=3, stream=None):
+        check(lib().slam_mls_add_cloud_dev(self.h, d_xyz.ptr, int(n), int(stride), _sp(stream)))
+
+    def offset_z(self, dz, stream=None):
+        check(lib().slam_mls_offset_z(self.h, float(dz), _sp(stream)))
+
+    def read_drivability(self):
+        out = np.empty(self.cells, np.int8)
+        check(lib().slam_mls_read_drivability(self.h, _ptr(out)))
+        return out
+
+    def segmented_clouds(self):
+        """(obstacle, ground) float32 [n, 3] in MLS::getSegmentedClouds' order."""
+        no, ng = C.c_int(), C.c_int()
+        rc = lib().slam_mls_segmented_clouds(self.h, None, 0, C.byref(no), None, 0, C.byref(ng))
+        if rc not in (SLAM_OK, E_NOMEM):
+            check(rc)
+        obs, gnd = np.empty((no.value, 3), np.float32), np.empty((ng.value, 3), np.float32)
+        check(lib().slam_mls_segmented_clouds(self.h, _ptr(obs), len(obs), C.byref(no), _ptr(gnd), len(gnd), C.byref(ng)))
+        return obs, gnd
+
+    def read_cells(self, cells, clusters=True):
+        """dict of per-cell arrays: n_clusters, clusters [n, capacity, 5] (mean x, y, z, cov_zz, num_pts; None without
+        clusters), drivable, byte, updated, pending"""
+        cells = np.ascontiguousarray(cells, dtype=np.int32)
+        n = len(cells)
+        out = {"n_clusters": np.zeros(n, np.int32), "clusters": np.zeros((n, self.capacity, 5)) if clusters else None,
+               "drivable": np.zeros(n, np.int8), "byte": np.zeros(n, np.int8), "updated": np.zeros(n, np.uint8),
+               "pending": np.zeros(n, np.int32)}
+        check(lib().slam_mls_read_cells(self.h, _ptr(cells), n, _ptr(out["n_clusters"]), _ptr(out["clusters"]),
+                                        _ptr(out["drivable"]), _ptr(out["byte"]), _ptr(out["updated"]), _ptr(out["pending"])))
+        return out
 
 
 class Mapper:

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "grid_cell.hpp"
 
 using namespace slam;
 
@@ -58,36 +59,11 @@ __device__ inline int storage_index(const GridView &g, int x, int y)
     return ix + g.sx * iy;
 }
 
-// (int)(v/res + size/2) of mls.cpp:77-78; false when an int cannot hold it
-// (undefined in the reference; x86 gives INT_MIN there, i.e. "skip").
-__device__ inline bool cell_coord(float v, double res, int half, int *out)
-{
-    const double f = __dadd_rn(__ddiv_rn((double)v, res), (double)half);
-    if (!(f > -2147483648.0 && f < 2147483648.0)) return false;
-    *out = (int)f; // truncation toward zero
-    return true;
-}
-
 // mls.cpp:77-90: window cell of a point, or false when the range gate or the
-// bounds test (with its `y >= size_x` quirk) drops it.
+// bounds test (with its `y >= size_x` quirk) drops it (grid_cell.hpp).
 __device__ inline bool point_cell(const GridView &g, float px, float py, int *cx, int *cy)
 {
-    int x, y;
-    if (!cell_coord(px, g.res, g.sx / 2, &x)) return false;
-    if (!cell_coord(py, g.res, g.sy / 2, &y)) return false;
-    double rng;
-    if (g.rolling) {
-        // mls.cpp:82: float expression, float sqrt, widened for the compare
-        rng = (double)__fsqrt_rn(__fadd_rn(__fmul_rn(px, px), __fmul_rn(py, py)));
-    } else {
-        const double rx = g.pose_x - (double)px, ry = g.pose_y - (double)py; // :84-86
-        rng = __dsqrt_rn(__dadd_rn(__dmul_rn(rx, rx), __dmul_rn(ry, ry)));
-    }
-    if (x < 0 || y < 0 || x >= g.sx || y >= g.sx || rng > g.max_range) return false; // :90
-    if (y >= g.sy) return false;
-    *cx = x;
-    *cy = y;
-    return true;
+    return point_cell_of(g.sx, g.sy, g.res, g.max_range, g.pose_x, g.pose_y, g.rolling, px, py, cx, cy);
 }
 
 constexpr int kUpdateSlots = 1024;

@@ -1,0 +1,199 @@
+"""Hand-worked cases of the height-cluster MLS, one per branch of updateCell (mls.cpp:152-342); the expected values
+are worked out here, not taken from the oracle.  Each case runs on the scalar restatement (tests/cpp/mls_map_oracle.cpp)
+and, marked gpu, on the device side by side with it (mls_map_oracle.Checked: the whole map compared bit for bit
+before every read).  And the C-ABI of slam_mls_* without a GPU."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import mls_map_oracle as MO
+from slam_amd import api, build
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+S = 20  # a 20 x 20 map at 1 m: cell (cx, cy) holds world (cx - 10 + 0.5, cy - 10 + 0.5)
+
+
+@pytest.fixture(params=["oracle", pytest.param("device", marks=pytest.mark.gpu)])
+def make(request):
+    made = []
+
+    def f(*a):
+        m = MO.OracleMls(*a) if request.param == "oracle" else MO.Checked(*a)
+        made.append(m)
+        return m
+    yield f
+    for m in made:
+        if request.param == "device":
+            m.check("end")
+        m.close()
+
+
+def params(**kw):
+    p = api.MlsParams()
+    d = dict(max_range=75.0, update_dist=-1, max_clusters=50, max_cluster_points=200, min_cluster_points=10,
+             normal_threshold=0.15, height_threshold=0.4, cluster_sigma_factor=3.0, cluster_dist_threshold=0.5,
+             cluster_combine_dist=0.2, drive_dist_threshold=1.0, robot_height=1.45)
+    d.update(kw)
+    for k, v in d.items():
+        setattr(p, k, v)
+    return p
+
+
+def column(cx, cy, zs):
+    return np.array([[cx - 10 + 0.5, cy - 10 + 0.5, z] for z in zs], np.float32)
+
+
+def cell(m, cx, cy):
+    r = m.read_cells([cx + S * cy])
+    k = r["n_clusters"][0]
+    return r["clusters"][0][:k], int(r["drivable"][0]), int(r["byte"][0]), int(r["updated"][0]), int(r["pending"][0])
+
+
+def test_start_pad_bytes_and_clear(make):
+    m = make(S, S, 1.0, params())
+    assert (m.read_drivability() == 0).all()               # mls.h:175: data.resize zero-fills
+    cl, drv, byte, upd, pend = cell(m, 9, 11)               # i = -1, j = +1 of the pad (set_size 1)
+    assert cl.tolist() == [[-1.0, 1.0, -1.45, 0.01, 10.0]] and (drv, upd, pend) == (-1, 0, 0)
+    assert len(m.touched()) == 9
+    m.clear()                                               # mls.cpp:18-31: no pad, bytes -1
+    assert (m.read_drivability() == -1).all() and len(m.touched()) == 0
+
+
+def test_uninitialised_match_new_cluster_sort_and_kept_points(make):
+    m = make(S, S, 1.0, params())
+    m.add_cloud(column(3, 3, [3.0, 0.0, 0.5]), (0, 0))
+    cl, drv, byte, upd, pend = cell(m, 3, 3)
+    # 3.0: new cluster A.  0.0: A is a candidate at 3.0 > robot_height: new cluster B, sorted in front.
+    # 0.5: B (uninitialised) is the nearest candidate: n 2, mean (0 + 0.5) / 2, cov 1/1 * 0.25^2
+    assert cl[:, 2].tolist() == [0.25, 3.0] and cl[:, 3].tolist() == [0.0625, 0.0] and cl[:, 4].tolist() == [2.0, 1.0]
+    assert (drv, byte, upd, pend) == (-1, 0, 0, 3)          # no ground cluster: the points stay pending
+    # the next call replays them ahead of the new point
+    m.add_cloud(column(3, 3, [0.0]), (0, 0))
+    cl, _, _, _, pend = cell(m, 3, 3)
+    assert pend == 4 and cl[:, 4].tolist() == [5.0, 2.0]
+
+
+def test_initialised_match_covariance_floor_and_drivable(make):
+    m = make(S, S, 1.0, params())
+    m.add_cloud(column(3, 3, [0.0] * 12), (0, 0))
+    cl, drv, byte, upd, pend = cell(m, 3, 3)
+    # ten points make the cluster; 11 and 12 match it as initialised (d 0 < sqrt(0.001) * 3 + 0.5); cov 0 -> 0.001
+    assert cl[:, 2:].tolist() == [[0.0, 0.001, 12.0]]
+    assert (drv, byte, upd, pend) == (1, 0, 0, 0)
+
+
+def test_point_dropped_at_max_clusters(make):
+    m = make(S, S, 1.0, params(max_clusters=1))
+    m.add_cloud(column(3, 3, [0.0, 5.0]), (0, 0))
+    cl, drv, byte, upd, pend = cell(m, 3, 3)
+    assert cl[:, 2:].tolist() == [[0.0, 0.0, 1.0]] and pend == 2
+
+
+def test_cap_erase_skip_and_stale_slot_then_combine(make):
+    m = make(S, S, 1.0, params(min_cluster_points=1, max_cluster_points=3))
+    # A -10 (n 1), B -5 (n 1), C 0 (n 3), D 10 (n 2); then 0 hits C at the cap: B drops to 0 and goes, C and D shift
+    # down, D lands on C's old slot (2) and is skipped by the decrement loop, and the update lands on D with its n = 2
+    m.add_cloud(column(3, 3, [-10.0, -5.0, 0.0, 10.0, 0.0, 0.0, 10.0, 0.0]), (0, 0))
+    cl, drv, byte, upd, pend = cell(m, 3, 3)
+    d_mean = 0.5 * 10.0 + 0.5 * 0.0
+    d_cov = 0.5 * 0.001 + 1.0 / 1.0 * (0.0 - d_mean) * (0.0 - d_mean)
+    # ground is C (first n > 1); D above it: clearance 5 - 2 sqrt(d_cov) - 0 < 0.2: combined, r = 3/5, 2/5
+    r0, r1 = 3.0 / (3.0 + 2.0), 2.0 / (3.0 + 2.0)
+    assert cl[:, 4].tolist() == [1.0, 3.0] and cl[0, 2] == -10.0
+    assert cl[1, 2] == r0 * 0.0 + r1 * d_mean and cl[1, 3] == r0 * 0.001 + r1 * d_cov
+    assert (drv, byte, pend) == (0, 100, 0)                 # cov 10.0008 > normal_threshold
+    # with the cap on A instead: the decrement skips the cluster shifted into the erased slot
+    m = make(S, S, 1.0, params(min_cluster_points=1, max_cluster_points=3))
+    m.add_cloud(column(3, 3, [0.0, 5.0, 10.0, 0.0, 10.0, 0.0, 0.0]), (0, 0))
+    cl = cell(m, 3, 3)[0]
+    assert cl[:, 2].tolist() == [0.0, 10.0] and cl[:, 4].tolist() == [3.0, 2.0]   # C kept its 2
+
+
+def test_stale_slot_past_the_end_is_lost(make):
+    m = make(S, S, 1.0, params(min_cluster_points=1, max_cluster_points=3))
+    m.add_cloud(column(3, 3, [-10.0, -5.0, 0.0, 0.0, 0.0, 0.25]), (0, 0))
+    cl = cell(m, 3, 3)[0]
+    assert cl[:, 2].tolist() == [-10.0, 0.0] and cl[:, 4].tolist() == [1.0, 3.0]   # 0.25 left no trace
+
+
+def test_clearance_neighbour_and_passing(make):
+    m = make(S, S, 1.0, params())
+    cloud = np.concatenate([column(3, 3, [0.0] * 12 + [1.0] * 12),      # clearance 1 - 2 sqrt(0.001) in [0.2, 1)
+                            column(5, 3, [0.0] * 12), column(6, 3, [1.0] * 12)])
+    m.add_cloud(cloud, (0, 0))
+    assert cell(m, 3, 3)[1:3] == (0, 100)
+    assert cell(m, 6, 3)[1:3] == (0, 100)                   # 1.0 above its neighbour (5, 3): > height_threshold
+    assert cell(m, 5, 3)[1:3] == (1, 0)                     # 1.0 below: passes
+    b = m.read_drivability()
+    assert b[3 + S * 3] == 100 and b[5 + S * 3] == 0
+
+
+def test_out_of_window_closure_chain(make):
+    m = make(S, S, 1.0, params(update_dist=2))
+    # pose (0, -5): window x 8..11, y 3..6.  (11, 5) is inside; (12..14, 5) outside, reached through the recursion
+    # one after the other; (16, 5) is outside and not adjacent: it keeps its points and its flag
+    cloud = np.concatenate([column(x, 5, [0.0] * 12) for x in (11, 12, 13, 14, 16)])
+    m.add_cloud(cloud, (0.0, -5.0))
+    for x in (11, 12, 13, 14):
+        assert cell(m, x, 5)[1:] == (1, 0, 0, 0), x
+    assert cell(m, 16, 5)[1:] == (-1, 0, 1, 12)
+
+
+# ---------------------------------------------------------------- C-ABI without a GPU
+
+@pytest.fixture(scope="module")
+def L():
+    build.build()
+    return api.lib()
+
+
+def test_mls_argument_errors_need_no_device(L):
+    h = C.c_void_p()
+    p = api.MlsParams()
+    L.slam_mls_default_params(C.byref(p))
+    assert (p.max_range, p.update_dist, p.max_clusters, p.max_cluster_points, p.min_cluster_points) == (75.0, -1, 50, 200, 10)
+    assert (p.normal_threshold, p.height_threshold, p.cluster_sigma_factor, p.cluster_dist_threshold) == (0.15, 0.4, 3.0, 0.5)
+    assert (p.cluster_combine_dist, p.drive_dist_threshold, p.robot_height) == (0.2, 1.0, 1.45)
+    assert L.slam_mls_create(0, 10, 0.5, C.byref(p), C.byref(h)) == api.E_INVALID
+    assert L.slam_mls_create(10, 10, -0.5, C.byref(p), C.byref(h)) == api.E_INVALID
+    p.max_clusters = 0
+    assert L.slam_mls_create(10, 10, 0.5, C.byref(p), C.byref(h)) == api.E_INVALID
+    assert L.slam_mls_add_cloud(None, None, 0, 3) == api.E_INVALID
+    assert L.slam_mls_read_cells(None, None, 0, None, None, None, None, None, None) == api.E_INVALID
+    assert L.slam_mls_set_params(None, None) == api.E_INVALID
+
+
+def test_start_pad_must_fit_the_grid(L):
+    """(2 * (int)(1/res) + 1) cells a side around the centre: a grid smaller than that is refused (the reference would wrap
+    the pad round and stack clusters), before any device is needed"""
+    h = C.c_void_p()
+    p = api.MlsParams()
+    L.slam_mls_default_params(C.byref(p))
+    assert L.slam_mls_create(4, 40, 0.5, C.byref(p), C.byref(h)) == api.E_INVALID   # pad 5 x 5
+    assert L.slam_mls_create(40, 40, 1e-6, C.byref(p), C.byref(h)) == api.E_INVALID
+    with pytest.raises(ValueError):
+        MO.OracleMls(4, 40, 0.5, params())
+
+
+def test_mls_compute_needs_a_device(L):
+    """without a GPU creation fails with E_NO_DEVICE (there is no CPU path); with one it succeeds"""
+    if api.device_count() > 0:
+        api.MlsMap(100, 100, 0.5).close()
+        return
+    with pytest.raises(api.SlamError) as e:
+        api.MlsMap(100, 100, 0.5)
+    assert e.value.code == api.E_NO_DEVICE
+
+
+def test_mls_map_header_compiles_against_the_library(tmp_path):
+    build.build()
+    src = tmp_path / "t.cpp"
+    src.write_text('#include "slam_amd/mls_map.hpp"\n'
+                   'int main() { slam_amd::MLSMap m(100, 100, 0.5, false, 1.45); m.setMinClusterPoints(5);\n'
+                   '  std::vector<float> o, g; m.getSegmentedClouds(o, g); return m.ok() ? 0 : 1; }\n')
+    lib = os.path.join(ROOT, "slam_amd", "lib")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "t"),
+                           "-L" + lib, "-l:libslam_mi355x.so", "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib"])
