@@ -1,0 +1,293 @@
+// slam_amd/graph_edges.hpp -- header-only adapter with the shape of graph_slam's keyframe tools
+// (graph_slam/include/graph_slam/graphSlamTools.h, src/graphSlamTools.cpp) over the C-ABI (slam_mi355x.h, slam_kf_*):
+//   graphSlamGetNearestKF   :43-65     getNearestKF
+//   graphSlamGetKNN         :72-106    getKNN
+//   calcEdgeIcp             :218-364   calcEdgeIcp / calcEdges (a batch in one device call)
+//   graph_slam.cpp:508-518             addEdgesForNewNode: the KNN edges and the edge to the previous keyframe, one call
+// A keyframe is filtered (pcl::VoxelGrid 0.5) and indexed once, when it is added; the reference filters both clouds again at
+// every edge, which gives the same clouds.  The device does the ICP and computeEdgeInformationLUM; what is left of
+// calcEdgeIcp runs here: the initial transform from the two poses, the edge pose and quaternion, the acceptance gate.
+// g2o (addVertex / addEdge / optimizeGraph) stays with the caller.
+//
+// Two places where this differs from the reference's host arithmetic by rounding, neither pinned (docs/KF_EDGE.md):
+// Mfrom.inverse() is taken as the rigid inverse (R', -R't) instead of Eigen's general 4 x 4 inverse, and the initial pose's
+// quaternion comes from the linear part of the f32 matrix instead of Affine3d::rotation()'s polar factor.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <utility>
+#include <vector>
+
+#include "slam_amd/mls.hpp" // Pose
+#include "slam_mi355x.h"
+
+namespace slam_amd {
+
+// graphSlamTools.h:27-34
+enum { CTYPE_HOME = 0, CTYPE_ODOM = 1, CTYPE_NN = 2 };
+
+struct GraphNode { // graph_slam.h Node: idx, pose (the keyframe cloud lives in the store)
+    int  idx = 0;
+    Pose pose;
+};
+
+struct GraphEdge { // graph_slam/Edge: from, to, ctype, edge (pose), edgeInf
+    int    from = 0, to = 0, ctype = CTYPE_NN;
+    Pose   edge;
+    double edgeInf[36] = {0};
+    // what the reference computes and drops: the Matrix4f handed to align and the one it returned, hasConverged() & co.
+    float  init[16] = {0}, transform[16] = {0};
+    int    iterations = 0, state = 0, converged = 0, pairs = 0, numCorr = 0, singular = 0;
+    double x_diff = 0, y_diff = 0, theta_diff = 0;
+    bool   accepted = false;
+};
+
+namespace graph_detail {
+
+// Eigen::Quaterniond(w, x, y, z).toRotationMatrix(), the rotation of tf::poseMsgToEigen
+inline void quat_to_matrix(const Pose &q, double m[9])
+{
+    const double tx = 2.0 * q.qx, ty = 2.0 * q.qy, tz = 2.0 * q.qz;
+    const double twx = tx * q.qw, twy = ty * q.qw, twz = tz * q.qw, txx = tx * q.qx, txy = ty * q.qx, txz = tz * q.qx, tyy = ty * q.qy,
+                 tyz = tz * q.qy, tzz = tz * q.qz;
+    m[0] = 1.0 - (tyy + tzz), m[1] = txy - twz, m[2] = txz + twy;
+    m[3] = txy + twz, m[4] = 1.0 - (txx + tzz), m[5] = tyz - twx;
+    m[6] = txz - twy, m[7] = tyz + twx, m[8] = 1.0 - (txx + tyy);
+}
+
+// (Mfrom^-1 Mto).cast<float>(), graphSlamTools.cpp:258, row-major 4 x 4
+inline void relative_f32(const Pose &from, const Pose &to, float out[16])
+{
+    double Rf[9], Rt[9];
+    quat_to_matrix(from, Rf);
+    quat_to_matrix(to, Rt);
+    const double d[3] = {to.x - from.x, to.y - from.y, to.z - from.z};
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) out[4 * r + c] = (float)((Rf[r] * Rt[c] + Rf[3 + r] * Rt[3 + c]) + Rf[6 + r] * Rt[6 + c]);
+        out[4 * r + 3] = (float)((Rf[r] * d[0] + Rf[3 + r] * d[1]) + Rf[6 + r] * d[2]);
+    }
+    out[12] = out[13] = out[14] = 0.0f, out[15] = 1.0f;
+}
+
+// Eigen::Quaterniond(Matrix3d) (tf::poseEigenToMsg, which also makes w >= 0)
+inline void eigen_quaternion(const double m[9], Pose *p)
+{
+    double q[4]; // x y z w
+    double t = m[0] + m[4] + m[8];
+    if (t > 0.0) {
+        t = std::sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (m[7] - m[5]) * t, q[1] = (m[2] - m[6]) * t, q[2] = (m[3] - m[1]) * t;
+    } else {
+        int i = 0;
+        if (m[4] > m[0]) i = 1;
+        if (m[8] > m[4 * i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = std::sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
+        q[i] = 0.5 * t;
+        t = 0.5 / t;
+        q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
+        q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
+        q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
+    }
+    if (q[3] < 0) q[0] = -q[0], q[1] = -q[1], q[2] = -q[2], q[3] = -q[3];
+    p->qx = q[0], p->qy = q[1], p->qz = q[2], p->qw = q[3];
+}
+
+// tf::Matrix3x3::getRotation
+inline void tf_quaternion(const double m[9], Pose *p)
+{
+    const double trace = m[0] + m[4] + m[8];
+    double       temp[4];
+    if (trace > 0.0) {
+        double s = std::sqrt(trace + 1.0);
+        temp[3] = s * 0.5;
+        s = 0.5 / s;
+        temp[0] = (m[7] - m[5]) * s, temp[1] = (m[2] - m[6]) * s, temp[2] = (m[3] - m[1]) * s;
+    } else {
+        const int i = m[0] < m[4] ? (m[4] < m[8] ? 2 : 1) : (m[0] < m[8] ? 2 : 0);
+        const int j = (i + 1) % 3, k = (i + 2) % 3;
+        double    s = std::sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
+        temp[i] = s * 0.5;
+        s = 0.5 / s;
+        temp[3] = (m[3 * k + j] - m[3 * j + k]) * s;
+        temp[j] = (m[3 * j + i] + m[3 * i + j]) * s;
+        temp[k] = (m[3 * k + i] + m[3 * i + k]) * s;
+    }
+    p->qx = temp[0], p->qy = temp[1], p->qz = temp[2], p->qw = temp[3];
+}
+
+// tf::getYaw: Matrix3x3(q).getRPY's yaw (setRotation, then getEulerYPR's first solution)
+inline double tf_yaw(const Pose &q)
+{
+    const double d = q.qx * q.qx + q.qy * q.qy + q.qz * q.qz + q.qw * q.qw, s = 2.0 / d;
+    const double ys = q.qy * s, zs = q.qz * s, wy = q.qw * ys, wz = q.qw * zs, xy = q.qx * ys, xz = q.qx * zs, yy = q.qy * ys,
+                 zz = q.qz * zs;
+    const double m00 = 1.0 - (yy + zz), m10 = xy + wz, m20 = xz - wy;
+    if (std::fabs(m20) >= 1.0) return 0.0;
+    const double pitch = -std::asin(m20), cp = std::cos(pitch);
+    return std::atan2(m10 / cp, m00 / cp);
+}
+
+} // namespace graph_detail
+
+class KeyframeGraph {
+public:
+    // graphSlamTools.h:23-24, 32-33: macros there, members here
+    double KNN_DIST_THRESH = 5.0;
+    int    GSLAM_KNN = 3;
+    double DIST_MOVE_THRESH = 10.0;
+    double ROT_MOVE_THRESH = 0.2;
+
+    std::vector<GraphNode> nodes; // PoseGraph
+    std::vector<GraphEdge> edges;
+
+    explicit KeyframeGraph(const slam_kf_params *params = nullptr) // null: setup_gicp's values
+    {
+        if (slam_kf_create(params, &h_) != SLAM_OK) {
+            warn();
+            h_ = nullptr;
+        }
+    }
+    ~KeyframeGraph() { slam_kf_destroy(h_); }
+    KeyframeGraph(const KeyframeGraph &) = delete;
+    KeyframeGraph &operator=(const KeyframeGraph &) = delete;
+    bool       ok() const { return h_ != nullptr; }
+    slam_kf_t *handle() { return h_; }
+
+    // graph_slam.cpp:501-504: *gN.keyframe = *current_cloud; pG.nodes.push_back(gN).  Returns the node's idx, -1 on failure.
+    int addNode(const float *xyz, int n, int stride, const Pose &pose)
+    {
+        int id = -1;
+        if (!h_ || slam_kf_add_keyframe(h_, xyz, n, stride, &id) != SLAM_OK) {
+            warn();
+            return -1;
+        }
+        GraphNode g;
+        g.idx = id, g.pose = pose;
+        nodes.push_back(g);
+        return id;
+    }
+
+    // graphSlamGetNearestKF (:43-65): the distance from a node (idx = nodes.size() for one not added yet) to its nearest other
+    double getNearestKF(const Pose &pose, int idx) const
+    {
+        double smallestDist = 1e20;
+        for (size_t i = 0; i < nodes.size(); ++i) {
+            const double dx = nodes[i].pose.x - pose.x, dy = nodes[i].pose.y - pose.y;
+            const double currDist = std::sqrt(dx * dx + dy * dy);
+            if (currDist < smallestDist && idx != nodes[i].idx) smallestDist = currDist;
+        }
+        return smallestDist;
+    }
+
+    // graphSlamGetKNN (:72-106), the loop bound numKF - 2 and K = min(numKF - 1, K) as written there
+    std::vector<int> getKNN(const GraphNode &gN, int K) const
+    {
+        std::vector<int>                    toReturn;
+        std::vector<std::pair<double, int>> sC;
+        const int                           numKF = (int)nodes.size();
+        K = std::min(numKF - 1, K);
+        for (int i = 0; i < numKF - 2; ++i) {
+            const double dx = nodes[i].pose.x - gN.pose.x, dy = nodes[i].pose.y - gN.pose.y;
+            sC.push_back(std::make_pair(std::sqrt(dx * dx + dy * dy), i));
+        }
+        // the reference's std::sort on the distance alone leaves the order of equal distances open; stable here
+        std::stable_sort(sC.begin(), sC.end(), [](const std::pair<double, int> &a, const std::pair<double, int> &b) { return a.first < b.first; });
+        for (int i = 0; i < K; ++i)
+            if (i < (int)sC.size() && gN.idx != sC[i].second) toReturn.push_back(sC[i].second);
+        return toReturn;
+    }
+
+    // calcEdgeIcp for a batch: every (from, to) registered in one device call.  out[e].accepted is calcEdgeIcp's return value.
+    bool calcEdges(const std::vector<std::pair<int, int>> &pairs, std::vector<GraphEdge> &out)
+    {
+        out.clear();
+        if (!h_ || pairs.empty()) return h_ != nullptr;
+        std::vector<slam_kf_edge_req>    req(pairs.size());
+        std::vector<slam_kf_edge_result> res(pairs.size());
+        for (size_t e = 0; e < pairs.size(); ++e) {
+            const int from = pairs[e].first, to = pairs[e].second;
+            if (from < 0 || to < 0 || from >= (int)nodes.size() || to >= (int)nodes.size()) return false;
+            req[e].from = from, req[e].to = to;
+            graph_detail::relative_f32(nodes[from].pose, nodes[to].pose, req[e].init); // :258
+        }
+        if (slam_kf_register_edges(h_, req.data(), (int)req.size(), res.data(), nullptr) != SLAM_OK) {
+            warn();
+            return false;
+        }
+        out.resize(pairs.size());
+        for (size_t e = 0; e < pairs.size(); ++e) finish(req[e], res[e], &out[e]);
+        return true;
+    }
+
+    // calcEdgeIcp (:218-364): true = a good match
+    bool calcEdgeIcp(int from, int to, GraphEdge &gE)
+    {
+        std::vector<GraphEdge> one;
+        if (!calcEdges({std::make_pair(from, to)}, one) || one.empty()) return false;
+        gE = one[0];
+        return gE.accepted;
+    }
+
+    // graph_slam.cpp:508-518 for the node added last: graphSlamAddEdgeToX for its KNN, then for its predecessor -- registered
+    // together, pushed in that order.  Returns the edges pushed; `tried` (optional) gets every edge, rejected ones too.
+    int addEdgesForNewNode(std::vector<GraphEdge> *tried = nullptr)
+    {
+        if (tried) tried->clear();
+        if (nodes.size() < 2) return 0; // graphSlamAddEdgeToX :409
+        const GraphNode                 &gN = nodes.back();
+        std::vector<std::pair<int, int>> pairs;
+        for (int k : getKNN(gN, GSLAM_KNN)) pairs.push_back(std::make_pair(k, gN.idx));
+        pairs.push_back(std::make_pair(gN.idx - 1, gN.idx));
+        std::vector<GraphEdge> got;
+        if (!calcEdges(pairs, got)) return 0;
+        int pushed = 0;
+        for (const GraphEdge &e : got)
+            if (e.accepted) edges.push_back(e), ++pushed;
+        if (tried) *tried = got;
+        return pushed;
+    }
+
+private:
+    void finish(const slam_kf_edge_req &req, const slam_kf_edge_result &res, GraphEdge *gE) const
+    {
+        using namespace graph_detail;
+        gE->from = req.from, gE->to = req.to, gE->ctype = CTYPE_NN;
+        for (int k = 0; k < 16; ++k) gE->init[k] = req.init[k], gE->transform[k] = res.transform[k];
+        for (int k = 0; k < 36; ++k) gE->edgeInf[k] = res.information[k];
+        gE->iterations = res.iterations, gE->state = res.state, gE->converged = res.converged, gE->pairs = res.pairs;
+        gE->numCorr = res.num_corr, gE->singular = res.singular;
+        // :259-260 initialization_pose(transformation.cast<double>()) -> initPose
+        Pose   initPose;
+        double m[9];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) m[3 * r + c] = (double)req.init[4 * r + c];
+        initPose.x = (double)req.init[3], initPose.y = (double)req.init[7], initPose.z = (double)req.init[11];
+        eigen_quaternion(m, &initPose);
+        // :318-331 the edge pose from the f32 result
+        const float *T = res.transform;
+        gE->edge.x = static_cast<double>(T[3]), gE->edge.y = static_cast<double>(T[7]), gE->edge.z = static_cast<double>(T[11]);
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) m[3 * r + c] = static_cast<double>(T[4 * r + c]);
+        tf_quaternion(m, &gE->edge);
+        // :335-342 (abs on doubles: fabs)
+        gE->x_diff = std::fabs(initPose.x - gE->edge.x);
+        gE->y_diff = std::fabs(initPose.y - gE->edge.y);
+        double theta_diff = std::fabs(tf_yaw(initPose) - tf_yaw(gE->edge));
+        if (theta_diff > 2 * M_PI)
+            theta_diff = theta_diff - 2 * M_PI;
+        else if (theta_diff > M_PI)
+            theta_diff = 2 * M_PI - theta_diff;
+        gE->theta_diff = theta_diff;
+        // :355-360
+        gE->accepted = !((gE->x_diff > DIST_MOVE_THRESH) || (gE->y_diff > DIST_MOVE_THRESH) || (theta_diff > ROT_MOVE_THRESH));
+    }
+    static void warn() { std::fprintf(stderr, "KeyframeGraph: %s\n", slam_last_error()); }
+
+    slam_kf_t *h_ = nullptr;
+};
+
+} // namespace slam_amd

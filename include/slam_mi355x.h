@@ -666,6 +666,76 @@ int  slam_mapper_stats(slam_mapper_t *m, long *chunks, long *merges, long *rebui
 typedef int (*slam_mapper_merge_fn)(void *ctx, slam_grid_t *grid, slam_stream_t stream, int *row_lo, int *row_hi);
 int  slam_mapper_set_merge(slam_mapper_t *m, slam_mapper_merge_fn begin, slam_mapper_merge_fn finish, void *ctx);
 
+/* -------------------------------------------------------------------------
+ * graph_slam's keyframe edges (graph_slam/src/graphSlamTools.cpp:108-364): a store of voxel-filtered keyframes, each
+ * with a 3-D search lattice, and calcEdgeIcp's registration -- pcl::IterativeClosestPoint, point to point, then
+ * computeEdgeInformationLUM -- for a batch of edges in one launch.  docs/KF_EDGE.md has the contract.
+ * ---------------------------------------------------------------------- */
+typedef struct slam_kf slam_kf_t;
+
+typedef struct {
+    double leaf_size;              /* pcl::VoxelGrid leaf, all three axes (graphSlamTools.cpp:281: 0.5) */
+    double gate;                   /* setMaxCorrespondenceDistance, also computeEdgeInformationLUM's (:29, :302: 0.75) */
+    double cell_size;              /* edge of the search lattice, >= gate; 0 = gate.  (The lattice adds 2^-16 of it, which
+                                      covers the rounding of the f32 distance test.) */
+    int    max_iterations;         /* setMaximumIterations (:31: 200) */
+    double transformation_epsilon; /* setTransformationEpsilon (:33: 1e-6) */
+    double fitness_epsilon;        /* setEuclideanFitnessEpsilon (:35: 1e-6) */
+    int    target_in_lds;          /* 1 (default): an edge's workgroup stages the target's sorted points in LDS when they fit
+                                      (6144 points); 0: they are read through L2.  Same results. */
+} slam_kf_params;
+
+/* why the iteration ended (pcl::registration::DefaultConvergenceCriteria's states) */
+#define SLAM_KF_NOT_CONVERGED 0
+#define SLAM_KF_ITERATIONS 1
+#define SLAM_KF_TRANSFORM 2
+#define SLAM_KF_ABS_MSE 3
+#define SLAM_KF_REL_MSE 4
+#define SLAM_KF_NO_CORRESPONDENCES 5
+
+typedef struct {
+    int   from, to;  /* keyframe ids: target = `from`, source = `to` (setInputSource(to_cld), setInputTarget(from_cld)) */
+    float init[16];  /* 4 x 4 row-major: the Matrix4f handed to align() */
+} slam_kf_edge_req;
+
+typedef struct {
+    float  transform[16];     /* getFinalTransformation(): the f64 result rounded once, row-major */
+    double transform64[16];
+    int    iterations, state; /* SLAM_KF_* */
+    int    converged, pairs;  /* hasConverged(); pairs kept in the last iteration */
+    double mse;               /* mean squared distance of those pairs */
+    double information[36];   /* computeEdgeInformationLUM: M'M / s^2, or the identity (singular != 0) */
+    int    num_corr, singular;
+    float  ss;
+    int    reserved;
+} slam_kf_edge_result;
+
+void slam_kf_default_params(slam_kf_params *p);
+int  slam_kf_create(const slam_kf_params *params, slam_kf_t **out);
+void slam_kf_destroy(slam_kf_t *s);
+int  slam_kf_set_params(slam_kf_t *s, const slam_kf_params *params); /* leaf, gate and cell hold for later keyframes only:
+                                                                         refused once the store holds one and they differ */
+/* Filters the cloud (`stride` >= 3 floats per point, x y z first) and builds its search lattice; *id = 0, 1, 2, ... in order
+ * of arrival.  The _dev form takes a device pointer.  Both wait for the work they enqueue on `stream`. */
+int  slam_kf_add_keyframe(slam_kf_t *s, const float *xyz, int n, int stride, int *id);
+int  slam_kf_add_keyframe_dev(slam_kf_t *s, const float *d_xyz, int n, int stride, int *id, slam_stream_t stream);
+/* n_points after the filter, occupied lattice cells, the largest cell, slots of the hash table, device bytes held */
+int  slam_kf_keyframe_info(slam_kf_t *s, int id, int *n_points, int *n_cells, int *max_cell_points, int *table_slots,
+                           long *device_bytes);
+int  slam_kf_count(slam_kf_t *s);
+/* the filtered cloud, 4 floats per point as slam_ccicp_voxel_downsample_dev writes them; room for max_points */
+int  slam_kf_read_keyframe(slam_kf_t *s, int id, float *xyz4, int max_points, int *n_points);
+/* The gated nearest neighbour of n device-resident queries in keyframe `id`: d_index[i] = index into the filtered cloud
+ * or -1, d_dist2[i] = the f32 squared distance (kept when <= gate^2, or < gate^2 with strict != 0). */
+int  slam_kf_nearest_dev(slam_kf_t *s, int id, const float *d_queries, int n, int stride, int strict, int32_t *d_index,
+                         float *d_dist2, slam_stream_t stream);
+/* Registers n_edges edges in one launch and waits for it; out[e] for req[e].  pairs_trace (optional, host): trace_cap ints
+ * per edge, the pairs kept in each iteration (-1 behind the last). */
+int  slam_kf_register_edges(slam_kf_t *s, const slam_kf_edge_req *req, int n_edges, slam_kf_edge_result *out,
+                            slam_stream_t stream);
+int  slam_kf_register_edges_traced(slam_kf_t *s, const slam_kf_edge_req *req, int n_edges, slam_kf_edge_result *out,
+                                   int32_t *pairs_trace, int trace_cap, slam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,25 @@ class MlsParams(C.Structure):
                 ("drive_dist_threshold", C.c_double), ("robot_height", C.c_double)]
 
 
+class KfParams(C.Structure):
+    _fields_ = [("leaf_size", C.c_double), ("gate", C.c_double), ("cell_size", C.c_double), ("max_iterations", C.c_int),
+                ("transformation_epsilon", C.c_double), ("fitness_epsilon", C.c_double), ("target_in_lds", C.c_int)]
+
+
+class KfEdgeReq(C.Structure):
+    _fields_ = [("from_", C.c_int), ("to", C.c_int), ("init", C.c_float * 16)]
+
+
+class KfEdgeResult(C.Structure):
+    _fields_ = [("transform", C.c_float * 16), ("transform64", C.c_double * 16), ("iterations", C.c_int),
+                ("state", C.c_int), ("converged", C.c_int), ("pairs", C.c_int), ("mse", C.c_double),
+                ("information", C.c_double * 36), ("num_corr", C.c_int), ("singular", C.c_int), ("ss", C.c_float),
+                ("reserved", C.c_int)]
+
+
+KF_NOT_CONVERGED, KF_ITERATIONS, KF_TRANSFORM, KF_ABS_MSE, KF_REL_MSE, KF_NO_CORRESPONDENCES = 0, 1, 2, 3, 4, 5
+KF_LATTICE_MARGIN = 1.0 + 2.0 ** -16   # the search lattice's edge is cell_size (or the gate) times this
+
 GSEG_DROPPED, GSEG_GROUND, GSEG_OBSTACLE, GSEG_OVERHEAD = 0, 1, 2, 3
 
 RESULT_DTYPE = np.dtype([("iters", np.int32), ("n_corr", np.int32), ("delta", np.float64)])
@@ -114,6 +133,9 @@ EXPORTS = [
     "slam_mls_default_params", "slam_mls_create", "slam_mls_destroy", "slam_mls_clear", "slam_mls_set_pose",
     "slam_mls_set_params", "slam_mls_add_cloud", "slam_mls_add_cloud_dev", "slam_mls_offset_z",
     "slam_mls_read_drivability", "slam_mls_segmented_clouds", "slam_mls_read_cells", "slam_mls_info",
+    "slam_kf_default_params", "slam_kf_create", "slam_kf_destroy", "slam_kf_set_params", "slam_kf_add_keyframe",
+    "slam_kf_add_keyframe_dev", "slam_kf_keyframe_info", "slam_kf_count", "slam_kf_read_keyframe", "slam_kf_nearest_dev",
+    "slam_kf_register_edges", "slam_kf_register_edges_traced",
 ]
 
 
@@ -285,6 +307,20 @@ def lib():
     L.slam_mls_read_cells.argtypes = [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
     L.slam_mls_info.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int),
                                 C.POINTER(MlsParams), C.POINTER(C.c_int)]
+    L.slam_kf_default_params.argtypes = [C.POINTER(KfParams)]
+    L.slam_kf_default_params.restype = None
+    L.slam_kf_create.argtypes = [C.POINTER(KfParams), C.POINTER(_vp)]
+    L.slam_kf_destroy.argtypes = [_vp]
+    L.slam_kf_destroy.restype = None
+    L.slam_kf_set_params.argtypes = [_vp, C.POINTER(KfParams)]
+    L.slam_kf_add_keyframe.argtypes = [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.slam_kf_add_keyframe_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_int), _vp]
+    L.slam_kf_keyframe_info.argtypes = [_vp, C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_long)]
+    L.slam_kf_count.argtypes = [_vp]
+    L.slam_kf_read_keyframe.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_int)]
+    L.slam_kf_nearest_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]
+    L.slam_kf_register_edges.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
+    L.slam_kf_register_edges_traced.argtypes = [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]
     _lib = L
     return L
 
@@ -797,6 +833,110 @@ def mls_default_params(**kw):
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def kf_default_params(**kw):
+    p = KfParams()
+    lib().slam_kf_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+class KeyframeStore:
+    """graph_slam's keyframes on the device (slam_kf_*): each one voxel-filtered once and indexed by a 3-D lattice; edges
+    (calcEdgeIcp: 3-D point-to-point ICP, then computeEdgeInformationLUM) registered in batches."""
+
+    def __init__(self, params=None, **kw):
+        self.h = None
+        p = params or kf_default_params(**kw)
+        h = _vp()
+        check(lib().slam_kf_create(C.byref(p), C.byref(h)))
+        self.h = h.value
+        self.params = p
+
+    def close(self):
+        if self.h:
+            lib().slam_kf_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return int(lib().slam_kf_count(self.h))
+
+    def set_params(self, **kw):
+        for k, v in kw.items():
+            setattr(self.params, k, v)
+        check(lib().slam_kf_set_params(self.h, C.byref(self.params)))
+
+    def add_keyframe(self, xyz):
+        """[n, >= 3] f32 cloud -> keyframe id."""
+        a = np.ascontiguousarray(xyz, dtype=np.float32)
+        kid = C.c_int(-1)
+        check(lib().slam_kf_add_keyframe(self.h, _ptr(a), len(a), a.shape[1] if a.ndim == 2 else 3, C.byref(kid)))
+        return kid.value
+
+    def add_keyframe_dev(self, d_xyz, n, stride=3, stream=None):
+        kid = C.c_int(-1)
+        check(lib().slam_kf_add_keyframe_dev(self.h, d_xyz.ptr, int(n), int(stride), C.byref(kid), _sp(stream)))
+        return kid.value
+
+    def info(self, kid):
+        v = [C.c_int() for _ in range(4)]
+        b = C.c_long()
+        check(lib().slam_kf_keyframe_info(self.h, int(kid), *[C.byref(x) for x in v], C.byref(b)))
+        return {"n_points": v[0].value, "n_cells": v[1].value, "max_cell_points": v[2].value, "table_slots": v[3].value,
+                "device_bytes": b.value}
+
+    def read_keyframe(self, kid):
+        """The filtered cloud, [n, 4] f32 (x, y, z and the filter's fourth field)."""
+        n = self.info(kid)["n_points"]
+        out = np.zeros((n, 4), np.float32)
+        got = C.c_int(0)
+        check(lib().slam_kf_read_keyframe(self.h, int(kid), _ptr(out), n, C.byref(got)))
+        return out[:got.value]
+
+    def nearest(self, kid, queries, strict=False):
+        """Gated 1-NN of [n, >= 3] f32 queries in keyframe kid: (index or -1, f32 squared distance)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        n = len(q)
+        d_q = DeviceArray.from_host(q)
+        d_i, d_d = DeviceArray((n,), np.int32), DeviceArray((n,), np.float32)
+        check(lib().slam_kf_nearest_dev(self.h, int(kid), d_q.ptr, n, q.shape[1], int(bool(strict)), d_i.ptr, d_d.ptr, None))
+        synchronize()
+        return d_i.download(), d_d.download()
+
+    def register_edges(self, edges, trace=0, stream=None):
+        """edges: [(from, to, init 4x4), ...] -> list of dicts (one per edge; 'pairs_trace' when trace > 0)."""
+        n = len(edges)
+        req = (KfEdgeReq * max(n, 1))()
+        for e, (f, t, init) in enumerate(edges):
+            req[e].from_, req[e].to = int(f), int(t)
+            req[e].init[:] = np.asarray(init, dtype=np.float32).reshape(16).tolist()
+        res = (KfEdgeResult * max(n, 1))()
+        tr = np.full((max(n, 1), max(trace, 1)), -1, np.int32)
+        if trace > 0:
+            check(lib().slam_kf_register_edges_traced(self.h, C.addressof(req), n, C.addressof(res), _ptr(tr), int(trace), _sp(stream)))
+        else:
+            check(lib().slam_kf_register_edges(self.h, C.addressof(req), n, C.addressof(res), _sp(stream)))
+        out = [kf_result_dict(res[e]) for e in range(n)]
+        if trace > 0:
+            for e in range(n):
+                out[e]["pairs_trace"] = tr[e].copy()
+        return out
+
+
+def kf_result_dict(r):
+    return {"transform": np.array(r.transform[:], np.float32).reshape(4, 4),
+            "transform64": np.array(r.transform64[:], np.float64).reshape(4, 4), "iterations": r.iterations, "state": r.state,
+            "converged": r.converged, "pairs": r.pairs, "mse": r.mse,
+            "information": np.array(r.information[:], np.float64).reshape(6, 6), "num_corr": r.num_corr,
+            "singular": r.singular, "ss": np.float32(r.ss)}
 
 
 class MlsMap:

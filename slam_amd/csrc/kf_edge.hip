@@ -1,0 +1,857 @@
+// kf_edge.hip -- graph_slam's keyframe edges on gfx950 (docs/KF_EDGE.md):
+//   keyframe store                    graphSlamTools.cpp:278-286  pcl::VoxelGrid(0.5) once per keyframe + a 3-D search lattice
+//   pcl::IterativeClosestPoint        :27-39, :294-296            3-D point to point, Umeyama step, PCL's stop rules
+//   computeEdgeInformationLUM         :108-214                    on the f32 final transform, in the same launch
+//
+// A keyframe's filtered cloud is sorted by lattice cell (edge >= the gate, so the gated nearest neighbour is among the 27
+// cells around a query); an open-addressing hash table of 2 n slots maps a cell key to its run of sorted points, so a
+// keyframe holds O(points) bytes whatever its extent.  One workgroup registers one edge: all iterations, the 3 x 3 SVD,
+// the stop rules and the LUM pass run inside one launch.  Sums are f64 (ss: f32, as the reference has it), reduced in a
+// fixed order -- lanes by shuffle, waves in wave order through LDS -- so a result is the same bits on every run and
+// whatever else is in the batch.
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include <rocprim/rocprim.hpp>
+
+#include "common.hpp"
+
+using namespace slam;
+
+namespace {
+
+constexpr int                kHalf = 1 << 20; // 21 bits of cell coordinate per axis
+constexpr unsigned long long kEmpty = ~0ull;
+constexpr int                kEdgeThreads = 512;
+constexpr int                kWaves = kEdgeThreads / 64;
+constexpr double             kLatticeMargin = 1.0 + 1.0 / 65536.0;
+constexpr int                kLdsPoints = 6144; // 96 KB of the CU's 160 KB: a make_cloud3d keyframe filtered at 0.5 m has up to 5 931
+
+struct KfView {
+    const float4 *pts;    // the filtered cloud, as the voxel filter wrote it
+    const float4 *sorted; // the same points by cell key; w = the point's index in `pts` (bits)
+    const int4   *table;  // x, y = cell key (low, high), z = first sorted point, w = points; key ~0 = empty
+    unsigned      mask;   // slots - 1
+    int           n;
+};
+
+struct EdgeTask {
+    KfView   src, tgt;
+    int32_t *corr; // src.n ints: the sorted slot of each source point's partner, -1 = none
+    float    init[16];
+};
+
+struct EdgeParams {
+    double inv_cell, gate2, eps_t, eps_f;
+    int    max_iter;
+};
+
+__host__ __device__ inline int cell_coord(float v, double inv)
+{
+    double c = floor((double)v * inv);
+    if (!(c >= -(double)kHalf)) c = -(double)kHalf; // also NaN
+    if (c > (double)(kHalf - 1)) c = (double)(kHalf - 1);
+    return (int)c + kHalf;
+}
+__host__ __device__ inline unsigned long long cell_key(int cx, int cy, int cz)
+{
+    return ((unsigned long long)cz << 42) | ((unsigned long long)cy << 21) | (unsigned long long)cx;
+}
+__device__ inline unsigned slot_of(unsigned long long key, unsigned mask)
+{
+    return (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask;
+}
+
+// The nearest point among the 27 cells around q: its index in the filtered cloud (lowest on an exact tie) or -1, the f32
+// squared distance dx dx + dy dy + dz dz summed in that order without FMA, and the sorted slot it sits in.  The query's own
+// cell goes first; a neighbouring cell is looked up only if the slab between it and the query is no wider than the best
+// distance so far and than the gate (a point beyond the gate is dropped by both callers).  The slab width is a lower bound
+// of the distance to every point of that cell, taken in double; the 2^-20 of slack is above the 3 ulp of the f32 sum, so no
+// point that could win or tie is skipped and the result is that of the full search (tests hold it against brute force).
+constexpr double kPruneSlack = 1.0 + 1.0 / 1048576.0;
+
+__device__ inline int nearest27(const KfView &t, double inv, double gate2, float qx, float qy, float qz, float *d2, int *slot)
+{
+    const float  q[3] = {qx, qy, qz};
+    const double cell = 1.0 / inv;
+    int          c[3];
+    double       lo[3], hi[3]; // distance to the lower and upper face of the query's cell
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double u = (double)q[k] * inv, f = floor(u);
+        c[k] = cell_coord(q[k], inv);
+        const bool inside = (double)(c[k] - kHalf) == f; // not clamped, not NaN
+        lo[k] = inside ? (u - f) * cell : 0.0;
+        hi[k] = inside ? ((f + 1.0) - u) * cell : 0.0;
+    }
+    int   best = -1, bslot = -1;
+    float bd = 0.0f;
+    auto  visit = [&](int x, int y, int z) {
+        if ((x | y | z) < 0 || x >= 2 * kHalf || y >= 2 * kHalf || z >= 2 * kHalf) return;
+        const unsigned long long key = cell_key(x, y, z);
+        unsigned                 h = slot_of(key, t.mask);
+        int                      start = 0, count = 0;
+        for (;;) { // at most half the slots are taken: the probe ends
+            const int4               s = t.table[h];
+            const unsigned long long k = ((unsigned long long)(unsigned)s.y << 32) | (unsigned)s.x;
+            if (k == key) {
+                start = s.z, count = s.w;
+                break;
+            }
+            if (k == kEmpty) break;
+            h = (h + 1) & t.mask;
+        }
+        for (int j = start; j < start + count; ++j) {
+            const float4 p = t.sorted[j];
+            const float  dx = __fsub_rn(qx, p.x), dy = __fsub_rn(qy, p.y), dz = __fsub_rn(qz, p.z);
+            const float  d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+            const int    idx = __float_as_int(p.w);
+            if (best < 0 || d < bd || (d == bd && idx < best)) best = idx, bd = d, bslot = j;
+        }
+    };
+    visit(c[0], c[1], c[2]);
+    const double gate_bound = gate2 * kPruneSlack;
+    for (int oz = -1; oz <= 1; ++oz) {
+        const double mz = oz < 0 ? lo[2] : oz > 0 ? hi[2] : 0.0;
+        for (int oy = -1; oy <= 1; ++oy) {
+            const double my = oy < 0 ? lo[1] : oy > 0 ? hi[1] : 0.0;
+            for (int ox = -1; ox <= 1; ++ox) {
+                if (!(ox | oy | oz)) continue;
+                const double mx = ox < 0 ? lo[0] : ox > 0 ? hi[0] : 0.0;
+                const double m2 = (mx * mx + my * my) + mz * mz;
+                if (m2 > gate_bound || (best >= 0 && m2 > (double)bd * kPruneSlack)) continue;
+                visit(c[0] + ox, c[1] + oy, c[2] + oz);
+            }
+        }
+    }
+    *d2 = bd;
+    *slot = bslot;
+    return best;
+}
+
+// ---------------------------------------------------------------- lattice build
+__global__ __launch_bounds__(256) void kf_key_kernel(const float4 *pts, int n, double inv, unsigned long long *keys, uint32_t *vals)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = pts[i];
+    keys[i] = cell_key(cell_coord(p.x, inv), cell_coord(p.y, inv), cell_coord(p.z, inv));
+    vals[i] = (uint32_t)i;
+}
+
+// sorted points, and one table entry per run of equal keys; stats[0] = cells, stats[1] = largest cell
+__global__ __launch_bounds__(256) void kf_table_kernel(const float4 *pts, const unsigned long long *keys, const uint32_t *vals, int n,
+                                                       float4 *sorted, int4 *table, unsigned mask, int *stats)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t src = vals[i];
+    float4         p = pts[src];
+    p.w = __int_as_float((int)src);
+    sorted[i] = p;
+    const unsigned long long key = keys[i];
+    if (i > 0 && keys[i - 1] == key) return;
+    int count = 1;
+    while (i + count < n && keys[i + count] == key) ++count;
+    unsigned h = slot_of(key, mask);
+    for (;;) { // keys are distinct here: a slot is claimed once
+        unsigned long long *kp = reinterpret_cast<unsigned long long *>(&table[h]);
+        if (atomicCAS(kp, kEmpty, key) == kEmpty) {
+            table[h].z = i;
+            table[h].w = count;
+            break;
+        }
+        h = (h + 1) & mask;
+    }
+    atomicAdd(&stats[0], 1);
+    atomicMax(&stats[1], count);
+}
+
+__global__ __launch_bounds__(256) void kf_nearest_kernel(KfView t, double inv, double gate2, int strict, const float *q, int n, int stride,
+                                                         int32_t *index, float *dist2)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float *p = q + (size_t)i * stride;
+    float        d2;
+    int          slot;
+    const int    j = nearest27(t, inv, gate2, p[0], p[1], p[2], &d2, &slot);
+    const bool   keep = j >= 0 && (strict ? (double)d2 < gate2 : (double)d2 <= gate2);
+    index[i] = keep ? j : -1;
+    dist2[i] = keep ? d2 : 0.0f;
+}
+
+// ---------------------------------------------------------------- the 3 x 3 solve (one lane, f64)
+// Every loop below has constant bounds and is unrolled, so that the small matrices stay in registers: indexed by a
+// run-time value they would live in scratch memory, and one lane's trips there were most of an iteration.
+__device__ inline void swap_columns(double a[9], double v[9], double s[3], int i, int j)
+{
+    double x = s[i];
+    s[i] = s[j], s[j] = x;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        x = a[3 * r + i], a[3 * r + i] = a[3 * r + j], a[3 * r + j] = x;
+        x = v[3 * r + i], v[3 * r + i] = v[3 * r + j], v[3 * r + j] = x;
+    }
+}
+
+// One-sided Jacobi SVD: A = U diag(s) V', s descending; columns of U for vanishing singular values completed to a
+// right-handed frame.  Returns the rank (singular values above 3 eps of the largest).
+__device__ int svd3(const double A[9], double U[9], double s[3], double V[9])
+{
+    const double eps = DBL_EPSILON;
+    double       a[9], v[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) a[i] = A[i], v[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        bool rotated = false;
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 3; ++q) {
+                double al = 0, be = 0, ga = 0;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    al += a[3 * i + p] * a[3 * i + p];
+                    be += a[3 * i + q] * a[3 * i + q];
+                    ga += a[3 * i + p] * a[3 * i + q];
+                }
+                if (ga == 0.0 || fabs(ga) <= eps * sqrt(al * be)) continue;
+                rotated = true;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const double ap = a[3 * i + p], aq = a[3 * i + q];
+                    a[3 * i + p] = c * ap - sn * aq;
+                    a[3 * i + q] = sn * ap + c * aq;
+                    const double vp = v[3 * i + p], vq = v[3 * i + q];
+                    v[3 * i + p] = c * vp - sn * vq;
+                    v[3 * i + q] = sn * vp + c * vq;
+                }
+            }
+        if (!rotated) break;
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) s[j] = sqrt(a[j] * a[j] + a[3 + j] * a[3 + j] + a[6 + j] * a[6 + j]);
+    // descending, stable: the selection sort of the restatement as three compare-and-swaps
+    if (s[1] > s[0]) swap_columns(a, v, s, 0, 1);
+    if (s[2] > s[0]) swap_columns(a, v, s, 0, 2);
+    if (s[2] > s[1]) swap_columns(a, v, s, 1, 2);
+    int rank = 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+        if (s[j] > 0.0 && s[j] > 3.0 * eps * s[0]) ++rank;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+        if (j < rank) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) a[3 * i + j] /= s[j];
+        }
+    if (rank == 0) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) a[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    } else {
+        if (rank == 1) { // any unit vector orthogonal to u0: u0 x e_k, e_k the axis u0 leans on least
+            int    k = 0;
+            double m = fabs(a[0]);
+            if (fabs(a[3]) < m) k = 1, m = fabs(a[3]);
+            if (fabs(a[6]) < m) k = 2;
+            const double e[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};
+            const double w[3] = {a[3] * e[2] - a[6] * e[1], a[6] * e[0] - a[0] * e[2], a[0] * e[1] - a[3] * e[0]};
+            const double nw = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+            a[1] = w[0] / nw, a[4] = w[1] / nw, a[7] = w[2] / nw;
+        }
+        if (rank <= 2) { // u2 = u0 x u1
+            a[2] = a[3] * a[7] - a[6] * a[4];
+            a[5] = a[6] * a[1] - a[0] * a[7];
+            a[8] = a[0] * a[4] - a[3] * a[1];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) U[i] = a[i], V[i] = v[i];
+    return rank;
+}
+
+__device__ inline double det3(const double m[9])
+{
+    return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
+}
+
+// Umeyama without scaling from H = sum (q - qm)(p - pm)' / n: R = U diag(1, 1, +-1) V', t = qm - R pm.  Full rank: the sign
+// of det H; a rank-deficient H (planar, collinear pairs): that of det U det V, so that R is always a proper rotation.
+__device__ void umeyama(const double H[9], const double pm[3], const double qm[3], double R[9], double t[3])
+{
+    double    U[9], s[3], V[9];
+    const int rank = svd3(H, U, s, V);
+    double    sign;
+    if (rank == 3)
+        sign = det3(H) < 0.0 ? -1.0 : 1.0;
+    else
+        sign = det3(U) * det3(V) > 0.0 ? 1.0 : -1.0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) R[3 * r + c] = (U[3 * r] * V[3 * c] + U[3 * r + 1] * V[3 * c + 1]) + sign * U[3 * r + 2] * V[3 * c + 2];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) t[r] = qm[r] - ((R[3 * r] * pm[0] + R[3 * r + 1] * pm[1]) + R[3 * r + 2] * pm[2]);
+}
+
+// The inverse of a 6 x 6 by LU with partial pivoting (what Eigen's inverse() of a fixed 6 x 6 goes through).  A vanishing
+// pivot divides by zero; the non-finite entries travel on to ss, where the test of :203 catches them.  Unrolled like the
+// solve above: the pivot row is found by value and swapped in by a chain of conditional swaps.
+__device__ void inverse6(const double A[36], double X[36])
+{
+    double a[36];
+    int    piv[6];
+#pragma unroll
+    for (int i = 0; i < 36; ++i) a[i] = A[i];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) piv[i] = i;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        int    m = k;
+        double big = fabs(a[6 * k + k]);
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i)
+            if (fabs(a[6 * i + k]) > big) big = fabs(a[6 * i + k]), m = i;
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i)
+            if (i == m) {
+#pragma unroll
+                for (int c = 0; c < 6; ++c) {
+                    const double x = a[6 * k + c];
+                    a[6 * k + c] = a[6 * i + c], a[6 * i + c] = x;
+                }
+                const int x = piv[k];
+                piv[k] = piv[i], piv[i] = x;
+            }
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i) {
+            a[6 * i + k] /= a[6 * k + k];
+#pragma unroll
+            for (int c = k + 1; c < 6; ++c) a[6 * i + c] -= a[6 * i + k] * a[6 * k + c];
+        }
+    }
+#pragma unroll
+    for (int col = 0; col < 6; ++col) {
+        double y[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            y[i] = piv[i] == col ? 1.0 : 0.0;
+#pragma unroll
+            for (int c = 0; c < i; ++c) y[i] -= a[6 * i + c] * y[c];
+        }
+#pragma unroll
+        for (int i = 5; i >= 0; --i) {
+#pragma unroll
+            for (int c = i + 1; c < 6; ++c) y[i] -= a[6 * i + c] * y[c];
+            y[i] /= a[6 * i + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) X[6 * i + col] = y[i];
+    }
+}
+
+// ---------------------------------------------------------------- reductions in a fixed order
+template <typename T, int K>
+__device__ inline void block_sum(T (&v)[K], T (*red)[16], T *tot)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        T x = v[k];
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+        if (lane == 0) red[wave][k] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        T s = red[0][threadIdx.x];
+        for (int w = 1; w < kWaves; ++w) s += red[w][threadIdx.x];
+        tot[threadIdx.x] = s;
+    }
+    __syncthreads();
+}
+
+// the source point moved by the total transform: in double, rounded to f32 once
+__device__ inline void move_f64(const double T[12], const float4 p, float m[3])
+{
+#pragma unroll
+    for (int r = 0; r < 3; ++r) m[r] = (float)(((T[4 * r] * (double)p.x + T[4 * r + 1] * (double)p.y) + T[4 * r + 2] * (double)p.z) + T[4 * r + 3]);
+}
+// pcl::transformPointCloud with a Matrix4f: in float, left to right
+__device__ inline void move_f32(const float M[12], const float4 p, float m[3])
+{
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        m[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(M[4 * r], p.x), __fmul_rn(M[4 * r + 1], p.y)), __fmul_rn(M[4 * r + 2], p.z)), M[4 * r + 3]);
+}
+
+// ---------------------------------------------------------------- one workgroup per edge
+__global__ __launch_bounds__(kEdgeThreads) void kf_edge_kernel(const EdgeTask *tasks, EdgeParams P, slam_kf_edge_result *results, int32_t *trace,
+                                                               int trace_cap, int lds_points)
+{
+    extern __shared__ float4 lds_sorted[]; // room for lds_points of the target's sorted points
+    __shared__ double sT[12];
+    __shared__ float  sTf[12];
+    __shared__ double sD[6];
+    __shared__ double red[kWaves][16];
+    __shared__ double tot[16];
+    __shared__ float  redf[kWaves][16];
+    __shared__ float  totf[16];
+    __shared__ int    sState;
+    __shared__ double sMM[36]; // thread 0's, from the solve to the final scaling
+
+    const EdgeTask      &task = tasks[blockIdx.x];
+    const KfView         src = task.src;
+    KfView               tgt = task.tgt;
+    int32_t             *corr = task.corr;
+    slam_kf_edge_result *out = results + blockIdx.x;
+    const int            tid = threadIdx.x;
+
+    // A target that fits is staged in LDS once per edge: every iteration's searches then read its points there and only the
+    // table through L2.  One that does not fit is read through L2 as it lies.
+    if (tgt.n <= lds_points) {
+        for (int i = tid; i < tgt.n; i += kEdgeThreads) lds_sorted[i] = tgt.sorted[i];
+        tgt.sorted = lds_sorted;
+    }
+    if (tid < 12) sT[tid] = (double)task.init[tid];
+    if (tid == 0) sState = 0;
+    if (trace)
+        for (int i = tid; i < trace_cap; i += kEdgeThreads) trace[(size_t)blockIdx.x * trace_cap + i] = -1;
+    int    iterations = 0, pairs = 0; // thread 0's are the ones that count
+    double mse = 0.0, mse_prev = DBL_MAX;
+    for (;;) {
+        __syncthreads();
+        double T[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) T[k] = sT[k];
+        // correspondences, the centroids' sums and the squared distances
+        double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int i = tid; i < src.n; i += kEdgeThreads) {
+            float m[3], d2;
+            int   slot;
+            move_f64(T, src.pts[i], m);
+            const int  j = nearest27(tgt, P.inv_cell, P.gate2, m[0], m[1], m[2], &d2, &slot);
+            const bool keep = j >= 0 && (double)d2 <= P.gate2; // PCL skips on >
+            corr[i] = keep ? slot : -1;
+            if (keep) {
+                const float4 q = tgt.sorted[slot];
+                acc[0] += 1.0;
+                acc[1] += (double)m[0], acc[2] += (double)m[1], acc[3] += (double)m[2];
+                acc[4] += (double)q.x, acc[5] += (double)q.y, acc[6] += (double)q.z;
+                acc[7] += (double)d2;
+            }
+        }
+        block_sum<double, 8>(acc, red, tot);
+        const double n = tot[0];
+        pairs = (int)n;
+        mse = pairs ? tot[7] / n : 0.0;
+        if (tid == 0 && trace && iterations < trace_cap) trace[(size_t)blockIdx.x * trace_cap + iterations] = pairs;
+        if (pairs < 3) { // uniform: every thread reads the same total
+            if (tid == 0) sState = SLAM_KF_NO_CORRESPONDENCES;
+            break;
+        }
+        const double pm[3] = {tot[1] / n, tot[2] / n, tot[3] / n}, qm[3] = {tot[4] / n, tot[5] / n, tot[6] / n};
+        double       h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (int i = tid; i < src.n; i += kEdgeThreads) {
+            const int slot = corr[i];
+            if (slot < 0) continue;
+            float m[3];
+            move_f64(T, src.pts[i], m);
+            const float4 q = tgt.sorted[slot];
+            const double dq[3] = {(double)q.x - qm[0], (double)q.y - qm[1], (double)q.z - qm[2]};
+            const double dp[3] = {(double)m[0] - pm[0], (double)m[1] - pm[1], (double)m[2] - pm[2]};
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) h[3 * r + c] += dq[r] * dp[c];
+        }
+        block_sum<double, 9>(h, red, tot);
+        if (tid == 0) {
+            double H[9], R[9], t[3], N[12];
+            for (int k = 0; k < 9; ++k) H[k] = tot[k] / n;
+            umeyama(H, pm, qm, R, t);
+            for (int r = 0; r < 3; ++r) { // total <- step . total
+                for (int c = 0; c < 3; ++c) N[4 * r + c] = (R[3 * r] * T[c] + R[3 * r + 1] * T[4 + c]) + R[3 * r + 2] * T[8 + c];
+                N[4 * r + 3] = ((R[3 * r] * T[3] + R[3 * r + 1] * T[7]) + R[3 * r + 2] * T[11]) + t[r];
+            }
+            for (int k = 0; k < 12; ++k) sT[k] = N[k];
+            ++iterations;
+            // DefaultConvergenceCriteria, in the order of docs/KF_EDGE.md
+            int state = 0;
+            if (iterations >= P.max_iter)
+                state = SLAM_KF_ITERATIONS;
+            else {
+                const double cosa = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
+                const double tt = (t[0] * t[0] + t[1] * t[1]) + t[2] * t[2];
+                const double d = fabs(mse - mse_prev);
+                if (cosa >= 1.0 - P.eps_t && tt <= P.eps_t)
+                    state = SLAM_KF_TRANSFORM;
+                else if (d < 1e-12)
+                    state = SLAM_KF_ABS_MSE;
+                else if (d / mse_prev < P.eps_f)
+                    state = SLAM_KF_REL_MSE;
+                else
+                    mse_prev = mse;
+            }
+            sState = state;
+        }
+        __syncthreads();
+        if (sState) break;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 0; k < 12; ++k) {
+            out->transform64[k] = sT[k];
+            out->transform[k] = sTf[k] = (float)sT[k];
+        }
+        for (int k = 12; k < 16; ++k) out->transform64[k] = k == 15 ? 1.0 : 0.0, out->transform[k] = k == 15 ? 1.0f : 0.0f;
+        out->iterations = iterations, out->state = sState, out->converged = sState != SLAM_KF_NO_CORRESPONDENCES;
+        out->pairs = pairs, out->mse = mse, out->reserved = 0;
+    }
+    __syncthreads();
+
+    // computeEdgeInformationLUM on the f32 transform (:108-214)
+    float M[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) M[k] = sTf[k];
+    double a16[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = tid; i < src.n; i += kEdgeThreads) {
+        float s[3], d2;
+        int   slot;
+        move_f32(M, src.pts[i], s);
+        const int  j = nearest27(tgt, P.inv_cell, P.gate2, s[0], s[1], s[2], &d2, &slot);
+        const bool keep = j >= 0 && (double)d2 < P.gate2; // :132, strict
+        corr[i] = keep ? slot : -1;
+        if (!keep) continue;
+        const float4 q = tgt.sorted[slot];
+        const float  a0 = __fmul_rn(0.5f, __fadd_rn(s[0], q.x)), a1 = __fmul_rn(0.5f, __fadd_rn(s[1], q.y)), a2 = __fmul_rn(0.5f, __fadd_rn(s[2], q.z));
+        const float  d0 = __fsub_rn(s[0], q.x), d1 = __fsub_rn(s[1], q.y), d2f = __fsub_rn(s[2], q.z);
+        a16[0] += 1.0;
+        a16[1] += (double)a0, a16[2] += (double)a1, a16[3] += (double)a2; // :155-160, up to sign
+        a16[4] += (double)__fmul_rn(a0, a2);                              // -(3,4)
+        a16[5] += (double)__fmul_rn(a0, a1);                              // -(3,5)
+        a16[6] += (double)__fmul_rn(a1, a2);                              // -(4,5)
+        a16[7] += (double)__fadd_rn(__fmul_rn(a1, a1), __fmul_rn(a2, a2));
+        a16[8] += (double)__fadd_rn(__fmul_rn(a0, a0), __fmul_rn(a1, a1));
+        a16[9] += (double)__fadd_rn(__fmul_rn(a0, a0), __fmul_rn(a2, a2));
+        a16[10] += (double)d0, a16[11] += (double)d1, a16[12] += (double)d2f;
+        a16[13] += (double)__fsub_rn(__fmul_rn(a1, d2f), __fmul_rn(a2, d1));
+        a16[14] += (double)__fsub_rn(__fmul_rn(a0, d1), __fmul_rn(a1, d0));
+        a16[15] += (double)__fsub_rn(__fmul_rn(a2, d0), __fmul_rn(a0, d2f));
+    }
+    block_sum<double, 16>(a16, red, tot);
+    if (tid == 0) {
+        double MM[36];
+        for (int k = 0; k < 36; ++k) MM[k] = 0.0;
+#define MMAT(r, c) MM[6 * (r) + (c)]
+        MMAT(0, 4) = -tot[2], MMAT(0, 5) = tot[3], MMAT(1, 3) = -tot[3], MMAT(1, 4) = tot[1], MMAT(2, 3) = tot[2], MMAT(2, 5) = -tot[1];
+        MMAT(3, 4) = -tot[4], MMAT(3, 5) = -tot[5], MMAT(4, 5) = -tot[6];
+        MMAT(3, 3) = tot[7], MMAT(4, 4) = tot[8], MMAT(5, 5) = tot[9];
+        MMAT(0, 0) = MMAT(1, 1) = MMAT(2, 2) = (double)(float)(int)tot[0];
+        MMAT(4, 0) = MMAT(0, 4), MMAT(5, 0) = MMAT(0, 5), MMAT(3, 1) = MMAT(1, 3), MMAT(4, 1) = MMAT(1, 4), MMAT(3, 2) = MMAT(2, 3);
+        MMAT(5, 2) = MMAT(2, 5), MMAT(4, 3) = MMAT(3, 4), MMAT(5, 3) = MMAT(3, 5), MMAT(5, 4) = MMAT(4, 5);
+#undef MMAT
+        double inv[36];
+        inverse6(MM, inv);
+        for (int k = 0; k < 36; ++k) sMM[k] = MM[k];
+        for (int r = 0; r < 6; ++r) {
+            double d = 0.0;
+            for (int c = 0; c < 6; ++c) d += inv[6 * r + c] * tot[10 + c];
+            sD[r] = d;
+        }
+    }
+    __syncthreads();
+    double D[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) D[k] = sD[k];
+    float ssv[1] = {0.0f};
+    for (int i = tid; i < src.n; i += kEdgeThreads) {
+        const int slot = corr[i];
+        if (slot < 0) continue;
+        float s[3];
+        move_f32(M, src.pts[i], s);
+        const float4 q = tgt.sorted[slot];
+        const float  a0 = __fmul_rn(0.5f, __fadd_rn(s[0], q.x)), a1 = __fmul_rn(0.5f, __fadd_rn(s[1], q.y)), a2 = __fmul_rn(0.5f, __fadd_rn(s[2], q.z));
+        const float  d0 = __fsub_rn(s[0], q.x), d1 = __fsub_rn(s[1], q.y), d2f = __fsub_rn(s[2], q.z);
+        const double e0 = (double)d0 - ((D[0] + (double)a2 * D[5]) - (double)a1 * D[4]); // :197-199 as written
+        const double e1 = (double)d1 - ((D[1] + (double)a0 * D[4]) - (double)a2 * D[3]);
+        const double e2 = (double)d2f - ((D[2] + (double)a1 * D[3]) - (double)a0 * D[5]);
+        ssv[0] = __fadd_rn(ssv[0], (float)((e0 * e0 + e1 * e1) + e2 * e2));
+    }
+    block_sum<float, 1>(ssv, redf, totf);
+    if (tid == 0) {
+        const float ss = totf[0];
+        const bool  singular = ss < 0.0000000000001 || !isfinite(ss); // :203
+        const float w = 1.0f / ss;                                    // :211
+        for (int k = 0; k < 36; ++k) out->information[k] = singular ? (k % 7 == 0 ? 1.0 : 0.0) : sMM[k] * (double)w;
+        out->num_corr = (int)tot[0], out->singular = singular ? 1 : 0, out->ss = ss;
+    }
+}
+
+struct GrowBuf {
+    void  *p = nullptr;
+    size_t cap = 0;
+    int    reserve(size_t bytes)
+    {
+        if (bytes <= cap) return SLAM_OK;
+        if (p) (void)hipFree(p);
+        p = nullptr, cap = 0;
+        SLAM_HIP(hipMalloc(&p, bytes + bytes / 4));
+        cap = bytes + bytes / 4;
+        return SLAM_OK;
+    }
+    ~GrowBuf()
+    {
+        if (p) (void)hipFree(p);
+    }
+};
+
+struct Keyframe {
+    void  *block = nullptr; // pts | sorted | table
+    KfView view{};
+    int    n_cells = 0, max_cell = 0;
+    size_t bytes = 0;
+};
+
+} // namespace
+
+struct slam_kf {
+    slam_kf_params        p;
+    slam_ccicp_t         *cc = nullptr;
+    std::vector<Keyframe> kfs;
+    bool                  lds_enabled = false;
+    GrowBuf               in, filtered, keys, sort_tmp, work, stats; // add_keyframe's; `work` also holds a call's tasks, results, pairs
+    ~slam_kf()
+    {
+        for (Keyframe &k : kfs)
+            if (k.block) (void)hipFree(k.block);
+        slam_ccicp_destroy(cc);
+    }
+};
+
+namespace {
+
+int check_params(const slam_kf_params *p)
+{
+    SLAM_REQUIRE(p->leaf_size > 0 && p->gate > 0 && p->max_iterations >= 1 && (p->cell_size == 0 || p->cell_size >= p->gate), SLAM_E_INVALID,
+                 "slam_kf: leaf_size and gate must be positive, max_iterations >= 1, cell_size 0 or >= gate");
+    return SLAM_OK;
+}
+double inv_cell(const slam_kf_params &p) { return 1.0 / ((p.cell_size > 0 ? p.cell_size : p.gate) * kLatticeMargin); }
+unsigned blocks(size_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+} // namespace
+
+extern "C" {
+
+void slam_kf_default_params(slam_kf_params *p)
+{
+    if (!p) return;
+    p->leaf_size = 0.5;               // graphSlamTools.cpp:281
+    p->gate = 0.75;                   // :29
+    p->cell_size = 0.0;
+    p->max_iterations = 200;          // :31
+    p->transformation_epsilon = 1e-6; // :33
+    p->fitness_epsilon = 1e-6;        // :35
+    p->target_in_lds = 1;
+}
+
+int slam_kf_create(const slam_kf_params *params, slam_kf_t **out)
+{
+    SLAM_REQUIRE(out, SLAM_E_INVALID, "slam_kf_create: null out pointer");
+    *out = nullptr;
+    slam_kf_params p;
+    slam_kf_default_params(&p);
+    if (params) p = *params;
+    SLAM_TRY(check_params(&p));
+    SLAM_TRY(require_device());
+    slam_kf *s = new (std::nothrow) slam_kf();
+    SLAM_REQUIRE(s, SLAM_E_NOMEM, "slam_kf_create: out of host memory");
+    s->p = p;
+    int rc = slam_ccicp_create(&s->cc);
+    if (rc == SLAM_OK) rc = s->stats.reserve(64);
+    if (rc != SLAM_OK) {
+        delete s;
+        return rc;
+    }
+    *out = s;
+    return SLAM_OK;
+}
+
+void slam_kf_destroy(slam_kf_t *s) { delete s; }
+
+int slam_kf_set_params(slam_kf_t *s, const slam_kf_params *params)
+{
+    SLAM_REQUIRE(s && params, SLAM_E_INVALID, "slam_kf_set_params: null argument");
+    SLAM_TRY(check_params(params));
+    SLAM_REQUIRE(s->kfs.empty() || (params->leaf_size == s->p.leaf_size && params->gate == s->p.gate && params->cell_size == s->p.cell_size),
+                 SLAM_E_INVALID, "slam_kf_set_params: leaf_size, gate and cell_size are fixed once the store holds a keyframe");
+    s->p = *params;
+    return SLAM_OK;
+}
+
+int slam_kf_count(slam_kf_t *s) { return s ? (int)s->kfs.size() : 0; }
+
+int slam_kf_add_keyframe_dev(slam_kf_t *s, const float *d_xyz, int n, int stride, int *id, slam_stream_t stream)
+{
+    SLAM_REQUIRE(s && id && n > 0 && stride >= 3 && d_xyz, SLAM_E_INVALID, "slam_kf_add_keyframe_dev: bad arguments");
+    *id = -1;
+    hipStream_t st = as_stream(stream);
+    SLAM_TRY(s->filtered.reserve(sizeof(float4) * (size_t)n));
+    int         m = 0;
+    const float leaf = (float)s->p.leaf_size;
+    SLAM_TRY(slam_ccicp_voxel_downsample_dev(s->cc, d_xyz, nullptr, n, stride, leaf, leaf, leaf, static_cast<float *>(s->filtered.p), n, &m, stream));
+    SLAM_REQUIRE(m > 0, SLAM_E_INVALID, "slam_kf_add_keyframe: the cloud has no finite point");
+    unsigned slots = 64;
+    while (slots < 2u * (unsigned)m) slots <<= 1;
+    Keyframe kf;
+    kf.bytes = sizeof(float4) * 2 * (size_t)m + sizeof(int4) * (size_t)slots;
+    SLAM_HIP(hipMalloc(&kf.block, kf.bytes));
+    float4 *pts = static_cast<float4 *>(kf.block), *sorted = pts + m;
+    int4   *table = reinterpret_cast<int4 *>(sorted + m);
+    kf.view = KfView{pts, sorted, table, slots - 1, m};
+    int rc = s->keys.reserve((sizeof(unsigned long long) + sizeof(uint32_t)) * 2 * (size_t)m);
+    unsigned long long *keys = static_cast<unsigned long long *>(s->keys.p), *keys_s = keys + m;
+    uint32_t           *vals = reinterpret_cast<uint32_t *>(keys_s + m), *vals_s = vals + m;
+    size_t              tb = 0;
+    hipError_t          e = hipSuccess;
+    if (rc == SLAM_OK) {
+        e = rocprim::radix_sort_pairs(nullptr, tb, keys, keys_s, vals, vals_s, (size_t)m, 0, 63, st);
+        if (e == hipSuccess) rc = s->sort_tmp.reserve(tb + 16);
+    }
+    int *stats = static_cast<int *>(s->stats.p);
+    int  got[2] = {0, 0};
+    if (rc == SLAM_OK && e == hipSuccess) e = hipMemcpyAsync(pts, s->filtered.p, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, st);
+    if (rc == SLAM_OK && e == hipSuccess) e = hipMemsetAsync(table, 0xff, sizeof(int4) * (size_t)slots, st);
+    if (rc == SLAM_OK && e == hipSuccess) e = hipMemsetAsync(stats, 0, 2 * sizeof(int), st);
+    if (rc == SLAM_OK && e == hipSuccess) {
+        hipLaunchKernelGGL(kf_key_kernel, dim3(blocks(m, 256)), dim3(256), 0, st, pts, m, inv_cell(s->p), keys, vals);
+        e = hipGetLastError();
+    }
+    if (rc == SLAM_OK && e == hipSuccess) e = rocprim::radix_sort_pairs(s->sort_tmp.p, tb, keys, keys_s, vals, vals_s, (size_t)m, 0, 63, st);
+    if (rc == SLAM_OK && e == hipSuccess) {
+        hipLaunchKernelGGL(kf_table_kernel, dim3(blocks(m, 256)), dim3(256), 0, st, pts, keys_s, vals_s, m, sorted, table, slots - 1, stats);
+        e = hipGetLastError();
+    }
+    if (rc == SLAM_OK && e == hipSuccess) e = hipMemcpyAsync(got, stats, sizeof got, hipMemcpyDeviceToHost, st);
+    if (rc == SLAM_OK && e == hipSuccess) e = hipStreamSynchronize(st);
+    if (rc != SLAM_OK || e != hipSuccess) {
+        (void)hipFree(kf.block);
+        return rc != SLAM_OK ? rc : hip_fail(e, "slam_kf_add_keyframe_dev", __FILE__, __LINE__);
+    }
+    kf.n_cells = got[0], kf.max_cell = got[1];
+    s->kfs.push_back(kf);
+    *id = (int)s->kfs.size() - 1;
+    return SLAM_OK;
+}
+
+int slam_kf_add_keyframe(slam_kf_t *s, const float *xyz, int n, int stride, int *id)
+{
+    SLAM_REQUIRE(s && id && n > 0 && stride >= 3 && xyz, SLAM_E_INVALID, "slam_kf_add_keyframe: bad arguments");
+    const size_t bytes = sizeof(float) * (size_t)n * stride;
+    SLAM_TRY(s->in.reserve(bytes));
+    SLAM_HIP(hipMemcpy(s->in.p, xyz, bytes, hipMemcpyHostToDevice));
+    return slam_kf_add_keyframe_dev(s, static_cast<const float *>(s->in.p), n, stride, id, nullptr);
+}
+
+int slam_kf_keyframe_info(slam_kf_t *s, int id, int *n_points, int *n_cells, int *max_cell_points, int *table_slots, long *device_bytes)
+{
+    SLAM_REQUIRE(s && id >= 0 && id < (int)s->kfs.size(), SLAM_E_INVALID, "slam_kf_keyframe_info: no keyframe %d", id);
+    const Keyframe &k = s->kfs[id];
+    if (n_points) *n_points = k.view.n;
+    if (n_cells) *n_cells = k.n_cells;
+    if (max_cell_points) *max_cell_points = k.max_cell;
+    if (table_slots) *table_slots = (int)(k.view.mask + 1);
+    if (device_bytes) *device_bytes = (long)k.bytes;
+    return SLAM_OK;
+}
+
+int slam_kf_read_keyframe(slam_kf_t *s, int id, float *xyz4, int max_points, int *n_points)
+{
+    SLAM_REQUIRE(s && n_points && id >= 0 && id < (int)s->kfs.size() && max_points >= 0 && (xyz4 || max_points == 0), SLAM_E_INVALID,
+                 "slam_kf_read_keyframe: bad arguments");
+    const Keyframe &k = s->kfs[id];
+    *n_points = k.view.n < max_points ? k.view.n : max_points;
+    if (*n_points) SLAM_HIP(hipMemcpy(xyz4, k.view.pts, sizeof(float4) * (size_t)*n_points, hipMemcpyDeviceToHost));
+    return SLAM_OK;
+}
+
+int slam_kf_nearest_dev(slam_kf_t *s, int id, const float *d_queries, int n, int stride, int strict, int32_t *d_index, float *d_dist2,
+                        slam_stream_t stream)
+{
+    SLAM_REQUIRE(s && id >= 0 && id < (int)s->kfs.size() && n >= 0 && stride >= 3 && (n == 0 || (d_queries && d_index && d_dist2)), SLAM_E_INVALID,
+                 "slam_kf_nearest_dev: bad arguments");
+    if (n == 0) return SLAM_OK;
+    hipLaunchKernelGGL(kf_nearest_kernel, dim3(blocks(n, 256)), dim3(256), 0, as_stream(stream), s->kfs[id].view, inv_cell(s->p),
+                       s->p.gate * s->p.gate, strict, d_queries, n, stride, d_index, d_dist2);
+    SLAM_HIP(hipGetLastError());
+    return SLAM_OK;
+}
+
+int slam_kf_register_edges_traced(slam_kf_t *s, const slam_kf_edge_req *req, int n_edges, slam_kf_edge_result *out, int32_t *pairs_trace,
+                                  int trace_cap, slam_stream_t stream)
+{
+    SLAM_REQUIRE(s && n_edges >= 0 && (n_edges == 0 || (req && out)) && (!pairs_trace || trace_cap > 0), SLAM_E_INVALID,
+                 "slam_kf_register_edges: bad arguments");
+    const int nk = (int)s->kfs.size();
+    size_t    n_corr = 0;
+    for (int e = 0; e < n_edges; ++e) {
+        SLAM_REQUIRE(req[e].from >= 0 && req[e].from < nk && req[e].to >= 0 && req[e].to < nk, SLAM_E_INVALID,
+                     "slam_kf_register_edges: edge %d names keyframes %d -> %d, the store holds %d", e, req[e].from, req[e].to, nk);
+        n_corr += (size_t)s->kfs[req[e].to].view.n;
+    }
+    if (n_edges == 0) return SLAM_OK;
+    if (!pairs_trace) trace_cap = 0;
+    hipStream_t  st = as_stream(stream);
+    const size_t task_b = sizeof(EdgeTask) * (size_t)n_edges, res_b = sizeof(slam_kf_edge_result) * (size_t)n_edges;
+    const size_t trace_b = sizeof(int32_t) * (size_t)n_edges * trace_cap, corr_b = sizeof(int32_t) * n_corr;
+    const size_t res_off = (task_b + 255) & ~(size_t)255, trace_off = res_off + ((res_b + 255) & ~(size_t)255);
+    const size_t corr_off = trace_off + ((trace_b + 255) & ~(size_t)255);
+    SLAM_TRY(s->work.reserve(corr_off + corr_b));
+    char *host = static_cast<char *>(pinned_scratch(corr_off));
+    SLAM_REQUIRE(host, SLAM_E_NOMEM, "slam_kf_register_edges: no pinned staging memory");
+    char     *dev = static_cast<char *>(s->work.p);
+    EdgeTask *tasks = reinterpret_cast<EdgeTask *>(host);
+    int32_t  *corr = reinterpret_cast<int32_t *>(dev + corr_off);
+    for (int e = 0; e < n_edges; ++e) {
+        tasks[e].src = s->kfs[req[e].to].view;
+        tasks[e].tgt = s->kfs[req[e].from].view;
+        tasks[e].corr = corr;
+        corr += tasks[e].src.n;
+        std::memcpy(tasks[e].init, req[e].init, sizeof tasks[e].init);
+    }
+    EdgeParams P;
+    P.inv_cell = inv_cell(s->p), P.gate2 = s->p.gate * s->p.gate;
+    P.eps_t = s->p.transformation_epsilon, P.eps_f = s->p.fitness_epsilon, P.max_iter = s->p.max_iterations;
+    int lds_points = 0;
+    if (s->p.target_in_lds)
+        for (int e = 0; e < n_edges; ++e)
+            if (tasks[e].tgt.n <= kLdsPoints && tasks[e].tgt.n > lds_points) lds_points = tasks[e].tgt.n;
+    if (lds_points && !s->lds_enabled) {
+        SLAM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kf_edge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)(sizeof(float4) * kLdsPoints)));
+        s->lds_enabled = true;
+    }
+    SLAM_HIP(hipMemcpyAsync(dev, host, task_b, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(kf_edge_kernel, dim3(n_edges), dim3(kEdgeThreads), sizeof(float4) * (size_t)lds_points, st, reinterpret_cast<const EdgeTask *>(dev), P,
+                       reinterpret_cast<slam_kf_edge_result *>(dev + res_off), trace_cap ? reinterpret_cast<int32_t *>(dev + trace_off) : nullptr,
+                       trace_cap, lds_points);
+    SLAM_HIP(hipGetLastError());
+    SLAM_HIP(hipMemcpyAsync(host + res_off, dev + res_off, (trace_off - res_off) + trace_b, hipMemcpyDeviceToHost, st));
+    SLAM_HIP(hipStreamSynchronize(st));
+    std::memcpy(out, host + res_off, res_b);
+    if (trace_cap) std::memcpy(pairs_trace, host + trace_off, trace_b);
+    return SLAM_OK;
+}
+
+int slam_kf_register_edges(slam_kf_t *s, const slam_kf_edge_req *req, int n_edges, slam_kf_edge_result *out, slam_stream_t stream)
+{
+    return slam_kf_register_edges_traced(s, req, n_edges, out, nullptr, 0, stream);
+}
+}

@@ -1,0 +1,308 @@
+"""ctypes wrapper of tests/cpp/kf_edge_oracle.cpp, the scalar restatement of graph_slam's keyframe edge
+(graphSlamTools.cpp:27-39, 108-364) that slam_kf_* is held against.  Compiled on first use with
+g++ -O2 -ffp-contract=off (the reference is x86-64 without FMA) into a temporary directory."""
+import ctypes as C
+import hashlib
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+
+from slam_amd import api, synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "cpp", "kf_edge_oracle.cpp")
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is not None:
+        return _lib
+    h = hashlib.sha1()
+    for f in (SRC, os.path.join(ROOT, "include", "slam_mi355x.h")):
+        h.update(open(f, "rb").read())
+    d = os.path.join(tempfile.gettempdir(), "slam_kf_edge_oracle_%d" % os.getuid())
+    os.makedirs(d, exist_ok=True)
+    so = os.path.join(d, "kf_edge_oracle_%s.so" % h.hexdigest()[:16])
+    if not os.path.exists(so):
+        tmp = so + ".%d.tmp" % os.getpid()
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-shared", "-fPIC",
+                               "-I", os.path.join(ROOT, "include"), SRC, "-o", tmp])
+        os.replace(tmp, so)
+    L = C.CDLL(so)
+    vp = C.c_void_p
+    L.kfo_index_create.restype = vp
+    L.kfo_index_create.argtypes = [vp, C.c_int, C.c_int, C.c_double]
+    L.kfo_index_destroy.argtypes = [vp]
+    L.kfo_index_destroy.restype = None
+    L.kfo_index_stats.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.kfo_nearest.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp]
+    L.kfo_solve.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
+    L.kfo_icp.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(api.KfParams), C.c_int, C.POINTER(api.KfEdgeResult),
+                          vp, C.c_int, C.POINTER(C.c_double)]
+    L.kfo_lum.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.POINTER(api.KfEdgeResult), vp, vp, vp]
+    L.kfo_inverse6.argtypes = [vp, vp]
+    _lib = L
+    return L
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+
+
+def default_params(**kw):
+    """setup_gicp's values (graphSlamTools.cpp:27-39) without the library."""
+    p = api.KfParams(0.5, 0.75, 0.0, 200, 1e-6, 1e-6, 1)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def lattice_edge(p):
+    return (p.cell_size if p.cell_size > 0 else p.gate) * api.KF_LATTICE_MARGIN
+
+
+class OracleKeyframe:
+    """A filtered cloud ([n, >= 3] f32) with the restatement's search lattice."""
+
+    def __init__(self, xyz, params=None):
+        self.params = params or default_params()
+        self.xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+        self.n, self.stride = self.xyz.shape
+        self.h = lib().kfo_index_create(_p(self.xyz), self.n, self.stride, lattice_edge(self.params))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().kfo_index_destroy(self.h)
+            self.h = None
+
+    def stats(self):
+        c, m = C.c_int(), C.c_int()
+        lib().kfo_index_stats(self.h, C.byref(c), C.byref(m))
+        return c.value, m.value
+
+    def nearest(self, q, strict=False, gate=None):
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        idx, d2 = np.zeros(len(q), np.int32), np.zeros(len(q), np.float32)
+        lib().kfo_nearest(self.h, _p(q), len(q), q.shape[1], self.params.gate if gate is None else gate, int(strict), _p(idx), _p(d2))
+        return idx, d2
+
+
+def solve(p, q, use_float=False):
+    """Umeyama without scaling, p -> q: (R [3,3], t [3], rank of H)."""
+    p, q = np.ascontiguousarray(p, np.float32), np.ascontiguousarray(q, np.float32)
+    R, t = np.zeros(9), np.zeros(3)
+    rank = lib().kfo_solve(_p(p), _p(q), len(p), int(use_float), _p(R), _p(t))
+    return R.reshape(3, 3), t, rank
+
+
+def register_edge(target, source, init, params=None, mode=0, trace=256, lum_detail=False):
+    """calcEdgeIcp's device part on two filtered clouds: target = OracleKeyframe (`from`), source = [n, >= 3] f32 (`to`).
+    Returns the dict of api.kf_result_dict plus 'pairs_trace', 'margin' (the smallest relative margin of any stop test)
+    and, with lum_detail, 'MM', 'MZ', 'aver', 'diff'."""
+    P = params or target.params
+    src = np.ascontiguousarray(source, dtype=np.float32)
+    init = np.ascontiguousarray(np.asarray(init, np.float32).reshape(16))
+    res = api.KfEdgeResult()
+    tr = np.full(max(trace, 1), -1, np.int32)
+    margin = C.c_double()
+    lib().kfo_icp(target.h, _p(src), len(src), src.shape[1], _p(init), C.byref(P), int(mode), C.byref(res), _p(tr), int(trace),
+                  C.byref(margin))
+    mm = np.zeros(42)
+    aver, diff = np.zeros((len(src), 3), np.float32), np.zeros((len(src), 3), np.float32)
+    lib().kfo_lum(target.h, _p(src), len(src), src.shape[1], P.gate, C.byref(res), _p(mm), _p(aver), _p(diff))
+    out = api.kf_result_dict(res)
+    out["pairs_trace"], out["margin"] = tr, margin.value
+    if lum_detail:
+        n = res.num_corr
+        out.update(MM=mm[:36].reshape(6, 6).copy(), MZ=mm[36:].copy(), aver=aver[:n], diff=diff[:n])
+    return out
+
+
+def lum_only(target, source, transform, gate=None):
+    src = np.ascontiguousarray(source, dtype=np.float32)
+    res = api.KfEdgeResult()
+    res.transform[:] = np.asarray(transform, np.float32).reshape(16).tolist()
+    mm = np.zeros(42)
+    aver, diff = np.zeros((len(src), 3), np.float32), np.zeros((len(src), 3), np.float32)
+    lib().kfo_lum(target.h, _p(src), len(src), src.shape[1], target.params.gate if gate is None else gate, C.byref(res), _p(mm),
+                  _p(aver), _p(diff))
+    out = api.kf_result_dict(res)
+    n = res.num_corr
+    out.update(MM=mm[:36].reshape(6, 6).copy(), MZ=mm[36:].copy(), aver=aver[:n], diff=diff[:n])
+    return out
+
+
+def inverse6(A):
+    A = np.ascontiguousarray(A, np.float64)
+    X = np.zeros((6, 6))
+    lib().kfo_inverse6(_p(A), _p(X))
+    return X
+
+
+# ------------------------------------------------------------------ the test edges
+EDGE_KS = (0, 1, 2, 4, 8, 25)
+PERTURB = (0.3, -0.2, 0.04)   # metres, metres, radians on top of the true relative pose
+
+
+def pose_matrix(x, y, th, z=0.0):
+    c, s = np.cos(th), np.sin(th)
+    return np.array([[c, -s, 0, x], [s, c, 0, y], [0, 0, 1, z], [0, 0, 0, 1]], np.float64)
+
+
+def relative_init(pose_from, pose_to, perturb=PERTURB):
+    """Mfrom^-1 Mto composed with the perturbation, rounded to f32 (what calcEdgeIcp hands to align)."""
+    M = np.linalg.inv(pose_matrix(*pose_from)) @ pose_matrix(*pose_to)
+    return (pose_matrix(*perturb) @ M).astype(np.float32)
+
+
+def true_relative(pose_from, pose_to):
+    return np.linalg.inv(pose_matrix(*pose_from)) @ pose_matrix(*pose_to)
+
+
+_clouds = {}
+
+
+def cloud(k):
+    if k not in _clouds:
+        _clouds[k] = synth.make_cloud3d(k)
+    return _clouds[k]
+
+
+def pose_error(Ta, Tb):
+    """(metres, radians) between two 4x4 transforms."""
+    Ta, Tb = np.asarray(Ta, np.float64), np.asarray(Tb, np.float64)
+    dR = Ta[:3, :3].T @ Tb[:3, :3]
+    # the sine from the skew part: the f32-rounded initial rotation leaves R'R off the identity by 1e-7, which an arccos of
+    # the trace would read as 4e-4 rad
+    w = 0.5 * np.array([dR[2, 1] - dR[1, 2], dR[0, 2] - dR[2, 0], dR[1, 0] - dR[0, 1]])
+    ang = np.arctan2(np.linalg.norm(w), 0.5 * (np.trace(dR) - 1.0))
+    return float(np.linalg.norm(Ta[:3, 3] - Tb[:3, 3])), float(ang)
+
+
+def brute_force(points, queries, gate, strict):
+    """index and f32 squared distance of the nearest point, the sum ordered as the contract orders it; lowest index on ties"""
+    p = np.ascontiguousarray(points[:, :3], np.float32)
+    idx = np.zeros(len(queries), np.int32)
+    d2 = np.zeros(len(queries), np.float32)
+    for lo in range(0, len(queries), 2048):
+        q = queries[lo:lo + 2048]
+        d = q[:, None, :] - p[None, :, :]
+        d = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+        assert d.dtype == np.float32
+        j = d.argmin(axis=1)               # the first of equal minima
+        idx[lo:lo + 2048], d2[lo:lo + 2048] = j, d[np.arange(len(q)), j]
+    g2 = gate * gate
+    keep = (d2.astype(np.float64) < g2) if strict else (d2.astype(np.float64) <= g2)
+    return np.where(keep, idx, -1).astype(np.int32), np.where(keep, d2, np.float32(0)).astype(np.float32)
+
+
+# ------------------------------------------------------------------ calcEdgeIcp's host parts (graphSlamTools.cpp:240-260, 318-360)
+# Python floats are IEEE doubles: the operations below are those of include/slam_amd/graph_edges.hpp in the same order.
+def quat_to_matrix(q):
+    """Eigen::Quaterniond(w, x, y, z).toRotationMatrix(); q = (x, y, z, w)."""
+    x, y, z, w = (float(v) for v in q)
+    tx, ty, tz = 2.0 * x, 2.0 * y, 2.0 * z
+    twx, twy, twz, txx, txy, txz, tyy, tyz, tzz = tx * w, ty * w, tz * w, tx * x, ty * x, tz * x, ty * y, tz * y, tz * z
+    return [1.0 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1.0 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1.0 - (txx + tyy)]
+
+
+def relative_f32(pose_from, pose_to):
+    """(Mfrom^-1 Mto).cast<float>() for two poses (x, y, z, qx, qy, qz, qw), :258."""
+    Rf, Rt = quat_to_matrix(pose_from[3:]), quat_to_matrix(pose_to[3:])
+    d = [float(pose_to[k]) - float(pose_from[k]) for k in range(3)]
+    out = np.zeros((4, 4), np.float32)
+    for r in range(3):
+        for c in range(3):
+            out[r, c] = np.float32((Rf[r] * Rt[c] + Rf[3 + r] * Rt[3 + c]) + Rf[6 + r] * Rt[6 + c])
+        out[r, 3] = np.float32((Rf[r] * d[0] + Rf[3 + r] * d[1]) + Rf[6 + r] * d[2])
+    out[3, 3] = 1.0
+    return out
+
+
+def eigen_quaternion(m):
+    """Eigen::Quaterniond(Matrix3d) with w >= 0 (tf::poseEigenToMsg); m: 9 doubles row-major -> (x, y, z, w)."""
+    q = [0.0] * 4
+    t = m[0] + m[4] + m[8]
+    if t > 0.0:
+        t = np.sqrt(t + 1.0)
+        q[3] = 0.5 * t
+        t = 0.5 / t
+        q[0], q[1], q[2] = (m[7] - m[5]) * t, (m[2] - m[6]) * t, (m[3] - m[1]) * t
+    else:
+        i = 0
+        if m[4] > m[0]:
+            i = 1
+        if m[8] > m[4 * i]:
+            i = 2
+        j = (i + 1) % 3
+        k = (j + 1) % 3
+        t = np.sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0)
+        q[i] = 0.5 * t
+        t = 0.5 / t
+        q[3] = (m[3 * k + j] - m[3 * j + k]) * t
+        q[j] = (m[3 * j + i] + m[3 * i + j]) * t
+        q[k] = (m[3 * k + i] + m[3 * i + k]) * t
+    if q[3] < 0:
+        q = [-v for v in q]
+    return q
+
+
+def tf_quaternion(m):
+    """tf::Matrix3x3::getRotation."""
+    trace = m[0] + m[4] + m[8]
+    temp = [0.0] * 4
+    if trace > 0.0:
+        s = np.sqrt(trace + 1.0)
+        temp[3] = s * 0.5
+        s = 0.5 / s
+        temp[0], temp[1], temp[2] = (m[7] - m[5]) * s, (m[2] - m[6]) * s, (m[3] - m[1]) * s
+    else:
+        i = (2 if m[4] < m[8] else 1) if m[0] < m[4] else (2 if m[0] < m[8] else 0)
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = np.sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0)
+        temp[i] = s * 0.5
+        s = 0.5 / s
+        temp[3] = (m[3 * k + j] - m[3 * j + k]) * s
+        temp[j] = (m[3 * j + i] + m[3 * i + j]) * s
+        temp[k] = (m[3 * k + i] + m[3 * i + k]) * s
+    return temp
+
+
+def tf_yaw(q):
+    x, y, z, w = (float(v) for v in q)
+    d = x * x + y * y + z * z + w * w
+    s = 2.0 / d
+    ys, zs = y * s, z * s
+    wy, wz, xy, xz, yy, zz = w * ys, w * zs, x * ys, x * zs, y * ys, z * zs
+    m00, m10, m20 = 1.0 - (yy + zz), xy + wz, xz - wy
+    if abs(m20) >= 1.0:
+        return 0.0
+    cp = np.cos(-np.arcsin(m20))
+    return float(np.arctan2(m10 / cp, m00 / cp))
+
+
+def edge_pose_and_gate(init, transform, dist_thresh=10.0, rot_thresh=0.2):
+    """From the f32 initial and final transforms: (edge pose x y z qx qy qz qw, accepted, (x_diff, y_diff, theta_diff))."""
+    init, T = np.asarray(init, np.float32).reshape(4, 4), np.asarray(transform, np.float32).reshape(4, 4)
+    qi = eigen_quaternion([float(v) for v in init[:3, :3].reshape(9)])
+    qe = tf_quaternion([float(v) for v in T[:3, :3].reshape(9)])
+    xd, yd = abs(float(init[0, 3]) - float(T[0, 3])), abs(float(init[1, 3]) - float(T[1, 3]))
+    th = abs(tf_yaw(qi) - tf_yaw(qe))
+    if th > 2 * np.pi:
+        th = th - 2 * np.pi
+    elif th > np.pi:
+        th = 2 * np.pi - th
+    ok = not (xd > dist_thresh or yd > dist_thresh or th > rot_thresh)
+    return [float(T[0, 3]), float(T[1, 3]), float(T[2, 3])] + qe, ok, (xd, yd, th)
+
+
+def get_knn(poses, idx, K):
+    """graphSlamGetKNN (:72-106) over poses[0 .. numKF) for node idx (= numKF - 1 in graph_slam.cpp:508)."""
+    num = len(poses)
+    K = min(num - 1, K)
+    sc = sorted(((float(np.sqrt((poses[i][0] - poses[idx][0]) ** 2 + (poses[i][1] - poses[idx][1]) ** 2)), i) for i in range(num - 2)),
+                key=lambda v: v[0])
+    return [sc[i][1] for i in range(K) if i < len(sc) and sc[i][1] != idx]
