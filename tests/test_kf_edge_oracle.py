@@ -10,32 +10,10 @@ import pytest
 
 import kf_edge_oracle as K
 import oracle_lib as O
+from kf_edge_cases import AXES, SOLVE_TOL, T_of, lattice_cloud, rot90   # shared with the branch tests
 from slam_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOLVE_TOL = 1e-12   # closed-form solves on exact pairs, as tests/test_gpu_icp.py
-
-
-def rot90(axis, quarter_turns):
-    c, s = [(1, 0), (0, 1), (-1, 0), (0, -1)][quarter_turns % 4]
-    R = np.eye(3)
-    i, j = [(1, 2), (2, 0), (0, 1)][axis]
-    R[i, i], R[i, j], R[j, i], R[j, j] = c, -s, s, c
-    return R
-
-
-def lattice_cloud(seed=5, n=4, pitch=2.0):
-    """n^3 points about `pitch` apart on dyadic coordinates (multiples of 2^-8): rotations by 90 degrees and dyadic
-    translations of it are exact in f32, and every point is its copy's nearest neighbour for offsets below pitch / 2"""
-    rs = np.random.RandomState(seed)
-    g = np.stack(np.meshgrid(*[np.arange(n) * pitch] * 3, indexing="ij"), -1).reshape(-1, 3)
-    return (g + rs.randint(-64, 65, g.shape) / 256.0 - pitch * (n - 1) / 2).astype(np.float32)
-
-
-def T_of(R, t):
-    T = np.eye(4)
-    T[:3, :3], T[:3, 3] = R, t
-    return T
 
 
 @pytest.mark.parametrize("axis,turns", [(0, 1), (1, 1), (2, 1), (0, 2), (1, 3), (2, 2)])
@@ -59,9 +37,6 @@ def test_exact_rigid_copy_is_recovered_in_one_step(axis, turns):
     assert np.abs(two["transform64"] - T_of(R, t)).max() < SOLVE_TOL and two["mse"] < 1e-24
     # LUM on an exact match: ss = 0, the identity fallback (:203-208)
     assert two["num_corr"] == len(src) and two["singular"] == 1 and np.array_equal(two["information"], np.eye(6))
-
-
-AXES = np.array([[4, 0, 0], [-4, 0, 0], [0, 2, 0], [0, -2, 0], [0, 0, 1], [0, 0, -1]], np.float32)
 
 
 def test_reflected_pairs_take_the_determinant_fix():
