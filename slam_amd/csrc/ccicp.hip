@@ -16,7 +16,7 @@
 
 #include <rocprim/rocprim.hpp> // device radix sort (the stable bin order of classifyPoints)
 
-#include "common.hpp"
+#include "device_mem.hpp"
 
 using namespace slam;
 
@@ -677,28 +677,6 @@ __global__ __launch_bounds__(kScanThreads) void compact1_kernel(Pred pred, Emit 
     }
 }
 
-struct DevBuf {
-    void  *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes)
-    {
-        if (bytes <= cap) return SLAM_OK;
-        // a quarter more than asked: clouds of a sequence differ by a few per cent, and every growth is a free (which waits
-        // for the device) and an allocation
-        const size_t want = bytes + bytes / 4;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        SLAM_HIP(hipMalloc(&p, want));
-        cap = want;
-        return SLAM_OK;
-    }
-    ~DevBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
-
 struct NoTail {
     int *total0, *total1;
     __device__ void operator()(const int tot[2]) const
@@ -721,14 +699,14 @@ struct OneEmit {
 } // namespace
 
 struct slam_ccicp {
-    DevBuf vox, small;                  // small: 6 min/max words, totals, 4 packed NN results
-    DevBuf status;                      // the one-launch compactions' epoch (word 0, kept by the kernels) and look-back words (compact1)
+    DevMem vox, small;                  // small: 6 min/max words, totals, 4 packed NN results
+    DevMem status;                      // the one-launch compactions' epoch (word 0, kept by the kernels) and look-back words (compact1)
     size_t vox_clean = 0;               // voxels of `vox` known to be zero (the chain's compaction leaves them so)
     const void *best_of = nullptr;      // the chain block whose packed neighbours (ChainSmall::best) have been set to "none"
-    DevBuf keys, sort_tmp;
+    DevMem keys, sort_tmp;
     long long max_voxels = 1ll << 26;
     // the chain (slam_ccicp_scene_dev): per-point scratch for the cloud's capacity, the lattice and the counts on the device
-    DevBuf labels, obs, flags, filtered, chain; // chain: VoxelGridView, counts, wheel points, packed neighbours
+    DevMem labels, obs, flags, filtered, chain; // chain: VoxelGridView, counts, wheel points, packed neighbours
     long long chain_voxels = 1ll << 21;         // accumulator capacity of the chain (64 MB): 0.5 x 0.5 x 2 m over 360 x 360 x 30 m
 };
 
@@ -743,7 +721,7 @@ int compact1(slam_ccicp *h, Pred pred, Emit emit, Tail tail, long long n, int li
     const int    n_blocks = (int)std::max<long long>((n + kItems - 1) / kItems, 1);
     const size_t need = sizeof(unsigned long long) * (1 + 2 * (size_t)n_blocks);
     if (need > h->status.cap) {
-        SLAM_TRY(h->status.reserve(std::max<size_t>(need, 1 << 16)));
+        SLAM_TRY(reserve_quarter(h->status, std::max<size_t>(need, 1 << 16)));
         SLAM_HIP(hipMemsetAsync(h->status.p, 0, h->status.cap, st)); // epoch 0, and no word carries a flag
     }
     const Domain dom = {n, d_n, d_n64};
@@ -792,7 +770,7 @@ int slam_ccicp_create(slam_ccicp_t **out)
     SLAM_TRY(require_device());
     slam_ccicp *h = new (std::nothrow) slam_ccicp();
     SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_ccicp_create: out of host memory");
-    int rc = h->small.reserve(256);
+    int rc = reserve_quarter(h->small, 256);
     if (rc != SLAM_OK) {
         delete h;
         return rc;
@@ -839,7 +817,7 @@ int slam_ccicp_voxel_downsample_dev(slam_ccicp_t *h, const float *d_xyz, const u
                      nv, h->max_voxels);
     }
     g.n_vox = nv;
-    SLAM_TRY(h->vox.reserve(sizeof(Voxel) * (size_t)nv));
+    SLAM_TRY(reserve_quarter(h->vox, sizeof(Voxel) * (size_t)nv));
     Voxel *vox = static_cast<Voxel *>(h->vox.p);
     SLAM_HIP(hipMemsetAsync(vox, 0, sizeof(Voxel) * (size_t)nv, st));
     h->vox_clean = 0; // (the chain of slam_ccicp_scene_dev shares the accumulator and expects it zero)
@@ -878,12 +856,12 @@ int slam_ccicp_bin_order_dev(slam_ccicp_t *h, const float *d_xyz, const uint8_t 
     *n_out = 0;
     if (n == 0) return SLAM_OK;
     hipStream_t st = as_stream(stream);
-    SLAM_TRY(h->keys.reserve(2 * sizeof(unsigned long long) * (size_t)n));
+    SLAM_TRY(reserve_quarter(h->keys, 2 * sizeof(unsigned long long) * (size_t)n));
     unsigned long long *k_in = static_cast<unsigned long long *>(h->keys.p), *k_out = k_in + n;
     hipLaunchKernelGGL(bin_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_xyz, d_flag, n, stride, k_in);
     size_t tmp = 0;
     SLAM_HIP(rocprim::radix_sort_keys(nullptr, tmp, k_in, k_out, (size_t)n, 0u, 53u, st));
-    SLAM_TRY(h->sort_tmp.reserve(tmp));
+    SLAM_TRY(reserve_quarter(h->sort_tmp, tmp));
     SLAM_HIP(rocprim::radix_sort_keys(h->sort_tmp.p, tmp, k_in, k_out, (size_t)n, 0u, 53u, st));
     int *d_n = reinterpret_cast<int *>(static_cast<unsigned *>(h->small.p) + 24);
     SLAM_HIP(hipMemsetAsync(d_n, 0, sizeof(int), st));
@@ -1075,11 +1053,11 @@ int slam_ccicp_scene_dev(slam_ccicp_t *h, slam_gseg_t *seg, const float *d_xyz, 
                  "slam_ccicp_scene_dev: bad arguments");
     hipStream_t st = as_stream(stream);
     const size_t np = (size_t)std::max(n, 1);
-    SLAM_TRY(h->labels.reserve(np));
-    SLAM_TRY(h->obs.reserve(16 * np));
-    SLAM_TRY(h->flags.reserve(np));
-    SLAM_TRY(h->filtered.reserve(16 * np));
-    SLAM_TRY(h->chain.reserve(sizeof(ChainSmall)));
+    SLAM_TRY(reserve_quarter(h->labels, np));
+    SLAM_TRY(reserve_quarter(h->obs, 16 * np));
+    SLAM_TRY(reserve_quarter(h->flags, np));
+    SLAM_TRY(reserve_quarter(h->filtered, 16 * np));
+    SLAM_TRY(reserve_quarter(h->chain, sizeof(ChainSmall)));
     ChainSmall    *c = static_cast<ChainSmall *>(h->chain.p);
     unsigned char *lab = static_cast<unsigned char *>(h->labels.p), *flg = static_cast<unsigned char *>(h->flags.p);
     float         *obs = static_cast<float *>(h->obs.p), *flt = static_cast<float *>(h->filtered.p);
@@ -1094,7 +1072,7 @@ int slam_ccicp_scene_dev(slam_ccicp_t *h, slam_gseg_t *seg, const float *d_xyz, 
         if (voxel) { // setSceneCloud's voxel filter (:620-633), leaf 0.5, 0.5, 2
             // the accumulator is zero where no scene has left a sum: the compaction below clears what it reads
             if (sizeof(Voxel) * (size_t)h->chain_voxels > h->vox.cap) h->vox_clean = 0;
-            SLAM_TRY(h->vox.reserve(sizeof(Voxel) * (size_t)h->chain_voxels));
+            SLAM_TRY(reserve_quarter(h->vox, sizeof(Voxel) * (size_t)h->chain_voxels));
             Voxel *vox = static_cast<Voxel *>(h->vox.p);
             if (h->vox_clean < (size_t)h->chain_voxels) {
                 SLAM_HIP(hipMemsetAsync(vox, 0, sizeof(Voxel) * (size_t)h->chain_voxels, st));
@@ -1106,12 +1084,12 @@ int slam_ccicp_scene_dev(slam_ccicp_t *h, slam_gseg_t *seg, const float *d_xyz, 
             SLAM_TRY((compact1<1, false>(h, OneOutput<VoxelUsed>{VoxelUsed{vox}}, OneEmit<VoxelEmitClean>{VoxelEmitClean{vox, flt}}, FltTail{&c->n_flt},
                                          h->chain_voxels, n, st, nullptr, &c->g.n_vox, &c->err)));
         } else { // setTargetCloud: classified, bin by bin, no voxel filter (:591-595)
-            SLAM_TRY(h->keys.reserve(2 * sizeof(unsigned long long) * (size_t)n));
+            SLAM_TRY(reserve_quarter(h->keys, 2 * sizeof(unsigned long long) * (size_t)n));
             unsigned long long *k_in = static_cast<unsigned long long *>(h->keys.p), *k_out = k_in + n;
             hipLaunchKernelGGL(bin_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, st, obs, flg, n, 4, k_in, &c->n_obs);
             size_t tmp = 0;
             SLAM_HIP(rocprim::radix_sort_keys(nullptr, tmp, k_in, k_out, (size_t)n, 0u, 53u, st));
-            SLAM_TRY(h->sort_tmp.reserve(tmp));
+            SLAM_TRY(reserve_quarter(h->sort_tmp, tmp));
             SLAM_HIP(rocprim::radix_sort_keys(h->sort_tmp.p, tmp, k_in, k_out, (size_t)n, 0u, 53u, st));
             hipLaunchKernelGGL(bin_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, st, obs, flg, 4, k_out, n,
                                reinterpret_cast<float4 *>(flt), &c->n_flt);
@@ -1163,7 +1141,7 @@ int slam_ccicp_height_rpy_pose_mirror_dev(slam_ccicp_t *h, const float *d_ground
     SLAM_REQUIRE(mirror_bytes == 0 || (mirror_dst && mirror_src && mirror_bytes % 8 == 0 && mirror_bytes <= 4096), SLAM_E_INVALID,
                  "slam_ccicp_height_rpy_pose_mirror_dev: the mirrored block is a multiple of 8 bytes, at most 4096");
     hipStream_t st = as_stream(stream);
-    SLAM_TRY(h->chain.reserve(sizeof(ChainSmall)));
+    SLAM_TRY(reserve_quarter(h->chain, sizeof(ChainSmall)));
     ChainSmall *c = static_cast<ChainSmall *>(h->chain.p);
     // (the four packed neighbours start as "none": set once for the block as it is, put back by every fit)
     if (h->best_of != h->chain.p) {

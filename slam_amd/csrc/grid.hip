@@ -27,9 +27,10 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
-#include "common.hpp"
+#include "device_mem.hpp"
 #include "grid_cell.hpp"
 
 using namespace slam;
@@ -1143,78 +1144,54 @@ struct slam_grid {
     slam_grid_params prm;
     GridView         gv;
     size_t           cells = 0;
-    int32_t         *d_planes = nullptr;  // [hits | misses]
-    double          *d_num_w = nullptr;   // window order, written by finalize
-    int8_t          *d_occ_w = nullptr;   // window order, written by finalize
-    double          *d_num_s = nullptr;   // storage order, in-order mode state
-    int8_t          *d_occ_s = nullptr;   // storage order, in-order mode state
-    unsigned long long *d_delta = nullptr; // [cells] per-scan deltas of the in-order mode
-    int             *d_touched = nullptr; // [2*cap_points] + counter
-    size_t           cap_touched = 0;
-    unsigned long long *d_updates = nullptr;
-    int             *d_dirty = nullptr;    // [2][4] see GridView::dirty; two buffers: slam_grid_finalize_reset reads one and starts the other
-    int32_t         *d_acc = nullptr;      // [hits | misses] accumulator planes (slam_grid_enable_accumulator)
-    Beam            *d_beams = nullptr;
-    size_t           cap_beams = 0;
-    int4            *d_chunk_box = nullptr;
-    size_t           cap_chunks = 0;
-    int             *d_tile_cnt = nullptr; // [n_tiles] overlapping chunks per tile
-    int             *d_tile_fill = nullptr; // [n_tiles+1] item_off: where each tile's list starts (grids beyond kMaxLdsTiles tiles)
-    int             *d_cursor = nullptr;   // [n_tiles+1] blocks of each tile's list handed out so far; behind them, the launch's tile write-backs
-    int             *d_items = nullptr;    // chunk ids bucketed by tile
-    size_t           cap_items = 0;
+    OwnedArray<int32_t> d_planes;  // [hits | misses]
+    OwnedArray<double>  d_num_w;   // window order, written by finalize
+    OwnedArray<int8_t>  d_occ_w;   // window order, written by finalize
+    OwnedArray<double>  d_num_s;   // storage order, in-order mode state
+    OwnedArray<int8_t>  d_occ_s;   // storage order, in-order mode state
+    OwnedArray<unsigned long long> d_delta; // [cells] per-scan deltas of the in-order mode
+    OwnedArray<int>     d_touched; // [2*cap_points] + counter
+    OwnedArray<unsigned long long> d_updates;
+    OwnedArray<int>     d_dirty;    // [2][4] see GridView::dirty; two buffers: slam_grid_finalize_reset reads one and starts the other
+    OwnedArray<int32_t> d_acc;      // [hits | misses] accumulator planes (slam_grid_enable_accumulator)
+    OwnedArray<Beam>    d_beams;
+    OwnedArray<int4>    d_chunk_box;
+    OwnedArray<int>     d_tile_cnt; // [n_tiles] overlapping chunks per tile
+    OwnedArray<int>     d_tile_fill; // [n_tiles+1] item_off: where each tile's list starts (grids beyond kMaxLdsTiles tiles)
+    OwnedArray<int>     d_cursor;   // [n_tiles+1] blocks of each tile's list handed out so far; behind them, the launch's tile write-backs
+    OwnedArray<int>     d_items;    // chunk ids bucketed by tile
     int              n_cu = 256;
     int              seg_items = 0;  // 64-beam blocks a workgroup takes from a tile's list at a time; 0 = kChunkDefault
     int              last_chunks = 0;
     int              ablate = 0;     // debug: SLAM_RAYCAST_ABLATE bit mask (timing experiments only)
     int              wg_per_cu = 0;  // persistent raycast workgroups per CU; 0 = by the number of tiles (raycast_wg_per_cu)
     bool             merge = false;  // tiled raycast: lanes on one cell add once (SLAM_RAYCAST_TILED_MERGE)
-    void            *d_stage = nullptr;   // host-API staging
-    size_t           cap_stage = 0;
+    DevMem           d_stage;             // host-API staging
     bool             state_from_inorder = false;
     long             shift_x = 0, shift_y = 0; // cells the rolling window has moved since creation (sum of setPose's dx, dy)
 };
 
 namespace {
 
-int reserve(void **p, size_t *cap, size_t bytes)
-{
-    if (bytes <= *cap) return SLAM_OK;
-    if (*p) (void)hipFree(*p); // (waits for the device: callers with varying sizes reserve up front, slam_grid_reserve)
-    const size_t grown = *cap + *cap / 4;
-    *p = nullptr;
-    *cap = 0;
-    size_t want = std::max(std::max(bytes, grown), (size_t)4096);
-    SLAM_HIP(hipMalloc(p, want));
-    *cap = want;
-    return SLAM_OK;
-}
+// The grid's growing buffers: at least a quarter more than before and never below 4 KB.  (The free waits for the device:
+// callers with varying sizes reserve up front, slam_grid_reserve.)
+int reserve(DevMem &b, size_t bytes) { return b.reserve(bytes, std::max(b.cap + b.cap / 4, (size_t)4096)); }
 
 int reserve_beams(slam_grid *g, size_t n)
 {
-    size_t cb = g->cap_beams * sizeof(Beam);
-    void  *p = g->d_beams;
-    SLAM_TRY(reserve(&p, &cb, n * sizeof(Beam)));
-    g->d_beams = static_cast<Beam *>(p);
-    g->cap_beams = cb / sizeof(Beam);
+    SLAM_TRY(reserve(g->d_beams, n * sizeof(Beam)));
     const size_t chunks = (n + kBlock - 1) / kBlock + kChunk / kBlock;
-    size_t       cc = g->cap_chunks * sizeof(int4);
-    p = g->d_chunk_box;
-    SLAM_TRY(reserve(&p, &cc, chunks * sizeof(int4)));
-    g->d_chunk_box = static_cast<int4 *>(p);
-    g->cap_chunks = cc / sizeof(int4);
+    SLAM_TRY(reserve(g->d_chunk_box, chunks * sizeof(int4)));
     if (g->prm.raycast_impl != SLAM_RAYCAST_GLOBAL) {
         const size_t n_tiles = (size_t)((g->gv.sx + kTile - 1) / kTile) * ((g->gv.sy + kTile - 1) / kTile);
-        if (!g->d_tile_cnt) {
-            SLAM_HIP(hipMalloc((void **)&g->d_tile_cnt, n_tiles * sizeof(int)));
-            SLAM_HIP(hipMalloc((void **)&g->d_tile_fill, (n_tiles + 1) * sizeof(int)));
-            SLAM_HIP(hipMalloc((void **)&g->d_cursor, (n_tiles + 1) * sizeof(int)));
+        if (!g->d_tile_cnt) { // the three together or none of them
+            OwnedArray<int> cnt, fill, cursor;
+            SLAM_TRY(cnt.alloc(n_tiles * sizeof(int)));
+            SLAM_TRY(fill.alloc((n_tiles + 1) * sizeof(int)));
+            SLAM_TRY(cursor.alloc((n_tiles + 1) * sizeof(int)));
+            g->d_tile_cnt = std::move(cnt), g->d_tile_fill = std::move(fill), g->d_cursor = std::move(cursor);
         }
-        size_t ci = g->cap_items * sizeof(int);
-        p = g->d_items;
-        SLAM_TRY(reserve(&p, &ci, (chunks * n_tiles) * sizeof(int)));
-        g->d_items = static_cast<int *>(p);
-        g->cap_items = ci / sizeof(int);
+        SLAM_TRY(reserve(g->d_items, (chunks * n_tiles) * sizeof(int)));
     }
     return SLAM_OK;
 }
@@ -1318,25 +1295,14 @@ int slam_grid_create(int size_x, int size_y, double resolution, const slam_grid_
     if (const char *e = getenv("SLAM_RAYCAST_ABLATE")) g->ablate = atoi(e);
     if (const char *e = getenv("SLAM_RAYCAST_WGPCU")) g->wg_per_cu = std::max(1, atoi(e));
 #endif
-    int rc = SLAM_OK;
-    auto alloc = [&](void **p, size_t bytes) {
-        if (rc == SLAM_OK && hipMalloc(p, bytes) != hipSuccess) {
-            set_error("slam_grid_create: hipMalloc of %zu bytes failed", bytes);
-            (void)hipGetLastError();
-            rc = SLAM_E_NOMEM;
-        }
-    };
-    alloc((void **)&g->d_planes, 2 * g->cells * sizeof(int32_t));
-    alloc((void **)&g->d_num_w, g->cells * sizeof(double));
-    alloc((void **)&g->d_occ_w, g->cells);
-    alloc((void **)&g->d_num_s, g->cells * sizeof(double));
-    alloc((void **)&g->d_occ_s, g->cells);
-    alloc((void **)&g->d_updates, kUpdateSlots * sizeof(unsigned long long));
-    alloc((void **)&g->d_dirty, 8 * sizeof(int));
-    if (rc != SLAM_OK) {
-        slam_grid_destroy(g);
-        return rc;
-    }
+    std::unique_ptr<slam_grid> guard(g); // an early return gives the handle and its buffers back
+    SLAM_TRY(g->d_planes.alloc(2 * g->cells * sizeof(int32_t)));
+    SLAM_TRY(g->d_num_w.alloc(g->cells * sizeof(double)));
+    SLAM_TRY(g->d_occ_w.alloc(g->cells));
+    SLAM_TRY(g->d_num_s.alloc(g->cells * sizeof(double)));
+    SLAM_TRY(g->d_occ_s.alloc(g->cells));
+    SLAM_TRY(g->d_updates.alloc(kUpdateSlots * sizeof(unsigned long long)));
+    SLAM_TRY(g->d_dirty.alloc(8 * sizeof(int)));
     GridView &v = g->gv;
     v.sx = size_x;
     v.sy = size_y;
@@ -1351,26 +1317,13 @@ int slam_grid_create(int size_x, int size_y, double resolution, const slam_grid_
     v.updates = g->d_updates;
     v.dirty = g->d_dirty;
     v.acc_hits = v.acc_misses = nullptr;
-    rc = slam_grid_clear(g, nullptr);
-    if (rc == SLAM_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = SLAM_E_HIP;
-    if (rc != SLAM_OK) {
-        slam_grid_destroy(g);
-        return rc;
-    }
-    *out = g;
+    SLAM_TRY(slam_grid_clear(g, nullptr));
+    SLAM_HIP(hipStreamSynchronize(nullptr));
+    *out = guard.release();
     return SLAM_OK;
 }
 
-void slam_grid_destroy(slam_grid_t *g)
-{
-    if (!g) return;
-    void *ptrs[] = {g->d_planes, g->d_num_w, g->d_occ_w, g->d_num_s,     g->d_occ_s, g->d_delta,
-                    g->d_touched, g->d_updates, g->d_beams, g->d_chunk_box, g->d_stage,
-                    g->d_tile_cnt, g->d_tile_fill, g->d_cursor, g->d_items, g->d_dirty, g->d_acc};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    delete g;
-}
+void slam_grid_destroy(slam_grid_t *g) { delete g; }
 
 int slam_grid_clear(slam_grid_t *g, slam_stream_t stream)
 {
@@ -1402,7 +1355,7 @@ int slam_grid_enable_accumulator(slam_grid_t *g)
 {
     SLAM_REQUIRE(g, SLAM_E_INVALID, "null handle");
     if (g->d_acc) return SLAM_OK;
-    SLAM_HIP(hipMalloc((void **)&g->d_acc, 2 * g->cells * sizeof(int32_t)));
+    SLAM_TRY(g->d_acc.alloc(2 * g->cells * sizeof(int32_t)));
     SLAM_HIP(hipMemset(g->d_acc, 0, 2 * g->cells * sizeof(int32_t)));
     g->gv.acc_hits = g->d_acc;
     g->gv.acc_misses = g->d_acc + g->cells;
@@ -1532,8 +1485,8 @@ static int stage_points(slam_grid *g, const float *obs, int n_obs, const float *
                         float **d_obs, float **d_gnd)
 {
     const size_t bo = (size_t)n_obs * stride * sizeof(float), bg = (size_t)n_gnd * stride * sizeof(float);
-    SLAM_TRY(reserve(&g->d_stage, &g->cap_stage, bo + bg + 16));
-    *d_obs = static_cast<float *>(g->d_stage);
+    SLAM_TRY(reserve(g->d_stage, bo + bg + 16));
+    *d_obs = g->d_stage.as<float>();
     *d_gnd = *d_obs + (size_t)n_obs * stride;
     if (bo) SLAM_HIP(hipMemcpyAsync(*d_obs, obs, bo, hipMemcpyHostToDevice, nullptr));
     if (bg) SLAM_HIP(hipMemcpyAsync(*d_gnd, gnd, bg, hipMemcpyHostToDevice, nullptr));
@@ -1691,16 +1644,10 @@ int slam_grid_add_scan_inorder_dev(slam_grid_t *g, const float *d_obs, int n_obs
     if (n == 0) return SLAM_OK;
     hipStream_t st = as_stream(stream);
     if (!g->d_delta) {
-        SLAM_HIP(hipMalloc((void **)&g->d_delta, g->cells * sizeof(unsigned long long)));
+        SLAM_TRY(g->d_delta.alloc(g->cells * sizeof(unsigned long long)));
         SLAM_HIP(hipMemsetAsync(g->d_delta, 0, g->cells * sizeof(unsigned long long), st));
     }
-    {
-        void  *p = g->d_touched;
-        size_t cap = g->cap_touched;
-        SLAM_TRY(reserve(&p, &cap, ((size_t)n + 1) * sizeof(int)));
-        g->d_touched = static_cast<int *>(p);
-        g->cap_touched = cap;
-    }
+    SLAM_TRY(reserve(g->d_touched, ((size_t)n + 1) * sizeof(int)));
     int *counter = g->d_touched + n;
     SLAM_HIP(hipMemsetAsync(counter, 0, sizeof(int), st));
     hipLaunchKernelGGL(inorder_count_kernel, dim3((n + 255) / 256), dim3(256), 0, st, g->gv, d_obs, n_obs, d_gnd, n_gnd, stride,
@@ -1731,13 +1678,12 @@ int slam_grid_read_counts(slam_grid_t *g, int32_t *hits, int32_t *misses)
 {
     SLAM_REQUIRE(g && hits && misses, SLAM_E_INVALID, "slam_grid_read_counts: bad arguments");
     SLAM_TRY(require_device());
-    int32_t *tmp = nullptr;
-    SLAM_HIP(hipMalloc((void **)&tmp, 2 * g->cells * sizeof(int32_t)));
+    DevMem scratch; // (freed on every way out; hipFree waits for the launch)
+    SLAM_TRY(scratch.alloc(2 * g->cells * sizeof(int32_t)));
+    int32_t *tmp = scratch.as<int32_t>();
     hipLaunchKernelGGL(gather_counts_kernel, grid2d(g), dim3(256), 0, nullptr, g->gv, tmp, tmp + g->cells);
-    hipError_t e = hipMemcpy(hits, tmp, g->cells * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(misses, tmp + g->cells, g->cells * sizeof(int32_t), hipMemcpyDeviceToHost);
-    (void)hipFree(tmp);
-    SLAM_HIP(e);
+    SLAM_HIP(hipMemcpy(hits, tmp, g->cells * sizeof(int32_t), hipMemcpyDeviceToHost));
+    SLAM_HIP(hipMemcpy(misses, tmp + g->cells, g->cells * sizeof(int32_t), hipMemcpyDeviceToHost));
     return SLAM_OK;
 }
 

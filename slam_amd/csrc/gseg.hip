@@ -19,10 +19,11 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
-#include "common.hpp"
+#include "device_mem.hpp"
 
 using namespace slam;
 
@@ -535,30 +536,21 @@ __global__ __launch_bounds__(256) void ga_flag_kernel(const float *xyz, int n, i
 
 struct slam_gseg {
     GsegParams prm;
-    int       *d_count = nullptr;
-    unsigned long long *d_proto = nullptr;
-    unsigned char *d_state = nullptr;
-    double    *d_value = nullptr;
-    double    *d_scratch = nullptr; // [2][72][200*200] Cholesky factor + forward-substitution rows
-    int       *d_iters = nullptr;
-    int       *d_bin_of = nullptr;
-    size_t     cap_points = 0;
-    unsigned  *d_ga_occ = nullptr; // 1200 x 1200 occupancy of classifyPoints: the epoch of the last call that marked the cell; behind it
+    OwnedArray<int>                d_count;
+    OwnedArray<unsigned long long> d_proto;
+    OwnedArray<unsigned char>      d_state;
+    OwnedArray<double>             d_value;
+    OwnedArray<double>             d_scratch; // [2][72][200*200] Cholesky factor + forward-substitution rows
+    OwnedArray<int>                d_iters;
+    OwnedArray<int>                d_bin_of;
+    OwnedArray<unsigned> d_ga_occ; // 1200 x 1200 occupancy of classifyPoints: the epoch of the last call that marked the cell; behind it
                                    // the calls' state {epoch, workgroups through}, kept by the kernels
-    void      *d_stage = nullptr; // host-API staging: points + labels
-    size_t     cap_stage = 0;
+    DevMem     d_stage; // host-API staging: points + labels
 };
 
 static int gseg_reserve(slam_gseg *h, size_t n)
 {
-    if (n <= h->cap_points) return SLAM_OK;
-    const size_t want = n + n / 4; // (clouds of a sequence differ by a few per cent: grow rarely)
-    if (h->d_bin_of) (void)hipFree(h->d_bin_of);
-    h->d_bin_of = nullptr;
-    h->cap_points = 0;
-    SLAM_HIP(hipMalloc((void **)&h->d_bin_of, sizeof(int) * want));
-    h->cap_points = want;
-    return SLAM_OK;
+    return h->d_bin_of.reserve(sizeof(int) * n, sizeof(int) * (n + n / 4)); // (clouds of a sequence differ by a few per cent: grow rarely)
 }
 
 extern "C" {
@@ -596,31 +588,20 @@ int slam_gseg_create(const slam_gseg_params *params, slam_gseg_t **out)
     h->prm = {p.rmax, p.num_seedpoints, p.gp_lengthparameter, p.gp_covariancescale, p.gp_modelnoise,
               p.gp_groundmodelconfidence, p.gp_grounddataconfidence, p.gp_groundthreshold, p.robotheight,
               p.seeding_maxrange, p.seeding_maxheight};
-    hipError_t e = hipMalloc((void **)&h->d_count, sizeof(int) * NA * NL);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_proto, sizeof(unsigned long long) * NA * NL);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_state, NA * NL);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_value, sizeof(double) * NA * NL);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_scratch, sizeof(double) * 2 * (size_t)NA * NL * NL);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_iters, sizeof(int) * NA);
-    if (e == hipSuccess) e = hipMemset(h->d_count, 0, sizeof(int) * NA * NL);
-    if (e == hipSuccess) e = hipMemset(h->d_proto, 0xff, sizeof(unsigned long long) * NA * NL);
-    if (e != hipSuccess) {
-        slam_gseg_destroy(h);
-        SLAM_HIP(e);
-    }
-    *out = h;
+    std::unique_ptr<slam_gseg> guard(h); // an early return gives the handle and its buffers back
+    SLAM_TRY(h->d_count.alloc(sizeof(int) * NA * NL));
+    SLAM_TRY(h->d_proto.alloc(sizeof(unsigned long long) * NA * NL));
+    SLAM_TRY(h->d_state.alloc(NA * NL));
+    SLAM_TRY(h->d_value.alloc(sizeof(double) * NA * NL));
+    SLAM_TRY(h->d_scratch.alloc(sizeof(double) * 2 * (size_t)NA * NL * NL));
+    SLAM_TRY(h->d_iters.alloc(sizeof(int) * NA));
+    SLAM_HIP(hipMemset(h->d_count, 0, sizeof(int) * NA * NL));
+    SLAM_HIP(hipMemset(h->d_proto, 0xff, sizeof(unsigned long long) * NA * NL));
+    *out = guard.release();
     return SLAM_OK;
 }
 
-void slam_gseg_destroy(slam_gseg_t *h)
-{
-    if (!h) return;
-    void *ptrs[] = {h->d_count, h->d_proto, h->d_state, h->d_value, h->d_scratch, h->d_iters, h->d_bin_of, h->d_stage,
-                    h->d_ga_occ};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    delete h;
-}
+void slam_gseg_destroy(slam_gseg_t *h) { delete h; }
 
 int slam_gseg_reserve(slam_gseg_t *h, int max_points)
 {
@@ -656,16 +637,9 @@ int slam_gseg_segment(slam_gseg_t *h, const float *xyz, int n, int stride, uint8
     SLAM_TRY(require_device());
     if (n == 0) return SLAM_OK;
     const size_t bytes = sizeof(float) * (size_t)n * stride;
-    if (bytes + (size_t)n > h->cap_stage) {
-        if (h->d_stage) (void)hipFree(h->d_stage);
-        h->d_stage = nullptr;
-        h->cap_stage = 0;
-        const size_t want = bytes + (size_t)n + (bytes + (size_t)n) / 4;
-        SLAM_HIP(hipMalloc(&h->d_stage, want));
-        h->cap_stage = want;
-    }
-    float   *d_xyz = static_cast<float *>(h->d_stage);
-    uint8_t *d_lab = reinterpret_cast<uint8_t *>(h->d_stage) + bytes;
+    SLAM_TRY(reserve_quarter(h->d_stage, bytes + (size_t)n));
+    float   *d_xyz = h->d_stage.as<float>();
+    uint8_t *d_lab = h->d_stage.as<uint8_t>() + bytes;
     SLAM_HIP(hipMemcpyAsync(d_xyz, xyz, bytes, hipMemcpyHostToDevice, nullptr));
     SLAM_TRY(slam_gseg_segment_dev(h, d_xyz, n, stride, d_lab, nullptr));
     SLAM_HIP(hipMemcpyAsync(labels, d_lab, (size_t)n, hipMemcpyDeviceToHost, nullptr));
@@ -696,7 +670,7 @@ static int classify_ga(slam_gseg_t *h, const float *d_obstacle_xyz, int n, const
     hipStream_t st = as_stream(stream);
     constexpr size_t kCells = (size_t)kGaBins * kGaBins;
     if (!h->d_ga_occ) {
-        SLAM_HIP(hipMalloc((void **)&h->d_ga_occ, sizeof(unsigned) * (kCells + 2)));
+        SLAM_TRY(h->d_ga_occ.alloc(sizeof(unsigned) * (kCells + 2)));
         SLAM_HIP(hipMemsetAsync(h->d_ga_occ, 0, sizeof(unsigned) * (kCells + 2), st)); // no cell holds an epoch, no workgroup is through
         SLAM_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->d_ga_occ + kCells), 1, 1, st)); // the first call's epoch
     }

@@ -1229,9 +1229,6 @@ void destroy_unsynchronised(slam_icp *icp)
     release_index(icp);
     for (auto &e : icp->ev)
         if (e) (void)hipEventDestroy(e);
-    if (icp->d_normals) pool_free(icp->d_normals);
-    if (icp->d_lnormals) pool_free(icp->d_lnormals);
-    for (DevBuf *b : {&icp->w_pts, &icp->w_stamps, &icp->w_ew, &icp->w_state, &icp->w_single}) b->release();
     delete icp;
 }
 } // namespace icp
@@ -1428,7 +1425,7 @@ int slam_icp_build_info(slam_icp_t *icp, int *on_device, double ms[4])
 int slam_icp_index_blob(slam_icp_t *icp, int which, void *buf, size_t cap, size_t *bytes)
 {
     SLAM_REQUIRE(icp && (which == 0 || which == 1), SLAM_E_INVALID, "slam_icp_index_blob: bad arguments");
-    const void  *src = which == 0 ? icp->d_blob : (icp->have_lists ? icp->d_lblob : nullptr);
+    const void  *src = which == 0 ? icp->d_blob.p : (icp->have_lists ? icp->d_lblob.p : nullptr);
     const size_t n = which == 0 ? icp->mv.blob_bytes : (icp->have_lists ? icp->mv.lblob_bytes : 0);
     if (bytes) *bytes = n;
     if (!buf || n == 0) return SLAM_OK;
@@ -1608,9 +1605,9 @@ int slam_icp_nearest_dev(slam_icp_t *icp, int cls, const float *d_query_xy, int 
 int slam_icp_get_normals(slam_icp_t *icp, double *normals_xy)
 {
     SLAM_REQUIRE(icp && normals_xy, SLAM_E_INVALID, "slam_icp_get_normals: bad arguments");
-    SLAM_REQUIRE(icp->d_normals, SLAM_E_INVALID, "normals exist only in SLAM_ICP_P2L mode");
+    SLAM_REQUIRE(icp->d_normals.p, SLAM_E_INVALID, "normals exist only in SLAM_ICP_P2L mode");
     const size_t n = (size_t)icp->mv.n_cls[0] + icp->mv.n_cls[1];
-    SLAM_HIP(hipMemcpy(normals_xy, icp->d_normals, 2 * n * sizeof(double), hipMemcpyDeviceToHost));
+    SLAM_HIP(hipMemcpy(normals_xy, icp->d_normals.p, 2 * n * sizeof(double), hipMemcpyDeviceToHost));
     return SLAM_OK;
 }
 

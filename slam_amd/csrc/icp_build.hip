@@ -459,10 +459,9 @@ int build_lists_host(slam_icp *h, const std::vector<float> xy[2], const int cnt[
             for (size_t j = 0; j < ent.size(); ++j)
                 lpts[mv.lbase[c] + j] = make_float2(xy[c][2 * ent[j].pt], xy[c][2 * ent[j].pt + 1]);
         }
-        h->d_lblob = pool_alloc(mv.lblob_bytes);
-        if (!h->d_lblob) return SLAM_E_NOMEM;
-        SLAM_HIP(hipMemcpy(h->d_lblob, blob.data(), mv.lblob_bytes, hipMemcpyHostToDevice));
-        mv.lblob = static_cast<const unsigned char *>(h->d_lblob);
+        SLAM_TRY(h->d_lblob.alloc(mv.lblob_bytes));
+        SLAM_HIP(hipMemcpy(h->d_lblob.p, blob.data(), mv.lblob_bytes, hipMemcpyHostToDevice));
+        mv.lblob = h->d_lblob.as<const unsigned char>();
         list_done(h);
         return SLAM_OK;
     }
@@ -517,10 +516,9 @@ int build_index_host(slam_icp *h, const double *m_ga, int n_ga, const double *m_
     else
         fill_index_host<uint16_t>(blob, mv, xy, cell_of);
 
-    h->d_blob = pool_alloc(mv.blob_bytes);
-    if (!h->d_blob) return SLAM_E_NOMEM;
-    SLAM_HIP(hipMemcpy(h->d_blob, blob.data(), mv.blob_bytes, hipMemcpyHostToDevice));
-    mv.blob = static_cast<const unsigned char *>(h->d_blob);
+    SLAM_TRY(h->d_blob.alloc(mv.blob_bytes));
+    SLAM_HIP(hipMemcpy(h->d_blob.p, blob.data(), mv.blob_bytes, hipMemcpyHostToDevice));
+    mv.blob = h->d_blob.as<const unsigned char>();
     BBox bb_lists = bb;
     if (bb_lists.nfin == 0) {
         bb_lists.lo[0] = bb_lists.lo[1] = 0.f;
@@ -1422,7 +1420,7 @@ constexpr int kSortBigGrid = 512; // workgroups per class of list_sort_big_kerne
 // A build that has been enqueued and not yet adopted: its workspace (still in use by the device), the plan's pinned copy
 // and the event behind it
 struct slam_icp_pending {
-    std::vector<void *> blocks;   // pool blocks of the build
+    std::vector<slam::PoolMem> blocks; // the build's workspace
     DevPlan            *h_plan = nullptr; // pinned
     hipEvent_t          done = nullptr;
     hipStream_t         st = nullptr;
@@ -1435,9 +1433,9 @@ namespace {
 
 void *ws_get(slam_icp_pending *pb, size_t bytes)
 {
-    void *p = pool_alloc(bytes);
-    if (p) pb->blocks.push_back(p);
-    return p;
+    pb->blocks.emplace_back();
+    (void)pb->blocks.back().alloc(bytes);
+    return pb->blocks.back().p;
 }
 
 // gives the workspace back; wait = the device may still be using it
@@ -1452,7 +1450,6 @@ void drop_pending(slam_icp *h, bool wait)
             (void)hipStreamSynchronize(pb->st); // a begin that failed half-way: whatever it enqueued
         (void)hipGetLastError();
     }
-    for (void *p : pb->blocks) pool_free(p);
     if (pb->h_plan) pinned_block_put(pb->h_plan);
     if (pb->done) (void)hipEventDestroy(pb->done);
     delete pb;
@@ -1510,9 +1507,9 @@ int build_begin_device(slam_icp *h, const double *m_ga, int cap_ga, const double
         w.p2l_host_cnt[1] = cap_nga;
         w.p2l_all = static_cast<double2 *>(ws_get(pb, 16 * (size_t)std::max(cap_all, 1)));
         w.p2l_cnt = static_cast<int *>(ws_get(pb, 2 * sizeof(int)));
-        h->d_normals = static_cast<double *>(pool_alloc(16 * (size_t)std::max(cap_all, 1)));
-        if (!w.p2l_all || !w.p2l_cnt || !h->d_normals) return SLAM_E_NOMEM;
-        w.normals = h->d_normals;
+        SLAM_TRY(h->d_normals.alloc(16 * (size_t)std::max(cap_all, 1)));
+        if (!w.p2l_all || !w.p2l_cnt) return SLAM_E_NOMEM;
+        w.normals = h->d_normals.as<double>();
         w.m[0] = nullptr;
         w.m[1] = reinterpret_cast<const double *>(w.p2l_all);
         w.cap[0] = w.host_cnt[0] = 0;
@@ -1537,30 +1534,29 @@ int build_begin_device(slam_icp *h, const double *m_ga, int cap_ga, const double
     const int tiles_idx = scan_tiles_for(cb), tiles_lst = scan_tiles_for(lcb);
     w.tiles = static_cast<unsigned *>(ws_get(pb, 4 * 2 * (size_t)std::max(tiles_idx, tiles_lst)));
     w.ent = want_lists ? static_cast<int *>(ws_get(pb, 4 * 2 * (size_t)65536)) : nullptr;
-    h->d_blob = pool_alloc(pb->blob_cap);
-    h->d_lblob = want_lists ? pool_alloc(pb->lblob_cap) : nullptr;
+    (void)h->d_blob.alloc(pb->blob_cap);
+    if (want_lists) (void)h->d_lblob.alloc(pb->lblob_cap);
     pb->h_plan = static_cast<DevPlan *>(pinned_block_get(sizeof(DevPlan)));
-    if (!zero || !w.rows || !w.xyf || !w.cell_of || !w.tmp || !w.tiles || (want_lists && (!w.ent || !h->d_lblob)) || !h->d_blob || !pb->h_plan)
+    if (!zero || !w.rows || !w.xyf || !w.cell_of || !w.tmp || !w.tiles || (want_lists && (!w.ent || !h->d_lblob.p)) || !h->d_blob.p || !pb->h_plan)
         return SLAM_E_NOMEM;
     w.plan = reinterpret_cast<DevPlan *>(zero);
     w.cellcnt = reinterpret_cast<unsigned *>(zero + plan_bytes);
     w.lcnt = w.cellcnt + cnt_words;
-    w.blob = static_cast<unsigned char *>(h->d_blob);
-    w.lblob = static_cast<unsigned char *>(h->d_lblob);
+    w.blob = h->d_blob.as<unsigned char>();
+    w.lblob = h->d_lblob.as<unsigned char>();
     SLAM_HIP(hipEventCreateWithFlags(&pb->done, hipEventDisableTiming));
     if (p2l && want_lists) { // a normal per halo-list entry: as many as a list blob can hold at most
         w.lnormals_cap = (int)(pb->lblob_cap / 8);
-        h->d_lnormals = static_cast<double *>(pool_alloc(16 * (size_t)w.lnormals_cap));
-        if (!h->d_lnormals) return SLAM_E_NOMEM;
-        w.lnormals = reinterpret_cast<double2 *>(h->d_lnormals);
+        SLAM_TRY(h->d_lnormals.alloc(16 * (size_t)w.lnormals_cap));
+        w.lnormals = h->d_lnormals.as<double2>();
         w.p2l_lidx = static_cast<int *>(ws_get(pb, 4 * (size_t)w.lnormals_cap));
         if (!w.p2l_lidx) return SLAM_E_NOMEM;
     }
     if (p2l) hipLaunchKernelGGL(p2l_merge_kernel, dim3(pblocks), dim3(256), 0, st, w);
 
     SLAM_HIP(hipMemsetAsync(zero, 0, zero_bytes, st));
-    SLAM_HIP(hipMemsetAsync(h->d_blob, 0, pb->blob_cap, st)); // the padding between the arrays is part of the blob
-    if (want_lists) SLAM_HIP(hipMemsetAsync(h->d_lblob, 0, pb->lblob_cap, st));
+    SLAM_HIP(hipMemsetAsync(h->d_blob.p, 0, pb->blob_cap, st)); // the padding between the arrays is part of the blob
+    if (want_lists) SLAM_HIP(hipMemsetAsync(h->d_lblob.p, 0, pb->lblob_cap, st));
     hipLaunchKernelGGL(idx_bbox_kernel, dim3(pblocks), dim3(256), 0, st, w);
     hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(64), 0, st, w);
     hipLaunchKernelGGL(idx_count_kernel, dim3(pblocks), dim3(256), 0, st, w);
@@ -1649,20 +1645,19 @@ int build_index_finish(slam_icp *h)
     }
     if (rc == SLAM_OK) {
         adopt_index_plan(h, p.ip);
-        h->mv.blob = static_cast<const unsigned char *>(h->d_blob);
+        h->mv.blob = h->d_blob.as<const unsigned char>();
         if (p.pick >= 0) {
             adopt_list_plan(h, p.lp);
-            h->mv.lblob = static_cast<const unsigned char *>(h->d_lblob);
+            h->mv.lblob = h->d_lblob.as<const unsigned char>();
             list_done(h);
-        } else if (h->d_lblob) {
-            pool_free(h->d_lblob);
-            h->d_lblob = nullptr;
+        } else {
+            h->d_lblob.release();
         }
         h->max_cell_points = (int)p.most;
         h->built_on_device = true;
         if (h->prm.mode == SLAM_ICP_P2L) { // (made by the build's last kernels: p2l_normals_kernel, p2l_list_normals_kernel)
-            h->mv.normals = h->d_normals;
-            h->mv.lnormals = p.pick >= 0 ? reinterpret_cast<const double2 *>(h->d_lnormals) : nullptr;
+            h->mv.normals = h->d_normals.as<const double>();
+            h->mv.lnormals = p.pick >= 0 ? h->d_lnormals.as<const double2>() : nullptr;
         }
     }
     drop_pending(h, false);
@@ -1683,9 +1678,8 @@ int build_index(slam_icp *h, const double *m_ga, int n_ga, const double *m_nga, 
 void release_index(slam_icp *h)
 {
     drop_pending(h, true);
-    if (h->d_blob) pool_free(h->d_blob);
-    if (h->d_lblob) pool_free(h->d_lblob);
-    h->d_blob = h->d_lblob = nullptr;
+    h->d_blob.release();
+    h->d_lblob.release();
 }
 
 } // namespace icp

@@ -5,7 +5,7 @@
 #include <cfloat>
 #include <cstdint>
 
-#include "common.hpp"
+#include "device_mem.hpp"
 
 namespace slam {
 namespace icp {
@@ -94,34 +94,6 @@ __device__ inline IndexPtrs<StartT> make_ptrs(const unsigned char *base, const M
     return ix;
 }
 
-// A device buffer of a handle, taken from the library's pool (common.hpp): a handle is made per match
-// where the reference makes its matcher per match, so buffers must not cost a hipMalloc each.
-struct DevBuf {
-    void  *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes)
-    {
-        if (bytes <= cap) return SLAM_OK;
-        if (p) {
-            // the old block may still be in use by enqueued work
-            SLAM_HIP(hipDeviceSynchronize());
-            pool_free(p);
-        }
-        p = nullptr;
-        cap = 0;
-        p = pool_alloc(bytes);
-        if (!p) return SLAM_E_NOMEM;
-        cap = bytes;
-        return SLAM_OK;
-    }
-    void release() // the owner has synchronised with the device
-    {
-        if (p) pool_free(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 // Ordering key of a halo list: 0 = x, 1 = y, 2 = x + y, 3 = x - y (the diagonals serve lists bent around a corner,
 // where either axis would put a whole wall on one key).  Host and device evaluate the same float expression.
 __host__ __device__ inline float list_key(int dir, float x, float y)
@@ -154,14 +126,16 @@ struct slam_icp {
     bool            start32 = false;
     int             G = 8;
     int             sweep = 0;     // 0 ring search, 2 halo-list sweeps (list_search) for every iteration
-    void           *d_lblob = nullptr;
+    slam::PoolMem   d_lblob;
     size_t          list_lds_bytes = 0;
     bool            have_lists = false;
     size_t          lds_bytes = 0;
-    void           *d_blob = nullptr;
-    double         *d_normals = nullptr;
-    double         *d_lnormals = nullptr; // normals per halo-list entry (P2L)
-    slam::icp::DevBuf          w_pts, w_stamps, w_ew, w_state, w_single; // w_pts: slam_icp_fit's block (points + header)
+    // pool blocks (common.hpp): a handle is made per match where the reference makes its matcher per match, so buffers
+    // must not cost a hipMalloc each
+    slam::PoolMem   d_blob;
+    slam::PoolMem   d_normals;
+    slam::PoolMem   d_lnormals; // normals per halo-list entry (P2L)
+    slam::PoolMem   w_pts, w_stamps, w_ew, w_state, w_single; // w_pts: slam_icp_fit's block (points + header)
     int             spread_points_hint = 0; // points of the batch when the caller knows them (slam_icp_fit), else 0
     size_t          step_pose_off = 0;   // where in w_pts the pose of the last executed step lies
     bool            two_phase = false;   // ring search, then list sweeps (the point-to-point default)

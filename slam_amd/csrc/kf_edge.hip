@@ -17,7 +17,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "common.hpp"
+#include "device_mem.hpp"
 
 using namespace slam;
 
@@ -594,29 +594,10 @@ __global__ __launch_bounds__(kEdgeThreads) void kf_edge_kernel(const EdgeTask *t
     }
 }
 
-struct GrowBuf {
-    void  *p = nullptr;
-    size_t cap = 0;
-    int    reserve(size_t bytes)
-    {
-        if (bytes <= cap) return SLAM_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr, cap = 0;
-        SLAM_HIP(hipMalloc(&p, bytes + bytes / 4));
-        cap = bytes + bytes / 4;
-        return SLAM_OK;
-    }
-    ~GrowBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
-
 struct Keyframe {
-    void  *block = nullptr; // pts | sorted | table
+    DevMem block; // pts | sorted | table
     KfView view{};
     int    n_cells = 0, max_cell = 0;
-    size_t bytes = 0;
 };
 
 } // namespace
@@ -626,13 +607,8 @@ struct slam_kf {
     slam_ccicp_t         *cc = nullptr;
     std::vector<Keyframe> kfs;
     bool                  lds_enabled = false;
-    GrowBuf               in, filtered, keys, sort_tmp, work, stats; // add_keyframe's; `work` also holds a call's tasks, results, pairs
-    ~slam_kf()
-    {
-        for (Keyframe &k : kfs)
-            if (k.block) (void)hipFree(k.block);
-        slam_ccicp_destroy(cc);
-    }
+    DevMem                in, filtered, keys, sort_tmp, work, stats; // add_keyframe's; `work` also holds a call's tasks, results, pairs
+    ~slam_kf() { slam_ccicp_destroy(cc); }
 };
 
 namespace {
@@ -675,7 +651,7 @@ int slam_kf_create(const slam_kf_params *params, slam_kf_t **out)
     SLAM_REQUIRE(s, SLAM_E_NOMEM, "slam_kf_create: out of host memory");
     s->p = p;
     int rc = slam_ccicp_create(&s->cc);
-    if (rc == SLAM_OK) rc = s->stats.reserve(64);
+    if (rc == SLAM_OK) rc = reserve_quarter(s->stats, 64);
     if (rc != SLAM_OK) {
         delete s;
         return rc;
@@ -703,7 +679,7 @@ int slam_kf_add_keyframe_dev(slam_kf_t *s, const float *d_xyz, int n, int stride
     SLAM_REQUIRE(s && id && n > 0 && stride >= 3 && d_xyz, SLAM_E_INVALID, "slam_kf_add_keyframe_dev: bad arguments");
     *id = -1;
     hipStream_t st = as_stream(stream);
-    SLAM_TRY(s->filtered.reserve(sizeof(float4) * (size_t)n));
+    SLAM_TRY(reserve_quarter(s->filtered, sizeof(float4) * (size_t)n));
     int         m = 0;
     const float leaf = (float)s->p.leaf_size;
     SLAM_TRY(slam_ccicp_voxel_downsample_dev(s->cc, d_xyz, nullptr, n, stride, leaf, leaf, leaf, static_cast<float *>(s->filtered.p), n, &m, stream));
@@ -711,42 +687,31 @@ int slam_kf_add_keyframe_dev(slam_kf_t *s, const float *d_xyz, int n, int stride
     unsigned slots = 64;
     while (slots < 2u * (unsigned)m) slots <<= 1;
     Keyframe kf;
-    kf.bytes = sizeof(float4) * 2 * (size_t)m + sizeof(int4) * (size_t)slots;
-    SLAM_HIP(hipMalloc(&kf.block, kf.bytes));
-    float4 *pts = static_cast<float4 *>(kf.block), *sorted = pts + m;
+    SLAM_TRY(kf.block.alloc(sizeof(float4) * 2 * (size_t)m + sizeof(int4) * (size_t)slots));
+    float4 *pts = kf.block.as<float4>(), *sorted = pts + m;
     int4   *table = reinterpret_cast<int4 *>(sorted + m);
     kf.view = KfView{pts, sorted, table, slots - 1, m};
-    int rc = s->keys.reserve((sizeof(unsigned long long) + sizeof(uint32_t)) * 2 * (size_t)m);
-    unsigned long long *keys = static_cast<unsigned long long *>(s->keys.p), *keys_s = keys + m;
+    SLAM_TRY(reserve_quarter(s->keys, (sizeof(unsigned long long) + sizeof(uint32_t)) * 2 * (size_t)m));
+    unsigned long long *keys = s->keys.as<unsigned long long>(), *keys_s = keys + m;
     uint32_t           *vals = reinterpret_cast<uint32_t *>(keys_s + m), *vals_s = vals + m;
     size_t              tb = 0;
-    hipError_t          e = hipSuccess;
-    if (rc == SLAM_OK) {
-        e = rocprim::radix_sort_pairs(nullptr, tb, keys, keys_s, vals, vals_s, (size_t)m, 0, 63, st);
-        if (e == hipSuccess) rc = s->sort_tmp.reserve(tb + 16);
-    }
-    int *stats = static_cast<int *>(s->stats.p);
+    SLAM_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys, keys_s, vals, vals_s, (size_t)m, 0, 63, st));
+    SLAM_TRY(reserve_quarter(s->sort_tmp, tb + 16));
+    int *stats = s->stats.as<int>();
     int  got[2] = {0, 0};
-    if (rc == SLAM_OK && e == hipSuccess) e = hipMemcpyAsync(pts, s->filtered.p, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, st);
-    if (rc == SLAM_OK && e == hipSuccess) e = hipMemsetAsync(table, 0xff, sizeof(int4) * (size_t)slots, st);
-    if (rc == SLAM_OK && e == hipSuccess) e = hipMemsetAsync(stats, 0, 2 * sizeof(int), st);
-    if (rc == SLAM_OK && e == hipSuccess) {
-        hipLaunchKernelGGL(kf_key_kernel, dim3(blocks(m, 256)), dim3(256), 0, st, pts, m, inv_cell(s->p), keys, vals);
-        e = hipGetLastError();
-    }
-    if (rc == SLAM_OK && e == hipSuccess) e = rocprim::radix_sort_pairs(s->sort_tmp.p, tb, keys, keys_s, vals, vals_s, (size_t)m, 0, 63, st);
-    if (rc == SLAM_OK && e == hipSuccess) {
-        hipLaunchKernelGGL(kf_table_kernel, dim3(blocks(m, 256)), dim3(256), 0, st, pts, keys_s, vals_s, m, sorted, table, slots - 1, stats);
-        e = hipGetLastError();
-    }
-    if (rc == SLAM_OK && e == hipSuccess) e = hipMemcpyAsync(got, stats, sizeof got, hipMemcpyDeviceToHost, st);
-    if (rc == SLAM_OK && e == hipSuccess) e = hipStreamSynchronize(st);
-    if (rc != SLAM_OK || e != hipSuccess) {
-        (void)hipFree(kf.block);
-        return rc != SLAM_OK ? rc : hip_fail(e, "slam_kf_add_keyframe_dev", __FILE__, __LINE__);
-    }
+    // (a failure below frees the keyframe's block on the way out: hipFree waits for what has been enqueued on it)
+    SLAM_HIP(hipMemcpyAsync(pts, s->filtered.p, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, st));
+    SLAM_HIP(hipMemsetAsync(table, 0xff, sizeof(int4) * (size_t)slots, st));
+    SLAM_HIP(hipMemsetAsync(stats, 0, 2 * sizeof(int), st));
+    hipLaunchKernelGGL(kf_key_kernel, dim3(blocks(m, 256)), dim3(256), 0, st, pts, m, inv_cell(s->p), keys, vals);
+    SLAM_HIP(hipGetLastError());
+    SLAM_HIP(rocprim::radix_sort_pairs(s->sort_tmp.p, tb, keys, keys_s, vals, vals_s, (size_t)m, 0, 63, st));
+    hipLaunchKernelGGL(kf_table_kernel, dim3(blocks(m, 256)), dim3(256), 0, st, pts, keys_s, vals_s, m, sorted, table, slots - 1, stats);
+    SLAM_HIP(hipGetLastError());
+    SLAM_HIP(hipMemcpyAsync(got, stats, sizeof got, hipMemcpyDeviceToHost, st));
+    SLAM_HIP(hipStreamSynchronize(st));
     kf.n_cells = got[0], kf.max_cell = got[1];
-    s->kfs.push_back(kf);
+    s->kfs.push_back(std::move(kf));
     *id = (int)s->kfs.size() - 1;
     return SLAM_OK;
 }
@@ -755,7 +720,7 @@ int slam_kf_add_keyframe(slam_kf_t *s, const float *xyz, int n, int stride, int 
 {
     SLAM_REQUIRE(s && id && n > 0 && stride >= 3 && xyz, SLAM_E_INVALID, "slam_kf_add_keyframe: bad arguments");
     const size_t bytes = sizeof(float) * (size_t)n * stride;
-    SLAM_TRY(s->in.reserve(bytes));
+    SLAM_TRY(reserve_quarter(s->in, bytes));
     SLAM_HIP(hipMemcpy(s->in.p, xyz, bytes, hipMemcpyHostToDevice));
     return slam_kf_add_keyframe_dev(s, static_cast<const float *>(s->in.p), n, stride, id, nullptr);
 }
@@ -768,7 +733,7 @@ int slam_kf_keyframe_info(slam_kf_t *s, int id, int *n_points, int *n_cells, int
     if (n_cells) *n_cells = k.n_cells;
     if (max_cell_points) *max_cell_points = k.max_cell;
     if (table_slots) *table_slots = (int)(k.view.mask + 1);
-    if (device_bytes) *device_bytes = (long)k.bytes;
+    if (device_bytes) *device_bytes = (long)k.block.cap;
     return SLAM_OK;
 }
 
@@ -813,7 +778,7 @@ int slam_kf_register_edges_traced(slam_kf_t *s, const slam_kf_edge_req *req, int
     const size_t trace_b = sizeof(int32_t) * (size_t)n_edges * trace_cap, corr_b = sizeof(int32_t) * n_corr;
     const size_t res_off = (task_b + 255) & ~(size_t)255, trace_off = res_off + ((res_b + 255) & ~(size_t)255);
     const size_t corr_off = trace_off + ((trace_b + 255) & ~(size_t)255);
-    SLAM_TRY(s->work.reserve(corr_off + corr_b));
+    SLAM_TRY(reserve_quarter(s->work, corr_off + corr_b));
     char *host = static_cast<char *>(pinned_scratch(corr_off));
     SLAM_REQUIRE(host, SLAM_E_NOMEM, "slam_kf_register_edges: no pinned staging memory");
     char     *dev = static_cast<char *>(s->work.p);

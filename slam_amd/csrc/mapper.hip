@@ -195,11 +195,11 @@ __global__ __launch_bounds__(kThinScan) void thin_scan_kernel(const unsigned *cn
 }
 
 struct Slot {
-    double  *d_pts = nullptr, *d_R = nullptr, *d_t = nullptr;
-    int32_t *d_off = nullptr, *d_nga = nullptr, *d_gab = nullptr;
+    OwnedArray<double>  d_pts, d_R, d_t;
+    OwnedArray<int32_t> d_off, d_nga, d_gab;
     // pinned staging the producer fills
-    double  *h_pts = nullptr, *h_R = nullptr, *h_t = nullptr;
-    int32_t *h_off = nullptr, *h_nga = nullptr, *h_gab = nullptr;
+    OwnedArray<double, Mem::Pinned>  h_pts, h_R, h_t;
+    OwnedArray<int32_t, Mem::Pinned> h_off, h_nga, h_gab;
     hipEvent_t copied = nullptr, fitted = nullptr, registered = nullptr, mapped = nullptr; // fitted: behind the registration
                                                                                           // launch; registered: poses on the host
     bool     busy = false;
@@ -209,7 +209,7 @@ struct Slot {
 constexpr int kMaxSlots = 8;
 
 struct WindowEntry {
-    double2 *ga = nullptr, *nga = nullptr; // device, room for max_points each
+    OwnedArray<double2> ga, nga;           // room for max_points each
     int      n_ga = 0, n_nga = 0;
     long     chunk = -1;                   // which chunk lies here
     hipEvent_t ready = nullptr;            // recorded behind the kernel that filled it
@@ -234,13 +234,12 @@ struct slam_mapper {
     long               chunks = 0, merges = 0, rebuilds = 0, last_rebuild = -1;
     std::vector<WindowEntry> window;
     std::vector<double> prior_ga, prior_nga; // host copies of the model given at create
-    double            *d_model_ga = nullptr, *d_model_nga = nullptr; // [prior | window part] per class
-    size_t             cap_model = 0;          // points reserved (both classes)
-    unsigned          *d_thin = nullptr;      // [nx*ny] lowest window rank per lattice cell (one class after the other); all ones
+    OwnedArray<double, Mem::Pool> d_model_ga; // [prior | window part] per class, both classes in one block
+    double            *d_model_nga = nullptr; // where class NGA begins in it
+    OwnedArray<unsigned> d_thin;              // [nx*ny] lowest window rank per lattice cell (one class after the other); all ones
                                               // between rebuilds: every rebuild's winners put their cells back (thin_pick_kernel<1>)
     bool               thin_dirty = false;    // a rebuild was abandoned half-way: fill the lattice before the next one
-    unsigned          *d_thin_blk = nullptr;  // [2][blocks + blocks + 1] winners per block, their prefix, the total
-    size_t             cap_thin_blk = 0;
+    OwnedArray<unsigned> d_thin_blk;          // [2][blocks + blocks + 1] winners per block, their prefix, the total
     slam_mapper_merge_fn merge_begin = nullptr, merge_finish = nullptr;
     void              *merge_ctx = nullptr;
     bool               merge_pending = false;
@@ -250,7 +249,7 @@ struct slam_mapper {
     int                max_lag = 0;            // pushes a build may stay un-adopted (0: every rebuild is waited for at once)
     slam_icp_t        *building = nullptr;     // the target whose build is enqueued and not yet adopted
     long               building_chunk = 0;     // m->chunks when it was begun
-    int               *d_cnt = nullptr;        // points per class of the model being built (the thinning leaves them here)
+    OwnedArray<int>    d_cnt;                  // points per class of the model being built (the thinning leaves them here)
     size_t             model_prior[2] = {0, 0}; // prior points resident at the head of d_model_ga / d_model_nga
 };
 
@@ -356,20 +355,17 @@ int thin_class(slam_mapper *m, const std::vector<const WindowEntry *> &use, int 
     const size_t cells = (size_t)g.nx * g.ny;
     const int    blocks = (s.total + 255) / 256;
     if (!m->d_thin) {
-        MAP_HIP(hipMalloc((void **)&m->d_thin, 4 * cells));
+        SLAM_TRY(m->d_thin.alloc(4 * cells));
         m->thin_dirty = true;
     }
     if (m->thin_dirty) {
         MAP_HIP(hipMemsetAsync(m->d_thin, 0xff, 4 * cells, st));
         m->thin_dirty = false;
     }
-    if ((size_t)(2 * blocks + 1) > m->cap_thin_blk) {
-        if (m->d_thin_blk) {
-            MAP_HIP(hipStreamSynchronize(st)); // (grows once or twice in a mapper's life)
-            (void)hipFree(m->d_thin_blk);
-        }
-        m->cap_thin_blk = (size_t)(2 * blocks + 1) * 2;
-        MAP_HIP(hipMalloc((void **)&m->d_thin_blk, 4 * m->cap_thin_blk));
+    const size_t blk_bytes = 4 * (size_t)(2 * blocks + 1);
+    if (blk_bytes > m->d_thin_blk.cap) {
+        if (m->d_thin_blk) MAP_HIP(hipStreamSynchronize(st)); // (grows once or twice in a mapper's life)
+        SLAM_TRY(m->d_thin_blk.reserve(blk_bytes, 2 * blk_bytes));
     }
     unsigned *cnt = m->d_thin_blk, *off = cnt + blocks, *total = off + blocks;
     // (the lattice is all ones: filled when it was allocated, and every rebuild's winners put it back, thin_pick_kernel<1>)
@@ -421,17 +417,16 @@ int begin_rebuild(slam_mapper *m, hipStream_t st)
     if (!thin && cap_ga + cap_nga < 5) return SLAM_OK;
     for (const WindowEntry *w : use) MAP_HIP(hipStreamWaitEvent(st, w->ready, 0));
     dt("rebuild>", st);
-    if (cap_ga + cap_nga > m->cap_model || !m->d_model_ga) {
+    const size_t model_bytes = 16 * (cap_ga + cap_nga);
+    if (model_bytes > m->d_model_ga.cap) {
         if (m->d_model_ga) {
             MAP_HIP(hipStreamSynchronize(st)); // an earlier build may still read the old block (grows once or twice)
-            pool_free(m->d_model_ga);
+            m->d_model_ga.release();
         }
-        m->cap_model = (cap_ga + cap_nga) * 2;
-        m->d_model_ga = static_cast<double *>(pool_alloc(16 * m->cap_model));
-        if (!m->d_model_ga) return SLAM_E_NOMEM;
+        SLAM_TRY(m->d_model_ga.reserve(model_bytes, 2 * model_bytes));
         m->model_prior[0] = m->model_prior[1] = (size_t)-1;
     }
-    if (!m->d_cnt) MAP_HIP(hipMalloc((void **)&m->d_cnt, 2 * sizeof(int)));
+    if (!m->d_cnt) SLAM_TRY(m->d_cnt.alloc(2 * sizeof(int)));
     // class GA at the head of the block, class NGA behind GA's reservation; the prior's points go in when the layout changes
     double *d_ga = m->d_model_ga, *d_nga = m->d_model_ga + 2 * cap_ga;
     if (m->model_prior[0] != p_ga || m->model_prior[1] != p_nga || m->d_model_nga != d_nga) {
@@ -565,6 +560,9 @@ int slam_mapper_create(const slam_mapper_params *params, const double *m_ga, int
     auto hip = [&](hipError_t e) {
         if (rc == SLAM_OK && e != hipSuccess) rc = hip_fail(e, "slam_mapper_create", __FILE__, __LINE__);
     };
+    auto own = [&](auto &buf, size_t bytes) {
+        if (rc == SLAM_OK) rc = buf.alloc(bytes);
+    };
     if (rc == SLAM_OK) {
         m->prior_ga.assign(m_ga, m_ga + 2 * (size_t)n_ga);
         m->prior_nga.assign(m_nga, m_nga + 2 * (size_t)n_nga);
@@ -634,18 +632,18 @@ int slam_mapper_create(const slam_mapper_params *params, const double *m_ga, int
         m->n_slots = params->slots >= 2 && params->slots <= kMaxSlots ? params->slots : 5;
         for (int k = 0; k < m->n_slots; ++k) {
             Slot &b = m->slot[k];
-            hip(hipMalloc((void **)&b.d_pts, 16 * np));
-            hip(hipMalloc((void **)&b.d_off, 4 * (ns + 1)));
-            hip(hipMalloc((void **)&b.d_nga, 4 * ns));
-            hip(hipMalloc((void **)&b.d_gab, 4 * (ns + 1)));
-            hip(hipMalloc((void **)&b.d_R, 32 * ns));
-            hip(hipMalloc((void **)&b.d_t, 16 * ns));
-            hip(hipHostMalloc((void **)&b.h_pts, 16 * np, hipHostMallocDefault));
-            hip(hipHostMalloc((void **)&b.h_off, 4 * (ns + 1), hipHostMallocDefault));
-            hip(hipHostMalloc((void **)&b.h_nga, 4 * ns, hipHostMallocDefault));
-            hip(hipHostMalloc((void **)&b.h_gab, 4 * (ns + 1), hipHostMallocDefault));
-            hip(hipHostMalloc((void **)&b.h_R, 32 * ns, hipHostMallocDefault));
-            hip(hipHostMalloc((void **)&b.h_t, 16 * ns, hipHostMallocDefault));
+            own(b.d_pts, 16 * np);
+            own(b.d_off, 4 * (ns + 1));
+            own(b.d_nga, 4 * ns);
+            own(b.d_gab, 4 * (ns + 1));
+            own(b.d_R, 32 * ns);
+            own(b.d_t, 16 * ns);
+            own(b.h_pts, 16 * np);
+            own(b.h_off, 4 * (ns + 1));
+            own(b.h_nga, 4 * ns);
+            own(b.h_gab, 4 * (ns + 1));
+            own(b.h_R, 32 * ns);
+            own(b.h_t, 16 * ns);
             hip(hipEventCreateWithFlags(&b.copied, hipEventDisableTiming));
             hip(hipEventCreateWithFlags(&b.fitted, hipEventDisableTiming));
             hip(hipEventCreateWithFlags(&b.registered, hipEventDisableTiming));
@@ -662,8 +660,8 @@ int slam_mapper_create(const slam_mapper_params *params, const double *m_ga, int
         const size_t per = params->thin_res > 0 ? (size_t)params->max_points
                                                 : (size_t)std::max(64, params->target_points / std::max(2 * params->window_chunks, 1)) + 8;
         for (WindowEntry &w : m->window) {
-            hip(hipMalloc((void **)&w.ga, 16 * per));
-            hip(hipMalloc((void **)&w.nga, 16 * per));
+            own(w.ga, 16 * per);
+            own(w.nga, 16 * per);
             hip(hipEventCreateWithFlags(&w.ready, hipEventDisableTiming));
         }
     }
@@ -681,22 +679,11 @@ void slam_mapper_destroy(slam_mapper_t *m)
     (void)hipDeviceSynchronize();
     if (m->building) slam_icp_destroy(m->building);
     for (Slot &b : m->slot) {
-        for (void *p : {(void *)b.d_pts, (void *)b.d_off, (void *)b.d_nga, (void *)b.d_gab, (void *)b.d_R, (void *)b.d_t})
-            if (p) (void)hipFree(p);
-        for (void *p : {(void *)b.h_pts, (void *)b.h_off, (void *)b.h_nga, (void *)b.h_gab, (void *)b.h_R, (void *)b.h_t})
-            if (p) (void)hipHostFree(p);
         for (hipEvent_t e : {b.copied, b.fitted, b.registered, b.mapped})
             if (e) (void)hipEventDestroy(e);
     }
-    for (WindowEntry &w : m->window) {
-        if (w.ga) (void)hipFree(w.ga);
-        if (w.nga) (void)hipFree(w.nga);
+    for (WindowEntry &w : m->window)
         if (w.ready) (void)hipEventDestroy(w.ready);
-    }
-    if (m->d_model_ga) pool_free(m->d_model_ga);
-    for (void *p : {(void *)m->d_thin, (void *)m->d_thin_blk, (void *)m->d_cnt})
-        if (p) (void)hipFree(p);
-
     if (m->target) slam_icp_destroy(m->target);
     if (m->retired) slam_icp_destroy(m->retired);
     if (m->grid) slam_grid_destroy(m->grid);
@@ -711,7 +698,7 @@ void slam_mapper_destroy(slam_mapper_t *m)
     if (!one && m->grid_s) (void)hipStreamDestroy(m->grid_s);
     if (m->build_s && m->build_s != m->copy && m->build_s != m->icp_s[0] && m->build_s != m->grid_s) (void)hipStreamDestroy(m->build_s);
     if (m->post_s && m->post_s != m->copy && m->post_s != m->icp_s[0] && m->post_s != m->grid_s) (void)hipStreamDestroy(m->post_s);
-    delete m;
+    delete m; // the buffers of the slots, the window and the model go with it
 }
 
 int slam_mapper_chunk_buffers(slam_mapper_t *m, int slot, double **pts, int32_t **scan_off, int32_t **scan_nga, double **R0,
@@ -821,7 +808,7 @@ int slam_mapper_push(slam_mapper_t *m, int n_scans, int n_points, double window_
         // (no wait for a rebuild in flight: it reads the entries of the window_chunks chunks before the push it was begun at,
         // the ring holds 1 + max_lag entries more than that, and a build is adopted -- complete -- before max_lag pushes have passed)
         hipLaunchKernelGGL(window_points_kernel, dim3((n_points + 255) / 256), dim3(256), 0, post_s,
-                           reinterpret_cast<const double2 *>(b.d_pts), b.d_off, b.d_nga, b.d_gab, n_scans, n_points, b.d_R, b.d_t, sg, sn,
+                           b.d_pts.as<const double2>(), b.d_off, b.d_nga, b.d_gab, n_scans, n_points, b.d_R, b.d_t, sg, sn,
                            w.ga, w.nga);
         MAP_HIP(hipGetLastError());
         w.n_ga = (n_ga + sg - 1) / sg;

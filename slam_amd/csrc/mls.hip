@@ -23,12 +23,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include <rocprim/rocprim.hpp>
 
-#include "common.hpp"
+#include "device_mem.hpp"
 #include "grid_cell.hpp"
 
 using namespace slam;
@@ -418,6 +419,25 @@ inline int blocks(long n, int t) { return (int)((n + t - 1) / t); }
 // the host stays a call ahead of the device and the bound below stays within m + kInFlight clouds
 constexpr int kInFlight = 2;
 
+namespace {
+// The pending store: [0, m) carried points, sorted by cell (two buffers, swapped by every call), and the scratch of a call
+struct Store {
+    size_t               cap = 0; // points
+    OwnedArray<float4>   pts[2];
+    OwnedArray<uint32_t> keys[2];
+    OwnedArray<uint32_t> vals_in, keys_s, vals_s, sel;
+    OwnedArray<uint8_t>  stage;
+    OwnedArray<Walk>     walk[2];
+    OwnedArray<int32_t>  claimed;
+    DevMem               tmp; // rocprim's scratch (sort and select)
+};
+// Last declared of a call's locals, so first destroyed: the scoped pool blocks declared before it go back to the pool
+// (which does not wait) only after the device has finished with them, on every way out.
+struct DeviceWait {
+    ~DeviceWait() { (void)hipDeviceSynchronize(); }
+};
+} // namespace
+
 struct slam_mls {
     int             sx = 0, sy = 0, cap = 0;
     double          res = 0;
@@ -425,29 +445,19 @@ struct slam_mls {
     double          pose_x = 0, pose_y = 0;
     uint32_t        inv = 0;
     int             key_bits = 0;
-    Slot           *slots = nullptr;
-    int32_t        *cnt = nullptr, *upd = nullptr, *pstart = nullptr, *pend = nullptr;
-    int8_t         *drv = nullptr, *byte = nullptr;
-    // the pending store: [0, m) carried points, sorted by cell (two buffers, swapped by every call)
-    size_t    pcap = 0;
-    float4   *pts[2] = {nullptr, nullptr};
-    uint32_t *keys[2] = {nullptr, nullptr};
-    int       cur = 0;
-    uint32_t *vals_in = nullptr, *keys_s = nullptr, *vals_s = nullptr, *sel = nullptr;
-    uint8_t  *stage = nullptr;
-    Walk     *walk[2] = {nullptr, nullptr};
-    int32_t  *claimed = nullptr;
-    uint32_t *d_ctr = nullptr; // [0] m, [1] blocked walks
-    void     *tmp = nullptr;
-    size_t    tmp_bytes = 0;
+    OwnedArray<Slot>    slots;
+    OwnedArray<int32_t> cnt, upd, pstart, pend;
+    OwnedArray<int8_t>  drv, byte;
+    Store     store;
+    int       cur = 0; // which of the store's two buffers holds the carried points
+    OwnedArray<uint32_t> d_ctr; // [0] m, [1] blocked walks
     // what the host knows of m without waiting: every call (add, clear) copies m into a pinned slot and records an event;
     // calls [seen, seq) are still in flight, `known` is m after call seen - 1, and each call in flight adds at most its n
-    uint32_t  *h_m = nullptr; // pinned [kInFlight]
+    OwnedArray<uint32_t, Mem::Pinned> h_m; // [kInFlight]
     hipEvent_t ev[kInFlight] = {};
     long       n_of[kInFlight] = {};
     long       seq = 0, seen = 0, known = 0;
-    float     *d_in = nullptr; // the host form's upload
-    size_t     d_in_cap = 0;
+    OwnedArray<float> d_in; // the host form's upload
 };
 
 namespace {
@@ -457,8 +467,8 @@ View view_of(slam_mls *m)
     View v;
     v.sx = m->sx, v.sy = m->sy, v.cap = m->cap;
     v.slots = m->slots, v.cnt = m->cnt, v.drv = m->drv, v.byte = m->byte, v.upd = m->upd, v.pstart = m->pstart, v.pend = m->pend;
-    v.pts = m->pts[m->cur];
-    v.vals = m->vals_s;
+    v.pts = m->store.pts[m->cur];
+    v.vals = m->store.vals_s;
     const slam_mls_params &q = m->p;
     v.p = Prm{q.max_range, q.normal_threshold, q.height_threshold, q.cluster_sigma_factor, q.cluster_dist_threshold,
               q.cluster_combine_dist, q.drive_dist_threshold, q.robot_height, (double)q.min_cluster_points,
@@ -480,59 +490,35 @@ Window window_of(const slam_mls *m)
     return w;
 }
 
-void free_store(slam_mls *m)
-{
-    for (int b = 0; b < 2; ++b) {
-        (void)hipFree(m->pts[b]), (void)hipFree(m->keys[b]), (void)hipFree(m->walk[b]);
-        m->pts[b] = nullptr, m->keys[b] = nullptr, m->walk[b] = nullptr;
-    }
-    for (void *p : {(void *)m->vals_in, (void *)m->keys_s, (void *)m->vals_s, (void *)m->sel, (void *)m->stage, (void *)m->claimed, m->tmp})
-        (void)hipFree(p);
-    m->vals_in = m->keys_s = m->vals_s = m->sel = nullptr;
-    m->stage = nullptr, m->claimed = nullptr, m->tmp = nullptr;
-    m->tmp_bytes = 0;
-    m->pcap = 0;
-}
-
 // A pending store of `want` items, keeping the m carried points of the current one (the stream has been waited for).
 int grow_store(slam_mls *m, size_t want, uint32_t carried)
 {
-    slam_mls old = {};
-    for (int b = 0; b < 2; ++b) old.pts[b] = m->pts[b], old.keys[b] = m->keys[b], old.walk[b] = m->walk[b];
-    old.vals_in = m->vals_in, old.keys_s = m->keys_s, old.vals_s = m->vals_s, old.sel = m->sel, old.stage = m->stage,
-    old.claimed = m->claimed, old.tmp = m->tmp;
-    const int cur = m->cur;
-    slam_mls  nw = {};
-    bool      ok = true;
+    Store nw; // (gives back what it got so far if the rest cannot be had)
+    bool  ok = true;
     for (int b = 0; b < 2 && ok; ++b)
-        ok = hipMalloc((void **)&nw.pts[b], want * sizeof(float4)) == hipSuccess &&
-             hipMalloc((void **)&nw.keys[b], want * sizeof(uint32_t)) == hipSuccess &&
-             hipMalloc((void **)&nw.walk[b], want * sizeof(Walk)) == hipSuccess;
-    ok = ok && hipMalloc((void **)&nw.vals_in, want * 4) == hipSuccess && hipMalloc((void **)&nw.keys_s, want * 4) == hipSuccess &&
-         hipMalloc((void **)&nw.vals_s, want * 4) == hipSuccess && hipMalloc((void **)&nw.sel, want * 4) == hipSuccess &&
-         hipMalloc((void **)&nw.stage, want) == hipSuccess && hipMalloc((void **)&nw.claimed, want * 4) == hipSuccess;
+        ok = nw.pts[b].alloc(want * sizeof(float4)) == SLAM_OK && nw.keys[b].alloc(want * sizeof(uint32_t)) == SLAM_OK &&
+             nw.walk[b].alloc(want * sizeof(Walk)) == SLAM_OK;
+    ok = ok && nw.vals_in.alloc(want * 4) == SLAM_OK && nw.keys_s.alloc(want * 4) == SLAM_OK && nw.vals_s.alloc(want * 4) == SLAM_OK &&
+         nw.sel.alloc(want * 4) == SLAM_OK && nw.stage.alloc(want) == SLAM_OK && nw.claimed.alloc(want * 4) == SLAM_OK;
     size_t sort_b = 0, sel_b = 0;
     if (ok) {
-        ok = rocprim::radix_sort_pairs(nullptr, sort_b, nw.keys[0], nw.keys_s, nw.vals_in, nw.vals_s, want, 0, m->key_bits) == hipSuccess &&
-             rocprim::select(nullptr, sel_b, rocprim::counting_iterator<uint32_t>(0), nw.stage, nw.sel, m->d_ctr, want) == hipSuccess;
-        nw.tmp_bytes = std::max(sort_b, sel_b);
-        ok = ok && hipMalloc(&nw.tmp, nw.tmp_bytes) == hipSuccess;
+        ok = rocprim::radix_sort_pairs(nullptr, sort_b, nw.keys[0].get(), nw.keys_s.get(), nw.vals_in.get(), nw.vals_s.get(), want, 0,
+                                       m->key_bits) == hipSuccess &&
+             rocprim::select(nullptr, sel_b, rocprim::counting_iterator<uint32_t>(0), nw.stage.get(), nw.sel.get(), m->d_ctr.get(), want) ==
+                 hipSuccess;
+        ok = ok && nw.tmp.alloc(std::max(sort_b, sel_b)) == SLAM_OK;
     }
     if (ok && carried) {
-        ok = hipMemcpy(nw.pts[0], old.pts[cur], carried * sizeof(float4), hipMemcpyDeviceToDevice) == hipSuccess &&
-             hipMemcpy(nw.keys[0], old.keys[cur], carried * sizeof(uint32_t), hipMemcpyDeviceToDevice) == hipSuccess;
+        ok = hipMemcpy(nw.pts[0], m->store.pts[m->cur], carried * sizeof(float4), hipMemcpyDeviceToDevice) == hipSuccess &&
+             hipMemcpy(nw.keys[0], m->store.keys[m->cur], carried * sizeof(uint32_t), hipMemcpyDeviceToDevice) == hipSuccess;
     }
     if (!ok) {
         (void)hipGetLastError();
-        free_store(&nw);
         set_error("slam_mls: the pending store cannot grow to %zu points", want);
         return SLAM_E_NOMEM;
     }
-    free_store(&old);
-    for (int b = 0; b < 2; ++b) m->pts[b] = nw.pts[b], m->keys[b] = nw.keys[b], m->walk[b] = nw.walk[b];
-    m->vals_in = nw.vals_in, m->keys_s = nw.keys_s, m->vals_s = nw.vals_s, m->sel = nw.sel, m->stage = nw.stage, m->claimed = nw.claimed;
-    m->tmp = nw.tmp, m->tmp_bytes = nw.tmp_bytes;
-    m->pcap = want;
+    nw.cap = want;
+    m->store = std::move(nw); // the old store's buffers are freed here
     m->cur = 0;
     return SLAM_OK;
 }
@@ -626,21 +612,18 @@ int slam_mls_create(int size_x, int size_y, double resolution, const slam_mls_pa
     m->key_bits = 1;
     while (((size_t)1 << m->key_bits) - 1 < cells) ++m->key_bits;
     m->inv = (uint32_t)(((size_t)1 << m->key_bits) - 1);
-    auto fail = [&](const char *what) {
-        (void)hipGetLastError();
-        slam_mls_destroy(m);
-        set_error("slam_mls_create: %s", what);
-        return SLAM_E_NOMEM;
-    };
-    if (hipMalloc((void **)&m->slots, cells * m->cap * sizeof(Slot)) != hipSuccess) return fail("no HBM for the cluster slots");
-    if (hipMalloc((void **)&m->cnt, cells * 4) != hipSuccess || hipMalloc((void **)&m->upd, cells * 4) != hipSuccess ||
-        hipMalloc((void **)&m->pstart, cells * 4) != hipSuccess || hipMalloc((void **)&m->pend, cells * 4) != hipSuccess ||
-        hipMalloc((void **)&m->drv, cells) != hipSuccess || hipMalloc((void **)&m->byte, cells) != hipSuccess ||
-        hipMalloc((void **)&m->d_ctr, 16) != hipSuccess)
-        return fail("no HBM for the cell state");
-    if (hipHostMalloc((void **)&m->h_m, sizeof(uint32_t) * kInFlight, 0) != hipSuccess) return fail("no pinned memory");
+    std::unique_ptr<slam_mls, void (*)(slam_mls *)> guard(m, slam_mls_destroy); // an early return gives everything back
+    SLAM_TRY(m->slots.alloc(cells * m->cap * sizeof(Slot)));
+    SLAM_TRY(m->cnt.alloc(cells * 4));
+    SLAM_TRY(m->upd.alloc(cells * 4));
+    SLAM_TRY(m->pstart.alloc(cells * 4));
+    SLAM_TRY(m->pend.alloc(cells * 4));
+    SLAM_TRY(m->drv.alloc(cells));
+    SLAM_TRY(m->byte.alloc(cells));
+    SLAM_TRY(m->d_ctr.alloc(16));
+    SLAM_TRY(m->h_m.alloc(sizeof(uint32_t) * kInFlight));
     for (int k = 0; k < kInFlight; ++k) {
-        if (hipEventCreateWithFlags(&m->ev[k], hipEventDisableTiming) != hipSuccess) return fail("no event");
+        SLAM_HIP(hipEventCreateWithFlags(&m->ev[k], hipEventDisableTiming));
         m->h_m[k] = 0;
     }
     SLAM_HIP(hipMemset(m->cnt, 0, cells * 4));
@@ -652,13 +635,9 @@ int slam_mls_create(int size_x, int size_y, double resolution, const slam_mls_pa
     hipLaunchKernelGGL(start_pad_kernel, dim3(blocks((long)(2 * set_size + 1) * (2 * set_size + 1), 256)), dim3(256), 0, nullptr, view_of(m),
                        set_size, resolution, -p.robot_height, (double)p.min_cluster_points);
     SLAM_HIP(hipGetLastError());
-    const int rc = grow_store(m, (size_t)1 << 20, 0);
-    if (rc != SLAM_OK) {
-        slam_mls_destroy(m);
-        return rc;
-    }
+    SLAM_TRY(grow_store(m, (size_t)1 << 20, 0));
     SLAM_HIP(hipDeviceSynchronize());
-    *out = m;
+    *out = guard.release();
     return SLAM_OK;
 }
 
@@ -666,11 +645,6 @@ void slam_mls_destroy(slam_mls_t *m)
 {
     if (!m) return;
     (void)hipDeviceSynchronize();
-    free_store(m);
-    for (void *p : {(void *)m->slots, (void *)m->cnt, (void *)m->upd, (void *)m->pstart, (void *)m->pend, (void *)m->drv, (void *)m->byte,
-                    (void *)m->d_ctr, (void *)m->d_in})
-        (void)hipFree(p);
-    if (m->h_m) (void)hipHostFree(m->h_m);
     for (hipEvent_t e : m->ev)
         if (e) (void)hipEventDestroy(e);
     delete m;
@@ -717,42 +691,45 @@ int slam_mls_add_cloud_dev(slam_mls_t *m, const float *d_xyz, int n, int stride,
     // the bound on the carried count (the padding the sort below runs over): at most kInFlight calls in flight
     SLAM_TRY(see_counts(m, m->seq - m->seen >= kInFlight));
     long bound = carried_bound(m);
-    if ((size_t)bound + n > m->pcap) {
+    if ((size_t)bound + n > m->store.cap) {
         while (m->seen < m->seq) SLAM_TRY(see_counts(m, true));
         bound = m->known;
-        if ((size_t)bound + n > m->pcap) {
+        if ((size_t)bound + n > m->store.cap) {
             SLAM_HIP(hipStreamSynchronize(st));
-            const size_t want = std::max((size_t)bound + n + ((size_t)bound + n) / 2, 2 * m->pcap);
+            const size_t want = std::max((size_t)bound + n + ((size_t)bound + n) / 2, 2 * m->store.cap);
             SLAM_REQUIRE(want < ((size_t)1 << 31), SLAM_E_NOMEM, "slam_mls_add_cloud_dev: %ld points pending plus %d new exceed the store",
                          bound, n);
             SLAM_TRY(grow_store(m, want, (uint32_t)bound));
         }
     }
     const int B = (int)bound, N = B + n;
-    const int c = m->cur;
+    const int    c = m->cur;
+    const Store &s = m->store;
     if (N == 0) return SLAM_OK;
     if (B > 0)
-        hipLaunchKernelGGL(pad_keys_kernel, dim3(blocks(B, 256)), dim3(256), 0, st, m->keys[c], m->vals_in, B, m->d_ctr, m->inv);
+        hipLaunchKernelGGL(pad_keys_kernel, dim3(blocks(B, 256)), dim3(256), 0, st, s.keys[c], s.vals_in, B, m->d_ctr, m->inv);
     if (n > 0)
         hipLaunchKernelGGL(bin_kernel, dim3(blocks(n, 256)), dim3(256), 0, st, d_xyz, n, stride, B, m->sx, m->sy, m->res, m->p.max_range,
-                           m->pose_x, m->pose_y, m->pts[c], m->keys[c], m->vals_in, m->upd, m->inv);
+                           m->pose_x, m->pose_y, s.pts[c], s.keys[c], s.vals_in, m->upd, m->inv);
     SLAM_HIP(hipGetLastError());
-    size_t tb = m->tmp_bytes;
-    SLAM_HIP(rocprim::radix_sort_pairs(m->tmp, tb, m->keys[c], m->keys_s, m->vals_in, m->vals_s, (size_t)N, 0, m->key_bits, st));
-    hipLaunchKernelGGL(segments_kernel, dim3(blocks(N, 256)), dim3(256), 0, st, m->keys_s, N, m->inv, m->pstart, m->pend);
+    size_t tb = s.tmp.cap;
+    SLAM_HIP(rocprim::radix_sort_pairs(s.tmp.p, tb, s.keys[c].get(), s.keys_s.get(), s.vals_in.get(), s.vals_s.get(),
+                                       (size_t)N, 0, m->key_bits, st));
+    hipLaunchKernelGGL(segments_kernel, dim3(blocks(N, 256)), dim3(256), 0, st, s.keys_s, N, m->inv, m->pstart, m->pend);
     const View   v = view_of(m);
     const Window win = window_of(m);
-    hipLaunchKernelGGL(core_kernel, dim3(blocks(N, 64)), dim3(64), 0, st, v, m->keys_s, N, m->inv, win, m->stage);
+    hipLaunchKernelGGL(core_kernel, dim3(blocks(N, 64)), dim3(64), 0, st, v, s.keys_s, N, m->inv, win, s.stage);
     SLAM_HIP(hipMemsetAsync(m->d_ctr + 1, 0, 4, st));
-    hipLaunchKernelGGL(walk_kernel, dim3(blocks(N, 256)), dim3(256), 0, st, v, m->keys_s, N, m->stage, m->walk[0], (int32_t *)(m->d_ctr + 1));
-    hipLaunchKernelGGL(closure_kernel, dim3(1), dim3(kClosureThreads), 0, st, v, m->walk[0], m->walk[1], m->claimed,
+    hipLaunchKernelGGL(walk_kernel, dim3(blocks(N, 256)), dim3(256), 0, st, v, s.keys_s, N, s.stage, s.walk[0], (int32_t *)(m->d_ctr + 1));
+    hipLaunchKernelGGL(closure_kernel, dim3(1), dim3(kClosureThreads), 0, st, v, s.walk[0], s.walk[1], s.claimed,
                        (const int32_t *)(m->d_ctr + 1));
-    hipLaunchKernelGGL(keep_kernel, dim3(blocks(N, 256)), dim3(256), 0, st, m->keys_s, N, m->inv, m->pstart, m->pend, m->stage);
+    hipLaunchKernelGGL(keep_kernel, dim3(blocks(N, 256)), dim3(256), 0, st, s.keys_s, N, m->inv, m->pstart, m->pend, s.stage);
     SLAM_HIP(hipGetLastError());
-    tb = m->tmp_bytes;
-    SLAM_HIP(rocprim::select(m->tmp, tb, rocprim::counting_iterator<uint32_t>(0), m->stage, m->sel, m->d_ctr, (size_t)N, st));
-    hipLaunchKernelGGL(gather_kernel, dim3(blocks(N, 256)), dim3(256), 0, st, N, m->d_ctr, m->sel, m->keys_s, m->vals_s, m->pts[c],
-                       m->pts[c ^ 1], m->keys[c ^ 1]);
+    tb = s.tmp.cap;
+    SLAM_HIP(rocprim::select(s.tmp.p, tb, rocprim::counting_iterator<uint32_t>(0), s.stage.get(), s.sel.get(), m->d_ctr.get(),
+                             (size_t)N, st));
+    hipLaunchKernelGGL(gather_kernel, dim3(blocks(N, 256)), dim3(256), 0, st, N, m->d_ctr, s.sel, s.keys_s, s.vals_s, s.pts[c],
+                       s.pts[c ^ 1], s.keys[c ^ 1]);
     SLAM_HIP(hipGetLastError());
     m->cur = c ^ 1;
     return record_count(m, st, n);
@@ -763,13 +740,7 @@ int slam_mls_add_cloud(slam_mls_t *m, const float *xyz, int n, int stride)
     SLAM_REQUIRE(m && n >= 0 && stride >= 3 && (xyz || n == 0), SLAM_E_INVALID, "slam_mls_add_cloud: bad arguments");
     SLAM_TRY(require_device());
     const size_t bytes = sizeof(float) * (size_t)n * stride;
-    if (bytes > m->d_in_cap) {
-        (void)hipFree(m->d_in);
-        m->d_in = nullptr;
-        m->d_in_cap = 0;
-        SLAM_REQUIRE(hipMalloc((void **)&m->d_in, bytes) == hipSuccess, SLAM_E_NOMEM, "slam_mls_add_cloud: no HBM for %zu bytes", bytes);
-        m->d_in_cap = bytes;
-    }
+    SLAM_TRY(m->d_in.reserve(bytes));
     if (n) SLAM_HIP(hipMemcpy(m->d_in, xyz, bytes, hipMemcpyHostToDevice));
     SLAM_TRY(slam_mls_add_cloud_dev(m, m->d_in, n, stride, nullptr));
     SLAM_HIP(hipStreamSynchronize(nullptr));
@@ -805,51 +776,31 @@ int slam_mls_segmented_clouds(slam_mls_t *m, float *obstacle, int obstacle_cap, 
     const long   nw = (long)(win.x1 - win.x0) * (win.y1 - win.y0);
     if (nw <= 0) return SLAM_OK;
     const View          v = view_of(m);
-    unsigned long long *counts = (unsigned long long *)pool_alloc(2 * nw * sizeof(unsigned long long) + 16);
-    SLAM_REQUIRE(counts, SLAM_E_NOMEM, "slam_mls_segmented_clouds: no device memory");
-    unsigned long long *offs = counts + nw;
+    PoolMem    count_mem, tmp, out;
+    DeviceWait wait_first;
+    SLAM_TRY(count_mem.alloc(2 * nw * sizeof(unsigned long long) + 16));
+    unsigned long long *counts = count_mem.as<unsigned long long>(), *offs = counts + nw;
     int32_t            *tot = (int32_t *)(offs + nw);
     size_t              tb = 0;
-    int                 rc = SLAM_OK;
-    void               *tmp = nullptr, *out = nullptr;
-    do {
-        hipLaunchKernelGGL(seg_count_kernel, dim3(blocks(nw, 256)), dim3(256), 0, nullptr, v, win, counts);
-        if (hipGetLastError() != hipSuccess ||
-            rocprim::exclusive_scan(nullptr, tb, counts, offs, 0ull, (size_t)nw, rocprim::plus<unsigned long long>()) != hipSuccess ||
-            !(tmp = pool_alloc(tb + 16)) ||
-            rocprim::exclusive_scan(tmp, tb, counts, offs, 0ull, (size_t)nw, rocprim::plus<unsigned long long>(), nullptr) != hipSuccess) {
-            rc = SLAM_E_HIP;
-            break;
-        }
-        hipLaunchKernelGGL(seg_total_kernel, dim3(1), dim3(1), 0, nullptr, counts, offs, (int)nw, tot);
-        int32_t t[2];
-        if (hipMemcpy(t, tot, 8, hipMemcpyDeviceToHost) != hipSuccess) {
-            rc = SLAM_E_HIP;
-            break;
-        }
-        *n_obstacle = t[0], *n_ground = t[1];
-        if (t[0] > obstacle_cap || t[1] > ground_cap) {
-            rc = SLAM_E_NOMEM;
-            set_error("slam_mls_segmented_clouds: %d obstacle / %d ground points, capacities %d / %d", t[0], t[1], obstacle_cap, ground_cap);
-            break;
-        }
-        const size_t bo = 12 * (size_t)t[0], bg = 12 * (size_t)t[1];
-        if (!(out = pool_alloc(bo + bg + 16))) {
-            rc = SLAM_E_NOMEM;
-            break;
-        }
-        float *d_o = (float *)out, *d_g = (float *)((char *)out + bo);
-        hipLaunchKernelGGL(seg_scatter_kernel, dim3(blocks(nw, 256)), dim3(256), 0, nullptr, v, win, offs, d_o, d_g);
-        if (hipGetLastError() != hipSuccess || (bo && hipMemcpy(obstacle, d_o, bo, hipMemcpyDeviceToHost) != hipSuccess) ||
-            (bg && hipMemcpy(ground, d_g, bg, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = SLAM_E_HIP;
-    } while (0);
-    (void)hipDeviceSynchronize();
-    if (rc == SLAM_E_HIP) set_error("slam_mls_segmented_clouds: a HIP call failed");
-    pool_free(counts);
-    if (tmp) pool_free(tmp);
-    if (out) pool_free(out);
-    return rc;
+    hipLaunchKernelGGL(seg_count_kernel, dim3(blocks(nw, 256)), dim3(256), 0, nullptr, v, win, counts);
+    SLAM_HIP(hipGetLastError());
+    SLAM_HIP(rocprim::exclusive_scan(nullptr, tb, counts, offs, 0ull, (size_t)nw, rocprim::plus<unsigned long long>()));
+    SLAM_TRY(tmp.alloc(tb + 16));
+    SLAM_HIP(rocprim::exclusive_scan(tmp.p, tb, counts, offs, 0ull, (size_t)nw, rocprim::plus<unsigned long long>(), nullptr));
+    hipLaunchKernelGGL(seg_total_kernel, dim3(1), dim3(1), 0, nullptr, counts, offs, (int)nw, tot);
+    int32_t t[2];
+    SLAM_HIP(hipMemcpy(t, tot, 8, hipMemcpyDeviceToHost));
+    *n_obstacle = t[0], *n_ground = t[1];
+    SLAM_REQUIRE(t[0] <= obstacle_cap && t[1] <= ground_cap, SLAM_E_NOMEM,
+                 "slam_mls_segmented_clouds: %d obstacle / %d ground points, capacities %d / %d", t[0], t[1], obstacle_cap, ground_cap);
+    const size_t bo = 12 * (size_t)t[0], bg = 12 * (size_t)t[1];
+    SLAM_TRY(out.alloc(bo + bg + 16));
+    float *d_o = out.as<float>(), *d_g = (float *)(out.as<char>() + bo);
+    hipLaunchKernelGGL(seg_scatter_kernel, dim3(blocks(nw, 256)), dim3(256), 0, nullptr, v, win, offs, d_o, d_g);
+    SLAM_HIP(hipGetLastError());
+    if (bo) SLAM_HIP(hipMemcpy(obstacle, d_o, bo, hipMemcpyDeviceToHost));
+    if (bg) SLAM_HIP(hipMemcpy(ground, d_g, bg, hipMemcpyDeviceToHost));
+    return SLAM_OK;
 }
 
 int slam_mls_read_cells(slam_mls_t *m, const int32_t *cells, int n, int32_t *n_clusters, double *clusters, int8_t *drivable, int8_t *bytes,
@@ -864,20 +815,18 @@ int slam_mls_read_cells(slam_mls_t *m, const int32_t *cells, int n, int32_t *n_c
     const size_t ncl = clusters ? (size_t)n * m->cap * 5 : 0;
     const size_t off_cl = 0, off_cnt = off_cl + 8 * ncl, off_pend = off_cnt + 4 * (size_t)n, off_cells = off_pend + 4 * (size_t)n,
                  off_drv = off_cells + 4 * (size_t)n, off_byte = off_drv + n, off_upd = off_byte + n, total = off_upd + n;
-    char *d = (char *)pool_alloc(total + 16);
-    SLAM_REQUIRE(d, SLAM_E_NOMEM, "slam_mls_read_cells: no device memory");
+    PoolMem    block;
+    DeviceWait wait_first;
+    SLAM_TRY(block.alloc(total + 16));
+    char             *d = block.as<char>();
     std::vector<char> h(total);
-    int               rc = SLAM_OK;
     SLAM_HIP(hipDeviceSynchronize());
-    if (hipMemcpy(d + off_cells, cells, 4 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) rc = SLAM_E_HIP;
-    if (rc == SLAM_OK) {
-        hipLaunchKernelGGL(read_cells_kernel, dim3(blocks(n, 256)), dim3(256), 0, nullptr, view_of(m), (const int32_t *)(d + off_cells), n,
-                           m->keys[m->cur], m->d_ctr, (int32_t *)(d + off_cnt), clusters ? (double *)(d + off_cl) : nullptr, (int8_t *)(d + off_drv),
-                           (int8_t *)(d + off_byte), (uint8_t *)(d + off_upd), (int32_t *)(d + off_pend));
-        if (hipGetLastError() != hipSuccess || hipMemcpy(h.data(), d, total, hipMemcpyDeviceToHost) != hipSuccess) rc = SLAM_E_HIP;
-    }
-    pool_free(d);
-    SLAM_REQUIRE(rc == SLAM_OK, rc, "slam_mls_read_cells: a HIP call failed");
+    SLAM_HIP(hipMemcpy(d + off_cells, cells, 4 * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(read_cells_kernel, dim3(blocks(n, 256)), dim3(256), 0, nullptr, view_of(m), (const int32_t *)(d + off_cells), n,
+                       m->store.keys[m->cur], m->d_ctr, (int32_t *)(d + off_cnt), clusters ? (double *)(d + off_cl) : nullptr, (int8_t *)(d + off_drv),
+                       (int8_t *)(d + off_byte), (uint8_t *)(d + off_upd), (int32_t *)(d + off_pend));
+    SLAM_HIP(hipGetLastError());
+    SLAM_HIP(hipMemcpy(h.data(), d, total, hipMemcpyDeviceToHost));
     if (n_clusters) std::memcpy(n_clusters, h.data() + off_cnt, 4 * (size_t)n);
     if (clusters) std::memcpy(clusters, h.data() + off_cl, 8 * ncl);
     if (drivable) std::memcpy(drivable, h.data() + off_drv, n);

@@ -10,7 +10,7 @@
 #include <new>
 #include <thread>
 
-#include "common.hpp"
+#include "device_mem.hpp"
 #include "slam_mi355x_rccl.h"
 
 using namespace slam;
@@ -31,9 +31,9 @@ struct slam_comm {
     static constexpr int kSlots = 4;   // the caller's own merges in flight (slam_grid_merge_begin / _finish)
     static constexpr int kMaxPosted = 8; // merges handed to the helper thread and not yet through
     struct Slot {
-        int       *d_key = nullptr;   // [kKeyInts] this rank's key
-        int       *d_range = nullptr; // [kKeyInts] the minimum over the ranks
-        int       *h_range = nullptr; // pinned copy
+        OwnedArray<int> d_key;   // [kKeyInts] this rank's key
+        OwnedArray<int> d_range; // [kKeyInts] the minimum over the ranks
+        OwnedArray<int, Mem::Pinned> h_range; // pinned copy
         hipEvent_t ev_range = nullptr;
         slam_grid_t *grid = nullptr;  // the grid the merge was begun on
     } slot[1 + kSlots];               // [0]: the helper thread's
@@ -69,8 +69,7 @@ struct slam_comm {
     char                    failed_msg[256] = "";
     std::atomic<double>     timeout_s{60.0};      // a united range that has not arrived by then is a lost rank (read by the helper thread's polls)
     double                  helper_wait_ms = 0.0; // the helper thread's waits for united ranges
-    int32_t   *h_stage = nullptr;   // pinned staging of the host-staged transport
-    size_t     cap_stage = 0;       // ints
+    OwnedArray<int32_t, Mem::Pinned> h_stage; // staging of the host-staged transport
     // statistics (slam_comm_get_stats)
     static constexpr int kTimed = 64;
     long long  merges = 0, rows = 0, bytes = 0;
@@ -95,16 +94,7 @@ __global__ void merge_key_kernel(const int *dirty, int cell_x, int cell_y, int *
 
 bool usable(const slam_comm *c) { return c && !c->aborted && (c->comm || c->host_fn); }
 
-int stage_reserve(slam_comm *c, size_t ints)
-{
-    if (ints <= c->cap_stage) return SLAM_OK;
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    c->h_stage = nullptr;
-    c->cap_stage = 0;
-    SLAM_HIP(hipHostMalloc((void **)&c->h_stage, ints * sizeof(int32_t), hipHostMallocDefault));
-    c->cap_stage = ints;
-    return SLAM_OK;
-}
+int stage_reserve(slam_comm *c, size_t ints) { return c->h_stage.reserve(ints * sizeof(int32_t)); }
 
 // host-staged sum of `count` ints at planes + first and planes + cells + first: both parts down, one all-reduce of the
 // two together, both back.  Synchronises the stream (the caller's transport blocks anyway).
@@ -290,13 +280,8 @@ void slam_comm_destroy(slam_comm_t *comm)
         comm->cv_job.notify_all();
         comm->worker.join();
     }
-    for (auto &sl : comm->slot) {
-        if (sl.d_range) (void)hipFree(sl.d_range);
-        if (sl.d_key) (void)hipFree(sl.d_key);
-        if (sl.h_range) (void)hipHostFree(sl.h_range);
+    for (auto &sl : comm->slot)
         if (sl.ev_range) (void)hipEventDestroy(sl.ev_range);
-    }
-    if (comm->h_stage) (void)hipHostFree(comm->h_stage);
     for (auto &pr : comm->ev_ar)
         for (hipEvent_t e : pr)
             if (e) (void)hipEventDestroy(e);
@@ -431,9 +416,9 @@ int slam_grid_allreduce_rows(slam_grid_t *grid, slam_comm_t *comm, int row_lo, i
 static int begin_body(slam_comm *comm, slam_comm::Slot &sl, slam_grid_t *grid, hipStream_t st, const int32_t *d_dirty, int cell_x, int cell_y)
 {
     if (!sl.ev_range) { // (ev_range is made last: a slot whose allocation failed half way is completed, not used as it is)
-        if (!sl.d_range) SLAM_HIP(hipMalloc((void **)&sl.d_range, kKeyInts * sizeof(int)));
-        if (!sl.d_key) SLAM_HIP(hipMalloc((void **)&sl.d_key, kKeyInts * sizeof(int)));
-        if (!sl.h_range) SLAM_HIP(hipHostMalloc((void **)&sl.h_range, kKeyInts * sizeof(int), hipHostMallocDefault));
+        if (!sl.d_range) SLAM_TRY(sl.d_range.alloc(kKeyInts * sizeof(int)));
+        if (!sl.d_key) SLAM_TRY(sl.d_key.alloc(kKeyInts * sizeof(int)));
+        if (!sl.h_range) SLAM_TRY(sl.h_range.alloc(kKeyInts * sizeof(int)));
         SLAM_HIP(hipEventCreateWithFlags(&sl.ev_range, hipEventDisableTiming));
     }
     hipLaunchKernelGGL(merge_key_kernel, dim3(1), dim3(64), 0, st, d_dirty, cell_x, cell_y, sl.d_key);

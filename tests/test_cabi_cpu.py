@@ -80,6 +80,22 @@ def test_product_never_imports_the_oracle():
                 assert "CDLL" not in txt or f == "api.py", f
 
 
+def test_device_memory_has_one_owner():
+    """Handles hold device, pool and pinned memory through slam_amd/csrc/device_mem.hpp alone: a raw allocation call
+    elsewhere is a buffer whose free somebody has to remember on every way out."""
+    csrc = os.path.join(ROOT, "slam_amd", "csrc")
+    raw = {"hipMalloc(": {"runtime.hip", "device_mem.hpp"}, "hipFree(": {"runtime.hip", "device_mem.hpp"},
+           "hipHostMalloc(": {"runtime.hip", "device_mem.hpp"}, "hipHostFree(": {"runtime.hip", "device_mem.hpp"},
+           "pool_alloc(": {"runtime.hip", "device_mem.hpp", "common.hpp"},
+           "pool_free(": {"runtime.hip", "device_mem.hpp", "common.hpp"}, "struct DevBuf": set(), "struct GrowBuf": set()}
+    files = sorted(os.listdir(csrc))
+    assert "device_mem.hpp" in files and len(files) > 10
+    for f in files:
+        txt = open(os.path.join(csrc, f), errors="replace").read()
+        for what, allowed in raw.items():
+            assert what not in txt or f in allowed, "%s holds '%s'" % (f, what)
+
+
 def test_python_binding_declares_pointer_signatures():
     """ctypes passes an undeclared Python int as a 32-bit C int: a device pointer handed to an entry point
     without argtypes would be truncated (a GPU fault, not an error code).  Only calls that take no pointer
