@@ -736,6 +736,71 @@ int  slam_kf_register_edges(slam_kf_t *s, const slam_kf_edge_req *req, int n_edg
 int  slam_kf_register_edges_traced(slam_kf_t *s, const slam_kf_edge_req *req, int n_edges, slam_kf_edge_result *out,
                                    int32_t *pairs_trace, int trace_cap, slam_stream_t stream);
 
+/* -------------------------------------------------------------------------
+ * Correlative scan matcher (Olson, ICRA 2009), class-constrained like the rest of ccicp2d: the best of N_theta x N_y x N_x
+ * poses around a start pose by a score looked up in a rasterised model, found exactly by a two-level branch and bound.  The
+ * reference has no such matcher; it is the wide-basin start for slam_icp_fit*.  docs/CSM.md has the
+ * contract.  Everything behind the per-angle transform is integer: the device equals tests/cpp/csm_oracle.cpp bit for bit.
+ * ---------------------------------------------------------------------- */
+typedef struct slam_csm slam_csm_t;
+
+typedef struct {
+    double resolution;   /* pitch of the lattice in metres (0.1); cell(v) = floor(v / resolution) */
+    double sigma;        /* standard deviation of the stamp in metres (0.2) */
+    int    kernel_cells; /* K: the stamp is (2K+1) x (2K+1) cells; 0 = ceil(3 sigma / resolution - 1e-9) (6); at most 64 */
+    int    block;        /* D: candidates per block and axis of the bound (8); 1 .. 16 */
+    int    half_x;       /* N_x = 2 half_x + 1 translations of whole cells along x (40) */
+    int    half_y;       /* (40) */
+    int    half_theta;   /* N_theta = 2 half_theta + 1 angles (120) */
+    double theta_step;   /* radians between two angles (0.01) */
+    int    exhaustive;   /* 1 = no bound: every candidate is evaluated (measurements and tests; same answer) */
+} slam_csm_params;
+
+typedef struct {
+    int k, a, b;          /* the winner: angle k, translation (a - half_x, b - half_y) cells; the lowest flat index
+                             (k N_y + b) N_x + a among equal scores */
+    int score;            /* its score; -1 = scan of fewer than 5 points, pose untouched */
+    int max_score;        /* 255 n_points */
+    int n_points;         /* points counted at angle k: of a class that has a table, finite, cells within +-2^30 */
+    int blocks_evaluated; /* blocks evaluated at full resolution (a diagnostic; all of them with exhaustive = 1) */
+} slam_csm_result;
+
+void slam_csm_default_params(slam_csm_params *p);
+/* The model arrays of slam_icp_create[_dev]: one table per class; a class of 3 points or fewer has none and scores nothing
+ * (icpPointToPoint.cpp:59,93).  Both wait for the tables.  Scratch for one scan is reserved. */
+int  slam_csm_create(const double *m_ga, int n_ga, const double *m_nga, int n_nga, const slam_csm_params *params, slam_csm_t **out);
+int  slam_csm_create_dev(const double *d_m_ga, int n_ga, const double *d_m_nga, int n_nga, const slam_csm_params *params,
+                         slam_csm_t **out);
+void slam_csm_destroy(slam_csm_t *csm);
+/* Scratch for batches of up to max_scans scans (bounds, survivor list, keys); the points are staged in pieces, so their
+ * number needs none.  Waits for the device when it has to grow. */
+int  slam_csm_reserve(slam_csm_t *csm, int max_scans);
+/* Another search window (the tables stay); re-sizes the scratch as slam_csm_reserve does. */
+int  slam_csm_set_window(slam_csm_t *csm, int half_x, int half_y, int half_theta, double theta_step);
+int  slam_csm_set_exhaustive(slam_csm_t *csm, int exhaustive);
+/* Host: cs[2 k], cs[2 k + 1] = cos, sin of theta_k = atan2(R0[2], R0[0]) + (k - half_theta) theta_step, N_theta pairs.  The
+ * angles are the one floating-point input that libm decides, so the host computes them and the device reads them. */
+int  slam_csm_angles(slam_csm_t *csm, const double R0[4], double *cs);
+/* A batch of scans laid out as for slam_icp_fit_batch_from_dev; d_cs = n_scans x N_theta x 2 doubles from slam_csm_angles
+ * for every scan's R0.  Writes the winner's pose to d_R / d_t (which may be d_R0 / d_t0) and d_result[s] (nullable).  A scan
+ * of fewer than 5 points gets its initial pose and score -1.  Asynchronous on `stream`; allocates, frees and waits for
+ * nothing (a graph may capture it); SLAM_E_INVALID beyond the reserved number of scans.  One call at a time per handle. */
+int  slam_csm_match_batch_dev(slam_csm_t *csm, const double *d_pts, const int32_t *d_scan_off, const int32_t *d_scan_nga,
+                              int n_scans, const double *d_R0, const double *d_t0, const double *d_cs, double *d_R, double *d_t,
+                              slam_csm_result *d_result, slam_stream_t stream);
+/* One scan on host pointers, synchronous, R and t in/out as slam_icp_fit; SLAM_E_TOO_FEW_SCENE_POINTS leaves them. */
+int  slam_csm_match(slam_csm_t *csm, const double *t_ga, int n_tga, const double *t_nga, int n_tnga, double R[4], double t[2],
+                    slam_csm_result *result);
+/* The exhaustive form for one scan (n points, the first n_ga of class GA; d_t0: 2 doubles, d_cs: N_theta x 2): every score,
+ * d_volume[(k N_y + b) N_x + a], int32.  Asynchronous. */
+int  slam_csm_score_volume_dev(slam_csm_t *csm, const double *d_pts, int n, int n_ga, const double *d_t0, const double *d_cs,
+                               int32_t *d_volume, slam_stream_t stream);
+/* Table of class cls (0 = GA, 1 = NGA), level 0 = T, 1 = W (the bound): the lattice cell of its first byte, its size (0 x 0: the
+ * class has no table) and, with buf, its w h bytes row by row (cap >= w h).  Synchronous. */
+int  slam_csm_read_table(slam_csm_t *csm, int cls, int level, int *origin_x, int *origin_y, int *w, int *h, uint8_t *buf, size_t cap);
+/* the parameters in force (kernel_cells resolved), N_theta N_x N_y and blocks per axis in dims[5], bytes of tables and scratch */
+int  slam_csm_info(slam_csm_t *csm, slam_csm_params *params, int dims[5], size_t *table_bytes, size_t *scratch_bytes, int *max_scans);
+
 #ifdef __cplusplus
 }
 #endif

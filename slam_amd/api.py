@@ -87,6 +87,19 @@ class KfEdgeResult(C.Structure):
                 ("reserved", C.c_int)]
 
 
+class CsmParams(C.Structure):
+    _fields_ = [("resolution", C.c_double), ("sigma", C.c_double), ("kernel_cells", C.c_int), ("block", C.c_int),
+                ("half_x", C.c_int), ("half_y", C.c_int), ("half_theta", C.c_int), ("theta_step", C.c_double),
+                ("exhaustive", C.c_int)]
+
+
+class CsmResult(C.Structure):
+    _fields_ = [("k", C.c_int), ("a", C.c_int), ("b", C.c_int), ("score", C.c_int), ("max_score", C.c_int),
+                ("n_points", C.c_int), ("blocks_evaluated", C.c_int)]
+
+
+CSM_RESULT_DTYPE = np.dtype([(f, np.int32) for f, _ in CsmResult._fields_])
+
 KF_NOT_CONVERGED, KF_ITERATIONS, KF_TRANSFORM, KF_ABS_MSE, KF_REL_MSE, KF_NO_CORRESPONDENCES = 0, 1, 2, 3, 4, 5
 KF_LATTICE_MARGIN = 1.0 + 2.0 ** -16   # the search lattice's edge is cell_size (or the gate) times this
 
@@ -136,6 +149,9 @@ EXPORTS = [
     "slam_kf_default_params", "slam_kf_create", "slam_kf_destroy", "slam_kf_set_params", "slam_kf_add_keyframe",
     "slam_kf_add_keyframe_dev", "slam_kf_keyframe_info", "slam_kf_count", "slam_kf_read_keyframe", "slam_kf_nearest_dev",
     "slam_kf_register_edges", "slam_kf_register_edges_traced",
+    "slam_csm_default_params", "slam_csm_create", "slam_csm_create_dev", "slam_csm_destroy", "slam_csm_reserve",
+    "slam_csm_set_window", "slam_csm_set_exhaustive", "slam_csm_angles", "slam_csm_match_batch_dev", "slam_csm_match",
+    "slam_csm_score_volume_dev", "slam_csm_read_table", "slam_csm_info",
 ]
 
 
@@ -321,6 +337,22 @@ def lib():
     L.slam_kf_nearest_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]
     L.slam_kf_register_edges.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
     L.slam_kf_register_edges_traced.argtypes = [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]
+    L.slam_csm_default_params.argtypes = [C.POINTER(CsmParams)]
+    L.slam_csm_default_params.restype = None
+    L.slam_csm_create.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(CsmParams), C.POINTER(_vp)]
+    L.slam_csm_create_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(CsmParams), C.POINTER(_vp)]
+    L.slam_csm_destroy.argtypes = [_vp]
+    L.slam_csm_destroy.restype = None
+    L.slam_csm_reserve.argtypes = [_vp, C.c_int]
+    L.slam_csm_set_window.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_double]
+    L.slam_csm_set_exhaustive.argtypes = [_vp, C.c_int]
+    L.slam_csm_angles.argtypes = [_vp, _vp, _vp]
+    L.slam_csm_match_batch_dev.argtypes = [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.slam_csm_match.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.POINTER(CsmResult)]
+    L.slam_csm_score_volume_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]
+    L.slam_csm_read_table.argtypes = [_vp, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4 + [_vp, C.c_size_t]
+    L.slam_csm_info.argtypes = [_vp, C.POINTER(CsmParams), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -669,6 +701,128 @@ class Icp:
     def close(self):
         if getattr(self, "h", None):
             lib().slam_icp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def csm_default_params(**kw):
+    p = CsmParams()
+    lib().slam_csm_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+class CorrelativeMatcher:
+    """The correlative scan matcher (slam_csm_*, docs/CSM.md): the best of N_theta x N_y x N_x poses around a start pose,
+    the wide-basin start for Icp.fit.  The model arrays are Icp's."""
+
+    def __init__(self, m_ga, m_nga, params=None, **kw):
+        m_ga = np.ascontiguousarray(m_ga, dtype=np.float64).reshape(-1, 2)
+        m_nga = np.ascontiguousarray(m_nga, dtype=np.float64).reshape(-1, 2)
+        self.params = params or csm_default_params(**kw)
+        h = _vp()
+        check(lib().slam_csm_create(_ptr(m_ga), len(m_ga), _ptr(m_nga), len(m_nga), C.byref(self.params), C.byref(h)))
+        self.h = h.value
+        self.params = self.info()["params"]
+
+    @classmethod
+    def from_device(cls, d_ga, n_ga, d_nga, n_nga, params=None, **kw):
+        """slam_csm_create_dev: the model arrays (f64 xy) are DeviceArrays / device pointers."""
+        self = object.__new__(cls)
+        self.params = params or csm_default_params(**kw)
+        h = _vp()
+        check(lib().slam_csm_create_dev(getattr(d_ga, "ptr", d_ga), int(n_ga), getattr(d_nga, "ptr", d_nga), int(n_nga),
+                                        C.byref(self.params), C.byref(h)))
+        self.h = h.value
+        self.params = self.info()["params"]
+        return self
+
+    def info(self):
+        p, dims, tb, sb, ms = CsmParams(), (C.c_int * 5)(), C.c_size_t(), C.c_size_t(), C.c_int()
+        check(lib().slam_csm_info(self.h, C.byref(p), dims, C.byref(tb), C.byref(sb), C.byref(ms)))
+        return dict(params=p, n_theta=dims[0], n_x=dims[1], n_y=dims[2], blocks_x=dims[3], blocks_y=dims[4],
+                    table_bytes=tb.value, scratch_bytes=sb.value, max_scans=ms.value)
+
+    def reserve(self, max_scans):
+        check(lib().slam_csm_reserve(self.h, int(max_scans)))
+
+    def set_window(self, half_x, half_y, half_theta, theta_step):
+        check(lib().slam_csm_set_window(self.h, int(half_x), int(half_y), int(half_theta), float(theta_step)))
+        self.params = self.info()["params"]
+
+    def set_exhaustive(self, on):
+        check(lib().slam_csm_set_exhaustive(self.h, int(bool(on))))
+        self.params.exhaustive = int(bool(on))
+
+    def angles(self, R0):
+        """cos, sin of every candidate angle around R0's: [N_theta, 2] f64 (host libm; the device reads them)."""
+        R0 = np.ascontiguousarray(R0, dtype=np.float64).reshape(4)
+        cs = np.zeros((2 * self.params.half_theta + 1, 2))
+        check(lib().slam_csm_angles(self.h, _ptr(R0), _ptr(cs)))
+        return cs
+
+    def table(self, cls, level=0):
+        """(origin_x, origin_y, u8 [h, w]) of class cls: level 0 = T, 1 = W; a class without a table has shape (0, 0)."""
+        ox, oy, w, h = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(lib().slam_csm_read_table(self.h, int(cls), int(level), C.byref(ox), C.byref(oy), C.byref(w), C.byref(h), None, 0))
+        buf = np.zeros((h.value, w.value), np.uint8)
+        if buf.size:
+            check(lib().slam_csm_read_table(self.h, int(cls), int(level), None, None, None, None, _ptr(buf), buf.size))
+        return ox.value, oy.value, buf
+
+    def match(self, t_ga, t_nga, R, t):
+        """slam_csm_match, host arrays: (R, t, CsmResult)."""
+        t_ga = np.ascontiguousarray(t_ga, dtype=np.float64).reshape(-1, 2)
+        t_nga = np.ascontiguousarray(t_nga, dtype=np.float64).reshape(-1, 2)
+        R = np.ascontiguousarray(R, dtype=np.float64).reshape(4).copy()
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(2).copy()
+        res = CsmResult()
+        check(lib().slam_csm_match(self.h, _ptr(t_ga), len(t_ga), _ptr(t_nga), len(t_nga), _ptr(R), _ptr(t), C.byref(res)))
+        return R.reshape(2, 2), t, res
+
+    def match_batch_dev(self, d_pts, d_off, d_nga, n_scans, d_R0, d_t0, d_cs, d_R, d_t, d_result=None, stream=None):
+        check(lib().slam_csm_match_batch_dev(self.h, d_pts.ptr, d_off.ptr, d_nga.ptr, int(n_scans), d_R0.ptr, d_t0.ptr, d_cs.ptr,
+                                             d_R.ptr, d_t.ptr, d_result.ptr if d_result is not None else None, _sp(stream)))
+
+    def match_batch(self, batch, R0=None, t0=None):
+        """Host convenience over a synth.ScanBatch: (R [S, 4], t [S, 2], result [S] of CSM_RESULT_DTYPE)."""
+        S = batch.n_scans
+        R0 = np.ascontiguousarray(batch.R if R0 is None else R0, dtype=np.float64).reshape(S, 4)
+        t0 = np.ascontiguousarray(batch.t if t0 is None else t0, dtype=np.float64).reshape(S, 2)
+        self.reserve(S)
+        d_pts = DeviceArray.from_host(batch.pts, np.float64)
+        d_off = DeviceArray.from_host(batch.scan_off, np.int32)
+        d_nga = DeviceArray.from_host(batch.scan_nga, np.int32)
+        d_R0, d_t0 = DeviceArray.from_host(R0), DeviceArray.from_host(t0)
+        d_cs = DeviceArray.from_host(np.stack([self.angles(R0[s]) for s in range(S)]))
+        d_R, d_t = DeviceArray((S, 4), np.float64), DeviceArray((S, 2), np.float64)
+        d_res = DeviceArray((S,), CSM_RESULT_DTYPE)
+        self.match_batch_dev(d_pts, d_off, d_nga, S, d_R0, d_t0, d_cs, d_R, d_t, d_res)
+        synchronize()
+        return d_R.download(), d_t.download(), d_res.download()
+
+    def score_volume(self, t_ga, t_nga, R0, t0):
+        """Every score of one scan: int32 [N_theta, N_y, N_x] (slam_csm_score_volume_dev)."""
+        pts = np.ascontiguousarray(np.concatenate([np.reshape(t_ga, (-1, 2)), np.reshape(t_nga, (-1, 2))]), dtype=np.float64)
+        i = self.info()
+        d_pts = DeviceArray.from_host(pts)
+        d_t0 = DeviceArray.from_host(np.ascontiguousarray(t0, dtype=np.float64).reshape(2))
+        d_cs = DeviceArray.from_host(self.angles(R0))
+        d_vol = DeviceArray((i["n_theta"], i["n_y"], i["n_x"]), np.int32)
+        check(lib().slam_csm_score_volume_dev(self.h, d_pts.ptr, len(pts), len(np.reshape(t_ga, (-1, 2))), d_t0.ptr, d_cs.ptr,
+                                              d_vol.ptr, None))
+        synchronize()
+        return d_vol.download()
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().slam_csm_destroy(self.h)
             self.h = None
 
     def __del__(self):

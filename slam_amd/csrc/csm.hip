@@ -1,0 +1,715 @@
+// csm.hip -- correlative scan matcher (slam_csm_*, docs/CSM.md): per-class u8 score tables T on one global lattice, their
+// D x D sliding maximum W, and an exact two-level search over (angle, y, x) candidates.
+//
+// A match is six launches on the caller's stream and no host wait: every bound U (csm_coarse_kernel, which also keeps the
+// largest per scan), the top block at full resolution (csm_blocks_kernel: its best score is the lower bound L), the blocks
+// with U >= L appended to a list (csm_select_kernel), those blocks at full resolution (csm_blocks_kernel again, a fixed
+// grid striding over the list), and the answer (csm_finish_kernel).  Scores are int32 sums of table bytes; the reduction is
+// an atomicMax on score << 32 | ~flat_index, so neither the list's order nor the order of the workgroups shows in the result.
+// The one floating-point step, point -> cell at an angle, is spelled with __dmul_rn / __dadd_rn and an IEEE division; cos and
+// sin come from the host (slam_csm_angles).
+#include <cmath>
+#include <cstring>
+#include <new>
+
+#include "common.hpp"
+#include "device_mem.hpp"
+
+using namespace slam;
+
+namespace {
+
+constexpr int    kChunk = 1024;           // scan points staged in LDS at a time (8 KB)
+constexpr int    kNo = -(1 << 30);        // staged row of a point that scores nothing: no row + b reaches the table
+constexpr int    kTileRows = 8;           // candidates along b per lane of the tile kernel
+constexpr int    kTileW = 64, kTileH = 4 * kTileRows;
+constexpr int    kCoarsePer = 2;          // blocks per lane of the coarse kernel
+constexpr int    kBlockPer = 4;           // candidates per lane of the block kernel: D * D <= 64 * kBlockPer
+constexpr int    kMaxD = 16, kMaxK = 64;
+constexpr double kCellLimit = 1073741824.0; // 2^30
+constexpr size_t kMaxTableBytes = (size_t)1 << 28;
+
+struct Tab {
+    const uint8_t *v;
+    int            ox, oy, w, h; // w = 0: no table
+};
+
+struct Geom {
+    Tab    T[2], W[2];
+    double res;
+    int    half_x, half_y, nx, ny, nth, D, nbx, nby;
+};
+
+// one scan of a batch; off == nullptr: the single scan [0, n) with n_ga points of class GA
+struct Scans {
+    const double  *pts;
+    const int32_t *off, *nga;
+    int            n, n_ga;
+    const double  *t0, *cs;
+};
+
+__device__ inline bool cell_of(double v, double res, int &c)
+{
+    const double f = floor(v / res);
+    if (!(fabs(f) <= kCellLimit)) return false; // NaN, infinite or beyond the lattice
+    c = (int)f;
+    return true;
+}
+
+__device__ inline void scan_range(const Scans &S, int s, int &first, int &n, int &n_ga)
+{
+    if (S.off) {
+        first = S.off[s];
+        n = S.off[s + 1] - first;
+        n_ga = S.nga[s];
+    } else {
+        first = 0, n = S.n, n_ga = S.n_ga;
+    }
+    n = n < 0 ? 0 : n;
+    n_ga = n_ga < 0 ? 0 : (n_ga > n ? n : n_ga);
+}
+
+// the cell of scan point i at (c, s, t0); false: the point is not counted
+__device__ inline bool point_cell(const Tab *tabs, const double *pts, int first, int i, int n_ga, double c, double s, double tx, double ty,
+                                  double res, int &cx, int &cy)
+{
+    if (tabs[i < n_ga ? 0 : 1].w == 0) return false;
+    const double px = pts[2 * (size_t)(first + i)], py = pts[2 * (size_t)(first + i) + 1];
+    const double qx = __dadd_rn(__dsub_rn(__dmul_rn(c, px), __dmul_rn(s, py)), tx);
+    const double qy = __dadd_rn(__dadd_rn(__dmul_rn(s, px), __dmul_rn(c, py)), ty);
+    return cell_of(qx, res, cx) && cell_of(qy, res, cy);
+}
+
+// Points [base, base + cn) of the scan into LDS as (column, row) of candidate (0, 0) in the table of their class (`tabs`: T or W).
+__device__ inline void stage(const Geom &G, const Tab *tabs, const double *pts, int first, int base, int cn, int n_ga, double c, double s,
+                             double tx, double ty, int2 *cells, int threads)
+{
+    for (int j = threadIdx.x; j < cn; j += threads) {
+        int  cx, cy;
+        int2 out = make_int2(0, kNo);
+        if (point_cell(tabs, pts, first, base + j, n_ga, c, s, tx, ty, G.res, cx, cy)) {
+            const Tab      &t = tabs[base + j < n_ga ? 0 : 1];
+            const long long rx = (long long)cx - t.ox - G.half_x, ry = (long long)cy - t.oy - G.half_y;
+            if (rx > kNo && rx < -(long long)kNo && ry > kNo && ry < -(long long)kNo) out = make_int2((int)rx, (int)ry);
+        }
+        cells[j] = out;
+    }
+}
+
+__device__ inline unsigned long long key_of(int score, unsigned flat) { return ((unsigned long long)(unsigned)score << 32) | (unsigned)~flat; }
+
+__device__ inline unsigned long long wave_max(unsigned long long v)
+{
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long o = __shfl_xor(v, d, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// ---------------------------------------------------------------- tables
+__global__ void csm_model_cells_kernel(const double *m, int n, double res, int2 *cells, int *bbox)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int  cx, cy;
+    int2 out = make_int2(0, kNo); // kNo in y: the point takes no part
+    if (cell_of(m[2 * (size_t)i], res, cx) && cell_of(m[2 * (size_t)i + 1], res, cy)) {
+        out = make_int2(cx, cy);
+        atomicMin(&bbox[0], cx), atomicMax(&bbox[1], cx), atomicMin(&bbox[2], cy), atomicMax(&bbox[3], cy);
+    }
+    cells[i] = out;
+}
+
+// one thread per (point, stamp entry): every write lies inside the window, which is the bounding box widened by K
+__global__ void csm_scatter_kernel(const int2 *cells, int n, const uint8_t *stamp, int K, int ox, int oy, int w, int h, unsigned *plane)
+{
+    const int       S = 2 * K + 1;
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (long long)n * S * S) return;
+    const int  p = (int)(g / (S * S)), e = (int)(g % (S * S));
+    const int2 c = cells[p];
+    const unsigned v = stamp[e];
+    if (c.y == kNo || v == 0) return;
+    const int col = c.x + e % S - K - ox, row = c.y + e / S - K - oy;
+    if (col >= 0 && col < w && row >= 0 && row < h) atomicMax(&plane[(size_t)row * w + col], v);
+}
+
+__global__ void csm_pack_kernel(const unsigned *plane, size_t n, uint8_t *T)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) T[i] = (uint8_t)plane[i];
+}
+
+// W[u, v] = max over 0 <= i, j < D of T[u + i, v + j]; W's window is T's widened by D - 1 towards smaller indices
+__global__ void csm_slide_kernel(const uint8_t *T, int w, int h, int D, uint8_t *W)
+{
+    const int    ww = w + D - 1, wh = h + D - 1;
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (size_t)ww * wh) return;
+    const int u = (int)(g % ww) - (D - 1), v = (int)(g / ww) - (D - 1); // in T's window
+    int       best = 0;
+    for (int j = 0; j < D; ++j)
+        for (int i = 0; i < D; ++i) {
+            const int x = u + i, y = v + j;
+            if (x >= 0 && x < w && y >= 0 && y < h) {
+                const int t = T[(size_t)y * w + x];
+                best = t > best ? t : best;
+            }
+        }
+    W[g] = (uint8_t)best;
+}
+
+// ---------------------------------------------------------------- the exhaustive form
+// One workgroup per (tile of 64 a x 32 b, angle, scan): lanes along a, every lane kTileRows rows of b.  For one point a wave
+// reads consecutive bytes of kTileRows table rows; the point is an LDS broadcast.  Writes the volume and / or offers the best key.
+__global__ __launch_bounds__(256) void csm_tiles_kernel(Geom G, Scans S, int32_t *vol, unsigned long long *best)
+{
+    __shared__ int2 cells[kChunk];
+    const int       tiles_x = (G.nx + kTileW - 1) / kTileW;
+    const int       k = blockIdx.y, s = blockIdx.z;
+    int             first, n, n_ga;
+    scan_range(S, s, first, n, n_ga);
+    if (n < 5) return;
+    const int    a = (blockIdx.x % tiles_x) * kTileW + (threadIdx.x & 63);
+    const int    b0 = (blockIdx.x / tiles_x) * kTileH + (threadIdx.x >> 6) * kTileRows;
+    const double c = S.cs[((size_t)s * G.nth + k) * 2], sn = S.cs[((size_t)s * G.nth + k) * 2 + 1];
+    const double tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
+    int          acc[kTileRows];
+#pragma unroll
+    for (int r = 0; r < kTileRows; ++r) acc[r] = 0;
+    for (int base = 0; base < n; base += kChunk) {
+        const int cn = n - base < kChunk ? n - base : kChunk;
+        __syncthreads();
+        stage(G, G.T, S.pts, first, base, cn, n_ga, c, sn, tx, ty, cells, 256);
+        __syncthreads();
+        const int split = n_ga - base < 0 ? 0 : (n_ga - base > cn ? cn : n_ga - base);
+        for (int cl = 0; cl < 2; ++cl) {
+            const Tab t = G.T[cl];
+            const int j1 = cl ? cn : split;
+            for (int j = cl ? split : 0; j < j1; ++j) {
+                const int2 q = cells[j];
+                const int  col = q.x + a, row0 = q.y + b0;
+                if ((unsigned)col < (unsigned)t.w) {
+#pragma unroll
+                    for (int r = 0; r < kTileRows; ++r)
+                        if ((unsigned)(row0 + r) < (unsigned)t.h) acc[r] += t.v[(size_t)(row0 + r) * t.w + col];
+                }
+            }
+        }
+    }
+    unsigned long long key = 0;
+    if (a < G.nx) {
+#pragma unroll
+        for (int r = 0; r < kTileRows; ++r)
+            if (b0 + r < G.ny) {
+                const unsigned flat = ((unsigned)k * G.ny + (b0 + r)) * G.nx + a;
+                if (vol) vol[flat] = acc[r];
+                const unsigned long long kk = key_of(acc[r], flat);
+                key = kk > key ? kk : key;
+            }
+    }
+    if (best) {
+        key = wave_max(key);
+        if ((threadIdx.x & 63) == 0 && key) atomicMax(&best[s], key);
+    }
+}
+
+// ---------------------------------------------------------------- the two-level form
+// One wave per (group of 128 blocks, angle, scan): U of kCoarsePer blocks per lane, and the scan's largest (U, block).
+__global__ __launch_bounds__(64) void csm_coarse_kernel(Geom G, Scans S, int32_t *U, unsigned long long *top)
+{
+    __shared__ int2 cells[kChunk];
+    const int       nb = G.nbx * G.nby, groups = (nb + 64 * kCoarsePer - 1) / (64 * kCoarsePer);
+    const int       k = blockIdx.x / groups, grp = blockIdx.x % groups, s = blockIdx.y;
+    int             first, n, n_ga;
+    scan_range(S, s, first, n, n_ga);
+    if (n < 5) return;
+    const double c = S.cs[((size_t)s * G.nth + k) * 2], sn = S.cs[((size_t)s * G.nth + k) * 2 + 1];
+    const double tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
+    int          blk[kCoarsePer], dx[kCoarsePer], dy[kCoarsePer], acc[kCoarsePer];
+#pragma unroll
+    for (int r = 0; r < kCoarsePer; ++r) {
+        blk[r] = (grp * kCoarsePer + r) * 64 + threadIdx.x;
+        dx[r] = (blk[r] % G.nbx) * G.D, dy[r] = (blk[r] / G.nbx) * G.D; // (a block beyond nb reads rows that may exist: it is not written)
+        acc[r] = 0;
+    }
+    for (int base = 0; base < n; base += kChunk) {
+        const int cn = n - base < kChunk ? n - base : kChunk;
+        __syncthreads();
+        stage(G, G.W, S.pts, first, base, cn, n_ga, c, sn, tx, ty, cells, 64);
+        __syncthreads();
+        const int split = n_ga - base < 0 ? 0 : (n_ga - base > cn ? cn : n_ga - base);
+        for (int cl = 0; cl < 2; ++cl) {
+            const Tab t = G.W[cl];
+            const int j1 = cl ? cn : split;
+            for (int j = cl ? split : 0; j < j1; ++j) {
+                const int2 q = cells[j];
+#pragma unroll
+                for (int r = 0; r < kCoarsePer; ++r) {
+                    const int col = q.x + dx[r], row = q.y + dy[r];
+                    if ((unsigned)col < (unsigned)t.w && (unsigned)row < (unsigned)t.h) acc[r] += t.v[(size_t)row * t.w + col];
+                }
+            }
+        }
+    }
+    unsigned long long key = 0;
+#pragma unroll
+    for (int r = 0; r < kCoarsePer; ++r)
+        if (blk[r] < nb) {
+            const unsigned f = (unsigned)k * nb + blk[r];
+            U[(size_t)s * G.nth * nb + f] = acc[r];
+            const unsigned long long kk = key_of(acc[r], f);
+            key = kk > key ? kk : key;
+        }
+    key = wave_max(key);
+    if (threadIdx.x == 0 && key) atomicMax(&top[s], key);
+}
+
+// One wave per block at full resolution.  list == nullptr: the scan's top block alone (grid.x = 1); else the wave strides over
+// the scan's list.  Lane c of D * D: candidate (A D + c % D, B D + c / D); a ragged block's missing candidates are left out.
+__global__ __launch_bounds__(64) void csm_blocks_kernel(Geom G, Scans S, const unsigned long long *top, const int32_t *list, const int32_t *count,
+                                                        unsigned long long *best)
+{
+    __shared__ int2 cells[kChunk];
+    const int       nb = G.nbx * G.nby, s = blockIdx.y;
+    int             first, n, n_ga;
+    scan_range(S, s, first, n, n_ga);
+    if (n < 5) return;
+    const int    items = list ? count[s] : 1;
+    const double tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
+    for (int it = blockIdx.x; it < items; it += gridDim.x) {
+        const unsigned f = list ? (unsigned)list[(size_t)s * G.nth * nb + it] : ~(unsigned)top[s];
+        const int      k = f / nb, A = (f % nb) % G.nbx, B = (f % nb) / G.nbx;
+        const double   c = S.cs[((size_t)s * G.nth + k) * 2], sn = S.cs[((size_t)s * G.nth + k) * 2 + 1];
+        int            a[kBlockPer], b[kBlockPer], acc[kBlockPer];
+#pragma unroll
+        for (int r = 0; r < kBlockPer; ++r) {
+            const int cnd = r * 64 + threadIdx.x;
+            a[r] = A * G.D + cnd % G.D, b[r] = B * G.D + cnd / G.D, acc[r] = 0;
+            if (cnd >= G.D * G.D || a[r] >= G.nx || b[r] >= G.ny) a[r] = -1;
+        }
+        for (int base = 0; base < n; base += kChunk) {
+            const int cn = n - base < kChunk ? n - base : kChunk;
+            __syncthreads();
+            stage(G, G.T, S.pts, first, base, cn, n_ga, c, sn, tx, ty, cells, 64);
+            __syncthreads();
+            const int split = n_ga - base < 0 ? 0 : (n_ga - base > cn ? cn : n_ga - base);
+            for (int cl = 0; cl < 2; ++cl) {
+                const Tab t = G.T[cl];
+                const int j1 = cl ? cn : split;
+                for (int j = cl ? split : 0; j < j1; ++j) {
+                    const int2 q = cells[j];
+#pragma unroll
+                    for (int r = 0; r < kBlockPer; ++r) {
+                        const int col = q.x + a[r], row = q.y + b[r];
+                        if (a[r] >= 0 && (unsigned)col < (unsigned)t.w && (unsigned)row < (unsigned)t.h) acc[r] += t.v[(size_t)row * t.w + col];
+                    }
+                }
+            }
+        }
+        unsigned long long key = 0;
+#pragma unroll
+        for (int r = 0; r < kBlockPer; ++r)
+            if (a[r] >= 0) {
+                const unsigned long long kk = key_of(acc[r], ((unsigned)k * G.ny + b[r]) * G.nx + a[r]);
+                key = kk > key ? kk : key;
+            }
+        key = wave_max(key);
+        if (threadIdx.x == 0 && key) atomicMax(&best[s], key);
+    }
+}
+
+// every block whose bound reaches the lower bound L (>=: a tie with the best so far must survive), the top block excepted
+__global__ void csm_select_kernel(Geom G, Scans S, const int32_t *U, const unsigned long long *top, const unsigned long long *best, int32_t *list,
+                                  int32_t *count)
+{
+    const int per = G.nth * G.nbx * G.nby, s = blockIdx.y;
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    int       first, n, n_ga;
+    scan_range(S, s, first, n, n_ga);
+    if (n < 5 || f >= per) return;
+    const int L = (int)(best[s] >> 32);
+    if (U[(size_t)s * per + f] >= L && (unsigned)f != ~(unsigned)top[s]) list[(size_t)s * per + atomicAdd(&count[s], 1)] = f;
+}
+
+// the answer of scan s: the winner's indices, the points counted at its angle, the pose
+__global__ __launch_bounds__(256) void csm_finish_kernel(Geom G, Scans S, const unsigned long long *best, const int32_t *count, int all_blocks,
+                                                         const double *R0, double *R, double *t, slam_csm_result *res)
+{
+    __shared__ int counted;
+    const int      s = blockIdx.x;
+    int            first, n, n_ga;
+    scan_range(S, s, first, n, n_ga);
+    const double tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
+    double       r0[4];
+    for (int i = 0; i < 4; ++i) r0[i] = R0[4 * s + i];
+    if (threadIdx.x == 0) counted = 0;
+    __syncthreads(); // (also: every read of the initial pose is behind us when R and t, which may be the same arrays, are written)
+    slam_csm_result out = {0, 0, 0, -1, 0, 0, 0};
+    if (n < 5) {
+        if (threadIdx.x == 0) {
+            for (int i = 0; i < 4; ++i) R[4 * s + i] = r0[i];
+            t[2 * s] = tx, t[2 * s + 1] = ty;
+            if (res) res[s] = out;
+        }
+        return;
+    }
+    const unsigned long long key = best[s];
+    const unsigned           flat = ~(unsigned)key;
+    out.k = flat / (G.nx * G.ny), out.b = flat / G.nx % G.ny, out.a = flat % G.nx, out.score = (int)(key >> 32);
+    const double c = S.cs[((size_t)s * G.nth + out.k) * 2], sn = S.cs[((size_t)s * G.nth + out.k) * 2 + 1];
+    int          mine = 0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        int cx, cy;
+        mine += point_cell(G.T, S.pts, first, i, n_ga, c, sn, tx, ty, G.res, cx, cy) ? 1 : 0;
+    }
+    atomicAdd(&counted, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out.n_points = counted, out.max_score = 255 * counted;
+        out.blocks_evaluated = all_blocks ? all_blocks : count[s] + 1;
+        R[4 * s] = c, R[4 * s + 1] = -sn, R[4 * s + 2] = sn, R[4 * s + 3] = c;
+        t[2 * s] = __dadd_rn(tx, __dmul_rn((double)(out.a - G.half_x), G.res));
+        t[2 * s + 1] = __dadd_rn(ty, __dmul_rn((double)(out.b - G.half_y), G.res));
+        if (res) res[s] = out;
+    }
+}
+
+inline unsigned blocks_for(size_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+} // namespace
+
+struct slam_csm {
+    slam_csm_params P;
+    struct Table {
+        int    ox = 0, oy = 0, w = 0, h = 0;
+        DevMem T, W;
+    } tab[2];
+    // scratch of a match, for max_scans scans: the bounds, the survivor list, then top and best keys and the list counters
+    DevMem U, list, keys;
+    int    max_scans = 0;
+    // staging of the host form
+    DevMem pts, small;
+
+    int  nth() const { return 2 * P.half_theta + 1; }
+    int  nx() const { return 2 * P.half_x + 1; }
+    int  ny() const { return 2 * P.half_y + 1; }
+    int  nbx() const { return (nx() + P.block - 1) / P.block; }
+    int  nby() const { return (ny() + P.block - 1) / P.block; }
+    Geom geom() const
+    {
+        Geom g;
+        for (int c = 0; c < 2; ++c) {
+            const int D1 = P.block - 1;
+            g.T[c] = Tab{tab[c].T.as<uint8_t>(), tab[c].ox, tab[c].oy, tab[c].w, tab[c].h};
+            g.W[c] = tab[c].w ? Tab{tab[c].W.as<uint8_t>(), tab[c].ox - D1, tab[c].oy - D1, tab[c].w + D1, tab[c].h + D1} : Tab{nullptr, 0, 0, 0, 0};
+        }
+        g.res = P.resolution, g.half_x = P.half_x, g.half_y = P.half_y, g.nx = nx(), g.ny = ny(), g.nth = nth(), g.D = P.block;
+        g.nbx = nbx(), g.nby = nby();
+        return g;
+    }
+};
+
+namespace {
+
+int check_window(int half_x, int half_y, int half_theta, double theta_step, int D)
+{
+    SLAM_REQUIRE(half_x >= 0 && half_y >= 0 && half_theta >= 0 && half_x <= 16383 && half_y <= 16383 && half_theta <= 16383 && std::isfinite(theta_step),
+                 SLAM_E_INVALID, "slam_csm: half_x, half_y and half_theta lie in 0 .. 16383 and theta_step is finite");
+    const double cand = (2.0 * half_x + 1) * (2.0 * half_y + 1) * (2.0 * half_theta + 1);
+    SLAM_REQUIRE(cand < 2147483648.0, SLAM_E_INVALID, "slam_csm: %.0f candidates do not fit a 31-bit index", cand);
+    return SLAM_OK;
+}
+
+int check_params(slam_csm_params &p)
+{
+    SLAM_REQUIRE(p.resolution > 0 && std::isfinite(p.resolution) && p.sigma > 0 && std::isfinite(p.sigma), SLAM_E_INVALID,
+                 "slam_csm: resolution and sigma must be positive");
+    if (p.kernel_cells <= 0) {
+        const double k = std::ceil(3.0 * p.sigma / p.resolution - 1e-9);
+        SLAM_REQUIRE(k <= kMaxK, SLAM_E_INVALID, "slam_csm: 3 sigma is %.0f cells, the stamp holds at most %d", k, kMaxK);
+        p.kernel_cells = k < 0 ? 0 : (int)k;
+    }
+    SLAM_REQUIRE(p.kernel_cells <= kMaxK, SLAM_E_INVALID, "slam_csm: kernel_cells at most %d", kMaxK);
+    SLAM_REQUIRE(p.block >= 1 && p.block <= kMaxD, SLAM_E_INVALID, "slam_csm: block lies in 1 .. %d", kMaxD);
+    return check_window(p.half_x, p.half_y, p.half_theta, p.theta_step, p.block);
+}
+
+// T and W of class c from n model points on the device; waits
+int build_table(slam_csm *s, int c, const double *d_m, int n, const uint8_t *d_stamp, hipStream_t st)
+{
+    if (n <= 3) return SLAM_OK; // icpPointToPoint.cpp:59,93: ICP does not use such a class either
+    const int K = s->P.kernel_cells, D = s->P.block, SS = (2 * K + 1) * (2 * K + 1);
+    DevMem    cells, bbox, plane;
+    SLAM_TRY(cells.alloc(sizeof(int2) * (size_t)n));
+    SLAM_TRY(bbox.alloc(4 * sizeof(int)));
+    const int init[4] = {INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN};
+    int       got[4];
+    SLAM_HIP(hipMemcpyAsync(bbox.p, init, sizeof init, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(csm_model_cells_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, d_m, n, s->P.resolution, cells.as<int2>(), bbox.as<int>());
+    SLAM_HIP(hipGetLastError());
+    SLAM_HIP(hipMemcpyAsync(got, bbox.p, sizeof got, hipMemcpyDeviceToHost, st));
+    SLAM_HIP(hipStreamSynchronize(st));
+    if (got[0] > got[1]) return SLAM_OK; // no point with a cell
+    const long long w = (long long)got[1] - got[0] + 1 + 2 * K, h = (long long)got[3] - got[2] + 1 + 2 * K;
+    SLAM_REQUIRE((double)(w + D) * (double)(h + D) <= (double)kMaxTableBytes, SLAM_E_INVALID,
+                 "slam_csm_create: class %d spans %lld x %lld cells, more than %zu bytes of table", c, w, h, kMaxTableBytes);
+    slam_csm::Table &t = s->tab[c];
+    const size_t     nT = (size_t)w * h, nW = (size_t)(w + D - 1) * (h + D - 1);
+    SLAM_TRY(t.T.alloc(nT));
+    SLAM_TRY(t.W.alloc(nW));
+    SLAM_TRY(plane.alloc(sizeof(unsigned) * nT));
+    t.ox = got[0] - K, t.oy = got[2] - K, t.w = (int)w, t.h = (int)h;
+    SLAM_HIP(hipMemsetAsync(plane.p, 0, sizeof(unsigned) * nT, st));
+    hipLaunchKernelGGL(csm_scatter_kernel, dim3(blocks_for((size_t)n * SS, 256)), dim3(256), 0, st, cells.as<int2>(), n, d_stamp, K, t.ox, t.oy, t.w, t.h,
+                       plane.as<unsigned>());
+    SLAM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(csm_pack_kernel, dim3(blocks_for(nT, 256)), dim3(256), 0, st, plane.as<unsigned>(), nT, t.T.as<uint8_t>());
+    SLAM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(csm_slide_kernel, dim3(blocks_for(nW, 256)), dim3(256), 0, st, t.T.as<uint8_t>(), t.w, t.h, D, t.W.as<uint8_t>());
+    SLAM_HIP(hipGetLastError());
+    SLAM_HIP(hipStreamSynchronize(st)); // the temporaries go back below
+    return SLAM_OK;
+}
+
+int reserve_scans(slam_csm *s, int max_scans)
+{
+    const size_t per = (size_t)s->nth() * s->nbx() * s->nby();
+    SLAM_REQUIRE((double)per * max_scans * sizeof(int32_t) < 4e9, SLAM_E_INVALID, "slam_csm_reserve: %d scans of %zu blocks are too many", max_scans, per);
+    SLAM_TRY(s->U.reserve(sizeof(int32_t) * per * max_scans));
+    SLAM_TRY(s->list.reserve(sizeof(int32_t) * per * max_scans));
+    SLAM_TRY(s->keys.reserve((2 * sizeof(unsigned long long) + sizeof(int32_t)) * (size_t)max_scans));
+    s->max_scans = max_scans;
+    return SLAM_OK;
+}
+
+int create_common(const double *d_ga, int n_ga, const double *d_nga, int n_nga, const slam_csm_params &p, slam_csm_t **out)
+{
+    slam_csm *s = new (std::nothrow) slam_csm();
+    SLAM_REQUIRE(s, SLAM_E_NOMEM, "slam_csm_create: out of host memory");
+    s->P = p;
+    const int K = p.kernel_cells, S = 2 * K + 1;
+    uint8_t   stamp[(2 * kMaxK + 1) * (2 * kMaxK + 1)];
+    for (int j = 0; j < S; ++j)
+        for (int i = 0; i < S; ++i) {
+            const double d2 = (double)((i - K) * (i - K) + (j - K) * (j - K));
+            stamp[j * S + i] = (uint8_t)std::rint(255.0 * std::exp(-(d2 * (p.resolution * p.resolution)) / (2.0 * (p.sigma * p.sigma))));
+        }
+    DevMem d_stamp;
+    int    rc = d_stamp.alloc((size_t)S * S);
+    if (rc == SLAM_OK && hipMemcpy(d_stamp.p, stamp, (size_t)S * S, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("slam_csm_create: the stamp's upload failed");
+        rc = SLAM_E_HIP;
+    }
+    if (rc == SLAM_OK) rc = build_table(s, 0, d_ga, n_ga, d_stamp.as<uint8_t>(), nullptr);
+    if (rc == SLAM_OK) rc = build_table(s, 1, d_nga, n_nga, d_stamp.as<uint8_t>(), nullptr);
+    if (rc == SLAM_OK) rc = reserve_scans(s, 1);
+    if (rc != SLAM_OK) {
+        delete s;
+        return rc;
+    }
+    *out = s;
+    return SLAM_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void slam_csm_default_params(slam_csm_params *p)
+{
+    if (!p) return;
+    p->resolution = 0.1, p->sigma = 0.2, p->kernel_cells = 0, p->block = 8;
+    p->half_x = p->half_y = 40, p->half_theta = 120, p->theta_step = 0.01, p->exhaustive = 0;
+}
+
+int slam_csm_create_dev(const double *d_m_ga, int n_ga, const double *d_m_nga, int n_nga, const slam_csm_params *params, slam_csm_t **out)
+{
+    SLAM_REQUIRE(out, SLAM_E_INVALID, "slam_csm_create: null out pointer");
+    *out = nullptr;
+    SLAM_REQUIRE(n_ga >= 0 && n_nga >= 0 && (n_ga == 0 || d_m_ga) && (n_nga == 0 || d_m_nga), SLAM_E_INVALID, "slam_csm_create: bad model arrays");
+    slam_csm_params p;
+    slam_csm_default_params(&p);
+    if (params) p = *params;
+    SLAM_TRY(check_params(p));
+    SLAM_TRY(require_device());
+    return create_common(d_m_ga, n_ga, d_m_nga, n_nga, p, out);
+}
+
+int slam_csm_create(const double *m_ga, int n_ga, const double *m_nga, int n_nga, const slam_csm_params *params, slam_csm_t **out)
+{
+    SLAM_REQUIRE(out, SLAM_E_INVALID, "slam_csm_create: null out pointer");
+    *out = nullptr;
+    SLAM_REQUIRE(n_ga >= 0 && n_nga >= 0 && (n_ga == 0 || m_ga) && (n_nga == 0 || m_nga), SLAM_E_INVALID, "slam_csm_create: bad model arrays");
+    slam_csm_params p;
+    slam_csm_default_params(&p);
+    if (params) p = *params;
+    SLAM_TRY(check_params(p));
+    SLAM_TRY(require_device());
+    DevMem       model;
+    const size_t b_ga = sizeof(double) * 2 * (size_t)n_ga, b_nga = sizeof(double) * 2 * (size_t)n_nga;
+    SLAM_TRY(model.alloc(b_ga + b_nga));
+    if (b_ga) SLAM_HIP(hipMemcpy(model.p, m_ga, b_ga, hipMemcpyHostToDevice));
+    if (b_nga) SLAM_HIP(hipMemcpy(model.as<char>() + b_ga, m_nga, b_nga, hipMemcpyHostToDevice));
+    return create_common(model.as<double>(), n_ga, model.as<double>() + 2 * (size_t)n_ga, n_nga, p, out);
+}
+
+void slam_csm_destroy(slam_csm_t *csm)
+{
+    delete csm; // (hipFree waits for what is still enqueued)
+}
+
+int slam_csm_reserve(slam_csm_t *csm, int max_scans)
+{
+    SLAM_REQUIRE(csm && max_scans >= 1, SLAM_E_INVALID, "slam_csm_reserve: bad arguments");
+    return reserve_scans(csm, max_scans > csm->max_scans ? max_scans : csm->max_scans);
+}
+
+int slam_csm_set_window(slam_csm_t *csm, int half_x, int half_y, int half_theta, double theta_step)
+{
+    SLAM_REQUIRE(csm, SLAM_E_INVALID, "slam_csm_set_window: null handle");
+    SLAM_TRY(check_window(half_x, half_y, half_theta, theta_step, csm->P.block));
+    const slam_csm_params old = csm->P;
+    csm->P.half_x = half_x, csm->P.half_y = half_y, csm->P.half_theta = half_theta, csm->P.theta_step = theta_step;
+    const int rc = reserve_scans(csm, csm->max_scans);
+    if (rc != SLAM_OK) csm->P = old;
+    return rc;
+}
+
+int slam_csm_set_exhaustive(slam_csm_t *csm, int exhaustive)
+{
+    SLAM_REQUIRE(csm, SLAM_E_INVALID, "slam_csm_set_exhaustive: null handle");
+    csm->P.exhaustive = exhaustive ? 1 : 0;
+    return SLAM_OK;
+}
+
+int slam_csm_angles(slam_csm_t *csm, const double R0[4], double *cs)
+{
+    SLAM_REQUIRE(csm && R0 && cs, SLAM_E_INVALID, "slam_csm_angles: null argument");
+    const double th0 = std::atan2(R0[2], R0[0]);
+    for (int k = 0; k < csm->nth(); ++k) {
+        const double th = th0 + (double)(k - csm->P.half_theta) * csm->P.theta_step;
+        cs[2 * k] = std::cos(th), cs[2 * k + 1] = std::sin(th);
+    }
+    return SLAM_OK;
+}
+
+int slam_csm_match_batch_dev(slam_csm_t *csm, const double *d_pts, const int32_t *d_scan_off, const int32_t *d_scan_nga, int n_scans,
+                             const double *d_R0, const double *d_t0, const double *d_cs, double *d_R, double *d_t, slam_csm_result *d_result,
+                             slam_stream_t stream)
+{
+    SLAM_REQUIRE(csm && n_scans >= 0, SLAM_E_INVALID, "slam_csm_match_batch_dev: bad arguments");
+    if (n_scans == 0) return SLAM_OK;
+    SLAM_REQUIRE(d_pts && d_scan_off && d_scan_nga && d_R0 && d_t0 && d_cs && d_R && d_t, SLAM_E_INVALID, "slam_csm_match_batch_dev: null array");
+    SLAM_REQUIRE(n_scans <= csm->max_scans && n_scans <= 65535, SLAM_E_INVALID,
+                 "slam_csm_match_batch_dev: %d scans, scratch is reserved for %d (slam_csm_reserve; at most 65535)", n_scans, csm->max_scans);
+    hipStream_t  st = as_stream(stream);
+    const Geom   G = csm->geom();
+    const Scans  S{d_pts, d_scan_off, d_scan_nga, 0, 0, d_t0, d_cs};
+    const int    nb = G.nbx * G.nby, per = G.nth * nb;
+    auto        *top = csm->keys.as<unsigned long long>(), *best = top + csm->max_scans;
+    int32_t     *count = reinterpret_cast<int32_t *>(best + csm->max_scans);
+    const size_t key_bytes = (2 * sizeof(unsigned long long) + sizeof(int32_t)) * (size_t)csm->max_scans;
+    SLAM_HIP(hipMemsetAsync(csm->keys.p, 0, key_bytes, st));
+    if (csm->P.exhaustive) {
+        const int tiles = ((G.nx + kTileW - 1) / kTileW) * ((G.ny + kTileH - 1) / kTileH);
+        hipLaunchKernelGGL(csm_tiles_kernel, dim3(tiles, G.nth, n_scans), dim3(256), 0, st, G, S, (int32_t *)nullptr, best);
+        SLAM_HIP(hipGetLastError());
+    } else {
+        const int groups = (nb + 64 * kCoarsePer - 1) / (64 * kCoarsePer);
+        int       stride = 4096 / n_scans; // workgroups striding over a scan's list
+        stride = stride < 8 ? 8 : (stride > 1024 ? 1024 : stride);
+        hipLaunchKernelGGL(csm_coarse_kernel, dim3(G.nth * groups, n_scans), dim3(64), 0, st, G, S, csm->U.as<int32_t>(), top);
+        SLAM_HIP(hipGetLastError());
+        hipLaunchKernelGGL(csm_blocks_kernel, dim3(1, n_scans), dim3(64), 0, st, G, S, top, (const int32_t *)nullptr, (const int32_t *)nullptr, best);
+        SLAM_HIP(hipGetLastError());
+        hipLaunchKernelGGL(csm_select_kernel, dim3(blocks_for(per, 256), n_scans), dim3(256), 0, st, G, S, csm->U.as<int32_t>(), top, best,
+                           csm->list.as<int32_t>(), count);
+        SLAM_HIP(hipGetLastError());
+        hipLaunchKernelGGL(csm_blocks_kernel, dim3(stride, n_scans), dim3(64), 0, st, G, S, top, csm->list.as<int32_t>(), count, best);
+        SLAM_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(csm_finish_kernel, dim3(n_scans), dim3(256), 0, st, G, S, best, count, csm->P.exhaustive ? per : 0, d_R0, d_R, d_t, d_result);
+    SLAM_HIP(hipGetLastError());
+    return SLAM_OK;
+}
+
+int slam_csm_match(slam_csm_t *csm, const double *t_ga, int n_tga, const double *t_nga, int n_tnga, double R[4], double t[2],
+                   slam_csm_result *result)
+{
+    SLAM_REQUIRE(csm && R && t && n_tga >= 0 && n_tnga >= 0 && (n_tga == 0 || t_ga) && (n_tnga == 0 || t_nga), SLAM_E_INVALID,
+                 "slam_csm_match: bad arguments");
+    const int n = n_tga + n_tnga;
+    SLAM_REQUIRE(n >= 5, SLAM_E_TOO_FEW_SCENE_POINTS, "slam_csm_match: %d scene points, at least 5 are needed", n);
+    // one block behind the points: offsets, class count, R0, t0, the angles, R, t, the result
+    const size_t cs_b = sizeof(double) * 2 * (size_t)csm->nth();
+    const size_t small_b = 16 + sizeof(double) * 12 + cs_b + sizeof(slam_csm_result);
+    SLAM_TRY(reserve_quarter(csm->pts, sizeof(double) * 2 * (size_t)n));
+    SLAM_TRY(csm->small.reserve(small_b));
+    char *host = static_cast<char *>(pinned_scratch(small_b));
+    SLAM_REQUIRE(host, SLAM_E_NOMEM, "slam_csm_match: no pinned staging memory");
+    int32_t *h_off = reinterpret_cast<int32_t *>(host);
+    double  *h_pose = reinterpret_cast<double *>(host + 16), *h_cs = h_pose + 12;
+    h_off[0] = 0, h_off[1] = n, h_off[2] = n_tga, h_off[3] = 0;
+    std::memcpy(h_pose, R, 4 * sizeof(double));
+    std::memcpy(h_pose + 4, t, 2 * sizeof(double));
+    SLAM_TRY(slam_csm_angles(csm, R, h_cs));
+    char    *dev = csm->small.as<char>();
+    double  *d_pose = reinterpret_cast<double *>(dev + 16);
+    auto    *d_res = reinterpret_cast<slam_csm_result *>(dev + 16 + sizeof(double) * 12 + cs_b);
+    double  *d_pts = csm->pts.as<double>();
+    if (n_tga) SLAM_HIP(hipMemcpyAsync(d_pts, t_ga, sizeof(double) * 2 * (size_t)n_tga, hipMemcpyHostToDevice, nullptr));
+    if (n_tnga) SLAM_HIP(hipMemcpyAsync(d_pts + 2 * (size_t)n_tga, t_nga, sizeof(double) * 2 * (size_t)n_tnga, hipMemcpyHostToDevice, nullptr));
+    SLAM_HIP(hipMemcpyAsync(dev, host, 16 + sizeof(double) * 12 + cs_b, hipMemcpyHostToDevice, nullptr));
+    SLAM_TRY(slam_csm_match_batch_dev(csm, d_pts, reinterpret_cast<int32_t *>(dev), reinterpret_cast<int32_t *>(dev) + 2, 1, d_pose, d_pose + 4,
+                                      d_pose + 12, d_pose + 6, d_pose + 10, d_res, nullptr));
+    SLAM_HIP(hipMemcpyAsync(host, dev, small_b, hipMemcpyDeviceToHost, nullptr));
+    SLAM_HIP(hipStreamSynchronize(nullptr));
+    std::memcpy(R, h_pose + 6, 4 * sizeof(double));
+    std::memcpy(t, h_pose + 10, 2 * sizeof(double));
+    if (result) std::memcpy(result, host + 16 + sizeof(double) * 12 + cs_b, sizeof *result);
+    return SLAM_OK;
+}
+
+int slam_csm_score_volume_dev(slam_csm_t *csm, const double *d_pts, int n, int n_ga, const double *d_t0, const double *d_cs, int32_t *d_volume,
+                              slam_stream_t stream)
+{
+    SLAM_REQUIRE(csm && d_pts && n >= 5 && n_ga >= 0 && d_t0 && d_cs && d_volume, SLAM_E_INVALID,
+                 "slam_csm_score_volume_dev: bad arguments (a scan has at least 5 points)");
+    const Geom  G = csm->geom();
+    const Scans S{d_pts, nullptr, nullptr, n, n_ga, d_t0, d_cs};
+    const int   tiles = ((G.nx + kTileW - 1) / kTileW) * ((G.ny + kTileH - 1) / kTileH);
+    hipLaunchKernelGGL(csm_tiles_kernel, dim3(tiles, G.nth, 1), dim3(256), 0, as_stream(stream), G, S, d_volume, (unsigned long long *)nullptr);
+    SLAM_HIP(hipGetLastError());
+    return SLAM_OK;
+}
+
+int slam_csm_read_table(slam_csm_t *csm, int cls, int level, int *origin_x, int *origin_y, int *w, int *h, uint8_t *buf, size_t cap)
+{
+    SLAM_REQUIRE(csm && (cls == 0 || cls == 1) && (level == 0 || level == 1), SLAM_E_INVALID, "slam_csm_read_table: bad arguments");
+    const Geom G = csm->geom();
+    const Tab &t = level ? G.W[cls] : G.T[cls];
+    if (origin_x) *origin_x = t.ox;
+    if (origin_y) *origin_y = t.oy;
+    if (w) *w = t.w;
+    if (h) *h = t.h;
+    if (buf && t.w) {
+        SLAM_REQUIRE(cap >= (size_t)t.w * t.h, SLAM_E_INVALID, "slam_csm_read_table: room for %zu bytes, the table has %zu", cap, (size_t)t.w * t.h);
+        SLAM_HIP(hipMemcpy(buf, t.v, (size_t)t.w * t.h, hipMemcpyDeviceToHost));
+    }
+    return SLAM_OK;
+}
+
+int slam_csm_info(slam_csm_t *csm, slam_csm_params *params, int dims[5], size_t *table_bytes, size_t *scratch_bytes, int *max_scans)
+{
+    SLAM_REQUIRE(csm, SLAM_E_INVALID, "slam_csm_info: null handle");
+    if (params) *params = csm->P;
+    if (dims) dims[0] = csm->nth(), dims[1] = csm->nx(), dims[2] = csm->ny(), dims[3] = csm->nbx(), dims[4] = csm->nby();
+    if (table_bytes) *table_bytes = csm->tab[0].T.cap + csm->tab[0].W.cap + csm->tab[1].T.cap + csm->tab[1].W.cap;
+    if (scratch_bytes) *scratch_bytes = csm->U.cap + csm->list.cap + csm->keys.cap;
+    if (max_scans) *max_scans = csm->max_scans;
+    return SLAM_OK;
+}
+
+} // extern "C"

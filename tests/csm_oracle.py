@@ -1,0 +1,176 @@
+"""ctypes wrapper of tests/cpp/csm_oracle.cpp, the scalar restatement of the correlative scan matcher's contract
+(docs/CSM.md) that slam_csm_* is held against bit for bit.  Compiled on first use with g++ -O2 -ffp-contract=off into a
+temporary directory.  The parameter and result structures are slam_amd.api's (the header's); nothing else of the
+library is used."""
+import ctypes as C
+import hashlib
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+
+from slam_amd import api, synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "cpp", "csm_oracle.cpp")
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is not None:
+        return _lib
+    h = hashlib.sha1()
+    for f in (SRC, os.path.join(ROOT, "include", "slam_mi355x.h")):
+        h.update(open(f, "rb").read())
+    d = os.path.join(tempfile.gettempdir(), "slam_csm_oracle_%d" % os.getuid())
+    os.makedirs(d, exist_ok=True)
+    so = os.path.join(d, "csm_oracle_%s.so" % h.hexdigest()[:16])
+    if not os.path.exists(so):
+        tmp = so + ".%d.tmp" % os.getpid()
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-shared", "-fPIC",
+                               "-I", os.path.join(ROOT, "include"), SRC, "-o", tmp])
+        os.replace(tmp, so)
+    L = C.CDLL(so)
+    vp, ip = C.c_void_p, C.POINTER(C.c_int)
+    L.csmo_create.restype = vp
+    L.csmo_create.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(api.CsmParams)]
+    L.csmo_destroy.argtypes = [vp]
+    L.csmo_destroy.restype = None
+    L.csmo_set_window.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double]
+    L.csmo_set_window.restype = None
+    L.csmo_kernel_cells.argtypes = [vp]
+    L.csmo_table.argtypes = [vp, C.c_int, C.c_int, ip, ip, ip, ip, vp]
+    L.csmo_table.restype = None
+    L.csmo_angles.argtypes = [vp, vp, vp]
+    L.csmo_angles.restype = None
+    L.csmo_volume.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.csmo_volume.restype = None
+    L.csmo_bounds.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.csmo_bounds.restype = None
+    L.csmo_match.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.POINTER(api.CsmResult)]
+    L.csmo_match.restype = None
+    _lib = L
+    return L
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+
+
+def default_params(**kw):
+    """slam_csm_default_params's values without the library."""
+    p = api.CsmParams(0.1, 0.2, 0, 8, 40, 40, 120, 0.01, 0)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def result_tuple(r):
+    """(k, a, b, score, n_points, max_score) of an api.CsmResult or a row of api.CSM_RESULT_DTYPE"""
+    if isinstance(r, api.CsmResult):
+        return (r.k, r.a, r.b, r.score, r.n_points, r.max_score)
+    return tuple(int(r[f]) for f in ("k", "a", "b", "score", "n_points", "max_score"))
+
+
+class OracleMatcher:
+    def __init__(self, m_ga, m_nga, params=None, **kw):
+        self.m_ga = np.ascontiguousarray(m_ga, dtype=np.float64).reshape(-1, 2)
+        self.m_nga = np.ascontiguousarray(m_nga, dtype=np.float64).reshape(-1, 2)
+        self.params = params or default_params(**kw)
+        self.h = lib().csmo_create(_p(self.m_ga), len(self.m_ga), _p(self.m_nga), len(self.m_nga), C.byref(self.params))
+        self.params.kernel_cells = lib().csmo_kernel_cells(self.h)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().csmo_destroy(self.h)
+            self.h = None
+
+    def set_window(self, half_x, half_y, half_theta, theta_step):
+        lib().csmo_set_window(self.h, int(half_x), int(half_y), int(half_theta), float(theta_step))
+        P = self.params
+        P.half_x, P.half_y, P.half_theta, P.theta_step = int(half_x), int(half_y), int(half_theta), float(theta_step)
+
+    @property
+    def dims(self):
+        """N_theta, N_y, N_x"""
+        P = self.params
+        return 2 * P.half_theta + 1, 2 * P.half_y + 1, 2 * P.half_x + 1
+
+    @property
+    def block_dims(self):
+        n_th, n_y, n_x = self.dims
+        D = self.params.block
+        return n_th, (n_y + D - 1) // D, (n_x + D - 1) // D
+
+    def table(self, cls, level=0):
+        ox, oy, w, h = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        lib().csmo_table(self.h, cls, level, C.byref(ox), C.byref(oy), C.byref(w), C.byref(h), None)
+        buf = np.zeros((h.value, w.value), np.uint8)
+        lib().csmo_table(self.h, cls, level, C.byref(ox), C.byref(oy), C.byref(w), C.byref(h), _p(buf))
+        return ox.value, oy.value, buf
+
+    def angles(self, R0):
+        R0 = np.ascontiguousarray(R0, dtype=np.float64).reshape(4)
+        cs = np.zeros((self.dims[0], 2))
+        lib().csmo_angles(self.h, _p(R0), _p(cs))
+        return cs
+
+    @staticmethod
+    def _scan(t_ga, t_nga):
+        t_ga, t_nga = np.reshape(t_ga, (-1, 2)), np.reshape(t_nga, (-1, 2))
+        return np.ascontiguousarray(np.concatenate([t_ga, t_nga]), dtype=np.float64), len(t_ga)
+
+    def volume(self, t_ga, t_nga, R0, t0, counted=False):
+        pts, n_ga = self._scan(t_ga, t_nga)
+        R0 = np.ascontiguousarray(R0, dtype=np.float64).reshape(4)
+        t0 = np.ascontiguousarray(t0, dtype=np.float64).reshape(2)
+        vol, cnt = np.zeros(self.dims, np.int32), np.zeros(self.dims[0], np.int32)
+        lib().csmo_volume(self.h, _p(pts), len(pts), n_ga, _p(R0), _p(t0), _p(vol), _p(cnt))
+        return (vol, cnt) if counted else vol
+
+    def bounds(self, t_ga, t_nga, R0, t0):
+        pts, n_ga = self._scan(t_ga, t_nga)
+        R0 = np.ascontiguousarray(R0, dtype=np.float64).reshape(4)
+        t0 = np.ascontiguousarray(t0, dtype=np.float64).reshape(2)
+        U = np.zeros(self.block_dims, np.int32)
+        lib().csmo_bounds(self.h, _p(pts), len(pts), n_ga, _p(R0), _p(t0), _p(U))
+        return U
+
+    def match(self, t_ga, t_nga, R0, t0, exhaustive=False):
+        """(R, t, api.CsmResult); a scan of fewer than 5 points keeps its pose, score -1"""
+        pts, n_ga = self._scan(t_ga, t_nga)
+        R = np.ascontiguousarray(R0, dtype=np.float64).reshape(4).copy()
+        t = np.ascontiguousarray(t0, dtype=np.float64).reshape(2).copy()
+        res = api.CsmResult()
+        lib().csmo_match(self.h, _p(pts), len(pts), n_ga, _p(R), _p(t), int(exhaustive), C.byref(res))
+        return R.reshape(2, 2), t, res
+
+
+# ------------------------------------------------------------------ the basin: scans far outside ICP's reach
+BASIN_KS = (0, 32, 64, 96, 128, 160, 192, 224)
+BASIN_OFFSET = (3.0, -3.0, 1.0)    # metres, metres, radians on top of the true pose
+_map = None
+
+
+def synth_map():
+    global _map
+    if _map is None:
+        _map = synth.make_map()
+    return _map
+
+
+def basin_case(k):
+    """(t_ga, t_nga, true pose, R0 [2, 2], t0 [2]) of scan k of the 256-pose loop, started BASIN_OFFSET off the truth"""
+    t_ga, t_nga, pose = synth.make_scan(k, 256)
+    R0, t0 = synth.pose_to_Rt(pose[0] + BASIN_OFFSET[0], pose[1] + BASIN_OFFSET[1], pose[2] + BASIN_OFFSET[2])
+    return t_ga, t_nga, pose, R0, t0
+
+
+def pose_error(R, t, pose):
+    """(metres, radians) of a 2-D pose from the truth (x, y, theta)"""
+    R = np.reshape(R, (2, 2))
+    d = np.arctan2(R[1, 0], R[0, 0]) - pose[2]
+    d = (d + np.pi) % (2 * np.pi) - np.pi
+    return float(np.hypot(t[0] - pose[0], t[1] - pose[1])), float(abs(d))
