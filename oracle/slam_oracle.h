@@ -200,6 +200,26 @@ void ogseg_default_params(ogseg_params *p);
 int ogseg_segment(const ogseg_params *p, const float *xyz, int n, int stride, unsigned char *labels,
                   int *bin_of, unsigned char *sector_model, double *sector_value);
 
+/* The same segmentation (one body serves both), and what it went through.  Optional outputs (may be NULL):
+ * sector_seeds[72] = size of the seed model; sector_rounds[72] = INSAC outer iterations; round_model[72*200] = the
+ * model size entering round r of sector s at [s*200 + r], -1 past the last round; margins[OGSEG_NMARGINS] = the smallest
+ * distance of any decision to its threshold, in the decision's own units (infinity where none was taken):
+ *   VF          Vf of a candidate to p_tmodel                     MET    |metric| to p_tdata, where Vf let it decide
+ *   GROUND      the float h of a point in a model bin to p_tg     ROBOT  the float h of a point not ground to robot_height
+ *   SEED_RANGE, SEED_HEIGHT  range and |height| of every signal bin to the seed gates
+ * long_double_solve != 0 carries the LU solve and the sums behind f_s and Vf in long double: the difference to the
+ * double run is the oracle's own rounding. */
+#define OGSEG_MARGIN_VF          0
+#define OGSEG_MARGIN_MET         1
+#define OGSEG_MARGIN_GROUND      2
+#define OGSEG_MARGIN_ROBOT       3
+#define OGSEG_MARGIN_SEED_RANGE  4
+#define OGSEG_MARGIN_SEED_HEIGHT 5
+#define OGSEG_NMARGINS           6
+int ogseg_segment_trace(const ogseg_params *p, const float *xyz, int n, int stride, unsigned char *labels,
+                        int *bin_of, unsigned char *sector_model, double *sector_value, int *sector_seeds,
+                        int *sector_rounds, int *round_model, double *margins, int long_double_solve);
+
 /* CCICP::classifyPoints (icpTools.cpp:36-103): per obstacle point 1 = ground adjacent,
  * 0 = not, 255 = dropped (outside the 1200 x 1200 x 0.5 m lattice or in its edge cells). */
 void occicp_classify(const float *xyz, int n, int stride, unsigned char *flags);

@@ -46,6 +46,18 @@ __device__ inline unsigned orderable(float z)
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// :129 atan2(y, x) in degrees.  On an axis or a diagonal the angle is a multiple of 45 degrees, the floor of a sector: libm's atan2
+// times 180/pi gives exactly that multiple there, and an atan2 one ulp short would put the point a sector lower.  Those
+// directions are answered outright; every other sector border is about 1e-8 rad from the nearest pair of floats.
+__device__ inline double gseg_azimuth_deg(double px, double py)
+{
+    const double ax = fabs(px), ay = fabs(py);
+    if (ax > 0 && ax == ay) return py > 0 ? (px > 0 ? 45.0 : 135.0) : (px > 0 ? -45.0 : -135.0);
+    if (ay == 0 && ax > 0) return px > 0 ? 0.0 : 180.0;
+    if (ax == 0 && ay > 0) return py > 0 ? 90.0 : -90.0;
+    return atan2(py, px) * (180 / M_PI);
+}
+
 // :110-162.  bin_of[i] = sector*200 + bin, or -1 beyond RMAX
 // (adjacent lanes are adjacent azimuth steps of one ring: a 5-degree sector is a run of ~28 lanes in one bin -- the run
 // is counted and its minimum taken inside the wavefront, its last lane issues the two atomics)
@@ -61,7 +73,7 @@ __global__ __launch_bounds__(256) void gseg_bin_kernel(GsegParams p, const float
         const double px = q[0], py = q[1], pz = q[2];
         if (sqrt(px * px + py * py + pz * pz) < p.rmax) { // :126
             const double bsize_rad = 360.0 / NA, bsize_lin = p.rmax / NL;
-            double       ph = atan2(py, px) * (180 / M_PI);
+            double       ph = gseg_azimuth_deg(px, py);
             if (ph < 0) ph = 360.0 + ph;
             unsigned bind_rad = (unsigned)floor(ph / bsize_rad);
             if (bind_rad >= (unsigned)NA) bind_rad = NA - 1; // the reference asserts (:136)
@@ -70,8 +82,11 @@ __global__ __launch_bounds__(256) void gseg_bin_kernel(GsegParams p, const float
             if (bind_lin >= (unsigned)NL) bind_lin = NL - 1;
             b = (int)bind_rad * NL + (int)bind_lin;
             cnt = 1;                                                       // binPoints.push_back :145
-            if (q[2] < kInvalid)                                           // :149 against INVALID; NaN never passes
-                key = ((unsigned long long)orderable(q[2]) << 32) | (unsigned)i;
+            if (q[2] < kInvalid) {                                         // :149 against INVALID; NaN never passes
+                // (`pz < proto_z` holds -0.0f and +0.0f equal and keeps the first: both zeros get one key, the index decides)
+                const float zk = q[2] == 0.0f ? 0.0f : q[2];
+                key = ((unsigned long long)orderable(zk) << 32) | (unsigned)i;
+            }
         }
         bin_of[i] = b;
     }
@@ -187,9 +202,13 @@ __global__ __launch_bounds__(kSecThreads) void gseg_insac_kernel(GsegParams p, c
     }
     __syncthreads();
     // ---- seeds :235-277: the first npt sorted entries that pass the gates; the others, in order, are the candidates
+    // (the reference's loop looks at an entry BEFORE it compares its count with npt (:239-266): with num_seedpoints = 0 it looks
+    // at the lowest entry alone, and takes it if it passes -- a model of one bin or none, "too small" either way)
     {
-        const int  npt = ns0 < p.num_seedpoints ? ns0 : p.num_seedpoints;
-        const bool pass = tid < ns0 && s_range[tid] < p.max_seed_range && fabs(s_height[tid]) < p.max_seed_height;
+        const int  want = ns0 < p.num_seedpoints ? ns0 : p.num_seedpoints;
+        const int  npt = want > 0 ? want : 1;
+        const bool pass = tid < ns0 && (want > 0 || tid == 0) && s_range[tid] < p.max_seed_range &&
+                          fabs(s_height[tid]) < p.max_seed_height;
         const unsigned long long pm = __ballot(pass);
         if ((tid & 63) == 0) s_wcnt[tid >> 6] = __popcll(pm);
         __syncthreads();
@@ -635,7 +654,11 @@ int slam_gseg_segment(slam_gseg_t *h, const float *xyz, int n, int stride, uint8
     SLAM_REQUIRE(h && n >= 0 && stride >= 3 && (n == 0 || (xyz && labels)), SLAM_E_INVALID,
                  "slam_gseg_segment: bad arguments");
     SLAM_TRY(require_device());
-    if (n == 0) return SLAM_OK;
+    if (n == 0) { // (no point, no label: the sector kernel still runs, so that slam_gseg_read_model shows this cloud's model -- none)
+        SLAM_TRY(slam_gseg_segment_dev(h, nullptr, 0, stride, nullptr, nullptr));
+        SLAM_HIP(hipStreamSynchronize(nullptr));
+        return SLAM_OK;
+    }
     const size_t bytes = sizeof(float) * (size_t)n * stride;
     SLAM_TRY(reserve_quarter(h->d_stage, bytes + (size_t)n));
     float   *d_xyz = h->d_stage.as<float>();

@@ -109,6 +109,9 @@ def lib():
     L.ogseg_segment.restype = C.c_int
     L.ogseg_segment.argtypes = [C.POINTER(OGsegParams), _fp, C.c_int, C.c_int, C.POINTER(C.c_ubyte), _ip,
                                 C.POINTER(C.c_ubyte), _dp]
+    L.ogseg_segment_trace.restype = C.c_int
+    L.ogseg_segment_trace.argtypes = [C.POINTER(OGsegParams), _fp, C.c_int, C.c_int, C.POINTER(C.c_ubyte), _ip,
+                                      C.POINTER(C.c_ubyte), _dp, _ip, _ip, _ip, _dp, C.c_int]
     L.occicp_classify.argtypes = [_fp, C.c_int, C.c_int, C.POINTER(C.c_ubyte)]
     _lib = L
     return L
@@ -362,6 +365,30 @@ def gseg_segment(xyz, params=None):
     it = lib().ogseg_segment(C.byref(p), _f(xyz), n, stride, labels.ctypes.data_as(C.POINTER(C.c_ubyte)),
                              _i(bin_of), state.ctypes.data_as(C.POINTER(C.c_ubyte)), _d(value))
     return labels[:n], bin_of[:n], state, value, it
+
+
+GSEG_MARGINS = ("vf", "met", "ground", "robot", "seed_range", "seed_height")     # OGSEG_MARGIN_*
+
+
+def gseg_segment_trace(xyz, params=None, long_double=False):
+    """gseg_segment and what the oracle went through: a dict with labels, bin_of, state, value, iterations and, per
+    sector, seeds[72], rounds[72], round_model (a list per sector: the model size entering each round), and margins: the
+    smallest distance of any decision to its threshold by GSEG_MARGINS name.  long_double: the solve in long double."""
+    xyz = as_f32(xyz)
+    n, stride = xyz.shape
+    p = params or gseg_params()
+    ub = C.POINTER(C.c_ubyte)
+    labels = np.zeros(max(n, 1), dtype=np.uint8)
+    bin_of = np.zeros(max(n, 1), dtype=np.int32)
+    state = np.zeros(72 * 200, dtype=np.uint8)
+    value = np.zeros(72 * 200)
+    seeds, rounds = np.zeros(72, dtype=np.int32), np.zeros(72, dtype=np.int32)
+    round_model = np.zeros((72, 200), dtype=np.int32)
+    margins = np.zeros(len(GSEG_MARGINS))
+    it = lib().ogseg_segment_trace(C.byref(p), _f(xyz), n, stride, labels.ctypes.data_as(ub), _i(bin_of), state.ctypes.data_as(ub),
+                                   _d(value), _i(seeds), _i(rounds), _i(round_model), _d(margins), int(bool(long_double)))
+    return dict(labels=labels[:n], bin_of=bin_of[:n], state=state, value=value, iterations=it, seeds=seeds, rounds=rounds,
+                round_model=[round_model[s, :rounds[s]].tolist() for s in range(72)], margins=dict(zip(GSEG_MARGINS, margins.tolist())))
 
 
 def classify_ga(xyz):

@@ -9,7 +9,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SUITE = ["tests/test_oracle_icp.py", "tests/test_oracle_grid.py", "tests/test_oracle_solves.py", "tests/test_gseg.py",
-         "tests/test_ccicp.py", "tests/test_multi_rank.py"]
+         "tests/test_ccicp.py", "tests/test_multi_rank.py", "tests/test_gseg_cases.py"]
 
 
 def test_cpu_suite_against_the_sanitized_oracle():
