@@ -141,6 +141,12 @@ public:
     double DIST_MOVE_THRESH = 10.0;
     double ROT_MOVE_THRESH = 0.2;
 
+    // The solver behind calcEdgeIcp / calcEdges / addEdgesForNewNode.  ICP: pcl::IterativeClosestPoint, what graph_slam runs.
+    // GICP: slam_kf_register_gicp (docs/KF_GICP.md), the solver graphSlamTools.cpp names its matcher after (:10,17,37); the
+    // information is still computeEdgeInformationLUM's block and the acceptance gate is the same.
+    enum Registration { ICP = 0, GICP = 1 };
+    Registration registration = ICP;
+
     std::vector<GraphNode> nodes; // PoseGraph
     std::vector<GraphEdge> edges;
 
@@ -214,7 +220,14 @@ public:
             req[e].from = from, req[e].to = to;
             graph_detail::relative_f32(nodes[from].pose, nodes[to].pose, req[e].init); // :258
         }
-        if (slam_kf_register_edges(h_, req.data(), (int)req.size(), res.data(), nullptr) != SLAM_OK) {
+        int rc;
+        if (registration == GICP) {
+            std::vector<slam_kf_gicp_result> gres(pairs.size());
+            rc = slam_kf_register_gicp(h_, req.data(), (int)req.size(), gres.data(), nullptr);
+            for (size_t e = 0; e < pairs.size(); ++e) res[e] = gres[e].edge;
+        } else
+            rc = slam_kf_register_edges(h_, req.data(), (int)req.size(), res.data(), nullptr);
+        if (rc != SLAM_OK) {
             warn();
             return false;
         }

@@ -736,6 +736,49 @@ int  slam_kf_register_edges(slam_kf_t *s, const slam_kf_edge_req *req, int n_edg
 int  slam_kf_register_edges_traced(slam_kf_t *s, const slam_kf_edge_req *req, int n_edges, slam_kf_edge_result *out,
                                    int32_t *pairs_trace, int trace_cap, slam_stream_t stream);
 
+/* Generalized ICP on the same store (pcl::GeneralizedIterativeClosestPoint, which global_matching's programs are built
+ * on: global_match.cpp:52,225-235): a plane-to-plane cost from per-point covariances, one Gauss-Newton step per
+ * iteration, a batch of requests in one launch.  docs/KF_GICP.md has the contract and its deviations from PCL. */
+typedef struct {
+    int    k_correspondences;      /* neighbours a covariance is taken over, the point included (20, PCL's); 4 .. 32 */
+    double cov_radius;             /* neighbours lie within this radius; 0 = twice the edge of the search lattice */
+    double gicp_epsilon;           /* the covariance along the normal, the other two being 1 (1e-3, PCL's) */
+    int    max_iterations;         /* outer iterations (global_match.cpp:229: 10) */
+    double transformation_epsilon; /* stop when no translation entry moved by more (1e-6) */
+    double rotation_epsilon;       /* ... and no rotation entry by more than this (2e-3, PCL's) */
+    int    cov_min_neighbours;     /* a point with fewer neighbours in the radius gets the identity (4) */
+} slam_kf_gicp_params;
+
+#define SLAM_KF_DEGENERATE 6 /* the Gauss-Newton step's 6 x 6 has a pivot that is not positive and finite */
+
+typedef struct {
+    slam_kf_edge_result edge;  /* transform, transform64, iterations, state (ITERATIONS, TRANSFORM, NO_CORRESPONDENCES,
+                                  DEGENERATE), converged, pairs; mse = mean f32 d^2 of the last iteration's pairs; the LUM
+                                  block on the f32 transform exactly as slam_kf_register_edges computes it */
+    double cost;               /* sum r' M r / pairs of the last iteration */
+    double hessian[36];        /* sum J' M J of the last iteration, unknowns (omega, v) */
+    double fitness;            /* mean f32 d^2 of the source points, moved in f32 by the f32 transform, whose nearest
+                                  target point lies strictly inside the gate (PCL's getFitnessScore is ungated) */
+    int    fitness_pairs, reserved;
+} slam_kf_gicp_result;
+
+void slam_kf_gicp_default_params(slam_kf_gicp_params *p);
+/* k_correspondences, cov_radius, gicp_epsilon and cov_min_neighbours are fixed once a keyframe holds covariances */
+int  slam_kf_set_gicp_params(slam_kf_t *s, const slam_kf_gicp_params *params);
+/* Per-point covariances of keyframe `id`; a second call does nothing.  A keyframe of fewer than k_correspondences points is
+ * refused (SLAM_E_INVALID).  slam_kf_register_gicp calls it for every keyframe it touches that has none. */
+int  slam_kf_compute_covariances(slam_kf_t *s, int id, slam_stream_t stream);
+/* six doubles per point of the filtered cloud: xx xy xz yy yz zz; SLAM_E_INVALID before compute_covariances */
+int  slam_kf_read_covariances(slam_kf_t *s, int id, double *cov6, int max_points, int *n_points);
+/* the lists the covariances were summed over: per point *k indices into the filtered cloud (-1 behind the last) and f32
+ * squared distances, ascending by (d^2, index), and the length of the list */
+int  slam_kf_read_neighbours(slam_kf_t *s, int id, int32_t *index, float *dist2, int32_t *count, int max_points, int *k);
+/* target = keyframe `from`, source = keyframe `to`, as slam_kf_register_edges; one workgroup per request, one launch, one
+ * wait.  pairs_trace as there. */
+int  slam_kf_register_gicp(slam_kf_t *s, const slam_kf_edge_req *req, int n, slam_kf_gicp_result *out, slam_stream_t stream);
+int  slam_kf_register_gicp_traced(slam_kf_t *s, const slam_kf_edge_req *req, int n, slam_kf_gicp_result *out,
+                                  int32_t *pairs_trace, int trace_cap, slam_stream_t stream);
+
 /* -------------------------------------------------------------------------
  * Correlative scan matcher (Olson, ICRA 2009), class-constrained like the rest of ccicp2d: the best of N_theta x N_y x N_x
  * poses around a start pose by a score looked up in a rasterised model, found exactly by a two-level branch and bound.  The

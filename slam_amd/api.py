@@ -5,6 +5,7 @@ pointers across that ABI.  There is no CPU path: if the library is missing or
 no HIP device is usable, calls raise SlamError.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -87,6 +88,17 @@ class KfEdgeResult(C.Structure):
                 ("reserved", C.c_int)]
 
 
+class KfGicpParams(C.Structure):
+    _fields_ = [("k_correspondences", C.c_int), ("cov_radius", C.c_double), ("gicp_epsilon", C.c_double),
+                ("max_iterations", C.c_int), ("transformation_epsilon", C.c_double), ("rotation_epsilon", C.c_double),
+                ("cov_min_neighbours", C.c_int)]
+
+
+class KfGicpResult(C.Structure):
+    _fields_ = [("edge", KfEdgeResult), ("cost", C.c_double), ("hessian", C.c_double * 36), ("fitness", C.c_double),
+                ("fitness_pairs", C.c_int), ("reserved", C.c_int)]
+
+
 class CsmParams(C.Structure):
     _fields_ = [("resolution", C.c_double), ("sigma", C.c_double), ("kernel_cells", C.c_int), ("block", C.c_int),
                 ("half_x", C.c_int), ("half_y", C.c_int), ("half_theta", C.c_int), ("theta_step", C.c_double),
@@ -101,6 +113,7 @@ class CsmResult(C.Structure):
 CSM_RESULT_DTYPE = np.dtype([(f, np.int32) for f, _ in CsmResult._fields_])
 
 KF_NOT_CONVERGED, KF_ITERATIONS, KF_TRANSFORM, KF_ABS_MSE, KF_REL_MSE, KF_NO_CORRESPONDENCES = 0, 1, 2, 3, 4, 5
+KF_DEGENERATE = 6   # Generalized ICP only: the step's 6 x 6 has a pivot that is not positive and finite
 KF_LATTICE_MARGIN = 1.0 + 2.0 ** -16   # the search lattice's edge is cell_size (or the gate) times this
 
 GSEG_DROPPED, GSEG_GROUND, GSEG_OBSTACLE, GSEG_OVERHEAD = 0, 1, 2, 3
@@ -149,6 +162,8 @@ EXPORTS = [
     "slam_kf_default_params", "slam_kf_create", "slam_kf_destroy", "slam_kf_set_params", "slam_kf_add_keyframe",
     "slam_kf_add_keyframe_dev", "slam_kf_keyframe_info", "slam_kf_count", "slam_kf_read_keyframe", "slam_kf_nearest_dev",
     "slam_kf_register_edges", "slam_kf_register_edges_traced",
+    "slam_kf_gicp_default_params", "slam_kf_set_gicp_params", "slam_kf_compute_covariances", "slam_kf_read_covariances",
+    "slam_kf_read_neighbours", "slam_kf_register_gicp", "slam_kf_register_gicp_traced",
     "slam_csm_default_params", "slam_csm_create", "slam_csm_create_dev", "slam_csm_destroy", "slam_csm_reserve",
     "slam_csm_set_window", "slam_csm_set_exhaustive", "slam_csm_angles", "slam_csm_match_batch_dev", "slam_csm_match",
     "slam_csm_score_volume_dev", "slam_csm_read_table", "slam_csm_info",
@@ -337,6 +352,14 @@ def lib():
     L.slam_kf_nearest_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]
     L.slam_kf_register_edges.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
     L.slam_kf_register_edges_traced.argtypes = [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]
+    L.slam_kf_gicp_default_params.argtypes = [C.POINTER(KfGicpParams)]
+    L.slam_kf_gicp_default_params.restype = None
+    L.slam_kf_set_gicp_params.argtypes = [_vp, C.POINTER(KfGicpParams)]
+    L.slam_kf_compute_covariances.argtypes = [_vp, C.c_int, _vp]
+    L.slam_kf_read_covariances.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_int)]
+    L.slam_kf_read_neighbours.argtypes = [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
+    L.slam_kf_register_gicp.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
+    L.slam_kf_register_gicp_traced.argtypes = [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]
     L.slam_csm_default_params.argtypes = [C.POINTER(CsmParams)]
     L.slam_csm_default_params.restype = None
     L.slam_csm_create.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(CsmParams), C.POINTER(_vp)]
@@ -997,6 +1020,14 @@ def kf_default_params(**kw):
     return p
 
 
+def kf_gicp_default_params(**kw):
+    p = KfGicpParams()
+    lib().slam_kf_gicp_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 class KeyframeStore:
     """graph_slam's keyframes on the device (slam_kf_*): each one voxel-filtered once and indexed by a 3-D lattice; edges
     (calcEdgeIcp: 3-D point-to-point ICP, then computeEdgeInformationLUM) registered in batches."""
@@ -1083,6 +1114,144 @@ class KeyframeStore:
             for e in range(n):
                 out[e]["pairs_trace"] = tr[e].copy()
         return out
+
+
+    # ---- Generalized ICP (docs/KF_GICP.md)
+    def set_gicp_params(self, params=None, **kw):
+        p = params or kf_gicp_default_params(**kw)
+        check(lib().slam_kf_set_gicp_params(self.h, C.byref(p)))
+        self.gicp_params = p
+
+    def compute_covariances(self, kid, stream=None):
+        """Per-point covariances of keyframe kid (a second call does nothing)."""
+        check(lib().slam_kf_compute_covariances(self.h, int(kid), _sp(stream)))
+
+    def covariances(self, kid):
+        """[n, 6] f64: xx xy xz yy yz zz per point of the filtered cloud."""
+        n = self.info(kid)["n_points"]
+        out = np.zeros((n, 6), np.float64)
+        got = C.c_int(0)
+        check(lib().slam_kf_read_covariances(self.h, int(kid), _ptr(out), n, C.byref(got)))
+        return out[:got.value]
+
+    def neighbours(self, kid):
+        """The lists the covariances were summed over: (index [n, k] i32, -1 behind the last; f32 d^2 [n, k]; count [n])."""
+        n = self.info(kid)["n_points"]
+        k = C.c_int(0)
+        check(lib().slam_kf_read_neighbours(self.h, int(kid), None, None, None, 0, C.byref(k)))
+        idx, d2 = np.zeros((n, k.value), np.int32), np.zeros((n, k.value), np.float32)
+        cnt = np.zeros(n, np.int32)
+        check(lib().slam_kf_read_neighbours(self.h, int(kid), _ptr(idx), _ptr(d2), _ptr(cnt), n, C.byref(k)))
+        return idx, d2, cnt
+
+    def register_gicp(self, edges, params=None, trace=0, stream=None):
+        """edges: [(from, to, init 4x4), ...] -> list of dicts: the fields of register_edges plus 'cost', 'hessian',
+        'fitness', 'fitness_pairs' ('pairs_trace' when trace > 0).  params: a KfGicpParams to set first."""
+        if params is not None:
+            self.set_gicp_params(params)
+        n = len(edges)
+        req = (KfEdgeReq * max(n, 1))()
+        for e, (f, t, init) in enumerate(edges):
+            req[e].from_, req[e].to = int(f), int(t)
+            req[e].init[:] = np.asarray(init, dtype=np.float32).reshape(16).tolist()
+        res = (KfGicpResult * max(n, 1))()
+        tr = np.full((max(n, 1), max(trace, 1)), -1, np.int32)
+        if trace > 0:
+            check(lib().slam_kf_register_gicp_traced(self.h, C.addressof(req), n, C.addressof(res), _ptr(tr), int(trace), _sp(stream)))
+        else:
+            check(lib().slam_kf_register_gicp(self.h, C.addressof(req), n, C.addressof(res), _sp(stream)))
+        out = [kf_gicp_result_dict(res[e]) for e in range(n)]
+        if trace > 0:
+            for e in range(n):
+                out[e]["pairs_trace"] = tr[e].copy()
+        return out
+
+
+class Lcg:
+    """x <- 1664525 x + 1013904223 mod 2^32; next() is the top 24 bits as a float32 in [0, 1): slam_amd::Lcg of
+    include/slam_amd/global_match.hpp, so that C++ and Python draw the same starts."""
+
+    def __init__(self, seed=1):
+        self.state = int(seed) & 0xffffffff
+
+    def next(self):
+        self.state = (self.state * 1664525 + 1013904223) & 0xffffffff
+        return np.float32(self.state >> 8) * np.float32(1.0 / 16777216.0)
+
+
+def global_match_starts(random, cur_x, cur_y, cur_yaw, iterations=20, dist_rng=10.0, angle_rng=2 * math.pi):
+    """[(dx, dy, dth)] as float32: start 0 is the current pose, the others are drawn around it (global_match.cpp:105-118)."""
+    out = [(np.float32(cur_x), np.float32(cur_y), np.float32(cur_yaw))]
+    for _ in range(1, iterations):
+        dx = np.float32(float(random()) * 2.0 * dist_rng - dist_rng + float(np.float32(cur_x)))
+        dy = np.float32(float(random()) * 2.0 * dist_rng - dist_rng + float(np.float32(cur_y)))
+        dth = np.float32(float(random()) * angle_rng)
+        out.append((dx, dy, dth))
+    return out
+
+
+class GlobalMatcher:
+    """global_matching's matcher (global_match.cpp:72-235) over KeyframeStore.register_gicp: the same behaviour as
+    slam_amd::GlobalMatcher of include/slam_amd/global_match.hpp, member for member (docs/KF_GICP.md section 4)."""
+
+    def __init__(self, leaf=1.5, gate=10.0, refine_leaf=0.25, refine_gate=1.0, seed=1, random=None):
+        self.MAX_SCORE, self.MAX_TRIES, self.ITERATIONS = 0.002, 50, 20
+        self.GUESS_DIST_RNG, self.GUESS_ANGLE_RNG, self.COV_YAW, self.COV_XY = 10.0, 2 * math.pi, 100.0, 1000.0
+        self.random = random or Lcg(seed).next
+        self.try_count = 0
+        self.coarse = KeyframeStore(leaf_size=leaf, gate=gate)
+        self.refine = KeyframeStore(leaf_size=refine_leaf, gate=refine_gate)
+        self.map_coarse = self.map_refine = -1
+        self.last, self.last_starts = [], []
+
+    def close(self):
+        self.coarse.close()
+        self.refine.close()
+
+    def set_map(self, xyz):
+        self.map_coarse, self.map_refine = self.coarse.add_keyframe(xyz), self.refine.add_keyframe(xyz)
+
+    @staticmethod
+    def planar(dx, dy, dth):
+        c, s = np.float32(math.cos(float(dth))), np.float32(math.sin(float(dth)))
+        return np.array([[c, -s, 0, dx], [s, c, 0, dy], [0, 0, 1, 0], [0, 0, 0, 1]], np.float32)
+
+    def starts(self, cur_x, cur_y, cur_yaw):
+        return global_match_starts(self.random, cur_x, cur_y, cur_yaw, self.ITERATIONS, self.GUESS_DIST_RNG, self.GUESS_ANGLE_RNG)
+
+    def _edge(self, id_, x, y, theta, **kw):
+        cov = np.zeros(9)
+        cov[0] = cov[4] = self.COV_XY
+        cov[8] = self.COV_YAW
+        return dict(kw, to=int(id_), x=float(x), y=float(y), theta=float(theta), covariance=cov, **{"from": 0})
+
+    def match(self, cloud, cur_x, cur_y, cur_yaw, id_=1):
+        """laser_callback: the edge (a dict; 'matched' False for the fallback edge of :204-221) or None."""
+        scan = self.coarse.add_keyframe(cloud)
+        n_scan = self.coarse.info(scan)["n_points"]
+        self.last_starts = self.starts(cur_x, cur_y, cur_yaw)
+        self.last = self.coarse.register_gicp([(self.map_coarse, scan, self.planar(*s)) for s in self.last_starts])
+        for i, r in enumerate(self.last):
+            norm_score = r["fitness"] / float(n_scan)
+            if not (r["converged"] and r["fitness_pairs"] > 0 and norm_score < self.MAX_SCORE):
+                continue
+            fine = self.refine.add_keyframe(cloud)
+            rr = self.refine.register_gicp([(self.map_refine, fine, r["transform"])])[0]
+            T = rr["transform"]
+            self.try_count = 0
+            return self._edge(id_, T[0, 3], T[1, 3], math.atan2(float(T[1, 0]), float(T[0, 0])), matched=True, start=i,
+                              norm_score=norm_score, coarse=r["transform"], refined=T, coarse_result=r, refine_result=rr)
+        self.try_count += 1
+        if self.try_count >= self.MAX_TRIES:
+            return self._edge(id_, np.float32(cur_x), np.float32(cur_y), np.float32(cur_yaw), matched=False, start=-1)
+        return None
+
+
+def kf_gicp_result_dict(r):
+    d = kf_result_dict(r.edge)
+    d.update(cost=r.cost, hessian=np.array(r.hessian[:], np.float64).reshape(6, 6), fitness=r.fitness,
+             fitness_pairs=r.fitness_pairs)
+    return d
 
 
 def kf_result_dict(r):

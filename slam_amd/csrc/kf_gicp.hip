@@ -1,0 +1,579 @@
+// kf_gicp.hip -- Generalized ICP on the keyframe store (docs/KF_GICP.md), the solver global_matching is built on
+// (global_match.cpp:52,225-235: pcl::GeneralizedIterativeClosestPoint):
+//   kf_cov_kernel    per point of a filtered cloud: the k nearest points within a radius, ordered by (f32 d^2, index), found
+//                    exactly in the store's lattice, and from them C' = V diag(1, 1, eps) V'.  One lane owns one point and
+//                    sums in list order, so the covariances are the restatement's bit for bit.
+//   kf_gicp_kernel   one workgroup per request: gated 1-NN pairs, M = (C'q + R C'p R')^-1 per pair, one Gauss-Newton step per
+//                    iteration by a 6 x 6 Cholesky on thread 0, PCL GICP's stop rule, then the fitness and the LUM block of
+//                    kf_edge.hip on the f32 transform.  Sums are f64, reduced by block_sum in a fixed order.
+#include "kf_common.hpp"
+
+namespace {
+
+constexpr int kCovThreads = 256;
+constexpr int kMaxK = 32;       // 256 lanes x 32 entries x 8 bytes = 64 KB of LDS
+constexpr int kMaxRings = 8;    // cov_radius is at most this many lattice edges
+constexpr int kJacobiSweeps = 8;
+
+struct CovParams {
+    double inv_cell, edge, radius2, eps;
+    int    k, rings, min_nbr;
+};
+
+struct GicpTask {
+    KfView        src, tgt;
+    const double *src_cov, *tgt_cov; // six doubles per point, by index in the filtered cloud
+    int32_t      *corr;              // src.n ints, the LUM pass's
+    float         init[16];
+};
+
+struct GicpParams {
+    double inv_cell, gate2, eps_t, eps_r;
+    int    max_iter;
+};
+
+// C' = V diag(1, 1, eps) V' of the symmetric C (xx xy xz yy yz zz): a cyclic Jacobi eigen-decomposition with a fixed number
+// of sweeps on scalars (nothing is indexed at run time), then, with n the eigenvector of the smallest eigenvalue (the last of
+// equal ones, as a stable descending sort leaves it), (I - n n') + eps n n', which is V diag(1, 1, eps) V' for an orthonormal V
+// and is exact when n is an axis.  The same text as tests/cpp/kf_gicp_oracle.cpp.
+__device__ inline void plane_covariance(const double C[6], double eps, double out[6])
+{
+    double a00 = C[0], a01 = C[1], a02 = C[2], a11 = C[3], a12 = C[4], a22 = C[5];
+    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+#define KF_JACOBI(app, aqq, apq, arp, arq, v0p, v0q, v1p, v1q, v2p, v2q)                                                                  \
+    if (apq != 0.0) {                                                                                                                     \
+        const double th = (aqq - app) / (2.0 * apq);                                                                                      \
+        const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));                                                     \
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;                                                                              \
+        app = app - t * apq, aqq = aqq + t * apq, apq = 0.0;                                                                              \
+        const double rp = arp, rq = arq, x0 = v0p, y0 = v0q, x1 = v1p, y1 = v1q, x2 = v2p, y2 = v2q;                                      \
+        arp = c * rp - s * rq, arq = s * rp + c * rq;                                                                                     \
+        v0p = c * x0 - s * y0, v0q = s * x0 + c * y0;                                                                                     \
+        v1p = c * x1 - s * y1, v1q = s * x1 + c * y1;                                                                                     \
+        v2p = c * x2 - s * y2, v2q = s * x2 + c * y2;                                                                                     \
+    }
+    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+        KF_JACOBI(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21)
+        KF_JACOBI(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22)
+        KF_JACOBI(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22)
+    }
+#undef KF_JACOBI
+    int    n = 0;
+    double mn = a00;
+    if (a11 <= mn) n = 1, mn = a11;
+    if (a22 <= mn) n = 2;
+    const double nx = n == 0 ? v00 : n == 1 ? v01 : v02, ny = n == 0 ? v10 : n == 1 ? v11 : v12, nz = n == 0 ? v20 : n == 1 ? v21 : v22;
+    const double xx = nx * nx, xy = nx * ny, xz = nx * nz, yy = ny * ny, yz = ny * nz, zz = nz * nz;
+    out[0] = (1.0 - xx) + eps * xx, out[1] = (0.0 - xy) + eps * xy, out[2] = (0.0 - xz) + eps * xz;
+    out[3] = (1.0 - yy) + eps * yy, out[4] = (0.0 - yz) + eps * yz, out[5] = (1.0 - zz) + eps * zz;
+}
+
+// ---------------------------------------------------------------- neighbour lists and covariances, one lane per point
+// A lane's list lives in LDS, entry e of lane l at [e][l], so that the lanes of a wave never share a bank.  An entry is
+// (bits of the f32 d^2) << 32 | index: d^2 is never negative, so the order of the entries as integers is the order by
+// (d^2, index).  Rings of cells around the point's own are visited outwards; the cells beyond ring r hold only points
+// farther than r edges, so the search ends once the list is full and its last entry is nearer than that (with
+// kPruneSlack against the roundings of the f32 sum), and it never goes past P.rings.  Nobody waits for anybody.
+__global__ __launch_bounds__(kCovThreads) void kf_cov_kernel(KfView v, CovParams P, double *cov6, int32_t *nbr_index, float *nbr_dist2,
+                                                             int32_t *nbr_count)
+{
+    extern __shared__ unsigned long long lds_list[]; // [P.k][kCovThreads]
+    const int s = blockIdx.x * kCovThreads + threadIdx.x;
+    if (s >= v.n) return;
+    unsigned long long *list = lds_list + threadIdx.x;
+    const float4        p = v.sorted[s];
+    const int           i = __float_as_int(p.w);
+    const int           c0 = cell_coord(p.x, P.inv_cell), c1 = cell_coord(p.y, P.inv_cell), c2 = cell_coord(p.z, P.inv_cell);
+    const int           K = P.k;
+    int                 m = 0;
+    for (int r = 0; r <= P.rings; ++r) {
+        for (int oz = -r; oz <= r; ++oz)
+            for (int oy = -r; oy <= r; ++oy)
+                for (int ox = -r; ox <= r; ++ox) {
+                    if (abs(ox) != r && abs(oy) != r && abs(oz) != r) continue; // inside the ring: seen already
+                    const int x = c0 + ox, y = c1 + oy, z = c2 + oz;
+                    if ((x | y | z) < 0 || x >= 2 * kHalf || y >= 2 * kHalf || z >= 2 * kHalf) continue;
+                    const unsigned long long key = cell_key(x, y, z);
+                    unsigned                 h = slot_of(key, v.mask);
+                    int                      start = 0, count = 0;
+                    for (;;) { // at most half the slots are taken: the probe ends
+                        const int4               e = v.table[h];
+                        const unsigned long long k = ((unsigned long long)(unsigned)e.y << 32) | (unsigned)e.x;
+                        if (k == key) {
+                            start = e.z, count = e.w;
+                            break;
+                        }
+                        if (k == kEmpty) break;
+                        h = (h + 1) & v.mask;
+                    }
+                    for (int j = start; j < start + count; ++j) {
+                        const float4 q = v.sorted[j];
+                        const float  dx = __fsub_rn(p.x, q.x), dy = __fsub_rn(p.y, q.y), dz = __fsub_rn(p.z, q.z);
+                        const float  d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+                        if (!((double)d <= P.radius2)) continue;
+                        const unsigned long long ent = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)__float_as_int(q.w);
+                        if (m == K && ent >= list[(K - 1) * kCovThreads]) continue;
+                        int at = m < K ? m : K - 1;
+                        while (at > 0) {
+                            const unsigned long long prev = list[(at - 1) * kCovThreads];
+                            if (prev <= ent) break;
+                            list[at * kCovThreads] = prev;
+                            --at;
+                        }
+                        list[at * kCovThreads] = ent;
+                        if (m < K) ++m;
+                    }
+                }
+        if (m == K) {
+            const double last = (double)__uint_as_float((unsigned)(list[(K - 1) * kCovThreads] >> 32)), reach = (double)r * P.edge;
+            if (last * kPruneSlack < reach * reach) break;
+        }
+    }
+    double C[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 1.0};
+    if (m >= P.min_nbr) {
+        double s1x = 0, s1y = 0, s1z = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0;
+        for (int e = 0; e < m; ++e) {
+            const float4 q = v.pts[(int)(unsigned)list[e * kCovThreads]];
+            const double dx = (double)q.x - (double)p.x, dy = (double)q.y - (double)p.y, dz = (double)q.z - (double)p.z;
+            s1x += dx, s1y += dy, s1z += dz;
+            sxx += dx * dx, sxy += dx * dy, sxz += dx * dz, syy += dy * dy, syz += dy * dz, szz += dz * dz;
+        }
+        const double dm = (double)m, mx = s1x / dm, my = s1y / dm, mz = s1z / dm;
+        const double raw[6] = {sxx / dm - mx * mx, sxy / dm - mx * my, sxz / dm - mx * mz, syy / dm - my * my, syz / dm - my * mz, szz / dm - mz * mz};
+        plane_covariance(raw, P.eps, C);
+    }
+#pragma unroll
+    for (int e = 0; e < 6; ++e) cov6[6 * (size_t)i + e] = C[e];
+    for (int e = 0; e < K; ++e) {
+        const unsigned long long ent = e < m ? list[e * kCovThreads] : 0ull;
+        nbr_index[(size_t)i * K + e] = e < m ? (int)(unsigned)ent : -1;
+        nbr_dist2[(size_t)i * K + e] = e < m ? __uint_as_float((unsigned)(ent >> 32)) : 0.0f;
+    }
+    nbr_count[i] = m;
+}
+
+// ---------------------------------------------------------------- one pair's share of the Gauss-Newton sums
+// x = R p + t in f64 from the original f32 point, r = q - x, M = (C'q + R C'p R')^-1 by the closed-form symmetric inverse,
+// J = [ [x]x , -I ]; h (the 21 entries of the upper triangle of J' M J, row by row), g = J' M r and r' M r are added to.
+// Every loop has constant bounds and is unrolled.  The same text as tests/cpp/kf_gicp_oracle.cpp.
+__device__ inline void gicp_pair(const double T[12], const float p[3], const float q[3], const double Cp[6], const double Cq[6], double h[21],
+                                 double g[6], double *cost)
+{
+    double x[3], r[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        x[k] = ((T[4 * k] * (double)p[0] + T[4 * k + 1] * (double)p[1]) + T[4 * k + 2] * (double)p[2]) + T[4 * k + 3];
+        r[k] = (double)q[k] - x[k];
+    }
+    const double cp[9] = {Cp[0], Cp[1], Cp[2], Cp[1], Cp[3], Cp[4], Cp[2], Cp[4], Cp[5]};
+    double       B[9], A[9];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) B[3 * a + b] = (T[4 * a] * cp[b] + T[4 * a + 1] * cp[3 + b]) + T[4 * a + 2] * cp[6 + b];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b) A[3 * a + b] = (B[3 * a] * T[4 * b] + B[3 * a + 1] * T[4 * b + 1]) + B[3 * a + 2] * T[4 * b + 2];
+    const double s00 = Cq[0] + A[0], s01 = Cq[1] + A[1], s02 = Cq[2] + A[2], s11 = Cq[3] + A[4], s12 = Cq[4] + A[5], s22 = Cq[5] + A[8];
+    const double c00 = s11 * s22 - s12 * s12, c01 = s02 * s12 - s01 * s22, c02 = s01 * s12 - s02 * s11;
+    const double c11 = s00 * s22 - s02 * s02, c12 = s01 * s02 - s00 * s12, c22 = s00 * s11 - s01 * s01;
+    const double det = (s00 * c00 + s01 * c01) + s02 * c02;
+    const double M[9] = {c00 / det, c01 / det, c02 / det, c01 / det, c11 / det, c12 / det, c02 / det, c12 / det, c22 / det};
+    const double J[18] = {0.0, -x[2], x[1], -1.0, 0.0, 0.0, x[2], 0.0, -x[0], 0.0, -1.0, 0.0, -x[1], x[0], 0.0, 0.0, 0.0, -1.0};
+    double       Mr[3], MJ[18];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        Mr[a] = (M[3 * a] * r[0] + M[3 * a + 1] * r[1]) + M[3 * a + 2] * r[2];
+#pragma unroll
+        for (int b = 0; b < 6; ++b) MJ[6 * a + b] = (M[3 * a] * J[b] + M[3 * a + 1] * J[6 + b]) + M[3 * a + 2] * J[12 + b];
+    }
+    int at = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        g[a] += (J[a] * Mr[0] + J[6 + a] * Mr[1]) + J[12 + a] * Mr[2];
+#pragma unroll
+        for (int b = a; b < 6; ++b, ++at) h[at] += (J[a] * MJ[b] + J[6 + a] * MJ[6 + b]) + J[12 + a] * MJ[12 + b];
+    }
+    *cost += (r[0] * Mr[0] + r[1] * Mr[1]) + r[2] * Mr[2];
+}
+
+// The step of one iteration from the full sums: H xi = -g by an unrolled Cholesky, Exp(omega) by Rodrigues (below
+// theta^2 = 1e-16 the series 1 - theta^2/6 and 1/2 - theta^2/24), N = step . T.  False when a pivot is not positive and
+// finite; N is then not to be used.  The same text as tests/cpp/kf_gicp_oracle.cpp.
+__device__ inline bool gicp_step(const double H[36], const double g[6], const double T[12], double N[12])
+{
+    double L[36], y[6], xi[6];
+    bool   ok = true;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        double d = H[6 * k + k];
+#pragma unroll
+        for (int j = 0; j < k; ++j) d -= L[6 * k + j] * L[6 * k + j];
+        if (!(d > 0.0) || !(d <= DBL_MAX)) ok = false;
+        L[6 * k + k] = sqrt(d);
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i) {
+            double s = H[6 * i + k];
+#pragma unroll
+            for (int j = 0; j < k; ++j) s -= L[6 * i + j] * L[6 * k + j];
+            L[6 * i + k] = s / L[6 * k + k];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double s = -g[i];
+#pragma unroll
+        for (int j = 0; j < i; ++j) s -= L[6 * i + j] * y[j];
+        y[i] = s / L[6 * i + i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double s = y[i];
+#pragma unroll
+        for (int j = i + 1; j < 6; ++j) s -= L[6 * j + i] * xi[j];
+        xi[i] = s / L[6 * i + i];
+    }
+    const double wx = xi[0], wy = xi[1], wz = xi[2];
+    const double th2 = (wx * wx + wy * wy) + wz * wz;
+    double       a, b;
+    if (th2 < 1e-16) {
+        a = 1.0 - th2 / 6.0, b = 0.5 - th2 / 24.0;
+    } else {
+        const double th = sqrt(th2);
+        a = sin(th) / th, b = (1.0 - cos(th)) / th2;
+    }
+    // I + a [w]x + b [w]x^2, [w]x^2 = w w' - theta^2 I
+    const double Rs[9] = {1.0 + b * (wx * wx - th2), b * (wx * wy) - a * wz,     b * (wx * wz) + a * wy,
+                          b * (wx * wy) + a * wz,     1.0 + b * (wy * wy - th2), b * (wy * wz) - a * wx,
+                          b * (wx * wz) - a * wy,     b * (wy * wz) + a * wx,     1.0 + b * (wz * wz - th2)};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) N[4 * r + c] = (Rs[3 * r] * T[c] + Rs[3 * r + 1] * T[4 + c]) + Rs[3 * r + 2] * T[8 + c];
+        N[4 * r + 3] = ((Rs[3 * r] * T[3] + Rs[3 * r + 1] * T[7]) + Rs[3 * r + 2] * T[11]) + xi[3 + r];
+    }
+    return ok;
+}
+
+// ---------------------------------------------------------------- one workgroup per request
+__global__ __launch_bounds__(kEdgeThreads) void kf_gicp_kernel(const GicpTask *tasks, GicpParams P, slam_kf_gicp_result *results, int32_t *trace,
+                                                               int trace_cap, int lds_points)
+{
+    extern __shared__ float4 lds_sorted[]; // room for lds_points of the target's sorted points
+    __shared__ double sT[12];
+    __shared__ float  sTf[12];
+    __shared__ double sD[6];
+    __shared__ double red[kWaves][16];
+    __shared__ double tot[16];
+    __shared__ float  redf[kWaves][16];
+    __shared__ float  totf[16];
+    __shared__ int    sState;
+    __shared__ double sMM[36];
+    __shared__ double sH[36]; // thread 0's: the last iteration's J' M J
+
+    const GicpTask      &task = tasks[blockIdx.x];
+    const KfView         src = task.src;
+    KfView               tgt = task.tgt;
+    const double        *src_cov = task.src_cov, *tgt_cov = task.tgt_cov;
+    int32_t             *corr = task.corr;
+    slam_kf_gicp_result *out = results + blockIdx.x;
+    const int            tid = threadIdx.x;
+
+    if (tgt.n <= lds_points) { // as kf_edge_kernel: the target's points in LDS when they fit, the table and the covariances through L2
+        for (int i = tid; i < tgt.n; i += kEdgeThreads) lds_sorted[i] = tgt.sorted[i];
+        tgt.sorted = lds_sorted;
+    }
+    if (tid < 12) sT[tid] = (double)task.init[tid];
+    if (tid < 36) sH[tid] = 0.0;
+    if (tid == 0) sState = 0;
+    if (trace)
+        for (int i = tid; i < trace_cap; i += kEdgeThreads) trace[(size_t)blockIdx.x * trace_cap + i] = -1;
+    int    iterations = 0, pairs = 0; // thread 0's are the ones that count
+    double mse = 0.0, cost = 0.0;
+    for (;;) {
+        __syncthreads();
+        double T[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) T[k] = sT[k];
+        double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // pairs, d^2, cost, g
+        double h16[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, h5[5] = {0, 0, 0, 0, 0};
+        for (int i = tid; i < src.n; i += kEdgeThreads) {
+            const float4 p = src.pts[i];
+            float        m[3], d2;
+            int          slot;
+            move_f64(T, p, m);
+            const int j = nearest27(tgt, P.inv_cell, P.gate2, m[0], m[1], m[2], &d2, &slot);
+            if (!(j >= 0 && (double)d2 < P.gate2)) continue; // strict: GICP drops a pair at the gate
+            const float4 q = tgt.sorted[slot];
+            const float  pf[3] = {p.x, p.y, p.z}, qf[3] = {q.x, q.y, q.z};
+            double       Cp[6], Cq[6], h[21] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, g[6] = {0, 0, 0, 0, 0, 0}, c = 0.0;
+#pragma unroll
+            for (int e = 0; e < 6; ++e) Cp[e] = src_cov[6 * (size_t)i + e], Cq[e] = tgt_cov[6 * (size_t)j + e];
+            gicp_pair(T, pf, qf, Cp, Cq, h, g, &c);
+            acc[0] += 1.0, acc[1] += (double)d2, acc[2] += c;
+#pragma unroll
+            for (int e = 0; e < 6; ++e) acc[3 + e] += g[e];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) h16[e] += h[e];
+#pragma unroll
+            for (int e = 0; e < 5; ++e) h5[e] += h[16 + e];
+        }
+        block_sum<double, 9>(acc, red, tot);
+        const double n = tot[0];
+        pairs = (int)n;
+        mse = pairs ? tot[1] / n : 0.0;
+        cost = pairs ? tot[2] / n : 0.0;
+        double g[6], hu[21];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) g[e] = tot[3 + e];
+        block_sum<double, 16>(h16, red, tot);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) hu[e] = tot[e];
+        block_sum<double, 5>(h5, red, tot);
+#pragma unroll
+        for (int e = 0; e < 5; ++e) hu[16 + e] = tot[e];
+        if (tid == 0) {
+            if (trace && iterations < trace_cap) trace[(size_t)blockIdx.x * trace_cap + iterations] = pairs;
+            double H[36];
+            int    at = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = a; b < 6; ++b, ++at) H[6 * a + b] = H[6 * b + a] = hu[at];
+#pragma unroll
+            for (int k = 0; k < 36; ++k) sH[k] = H[k];
+            int state = 0;
+            if (pairs < 3)
+                state = SLAM_KF_NO_CORRESPONDENCES;
+            else {
+                double N[12];
+                if (!gicp_step(H, g, T, N))
+                    state = SLAM_KF_DEGENERATE;
+                else {
+#pragma unroll
+                    for (int k = 0; k < 12; ++k) sT[k] = N[k];
+                    ++iterations;
+                    if (iterations >= P.max_iter)
+                        state = SLAM_KF_ITERATIONS;
+                    else { // PCL GICP's rule: no entry of the rotation moved by more than eps_r, none of the translation by more than eps_t
+                        double dr = 0.0, dt = 0.0;
+#pragma unroll
+                        for (int k = 0; k < 12; ++k) {
+                            const double d = fabs(N[k] - T[k]);
+                            if (k % 4 == 3)
+                                dt = d > dt ? d : dt;
+                            else
+                                dr = d > dr ? d : dr;
+                        }
+                        if (dr <= P.eps_r && dt <= P.eps_t) state = SLAM_KF_TRANSFORM;
+                    }
+                }
+            }
+            sState = state;
+        }
+        __syncthreads();
+        if (sState) break;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        slam_kf_edge_result *e = &out->edge;
+        for (int k = 0; k < 12; ++k) {
+            e->transform64[k] = sT[k];
+            e->transform[k] = sTf[k] = (float)sT[k];
+        }
+        for (int k = 12; k < 16; ++k) e->transform64[k] = k == 15 ? 1.0 : 0.0, e->transform[k] = k == 15 ? 1.0f : 0.0f;
+        e->iterations = iterations, e->state = sState;
+        e->converged = sState == SLAM_KF_ITERATIONS || sState == SLAM_KF_TRANSFORM;
+        e->pairs = pairs, e->mse = mse, e->reserved = 0;
+        out->cost = cost;
+        for (int k = 0; k < 36; ++k) out->hessian[k] = sH[k];
+    }
+    __syncthreads();
+
+    lum_pass(src, tgt, corr, P.inv_cell, P.gate2, sTf, red, tot, redf, totf, sD, sMM, &out->edge);
+
+    // the fitness, over the pairs the LUM pass has just kept: the same points moved the same way, strictly inside the gate
+    float M[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) M[k] = sTf[k];
+    double f[2] = {0, 0};
+    for (int i = tid; i < src.n; i += kEdgeThreads) {
+        const int slot = corr[i];
+        if (slot < 0) continue;
+        float s[3];
+        move_f32(M, src.pts[i], s);
+        const float4 q = tgt.sorted[slot];
+        const float  dx = __fsub_rn(s[0], q.x), dy = __fsub_rn(s[1], q.y), dz = __fsub_rn(s[2], q.z);
+        f[0] += 1.0;
+        f[1] += (double)__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+    }
+    block_sum<double, 2>(f, red, tot);
+    if (tid == 0) {
+        out->fitness_pairs = (int)tot[0], out->reserved = 0;
+        out->fitness = tot[0] > 0.0 ? tot[1] / tot[0] : 0.0;
+    }
+}
+
+int check_gicp_params(const slam_kf_gicp_params *p)
+{
+    SLAM_REQUIRE(p->k_correspondences >= 1 && p->k_correspondences <= kMaxK && p->cov_radius >= 0 && p->gicp_epsilon > 0 &&
+                     p->max_iterations >= 1 && p->cov_min_neighbours >= 1,
+                 SLAM_E_INVALID,
+                 "slam_kf: k_correspondences must be 1 .. %d, cov_radius >= 0, gicp_epsilon > 0, max_iterations and cov_min_neighbours >= 1", kMaxK);
+    return SLAM_OK;
+}
+
+double lattice_edge(const slam_kf_params &p) { return 1.0 / inv_cell(p); }
+double cov_radius(const slam_kf *s) { return s->gp.cov_radius > 0 ? s->gp.cov_radius : 2.0 * lattice_edge(s->p); }
+
+} // namespace
+
+extern "C" {
+
+void slam_kf_gicp_default_params(slam_kf_gicp_params *p)
+{
+    if (!p) return;
+    p->k_correspondences = 20; // PCL's
+    p->cov_radius = 0.0;
+    p->gicp_epsilon = 1e-3;    // PCL's
+    p->max_iterations = 10;    // global_match.cpp:229
+    p->transformation_epsilon = 1e-6;
+    p->rotation_epsilon = 2e-3; // PCL's
+    p->cov_min_neighbours = 4;
+}
+
+int slam_kf_set_gicp_params(slam_kf_t *s, const slam_kf_gicp_params *params)
+{
+    SLAM_REQUIRE(s && params, SLAM_E_INVALID, "slam_kf_set_gicp_params: null argument");
+    SLAM_TRY(check_gicp_params(params));
+    SLAM_REQUIRE(s->n_cov == 0 || (params->k_correspondences == s->gp.k_correspondences && params->cov_radius == s->gp.cov_radius &&
+                                   params->gicp_epsilon == s->gp.gicp_epsilon && params->cov_min_neighbours == s->gp.cov_min_neighbours),
+                 SLAM_E_INVALID,
+                 "slam_kf_set_gicp_params: k_correspondences, cov_radius, gicp_epsilon and cov_min_neighbours are fixed once a keyframe holds covariances");
+    s->gp = *params;
+    return SLAM_OK;
+}
+
+int slam_kf_compute_covariances(slam_kf_t *s, int id, slam_stream_t stream)
+{
+    SLAM_REQUIRE(s && id >= 0 && id < (int)s->kfs.size(), SLAM_E_INVALID, "slam_kf_compute_covariances: no keyframe %d", id);
+    Keyframe &kf = s->kfs[id];
+    if (kf.cov6) return SLAM_OK;
+    const int    n = kf.view.n, K = s->gp.k_correspondences;
+    const double edge = lattice_edge(s->p), radius = cov_radius(s);
+    SLAM_REQUIRE(n >= K, SLAM_E_INVALID, "slam_kf_compute_covariances: keyframe %d has %d points, fewer than k_correspondences = %d", id, n, K);
+    SLAM_REQUIRE(radius <= kMaxRings * edge, SLAM_E_INVALID, "slam_kf_compute_covariances: cov_radius %g is more than %d lattice edges of %g", radius,
+                 kMaxRings, edge);
+    CovParams P;
+    P.inv_cell = inv_cell(s->p), P.edge = edge, P.radius2 = radius * radius, P.eps = s->gp.gicp_epsilon;
+    P.k = K, P.rings = (int)ceil(radius / edge), P.min_nbr = s->gp.cov_min_neighbours;
+    DevMem       mem;
+    const size_t cov_b = sizeof(double) * 6 * (size_t)n, list_b = sizeof(int32_t) * (size_t)K * n;
+    SLAM_TRY(mem.alloc(cov_b + 2 * list_b + sizeof(int32_t) * (size_t)n));
+    double  *cov6 = mem.as<double>();
+    int32_t *index = reinterpret_cast<int32_t *>(static_cast<char *>(mem.p) + cov_b);
+    float   *dist2 = reinterpret_cast<float *>(index + (size_t)K * n);
+    int32_t *count = reinterpret_cast<int32_t *>(dist2 + (size_t)K * n);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(kf_cov_kernel, dim3(blocks(n, kCovThreads)), dim3(kCovThreads), sizeof(unsigned long long) * kCovThreads * (size_t)K, st, kf.view, P,
+                       cov6, index, dist2, count);
+    SLAM_HIP(hipGetLastError());
+    SLAM_HIP(hipStreamSynchronize(st));
+    kf.cov = std::move(mem);
+    kf.cov6 = cov6, kf.nbr_index = index, kf.nbr_dist2 = dist2, kf.nbr_count = count, kf.nbr_k = K;
+    ++s->n_cov;
+    return SLAM_OK;
+}
+
+int slam_kf_read_covariances(slam_kf_t *s, int id, double *cov6, int max_points, int *n_points)
+{
+    SLAM_REQUIRE(s && n_points && id >= 0 && id < (int)s->kfs.size() && max_points >= 0 && (cov6 || max_points == 0), SLAM_E_INVALID,
+                 "slam_kf_read_covariances: bad arguments");
+    const Keyframe &k = s->kfs[id];
+    SLAM_REQUIRE(k.cov6, SLAM_E_INVALID, "slam_kf_read_covariances: keyframe %d has no covariances yet", id);
+    *n_points = k.view.n < max_points ? k.view.n : max_points;
+    if (*n_points) SLAM_HIP(hipMemcpy(cov6, k.cov6, sizeof(double) * 6 * (size_t)*n_points, hipMemcpyDeviceToHost));
+    return SLAM_OK;
+}
+
+int slam_kf_read_neighbours(slam_kf_t *s, int id, int32_t *index, float *dist2, int32_t *count, int max_points, int *k)
+{
+    SLAM_REQUIRE(s && k && id >= 0 && id < (int)s->kfs.size() && max_points >= 0, SLAM_E_INVALID, "slam_kf_read_neighbours: bad arguments");
+    const Keyframe &kf = s->kfs[id];
+    SLAM_REQUIRE(kf.cov6, SLAM_E_INVALID, "slam_kf_read_neighbours: keyframe %d has no covariances yet", id);
+    *k = kf.nbr_k;
+    const size_t n = (size_t)(kf.view.n < max_points ? kf.view.n : max_points);
+    if (!n) return SLAM_OK;
+    if (index) SLAM_HIP(hipMemcpy(index, kf.nbr_index, sizeof(int32_t) * n * kf.nbr_k, hipMemcpyDeviceToHost));
+    if (dist2) SLAM_HIP(hipMemcpy(dist2, kf.nbr_dist2, sizeof(float) * n * kf.nbr_k, hipMemcpyDeviceToHost));
+    if (count) SLAM_HIP(hipMemcpy(count, kf.nbr_count, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    return SLAM_OK;
+}
+
+int slam_kf_register_gicp_traced(slam_kf_t *s, const slam_kf_edge_req *req, int n_req, slam_kf_gicp_result *out, int32_t *pairs_trace, int trace_cap,
+                                 slam_stream_t stream)
+{
+    SLAM_REQUIRE(s && n_req >= 0 && (n_req == 0 || (req && out)) && (!pairs_trace || trace_cap > 0), SLAM_E_INVALID,
+                 "slam_kf_register_gicp: bad arguments");
+    const int nk = (int)s->kfs.size();
+    size_t    n_corr = 0;
+    for (int e = 0; e < n_req; ++e) {
+        SLAM_REQUIRE(req[e].from >= 0 && req[e].from < nk && req[e].to >= 0 && req[e].to < nk, SLAM_E_INVALID,
+                     "slam_kf_register_gicp: request %d names keyframes %d -> %d, the store holds %d", e, req[e].from, req[e].to, nk);
+        n_corr += (size_t)s->kfs[req[e].to].view.n;
+    }
+    if (n_req == 0) return SLAM_OK;
+    for (int e = 0; e < n_req; ++e) {
+        SLAM_TRY(slam_kf_compute_covariances(s, req[e].from, stream));
+        SLAM_TRY(slam_kf_compute_covariances(s, req[e].to, stream));
+    }
+    if (!pairs_trace) trace_cap = 0;
+    hipStream_t  st = as_stream(stream);
+    const size_t task_b = sizeof(GicpTask) * (size_t)n_req, res_b = sizeof(slam_kf_gicp_result) * (size_t)n_req;
+    const size_t trace_b = sizeof(int32_t) * (size_t)n_req * trace_cap, corr_b = sizeof(int32_t) * n_corr;
+    const size_t res_off = (task_b + 255) & ~(size_t)255, trace_off = res_off + ((res_b + 255) & ~(size_t)255);
+    const size_t corr_off = trace_off + ((trace_b + 255) & ~(size_t)255);
+    SLAM_TRY(reserve_quarter(s->work, corr_off + corr_b));
+    char *host = static_cast<char *>(pinned_scratch(corr_off));
+    SLAM_REQUIRE(host, SLAM_E_NOMEM, "slam_kf_register_gicp: no pinned staging memory");
+    char     *dev = static_cast<char *>(s->work.p);
+    GicpTask *tasks = reinterpret_cast<GicpTask *>(host);
+    int32_t  *corr = reinterpret_cast<int32_t *>(dev + corr_off);
+    for (int e = 0; e < n_req; ++e) {
+        const Keyframe &src = s->kfs[req[e].to], &tgt = s->kfs[req[e].from];
+        tasks[e].src = src.view, tasks[e].tgt = tgt.view;
+        tasks[e].src_cov = src.cov6, tasks[e].tgt_cov = tgt.cov6;
+        tasks[e].corr = corr;
+        corr += src.view.n;
+        std::memcpy(tasks[e].init, req[e].init, sizeof tasks[e].init);
+    }
+    GicpParams P;
+    P.inv_cell = inv_cell(s->p), P.gate2 = s->p.gate * s->p.gate;
+    P.eps_t = s->gp.transformation_epsilon, P.eps_r = s->gp.rotation_epsilon, P.max_iter = s->gp.max_iterations;
+    int lds_points = 0;
+    if (s->p.target_in_lds)
+        for (int e = 0; e < n_req; ++e)
+            if (tasks[e].tgt.n <= kLdsPoints && tasks[e].tgt.n > lds_points) lds_points = tasks[e].tgt.n;
+    if (lds_points && !s->gicp_lds_enabled) {
+        SLAM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kf_gicp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)(sizeof(float4) * kLdsPoints)));
+        s->gicp_lds_enabled = true;
+    }
+    SLAM_HIP(hipMemcpyAsync(dev, host, task_b, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(kf_gicp_kernel, dim3(n_req), dim3(kEdgeThreads), sizeof(float4) * (size_t)lds_points, st, reinterpret_cast<const GicpTask *>(dev), P,
+                       reinterpret_cast<slam_kf_gicp_result *>(dev + res_off), trace_cap ? reinterpret_cast<int32_t *>(dev + trace_off) : nullptr,
+                       trace_cap, lds_points);
+    SLAM_HIP(hipGetLastError());
+    SLAM_HIP(hipMemcpyAsync(host + res_off, dev + res_off, (trace_off - res_off) + trace_b, hipMemcpyDeviceToHost, st));
+    SLAM_HIP(hipStreamSynchronize(st));
+    std::memcpy(out, host + res_off, res_b);
+    if (trace_cap) std::memcpy(pairs_trace, host + trace_off, trace_b);
+    return SLAM_OK;
+}
+
+int slam_kf_register_gicp(slam_kf_t *s, const slam_kf_edge_req *req, int n, slam_kf_gicp_result *out, slam_stream_t stream)
+{
+    return slam_kf_register_gicp_traced(s, req, n, out, nullptr, 0, stream);
+}
+}
