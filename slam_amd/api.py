@@ -1096,25 +1096,29 @@ class KeyframeStore:
         synchronize()
         return d_i.download(), d_d.download()
 
-    def register_edges(self, edges, trace=0, stream=None):
-        """edges: [(from, to, init 4x4), ...] -> list of dicts (one per edge; 'pairs_trace' when trace > 0)."""
+    def _register(self, plain, traced, result_type, to_dict, edges, trace, stream):
+        """One batch through a solver's plain and traced entry points: a dict per request by to_dict."""
         n = len(edges)
         req = (KfEdgeReq * max(n, 1))()
         for e, (f, t, init) in enumerate(edges):
             req[e].from_, req[e].to = int(f), int(t)
             req[e].init[:] = np.asarray(init, dtype=np.float32).reshape(16).tolist()
-        res = (KfEdgeResult * max(n, 1))()
+        res = (result_type * max(n, 1))()
         tr = np.full((max(n, 1), max(trace, 1)), -1, np.int32)
         if trace > 0:
-            check(lib().slam_kf_register_edges_traced(self.h, C.addressof(req), n, C.addressof(res), _ptr(tr), int(trace), _sp(stream)))
+            check(traced(self.h, C.addressof(req), n, C.addressof(res), _ptr(tr), int(trace), _sp(stream)))
         else:
-            check(lib().slam_kf_register_edges(self.h, C.addressof(req), n, C.addressof(res), _sp(stream)))
-        out = [kf_result_dict(res[e]) for e in range(n)]
+            check(plain(self.h, C.addressof(req), n, C.addressof(res), _sp(stream)))
+        out = [to_dict(res[e]) for e in range(n)]
         if trace > 0:
             for e in range(n):
                 out[e]["pairs_trace"] = tr[e].copy()
         return out
 
+    def register_edges(self, edges, trace=0, stream=None):
+        """edges: [(from, to, init 4x4), ...] -> list of dicts (one per edge; 'pairs_trace' when trace > 0)."""
+        L = lib()
+        return self._register(L.slam_kf_register_edges, L.slam_kf_register_edges_traced, KfEdgeResult, kf_result_dict, edges, trace, stream)
 
     # ---- Generalized ICP (docs/KF_GICP.md)
     def set_gicp_params(self, params=None, **kw):
@@ -1149,22 +1153,8 @@ class KeyframeStore:
         'fitness', 'fitness_pairs' ('pairs_trace' when trace > 0).  params: a KfGicpParams to set first."""
         if params is not None:
             self.set_gicp_params(params)
-        n = len(edges)
-        req = (KfEdgeReq * max(n, 1))()
-        for e, (f, t, init) in enumerate(edges):
-            req[e].from_, req[e].to = int(f), int(t)
-            req[e].init[:] = np.asarray(init, dtype=np.float32).reshape(16).tolist()
-        res = (KfGicpResult * max(n, 1))()
-        tr = np.full((max(n, 1), max(trace, 1)), -1, np.int32)
-        if trace > 0:
-            check(lib().slam_kf_register_gicp_traced(self.h, C.addressof(req), n, C.addressof(res), _ptr(tr), int(trace), _sp(stream)))
-        else:
-            check(lib().slam_kf_register_gicp(self.h, C.addressof(req), n, C.addressof(res), _sp(stream)))
-        out = [kf_gicp_result_dict(res[e]) for e in range(n)]
-        if trace > 0:
-            for e in range(n):
-                out[e]["pairs_trace"] = tr[e].copy()
-        return out
+        L = lib()
+        return self._register(L.slam_kf_register_gicp, L.slam_kf_register_gicp_traced, KfGicpResult, kf_gicp_result_dict, edges, trace, stream)
 
 
 class Lcg:

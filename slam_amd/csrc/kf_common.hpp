@@ -1,8 +1,9 @@
-// kf_common.hpp -- what the keyframe store's kernels share (kf_edge.hip: point-to-point ICP; kf_gicp.hip: covariances and
-// Generalized ICP): the lattice view and its gated search, the fixed-order block reduction, the register-resident 3 x 3
-// SVD and 6 x 6 inverse, the two ways a point is moved, computeEdgeInformationLUM's pass, and the store itself.
-// Device code sits in an unnamed namespace on purpose: every translation unit compiles its own copy with internal linkage,
-// exactly as when it lived in kf_edge.hip, so that kf_edge_kernel's code did not change with the move (docs/KF_GICP.md).
+// kf_common.hpp -- what the keyframe store's two solvers share (kf_edge.hip: point-to-point ICP; kf_gicp.hip: covariances
+// and Generalized ICP): the lattice view and its gated search, the fixed-order block reduction, the register-resident 3 x 3
+// SVD and 6 x 6 inverse, the two ways a point is moved, computeEdgeInformationLUM's pass, the store itself, and the one
+// host path of a batch of registrations (kf_register_batch, at the end).
+// Device code sits in an unnamed namespace on purpose: every translation unit compiles its own copy with internal linkage.
+// Putting the host path here left the device code of all kernels of both files as it was (docs/KF_GICP.md section 2).
 #pragma once
 #include <cfloat>
 #include <cmath>
@@ -411,5 +412,65 @@ namespace {
 
 inline double   inv_cell(const slam_kf_params &p) { return 1.0 / ((p.cell_size > 0 ? p.cell_size : p.gate) * kLatticeMargin); }
 inline unsigned blocks(size_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+// ---------------------------------------------------------------- one batch of registrations, from the requests to the results
+// The host path of both solvers: `who` is the entry point's name and `what` its word for a request (both for the error
+// texts), `kernel` runs one workgroup per request, `lds_enabled` is that kernel's flag in the store (its dynamic LDS limit
+// is raised at most once per store), `fill(task, request)` adds what the task holds beyond the views, `corr` and `init` (which every task type has under these names) and may refuse.  It runs
+// after the work buffer and the pinned staging are laid out: it may launch work on the stream and wait for it (Generalized
+// ICP computes missing covariances there), but must not touch s->work or call pinned_scratch.
+// s->work holds tasks | results | trace | corr, each from a multiple of 256 bytes; all but corr are mirrored in pinned
+// memory.  One upload, one launch, one download, one wait.
+template <typename Task, typename Result, typename Params, typename Fill>
+int kf_register_batch(slam_kf *s, const char *who, const char *what, void (*kernel)(const Task *, Params, Result *, int32_t *, int, int),
+                      bool &lds_enabled, const Params &P, Fill fill, const slam_kf_edge_req *req, int n, Result *out, int32_t *pairs_trace,
+                      int trace_cap, slam_stream_t stream)
+{
+    const int nk = (int)s->kfs.size();
+    size_t    n_corr = 0;
+    for (int e = 0; e < n; ++e) {
+        SLAM_REQUIRE(req[e].from >= 0 && req[e].from < nk && req[e].to >= 0 && req[e].to < nk, SLAM_E_INVALID,
+                     "%s: %s %d names keyframes %d -> %d, the store holds %d", who, what, e, req[e].from, req[e].to, nk);
+        n_corr += (size_t)s->kfs[req[e].to].view.n;
+    }
+    if (n == 0) return SLAM_OK;
+    if (!pairs_trace) trace_cap = 0;
+    hipStream_t  st = as_stream(stream);
+    const size_t task_b = sizeof(Task) * (size_t)n, res_b = sizeof(Result) * (size_t)n;
+    const size_t trace_b = sizeof(int32_t) * (size_t)n * trace_cap, corr_b = sizeof(int32_t) * n_corr;
+    const size_t res_off = (task_b + 255) & ~(size_t)255, trace_off = res_off + ((res_b + 255) & ~(size_t)255);
+    const size_t corr_off = trace_off + ((trace_b + 255) & ~(size_t)255);
+    SLAM_TRY(reserve_quarter(s->work, corr_off + corr_b));
+    char *host = static_cast<char *>(pinned_scratch(corr_off));
+    SLAM_REQUIRE(host, SLAM_E_NOMEM, "%s: no pinned staging memory", who);
+    char    *dev = static_cast<char *>(s->work.p);
+    Task    *tasks = reinterpret_cast<Task *>(host);
+    int32_t *corr = reinterpret_cast<int32_t *>(dev + corr_off);
+    int      lds_points = 0;
+    for (int e = 0; e < n; ++e) {
+        const Keyframe &src = s->kfs[req[e].to], &tgt = s->kfs[req[e].from];
+        tasks[e].src = src.view, tasks[e].tgt = tgt.view;
+        tasks[e].corr = corr;
+        corr += src.view.n;
+        std::memcpy(tasks[e].init, req[e].init, sizeof tasks[e].init);
+        SLAM_TRY(fill(tasks[e], req[e]));
+        if (s->p.target_in_lds && tgt.view.n <= kLdsPoints && tgt.view.n > lds_points) lds_points = tgt.view.n;
+    }
+    if (lds_points && !lds_enabled) {
+        SLAM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)(sizeof(float4) * kLdsPoints)));
+        lds_enabled = true;
+    }
+    SLAM_HIP(hipMemcpyAsync(dev, host, task_b, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(kernel, dim3(n), dim3(kEdgeThreads), sizeof(float4) * (size_t)lds_points, st, reinterpret_cast<const Task *>(dev), P,
+                       reinterpret_cast<Result *>(dev + res_off), trace_cap ? reinterpret_cast<int32_t *>(dev + trace_off) : nullptr, trace_cap,
+                       lds_points);
+    SLAM_HIP(hipGetLastError());
+    SLAM_HIP(hipMemcpyAsync(host + res_off, dev + res_off, (trace_off - res_off) + trace_b, hipMemcpyDeviceToHost, st));
+    SLAM_HIP(hipStreamSynchronize(st));
+    std::memcpy(out, host + res_off, res_b);
+    if (trace_cap) std::memcpy(pairs_trace, host + trace_off, trace_b);
+    return SLAM_OK;
+}
 
 } // namespace

@@ -386,55 +386,11 @@ int slam_kf_register_edges_traced(slam_kf_t *s, const slam_kf_edge_req *req, int
 {
     SLAM_REQUIRE(s && n_edges >= 0 && (n_edges == 0 || (req && out)) && (!pairs_trace || trace_cap > 0), SLAM_E_INVALID,
                  "slam_kf_register_edges: bad arguments");
-    const int nk = (int)s->kfs.size();
-    size_t    n_corr = 0;
-    for (int e = 0; e < n_edges; ++e) {
-        SLAM_REQUIRE(req[e].from >= 0 && req[e].from < nk && req[e].to >= 0 && req[e].to < nk, SLAM_E_INVALID,
-                     "slam_kf_register_edges: edge %d names keyframes %d -> %d, the store holds %d", e, req[e].from, req[e].to, nk);
-        n_corr += (size_t)s->kfs[req[e].to].view.n;
-    }
-    if (n_edges == 0) return SLAM_OK;
-    if (!pairs_trace) trace_cap = 0;
-    hipStream_t  st = as_stream(stream);
-    const size_t task_b = sizeof(EdgeTask) * (size_t)n_edges, res_b = sizeof(slam_kf_edge_result) * (size_t)n_edges;
-    const size_t trace_b = sizeof(int32_t) * (size_t)n_edges * trace_cap, corr_b = sizeof(int32_t) * n_corr;
-    const size_t res_off = (task_b + 255) & ~(size_t)255, trace_off = res_off + ((res_b + 255) & ~(size_t)255);
-    const size_t corr_off = trace_off + ((trace_b + 255) & ~(size_t)255);
-    SLAM_TRY(reserve_quarter(s->work, corr_off + corr_b));
-    char *host = static_cast<char *>(pinned_scratch(corr_off));
-    SLAM_REQUIRE(host, SLAM_E_NOMEM, "slam_kf_register_edges: no pinned staging memory");
-    char     *dev = static_cast<char *>(s->work.p);
-    EdgeTask *tasks = reinterpret_cast<EdgeTask *>(host);
-    int32_t  *corr = reinterpret_cast<int32_t *>(dev + corr_off);
-    for (int e = 0; e < n_edges; ++e) {
-        tasks[e].src = s->kfs[req[e].to].view;
-        tasks[e].tgt = s->kfs[req[e].from].view;
-        tasks[e].corr = corr;
-        corr += tasks[e].src.n;
-        std::memcpy(tasks[e].init, req[e].init, sizeof tasks[e].init);
-    }
     EdgeParams P;
     P.inv_cell = inv_cell(s->p), P.gate2 = s->p.gate * s->p.gate;
     P.eps_t = s->p.transformation_epsilon, P.eps_f = s->p.fitness_epsilon, P.max_iter = s->p.max_iterations;
-    int lds_points = 0;
-    if (s->p.target_in_lds)
-        for (int e = 0; e < n_edges; ++e)
-            if (tasks[e].tgt.n <= kLdsPoints && tasks[e].tgt.n > lds_points) lds_points = tasks[e].tgt.n;
-    if (lds_points && !s->lds_enabled) {
-        SLAM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kf_edge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(sizeof(float4) * kLdsPoints)));
-        s->lds_enabled = true;
-    }
-    SLAM_HIP(hipMemcpyAsync(dev, host, task_b, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(kf_edge_kernel, dim3(n_edges), dim3(kEdgeThreads), sizeof(float4) * (size_t)lds_points, st, reinterpret_cast<const EdgeTask *>(dev), P,
-                       reinterpret_cast<slam_kf_edge_result *>(dev + res_off), trace_cap ? reinterpret_cast<int32_t *>(dev + trace_off) : nullptr,
-                       trace_cap, lds_points);
-    SLAM_HIP(hipGetLastError());
-    SLAM_HIP(hipMemcpyAsync(host + res_off, dev + res_off, (trace_off - res_off) + trace_b, hipMemcpyDeviceToHost, st));
-    SLAM_HIP(hipStreamSynchronize(st));
-    std::memcpy(out, host + res_off, res_b);
-    if (trace_cap) std::memcpy(pairs_trace, host + trace_off, trace_b);
-    return SLAM_OK;
+    return kf_register_batch(s, "slam_kf_register_edges", "edge", kf_edge_kernel, s->lds_enabled, P,
+                             [](EdgeTask &, const slam_kf_edge_req &) -> int { return SLAM_OK; }, req, n_edges, out, pairs_trace, trace_cap, stream);
 }
 
 int slam_kf_register_edges(slam_kf_t *s, const slam_kf_edge_req *req, int n_edges, slam_kf_edge_result *out, slam_stream_t stream)

@@ -516,60 +516,17 @@ int slam_kf_register_gicp_traced(slam_kf_t *s, const slam_kf_edge_req *req, int 
 {
     SLAM_REQUIRE(s && n_req >= 0 && (n_req == 0 || (req && out)) && (!pairs_trace || trace_cap > 0), SLAM_E_INVALID,
                  "slam_kf_register_gicp: bad arguments");
-    const int nk = (int)s->kfs.size();
-    size_t    n_corr = 0;
-    for (int e = 0; e < n_req; ++e) {
-        SLAM_REQUIRE(req[e].from >= 0 && req[e].from < nk && req[e].to >= 0 && req[e].to < nk, SLAM_E_INVALID,
-                     "slam_kf_register_gicp: request %d names keyframes %d -> %d, the store holds %d", e, req[e].from, req[e].to, nk);
-        n_corr += (size_t)s->kfs[req[e].to].view.n;
-    }
-    if (n_req == 0) return SLAM_OK;
-    for (int e = 0; e < n_req; ++e) {
-        SLAM_TRY(slam_kf_compute_covariances(s, req[e].from, stream));
-        SLAM_TRY(slam_kf_compute_covariances(s, req[e].to, stream));
-    }
-    if (!pairs_trace) trace_cap = 0;
-    hipStream_t  st = as_stream(stream);
-    const size_t task_b = sizeof(GicpTask) * (size_t)n_req, res_b = sizeof(slam_kf_gicp_result) * (size_t)n_req;
-    const size_t trace_b = sizeof(int32_t) * (size_t)n_req * trace_cap, corr_b = sizeof(int32_t) * n_corr;
-    const size_t res_off = (task_b + 255) & ~(size_t)255, trace_off = res_off + ((res_b + 255) & ~(size_t)255);
-    const size_t corr_off = trace_off + ((trace_b + 255) & ~(size_t)255);
-    SLAM_TRY(reserve_quarter(s->work, corr_off + corr_b));
-    char *host = static_cast<char *>(pinned_scratch(corr_off));
-    SLAM_REQUIRE(host, SLAM_E_NOMEM, "slam_kf_register_gicp: no pinned staging memory");
-    char     *dev = static_cast<char *>(s->work.p);
-    GicpTask *tasks = reinterpret_cast<GicpTask *>(host);
-    int32_t  *corr = reinterpret_cast<int32_t *>(dev + corr_off);
-    for (int e = 0; e < n_req; ++e) {
-        const Keyframe &src = s->kfs[req[e].to], &tgt = s->kfs[req[e].from];
-        tasks[e].src = src.view, tasks[e].tgt = tgt.view;
-        tasks[e].src_cov = src.cov6, tasks[e].tgt_cov = tgt.cov6;
-        tasks[e].corr = corr;
-        corr += src.view.n;
-        std::memcpy(tasks[e].init, req[e].init, sizeof tasks[e].init);
-    }
     GicpParams P;
     P.inv_cell = inv_cell(s->p), P.gate2 = s->p.gate * s->p.gate;
     P.eps_t = s->gp.transformation_epsilon, P.eps_r = s->gp.rotation_epsilon, P.max_iter = s->gp.max_iterations;
-    int lds_points = 0;
-    if (s->p.target_in_lds)
-        for (int e = 0; e < n_req; ++e)
-            if (tasks[e].tgt.n <= kLdsPoints && tasks[e].tgt.n > lds_points) lds_points = tasks[e].tgt.n;
-    if (lds_points && !s->gicp_lds_enabled) {
-        SLAM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kf_gicp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(sizeof(float4) * kLdsPoints)));
-        s->gicp_lds_enabled = true;
-    }
-    SLAM_HIP(hipMemcpyAsync(dev, host, task_b, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(kf_gicp_kernel, dim3(n_req), dim3(kEdgeThreads), sizeof(float4) * (size_t)lds_points, st, reinterpret_cast<const GicpTask *>(dev), P,
-                       reinterpret_cast<slam_kf_gicp_result *>(dev + res_off), trace_cap ? reinterpret_cast<int32_t *>(dev + trace_off) : nullptr,
-                       trace_cap, lds_points);
-    SLAM_HIP(hipGetLastError());
-    SLAM_HIP(hipMemcpyAsync(host + res_off, dev + res_off, (trace_off - res_off) + trace_b, hipMemcpyDeviceToHost, st));
-    SLAM_HIP(hipStreamSynchronize(st));
-    std::memcpy(out, host + res_off, res_b);
-    if (trace_cap) std::memcpy(pairs_trace, host + trace_off, trace_b);
-    return SLAM_OK;
+    auto covariances = [&](GicpTask &t, const slam_kf_edge_req &r) -> int { // computed by the first request that names the keyframe
+        SLAM_TRY(slam_kf_compute_covariances(s, r.from, stream));
+        SLAM_TRY(slam_kf_compute_covariances(s, r.to, stream));
+        t.src_cov = s->kfs[r.to].cov6, t.tgt_cov = s->kfs[r.from].cov6;
+        return SLAM_OK;
+    };
+    return kf_register_batch(s, "slam_kf_register_gicp", "request", kf_gicp_kernel, s->gicp_lds_enabled, P, covariances, req, n_req, out, pairs_trace,
+                             trace_cap, stream);
 }
 
 int slam_kf_register_gicp(slam_kf_t *s, const slam_kf_edge_req *req, int n, slam_kf_gicp_result *out, slam_stream_t stream)

@@ -22,57 +22,10 @@
 #include <unordered_map>
 #include <vector>
 
+#include "kf_oracle_common.hpp"
 #include "slam_mi355x.h"
 
 namespace {
-
-// ---------------------------------------------------------------- the gated search
-// A lattice of edge `cell` >= gate: the nearest neighbour within the gate of a query is in the 27 cells around it.
-struct Index {
-    std::vector<float> p; // x y z per point, filtered-cloud order
-    int                n = 0;
-    double             inv = 0;
-    std::unordered_map<uint64_t, std::vector<int>> cells;
-};
-
-const int64_t kHalf = 1 << 20; // 21 bits per axis
-
-inline int64_t coord(float v, double inv)
-{
-    double c = std::floor((double)v * inv);
-    if (!(c >= -(double)kHalf)) c = -(double)kHalf; // also NaN
-    if (c > (double)(kHalf - 1)) c = (double)(kHalf - 1);
-    return (int64_t)c + kHalf;
-}
-inline uint64_t key_of(int64_t cx, int64_t cy, int64_t cz) { return ((uint64_t)cz << 42) | ((uint64_t)cy << 21) | (uint64_t)cx; }
-
-// f32, in this order, no FMA: dx*dx + dy*dy + dz*dz
-inline float dist2(const float *a, const float *b)
-{
-    const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-// the nearest point among the 27 cells (lowest index on an exact tie), -1 when they are empty
-int nearest(const Index &ix, const float *q, float *d2)
-{
-    const int64_t c[3] = {coord(q[0], ix.inv), coord(q[1], ix.inv), coord(q[2], ix.inv)};
-    int   best = -1;
-    float bd = 0;
-    for (int64_t z = c[2] - 1; z <= c[2] + 1; ++z)
-        for (int64_t y = c[1] - 1; y <= c[1] + 1; ++y)
-            for (int64_t x = c[0] - 1; x <= c[0] + 1; ++x) {
-                if (x < 0 || y < 0 || z < 0 || x >= 2 * kHalf || y >= 2 * kHalf || z >= 2 * kHalf) continue;
-                auto it = ix.cells.find(key_of(x, y, z));
-                if (it == ix.cells.end()) continue;
-                for (int j : it->second) {
-                    const float d = dist2(q, &ix.p[3 * (size_t)j]);
-                    if (best < 0 || d < bd || (d == bd && j < best)) best = j, bd = d;
-                }
-            }
-    *d2 = bd;
-    return best;
-}
 
 // ---------------------------------------------------------------- Umeyama without scaling
 // One-sided Jacobi SVD of a 3 x 3 matrix: A = U diag(s) V', s descending.  Columns of U for vanishing singular values
@@ -183,15 +136,6 @@ int solve(const float *p, const float *q, int n, S R[9], S t[3])
 }
 
 // ---------------------------------------------------------------- the ICP loop
-struct Margin {
-    double m = DBL_MAX;
-    void   see(double lhs, double rhs)
-    {
-        const double d = std::fabs(lhs - rhs) / (rhs != 0 ? std::fabs(rhs) : 1.0);
-        if (d < m) m = d;
-    }
-};
-
 // DefaultConvergenceCriteria::hasConverged after a step (R, t), in the order of docs/KF_EDGE.md; 0 = go on
 int stop_rule(int iterations, const double R[9], const double t[3], double mse, double *mse_prev, const slam_kf_params &P, Margin *mg)
 {
@@ -210,12 +154,6 @@ int stop_rule(int iterations, const double R[9], const double t[3], double mse, 
     if (d / *mse_prev < P.fitness_epsilon) return SLAM_KF_REL_MSE;
     *mse_prev = mse;
     return 0;
-}
-
-// pcl::transformPointCloud with a Matrix4f, in float, left to right: m00 x + m01 y + m02 z + m03
-inline void move_f32(const float M[16], const float *p, float *o)
-{
-    for (int r = 0; r < 3; ++r) o[r] = ((M[4 * r] * p[0] + M[4 * r + 1] * p[1]) + M[4 * r + 2] * p[2]) + M[4 * r + 3];
 }
 
 void icp(const Index &tgt, const float *src, int ns, int stride, const float init[16], const slam_kf_params &P, int mode,

@@ -16,18 +16,12 @@
 #include <unordered_map>
 #include <vector>
 
+#include "kf_oracle_common.hpp"
 #include "slam_mi355x.h"
 
 namespace {
 
 constexpr int kJacobiSweeps = 8;
-
-// f32, in this order, no FMA: dx*dx + dy*dy + dz*dz
-inline float dist2(const float *a, const float *b)
-{
-    const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
-    return (dx * dx + dy * dy) + dz * dz;
-}
 
 inline void plane_covariance(const double C[6], double eps, double out[6])
 {
@@ -180,55 +174,6 @@ void covariances(const float *xyz, int n, int stride, int k, const int32_t *idx,
     }
 }
 
-// ---------------------------------------------------------------- the gated search, as tests/cpp/kf_edge_oracle.cpp has it
-struct Index {
-    std::vector<float>  p; // x y z per point, filtered-cloud order
-    std::vector<double> cov;
-    int                 n = 0;
-    double              inv = 0;
-    std::unordered_map<uint64_t, std::vector<int>> cells;
-};
-
-const int64_t kHalf = 1 << 20;
-
-inline int64_t coord(float v, double inv)
-{
-    double c = std::floor((double)v * inv);
-    if (!(c >= -(double)kHalf)) c = -(double)kHalf; // also NaN
-    if (c > (double)(kHalf - 1)) c = (double)(kHalf - 1);
-    return (int64_t)c + kHalf;
-}
-inline uint64_t key_of(int64_t cx, int64_t cy, int64_t cz) { return ((uint64_t)cz << 42) | ((uint64_t)cy << 21) | (uint64_t)cx; }
-
-int nearest(const Index &ix, const float *q, float *d2)
-{
-    const int64_t c[3] = {coord(q[0], ix.inv), coord(q[1], ix.inv), coord(q[2], ix.inv)};
-    int   best = -1;
-    float bd = 0;
-    for (int64_t z = c[2] - 1; z <= c[2] + 1; ++z)
-        for (int64_t y = c[1] - 1; y <= c[1] + 1; ++y)
-            for (int64_t x = c[0] - 1; x <= c[0] + 1; ++x) {
-                if (x < 0 || y < 0 || z < 0 || x >= 2 * kHalf || y >= 2 * kHalf || z >= 2 * kHalf) continue;
-                auto it = ix.cells.find(key_of(x, y, z));
-                if (it == ix.cells.end()) continue;
-                for (int j : it->second) {
-                    const float d = dist2(q, &ix.p[3 * (size_t)j]);
-                    if (best < 0 || d < bd || (d == bd && j < best)) best = j, bd = d;
-                }
-            }
-    *d2 = bd;
-    return best;
-}
-
-struct Margin {
-    double m = DBL_MAX;
-    void   see(double lhs, double rhs)
-    {
-        const double d = std::fabs(lhs - rhs) / (rhs != 0 ? std::fabs(rhs) : 1.0);
-        if (d < m) m = d;
-    }
-};
-
 // ---------------------------------------------------------------- the iteration
 void gicp(const Index &tgt, const float *src, int ns, int stride, const double *src_cov, const float init[16], double gate,
           const slam_kf_gicp_params &P, slam_kf_gicp_result *out, int32_t *trace, int trace_cap, double *margin)
@@ -304,12 +249,6 @@ void gicp(const Index &tgt, const float *src, int ns, int stride, const double *
     out->cost = cost;
     std::memcpy(out->hessian, H, sizeof H);
     if (margin) *margin = mg.m;
-}
-
-// pcl::transformPointCloud with a Matrix4f, in float, left to right
-inline void move_f32(const float M[16], const float *p, float *o)
-{
-    for (int r = 0; r < 3; ++r) o[r] = ((M[4 * r] * p[0] + M[4 * r + 1] * p[1]) + M[4 * r + 2] * p[2]) + M[4 * r + 3];
 }
 
 } // namespace

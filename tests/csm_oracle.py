@@ -1,15 +1,12 @@
 """ctypes wrapper of tests/cpp/csm_oracle.cpp, the scalar restatement of the correlative scan matcher's contract
-(docs/CSM.md) that slam_csm_* is held against bit for bit.  Compiled on first use with g++ -O2 -ffp-contract=off into a
-temporary directory.  The parameter and result structures are slam_amd.api's (the header's); nothing else of the
-library is used."""
+(docs/CSM.md) that slam_csm_* is held against bit for bit.  Compiled on first use by tests/oracle_build.py.  The
+parameter and result structures are slam_amd.api's (the header's); nothing else of the library is used."""
 import ctypes as C
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from oracle_build import load, ptr as _p
 from slam_amd import api, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,18 +18,7 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    h = hashlib.sha1()
-    for f in (SRC, os.path.join(ROOT, "include", "slam_mi355x.h")):
-        h.update(open(f, "rb").read())
-    d = os.path.join(tempfile.gettempdir(), "slam_csm_oracle_%d" % os.getuid())
-    os.makedirs(d, exist_ok=True)
-    so = os.path.join(d, "csm_oracle_%s.so" % h.hexdigest()[:16])
-    if not os.path.exists(so):
-        tmp = so + ".%d.tmp" % os.getpid()
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-shared", "-fPIC",
-                               "-I", os.path.join(ROOT, "include"), SRC, "-o", tmp])
-        os.replace(tmp, so)
-    L = C.CDLL(so)
+    L = load("csm_oracle", SRC)
     vp, ip = C.c_void_p, C.POINTER(C.c_int)
     L.csmo_create.restype = vp
     L.csmo_create.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(api.CsmParams)]
@@ -53,10 +39,6 @@ def lib():
     L.csmo_match.restype = None
     _lib = L
     return L
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
 
 
 def default_params(**kw):

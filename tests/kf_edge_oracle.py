@@ -1,18 +1,16 @@
 """ctypes wrapper of tests/cpp/kf_edge_oracle.cpp, the scalar restatement of graph_slam's keyframe edge
-(graphSlamTools.cpp:27-39, 108-364) that slam_kf_* is held against.  Compiled on first use with
-g++ -O2 -ffp-contract=off (the reference is x86-64 without FMA) into a temporary directory."""
+(graphSlamTools.cpp:27-39, 108-364) that slam_kf_* is held against.  Compiled on first use by tests/oracle_build.py."""
 import ctypes as C
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from oracle_build import load, ptr as _p
 from slam_amd import api, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "kf_edge_oracle.cpp")
+COMMON = os.path.join(ROOT, "tests", "cpp", "kf_oracle_common.hpp")   # shared with kf_gicp_oracle.cpp
 _lib = None
 
 
@@ -20,18 +18,7 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    h = hashlib.sha1()
-    for f in (SRC, os.path.join(ROOT, "include", "slam_mi355x.h")):
-        h.update(open(f, "rb").read())
-    d = os.path.join(tempfile.gettempdir(), "slam_kf_edge_oracle_%d" % os.getuid())
-    os.makedirs(d, exist_ok=True)
-    so = os.path.join(d, "kf_edge_oracle_%s.so" % h.hexdigest()[:16])
-    if not os.path.exists(so):
-        tmp = so + ".%d.tmp" % os.getpid()
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-shared", "-fPIC",
-                               "-I", os.path.join(ROOT, "include"), SRC, "-o", tmp])
-        os.replace(tmp, so)
-    L = C.CDLL(so)
+    L = load("kf_edge_oracle", SRC, (COMMON,))
     vp = C.c_void_p
     L.kfo_index_create.restype = vp
     L.kfo_index_create.argtypes = [vp, C.c_int, C.c_int, C.c_double]
@@ -46,10 +33,6 @@ def lib():
     L.kfo_inverse6.argtypes = [vp, vp]
     _lib = L
     return L
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
 
 
 def default_params(**kw):

@@ -1,15 +1,13 @@
 """ctypes wrapper of tests/cpp/kf_gicp_oracle.cpp, the scalar restatement of the store's Generalized ICP
 (docs/KF_GICP.md) that slam_kf_compute_covariances and slam_kf_register_gicp are held against.  Compiled on first use
-with g++ -O2 -ffp-contract=off into a temporary directory, as tests/kf_edge_oracle.py compiles its own."""
+by tests/oracle_build.py."""
 import ctypes as C
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import kf_edge_oracle as K
+from oracle_build import load, ptr as _p
 from slam_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,18 +19,7 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    h = hashlib.sha1()
-    for f in (SRC, os.path.join(ROOT, "include", "slam_mi355x.h")):
-        h.update(open(f, "rb").read())
-    d = os.path.join(tempfile.gettempdir(), "slam_kf_gicp_oracle_%d" % os.getuid())
-    os.makedirs(d, exist_ok=True)
-    so = os.path.join(d, "kf_gicp_oracle_%s.so" % h.hexdigest()[:16])
-    if not os.path.exists(so):
-        tmp = so + ".%d.tmp" % os.getpid()
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-shared", "-fPIC",
-                               "-I", os.path.join(ROOT, "include"), SRC, "-o", tmp])
-        os.replace(tmp, so)
-    L = C.CDLL(so)
+    L = load("kf_gicp_oracle", SRC, (K.COMMON,))
     vp = C.c_void_p
     L.kgo_covariances.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp]
     L.kgo_plane_covariance.argtypes = [vp, C.c_double, vp]
@@ -51,10 +38,6 @@ def lib():
     L.kgo_fitness.restype = None
     _lib = L
     return L
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
 
 
 def default_gicp(**kw):

@@ -1,14 +1,12 @@
 """ctypes wrapper of tests/cpp/mls_map_oracle.cpp, the scalar restatement of the height-cluster MLS
-(mls.cpp:18-53, 152-402, 481-556) that slam_mls_* is held against.  Compiled on first use with
-g++ -O2 -ffp-contract=off (the reference is x86-64 without FMA) into a temporary directory."""
+(mls.cpp:18-53, 152-402, 481-556) that slam_mls_* is held against.  Compiled on first use by
+tests/oracle_build.py."""
 import ctypes as C
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from oracle_build import load, ptr as _p
 from slam_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,18 +18,7 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    h = hashlib.sha1()
-    for f in (SRC, os.path.join(ROOT, "include", "slam_mi355x.h")):
-        h.update(open(f, "rb").read())
-    d = os.path.join(tempfile.gettempdir(), "slam_mls_map_oracle_%d" % os.getuid())
-    os.makedirs(d, exist_ok=True)
-    so = os.path.join(d, "mls_map_oracle_%s.so" % h.hexdigest()[:16])
-    if not os.path.exists(so):
-        tmp = so + ".%d.tmp" % os.getpid()
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-shared", "-fPIC",
-                               "-I", os.path.join(ROOT, "include"), SRC, "-o", tmp])
-        os.replace(tmp, so)
-    L = C.CDLL(so)
+    L = load("mls_map_oracle", SRC)
     vp = C.c_void_p
     L.mlso_create.restype = vp
     L.mlso_create.argtypes = [C.c_int, C.c_int, C.c_double, C.POINTER(api.MlsParams)]
@@ -55,10 +42,6 @@ def lib():
     L.mlso_outside_updates.argtypes = [vp]
     _lib = L
     return L
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
 
 
 class OracleMls:

@@ -2,7 +2,10 @@
 tests/cpp/kf_gicp_oracle.cpp: neighbour lists and covariances bit for bit, the iteration with and without its stop rule,
 the hand-worked requests of tests/kf_gicp_cases.py, batch independence, the LDS boundary, the untouched ICP path and the
 argument errors.  Bounds: docs/KF_GICP.md section 5."""
+import os
 import signal
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -34,12 +37,18 @@ def bits(a):
     return np.ascontiguousarray(a).view(np.uint8)
 
 
-def same_result(a, b):
-    return all(np.array_equal(bits(a[k]), bits(b[k])) for k in ("transform", "transform64", "information", "hessian")) and \
-        all(a[k] == b[k] for k in ("iterations", "state", "converged", "pairs", "num_corr", "singular", "fitness_pairs")) and \
-        all(np.array_equal(bits(np.float64(a[k])), bits(np.float64(b[k]))) for k in ("mse", "cost", "fitness")) and \
+def same_edge(a, b):
+    """Every field of a slam_kf_edge_result, and the trace where there is one, the same bits."""
+    return all(np.array_equal(bits(a[k]), bits(b[k])) for k in ("transform", "transform64", "information")) and \
+        all(a[k] == b[k] for k in ("iterations", "state", "converged", "pairs", "num_corr", "singular")) and \
+        np.array_equal(bits(np.float64(a["mse"])), bits(np.float64(b["mse"]))) and \
         np.array_equal(bits(np.float32(a["ss"])), bits(np.float32(b["ss"]))) and \
         ("pairs_trace" not in a or np.array_equal(a["pairs_trace"], b["pairs_trace"]))
+
+
+def same_result(a, b):
+    return same_edge(a, b) and np.array_equal(bits(a["hessian"]), bits(b["hessian"])) and a["fitness_pairs"] == b["fitness_pairs"] and \
+        all(np.array_equal(bits(np.float64(a[k])), bits(np.float64(b[k]))) for k in ("cost", "fitness"))
 
 
 class Store:
@@ -301,6 +310,52 @@ def test_icp_edges_are_the_same_bits_before_and_after_covariances():
         assert np.array_equal(bits(before[k]), bits(after[k])), k
     for k in ("iterations", "state", "converged", "pairs", "mse", "num_corr", "singular", "ss"):
         assert before[k] == after[k], k
+
+
+ORDERS = {"gicp-first": ("gicp", "icp"), "icp-first": ("icp", "gicp")}
+ORDER_CHILD = "import sys; sys.path[:0] = [%r, %r]; import test_gpu_kf_gicp as t; t.order_child(sys.argv[1], sys.argv[2])"
+
+
+def order_request():
+    poses = [K.cloud(k)[1] for k in (0, 1)]
+    return [(0, 1, K.relative_init(poses[0], poses[1]))]
+
+
+def order_run(solvers):
+    """A fresh store with keyframes 0 and 1, then one request per solver in the order given: {solver: result}."""
+    store = api.KeyframeStore()
+    for k in (0, 1):
+        store.add_keyframe(K.cloud(k)[0])
+    assert 4096 < store.info(0)["n_points"] <= 6144      # the target: more dynamic LDS than the default 64 KB
+    req = order_request()
+    return {s: (store.register_gicp(req, trace=16) if s == "gicp" else store.register_edges(req, trace=64))[0] for s in solvers}
+
+
+def order_child(order, path):
+    """What a child process of the test below runs: its own first launches of both kernels, results to an .npz."""
+    api.set_device(0)
+    got = order_run(ORDERS[order])
+    np.savez(path, **{"%s/%s" % (s, k): np.asarray(v) for s, r in got.items() for k, v in r.items()})
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("order", sorted(ORDERS))
+def test_either_solver_first_in_a_fresh_process_gives_what_each_gives_alone(order, tmp_path):
+    """The two kernels share a host path that raises each kernel's dynamic-LDS limit under that kernel's own flag.  Only a
+    target of 4 097 .. 6 144 points asks for more than the default 64 KB, and the limit, once raised, holds for the kernel in
+    the whole process, whichever store raised it.  So each order runs in a child process of its own, where neither kernel has
+    been launched before: a flag set by the other solver would leave the second kernel at the default limit and its launch
+    refused (the child then fails).  The child's results are the bits of the same requests made here, each on its own store."""
+    tests = os.path.dirname(os.path.abspath(__file__))
+    out = str(tmp_path / "results.npz")
+    child = subprocess.run([sys.executable, "-c", ORDER_CHILD % (os.path.dirname(tests), tests), order, out],
+                           capture_output=True, text=True, timeout=120)
+    assert child.returncode == 0, child.stderr[-2000:]
+    z = np.load(out)
+    got = {s: {k.split("/")[1]: z[k][()] for k in z.files if k.startswith(s + "/")} for s in ORDERS[order]}
+    gicp_alone, icp_alone = order_run(["gicp"])["gicp"], order_run(["icp"])["icp"]
+    assert gicp_alone["pairs"] > 1000 and icp_alone["pairs"] > 1000
+    assert same_result(got["gicp"], gicp_alone) and same_edge(got["icp"], icp_alone)
 
 
 # ------------------------------------------------------------------ refusals
