@@ -14,7 +14,8 @@
 //     repeated and C++ and Python draw the same starts;
 //   * the store always filters: the refinement's target is the map at `refine_leaf` (0.25 m), not the unfiltered map, with a
 //     gate of `refine_gate` (1 m) instead of 10 m, which the coarse match is well inside;
-//   * scans stay in the stores (the store has no remove call): a known leak of one filtered scan per match() and store.
+//   * scans stay in the stores: one filtered scan per match() and store, which a test reads back afterwards; a caller that
+//     minds frees them with slam_kf_remove_keyframe (docs/VOXEL_MAP.md section 4).
 #pragma once
 #include <cmath>
 #include <cstdint>

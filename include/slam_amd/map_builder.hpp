@@ -1,0 +1,174 @@
+// slam_amd/map_builder.hpp -- header-only adapter with the shape of global_matching's map builder
+// (global_matching/src/global_generate.cpp:122-232) over the C-ABI (slam_mi355x.h: slam_vmap_*, slam_kf_*):
+//   laser_callback   :59-80     the first cloud is the map
+//   setup_gicp       :82-92     100 iterations, epsilons 1e-6
+//   the loop         :122-232   addCloud(): filter scan and map, crop the map around the pose, Generalized ICP of the scan
+//                               onto the map, drop the scan on a bad score, otherwise move it and append it to the map
+// The map is a slam_vmap_t (exact mean per voxel of everything integrated); the store holds the scan and the cropped map
+// for the length of one call.  ROS, the publishers and the .csv stay with the caller.
+// slam_amd.api.GlobalMapBuilder is the same thing with Python's names and habits:
+//   addCloud -> add_cloud, returning (accepted, result or None) where this sets `last` and `last_valid`;
+//   mapKeyframe() -> map_id, cropBox() -> crop_box(), pose() and map() alike, ok() has no twin (the constructor raises);
+//   an error of the library is printed here and counts as a rejection, there it raises SlamError (the scan keyframe is
+//   removed on both ways out).
+//
+// Stated deviations (docs/VOXEL_MAP.md section 5):
+//   * the start is passed to the solver as `init` instead of moving the source first (:144), so the solver's result is
+//     trans_full itself and not a factor of it (:188);
+//   * the map is the exact mean per voxel of every point integrated; the reference filters the previous round's centroids
+//     again together with the new scan (:135-137, :223), which weights old points by their voxel, not by their number;
+//   * the gate is `gate` = 2 m, not 10 (:84): docs/KF_GICP.md section 4's reasoning for refine_gate;
+//   * the fitness is gated at the store's gate, not at MAX_DIST (:178); MAX_DIST is kept as a member and unused;
+//   * the source is not cropped (:160-168): a scan reaches 100 m at most, so the crop around the pose keeps all of it.
+#pragma once
+#include <cstdio>
+#include <vector>
+
+#include "slam_mi355x.h"
+
+namespace slam_amd {
+
+class GlobalMapBuilder {
+public:
+    // global_generate.cpp:21-29, :84-90: macros and setup_gicp's arguments there, members here.  The store and the map are made
+    // with them, so all but the two below are fixed at construction (const here, read-only properties in Python).
+    const double LEAF_SIZE;
+    const double gate;
+    const int    MAX_ITERATIONS = 100;
+    const double TRANSFORMATION_EPSILON = 1e-6, FITNESS_EPSILON = 1e-6;
+    const double MAX_DIST = 4.0; // of getFitnessScore(MAX_DIST), :178: kept for the name, without effect (the store's gate rules)
+    // read at every addCloud: may be changed between calls
+    double MAX_SCORE = 1.0;
+    double CROP_DIST = 100.0;
+
+    float               trans_full[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    int                 n_clouds = 0, n_accepted = 0;
+    slam_kf_gicp_result last;            // the last request's result
+    bool                last_valid = false; // false for the first cloud and when nothing of the map was near the pose
+
+    explicit GlobalMapBuilder(double leaf = 0.30, double gate_ = 2.0) : LEAF_SIZE(leaf), gate(gate_), last()
+    {
+        slam_vmap_params vp;
+        slam_vmap_default_params(&vp);
+        vp.leaf = leaf;
+        if (slam_vmap_create(&vp, &vmap_) != SLAM_OK) warn(), vmap_ = nullptr;
+        slam_kf_params p;
+        slam_kf_default_params(&p);
+        p.leaf_size = leaf, p.gate = gate_, p.transformation_epsilon = TRANSFORMATION_EPSILON, p.fitness_epsilon = FITNESS_EPSILON;
+        slam_kf_gicp_params gp;
+        slam_kf_gicp_default_params(&gp);
+        gp.max_iterations = MAX_ITERATIONS, gp.transformation_epsilon = TRANSFORMATION_EPSILON;
+        if (slam_kf_create(&p, &store_) != SLAM_OK || slam_kf_set_gicp_params(store_, &gp) != SLAM_OK) {
+            warn();
+            slam_kf_destroy(store_);
+            store_ = nullptr;
+        }
+    }
+    ~GlobalMapBuilder()
+    {
+        slam_free(d_scan_);
+        slam_free(d_map_);
+        slam_kf_destroy(store_);
+        slam_vmap_destroy(vmap_);
+    }
+    GlobalMapBuilder(const GlobalMapBuilder &) = delete;
+    GlobalMapBuilder &operator=(const GlobalMapBuilder &) = delete;
+    bool         ok() const { return vmap_ && store_; }
+    slam_vmap_t *vmap() { return vmap_; }
+    slam_kf_t   *store() { return store_; }
+    int          mapKeyframe() const { return map_id_; }
+    const float *pose() const { return trans_full; }
+    // :149-157: -+CROP_DIST around the pose, the limits in double rounded to float once
+    void cropBox(float lo[2], float hi[2]) const
+    {
+        for (int k = 0; k < 2; ++k) {
+            lo[k] = (float)(-CROP_DIST + (double)trans_full[4 * k + 3]);
+            hi[k] = (float)(CROP_DIST + (double)trans_full[4 * k + 3]);
+        }
+    }
+
+    // One scan (sensor frame, `stride` >= 3 floats per point).  True when it was integrated into the map; `last` holds the
+    // request's result when last_valid.  An error of the library is printed and counts as a rejection.
+    bool addCloud(const float *xyz, int n, int stride)
+    {
+        if (!ok() || n <= 0 || stride < 3 || !xyz) return false;
+        ++n_clouds;
+        last_valid = false;
+        int64_t n_points = 0, n_voxels = 0;
+        if (slam_vmap_info(vmap_, &n_voxels, nullptr, &n_points, nullptr) != SLAM_OK) return warn(), false;
+        if (n_points == 0) { // :63-70: the first cloud is the map
+            if (slam_vmap_integrate(vmap_, xyz, n, stride, nullptr, nullptr, nullptr) != SLAM_OK) return warn(), false;
+            ++n_accepted;
+            return true;
+        }
+        const size_t scan_bytes = sizeof(float) * (size_t)n * stride;
+        if (!reserve(&d_scan_, &scan_cap_, scan_bytes) || slam_memcpy_h2d(d_scan_, xyz, scan_bytes, nullptr) != SLAM_OK) return warn(), false;
+        int scan = -1;
+        if (slam_kf_add_keyframe_dev(store_, static_cast<const float *>(d_scan_), n, stride, &scan, nullptr) != SLAM_OK) return warn(), false;
+        const bool accepted = registerAndIntegrate(scan, n, stride, (int)n_voxels);
+        if (slam_kf_remove_keyframe(store_, scan) != SLAM_OK) warn(); // the store holds two keyframes at most
+        if (accepted) ++n_accepted;
+        return accepted;
+    }
+
+    // the whole map as GlobalMatcher::setMap takes it: (x, y, z, 0) per voxel in key order, stride 4
+    std::vector<float> map()
+    {
+        std::vector<float> out;
+        int64_t            n_voxels = 0;
+        if (!ok() || slam_vmap_info(vmap_, &n_voxels, nullptr, nullptr, nullptr) != SLAM_OK || n_voxels == 0) return out;
+        out.resize(4 * (size_t)n_voxels);
+        int n = 0;
+        if (slam_vmap_read(vmap_, nullptr, nullptr, 0, out.data(), nullptr, nullptr, (int)n_voxels, &n) != SLAM_OK) warn(), n = 0;
+        out.resize(4 * (size_t)n);
+        return out;
+    }
+
+private:
+    bool registerAndIntegrate(int scan, int n, int stride, int n_voxels)
+    {
+        float lo[2], hi[2]; // the map inside the crop box
+        cropBox(lo, hi);
+        const int   cap = n_voxels > 0 ? n_voxels : 1;
+        int         n_map = 0;
+        if (!reserve(&d_map_, &map_cap_, sizeof(float) * 4 * (size_t)cap)) return warn(), false;
+        if (slam_vmap_extract_dev(vmap_, lo, hi, 0, static_cast<float *>(d_map_), nullptr, nullptr, cap, &n_map, nullptr) != SLAM_OK) return warn(), false;
+        if (slam_device_synchronize() != SLAM_OK) return warn(), false;
+        if (n_map == 0) return false; // nothing of the map near the pose: nothing to register against
+        const int rc = map_id_ < 0 ? slam_kf_add_keyframe_dev(store_, static_cast<const float *>(d_map_), n_map, 4, &map_id_, nullptr)
+                                   : slam_kf_replace_keyframe_dev(store_, map_id_, static_cast<const float *>(d_map_), n_map, 4, nullptr);
+        if (rc != SLAM_OK) return warn(), false;
+        slam_kf_edge_req rq;
+        rq.from = map_id_, rq.to = scan;
+        for (int k = 0; k < 16; ++k) rq.init[k] = trans_full[k];
+        if (slam_kf_register_gicp(store_, &rq, 1, &last, nullptr) != SLAM_OK) return warn(), false;
+        last_valid = true;
+        if (last.fitness_pairs <= 0 || !last.edge.converged || last.fitness > MAX_SCORE) return false; // :182
+        double R[9], t[3];
+        for (int k = 0; k < 16; ++k) trans_full[k] = last.edge.transform[k];
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) R[3 * r + c] = (double)trans_full[4 * r + c];
+            t[r] = (double)trans_full[4 * r + 3];
+        }
+        if (slam_vmap_integrate_dev(vmap_, static_cast<const float *>(d_scan_), n, stride, R, t, nullptr, nullptr) != SLAM_OK) return warn(), false;
+        return true;
+    }
+    static bool reserve(void **p, size_t *cap, size_t bytes)
+    {
+        if (bytes <= *cap) return true;
+        slam_free(*p);
+        *p = nullptr, *cap = 0;
+        if (slam_malloc(p, bytes + bytes / 4) != SLAM_OK) return false;
+        *cap = bytes + bytes / 4;
+        return true;
+    }
+    static void warn() { std::fprintf(stderr, "GlobalMapBuilder: %s\n", slam_last_error()); }
+
+    slam_vmap_t *vmap_ = nullptr;
+    slam_kf_t   *store_ = nullptr;
+    void        *d_scan_ = nullptr, *d_map_ = nullptr;
+    size_t       scan_cap_ = 0, map_cap_ = 0;
+    int          map_id_ = -1;
+};
+
+} // namespace slam_amd

@@ -719,6 +719,13 @@ int  slam_kf_set_params(slam_kf_t *s, const slam_kf_params *params); /* leaf, ga
  * of arrival.  The _dev form takes a device pointer.  Both wait for the work they enqueue on `stream`. */
 int  slam_kf_add_keyframe(slam_kf_t *s, const float *xyz, int n, int stride, int *id);
 int  slam_kf_add_keyframe_dev(slam_kf_t *s, const float *d_xyz, int n, int stride, int *id, slam_stream_t stream);
+/* Lets go of keyframe `id`: its cloud, lattice and covariances are freed (waits for the device).  The id is never issued
+ * again and slam_kf_count stays the number of ids issued; every later call that names the id returns SLAM_E_INVALID.  The
+ * parameters that the store's keyframes had fixed (slam_kf_set_params, slam_kf_set_gicp_params) stay fixed. */
+int  slam_kf_remove_keyframe(slam_kf_t *s, int id);
+/* slam_kf_add_keyframe_dev's filter and lattice into the existing keyframe `id`; its covariances are dropped and computed
+ * again on demand.  When the new cloud is refused the old keyframe stays.  Waits as slam_kf_add_keyframe_dev does. */
+int  slam_kf_replace_keyframe_dev(slam_kf_t *s, int id, const float *d_xyz, int n, int stride, slam_stream_t stream);
 /* n_points after the filter, occupied lattice cells, the largest cell, slots of the hash table, device bytes held */
 int  slam_kf_keyframe_info(slam_kf_t *s, int id, int *n_points, int *n_cells, int *max_cell_points, int *table_slots,
                            long *device_bytes);
@@ -843,6 +850,60 @@ int  slam_csm_score_volume_dev(slam_csm_t *csm, const double *d_pts, int n, int 
 int  slam_csm_read_table(slam_csm_t *csm, int cls, int level, int *origin_x, int *origin_y, int *w, int *h, uint8_t *buf, size_t cap);
 /* the parameters in force (kernel_cells resolved), N_theta N_x N_y and blocks per axis in dims[5], bytes of tables and scratch */
 int  slam_csm_info(slam_csm_t *csm, slam_csm_params *params, int dims[5], size_t *table_bytes, size_t *scratch_bytes, int *max_scans);
+
+/* -------------------------------------------------------------------------
+ * Exact sparse voxel map: the growing prior map of global_generate.cpp (the reference keeps it as a point cloud that is
+ * voxel-filtered again every round, global_generate.cpp:122-232).  Clouds are integrated in place into an open-addressing
+ * table in HBM; a voxel holds a point count and three integer sums of the coordinates in units of 2^-20 m, so the map of a
+ * set of (cloud, transform) pairs is the same bits in any order of clouds, points and threads.  docs/VOXEL_MAP.md has the
+ * contract; the device equals tests/cpp/vmap_oracle.cpp bit for bit.
+ *   point     q = (float)(((r0 x + r1 y) + r2 z) + t) per axis in double without contraction (slam_grid_transform_cloud_dev's
+ *             arithmetic); q = p without a transform
+ *   cell      (int32) floor((double) q / leaf); a point is dropped (and counted) when a coordinate is not finite or
+ *             |q| >= 2^22, or |cell| >= 2^20 on any axis
+ *   key       (iz + 2^20) << 42 | (iy + 2^20) << 21 | (ix + 2^20); all ones = empty
+ *   sums      int64 of rint((double) q * 2^20) (to nearest even) per axis: exact while a voxel holds fewer than 2^21 points
+ *   centroid  (float)(((double) S / (double) count) * 2^-20)
+ * ---------------------------------------------------------------------- */
+typedef struct slam_vmap slam_vmap_t;
+
+typedef struct {
+    double leaf;             /* edge of a voxel in metres (0.30, LEAF_SIZE of global_generate.cpp:26) */
+    int    initial_capacity; /* slots of the first table (65536), rounded up to a power of two, at least 64; at most 2^30 */
+} slam_vmap_params;
+
+void slam_vmap_default_params(slam_vmap_params *p);
+int  slam_vmap_create(const slam_vmap_params *params, slam_vmap_t **out);
+void slam_vmap_destroy(slam_vmap_t *m);
+/* Empties the map and keeps the table's size.  Asynchronous on `stream`.  One call at a time per handle (the table). */
+int  slam_vmap_clear(slam_vmap_t *m, slam_stream_t stream);
+/* n points, `stride` floats apart (>= 3), moved by R (9 doubles, row-major) and t (3 doubles) when both are given, neither
+ * otherwise.  A call that does not grow the table WAITS ONCE for `stream`, to read the voxel count, the dropped points
+ * (*n_dropped, nullable) and the error word back.  The host keeps the table at most half full: when
+ * n_voxels + n > capacity / 2 the call first rehashes the table into one at least twice the size, in a launch of its own.
+ * Such a growing call waits THREE times and synchronises the whole device: for `stream` after the rehash (to check that every
+ * voxel arrived), for the device when the old table is freed, and for the counters as above.  A probe that ran out of table is
+ * SLAM_E_HIP (it cannot happen under the load rule).  One call at a time per handle. */
+int  slam_vmap_integrate_dev(slam_vmap_t *m, const float *d_xyz, int n, int stride, const double R[9], const double t[3],
+                             int *n_dropped, slam_stream_t stream);
+int  slam_vmap_integrate(slam_vmap_t *m, const float *xyz, int n, int stride, const double R[9], const double t[3], int *n_dropped);
+/* The voxels with count >= min_count whose centroid c has lo_xy[0] <= c.x <= hi_xy[0] and lo_xy[1] <= c.y <= hi_xy[1] in f32
+ * (both ends kept, as pcl::PassThrough; lo_xy = hi_xy = NULL: everything), in ascending key order: d_xyz4[4 i ..] =
+ * (x, y, z, 0) and, where given, d_count[i] (uint32) and d_key[i] (uint64).  *n_out is the number of such voxels; when it
+ * exceeds `cap` nothing is written and the call returns SLAM_E_NOMEM.  WAITS ONCE for `stream`, to read that number; the
+ * sort and the writes that follow are asynchronous.  The first call after the table grew, or with more voxels than any call
+ * before, regrows the handle's scratch, which frees the old blocks and so waits for the whole device besides.  One call at a
+ * time per handle: it shares the scratch and the table with integrate and clear. */
+int  slam_vmap_extract_dev(slam_vmap_t *m, const float lo_xy[2], const float hi_xy[2], int min_count, float *d_xyz4,
+                           uint32_t *d_count, uint64_t *d_key, int cap, int *n_out, slam_stream_t stream);
+/* The same into host arrays (each nullable), synchronous. */
+int  slam_vmap_read(slam_vmap_t *m, const float lo_xy[2], const float hi_xy[2], int min_count, float *xyz4, uint32_t *count,
+                    uint64_t *key, int cap, int *n_out);
+/* The accumulators themselves, for tests and for saving a map: every occupied voxel in ascending key order, sums[3 i ..] =
+ * the three int64 sums in units of 2^-20 m.  Host arrays, each nullable; synchronous; `cap` and *n_out as above. */
+int  slam_vmap_read_sums(slam_vmap_t *m, int64_t *sums, uint32_t *count, uint64_t *key, int cap, int *n_out);
+/* occupied voxels, slots of the table, points integrated (dropped ones not counted), bytes of device memory held */
+int  slam_vmap_info(slam_vmap_t *m, int64_t *n_voxels, int64_t *capacity, int64_t *n_points, size_t *device_bytes);
 
 #ifdef __cplusplus
 }

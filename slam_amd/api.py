@@ -110,6 +110,10 @@ class CsmResult(C.Structure):
                 ("n_points", C.c_int), ("blocks_evaluated", C.c_int)]
 
 
+class VmapParams(C.Structure):
+    _fields_ = [("leaf", C.c_double), ("initial_capacity", C.c_int)]
+
+
 CSM_RESULT_DTYPE = np.dtype([(f, np.int32) for f, _ in CsmResult._fields_])
 
 KF_NOT_CONVERGED, KF_ITERATIONS, KF_TRANSFORM, KF_ABS_MSE, KF_REL_MSE, KF_NO_CORRESPONDENCES = 0, 1, 2, 3, 4, 5
@@ -161,12 +165,14 @@ EXPORTS = [
     "slam_mls_read_drivability", "slam_mls_segmented_clouds", "slam_mls_read_cells", "slam_mls_info",
     "slam_kf_default_params", "slam_kf_create", "slam_kf_destroy", "slam_kf_set_params", "slam_kf_add_keyframe",
     "slam_kf_add_keyframe_dev", "slam_kf_keyframe_info", "slam_kf_count", "slam_kf_read_keyframe", "slam_kf_nearest_dev",
-    "slam_kf_register_edges", "slam_kf_register_edges_traced",
+    "slam_kf_register_edges", "slam_kf_register_edges_traced", "slam_kf_remove_keyframe", "slam_kf_replace_keyframe_dev",
     "slam_kf_gicp_default_params", "slam_kf_set_gicp_params", "slam_kf_compute_covariances", "slam_kf_read_covariances",
     "slam_kf_read_neighbours", "slam_kf_register_gicp", "slam_kf_register_gicp_traced",
     "slam_csm_default_params", "slam_csm_create", "slam_csm_create_dev", "slam_csm_destroy", "slam_csm_reserve",
     "slam_csm_set_window", "slam_csm_set_exhaustive", "slam_csm_angles", "slam_csm_match_batch_dev", "slam_csm_match",
     "slam_csm_score_volume_dev", "slam_csm_read_table", "slam_csm_info",
+    "slam_vmap_default_params", "slam_vmap_create", "slam_vmap_destroy", "slam_vmap_clear", "slam_vmap_integrate",
+    "slam_vmap_integrate_dev", "slam_vmap_extract_dev", "slam_vmap_read", "slam_vmap_read_sums", "slam_vmap_info",
 ]
 
 
@@ -346,6 +352,8 @@ def lib():
     L.slam_kf_set_params.argtypes = [_vp, C.POINTER(KfParams)]
     L.slam_kf_add_keyframe.argtypes = [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.slam_kf_add_keyframe_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_int), _vp]
+    L.slam_kf_remove_keyframe.argtypes = [_vp, C.c_int]
+    L.slam_kf_replace_keyframe_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp]
     L.slam_kf_keyframe_info.argtypes = [_vp, C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_long)]
     L.slam_kf_count.argtypes = [_vp]
     L.slam_kf_read_keyframe.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_int)]
@@ -376,6 +384,18 @@ def lib():
     L.slam_csm_read_table.argtypes = [_vp, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4 + [_vp, C.c_size_t]
     L.slam_csm_info.argtypes = [_vp, C.POINTER(CsmParams), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                 C.POINTER(C.c_int)]
+    L.slam_vmap_default_params.argtypes = [C.POINTER(VmapParams)]
+    L.slam_vmap_default_params.restype = None
+    L.slam_vmap_create.argtypes = [C.POINTER(VmapParams), C.POINTER(_vp)]
+    L.slam_vmap_destroy.argtypes = [_vp]
+    L.slam_vmap_destroy.restype = None
+    L.slam_vmap_clear.argtypes = [_vp, _vp]
+    L.slam_vmap_integrate.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_int)]
+    L.slam_vmap_integrate_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_int), _vp]
+    L.slam_vmap_extract_dev.argtypes = [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int), _vp]
+    L.slam_vmap_read.argtypes = [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
+    L.slam_vmap_read_sums.argtypes = [_vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
+    L.slam_vmap_info.argtypes = [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -855,6 +875,105 @@ class CorrelativeMatcher:
             pass
 
 
+def vmap_default_params(**kw):
+    p = VmapParams()
+    lib().slam_vmap_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+class VoxelMap:
+    """The exact sparse voxel map (slam_vmap_*, docs/VOXEL_MAP.md): clouds are integrated in place, each with its own
+    transform; a voxel's centroid is the exact mean of its points in units of 2^-20 m, the same bits in any order."""
+
+    def __init__(self, params=None, **kw):
+        self.params = params or vmap_default_params(**kw)
+        h = _vp()
+        check(lib().slam_vmap_create(C.byref(self.params), C.byref(h)))
+        self.h = h.value
+
+    @staticmethod
+    def _Rt(R, t):
+        if R is None and t is None:
+            return None, None
+        return (np.ascontiguousarray(R, dtype=np.float64).reshape(9), np.ascontiguousarray(t, dtype=np.float64).reshape(3))
+
+    @staticmethod
+    def _box(lo, hi):
+        if lo is None and hi is None:
+            return None, None
+        return np.ascontiguousarray(lo, dtype=np.float32).reshape(2), np.ascontiguousarray(hi, dtype=np.float32).reshape(2)
+
+    def info(self):
+        nv, cap, npts, b = C.c_int64(), C.c_int64(), C.c_int64(), C.c_size_t()
+        check(lib().slam_vmap_info(self.h, C.byref(nv), C.byref(cap), C.byref(npts), C.byref(b)))
+        return dict(n_voxels=nv.value, capacity=cap.value, n_points=npts.value, device_bytes=b.value)
+
+    def clear(self, stream=None):
+        check(lib().slam_vmap_clear(self.h, _sp(stream)))
+
+    def integrate(self, xyz, R=None, t=None):
+        """slam_vmap_integrate, host array [n, >= 3] f32: the number of points dropped."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+        xyz = xyz.reshape(-1, xyz.shape[-1] if xyz.ndim > 1 else 3)
+        R, t = self._Rt(R, t)
+        nd = C.c_int()
+        check(lib().slam_vmap_integrate(self.h, _ptr(xyz), len(xyz), xyz.shape[1], _ptr(R), _ptr(t), C.byref(nd)))
+        return nd.value
+
+    def integrate_dev(self, d_xyz, n, stride=3, R=None, t=None, stream=None):
+        R, t = self._Rt(R, t)
+        nd = C.c_int()
+        check(lib().slam_vmap_integrate_dev(self.h, getattr(d_xyz, "ptr", d_xyz), int(n), int(stride), _ptr(R), _ptr(t), C.byref(nd),
+                                            _sp(stream)))
+        return nd.value
+
+    def extract_dev(self, d_xyz4, cap, lo=None, hi=None, min_count=0, d_count=None, d_key=None, stream=None):
+        """slam_vmap_extract_dev: the number of voxels written; SlamError(E_NOMEM) with .needed set when cap is too small."""
+        lo, hi = self._box(lo, hi)
+        n = C.c_int()
+        rc = lib().slam_vmap_extract_dev(self.h, _ptr(lo), _ptr(hi), int(min_count), getattr(d_xyz4, "ptr", d_xyz4),
+                                         getattr(d_count, "ptr", d_count), getattr(d_key, "ptr", d_key), int(cap), C.byref(n), _sp(stream))
+        if rc != SLAM_OK:
+            e = SlamError(rc, lib().slam_last_error().decode("utf-8", "replace"))
+            e.needed = n.value
+            raise e
+        return n.value
+
+    def read(self, lo=None, hi=None, min_count=0):
+        """slam_vmap_read: (xyz4 [n, 4] f32, count [n] u32, key [n] u64) in ascending key order."""
+        lo, hi = self._box(lo, hi)
+        n = C.c_int()
+        rc = lib().slam_vmap_read(self.h, _ptr(lo), _ptr(hi), int(min_count), None, None, None, 0, C.byref(n))
+        if rc not in (SLAM_OK, E_NOMEM):
+            check(rc)
+        xyz4, count, key = np.zeros((n.value, 4), np.float32), np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint64)
+        if n.value:
+            check(lib().slam_vmap_read(self.h, _ptr(lo), _ptr(hi), int(min_count), _ptr(xyz4), _ptr(count), _ptr(key), n.value, C.byref(n)))
+        return xyz4, count, key
+
+    def read_sums(self):
+        """slam_vmap_read_sums: (sums [n, 3] i64 in units of 2^-20 m, count [n] u32, key [n] u64) of every voxel."""
+        n = self.info()["n_voxels"]
+        sums, count, key = np.zeros((n, 3), np.int64), np.zeros(n, np.uint32), np.zeros(n, np.uint64)
+        got = C.c_int()
+        check(lib().slam_vmap_read_sums(self.h, _ptr(sums), _ptr(count), _ptr(key), n, C.byref(got)))
+        assert got.value == n
+        return sums, count, key
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().slam_vmap_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def grid_default_params(**kw):
     p = GridParams()
     lib().slam_grid_default_params(C.byref(p))
@@ -1071,6 +1190,20 @@ class KeyframeStore:
         check(lib().slam_kf_add_keyframe_dev(self.h, d_xyz.ptr, int(n), int(stride), C.byref(kid), _sp(stream)))
         return kid.value
 
+    def remove_keyframe(self, kid):
+        """Frees keyframe kid; the id is never issued again and every later call that names it raises E_INVALID."""
+        check(lib().slam_kf_remove_keyframe(self.h, int(kid)))
+
+    def replace_keyframe_dev(self, kid, d_xyz, n, stride=3, stream=None):
+        """add_keyframe_dev's filter and lattice into the existing id; a refused cloud leaves the old keyframe."""
+        check(lib().slam_kf_replace_keyframe_dev(self.h, int(kid), getattr(d_xyz, "ptr", d_xyz), int(n), int(stride), _sp(stream)))
+
+    def replace_keyframe(self, kid, xyz):
+        a = np.ascontiguousarray(xyz, dtype=np.float32)
+        a = a.reshape(-1, a.shape[1] if a.ndim == 2 else 3)
+        d = DeviceArray.from_host(a) if a.size else None
+        self.replace_keyframe_dev(kid, d, len(a), a.shape[1])
+
     def info(self, kid):
         v = [C.c_int() for _ in range(4)]
         b = C.c_long()
@@ -1235,6 +1368,89 @@ class GlobalMatcher:
         if self.try_count >= self.MAX_TRIES:
             return self._edge(id_, np.float32(cur_x), np.float32(cur_y), np.float32(cur_yaw), matched=False, start=-1)
         return None
+
+
+class GlobalMapBuilder:
+    """global_matching's map builder (global_generate.cpp:122-232) over VoxelMap and KeyframeStore.register_gicp: the
+    same behaviour as slam_amd::GlobalMapBuilder of include/slam_amd/map_builder.hpp, whose head lists how the names
+    correspond (docs/VOXEL_MAP.md section 5 states the deviations from the reference).  An error of the library raises
+    SlamError here (C++ prints it and rejects the cloud); the scan keyframe is removed on every way out."""
+
+    def __init__(self, leaf=0.30, gate=2.0):
+        # global_generate.cpp:21-29, :84-90: macros and setup_gicp's values there, members here.  The store and the map are made
+        # with the fixed ones (read-only properties below); MAX_SCORE and CROP_DIST are read at every add_cloud
+        self._fixed = dict(LEAF_SIZE=float(leaf), gate=float(gate), MAX_ITERATIONS=100, TRANSFORMATION_EPSILON=1e-6,
+                           FITNESS_EPSILON=1e-6, MAX_DIST=4.0)
+        self.MAX_SCORE, self.CROP_DIST = 1.0, 100.0
+        self.vmap = VoxelMap(leaf=self.LEAF_SIZE)
+        self.store = KeyframeStore(leaf_size=self.LEAF_SIZE, gate=self.gate, transformation_epsilon=self.TRANSFORMATION_EPSILON,
+                                   fitness_epsilon=self.FITNESS_EPSILON)
+        self.store.set_gicp_params(max_iterations=self.MAX_ITERATIONS, transformation_epsilon=self.TRANSFORMATION_EPSILON)
+        self.trans_full = np.eye(4, dtype=np.float32)
+        self.map_id, self.n_clouds, self.n_accepted = -1, 0, 0
+        self.last = None        # the last request's result
+
+    def close(self):
+        self.vmap.close()
+        self.store.close()
+
+    LEAF_SIZE = property(lambda self: self._fixed["LEAF_SIZE"])
+    gate = property(lambda self: self._fixed["gate"])
+    MAX_ITERATIONS = property(lambda self: self._fixed["MAX_ITERATIONS"])
+    TRANSFORMATION_EPSILON = property(lambda self: self._fixed["TRANSFORMATION_EPSILON"])
+    FITNESS_EPSILON = property(lambda self: self._fixed["FITNESS_EPSILON"])
+    MAX_DIST = property(lambda self: self._fixed["MAX_DIST"])    # kept for the name, without effect: the store's gate rules
+
+    def pose(self):
+        """trans_full: the accumulated transform of the last accepted cloud, 4 x 4 f32."""
+        return self.trans_full.copy()
+
+    def crop_box(self):
+        """(lo_xy, hi_xy) of :149-157 as f32: -+CROP_DIST + trans_full(i, 3) in double, rounded once"""
+        c = [float(self.trans_full[0, 3]), float(self.trans_full[1, 3])]
+        return (np.array([-self.CROP_DIST + c[0], -self.CROP_DIST + c[1]], np.float32),
+                np.array([self.CROP_DIST + c[0], self.CROP_DIST + c[1]], np.float32))
+
+    def map(self):
+        """The whole map as GlobalMatcher.set_map takes it: [n, 4] f32 (x, y, z, 0) in key order."""
+        return self.vmap.read()[0]
+
+    def add_cloud(self, xyz):
+        """One scan ([n, >= 3] f32, sensor frame): (accepted, result dict of register_gicp or None for the first cloud)."""
+        a = np.ascontiguousarray(xyz, dtype=np.float32)
+        a = a.reshape(-1, a.shape[1] if a.ndim == 2 else 3)
+        self.n_clouds += 1
+        if self.vmap.info()["n_points"] == 0:      # :63-70: the first cloud is the map
+            self.vmap.integrate(a)
+            self.n_accepted += 1
+            self.last = None
+            return True, None
+        d_scan = DeviceArray.from_host(a)
+        scan = self.store.add_keyframe_dev(d_scan, len(a), a.shape[1])
+        try:
+            lo, hi = self.crop_box()
+            cap = max(self.vmap.info()["n_voxels"], 1)
+            d_map = DeviceArray((cap, 4), np.float32)
+            n_map = self.vmap.extract_dev(d_map, cap, lo=lo, hi=hi)
+            synchronize()
+            if n_map == 0:                         # nothing of the map near the pose: nothing to register against
+                self.last = None
+                return False, None
+            if self.map_id < 0:
+                self.map_id = self.store.add_keyframe_dev(d_map, n_map, 4)
+            else:
+                self.store.replace_keyframe_dev(self.map_id, d_map, n_map, 4)
+            r = self.store.register_gicp([(self.map_id, scan, self.trans_full)])[0]
+            self.last = r
+            if r["fitness_pairs"] <= 0 or not r["converged"] or r["fitness"] > self.MAX_SCORE:      # :182
+                return False, r
+            self.trans_full = np.array(r["transform"], np.float32).reshape(4, 4)
+            T = self.trans_full.astype(np.float64)
+            self.vmap.integrate_dev(d_scan, len(a), a.shape[1], R=T[:3, :3], t=T[:3, 3])
+            self.n_accepted += 1
+            return True, r
+        finally:
+            self.store.remove_keyframe(scan)
 
 
 def kf_gicp_result_dict(r):

@@ -393,6 +393,7 @@ struct Keyframe {
     int32_t *nbr_index = nullptr, *nbr_count = nullptr;
     float   *nbr_dist2 = nullptr;
     int      nbr_k = 0;
+    bool     removed = false; // slam_kf_remove_keyframe: the id stays issued, the memory is gone, every call refuses it
 };
 
 } // namespace
@@ -410,6 +411,8 @@ struct slam_kf {
 
 namespace {
 
+// an id that was issued and not removed
+inline bool     kf_live(const slam_kf *s, int id) { return s && id >= 0 && id < (int)s->kfs.size() && !s->kfs[id].removed; }
 inline double   inv_cell(const slam_kf_params &p) { return 1.0 / ((p.cell_size > 0 ? p.cell_size : p.gate) * kLatticeMargin); }
 inline unsigned blocks(size_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
@@ -429,8 +432,8 @@ int kf_register_batch(slam_kf *s, const char *who, const char *what, void (*kern
     const int nk = (int)s->kfs.size();
     size_t    n_corr = 0;
     for (int e = 0; e < n; ++e) {
-        SLAM_REQUIRE(req[e].from >= 0 && req[e].from < nk && req[e].to >= 0 && req[e].to < nk, SLAM_E_INVALID,
-                     "%s: %s %d names keyframes %d -> %d, the store holds %d", who, what, e, req[e].from, req[e].to, nk);
+        SLAM_REQUIRE(kf_live(s, req[e].from) && kf_live(s, req[e].to), SLAM_E_INVALID,
+                     "%s: %s %d names keyframes %d -> %d, the store holds %d (removed ones are refused)", who, what, e, req[e].from, req[e].to, nk);
         n_corr += (size_t)s->kfs[req[e].to].view.n;
     }
     if (n == 0) return SLAM_OK;

@@ -349,7 +349,7 @@ int slam_kf_add_keyframe(slam_kf_t *s, const float *xyz, int n, int stride, int 
 
 int slam_kf_keyframe_info(slam_kf_t *s, int id, int *n_points, int *n_cells, int *max_cell_points, int *table_slots, long *device_bytes)
 {
-    SLAM_REQUIRE(s && id >= 0 && id < (int)s->kfs.size(), SLAM_E_INVALID, "slam_kf_keyframe_info: no keyframe %d", id);
+    SLAM_REQUIRE(kf_live(s, id), SLAM_E_INVALID, "slam_kf_keyframe_info: no keyframe %d", id);
     const Keyframe &k = s->kfs[id];
     if (n_points) *n_points = k.view.n;
     if (n_cells) *n_cells = k.n_cells;
@@ -361,7 +361,7 @@ int slam_kf_keyframe_info(slam_kf_t *s, int id, int *n_points, int *n_cells, int
 
 int slam_kf_read_keyframe(slam_kf_t *s, int id, float *xyz4, int max_points, int *n_points)
 {
-    SLAM_REQUIRE(s && n_points && id >= 0 && id < (int)s->kfs.size() && max_points >= 0 && (xyz4 || max_points == 0), SLAM_E_INVALID,
+    SLAM_REQUIRE(s && n_points && kf_live(s, id) && max_points >= 0 && (xyz4 || max_points == 0), SLAM_E_INVALID,
                  "slam_kf_read_keyframe: bad arguments");
     const Keyframe &k = s->kfs[id];
     *n_points = k.view.n < max_points ? k.view.n : max_points;
@@ -372,7 +372,7 @@ int slam_kf_read_keyframe(slam_kf_t *s, int id, float *xyz4, int max_points, int
 int slam_kf_nearest_dev(slam_kf_t *s, int id, const float *d_queries, int n, int stride, int strict, int32_t *d_index, float *d_dist2,
                         slam_stream_t stream)
 {
-    SLAM_REQUIRE(s && id >= 0 && id < (int)s->kfs.size() && n >= 0 && stride >= 3 && (n == 0 || (d_queries && d_index && d_dist2)), SLAM_E_INVALID,
+    SLAM_REQUIRE(kf_live(s, id) && n >= 0 && stride >= 3 && (n == 0 || (d_queries && d_index && d_dist2)), SLAM_E_INVALID,
                  "slam_kf_nearest_dev: bad arguments");
     if (n == 0) return SLAM_OK;
     hipLaunchKernelGGL(kf_nearest_kernel, dim3(blocks(n, 256)), dim3(256), 0, as_stream(stream), s->kfs[id].view, inv_cell(s->p),

@@ -457,7 +457,7 @@ int slam_kf_set_gicp_params(slam_kf_t *s, const slam_kf_gicp_params *params)
 
 int slam_kf_compute_covariances(slam_kf_t *s, int id, slam_stream_t stream)
 {
-    SLAM_REQUIRE(s && id >= 0 && id < (int)s->kfs.size(), SLAM_E_INVALID, "slam_kf_compute_covariances: no keyframe %d", id);
+    SLAM_REQUIRE(kf_live(s, id), SLAM_E_INVALID, "slam_kf_compute_covariances: no keyframe %d", id);
     Keyframe &kf = s->kfs[id];
     if (kf.cov6) return SLAM_OK;
     const int    n = kf.view.n, K = s->gp.k_correspondences;
@@ -488,7 +488,7 @@ int slam_kf_compute_covariances(slam_kf_t *s, int id, slam_stream_t stream)
 
 int slam_kf_read_covariances(slam_kf_t *s, int id, double *cov6, int max_points, int *n_points)
 {
-    SLAM_REQUIRE(s && n_points && id >= 0 && id < (int)s->kfs.size() && max_points >= 0 && (cov6 || max_points == 0), SLAM_E_INVALID,
+    SLAM_REQUIRE(s && n_points && kf_live(s, id) && max_points >= 0 && (cov6 || max_points == 0), SLAM_E_INVALID,
                  "slam_kf_read_covariances: bad arguments");
     const Keyframe &k = s->kfs[id];
     SLAM_REQUIRE(k.cov6, SLAM_E_INVALID, "slam_kf_read_covariances: keyframe %d has no covariances yet", id);
@@ -499,7 +499,7 @@ int slam_kf_read_covariances(slam_kf_t *s, int id, double *cov6, int max_points,
 
 int slam_kf_read_neighbours(slam_kf_t *s, int id, int32_t *index, float *dist2, int32_t *count, int max_points, int *k)
 {
-    SLAM_REQUIRE(s && k && id >= 0 && id < (int)s->kfs.size() && max_points >= 0, SLAM_E_INVALID, "slam_kf_read_neighbours: bad arguments");
+    SLAM_REQUIRE(s && k && kf_live(s, id) && max_points >= 0, SLAM_E_INVALID, "slam_kf_read_neighbours: bad arguments");
     const Keyframe &kf = s->kfs[id];
     SLAM_REQUIRE(kf.cov6, SLAM_E_INVALID, "slam_kf_read_neighbours: keyframe %d has no covariances yet", id);
     *k = kf.nbr_k;

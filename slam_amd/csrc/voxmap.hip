@@ -1,0 +1,472 @@
+// voxmap.hip -- the exact sparse voxel map (slam_vmap_*): the growing prior map of the reference's
+//   global_generate.cpp:122-232 (voxel-filter scan and map, GICP, append the moved scan)
+// kept as integer sums per voxel instead of a cloud that is filtered again every round.  The contract is
+// docs/VOXEL_MAP.md section 1 (restated above the declarations in slam_mi355x.h); the scalar restatement the tests hold
+// this against bit for bit is tests/cpp/vmap_oracle.cpp.
+//
+// The table is open addressing with linear probing over a power-of-two number of slots in HBM, as five arrays in one block:
+// key (u64, all ones = empty), the three sums (i64, units of 2^-20 m) and the count (u32).
+//   integrate  one lane per point: transform, cell, key; the lane finds its key or claims an empty slot with a 64-bit
+//              atomicCAS, then adds with three 64-bit integer atomicAdds and one 32-bit.  Nothing waits for another lane: a
+//              slot's sums are zero from the moment the table is cleared, so an add may land before or after any other.
+//              Integer adds commute, so no order of lanes shows in the sums; where a key sits does not show in any result
+//              because extraction sorts by key.
+//   rehash     one lane per old slot: claims the key's slot in the larger table and stores sums and count (keys are
+//              distinct, so plain stores).  Only ever launched by the host between integrate launches.
+//   extract    flag (count, box) per slot -> rocprim select of the slot indices -> gather their keys -> rocprim radix sort
+//              of (key, slot) -> one lane per voxel writes centroid, count and key.
+// The hash is the 64-bit finaliser of MurmurHash3 (fmix64: two multiply-xorshift rounds), masked to the table: neighbouring
+// cells differ in the low bits of one 21-bit field, and fmix64 spreads any one-bit difference over the whole word.
+// The probe loop ends after `capacity` slots and then raises the handle's error word; the host keeps the load at one half
+// or below (n_voxels + n <= capacity / 2 before a launch of n points), so that never happens.
+#include <cmath>
+#include <cstring>
+#include <new>
+
+#include <rocprim/rocprim.hpp>
+
+#include "device_mem.hpp"
+
+using namespace slam;
+
+namespace {
+
+constexpr uint64_t kEmpty = ~0ull;
+constexpr int64_t  kMaxSlots = 1ll << 31; // slot indices travel as u32 through select and sort
+constexpr double   kFix = 1048576.0;      // 2^20: sums are in units of 2^-20 m
+constexpr int      kCellLimit = 1 << 20;
+constexpr float    kCoordLimit = 4194304.0f; // 2^22
+
+struct Table {
+    uint64_t           *key;
+    unsigned long long *sum[3];
+    uint32_t           *count;
+    uint64_t            mask; // slots - 1
+};
+struct Transform {
+    double r[9], t[3];
+    int    on;
+};
+struct Box {
+    float lo[2], hi[2];
+    int   on;
+};
+// the handle's counters on the device
+enum { kClaimed = 0, kDropped = 1, kError = 2, kSelected = 3, kCounters = 4 };
+
+__device__ __forceinline__ uint64_t fmix64(uint64_t k)
+{
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return k;
+}
+
+// The slot that holds `key`, claimed if nobody had; -1 when `capacity` probes found neither (the error word's case).
+__device__ __forceinline__ long long find_or_claim(const Table &T, uint64_t key, uint32_t *claimed)
+{
+    uint64_t h = fmix64(key) & T.mask;
+    for (uint64_t probe = 0; probe <= T.mask; ++probe, h = (h + 1) & T.mask) {
+        uint64_t cur = __hip_atomic_load(&T.key[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == kEmpty) {
+            cur = atomicCAS((unsigned long long *)&T.key[h], (unsigned long long)kEmpty, (unsigned long long)key);
+            if (cur == kEmpty) {
+                atomicAdd(claimed, 1u);
+                return (long long)h;
+            }
+        }
+        if (cur == key) return (long long)h;
+    }
+    return -1;
+}
+
+__global__ __launch_bounds__(256) void vmap_integrate_kernel(const float *xyz, int n, int stride, Transform X, double leaf, Table T,
+                                                             uint32_t *ctr)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; // n may be close to 2^31
+    if (i >= (size_t)n) return;
+    const float *p = xyz + i * stride;
+    float        q[3] = {p[0], p[1], p[2]};
+    if (X.on) {
+        const double px = q[0], py = q[1], pz = q[2];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            q[k] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(X.r[3 * k], px), __dmul_rn(X.r[3 * k + 1], py)), __dmul_rn(X.r[3 * k + 2], pz)),
+                                    X.t[k]);
+    }
+    uint64_t  key = 0;
+    long long f[3];
+    bool      keep = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float v = q[k];
+        const double c = floor((double)v / leaf);
+        if (!(fabsf(v) < kCoordLimit) || !(fabs(c) < (double)kCellLimit)) { // written so that a NaN fails both tests
+            keep = false;
+            continue;
+        }
+        key |= (uint64_t)((int)c + kCellLimit) << (21 * k);
+        f[k] = (long long)rint((double)v * kFix);
+    }
+    if (!keep) {
+        atomicAdd(&ctr[kDropped], 1u);
+        return;
+    }
+    const long long h = find_or_claim(T, key, &ctr[kClaimed]);
+    if (h < 0) {
+        atomicExch(&ctr[kError], 1u);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) atomicAdd(&T.sum[k][h], (unsigned long long)f[k]);
+    atomicAdd(&T.count[h], 1u);
+}
+
+__global__ __launch_bounds__(256) void vmap_rehash_kernel(Table from, Table to, uint32_t *ctr)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > from.mask) return;
+    const uint64_t key = from.key[i];
+    if (key == kEmpty) return;
+    const long long h = find_or_claim(to, key, ctr + kClaimed);
+    if (h < 0) {
+        atomicExch(&ctr[kError], 1u);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) to.sum[k][h] = from.sum[k][i];
+    to.count[h] = from.count[i];
+}
+
+__device__ __forceinline__ float centroid(unsigned long long s, uint32_t count)
+{
+    return (float)(((double)(long long)s / (double)count) * (1.0 / kFix));
+}
+
+__global__ __launch_bounds__(256) void vmap_flag_kernel(Table T, Box box, uint32_t min_count, uint8_t *flag)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > T.mask) return;
+    bool           keep = false;
+    const uint32_t c = T.count[i];
+    if (T.key[i] != kEmpty && c >= min_count && c > 0) {
+        keep = true;
+        if (box.on) {
+            const float x = centroid(T.sum[0][i], c), y = centroid(T.sum[1][i], c);
+            keep = box.lo[0] <= x && x <= box.hi[0] && box.lo[1] <= y && y <= box.hi[1];
+        }
+    }
+    flag[i] = keep ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void vmap_gather_keys_kernel(Table T, const uint32_t *slot, int n, uint64_t *key)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (size_t)n) key[i] = T.key[slot[i]];
+}
+
+__global__ __launch_bounds__(256) void vmap_write_kernel(Table T, const uint32_t *slot, const uint64_t *key, int n, float *xyz4, uint32_t *count,
+                                                         uint64_t *key_out, int64_t *sums)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)n) return;
+    const uint32_t s = slot[i], c = T.count[s];
+    if (sums)
+        for (int k = 0; k < 3; ++k) sums[3 * i + k] = (int64_t)T.sum[k][s];
+    if (xyz4) {
+        float4 o;
+        o.x = centroid(T.sum[0][s], c), o.y = centroid(T.sum[1][s], c), o.z = centroid(T.sum[2][s], c), o.w = 0.0f;
+        reinterpret_cast<float4 *>(xyz4)[i] = o;
+    }
+    if (count) count[i] = c;
+    if (key_out) key_out[i] = key[i];
+}
+
+inline unsigned blocks_for(uint64_t n) { return (unsigned)((n + 255) / 256); }
+constexpr size_t kSlotBytes = sizeof(uint64_t) + 3 * sizeof(long long) + sizeof(uint32_t);
+
+} // namespace
+
+struct slam_vmap {
+    slam_vmap_params P;
+    int64_t          capacity = 0, n_voxels = 0, n_points = 0;
+    DevMem           table, ctr;
+    // extraction: flags and selected slots (capacity each), then keys and slots before and after the sort, rocprim's scratch
+    DevMem flag, sel, keys_in, keys_out, sel_sorted, tmp;
+    // staging of the host forms
+    DevMem stage_in, stage_out;
+
+    static Table view(const DevMem &b, int64_t cap)
+    {
+        Table    T;
+        uint8_t *p = b.as<uint8_t>();
+        T.key = reinterpret_cast<uint64_t *>(p);
+        for (int k = 0; k < 3; ++k) T.sum[k] = reinterpret_cast<unsigned long long *>(p + (size_t)cap * 8 * (k + 1));
+        T.count = reinterpret_cast<uint32_t *>(p + (size_t)cap * 32);
+        T.mask = (uint64_t)cap - 1;
+        return T;
+    }
+    Table view() const { return view(table, capacity); }
+};
+
+namespace {
+
+// an empty table of `cap` slots in `b`, enqueued on st
+int new_table(DevMem &b, int64_t cap, hipStream_t st)
+{
+    SLAM_REQUIRE(cap <= kMaxSlots, SLAM_E_NOMEM, "slam_vmap: a table of %lld slots is more than the %lld a map may have", (long long)cap,
+                 (long long)kMaxSlots);
+    SLAM_TRY(b.alloc((size_t)cap * kSlotBytes));
+    SLAM_HIP(hipMemsetAsync(b.p, 0xff, (size_t)cap * 8, st));
+    SLAM_HIP(hipMemsetAsync(b.as<uint8_t>() + (size_t)cap * 8, 0, (size_t)cap * (kSlotBytes - 8), st));
+    return SLAM_OK;
+}
+
+int64_t pow2_at_least(int64_t v)
+{
+    int64_t c = 64;
+    while (c < v) c <<= 1;
+    return c;
+}
+
+// Room for n more points under the load rule; waits for st when it grows (the old table is freed afterwards).
+int make_room(slam_vmap *m, int64_t n, hipStream_t st)
+{
+    if (m->n_voxels + n <= m->capacity / 2) return SLAM_OK;
+    const int64_t cap = pow2_at_least(2 * (m->n_voxels + n));
+    DevMem        nt;
+    SLAM_TRY(new_table(nt, cap, st));
+    SLAM_HIP(hipMemsetAsync(m->ctr.p, 0, kCounters * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(vmap_rehash_kernel, dim3(blocks_for((uint64_t)m->capacity)), dim3(256), 0, st, m->view(), slam_vmap::view(nt, cap),
+                       m->ctr.as<uint32_t>());
+    SLAM_HIP(hipGetLastError());
+    uint32_t *h = static_cast<uint32_t *>(pinned_scratch(kCounters * sizeof(uint32_t)));
+    SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
+    SLAM_HIP(hipMemcpyAsync(h, m->ctr.p, kCounters * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SLAM_HIP(hipStreamSynchronize(st));
+    SLAM_REQUIRE(!h[kError] && (int64_t)h[kClaimed] == m->n_voxels, SLAM_E_HIP, "slam_vmap: the rehash moved %u of %lld voxels (error word %u)",
+                 h[kClaimed], (long long)m->n_voxels, h[kError]);
+    m->table = std::move(nt);
+    m->capacity = cap;
+    return SLAM_OK;
+}
+
+// The qualifying slots into m->sel and their number into *n: waits for st once.
+int select_slots(slam_vmap *m, const float lo[2], const float hi[2], int min_count, hipStream_t st, int64_t *n)
+{
+    const uint64_t cap = (uint64_t)m->capacity;
+    SLAM_TRY(m->flag.reserve(cap));
+    SLAM_TRY(m->sel.reserve(cap * sizeof(uint32_t)));
+    Box box{};
+    box.on = lo != nullptr;
+    if (lo) box.lo[0] = lo[0], box.lo[1] = lo[1], box.hi[0] = hi[0], box.hi[1] = hi[1];
+    uint32_t *d_n = m->ctr.as<uint32_t>() + kSelected;
+    hipLaunchKernelGGL(vmap_flag_kernel, dim3(blocks_for(cap)), dim3(256), 0, st, m->view(), box, (uint32_t)min_count, m->flag.as<uint8_t>());
+    SLAM_HIP(hipGetLastError());
+    size_t tb = 0;
+    SLAM_HIP(rocprim::select(nullptr, tb, rocprim::counting_iterator<uint32_t>(0), m->flag.as<uint8_t>(), m->sel.as<uint32_t>(), d_n, (size_t)cap, st));
+    SLAM_TRY(m->tmp.reserve(tb + 16));
+    tb = m->tmp.cap;
+    SLAM_HIP(rocprim::select(m->tmp.p, tb, rocprim::counting_iterator<uint32_t>(0), m->flag.as<uint8_t>(), m->sel.as<uint32_t>(), d_n, (size_t)cap, st));
+    uint32_t *h = static_cast<uint32_t *>(pinned_scratch(sizeof(uint32_t)));
+    SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
+    SLAM_HIP(hipMemcpyAsync(h, d_n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SLAM_HIP(hipStreamSynchronize(st));
+    *n = (int64_t)*h;
+    return SLAM_OK;
+}
+
+// The n selected slots in key order into the caller's device arrays: asynchronous.
+int sort_and_write(slam_vmap *m, int n, float *d_xyz4, uint32_t *d_count, uint64_t *d_key, hipStream_t st, int64_t *d_sums = nullptr)
+{
+    if (n == 0) return SLAM_OK;
+    SLAM_TRY(reserve_quarter(m->keys_in, (size_t)n * sizeof(uint64_t)));
+    SLAM_TRY(reserve_quarter(m->keys_out, (size_t)n * sizeof(uint64_t)));
+    SLAM_TRY(reserve_quarter(m->sel_sorted, (size_t)n * sizeof(uint32_t)));
+    hipLaunchKernelGGL(vmap_gather_keys_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, st, m->view(), m->sel.as<uint32_t>(), n,
+                       m->keys_in.as<uint64_t>());
+    SLAM_HIP(hipGetLastError());
+    size_t tb = 0;
+    SLAM_HIP(rocprim::radix_sort_pairs(nullptr, tb, m->keys_in.as<uint64_t>(), m->keys_out.as<uint64_t>(), m->sel.as<uint32_t>(),
+                                       m->sel_sorted.as<uint32_t>(), (size_t)n, 0, 63, st));
+    if (tb + 16 > m->tmp.cap) {
+        SLAM_HIP(hipStreamSynchronize(st)); // hipFree waits anyway; the error, if any, is this stream's
+        SLAM_TRY(m->tmp.reserve(tb + 16));
+    }
+    tb = m->tmp.cap;
+    SLAM_HIP(rocprim::radix_sort_pairs(m->tmp.p, tb, m->keys_in.as<uint64_t>(), m->keys_out.as<uint64_t>(), m->sel.as<uint32_t>(),
+                                       m->sel_sorted.as<uint32_t>(), (size_t)n, 0, 63, st));
+    hipLaunchKernelGGL(vmap_write_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, st, m->view(), m->sel_sorted.as<uint32_t>(),
+                       m->keys_out.as<uint64_t>(), n, d_xyz4, d_count, d_key, d_sums);
+    SLAM_HIP(hipGetLastError());
+    return SLAM_OK;
+}
+
+int check_extract(const char *who, slam_vmap *m, const float *lo, const float *hi, int min_count, int cap, int *n_out)
+{
+    SLAM_REQUIRE(m && n_out && cap >= 0 && min_count >= 0 && (lo == nullptr) == (hi == nullptr), SLAM_E_INVALID,
+                 "%s: a map, n_out, cap >= 0, min_count >= 0, and lo_xy and hi_xy both or neither", who);
+    return SLAM_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void slam_vmap_default_params(slam_vmap_params *p)
+{
+    if (!p) return;
+    p->leaf = 0.30; // global_generate.cpp:26
+    p->initial_capacity = 65536;
+}
+
+int slam_vmap_create(const slam_vmap_params *params, slam_vmap_t **out)
+{
+    SLAM_REQUIRE(out, SLAM_E_INVALID, "slam_vmap_create: out is NULL");
+    slam_vmap_params p;
+    slam_vmap_default_params(&p);
+    if (params) p = *params;
+    SLAM_REQUIRE(p.leaf > 0 && std::isfinite(p.leaf) && p.initial_capacity >= 0 && p.initial_capacity <= (1 << 30), SLAM_E_INVALID,
+                 "slam_vmap_create: leaf must be positive and finite, initial_capacity lie in 0 .. 2^30");
+    SLAM_TRY(require_device());
+    slam_vmap *m = new (std::nothrow) slam_vmap();
+    SLAM_REQUIRE(m, SLAM_E_NOMEM, "slam_vmap_create: out of host memory");
+    m->P = p;
+    m->capacity = pow2_at_least(p.initial_capacity);
+    m->P.initial_capacity = (int)m->capacity;
+    int rc = m->ctr.alloc(kCounters * sizeof(uint32_t));
+    if (rc == SLAM_OK) rc = new_table(m->table, m->capacity, nullptr);
+    if (rc == SLAM_OK && hipStreamSynchronize(nullptr) != hipSuccess) {
+        set_error("slam_vmap_create: clearing the table failed");
+        rc = SLAM_E_HIP;
+    }
+    if (rc != SLAM_OK) {
+        delete m;
+        return rc;
+    }
+    *out = m;
+    return SLAM_OK;
+}
+
+void slam_vmap_destroy(slam_vmap_t *m)
+{
+    if (!m) return;
+    (void)hipDeviceSynchronize();
+    delete m;
+}
+
+int slam_vmap_clear(slam_vmap_t *m, slam_stream_t stream)
+{
+    SLAM_REQUIRE(m, SLAM_E_INVALID, "slam_vmap_clear: map is NULL");
+    hipStream_t st = as_stream(stream);
+    SLAM_HIP(hipMemsetAsync(m->table.p, 0xff, (size_t)m->capacity * 8, st));
+    SLAM_HIP(hipMemsetAsync(m->table.as<uint8_t>() + (size_t)m->capacity * 8, 0, (size_t)m->capacity * (kSlotBytes - 8), st));
+    m->n_voxels = m->n_points = 0;
+    return SLAM_OK;
+}
+
+int slam_vmap_integrate_dev(slam_vmap_t *m, const float *d_xyz, int n, int stride, const double R[9], const double t[3], int *n_dropped,
+                            slam_stream_t stream)
+{
+    SLAM_REQUIRE(m && n >= 0 && stride >= 3 && (d_xyz || n == 0) && (R == nullptr) == (t == nullptr), SLAM_E_INVALID,
+                 "slam_vmap_integrate_dev: a map, n >= 0, stride >= 3, points, and R and t both or neither");
+    if (n_dropped) *n_dropped = 0;
+    if (n == 0) return SLAM_OK;
+    hipStream_t st = as_stream(stream);
+    SLAM_TRY(make_room(m, n, st));
+    Transform X{};
+    X.on = R != nullptr;
+    if (R) {
+        for (int k = 0; k < 9; ++k) X.r[k] = R[k];
+        for (int k = 0; k < 3; ++k) X.t[k] = t[k];
+    }
+    uint32_t *h = static_cast<uint32_t *>(pinned_scratch(kCounters * sizeof(uint32_t)));
+    SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
+    SLAM_HIP(hipMemsetAsync(m->ctr.p, 0, kCounters * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(vmap_integrate_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, st, d_xyz, n, stride, X, m->P.leaf, m->view(),
+                       m->ctr.as<uint32_t>());
+    SLAM_HIP(hipGetLastError());
+    SLAM_HIP(hipMemcpyAsync(h, m->ctr.p, kCounters * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SLAM_HIP(hipStreamSynchronize(st));
+    m->n_voxels += h[kClaimed];
+    m->n_points += (int64_t)n - h[kDropped];
+    if (n_dropped) *n_dropped = (int)h[kDropped];
+    SLAM_REQUIRE(!h[kError], SLAM_E_HIP, "slam_vmap_integrate: a probe ran through all %lld slots (%lld voxels): points were lost",
+                 (long long)m->capacity, (long long)m->n_voxels);
+    return SLAM_OK;
+}
+
+int slam_vmap_integrate(slam_vmap_t *m, const float *xyz, int n, int stride, const double R[9], const double t[3], int *n_dropped)
+{
+    SLAM_REQUIRE(m && n >= 0 && stride >= 3 && (xyz || n == 0) && (R == nullptr) == (t == nullptr), SLAM_E_INVALID,
+                 "slam_vmap_integrate: a map, n >= 0, stride >= 3, points, and R and t both or neither");
+    if (n_dropped) *n_dropped = 0;
+    if (n == 0) return SLAM_OK;
+    const size_t bytes = (size_t)n * stride * sizeof(float);
+    SLAM_TRY(reserve_quarter(m->stage_in, bytes));
+    SLAM_HIP(hipMemcpy(m->stage_in.p, xyz, bytes, hipMemcpyHostToDevice));
+    return slam_vmap_integrate_dev(m, m->stage_in.as<float>(), n, stride, R, t, n_dropped, nullptr);
+}
+
+int slam_vmap_extract_dev(slam_vmap_t *m, const float lo_xy[2], const float hi_xy[2], int min_count, float *d_xyz4, uint32_t *d_count,
+                          uint64_t *d_key, int cap, int *n_out, slam_stream_t stream)
+{
+    SLAM_TRY(check_extract("slam_vmap_extract_dev", m, lo_xy, hi_xy, min_count, cap, n_out));
+    hipStream_t st = as_stream(stream);
+    int64_t     n = 0;
+    SLAM_TRY(select_slots(m, lo_xy, hi_xy, min_count, st, &n));
+    *n_out = (int)n;
+    SLAM_REQUIRE(n <= cap, SLAM_E_NOMEM, "slam_vmap_extract_dev: %lld voxels, room for %d", (long long)n, cap);
+    return sort_and_write(m, (int)n, d_xyz4, d_count, d_key, st);
+}
+
+static int read_host(const char *who, slam_vmap_t *m, const float lo_xy[2], const float hi_xy[2], int min_count, float *xyz4, uint32_t *count,
+                     uint64_t *key, int64_t *sums, int cap, int *n_out)
+{
+    SLAM_TRY(check_extract(who, m, lo_xy, hi_xy, min_count, cap, n_out));
+    int64_t n = 0;
+    SLAM_TRY(select_slots(m, lo_xy, hi_xy, min_count, nullptr, &n));
+    *n_out = (int)n;
+    SLAM_REQUIRE(n <= cap, SLAM_E_NOMEM, "%s: %lld voxels, room for %d", who, (long long)n, cap);
+    if (n == 0) return SLAM_OK;
+    const size_t N = (size_t)n;
+    SLAM_TRY(reserve_quarter(m->stage_out, N * 52)); // keys, sums, then centroids, then counts: each aligned to its type
+    uint64_t *d_key = m->stage_out.as<uint64_t>();
+    int64_t  *d_sums = reinterpret_cast<int64_t *>(d_key + N);
+    float    *d_xyz4 = reinterpret_cast<float *>(d_sums + 3 * N);
+    uint32_t *d_count = reinterpret_cast<uint32_t *>(d_xyz4 + 4 * N);
+    SLAM_TRY(sort_and_write(m, (int)n, xyz4 ? d_xyz4 : nullptr, count ? d_count : nullptr, key ? d_key : nullptr, nullptr, sums ? d_sums : nullptr));
+    if (xyz4) SLAM_HIP(hipMemcpy(xyz4, d_xyz4, N * 16, hipMemcpyDeviceToHost));
+    if (count) SLAM_HIP(hipMemcpy(count, d_count, N * 4, hipMemcpyDeviceToHost));
+    if (key) SLAM_HIP(hipMemcpy(key, d_key, N * 8, hipMemcpyDeviceToHost));
+    if (sums) SLAM_HIP(hipMemcpy(sums, d_sums, N * 24, hipMemcpyDeviceToHost));
+    SLAM_HIP(hipStreamSynchronize(nullptr));
+    return SLAM_OK;
+}
+
+int slam_vmap_read(slam_vmap_t *m, const float lo_xy[2], const float hi_xy[2], int min_count, float *xyz4, uint32_t *count, uint64_t *key,
+                   int cap, int *n_out)
+{
+    return read_host("slam_vmap_read", m, lo_xy, hi_xy, min_count, xyz4, count, key, nullptr, cap, n_out);
+}
+
+int slam_vmap_read_sums(slam_vmap_t *m, int64_t *sums, uint32_t *count, uint64_t *key, int cap, int *n_out)
+{
+    return read_host("slam_vmap_read_sums", m, nullptr, nullptr, 0, nullptr, count, key, sums, cap, n_out);
+}
+
+int slam_vmap_info(slam_vmap_t *m, int64_t *n_voxels, int64_t *capacity, int64_t *n_points, size_t *device_bytes)
+{
+    SLAM_REQUIRE(m, SLAM_E_INVALID, "slam_vmap_info: map is NULL");
+    if (n_voxels) *n_voxels = m->n_voxels;
+    if (capacity) *capacity = m->capacity;
+    if (n_points) *n_points = m->n_points;
+    if (device_bytes)
+        *device_bytes = m->table.cap + m->ctr.cap + m->flag.cap + m->sel.cap + m->keys_in.cap + m->keys_out.cap + m->sel_sorted.cap + m->tmp.cap +
+                        m->stage_in.cap + m->stage_out.cap;
+    return SLAM_OK;
+}
+
+} // extern "C"
