@@ -1,8 +1,10 @@
 """The device-resident chain (slam_ccicp_scene_dev, slam_ccicp_height_pose_dev) is the stepwise entry points without
 their host round trips: ground segmentation -> select -> classify -> voxel filter / bin order -> crop + split + cap,
 every count left on the device.  Same clouds, same bytes; and a registration run straight from its outputs (the host
-never learns the cloud's size) equals one run from host arrays.  The stepwise entry points are what tests/test_ccicp.py
-and tests/test_gseg.py hold against the oracle."""
+never learns the cloud's size) equals one run from host arrays.  Both sides of these comparisons run the same one-launch
+compaction, so a fault of it can cancel here: tests/test_gpu_ccicp_edges.py holds the chain's entry points and the stepwise
+ones to numpy and the oracle at their edges (block sizes, the look-back's second round, caps that bite), tests/test_ccicp.py
+and tests/test_gseg.py the stepwise entry points to the oracle at the workload's sizes."""
 import ctypes as C
 
 import numpy as np
