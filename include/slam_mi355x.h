@@ -557,8 +557,10 @@ int slam_ccicp_height_dev(slam_ccicp_t *h, const float *d_ground, int n, int str
  *   d_scan   out: int32[3] = {0, n_ga + n_nga, n_ga}: d_scan_off = d_scan, d_scan_nga = d_scan + 2 of a
  *            slam_icp_fit_batch_dev call with n_scans = 1 that registers the cloud without the host knowing its size
  *   d_ground out, nullable: the ground cloud as x,y,z,0 records (room for n)
- *   d_counts out: int32[4] = {obstacle points, ground points, points after the filter, 1 if the voxel lattice did not
- *            fit the chain's accumulator (2 M voxels; the stepwise entry point takes larger extents)}
+ *   d_counts out: int32[4] = {obstacle points, ground points, points after the filter, error bits}.  Bit 1: the voxel lattice did
+ *            not fit the chain's accumulator (2 M voxels; the stepwise entry point takes larger extents).  Bit 4: a block of a
+ *            compaction gave up waiting for the blocks before it (a safeguard against a hang, seconds long): d_pts and d_scan are
+ *            not valid.  The stepwise entry points return SLAM_E_HIP for the same.
  * Nothing is read back and nothing waits: the caller reads d_counts when it needs them. */
 int slam_ccicp_scene_dev(slam_ccicp_t *h, slam_gseg_t *seg, const float *d_xyz, int n, int stride, int voxel, int crop,
                          double cur_x, double cur_y, double crop_dist, int cap, double *d_pts, int32_t *d_scan,

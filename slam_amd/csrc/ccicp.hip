@@ -57,16 +57,14 @@ __host__ __device__ inline float unorder_f32(unsigned u)
 
 __device__ inline bool finite3(const float *p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
 
-// getMinMax3D over finite points: wave reduction, one atomic per wavefront and bound
-// `n` is the launch's bound; where the number of points is only known on the device (the chain of slam_ccicp_scene_dev)
+// `n` is a launch's bound; where the number of points is only known on the device (the chain of slam_ccicp_scene_dev)
 // d_n holds it and n is the capacity the grid was sized for
 __device__ inline int bound(int n, const int *d_n) { return d_n ? min(*d_n, n) : n; }
 
-__global__ __launch_bounds__(256) void minmax_kernel(const float *xyz, const unsigned char *flag, int n, int stride,
-                                                     unsigned *mm /*[6]*/, const int *d_n = nullptr)
+// getMinMax3D over finite points: wave reduction, one atomic per wavefront and bound
+__global__ __launch_bounds__(256) void minmax_kernel(const float *xyz, const unsigned char *flag, int n, int stride, unsigned *mm /*[6]*/)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    n = bound(n, d_n);
     unsigned  lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
     if (i < n) {
         const float *p = xyz + (size_t)i * stride;
@@ -105,28 +103,63 @@ __device__ inline long long voxel_of(const VoxelGridView &g, const float *p)
     return (long long)i + (long long)j * g.div_b[0] + (long long)k * g.div_b[0] * g.div_b[1];
 }
 
+// the voxel lattice from the extent, on the device (slam_ccicp_voxel_downsample_dev's host code, PCL voxel_grid.hpp); *overflow
+// when it does not fit the accumulator (n_vox = 0 then: nothing is accumulated)
+__device__ inline VoxelGridView voxel_geometry(const unsigned *mm, float leaf_x, float leaf_y, float leaf_z, long long capacity, bool *overflow)
+{
+    VoxelGridView v;
+    const float   leaf[3] = {leaf_x, leaf_y, leaf_z};
+    long long     nv = 1;
+    bool          bad = mm[0] == 0xffffffffu; // no finite point
+    for (int d = 0; d < 3; ++d) {
+        v.inv[d] = 1.0f / leaf[d];
+        const double lo = floor((double)(unorder_f32(mm[d]) * v.inv[d]));
+        const double hi = floor((double)(unorder_f32(mm[3 + d]) * v.inv[d]));
+        if (bad || !(fabs(lo) < 1e9) || !(hi - lo + 1.0 <= (double)capacity)) {
+            bad = true;
+            v.min_b[d] = 0;
+            v.div_b[d] = 0;
+            continue;
+        }
+        v.min_b[d] = (int)lo;
+        v.div_b[d] = (int)(hi - lo) + 1;
+        nv *= v.div_b[d];
+        if (nv <= 0 || nv > capacity) bad = true;
+    }
+    v.n_vox = bad ? 0 : nv;
+    *overflow = bad && mm[0] != 0xffffffffu;
+    return v;
+}
+
+// Where the lattice of an accumulation comes from: the launch's argument (mm null), or the extent the classification left on the
+// device (the chain of slam_ccicp_scene_dev: the point count lies there too)
+struct DeviceLattice {
+    const unsigned *mm;  // [6] ordered floats
+    const int      *n;   // points in the cloud
+    VoxelGridView  *g;   // out: the lattice, for the compaction behind the accumulation
+    int            *err; // |= 1 where the lattice does not fit
+    float3          leaf;
+    long long       capacity;
+};
+
 // Points of a cloud come ring by ring, azimuth by azimuth: near the sensor, where the voxels are fullest, adjacent
 // lanes fall into the same voxel.  Runs of equal voxels in adjacent lanes are added up inside the wavefront (a
 // segmented scan over the run heads) and the run's last lane issues the atomics: integer sums, so the result does not
 // depend on who adds -- and the hot voxels see a fraction of the same-address atomics (80 -> 35 us per 70 k-point cloud).
-__device__ inline VoxelGridView voxel_geometry(const unsigned *mm, float leaf_x, float leaf_y, float leaf_z, long long capacity, bool *overflow);
-__global__ __launch_bounds__(256) void voxel_accumulate_kernel(VoxelGridView g, const float *xyz, const unsigned char *flag,
-                                                               int n, int stride, Voxel *vox, VoxelGridView *d_g = nullptr,
-                                                               const int *d_n = nullptr, const unsigned *d_mm = nullptr,
-                                                               float3 leaf = make_float3(0.f, 0.f, 0.f), long long capacity = 0, int *d_err = nullptr)
+__global__ __launch_bounds__(256) void voxel_accumulate_kernel(VoxelGridView g, DeviceLattice dl, const float *xyz, const unsigned char *flag,
+                                                               int n, int stride, Voxel *vox)
 {
     const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
-    if (d_g && !d_mm) g = *d_g; // the lattice worked out on the device (voxel_geometry_kernel)
-    if (d_mm) {
-        // ... or here, by every block for itself from the extent the classification left (the chain of slam_ccicp_scene_dev: one
-        // launch less); block 0 leaves it for the compaction behind this kernel
+    if (dl.mm) {
+        // every block works the lattice out for itself (one launch less than a kernel of one thread); block 0 leaves it for the
+        // compaction behind this kernel
         __shared__ VoxelGridView gs;
         if (threadIdx.x == 0) {
             bool overflow = false;
-            gs = voxel_geometry(d_mm, leaf.x, leaf.y, leaf.z, capacity, &overflow);
+            gs = voxel_geometry(dl.mm, dl.leaf.x, dl.leaf.y, dl.leaf.z, dl.capacity, &overflow);
             if (blockIdx.x == 0) {
-                *d_g = gs;
-                if (overflow) atomicOr(d_err, 1);
+                *dl.g = gs;
+                if (overflow) atomicOr(dl.err, 1);
             }
         }
         __syncthreads();
@@ -134,7 +167,7 @@ __global__ __launch_bounds__(256) void voxel_accumulate_kernel(VoxelGridView g, 
     }
     long long          key = -1; // no contribution
     unsigned long long sx = 0, sy = 0, sz = 0, cf = 0; // cf: count in the high word, ground_adj count in the low (Voxel::sflag, ::count)
-    if (i < bound(n, d_n)) {
+    if (i < bound(n, dl.n)) {
         const float *p = xyz + (size_t)i * stride;
         if (finite3(p) && !(flag && flag[i] == 255)) {
             const long long v = voxel_of(g, p);
@@ -236,58 +269,98 @@ struct Xyz4Emit {
     }
 };
 
-// crop (pcl::PassThrough x then y) + class predicate of the split
-struct SplitPred {
+// doICPMatch's marshalling as ONE pass: the crop (pcl::PassThrough x then y) and the class of a point that survives it (0 = GA,
+// 1 = NGA, -1 = cropped)
+struct SplitClass {
     const float *xyzg;
-    int          stride, want_ga;
+    int          stride, crop;
     float        x_lo, x_hi, y_lo, y_hi;
-    int          crop;
-    __device__ bool operator()(long long i) const
+    __device__ int operator()(long long i) const
     {
-        const float *p = xyzg + (size_t)i * stride;
-        if (crop && !(finite3(p) && p[0] >= x_lo && p[0] <= x_hi && p[1] >= y_lo && p[1] <= y_hi)) return false;
-        return (p[3] > 0.5f) == (want_ga != 0); // isGA, PointcloudXYZGD.h:28-30
+        const float *q = xyzg + (size_t)i * stride;
+        if (crop && !(finite3(q) && q[0] >= x_lo && q[0] <= x_hi && q[1] >= y_lo && q[1] <= y_hi)) return -1;
+        return q[3] > 0.5f ? 0 : 1; // isGA, PointcloudXYZGD.h:28-30
     }
 };
-struct SplitEmit {
+struct SplitEmit { // both classes into one array (the chain: its compaction puts class 1 behind class 0)
     const float *xyzg;
     int          stride;
     double      *out;
-    const int   *d_base; // nullable: points already in `out` (capped at `base_cap`): this class is written behind them
-    int          base_cap;
-    __device__ void operator()(long long i, int pos) const
+    __device__ void operator()(long long i, int, int pos) const
     {
-        const float *p = xyzg + (size_t)i * stride;
-        const size_t o = (size_t)pos + (d_base ? (size_t)min(*d_base, base_cap) : 0);
-        out[2 * o] = (double)p[0]; // icpTools.cpp:252, 267: float coordinates widened
-        out[2 * o + 1] = (double)p[1];
+        const float *q = xyzg + (size_t)i * stride;
+        out[2 * (size_t)pos] = (double)q[0]; // icpTools.cpp:252, 267: float coordinates widened
+        out[2 * (size_t)pos + 1] = (double)q[1];
     }
 };
+struct SplitEmitPair { // ... or each class into its own
+    const float *xyzg;
+    int          stride;
+    double      *ga, *nga;
+    __device__ void operator()(long long i, int c, int pos) const { SplitEmit{xyzg, stride, c ? nga : ga}(i, c, pos); }
+};
+
+// doHeightInterpolate's four wheel points (icpTools.cpp:303-332), host or device
+__host__ __device__ inline void wheel_points(const double pose[7], float4 q[4])
+{
+    const double ROBO_HEIGHT = 1.45, wheel = 0.5; // icpTools.cpp:303-305
+    const double x = pose[3], y = pose[4], z = pose[5], w = pose[6];
+    const double d = x * x + y * y + z * z + w * w, s = 2.0 / d;
+    const double xs = x * s, ys = y * s, zs = z * s, wx = w * xs, wy = w * ys, wz = w * zs, xx = x * xs, xy = x * ys,
+                 xz = x * zs, yy = y * ys, yz = y * zs, zz = z * zs;
+    const float M[3][4] = {{(float)(1.0 - (yy + zz)), (float)(xy - wz), (float)(xz + wy), (float)pose[0]},
+                           {(float)(xy + wz), (float)(1.0 - (xx + zz)), (float)(yz - wx), (float)pose[1]},
+                           {(float)(xz - wy), (float)(yz + wx), (float)(1.0 - (xx + yy)), (float)pose[2]}};
+    int k = 0;
+    for (int i = -1; i <= 1; i += 2)
+        for (int j = -1; j <= 1; j += 2, ++k) { // :311-318
+            const float p[3] = {(float)(i * wheel), (float)(j * wheel), (float)(-1.0 * ROBO_HEIGHT)};
+            float       t[3];
+            for (int r = 0; r < 3; ++r) t[r] = M[r][0] * p[0] + M[r][1] * p[1] + M[r][2] * p[2] + M[r][3];
+            q[k] = make_float4(t[0], t[1], t[2], 0.f);
+        }
+}
+
+// ... from a pose held on the device: R (2 x 2), t of the match and z0; the quaternion of the yaw (qz = sin(yaw / 2),
+// qw = cos(yaw / 2)) goes through the same arithmetic as the host form
+__device__ inline void height_pose(const double *R, const double *t, double z0, double roll, double pitch, float4 *q /*[4]*/)
+{
+    const double yaw = atan2(R[2], R[0]); // icpTools.cpp:195-197
+    // tf::createQuaternionFromRPY(roll, pitch, yaw): the matched yaw with the roll and pitch the initial pose carried (:205-212)
+    const double hy = yaw * 0.5, hp = pitch * 0.5, hr = roll * 0.5;
+    const double cy = cos(hy), sy = sin(hy), cp = cos(hp), sp = sin(hp), cr = cos(hr), sr = sin(hr);
+    const double pose[7] = {t[0], t[1], z0, sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy,
+                            cr * cp * cy + sr * sp * sy};
+    wheel_points(pose, q);
+}
 
 // four wheel points against all ground points: exact squared L2 in float (KdTreeFLANN, k = 1), packed
 // (distance bits, index) minimum -> lowest index on a tie
-struct HeightPose { // the pose the wheel points come from, where it lies on the device (null R: the points are given)
+struct WheelPoints {
+    float4 q[4];
+};
+struct HeightPose { // the pose the wheel points come from, where it lies on the device (null R: the points are the launch's argument)
     const double *R, *t;
     double        z0, roll, pitch;
 };
-__device__ inline void height_pose(const double *R, const double *t, double z0, double roll, double pitch, float4 *q);
-__global__ __launch_bounds__(256) void height_nn_kernel(const float *ground, int n, int stride, float4 q0, float4 q1,
-                                                        float4 q2, float4 q3, unsigned long long *best /*[4]*/,
-                                                        const float4 *d_q = nullptr, const int *d_n = nullptr, HeightPose hp = HeightPose{nullptr, nullptr, 0, 0, 0})
+__global__ __launch_bounds__(256) void height_nn_kernel(const float *ground, int n, const int *d_n, int stride, WheelPoints wp, HeightPose hp,
+                                                        unsigned long long *best /*[4]*/)
 {
     const int          i = blockIdx.x * 256 + threadIdx.x;
     unsigned long long b[4] = {~0ull, ~0ull, ~0ull, ~0ull};
     __shared__ float4  qs[4];
-    if (hp.R) { // every block works the four wheel points out for itself (a launch of one thread did: round 6, a match is bound by its launches)
-        if (threadIdx.x == 0) height_pose(hp.R, hp.t, hp.z0, hp.roll, hp.pitch, qs);
-        __syncthreads();
+    // the block's four wheel points: given, or worked out by every block for itself (a launch of one thread did: round 6, a match is
+    // bound by its launches)
+    if (threadIdx.x == 0) {
+        if (hp.R) height_pose(hp.R, hp.t, hp.z0, hp.roll, hp.pitch, qs);
+        else
+            for (int k = 0; k < 4; ++k) qs[k] = wp.q[k];
     }
+    __syncthreads();
     if (i < bound(n, d_n)) {
         const float *c = ground + (size_t)i * stride;
-        const float4 q[4] = {hp.R ? qs[0] : (d_q ? d_q[0] : q0), hp.R ? qs[1] : (d_q ? d_q[1] : q1), hp.R ? qs[2] : (d_q ? d_q[2] : q2),
-                             hp.R ? qs[3] : (d_q ? d_q[3] : q3)};
         for (int k = 0; k < 4; ++k) {
-            const float dx = c[0] - q[k].x, dy = c[1] - q[k].y, dz = c[2] - q[k].z;
+            const float dx = c[0] - qs[k].x, dy = c[1] - qs[k].y, dz = c[2] - qs[k].z;
             const float dd = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
             if (dd == dd) b[k] = ((unsigned long long)__float_as_uint(dd) << 32) | (unsigned)i; // dd >= 0: bits order as values
         }
@@ -314,7 +387,7 @@ __global__ __launch_bounds__(256) void height_nn_kernel(const float *ground, int
 // 1200 x 1200 lattice :60, edge cells :72-77 -- flag 255 from slam_gseg_classify_ga_dev) get the last key.
 constexpr int kGaBins = 1200; // icpTools.h:24-26
 __global__ __launch_bounds__(256) void bin_keys_kernel(const float *xyz, const unsigned char *flag, int n, int stride,
-                                                       unsigned long long *keys, const int *d_n = nullptr)
+                                                       unsigned long long *keys, const int *d_n)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -345,116 +418,6 @@ __global__ __launch_bounds__(256) void bin_gather_kernel(const float *xyz, const
     // kept points come first: the boundary is where the count stands
     const bool next_kept = i + 1 < n && (keys[i + 1] >> 32) != 0x1fffffull;
     if (kept && !next_kept) *n_out = i + 1;
-}
-
-// ---- the chain of slam_ccicp_scene_dev: what the stepwise entry points work out on the host, on the device
-// the voxel lattice from the extent (slam_ccicp_voxel_downsample_dev's host code, PCL voxel_grid.hpp); err |= 1 when it
-// does not fit the accumulator (n_vox = 0 then: nothing is accumulated)
-__device__ inline VoxelGridView voxel_geometry(const unsigned *mm, float leaf_x, float leaf_y, float leaf_z, long long capacity, bool *overflow)
-{
-    VoxelGridView v;
-    const float   leaf[3] = {leaf_x, leaf_y, leaf_z};
-    long long     nv = 1;
-    bool          bad = mm[0] == 0xffffffffu; // no finite point
-    for (int d = 0; d < 3; ++d) {
-        v.inv[d] = 1.0f / leaf[d];
-        const double lo = floor((double)(unorder_f32(mm[d]) * v.inv[d]));
-        const double hi = floor((double)(unorder_f32(mm[3 + d]) * v.inv[d]));
-        if (bad || !(fabs(lo) < 1e9) || !(hi - lo + 1.0 <= (double)capacity)) {
-            bad = true;
-            v.min_b[d] = 0;
-            v.div_b[d] = 0;
-            continue;
-        }
-        v.min_b[d] = (int)lo;
-        v.div_b[d] = (int)(hi - lo) + 1;
-        nv *= v.div_b[d];
-        if (nv <= 0 || nv > capacity) bad = true;
-    }
-    v.n_vox = bad ? 0 : nv;
-    *overflow = bad && mm[0] != 0xffffffffu;
-    return v;
-}
-
-__global__ void voxel_geometry_kernel(const unsigned *mm, float leaf_x, float leaf_y, float leaf_z, long long capacity,
-                                      VoxelGridView *g, int *err)
-{
-    if (threadIdx.x || blockIdx.x) return;
-    bool overflow = false;
-    *g = voxel_geometry(mm, leaf_x, leaf_y, leaf_z, capacity, &overflow);
-    if (overflow) atomicOr(err, 1);
-}
-
-__global__ __launch_bounds__(256) void voxel_zero_kernel(const VoxelGridView *g, Voxel *vox)
-{
-    const long long nv = g->n_vox;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long long)gridDim.x * 256) {
-        Voxel z;
-        z.sx = z.sy = z.sz = 0;
-        z.sflag = z.count = 0;
-        vox[i] = z;
-    }
-}
-
-// {0, n_ga + n_nga, n_ga}: scan_off[0..1] and scan_nga[0] of the one scan slam_icp_fit_batch_dev then registers; the
-// class totals are capped as CCICP::doICPMatch caps them (ICP_MAX_PTS - 1, icpTools.cpp:256,259)
-__global__ void scene_scan_kernel(const int *tot /*[2]*/, int cap, const int *n_obs, const int *n_gnd, const int *n_flt, int *scan,
-                                  int *counts)
-{
-    if (threadIdx.x || blockIdx.x) return;
-    const int ga = min(tot[0], cap - 1), nga = min(tot[1], cap - 1);
-    scan[0] = 0;
-    scan[1] = ga + nga;
-    scan[2] = ga;
-    counts[0] = *n_obs;
-    counts[1] = *n_gnd;
-    counts[2] = *n_flt;
-}
-
-// doHeightInterpolate's four wheel points from a pose held on the device: R (2 x 2), t of the match and z0; the
-// quaternion of the yaw (qz = sin(yaw / 2), qw = cos(yaw / 2)) goes through the same arithmetic as the host form
-__host__ __device__ inline void wheel_points(const double pose[7], float4 q[4])
-{
-    const double ROBO_HEIGHT = 1.45, wheel = 0.5; // icpTools.cpp:303-305
-    const double x = pose[3], y = pose[4], z = pose[5], w = pose[6];
-    const double d = x * x + y * y + z * z + w * w, s = 2.0 / d;
-    const double xs = x * s, ys = y * s, zs = z * s, wx = w * xs, wy = w * ys, wz = w * zs, xx = x * xs, xy = x * ys,
-                 xz = x * zs, yy = y * ys, yz = y * zs, zz = z * zs;
-    const float M[3][4] = {{(float)(1.0 - (yy + zz)), (float)(xy - wz), (float)(xz + wy), (float)pose[0]},
-                           {(float)(xy + wz), (float)(1.0 - (xx + zz)), (float)(yz - wx), (float)pose[1]},
-                           {(float)(xz - wy), (float)(yz + wx), (float)(1.0 - (xx + yy)), (float)pose[2]}};
-    int k = 0;
-    for (int i = -1; i <= 1; i += 2)
-        for (int j = -1; j <= 1; j += 2, ++k) { // :311-318
-            const float p[3] = {(float)(i * wheel), (float)(j * wheel), (float)(-1.0 * ROBO_HEIGHT)};
-            float       t[3];
-            for (int r = 0; r < 3; ++r) t[r] = M[r][0] * p[0] + M[r][1] * p[1] + M[r][2] * p[2] + M[r][3];
-            q[k] = make_float4(t[0], t[1], t[2], 0.f);
-        }
-}
-
-__device__ inline void height_pose(const double *R, const double *t, double z0, double roll, double pitch, float4 *q /*[4]*/)
-{
-    const double yaw = atan2(R[2], R[0]); // icpTools.cpp:195-197
-    const double hy = yaw * 0.5, hp = pitch * 0.5, hr = roll * 0.5;
-    const double cy = cos(hy), sy = sin(hy), cp = cos(hp), sp = sin(hp), cr = cos(hr), sr = sin(hr);
-    const double pose[7] = {t[0], t[1], z0, sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy,
-                            cr * cp * cy + sr * sp * sy};
-    wheel_points(pose, q);
-}
-
-__global__ void height_pose_kernel(const double *R, const double *t, double z0, double roll, double pitch, float4 *q /*[4]*/,
-                                   unsigned long long *best)
-{
-    if (threadIdx.x || blockIdx.x) return;
-    const double yaw = atan2(R[2], R[0]); // icpTools.cpp:195-197
-    // tf::createQuaternionFromRPY(roll, pitch, yaw): the matched yaw with the roll and pitch the initial pose carried (:205-212)
-    const double hy = yaw * 0.5, hp = pitch * 0.5, hr = roll * 0.5;
-    const double cy = cos(hy), sy = sin(hy), cp = cos(hp), sp = sin(hp), cr = cos(hr), sr = sin(hr);
-    const double pose[7] = {t[0], t[1], z0, sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy,
-                            cr * cp * cy + sr * sp * sy};
-    wheel_points(pose, q);
-    for (int k = 0; k < 4; ++k) best[k] = ~0ull;
 }
 
 // 3x3 symmetric: eigenvector of the smallest eigenvalue by Jacobi sweeps (four points: one thread, host or device)
@@ -517,13 +480,14 @@ __host__ __device__ inline double height_from_neighbours(const float corr[4][3],
     return (double)(float)((float)nrm[2] * ROBO_HEIGHT + (float)mean[2]);      // :376
 }
 
-__global__ void height_fit_kernel(const float *ground, int stride, unsigned long long *best, double z0, double *out /*[2]*/, bool clear = false,
-                                  unsigned long long *mirror_dst = nullptr, const unsigned long long *mirror_src = nullptr, int mirror_words = 0)
+// (mirror_src may contain `out`, which is written as doubles: the mirrored words go through a type that may alias anything)
+typedef unsigned long long __attribute__((may_alias)) word64;
+__global__ void height_fit_kernel(const float *ground, int stride, unsigned long long *best, double z0, double *out /*[2]*/, int mirror_words,
+                                  word64 *mirror_dst, const word64 *mirror_src)
 {
     if (threadIdx.x || blockIdx.x) return;
     const unsigned long long b[4] = {best[0], best[1], best[2], best[3]};
-    if (clear)
-        for (int k = 0; k < 4; ++k) best[k] = ~0ull; // as the next call's neighbour search must find them
+    for (int k = 0; k < 4; ++k) best[k] = ~0ull; // as the next call's neighbour search must find them
     float                    all[4][3];
     for (int k = 0; k < 4; ++k) { // four independent gathers (index 0 where there is no neighbour: read, not used)
         const size_t idx = b[k] == ~0ull ? 0 : (size_t)(unsigned)(b[k] & 0xffffffffu);
@@ -696,17 +660,42 @@ struct OneEmit {
     __device__ void operator()(long long i, int, int pos) const { emit(i, pos); }
 };
 
+// ---- the handle's device words.  The stepwise entry points have theirs in slam_ccicp::small (StepSmall), the chain has its own
+// in slam_ccicp::chain (ChainSmall): every entry point its own members, so that calls in any order on one handle never meet
+// another's words -- and nothing a captured chain addresses is touched, or moved, by a stepwise call.
+struct StepTotals { // what the stepwise compactions leave: fetched whole, in the one copy an entry point makes for its total
+    int err;        // the look-back's error bits (stat_wait: 4); zero from slam_ccicp_create on, put back by whoever reports it
+    int voxel;      // slam_ccicp_voxel_downsample_dev: occupied voxels
+    int select;     // slam_ccicp_select_dev: points kept
+    int split[2];   // slam_ccicp_split_box_dev: GA and NGA points inside the box, before the cap
+};
+struct StepSmall {
+    unsigned           mm[6];   // slam_ccicp_voxel_downsample_dev: the extent as ordered floats (minmax_kernel)
+    int                bin_n;   // slam_ccicp_bin_order_dev: points kept
+    StepTotals         tot;
+    unsigned long long best[4]; // slam_ccicp_height_dev: the packed nearest neighbours (64-bit atomicMin, one copy of all four)
+};
+struct ChainSmall {
+    VoxelGridView      g;       // (n_vox: the domain of the voxel compaction, read as one 64-bit word)
+    unsigned           mm[8];   // the extent slam_gseg_classify_ga_extent_dev leaves ([6], [7] unused)
+    int                n_obs, n_gnd, n_flt, tot[2], err, pad[2];
+    unsigned long long best[4]; // slam_ccicp_height_rpy_pose_mirror_dev's packed nearest neighbours
+};
+static_assert(sizeof(StepTotals) == 5 * sizeof(int) && offsetof(StepSmall, tot) % 4 == 0, "the totals are one copy of five ints");
+static_assert(offsetof(StepSmall, best) % 8 == 0 && offsetof(ChainSmall, best) % 8 == 0, "64-bit atomics on the packed neighbours");
+static_assert((offsetof(ChainSmall, g) + offsetof(VoxelGridView, n_vox)) % 8 == 0, "n_vox is read as a 64-bit word");
+
 } // namespace
 
 struct slam_ccicp {
-    DevMem vox, small;                  // small: 6 min/max words, totals, 4 packed NN results
+    DevMem vox, small;                  // small: StepSmall
     DevMem status;                      // the one-launch compactions' epoch (word 0, kept by the kernels) and look-back words (compact1)
     size_t vox_clean = 0;               // voxels of `vox` known to be zero (the chain's compaction leaves them so)
     const void *best_of = nullptr;      // the chain block whose packed neighbours (ChainSmall::best) have been set to "none"
     DevMem keys, sort_tmp;
     long long max_voxels = 1ll << 26;
     // the chain (slam_ccicp_scene_dev): per-point scratch for the cloud's capacity, the lattice and the counts on the device
-    DevMem labels, obs, flags, filtered, chain; // chain: VoxelGridView, counts, wheel points, packed neighbours
+    DevMem labels, obs, flags, filtered, chain; // chain: ChainSmall
     long long chain_voxels = 1ll << 21;         // accumulator capacity of the chain (64 MB): 0.5 x 0.5 x 2 m over 360 x 360 x 30 m
 };
 
@@ -730,12 +719,26 @@ int compact1(slam_ccicp *h, Pred pred, Emit emit, Tail tail, long long n, int li
     SLAM_HIP(hipGetLastError());
     return SLAM_OK;
 }
-// the three-step compaction's interface on the one-launch kernel
+// a stepwise compaction with a yes/no predicate: the total to *d_total, the look-back's error bits to StepTotals::err
 template <class Pred, class Emit>
-int compact_one(slam_ccicp *h, Pred pred, Emit emit, long long n, int limit, int *d_total, hipStream_t st, const int *d_n = nullptr,
-                const long long *d_n64 = nullptr)
+int compact_one(slam_ccicp *h, Pred pred, Emit emit, long long n, int limit, int *d_total, hipStream_t st)
 {
-    return compact1<1, false>(h, OneOutput<Pred>{pred}, OneEmit<Emit>{emit}, NoTail{d_total, nullptr}, n, limit, st, d_n, d_n64);
+    return compact1<1, false>(h, OneOutput<Pred>{pred}, OneEmit<Emit>{emit}, NoTail{d_total, nullptr}, n, limit, st, nullptr, nullptr,
+                              &h->small.as<StepSmall>()->tot.err);
+}
+// ... and what it left, in the one copy and the one wait the entry point makes for its total.  Error bits mean that a block gave up
+// waiting for a prefix and wrote from a prefix of 0: the output is not to be trusted.  They are cleared for the next call and reported.
+int fetch_totals(slam_ccicp *h, StepTotals *t, hipStream_t st, const char *who)
+{
+    StepTotals *d_tot = &h->small.as<StepSmall>()->tot;
+    SLAM_HIP(hipMemcpyAsync(t, d_tot, sizeof *t, hipMemcpyDeviceToHost, st));
+    SLAM_HIP(hipStreamSynchronize(st));
+    if (t->err) {
+        SLAM_HIP(hipMemsetAsync(&d_tot->err, 0, sizeof d_tot->err, st));
+        set_error("%s: a compaction block gave up waiting for the blocks before it (error bits %d): the output is not valid", who, t->err);
+        return SLAM_E_HIP;
+    }
+    return SLAM_OK;
 }
 } // namespace
 
@@ -770,7 +773,13 @@ int slam_ccicp_create(slam_ccicp_t **out)
     SLAM_TRY(require_device());
     slam_ccicp *h = new (std::nothrow) slam_ccicp();
     SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_ccicp_create: out of host memory");
-    int rc = reserve_quarter(h->small, 256);
+    const auto words = [h]() -> int {
+        SLAM_TRY(h->small.alloc(sizeof(StepSmall)));
+        SLAM_HIP(hipMemset(h->small.p, 0, sizeof(StepSmall))); // StepTotals::err starts as zero, on whatever stream the first call comes
+        SLAM_HIP(hipStreamSynchronize(nullptr));
+        return SLAM_OK;
+    };
+    const int rc = words();
     if (rc != SLAM_OK) {
         delete h;
         return rc;
@@ -791,7 +800,8 @@ int slam_ccicp_voxel_downsample_dev(slam_ccicp_t *h, const float *d_xyz, const u
     *n_out = 0;
     if (n == 0) return SLAM_OK;
     hipStream_t st = as_stream(stream);
-    unsigned   *mm = static_cast<unsigned *>(h->small.p);
+    StepSmall  *w = h->small.as<StepSmall>();
+    unsigned   *mm = w->mm;
     const unsigned init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
     SLAM_HIP(hipMemcpyAsync(mm, init, sizeof init, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(minmax_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_xyz, d_flag, n, stride, mm);
@@ -821,12 +831,11 @@ int slam_ccicp_voxel_downsample_dev(slam_ccicp_t *h, const float *d_xyz, const u
     Voxel *vox = static_cast<Voxel *>(h->vox.p);
     SLAM_HIP(hipMemsetAsync(vox, 0, sizeof(Voxel) * (size_t)nv, st));
     h->vox_clean = 0; // (the chain of slam_ccicp_scene_dev shares the accumulator and expects it zero)
-    hipLaunchKernelGGL(voxel_accumulate_kernel, dim3((n + 255) / 256), dim3(256), 0, st, g, d_xyz, d_flag, n, stride, vox);
-    int *d_total = reinterpret_cast<int *>(mm + 8);
-    SLAM_TRY(compact_one(h, VoxelUsed{vox}, VoxelEmit{vox, d_out}, nv, max_out, d_total, st));
-    int total = 0;
-    SLAM_HIP(hipMemcpyAsync(&total, d_total, sizeof(int), hipMemcpyDeviceToHost, st));
-    SLAM_HIP(hipStreamSynchronize(st));
+    hipLaunchKernelGGL(voxel_accumulate_kernel, dim3((n + 255) / 256), dim3(256), 0, st, g, DeviceLattice{}, d_xyz, d_flag, n, stride, vox);
+    SLAM_TRY(compact_one(h, VoxelUsed{vox}, VoxelEmit{vox, d_out}, nv, max_out, &w->tot.voxel, st));
+    StepTotals t;
+    SLAM_TRY(fetch_totals(h, &t, st, "slam_ccicp_voxel_downsample_dev"));
+    const int total = t.voxel;
     *n_out = total;
     SLAM_REQUIRE(total <= max_out, SLAM_E_INVALID, "output holds %d voxels, %d produced (first %d written)", max_out,
                  total, max_out);
@@ -841,10 +850,11 @@ int slam_ccicp_select_dev(slam_ccicp_t *h, const float *d_xyz, int n, int stride
     *n_out = 0;
     if (n == 0) return SLAM_OK;
     hipStream_t st = as_stream(stream);
-    int        *d_tot = reinterpret_cast<int *>(static_cast<unsigned *>(h->small.p) + 26);
-    SLAM_TRY(compact_one(h, LabelPred{d_labels, label_mask}, Xyz4Emit{d_xyz, stride, reinterpret_cast<float4 *>(d_out_xyz4)}, n, n, d_tot, st));
-    SLAM_HIP(hipMemcpyAsync(n_out, d_tot, sizeof(int), hipMemcpyDeviceToHost, st));
-    SLAM_HIP(hipStreamSynchronize(st));
+    SLAM_TRY(compact_one(h, LabelPred{d_labels, label_mask}, Xyz4Emit{d_xyz, stride, reinterpret_cast<float4 *>(d_out_xyz4)}, n, n,
+                         &h->small.as<StepSmall>()->tot.select, st));
+    StepTotals t;
+    SLAM_TRY(fetch_totals(h, &t, st, "slam_ccicp_select_dev"));
+    *n_out = t.select;
     return SLAM_OK;
 }
 
@@ -858,12 +868,12 @@ int slam_ccicp_bin_order_dev(slam_ccicp_t *h, const float *d_xyz, const uint8_t 
     hipStream_t st = as_stream(stream);
     SLAM_TRY(reserve_quarter(h->keys, 2 * sizeof(unsigned long long) * (size_t)n));
     unsigned long long *k_in = static_cast<unsigned long long *>(h->keys.p), *k_out = k_in + n;
-    hipLaunchKernelGGL(bin_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_xyz, d_flag, n, stride, k_in);
+    hipLaunchKernelGGL(bin_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_xyz, d_flag, n, stride, k_in, nullptr);
     size_t tmp = 0;
     SLAM_HIP(rocprim::radix_sort_keys(nullptr, tmp, k_in, k_out, (size_t)n, 0u, 53u, st));
     SLAM_TRY(reserve_quarter(h->sort_tmp, tmp));
     SLAM_HIP(rocprim::radix_sort_keys(h->sort_tmp.p, tmp, k_in, k_out, (size_t)n, 0u, 53u, st));
-    int *d_n = reinterpret_cast<int *>(static_cast<unsigned *>(h->small.p) + 24);
+    int *d_n = &h->small.as<StepSmall>()->bin_n;
     SLAM_HIP(hipMemsetAsync(d_n, 0, sizeof(int), st));
     hipLaunchKernelGGL(bin_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_xyz, d_flag, stride, k_out, n,
                        reinterpret_cast<float4 *>(d_out_xyzg), d_n);
@@ -882,22 +892,14 @@ int slam_ccicp_split_box_dev(slam_ccicp_t *h, const float *d_xyzg, int n, int st
     if (totals) totals[0] = totals[1] = 0;
     if (n == 0) return SLAM_OK;
     hipStream_t st = as_stream(stream);
-    int        *d_tot = reinterpret_cast<int *>(static_cast<unsigned *>(h->small.p) + 12);
-    SplitPred   p;
-    p.xyzg = d_xyzg;
-    p.stride = stride;
-    p.crop = box ? 1 : 0;
-    p.x_lo = box ? box[0] : 0.f;
-    p.x_hi = box ? box[1] : 0.f;
-    p.y_lo = box ? box[2] : 0.f;
-    p.y_hi = box ? box[3] : 0.f;
-    p.want_ga = 1;
-    SLAM_TRY(compact_one(h, p, SplitEmit{d_xyzg, stride, d_ga_xy, nullptr, 0}, n, cap - 1, d_tot, st)); // ICP_MAX_PTS-1 (:256,:259)
-    p.want_ga = 0;
-    SLAM_TRY(compact_one(h, p, SplitEmit{d_xyzg, stride, d_nga_xy, nullptr, 0}, n, cap - 1, d_tot + 1, st));
-    int tot[2];
-    SLAM_HIP(hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, st));
-    SLAM_HIP(hipStreamSynchronize(st));
+    StepTotals  *d_tot = &h->small.as<StepSmall>()->tot;
+    const SplitClass p = {d_xyzg, stride, box ? 1 : 0, box ? box[0] : 0.f, box ? box[1] : 0.f, box ? box[2] : 0.f, box ? box[3] : 0.f};
+    // both classes from one pass, each cut at ICP_MAX_PTS - 1 (:256,:259)
+    SLAM_TRY((compact1<2, false>(h, p, SplitEmitPair{d_xyzg, stride, d_ga_xy, d_nga_xy}, NoTail{&d_tot->split[0], &d_tot->split[1]}, n, cap - 1, st,
+                                 nullptr, nullptr, &d_tot->err)));
+    StepTotals t;
+    SLAM_TRY(fetch_totals(h, &t, st, "slam_ccicp_split_box_dev"));
+    const int *tot = t.split;
     counts[0] = tot[0] < cap - 1 ? tot[0] : cap - 1;
     counts[1] = tot[1] < cap - 1 ? tot[1] : cap - 1;
     if (totals) totals[0] = tot[0], totals[1] = tot[1];
@@ -923,14 +925,13 @@ int slam_ccicp_height_dev(slam_ccicp_t *h, const float *d_ground, int n, int str
     if (nn_idx) nn_idx[0] = nn_idx[1] = nn_idx[2] = nn_idx[3] = -1;
     if (n == 0) return SLAM_OK;
     // tf::Matrix3x3(q) stored to an Eigen::Matrix4f (:321-329), then pcl::transformPointCloud in float (:332)
-    float4 q[4];
-    wheel_points(pose, q);
+    WheelPoints wp;
+    wheel_points(pose, wp.q);
     int k = 0;
     hipStream_t         st = as_stream(stream);
-    unsigned long long *best = reinterpret_cast<unsigned long long *>(static_cast<unsigned *>(h->small.p) + 16);
+    unsigned long long *best = h->small.as<StepSmall>()->best;
     SLAM_HIP(hipMemsetAsync(best, 0xff, 4 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(height_nn_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_ground, n, stride, q[0], q[1], q[2],
-                       q[3], best);
+    hipLaunchKernelGGL(height_nn_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_ground, n, nullptr, stride, wp, HeightPose{}, best);
     unsigned long long got[4];
     SLAM_HIP(hipMemcpyAsync(got, best, sizeof got, hipMemcpyDeviceToHost, st));
     SLAM_HIP(hipStreamSynchronize(st));
@@ -955,14 +956,6 @@ int slam_ccicp_height_dev(slam_ccicp_t *h, const float *d_ground, int n, int str
 
 // ---- the device-resident chain
 namespace {
-struct ChainSmall { // layout of slam_ccicp::chain
-    VoxelGridView      g;
-    unsigned           mm[8];
-    int                n_obs, n_gnd, n_flt, tot[2], err, pad[2];
-    float4             q[4];
-    unsigned long long best[4];
-};
-
 // obstacle cloud (output 0) and ground cloud (output 1) from one pass over the labels
 struct ObsGndPred {
     const unsigned char *labels;
@@ -1001,28 +994,7 @@ struct FltTail {
     int *n_flt;
     __device__ void operator()(const int tot[2]) const { *n_flt = tot[0]; }
 };
-// doICPMatch's marshalling as ONE pass: class of a point that survives the crop (0 = GA, 1 = NGA), GA in front of NGA
-struct SplitClass {
-    SplitPred p; // (want_ga unused)
-    __device__ int operator()(long long i) const
-    {
-        const float *q = p.xyzg + (size_t)i * p.stride;
-        if (p.crop && !(finite3(q) && q[0] >= p.x_lo && q[0] <= p.x_hi && q[1] >= p.y_lo && q[1] <= p.y_hi)) return -1;
-        return q[3] > 0.5f ? 0 : 1; // isGA, PointcloudXYZGD.h:28-30
-    }
-};
-struct SplitEmit2 {
-    const float *xyzg;
-    int          stride;
-    double      *out;
-    __device__ void operator()(long long i, int, int pos) const
-    {
-        const float *q = xyzg + (size_t)i * stride;
-        out[2 * (size_t)pos] = (double)q[0]; // icpTools.cpp:252, 267: float coordinates widened
-        out[2 * (size_t)pos + 1] = (double)q[1];
-    }
-};
-// ... and the scan descriptor {0, n_ga + n_nga, n_ga} of the one scan slam_icp_fit_batch_dev then registers, the class totals
+// the split's tail: the scan descriptor {0, n_ga + n_nga, n_ga} of the one scan slam_icp_fit_batch_dev then registers, the class totals
 // capped as CCICP::doICPMatch caps them (ICP_MAX_PTS - 1, icpTools.cpp:256,259), and the chain's counts
 struct SceneTail {
     ChainSmall *c;
@@ -1078,8 +1050,8 @@ int slam_ccicp_scene_dev(slam_ccicp_t *h, slam_gseg_t *seg, const float *d_xyz, 
                 SLAM_HIP(hipMemsetAsync(vox, 0, sizeof(Voxel) * (size_t)h->chain_voxels, st));
                 h->vox_clean = (size_t)h->chain_voxels;
             }
-            hipLaunchKernelGGL(voxel_accumulate_kernel, dim3((n + 255) / 256), dim3(256), 0, st, VoxelGridView(), obs, flg, n, 4, vox, &c->g,
-                               &c->n_obs, c->mm, make_float3(0.5f, 0.5f, 2.0f), h->chain_voxels, &c->err);
+            hipLaunchKernelGGL(voxel_accumulate_kernel, dim3((n + 255) / 256), dim3(256), 0, st, VoxelGridView(),
+                               DeviceLattice{c->mm, &c->n_obs, &c->g, &c->err, make_float3(0.5f, 0.5f, 2.0f), h->chain_voxels}, obs, flg, n, 4, vox);
             // (there are never more occupied voxels than points: n bounds the output)
             SLAM_TRY((compact1<1, false>(h, OneOutput<VoxelUsed>{VoxelUsed{vox}}, OneEmit<VoxelEmitClean>{VoxelEmitClean{vox, flt}}, FltTail{&c->n_flt},
                                          h->chain_voxels, n, st, nullptr, &c->g.n_vox, &c->err)));
@@ -1096,16 +1068,8 @@ int slam_ccicp_scene_dev(slam_ccicp_t *h, slam_gseg_t *seg, const float *d_xyz, 
         }
     }
     // doICPMatch marshalling (:225-276): crop, split by class with the cap, GA in front of NGA -- and the scan's descriptor
-    SplitClass p;
-    p.p.xyzg = flt;
-    p.p.stride = 4;
-    p.p.want_ga = 0;
-    p.p.crop = crop;
-    p.p.x_lo = (float)(-crop_dist + cur_x);
-    p.p.x_hi = (float)(crop_dist + cur_x);
-    p.p.y_lo = (float)(-crop_dist + cur_y);
-    p.p.y_hi = (float)(crop_dist + cur_y);
-    SLAM_TRY((compact1<2, true>(h, p, SplitEmit2{flt, 4, d_pts}, SceneTail{c, cap, d_scan, d_counts}, n, cap - 1, st, &c->n_flt, nullptr, &c->err)));
+    const SplitClass p = {flt, 4, crop, (float)(-crop_dist + cur_x), (float)(crop_dist + cur_x), (float)(-crop_dist + cur_y), (float)(crop_dist + cur_y)};
+    SLAM_TRY((compact1<2, true>(h, p, SplitEmit{flt, 4, d_pts}, SceneTail{c, cap, d_scan, d_counts}, n, cap - 1, st, &c->n_flt, nullptr, &c->err)));
     SLAM_HIP(hipGetLastError());
     return SLAM_OK;
 }
@@ -1149,11 +1113,10 @@ int slam_ccicp_height_rpy_pose_mirror_dev(slam_ccicp_t *h, const float *d_ground
         h->best_of = h->chain.p;
     }
     if (n_capacity > 0)
-        hipLaunchKernelGGL(height_nn_kernel, dim3((n_capacity + 255) / 256), dim3(256), 0, st, d_ground, n_capacity, stride,
-                           make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), c->best,
-                           nullptr, d_n_ground, HeightPose{d_R, d_t, z0, roll, pitch});
-    hipLaunchKernelGGL(height_fit_kernel, dim3(1), dim3(64), 0, st, d_ground, stride, c->best, z0, d_out, true,
-                       static_cast<unsigned long long *>(mirror_dst), static_cast<const unsigned long long *>(mirror_src), (int)(mirror_bytes / 8));
+        hipLaunchKernelGGL(height_nn_kernel, dim3((n_capacity + 255) / 256), dim3(256), 0, st, d_ground, n_capacity, d_n_ground, stride,
+                           WheelPoints{}, HeightPose{d_R, d_t, z0, roll, pitch}, c->best);
+    hipLaunchKernelGGL(height_fit_kernel, dim3(1), dim3(64), 0, st, d_ground, stride, c->best, z0, d_out, (int)(mirror_bytes / 8),
+                       static_cast<word64 *>(mirror_dst), static_cast<const word64 *>(mirror_src));
     SLAM_HIP(hipGetLastError());
     return SLAM_OK;
 }

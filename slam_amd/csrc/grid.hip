@@ -1132,12 +1132,6 @@ __global__ __launch_bounds__(256) void window_from_storage_kernel(GridView g, co
     occ_w[x + (size_t)g.sx * y] = occ_s[s];
 }
 
-__global__ void fill_i8_kernel(int8_t *p, size_t n, int8_t v)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-
 } // namespace
 
 struct slam_grid {

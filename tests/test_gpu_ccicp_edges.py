@@ -565,6 +565,123 @@ def test_height_mirror():
     cc.close()
 
 
+# ------------------------------------------------------------------ every entry point on one handle
+def test_every_entry_point_interleaved_on_one_handle():
+    """the stepwise entry points and the chain, interleaved on ONE slam_ccicp handle, forwards and then backwards, a selection
+    over 65 * 1024 + 1 items among them (look-back words of a larger launch in the way of the 8-block cloud's): every output
+    buffer, the sentinel rows past the counts included, equals byte for byte what the same call leaves on a fresh handle --
+    the handle's device words are every entry point's own, and no call finds what another left"""
+    L = api.lib()
+    xyz = np.ascontiguousarray(synth.make_cloud3d(**E.CHAIN_RINGS)[0], np.float32)
+    n = len(xyz)
+    assert n == 8 * E.BLOCK
+    # the inputs of the later steps, made once by a pair of handles of their own
+    seg0, cc0 = api.GroundSegmentation(), api.Ccicp()
+    d_xyz, d_lab = api.DeviceArray.from_host(xyz), api.DeviceArray((n,), np.uint8)
+    seg0.segment_dev(d_xyz, n, 3, d_lab)
+    d_obs, d_gnd, d_flag, d_flt = dev((n, 4), np.float32), dev((n, 4), np.float32), dev(n, np.uint8), dev((n, 4), np.float32)
+    n_obs, n_gnd, n_flt = C.c_int(0), C.c_int(0), C.c_int(0)
+    api.check(L.slam_ccicp_select_dev(cc0.h, d_xyz.ptr, n, 3, d_lab.ptr, (1 << 2) | (1 << 3), d_obs.ptr, C.byref(n_obs), None))
+    api.check(L.slam_ccicp_select_dev(cc0.h, d_xyz.ptr, n, 3, d_lab.ptr, 1 << 1, d_gnd.ptr, C.byref(n_gnd), None))
+    api.check(L.slam_gseg_classify_ga_dev(seg0.h, d_obs.ptr, n_obs.value, 4, d_flag.ptr, None))
+    api.check(L.slam_ccicp_voxel_downsample_dev(cc0.h, d_obs.ptr, d_flag.ptr, n_obs.value, 4, 0.5, 0.5, 2.0, d_flt.ptr, n, C.byref(n_flt), None))
+    api.synchronize()
+    n_obs, n_gnd, n_flt = n_obs.value, n_gnd.value, n_flt.value
+    assert n_obs > E.BLOCK and n_gnd > E.BLOCK and n_flt > 60
+    seg0.close()
+    cc0.close()
+    n_big = 65 * E.BLOCK + 1
+    d_big = api.DeviceArray.from_host(E.cloud_of(n_big))
+    d_big_lab = api.DeviceArray.from_host((2 * (np.arange(n_big) % 3 == 0)).astype(np.uint8))
+    cx, cy = E.CHAIN_CROPS[1]
+    box = (C.c_float * 4)(-E.CHAIN_CROP_DIST + cx, E.CHAIN_CROP_DIST + cx, -E.CHAIN_CROP_DIST + cy, E.CHAIN_CROP_DIST + cy)
+    d_R, d_t, d_ngnd = api.DeviceArray.from_host(np.array(E.rot2(0.4))), api.DeviceArray.from_host(np.array([0.5, -0.25])), i32(n_gnd)
+    pattern = (np.arange(64, dtype=np.uint32) * 2654435761 >> 13).astype(np.uint8)
+    pinned = api.PinnedArray((72,), np.uint8)
+    # the outputs, allocated once: a call refills its own with the sentinel
+    o_rows, o_big, o_ga, o_nga = dev((n + 1, 4), np.float32), dev((n_big + 1, 4), np.float32), dev((n + 1, 2), np.float64), dev((n + 1, 2), np.float64)
+    o_pts, o_scan, o_counts, o_gnd, o_src = dev((2 * n + 2, 2), np.float64), dev(3, np.int32), dev(4, np.int32), dev((n + 1, 4), np.float32), dev(64, np.uint8)
+
+    def left(*bufs):
+        api.synchronize()
+        return [b.download().tobytes() for b in bufs]
+
+    def voxel(cc, seg):
+        refill(o_rows)
+        cnt = C.c_int(-1)
+        api.check(L.slam_ccicp_voxel_downsample_dev(cc.h, d_obs.ptr, d_flag.ptr, n_obs, 4, 0.5, 0.5, 2.0, o_rows.ptr, n, C.byref(cnt), None))
+        return [cnt.value] + left(o_rows)
+
+    def select(cc, seg):
+        refill(o_rows)
+        cnt = C.c_int(-1)
+        api.check(L.slam_ccicp_select_dev(cc.h, d_xyz.ptr, n, 3, d_lab.ptr, (1 << 2) | (1 << 3), o_rows.ptr, C.byref(cnt), None))
+        return [cnt.value] + left(o_rows)
+
+    def select_big(cc, seg):
+        refill(o_big)
+        cnt = C.c_int(-1)
+        api.check(L.slam_ccicp_select_dev(cc.h, d_big.ptr, n_big, 3, d_big_lab.ptr, 1 << 2, o_big.ptr, C.byref(cnt), None))
+        return [cnt.value] + left(o_big)
+
+    def bin_order(cc, seg):
+        refill(o_rows)
+        cnt = C.c_int(-1)
+        api.check(L.slam_ccicp_bin_order_dev(cc.h, d_obs.ptr, d_flag.ptr, n_obs, 4, o_rows.ptr, C.byref(cnt), None))
+        return [cnt.value] + left(o_rows)
+
+    def split(with_box, cap):
+        def call(cc, seg):
+            refill(o_ga)
+            refill(o_nga)
+            counts, totals = (C.c_int * 2)(-1, -1), (C.c_int * 2)(-1, -1)
+            api.check(L.slam_ccicp_split_box_dev(cc.h, d_flt.ptr, n_flt, 4, box if with_box else None, cap, o_ga.ptr, o_nga.ptr, counts, totals, None))
+            return [list(counts), list(totals)] + left(o_ga, o_nga)
+        return call
+
+    def height(cc, seg):
+        z, nc, idx = C.c_double(7), C.c_int(-1), (C.c_int * 4)()
+        pose = E.pose_of(E.rot2(0.4), [0.5, -0.25], 0.125, 0.03, -0.03)
+        api.check(L.slam_ccicp_height_dev(cc.h, d_gnd.ptr, n_gnd, 4, (C.c_double * 7)(*pose), C.byref(z), C.byref(nc), idx, None))
+        return [z.value, nc.value, list(idx)]
+
+    def scene_call(voxel, crop, cap):
+        def call(cc, seg):
+            for b in (o_pts, o_scan, o_counts, o_gnd, o_rows):
+                refill(b)
+            scan, counts = scene(L, cc, seg, d_xyz, n, voxel, crop, cap, o_pts, o_scan, o_gnd, o_counts)
+            api.check(L.slam_ccicp_scene_cloud_dev(cc.h, o_rows.ptr, int(counts[2]), None))
+            return left(o_pts, o_scan, o_counts, o_gnd, o_rows)
+        return call
+
+    def mirror(cc, seg):
+        put(o_src, pattern)
+        pinned.array[:] = E.SENTINEL
+        api.check(L.slam_ccicp_height_rpy_pose_mirror_dev(cc.h, d_gnd.ptr, d_ngnd.ptr, n_gnd, 4, d_R.ptr, d_t.ptr, 0.125, 0.03, -0.03,
+                                                          o_src.view(0, (16,)).ptr, pinned.ptr, o_src.ptr, 64, None))
+        return left(o_src) + [pinned.array.tobytes()]
+
+    calls = [("voxel_downsample", voxel), ("select over %d" % n_big, select_big), ("select", select), ("bin_order", bin_order),
+             ("split_box with a box", split(True, 50)), ("height", height), ("scene, voxel filter", scene_call(1, E.CHAIN_CROPS[1], 50)),
+             ("split_box without a box", split(False, n + 2)), ("height_rpy_pose_mirror", mirror), ("scene, bin order", scene_call(0, None, n))]
+    fresh = {}
+    for name, call in calls:
+        seg, cc = api.GroundSegmentation(), api.Ccicp()
+        fresh[name] = call(cc, seg)
+        seg.close()
+        cc.close()
+    assert fresh["select"][0] == n_obs and fresh["voxel_downsample"][0] == n_flt and fresh["height"][1] == 4
+    assert fresh["split_box with a box"][0] != fresh["split_box with a box"][1]              # the cap bites
+    assert np.frombuffer(fresh["height_rpy_pose_mirror"][0][:16], np.float64)[1] == 4
+    seg, cc = api.GroundSegmentation(), api.Ccicp()
+    for order in (calls, calls[::-1]):
+        for name, call in order:
+            assert call(cc, seg) == fresh[name], name
+    pinned.free()
+    seg.close()
+    cc.close()
+
+
 # ------------------------------------------------------------------ packing
 @pytest.mark.parametrize("case", list(E.pack_cases()), ids=lambda c: c[0])
 def test_pack_scans(case):
