@@ -7,7 +7,7 @@
 // A keyframe is filtered (pcl::VoxelGrid 0.5) and indexed once, when it is added; the reference filters both clouds again at
 // every edge, which gives the same clouds.  The device does the ICP and computeEdgeInformationLUM; what is left of
 // calcEdgeIcp runs here: the initial transform from the two poses, the edge pose and quaternion, the acceptance gate.
-// g2o (addVertex / addEdge / optimizeGraph) stays with the caller.
+// addVertex / addEdge / optimizeGraph are slam_amd/pose_graph.hpp.
 //
 // Two places where this differs from the reference's host arithmetic by rounding, neither pinned (docs/KF_EDGE.md):
 // Mfrom.inverse() is taken as the rigid inverse (R', -R't) instead of Eigen's general 4 x 4 inverse, and the initial pose's

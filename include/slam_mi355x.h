@@ -907,6 +907,92 @@ int  slam_vmap_read_sums(slam_vmap_t *m, int64_t *sums, uint32_t *count, uint64_
 /* occupied voxels, slots of the table, points integrated (dropped ones not counted), bytes of device memory held */
 int  slam_vmap_info(slam_vmap_t *m, int64_t *n_voxels, int64_t *capacity, int64_t *n_points, size_t *device_bytes);
 
+/* -------------------------------------------------------------------------
+ * Pose-graph optimiser: graph_slam's optimizeGraph (graph_slam.cpp:322-390), i.e. g2o's VertexSE3 / EdgeSE3 under
+ * OptimizationAlgorithmLevenberg, restated in docs/PGO.md (parity with g2o itself is unpinned; the yardstick is
+ * tests/cpp/pgo_oracle.cpp).  Everything is f64.
+ *   pose      7 doubles: t (x y z) and a quaternion (x y z w); a quaternion arriving through the ABI is divided by its norm
+ *             unless |q|^2 is within 8 ulp of 1 already (a pose read back and handed in again keeps its bits)
+ *   edge      from -> to with measurement Z (a pose) and information (36 doubles, row-major, x y z then rotation x y z):
+ *             e = toVectorMQT(Z^-1 Xfrom^-1 Xto), chi2 = e' info e
+ *   update    X <- X fromVectorMQT(delta), quaternion renormalised
+ *   system    H = sum J' info J, b = -sum J' info e with the closed-form Jacobians of docs/PGO.md, block rows in a reverse
+ *             Cuthill-McKee order of the free vertices, a uniform block band, Cholesky in one workgroup
+ * The graph is host state: create, clear, add_vertex, set_vertex, add_edge and destroy touch no device and work without
+ * one.  The calls that take a stream upload the graph and WAIT for that stream; on a machine without a usable device they
+ * return SLAM_E_HIP.  One call at a time per handle.
+ * ---------------------------------------------------------------------- */
+typedef struct slam_pgo slam_pgo_t;
+
+#define SLAM_PGO_ORDER_RCM       0 /* reverse Cuthill-McKee, ties by degree then id */
+#define SLAM_PGO_ORDER_NATURAL   1 /* free vertices by id (tests) */
+#define SLAM_PGO_STOP_ITERATIONS 0
+#define SLAM_PGO_STOP_MAX_TRIALS 1
+#define SLAM_PGO_STOP_RHO_ZERO   2
+#define SLAM_PGO_TRACE           64
+
+typedef struct {
+    int    max_trials;     /* 10: trials of one iteration (g2o's maxTrialsAfterFailure) */
+    double tau;            /* 1e-5: lambda of iteration 0 = tau * max diag(H) */
+    double good_lower;     /* 1/3 */
+    double good_upper;     /* 2/3 */
+    int    ordering;       /* SLAM_PGO_ORDER_* */
+    size_t max_band_bytes; /* 1 GiB: a band of more bytes is SLAM_E_NOMEM, nothing is truncated */
+} slam_pgo_params;
+
+typedef struct {
+    double lambda;   /* the damping this trial solved with */
+    double rho;
+    double chi2;     /* of the candidate poses; DBL_MAX where the factorisation met a pivot <= 0 */
+    int    accepted;
+    int    reserved;
+} slam_pgo_trial;
+
+typedef struct {
+    int            iterations;     /* linearisations done */
+    int            stop_reason;    /* SLAM_PGO_STOP_* */
+    int            half_bandwidth; /* w, in blocks */
+    int            free_vertices;
+    double         chi2_initial;
+    double         chi2_final;
+    size_t         band_bytes;     /* free_vertices * (w + 1) * 36 * 8 */
+    int            n_trials;       /* all trials of the call; the first SLAM_PGO_TRACE of them are in `trace` */
+    int            reserved;
+    slam_pgo_trial trace[SLAM_PGO_TRACE];
+} slam_pgo_result;
+
+void slam_pgo_default_params(slam_pgo_params *p);
+int  slam_pgo_create(const slam_pgo_params *params, slam_pgo_t **out); /* params may be NULL */
+void slam_pgo_destroy(slam_pgo_t *g);
+int  slam_pgo_clear(slam_pgo_t *g); /* no vertices, no edges; the device buffers stay */
+/* Ids are dense and in order: id must be the number of vertices so far.  SLAM_E_INVALID otherwise, or for a pose that is
+ * not finite or has a zero quaternion. */
+int  slam_pgo_add_vertex(slam_pgo_t *g, int id, const double pose[7], int fixed);
+int  slam_pgo_set_vertex(slam_pgo_t *g, int id, const double pose[7]);
+/* from != to, both existing vertices; Z^-1 is taken here, once. */
+int  slam_pgo_add_edge(slam_pgo_t *g, int from, int to, const double meas[7], const double info[36]);
+int  slam_pgo_size(slam_pgo_t *g, int *n_vertices, int *n_edges);
+/* Up to `iterations` Levenberg-Marquardt iterations from the current poses; lambda starts anew in every call.  The
+ * estimates replace the handle's poses.  SLAM_E_INVALID without a fixed vertex, SLAM_E_NOMEM beyond max_band_bytes.
+ * Waits once per trial (one pinned record) and once for the poses. */
+int  slam_pgo_optimize(slam_pgo_t *g, int iterations, slam_pgo_result *result, slam_stream_t stream);
+/* 7 doubles per vertex, the quaternion with w >= 0.  Host state: no device. */
+int  slam_pgo_read_vertices(slam_pgo_t *g, double *pose, int cap, int *n_out);
+/* Stage entry points (tests, debugging); each applies nothing.
+ * chi2: the sum and, where given, e (6 per edge) and chi2 per edge at the current poses. */
+int  slam_pgo_chi2(slam_pgo_t *g, double *chi2, double *e, double *chi2_e, slam_stream_t stream);
+/* The undamped system (lambda = 0) at the current poses: every block of the band's lower part as (rows[k], cols[k],
+ * blocks[36 k ..]) with rows and cols in vertex numbering, b (6 per vertex, zeros at fixed ones), perm (block row ->
+ * vertex, free_vertices of them) and w.  *n_blocks is the number of blocks; with more than `cap` nothing but the three
+ * counts is written and the call returns SLAM_E_NOMEM.  Array arguments are nullable. */
+int  slam_pgo_read_system(slam_pgo_t *g, int *rows, int *cols, double *blocks, int cap, int *n_blocks, double *b, int *perm,
+                          int *free_vertices, int *half_bandwidth, slam_stream_t stream);
+/* One trial at the given lambda: delta (6 per vertex, vertex numbering), chi2 before and at the candidate poses as computed
+ * (not replaced by DBL_MAX), scale = sum delta (lambda delta + b) without the 1e-3, *pivot_flag = 1 where a pivot <= 0 ended
+ * the factorisation (delta and scale are zero then). */
+int  slam_pgo_step(slam_pgo_t *g, double lambda, double *delta, double *chi2_before, double *chi2_after, double *scale,
+                   int *pivot_flag, slam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,27 @@ class VmapParams(C.Structure):
     _fields_ = [("leaf", C.c_double), ("initial_capacity", C.c_int)]
 
 
+class PgoParams(C.Structure):
+    _fields_ = [("max_trials", C.c_int), ("tau", C.c_double), ("good_lower", C.c_double), ("good_upper", C.c_double),
+                ("ordering", C.c_int), ("max_band_bytes", C.c_size_t)]
+
+
+class PgoTrial(C.Structure):
+    _fields_ = [("lambda_", C.c_double), ("rho", C.c_double), ("chi2", C.c_double), ("accepted", C.c_int), ("reserved", C.c_int)]
+
+
+PGO_TRACE = 64
+
+
+class PgoResult(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("stop_reason", C.c_int), ("half_bandwidth", C.c_int), ("free_vertices", C.c_int),
+                ("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("band_bytes", C.c_size_t), ("n_trials", C.c_int),
+                ("reserved", C.c_int), ("trace", PgoTrial * PGO_TRACE)]
+
+
+PGO_ORDER_RCM, PGO_ORDER_NATURAL = 0, 1
+PGO_STOP_ITERATIONS, PGO_STOP_MAX_TRIALS, PGO_STOP_RHO_ZERO = 0, 1, 2
+
 CSM_RESULT_DTYPE = np.dtype([(f, np.int32) for f, _ in CsmResult._fields_])
 
 KF_NOT_CONVERGED, KF_ITERATIONS, KF_TRANSFORM, KF_ABS_MSE, KF_REL_MSE, KF_NO_CORRESPONDENCES = 0, 1, 2, 3, 4, 5
@@ -173,6 +194,9 @@ EXPORTS = [
     "slam_csm_score_volume_dev", "slam_csm_read_table", "slam_csm_info",
     "slam_vmap_default_params", "slam_vmap_create", "slam_vmap_destroy", "slam_vmap_clear", "slam_vmap_integrate",
     "slam_vmap_integrate_dev", "slam_vmap_extract_dev", "slam_vmap_read", "slam_vmap_read_sums", "slam_vmap_info",
+    "slam_pgo_default_params", "slam_pgo_create", "slam_pgo_destroy", "slam_pgo_clear", "slam_pgo_add_vertex",
+    "slam_pgo_set_vertex", "slam_pgo_add_edge", "slam_pgo_size", "slam_pgo_optimize", "slam_pgo_read_vertices", "slam_pgo_chi2",
+    "slam_pgo_read_system", "slam_pgo_step",
 ]
 
 
@@ -396,6 +420,22 @@ def lib():
     L.slam_vmap_read.argtypes = [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
     L.slam_vmap_read_sums.argtypes = [_vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
     L.slam_vmap_info.argtypes = [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]
+    _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+    L.slam_pgo_default_params.argtypes = [C.POINTER(PgoParams)]
+    L.slam_pgo_default_params.restype = None
+    L.slam_pgo_create.argtypes = [C.POINTER(PgoParams), C.POINTER(_vp)]
+    L.slam_pgo_destroy.argtypes = [_vp]
+    L.slam_pgo_destroy.restype = None
+    L.slam_pgo_clear.argtypes = [_vp]
+    L.slam_pgo_add_vertex.argtypes = [_vp, C.c_int, _vp, C.c_int]
+    L.slam_pgo_set_vertex.argtypes = [_vp, C.c_int, _vp]
+    L.slam_pgo_add_edge.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp]
+    L.slam_pgo_size.argtypes = [_vp, _ip, _ip]
+    L.slam_pgo_optimize.argtypes = [_vp, C.c_int, C.POINTER(PgoResult), _vp]
+    L.slam_pgo_read_vertices.argtypes = [_vp, _vp, C.c_int, _ip]
+    L.slam_pgo_chi2.argtypes = [_vp, _dp, _vp, _vp, _vp]
+    L.slam_pgo_read_system.argtypes = [_vp, _vp, _vp, _vp, C.c_int, _ip, _vp, _vp, _ip, _ip, _vp]
+    L.slam_pgo_step.argtypes = [_vp, C.c_double, _vp, _dp, _dp, _dp, _ip, _vp]
     _lib = L
     return L
 
@@ -866,6 +906,139 @@ class CorrelativeMatcher:
     def close(self):
         if getattr(self, "h", None):
             lib().slam_csm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pgo_default_params(**kw):
+    p = PgoParams()
+    lib().slam_pgo_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+class PoseGraph:
+    """The pose-graph optimiser (slam_pgo_*, docs/PGO.md): SE3 vertices (x y z, quaternion x y z w) and edges with a 6 x 6
+    information, Levenberg-Marquardt as graph_slam's optimizeGraph runs it.  The graph is host state; optimize, chi2,
+    read_system and step run on the device."""
+
+    def __init__(self, params=None, **kw):
+        self.params = params or pgo_default_params(**kw)
+        h = _vp()
+        check(lib().slam_pgo_create(C.byref(self.params), C.byref(h)))
+        self.h = h.value
+
+    @staticmethod
+    def _f64(a, n):
+        return np.ascontiguousarray(a, dtype=np.float64).reshape(n)
+
+    def clear(self):
+        check(lib().slam_pgo_clear(self.h))
+
+    def add_vertex(self, id, pose7, fixed=False):
+        check(lib().slam_pgo_add_vertex(self.h, int(id), _ptr(self._f64(pose7, 7)), int(bool(fixed))))
+
+    def set_vertex(self, id, pose7):
+        check(lib().slam_pgo_set_vertex(self.h, int(id), _ptr(self._f64(pose7, 7))))
+
+    def add_edge(self, from_, to, meas7, info36):
+        check(lib().slam_pgo_add_edge(self.h, int(from_), int(to), _ptr(self._f64(meas7, 7)), _ptr(self._f64(info36, 36))))
+
+    def size(self):
+        """(vertices, edges)"""
+        nv, ne = C.c_int(), C.c_int()
+        check(lib().slam_pgo_size(self.h, C.byref(nv), C.byref(ne)))
+        return nv.value, ne.value
+
+    def optimize(self, iterations=10, stream=None):
+        """slam_pgo_optimize: the PgoResult; the estimates replace the poses (read_vertices)."""
+        res = PgoResult()
+        check(lib().slam_pgo_optimize(self.h, int(iterations), C.byref(res), _sp(stream)))
+        return res
+
+    def read_vertices(self):
+        """[n, 7] f64, quaternions with w >= 0"""
+        n = self.size()[0]
+        out = np.zeros((n, 7))
+        got = C.c_int()
+        check(lib().slam_pgo_read_vertices(self.h, _ptr(out), n, C.byref(got)))
+        return out
+
+    def chi2(self, stream=None):
+        """slam_pgo_chi2: (chi2, e [edges, 6], chi2 per edge) at the current poses"""
+        ne = self.size()[1]
+        total, e, ce = C.c_double(), np.zeros((ne, 6)), np.zeros(ne)
+        check(lib().slam_pgo_chi2(self.h, C.byref(total), _ptr(e), _ptr(ce), _sp(stream)))
+        return total.value, e, ce
+
+    def read_system(self, stream=None):
+        """slam_pgo_read_system: dict(rows, cols, blocks [k, 6, 6], b [vertices, 6], perm, w) of the undamped system"""
+        nb, nf, w = C.c_int(), C.c_int(), C.c_int()
+        check(lib().slam_pgo_read_system(self.h, None, None, None, 0, C.byref(nb), None, None, C.byref(nf), C.byref(w), _sp(stream)))
+        rows, cols = np.zeros(nb.value, np.int32), np.zeros(nb.value, np.int32)
+        blocks, b, perm = np.zeros((nb.value, 6, 6)), np.zeros((self.size()[0], 6)), np.zeros(nf.value, np.int32)
+        check(lib().slam_pgo_read_system(self.h, _ptr(rows), _ptr(cols), _ptr(blocks), nb.value, C.byref(nb), _ptr(b), _ptr(perm),
+                                         C.byref(nf), C.byref(w), _sp(stream)))
+        return dict(rows=rows, cols=cols, blocks=blocks, b=b, perm=perm, w=w.value)
+
+    def step(self, lam, stream=None):
+        """slam_pgo_step: dict(delta [vertices, 6], chi2_before, chi2_after, scale, pivot) of one trial; applies nothing"""
+        delta = np.zeros((self.size()[0], 6))
+        c0, c1, sc, pv = C.c_double(), C.c_double(), C.c_double(), C.c_int()
+        check(lib().slam_pgo_step(self.h, float(lam), _ptr(delta), C.byref(c0), C.byref(c1), C.byref(sc), C.byref(pv), _sp(stream)))
+        return dict(delta=delta, chi2_before=c0.value, chi2_after=c1.value, scale=sc.value, pivot=pv.value)
+
+    # ---- the calls of slam_amd::PoseGraphOptimizer (include/slam_amd/pose_graph.hpp), graph_slam.cpp's optimiser globals
+    def init_optimizer(self, cur_pose):
+        """initOptimizer (:286-306): an empty graph with vertex 0 fixed at the origin in cur_pose's orientation; the first node's pose"""
+        self.clear()
+        first = np.concatenate([np.zeros(3), self._f64(cur_pose, 7)[3:]])
+        self.add_vertex(0, first, True)
+        return first
+
+    @staticmethod
+    def _tf_yaw(p):
+        """tf::getYaw as slam_amd::graph_detail::tf_yaw computes it"""
+        qx, qy, qz, qw = (float(v) for v in p[3:7])
+        s = 2.0 / (qx * qx + qy * qy + qz * qz + qw * qw)
+        ys, zs = qy * s, qz * s
+        wy, wz, xy, xz, yy, zz = qw * ys, qw * zs, qx * ys, qx * zs, qy * ys, qz * zs
+        m00, m10, m20 = 1.0 - (yy + zz), xy + wz, xz - wy
+        if abs(m20) >= 1.0:
+            return 0.0
+        cp = math.cos(-math.asin(m20))
+        return math.atan2(m10 / cp, m00 / cp)
+
+    @classmethod
+    def pose_offset(cls, pre, post, cur_pose):
+        """graph_slam.cpp:356-384 as written (not a rigid transform; see include/slam_amd/pose_graph.hpp)"""
+        def wrapped(d):
+            return -(d - 2 * math.pi) if d > math.pi else (-(d + 2 * math.pi) if d < -math.pi else d)
+        pre, post, cur = ([float(v) for v in p] for p in (pre, post, cur_pose))
+        vnx, vny, vnz = post[0] - pre[0], post[1] - pre[1], post[2] - pre[2]
+        vnth = wrapped(cls._tf_yaw(post) - cls._tf_yaw(pre))
+        vpx, vpy = cur[0] - pre[0], cur[1] - pre[1]
+        vpth = wrapped(cls._tf_yaw(cur) - cls._tf_yaw(pre))
+        half = (vnth + vpth) * 0.5
+        return np.array([(vpx * math.cos(vnth) + vpy * math.sin(vnth) + vnx) - vpx, (vpy * math.cos(vnth) + vpx * math.sin(vnth) + vny) - vpy,
+                         vnz, 0.0, 0.0, math.sin(half), math.cos(half)])
+
+    def optimize_graph(self, node_poses, cur_pose, iterations=10):
+        """optimizeGraph (:322-390): (the estimates [n, 7] that replace node_poses, the pose offset, the PgoResult)"""
+        node_poses = np.reshape(np.asarray(node_poses, dtype=np.float64), (-1, 7))
+        res = self.optimize(iterations)
+        est = self.read_vertices()[:len(node_poses)]
+        return est, self.pose_offset(node_poses[-1], est[-1], cur_pose), res
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().slam_pgo_destroy(self.h)
             self.h = None
 
     def __del__(self):
