@@ -118,6 +118,8 @@ __device__ inline float list_key_u(float ux, float uy, float x, float y) { retur
 // scans in pairs (one scan per workgroup 0.373 / 0.368 / 0.366 / 0.363); 2 steps instead of 3: the same.
 constexpr int kListWin = 5;
 constexpr int kListWalk = 3;
+constexpr int kListEntries = 2 * kListWin + 1;
+static_assert(8u * (kListEntries - 1) <= kListOverread, "the window reads up to 2 kListWin entries past a list's last");
 
 // An exact tie is noticed through the SECOND best of everything examined (one v_med3_f32 per candidate; a tie is second == best at
 // the end) -- round 4: the flag this replaced (set whenever a candidate equalled the best so far: a compare, an AND and an OR per
@@ -161,23 +163,54 @@ __device__ inline bool list_search(Best &b, float2 &m, const ListPtrs &lp, const
         }
         g = min(blo, e - 1);
     }
-    const int lo = max(a, g - kListWin), hi = min(e - 1, g + kListWin);
-    float d = FLT_MAX, d2nd = FLT_MAX, klo = 0.f, khi = 0.f;
-    int   pos = -1;
+    const int lo = max(a, g - kListWin), hi = min(e - 1, g + kListWin), last = hi - lo;
+    // The window's entries are CONSECUTIVE from lo, read from one address with constant offsets, all issued before the first is
+    // used, and so is pts[hi], whose key the walk needs.  An entry past hi belongs to the next list, or to the tables behind the
+    // last one (kListOverread, icp_model.hpp), and is masked out, not clamped: it counts as FLT_MAX, never as a second pts[hi].
+    const float2 *win = pts + lo;
+    float2        p[kListEntries];
+    float2        pe = win[last];
+    {
+        // eleven ds_read_b64 and one wait, spelled out: plain loads become five ds_read2_b64, which measured no faster than the
+        // parent's clamped reads (docs/NOTEBOOK.md, 2026-10-19).  `win` points into LDS -- a ListPtrs is only ever made by
+        // make_list_ptrs from the workgroup's LDS base (the three fit kernels) -- and the low word of such a pointer is its LDS
+        // address; lists in global memory would need another read here.  The statement ends with every read complete.
+        const unsigned     wa = (unsigned)(unsigned long long)win;
+        unsigned long long w0, w1, w2, w3, w4, w5, w6, w7, w8, w9, w10;
+        asm volatile("ds_read_b64 %0, %11\n\tds_read_b64 %1, %11 offset:8\n\tds_read_b64 %2, %11 offset:16\n\t"
+                     "ds_read_b64 %3, %11 offset:24\n\tds_read_b64 %4, %11 offset:32\n\tds_read_b64 %5, %11 offset:40\n\t"
+                     "ds_read_b64 %6, %11 offset:48\n\tds_read_b64 %7, %11 offset:56\n\tds_read_b64 %8, %11 offset:64\n\t"
+                     "ds_read_b64 %9, %11 offset:72\n\tds_read_b64 %10, %11 offset:80\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&v"(w0), "=&v"(w1), "=&v"(w2), "=&v"(w3), "=&v"(w4), "=&v"(w5), "=&v"(w6), "=&v"(w7), "=&v"(w8), "=&v"(w9),
+                       "=&v"(w10)
+                     : "v"(wa)
+                     : "memory");
+        const unsigned long long w[kListEntries] = {w0, w1, w2, w3, w4, w5, w6, w7, w8, w9, w10};
 #pragma unroll
-    for (int j = 0; j <= 2 * kListWin; ++j) {
-        const int    i = lo + j;
-        const bool   ok = i <= hi;
-        const float2 p = pts[min(i, hi)];
-        const float  dj = ok ? dist2(p, qx, qy) : FLT_MAX;
-        const float  kj = list_key_u(ux, uy, p.x, p.y);
-        if (j == 0) klo = kj;
-        khi = ok ? kj : khi;
-        d2nd = __builtin_amdgcn_fmed3f(d, dj, d2nd);
-        const bool up = dj < d;
-        d = up ? dj : d;
-        pos = up ? i : pos;
+        for (int j = 0; j < kListEntries; ++j) p[j] = make_float2(__int_as_float((int)(unsigned)w[j]), __int_as_float((int)(unsigned)(w[j] >> 32)));
     }
+    // (every entry named here, in no instruction: pts[hi]'s read, a plain load, is issued above this line with the others)
+    static_assert(kListEntries == 11, "the statement below names every entry of the window");
+    asm volatile("" : "+v"(p[0].x), "+v"(p[0].y), "+v"(p[1].x), "+v"(p[1].y), "+v"(p[2].x), "+v"(p[2].y), "+v"(p[3].x), "+v"(p[3].y),
+                      "+v"(p[4].x), "+v"(p[4].y), "+v"(p[5].x), "+v"(p[5].y), "+v"(p[6].x), "+v"(p[6].y), "+v"(p[7].x), "+v"(p[7].y),
+                      "+v"(p[8].x), "+v"(p[8].y), "+v"(p[9].x), "+v"(p[9].y), "+v"(p[10].x), "+v"(p[10].y), "+v"(pe.x), "+v"(pe.y));
+    float        d = FLT_MAX, d2nd = FLT_MAX;
+    int          rel = -0x10000; // the best entry relative to lo; none yet: lo + rel < 0, list positions being 16-bit (start[])
+    // (the distances outside the masking selects: with a distance inside them, the first select becomes a branch around its read)
+    float dd[kListEntries];
+#pragma unroll
+    for (int j = 0; j < kListEntries; ++j) dd[j] = dist2(p[j], qx, qy);
+#pragma unroll
+    for (int j = 1; j < kListEntries; ++j) dd[j] = j <= last ? dd[j] : FLT_MAX;
+#pragma unroll
+    for (int j = 0; j < kListEntries; ++j) { // scan_step, with the minimum as a minimum (no distance here is a NaN): only the
+        const float dj = dd[j];              // position waits for the compare
+        d2nd = __builtin_amdgcn_fmed3f(d, dj, d2nd);
+        rel = dj < d ? j : rel;
+        d = fminf(d, dj);
+    }
+    int         pos = lo + rel;
+    const float klo = list_key_u(ux, uy, p[0].x, p[0].y), khi = list_key_u(ux, uy, pe.x, pe.y);
     // beyond an end whose key distance alone rules it out (on the far side of the query) nothing can beat or
     // tie the best; otherwise walk on from that end
     const float dl = klo - kq, dr = khi - kq;
@@ -280,18 +313,22 @@ struct Team {
 // would wait for a few lanes): its offset goes to the wavefront's region of a queue in LDS (fixed regions:
 // the order does not depend on timing, so sums stay bitwise reproducible) that all wavefronts drain
 // together afterwards (drain_queue).
-template <int MODE>
-__device__ inline void list_pass(const ListPtrs &lp, const ModelView &mv, const FitArgs &fa, const Pose &T, int n, int nga,
-                                 int p0, const double2 P, double acc[kNumAcc], unsigned *wave_cnt, unsigned short *queue,
-                                 int &fell_back, int tid, int &lseed)
+// The passes of an iteration run back to back and share the queue: `qcnt` is how many entries the wavefront's region holds (the
+// same in every lane), an entry is the point's index less `qbase`.  A query that finds its wavefront's region full is searched
+// by its own lane then and there (the exact ring search on the cell index, as the cooperative round would do it): which
+// queries those are depends on the wavefront's own queries alone, so the sums stay reproducible.
+template <typename StartT, int MODE>
+__device__ inline void list_pass(const IndexPtrs<StartT> &ix, const ListPtrs &lp, const ModelView &mv, const FitArgs &fa, const Pose &T,
+                                 int n, int nga, int p0, const double2 P, double acc[kNumAcc], unsigned *wave_cnt,
+                                 unsigned short *queue, int &fell_back, int tid, int &lseed, int &qcnt, int qbase)
 {
     const int  lane = tid & 63, wave = tid >> 6;
     const int  p = p0 + tid;
     const int  cls = MODE == SLAM_ICP_P2L ? 1 : (p < nga ? 0 : 1);                  // a point-to-line model is one class
     const bool valid = p < n && (MODE == SLAM_ICP_P2L || mv.n_cls[cls] > 3); // icpPointToPoint.cpp:59,93
     bool       done = true;
+    float      qx = 0.f, qy = 0.f;
     if (valid) {
-        float  qx, qy;
         Best   b;
         float2 m;
         transform_query(T, P, qx, qy);
@@ -305,8 +342,22 @@ __device__ inline void list_pass(const ListPtrs &lp, const ModelView &mv, const 
         fell_back += done ? 0 : 1;
     }
     const unsigned long long need = __ballot(!done);
-    if (lane == 0) wave_cnt[wave] = (unsigned)__popcll(need);
-    if (!done) queue[wave * 64 + __popcll(need & ((1ull << lane) - 1ull))] = (unsigned short)tid;
+    const int                slot = qcnt + __popcll(need & ((1ull << lane) - 1ull));
+    if (!done) {
+        if (slot < 64) {
+            queue[wave * 64 + slot] = (unsigned short)(p - qbase);
+        } else { // the region is full
+            const double gate = MODE == SLAM_ICP_P2L ? (double)INFINITY : fa.indist;
+            const Best   b = nn_search<1, StartT>(ix, mv, cls, qx, qy, 0, gate);
+            if (MODE == SLAM_ICP_P2L) {
+                if (b.pos >= 0) add_p2l(ix.pts[mv.base[1] + b.pos], reinterpret_cast<const double2 *>(mv.normals)[b.oidx], qx, qy, acc);
+            } else if (b.pos >= 0 && (double)b.d < fa.indist) { // :76
+                add_p2p_xy(mv, ix.pts[mv.base[cls] + b.pos], qx, qy, acc);
+            }
+        }
+    }
+    qcnt = min(64, qcnt + (int)__popcll(need));
+    if (lane == 0) wave_cnt[wave] = (unsigned)qcnt;
 }
 
 // All wavefronts take kCoopPerWave points at a time and search each with kCoop lanes: first the `tail`
@@ -316,7 +367,7 @@ __device__ inline void list_pass(const ListPtrs &lp, const ModelView &mv, const 
 template <typename StartT, bool LISTS, int TB, int MODE>
 __device__ inline void drain_queue(const IndexPtrs<StartT> &ix, const ListPtrs &lp, const ModelView &mv, const FitArgs &fa,
                                    const Pose &T, int off, int n, int nga, int p0, double acc[kNumAcc], int tail,
-                                   const unsigned *wave_cnt, const unsigned short *queue, int tid)
+                                   const unsigned *wave_cnt, const unsigned short *queue, int tid, int qbase)
 {
     constexpr int kW = TeamDims<TB>::kW, kCoopBlock = TeamDims<TB>::kCoopBlock; // kW <= 16: one count per lane of a DPP row
     const int lane = tid & 63, wave = tid >> 6;
@@ -343,7 +394,7 @@ __device__ inline void drain_queue(const IndexPtrs<StartT> &ix, const ListPtrs &
         }
         if (e < total) {
             const bool is_tail = e < tail;
-            const int  p = p0 + (is_tail ? TB + e : (int)queue[min(w, kW - 1) * 64 + (e - tail - excl)]);
+            const int  p = is_tail ? p0 + TB + e : qbase + (int)queue[min(w, kW - 1) * 64 + (e - tail - excl)];
             const int  cls = MODE == SLAM_ICP_P2L ? 1 : (p < nga ? 0 : 1);
             if (MODE == SLAM_ICP_P2L || mv.n_cls[cls] > 3) { // icpPointToPoint.cpp:59,93
                 const double gate = MODE == SLAM_ICP_P2L ? (double)INFINITY : fa.indist; // icpPointToPlane.cpp has no gate
@@ -587,19 +638,27 @@ __device__ __forceinline__ void fit_iterations(const ModelView &mv, const FitArg
             if (SLAM_STAMPS(fa)) c0 = __builtin_amdgcn_s_memtime();
 
             int pass = 0, chain = -1; // chain: the neighbour found in the pass before (kSeedChain)
+            int qcnt = 0;             // list form: entries in the wavefront's region of the queue
             for (int p0 = 0; p0 < n; ++pass) {
                 int rem = n - p0;
                 if (SWEEP) {
-                    // a pass of kBlock points, then the cooperative rounds: the queries the pass left
-                    // undecided and, when fewer than kCoopPerBlock points remain after it, those too
+                    // passes of kBlock points back to back, then ONE cooperative phase: the queries the passes left undecided
+                    // and, when fewer than kCoopPerBlock points remain after the last, those too.  (A queue entry is 16 bits:
+                    // a scan of more points drains after every pass, its entries counted from the pass's first point.)
                     int tail = 0;
+                    const bool one_drain = n <= 0x10000;
+                    const int  qbase = one_drain ? 0 : p0;
                     if (rem > kCoopPerBlock) {
                         const double2 P = (pass == 0 && kKeepPoint) ? Pc0 : (p0 + tid < n ? fa.pts[off + p0 + tid] : Pc0);
                         // (the lane's entry of the iteration before, per pass: the ring form's seed registers are free here)
                         int ls = kListSeed ? (pass == 0 ? sd0 : (pass == 1 ? sd1 : -1)) : -1;
-                        list_pass<MODE>(lp, mv, fa, T, n, nga, p0, P, acc, wave_cnt, queue, fell_back, tid, ls);
+                        list_pass<StartT, MODE>(ix, lp, mv, fa, T, n, nga, p0, P, acc, wave_cnt, queue, fell_back, tid, ls, qcnt, qbase);
                         if (kListSeed) sd0 = pass == 0 ? ls : sd0, sd1 = pass == 1 ? ls : sd1;
                         tail = rem - kBlock;
+                        if (one_drain && tail > kCoopPerBlock) { // (the same for the whole team: n alone decides)
+                            p0 += kBlock;
+                            continue;
+                        }
                         tail = tail > 0 && tail <= kCoopPerBlock ? tail : 0;
                     } else { // a scan shorter than one cooperative round
                         if (lane == 0) wave_cnt[wave] = 0;
@@ -608,9 +667,10 @@ __device__ __forceinline__ void fit_iterations(const ModelView &mv, const FitArg
                     }
                     tm.sync();
                     if (SLAM_STAMPS(fa)) c_mid = __builtin_amdgcn_s_memtime();
-                    drain_queue<StartT, SWEEP == 2, TB, MODE>(ix, lp, mv, fa, T, off, n, nga, p0, acc, tail, wave_cnt, queue, tid);
+                    drain_queue<StartT, SWEEP == 2, TB, MODE>(ix, lp, mv, fa, T, off, n, nga, p0, acc, tail, wave_cnt, queue, tid, qbase);
                     p0 += kBlock + tail;
-                    if (p0 < n) tm.sync(); // the queue is reused by the next pass
+                    qcnt = 0;
+                    if (p0 < n) tm.sync(); // (a scan beyond 16-bit entries) the queue is reused by the next pass
                 } else if (G > 0) {
                     const int p = ring_point(pass);
                     double2   P = pass == 0 ? Pc0 : (pass == 1 ? Pc1 : Pc2);

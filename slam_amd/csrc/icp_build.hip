@@ -265,8 +265,9 @@ __host__ __device__ inline bool accept_list_core(const ListCand &c, const unsign
 #pragma clang fp contract(off)
     if (n_ent[0] > 65535 || n_ent[1] > 65535) return false;
     const int    ncells = (int)(c.nx * c.ny);
-    const size_t bytes = align16(8u * (unsigned)(n_ent[0] + n_ent[1])) + 2 * (size_t)align16(2u * (unsigned)(ncells + 1)) +
-                         2 * (size_t)align16(4u * (unsigned)(ncells / 16 + 1));
+    // (the tables behind the entries are what list_search's window may read past the last list; fewer than 8 cells: padded up)
+    const size_t tables = 2 * (size_t)align16(2u * (unsigned)(ncells + 1)) + 2 * (size_t)align16(4u * (unsigned)(ncells / 16 + 1));
+    const size_t bytes = align16(8u * (unsigned)(n_ent[0] + n_ent[1])) + (tables > kListOverread ? tables : (size_t)kListOverread);
     if ((double)bytes > budget) return false;
     unsigned o = 0;
     lp.loff_pts = o;
@@ -279,7 +280,7 @@ __host__ __device__ inline bool accept_list_core(const ListCand &c, const unsign
         lp.loff_axis[k] = o;
         o = align16(o + 4u * (unsigned)(ncells / 16 + 1));
     }
-    lp.lblob_bytes = o;
+    lp.lblob_bytes = o > lp.loff_start[0] + kListOverread ? o : lp.loff_start[0] + kListOverread;
     lp.lbase[0] = 0;
     lp.lbase[1] = (int)n_ent[0];
     lp.llat.nx = (int)c.nx;

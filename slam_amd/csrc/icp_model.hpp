@@ -22,6 +22,10 @@ constexpr int kCoopPerWave = 64 / kCoop;       // queries a wavefront searches a
 constexpr int kCoopPerBlock = kWaves * kCoopPerWave;
 constexpr unsigned kReduceBytes = (2u * kWaves * kNumAcc + 2u * 8u) * sizeof(double); // reduction + broadcast
 constexpr unsigned kQueueBytes = 4u * kWaves + 2u * kBlock; // per-wavefront counts + 64 u16 entries per wavefront
+// The list form reads a window of consecutive entries without clamping it to its list (list_search): up to this many bytes behind
+// the lists' last entry must lie inside the lists' blob.  The cell tables that follow the entries are that many bytes for every
+// lattice of 8 cells or more; a smaller blob is padded at its end (accept_list_core), so no planned lattice changes.
+constexpr unsigned kListOverread = 96u;
 static_assert(kHoist == 3, "the pass loop selects Pc0, Pc1, Pc2 explicitly");
 static_assert(kWaves == 16 && 16 % kCoop == 0, "drain_queue keeps one wavefront count per lane of a 16-lane DPP row");
 constexpr unsigned kScratchBytes = (kReduceBytes + kQueueBytes + 15u) & ~15u;
