@@ -11,6 +11,9 @@
 //   mapKeyframe() -> map_id, cropBox() -> crop_box(), pose() and map() alike, ok() has no twin (the constructor raises);
 //   an error of the library is printed here and counts as a rejection, there it raises SlamError (the scan keyframe is
 //   removed on both ways out).
+// `carve` (default false, fixed at construction; docs/VOXEL_MAP.md section 8): every accepted cloud, the first included, is
+// carved with trans_full right after it is integrated, and map() and the cropped map a scan registers against are the carved
+// extraction at CARVE_NUM / CARVE_DEN.  While it is false nothing here calls a carve entry point.
 //
 // Stated deviations (docs/VOXEL_MAP.md section 5):
 //   * the start is passed to the solver as `init` instead of moving the source first (:144), so the solver's result is
@@ -40,14 +43,21 @@ public:
     // read at every addCloud: may be changed between calls
     double MAX_SCORE = 1.0;
     double CROP_DIST = 100.0;
+    // free-space carving: the switch is fixed at construction, the ratio and the parameters are read at every call
+    const bool             carve;
+    int                    CARVE_NUM = 1, CARVE_DEN = 1; // a voxel stays while miss * CARVE_DEN <= max(seen, 1) * CARVE_NUM
+    slam_vmap_carve_params carve_params;
+    slam_vmap_carve_result last_carve; // of the last accepted cloud when carve is on
 
     float               trans_full[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     int                 n_clouds = 0, n_accepted = 0;
     slam_kf_gicp_result last;            // the last request's result
     bool                last_valid = false; // false for the first cloud and when nothing of the map was near the pose
 
-    explicit GlobalMapBuilder(double leaf = 0.30, double gate_ = 2.0) : LEAF_SIZE(leaf), gate(gate_), last()
+    explicit GlobalMapBuilder(double leaf = 0.30, double gate_ = 2.0, bool carve_ = false)
+        : LEAF_SIZE(leaf), gate(gate_), carve(carve_), last_carve(), last()
     {
+        slam_vmap_default_carve_params(&carve_params);
         slam_vmap_params vp;
         slam_vmap_default_params(&vp);
         vp.leaf = leaf;
@@ -98,6 +108,7 @@ public:
         if (slam_vmap_info(vmap_, &n_voxels, nullptr, &n_points, nullptr) != SLAM_OK) return warn(), false;
         if (n_points == 0) { // :63-70: the first cloud is the map
             if (slam_vmap_integrate(vmap_, xyz, n, stride, nullptr, nullptr, nullptr) != SLAM_OK) return warn(), false;
+            if (carve && slam_vmap_carve(vmap_, xyz, n, stride, nullptr, nullptr, nullptr, &carve_params, &last_carve) != SLAM_OK) return warn(), false;
             ++n_accepted;
             return true;
         }
@@ -119,7 +130,9 @@ public:
         if (!ok() || slam_vmap_info(vmap_, &n_voxels, nullptr, nullptr, nullptr) != SLAM_OK || n_voxels == 0) return out;
         out.resize(4 * (size_t)n_voxels);
         int n = 0;
-        if (slam_vmap_read(vmap_, nullptr, nullptr, 0, out.data(), nullptr, nullptr, (int)n_voxels, &n) != SLAM_OK) warn(), n = 0;
+        const int rc = carve ? slam_vmap_read_carved(vmap_, nullptr, nullptr, 0, CARVE_NUM, CARVE_DEN, out.data(), nullptr, nullptr, (int)n_voxels, &n)
+                             : slam_vmap_read(vmap_, nullptr, nullptr, 0, out.data(), nullptr, nullptr, (int)n_voxels, &n);
+        if (rc != SLAM_OK) warn(), n = 0;
         out.resize(4 * (size_t)n);
         return out;
     }
@@ -132,7 +145,10 @@ private:
         const int   cap = n_voxels > 0 ? n_voxels : 1;
         int         n_map = 0;
         if (!reserve(&d_map_, &map_cap_, sizeof(float) * 4 * (size_t)cap)) return warn(), false;
-        if (slam_vmap_extract_dev(vmap_, lo, hi, 0, static_cast<float *>(d_map_), nullptr, nullptr, cap, &n_map, nullptr) != SLAM_OK) return warn(), false;
+        const int rx = carve ? slam_vmap_extract_carved_dev(vmap_, lo, hi, 0, CARVE_NUM, CARVE_DEN, static_cast<float *>(d_map_), nullptr, nullptr, cap,
+                                                            &n_map, nullptr)
+                             : slam_vmap_extract_dev(vmap_, lo, hi, 0, static_cast<float *>(d_map_), nullptr, nullptr, cap, &n_map, nullptr);
+        if (rx != SLAM_OK) return warn(), false;
         if (slam_device_synchronize() != SLAM_OK) return warn(), false;
         if (n_map == 0) return false; // nothing of the map near the pose: nothing to register against
         const int rc = map_id_ < 0 ? slam_kf_add_keyframe_dev(store_, static_cast<const float *>(d_map_), n_map, 4, &map_id_, nullptr)
@@ -151,6 +167,8 @@ private:
             t[r] = (double)trans_full[4 * r + 3];
         }
         if (slam_vmap_integrate_dev(vmap_, static_cast<const float *>(d_scan_), n, stride, R, t, nullptr, nullptr) != SLAM_OK) return warn(), false;
+        if (carve && slam_vmap_carve_dev(vmap_, static_cast<const float *>(d_scan_), n, stride, R, t, nullptr, &carve_params, &last_carve, nullptr) != SLAM_OK)
+            return warn(), false;
         return true;
     }
     static bool reserve(void **p, size_t *cap, size_t bytes)

@@ -907,6 +907,54 @@ int  slam_vmap_read_sums(slam_vmap_t *m, int64_t *sums, uint32_t *count, uint64_
 /* occupied voxels, slots of the table, points integrated (dropped ones not counted), bytes of device memory held */
 int  slam_vmap_info(slam_vmap_t *m, int64_t *n_voxels, int64_t *capacity, int64_t *n_points, size_t *device_bytes);
 
+/* Free-space carving (docs/VOXEL_MAP.md section 8; the device equals tests/cpp/vmap_carve_oracle.cpp bit for bit).  Two more
+ * u32 accumulators per voxel, in units of scans: `seen` counts the carve calls whose cloud had an endpoint in the voxel,
+ * `miss` those in which a ray crossed it and no endpoint of that cloud lay in it.  A carve call touches only voxels that
+ * exist: nothing is claimed.
+ *   endpoint  q as slam_vmap_integrate moves and drops it; origin O = the same arithmetic on `origin` (NULL: 0, 0, 0)
+ *   ray       c0 = cell(O), c1 = cell(q), a_k = |c1_k - c0_k|, n = max a_k; the cell of step i is
+ *             c0_k + s_k floor((2 a_k i + n - 1) / (2 n)) per axis (the driving-axis 3-D Bresenham)
+ *   visited   i = 0 .. n - T - 1 with T = max(end_margin, ceil(n tail_num / tail_den)); n > max_ray_cells: not walked
+ *   phases    (1) every voxel holding an endpoint: seen += 1 once; (2) every other voxel visited: miss += 1 once
+ * The planes are allocated at the first carve; a map never carved holds what it held before and answers with zeros. */
+typedef struct {
+    int end_margin;    /* steps before the end cell that are never visited, at least (1) */
+    int tail_num;      /* the last ceil(n tail_num / tail_den) steps of a ray of n steps are not visited (1 / 8) */
+    int tail_den;
+    int max_ray_cells; /* a ray of more steps is not walked and counted in n_skipped (512) */
+} slam_vmap_carve_params;
+
+typedef struct {
+    int64_t n_rays;    /* endpoints kept (n - n_dropped), skipped rays included */
+    int64_t n_dropped; /* points dropped by integrate's rules */
+    int64_t n_skipped; /* rays longer than max_ray_cells */
+    int64_t n_steps;   /* cells visited, existing voxels or not */
+    int64_t n_seen;    /* voxels charged in phase 1 */
+    int64_t n_missed;  /* voxels charged in phase 2 */
+} slam_vmap_carve_result;
+
+void slam_vmap_default_carve_params(slam_vmap_carve_params *p);
+/* Points, stride, R and t as slam_vmap_integrate_dev; origin: 3 doubles in the cloud's frame or NULL; params NULL: the
+ * defaults; result nullable.  SLAM_E_INVALID before anything is launched for stride < 3, tail_den <= 0, a negative
+ * end_margin or tail_num, max_ray_cells < 1, one of R / t without the other, and an origin that has no cell.  WAITS ONCE for
+ * `stream`, to read the counters (the first carve allocates the planes; a call with more rays than any before regrows its
+ * scratch, which waits for the device besides).  One call at a time per handle. */
+int  slam_vmap_carve_dev(slam_vmap_t *m, const float *d_xyz, int n, int stride, const double R[9], const double t[3],
+                         const double origin[3], const slam_vmap_carve_params *params, slam_vmap_carve_result *result,
+                         slam_stream_t stream);
+int  slam_vmap_carve(slam_vmap_t *m, const float *xyz, int n, int stride, const double R[9], const double t[3], const double origin[3],
+                     const slam_vmap_carve_params *params, slam_vmap_carve_result *result);
+/* slam_vmap_extract_dev and slam_vmap_read with one test more: a voxel is kept iff
+ * (uint64) miss * max_miss_den <= (uint64) max(seen, 1) * max_miss_num, equality kept (num >= 0, den > 0; 1 / 1 keeps a voxel
+ * hit at least as often as crossed). */
+int  slam_vmap_extract_carved_dev(slam_vmap_t *m, const float lo_xy[2], const float hi_xy[2], int min_count, int max_miss_num,
+                                  int max_miss_den, float *d_xyz4, uint32_t *d_count, uint64_t *d_key, int cap, int *n_out,
+                                  slam_stream_t stream);
+int  slam_vmap_read_carved(slam_vmap_t *m, const float lo_xy[2], const float hi_xy[2], int min_count, int max_miss_num, int max_miss_den,
+                           float *xyz4, uint32_t *count, uint64_t *key, int cap, int *n_out);
+/* seen and miss of every occupied voxel in ascending key order, as slam_vmap_read_sums; zeros on a map never carved. */
+int  slam_vmap_read_carve(slam_vmap_t *m, uint32_t *seen, uint32_t *miss, uint64_t *key, int cap, int *n_out);
+
 /* -------------------------------------------------------------------------
  * Pose-graph optimiser: graph_slam's optimizeGraph (graph_slam.cpp:322-390), i.e. g2o's VertexSE3 / EdgeSE3 under
  * OptimizationAlgorithmLevenberg, restated in docs/PGO.md (parity with g2o itself is unpinned; the yardstick is

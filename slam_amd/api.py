@@ -114,6 +114,15 @@ class VmapParams(C.Structure):
     _fields_ = [("leaf", C.c_double), ("initial_capacity", C.c_int)]
 
 
+class VmapCarveParams(C.Structure):
+    _fields_ = [("end_margin", C.c_int), ("tail_num", C.c_int), ("tail_den", C.c_int), ("max_ray_cells", C.c_int)]
+
+
+class VmapCarveResult(C.Structure):
+    _fields_ = [("n_rays", C.c_int64), ("n_dropped", C.c_int64), ("n_skipped", C.c_int64), ("n_steps", C.c_int64),
+                ("n_seen", C.c_int64), ("n_missed", C.c_int64)]
+
+
 class PgoParams(C.Structure):
     _fields_ = [("max_trials", C.c_int), ("tau", C.c_double), ("good_lower", C.c_double), ("good_upper", C.c_double),
                 ("ordering", C.c_int), ("max_band_bytes", C.c_size_t)]
@@ -194,6 +203,8 @@ EXPORTS = [
     "slam_csm_score_volume_dev", "slam_csm_read_table", "slam_csm_info",
     "slam_vmap_default_params", "slam_vmap_create", "slam_vmap_destroy", "slam_vmap_clear", "slam_vmap_integrate",
     "slam_vmap_integrate_dev", "slam_vmap_extract_dev", "slam_vmap_read", "slam_vmap_read_sums", "slam_vmap_info",
+    "slam_vmap_default_carve_params", "slam_vmap_carve_dev", "slam_vmap_carve", "slam_vmap_extract_carved_dev", "slam_vmap_read_carved",
+    "slam_vmap_read_carve",
     "slam_pgo_default_params", "slam_pgo_create", "slam_pgo_destroy", "slam_pgo_clear", "slam_pgo_add_vertex",
     "slam_pgo_set_vertex", "slam_pgo_add_edge", "slam_pgo_size", "slam_pgo_optimize", "slam_pgo_read_vertices", "slam_pgo_chi2",
     "slam_pgo_read_system", "slam_pgo_step",
@@ -420,6 +431,13 @@ def lib():
     L.slam_vmap_read.argtypes = [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
     L.slam_vmap_read_sums.argtypes = [_vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
     L.slam_vmap_info.argtypes = [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]
+    L.slam_vmap_default_carve_params.argtypes = [C.POINTER(VmapCarveParams)]
+    L.slam_vmap_default_carve_params.restype = None
+    L.slam_vmap_carve_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(VmapCarveParams), C.POINTER(VmapCarveResult), _vp]
+    L.slam_vmap_carve.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(VmapCarveParams), C.POINTER(VmapCarveResult)]
+    L.slam_vmap_extract_carved_dev.argtypes = [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int), _vp]
+    L.slam_vmap_read_carved.argtypes = [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
+    L.slam_vmap_read_carve.argtypes = [_vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
     _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
     L.slam_pgo_default_params.argtypes = [C.POINTER(PgoParams)]
     L.slam_pgo_default_params.restype = None
@@ -1056,6 +1074,18 @@ def vmap_default_params(**kw):
     return p
 
 
+def vmap_default_carve_params(**kw):
+    p = VmapCarveParams()
+    lib().slam_vmap_default_carve_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def vmap_carve_result_dict(r):
+    return {f: int(getattr(r, f)) for f, _ in VmapCarveResult._fields_}
+
+
 class VoxelMap:
     """The exact sparse voxel map (slam_vmap_*, docs/VOXEL_MAP.md): clouds are integrated in place, each with its own
     transform; a voxel's centroid is the exact mean of its points in units of 2^-20 m, the same bits in any order."""
@@ -1102,28 +1132,68 @@ class VoxelMap:
                                             _sp(stream)))
         return nd.value
 
-    def extract_dev(self, d_xyz4, cap, lo=None, hi=None, min_count=0, d_count=None, d_key=None, stream=None):
-        """slam_vmap_extract_dev: the number of voxels written; SlamError(E_NOMEM) with .needed set when cap is too small."""
+    def carve(self, xyz, R=None, t=None, origin=None, params=None, **kw):
+        """slam_vmap_carve, host array [n, >= 3] f32 and the sensor origin in the cloud's frame (None: 0, 0, 0): the six
+        counters of the call as a dict.  params: a VmapCarveParams, or its fields as keywords over the defaults."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+        xyz = xyz.reshape(-1, xyz.shape[-1] if xyz.ndim > 1 else 3)
+        R, t = self._Rt(R, t)
+        o = None if origin is None else np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        p, r = params or vmap_default_carve_params(**kw), VmapCarveResult()
+        check(lib().slam_vmap_carve(self.h, _ptr(xyz), len(xyz), xyz.shape[1], _ptr(R), _ptr(t), _ptr(o), C.byref(p), C.byref(r)))
+        return vmap_carve_result_dict(r)
+
+    def carve_dev(self, d_xyz, n, stride=3, R=None, t=None, origin=None, params=None, stream=None, **kw):
+        """slam_vmap_carve_dev: as carve, on a device array of n points `stride` floats apart."""
+        R, t = self._Rt(R, t)
+        o = None if origin is None else np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        p, r = params or vmap_default_carve_params(**kw), VmapCarveResult()
+        check(lib().slam_vmap_carve_dev(self.h, getattr(d_xyz, "ptr", d_xyz), int(n), int(stride), _ptr(R), _ptr(t), _ptr(o), C.byref(p),
+                                        C.byref(r), _sp(stream)))
+        return vmap_carve_result_dict(r)
+
+    def read_carve(self):
+        """slam_vmap_read_carve: (seen [n] u32, miss [n] u32, key [n] u64) of every voxel; zeros on a map never carved."""
+        n = self.info()["n_voxels"]
+        seen, miss, key = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint64)
+        got = C.c_int()
+        check(lib().slam_vmap_read_carve(self.h, _ptr(seen), _ptr(miss), _ptr(key), n, C.byref(got)))
+        assert got.value == n
+        return seen, miss, key
+
+    def extract_dev(self, d_xyz4, cap, lo=None, hi=None, min_count=0, d_count=None, d_key=None, stream=None, max_miss=None):
+        """slam_vmap_extract_dev: the number of voxels written; SlamError(E_NOMEM) with .needed set when cap is too small.
+        max_miss = (num, den): slam_vmap_extract_carved_dev, which keeps a voxel iff miss den <= max(seen, 1) num."""
         lo, hi = self._box(lo, hi)
         n = C.c_int()
-        rc = lib().slam_vmap_extract_dev(self.h, _ptr(lo), _ptr(hi), int(min_count), getattr(d_xyz4, "ptr", d_xyz4),
-                                         getattr(d_count, "ptr", d_count), getattr(d_key, "ptr", d_key), int(cap), C.byref(n), _sp(stream))
+        out = (getattr(d_xyz4, "ptr", d_xyz4), getattr(d_count, "ptr", d_count), getattr(d_key, "ptr", d_key), int(cap), C.byref(n), _sp(stream))
+        if max_miss is not None:
+            rc = lib().slam_vmap_extract_carved_dev(self.h, _ptr(lo), _ptr(hi), int(min_count), int(max_miss[0]), int(max_miss[1]), *out)
+        else:
+            rc = lib().slam_vmap_extract_dev(self.h, _ptr(lo), _ptr(hi), int(min_count), *out)
         if rc != SLAM_OK:
             e = SlamError(rc, lib().slam_last_error().decode("utf-8", "replace"))
             e.needed = n.value
             raise e
         return n.value
 
-    def read(self, lo=None, hi=None, min_count=0):
-        """slam_vmap_read: (xyz4 [n, 4] f32, count [n] u32, key [n] u64) in ascending key order."""
+    def read(self, lo=None, hi=None, min_count=0, max_miss=None):
+        """slam_vmap_read: (xyz4 [n, 4] f32, count [n] u32, key [n] u64) in ascending key order.  max_miss = (num, den):
+        slam_vmap_read_carved."""
         lo, hi = self._box(lo, hi)
         n = C.c_int()
-        rc = lib().slam_vmap_read(self.h, _ptr(lo), _ptr(hi), int(min_count), None, None, None, 0, C.byref(n))
+        if max_miss is not None:
+            def call(*out):
+                return lib().slam_vmap_read_carved(self.h, _ptr(lo), _ptr(hi), int(min_count), int(max_miss[0]), int(max_miss[1]), *out)
+        else:
+            def call(*out):
+                return lib().slam_vmap_read(self.h, _ptr(lo), _ptr(hi), int(min_count), *out)
+        rc = call(None, None, None, 0, C.byref(n))
         if rc not in (SLAM_OK, E_NOMEM):
             check(rc)
         xyz4, count, key = np.zeros((n.value, 4), np.float32), np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint64)
         if n.value:
-            check(lib().slam_vmap_read(self.h, _ptr(lo), _ptr(hi), int(min_count), _ptr(xyz4), _ptr(count), _ptr(key), n.value, C.byref(n)))
+            check(call(_ptr(xyz4), _ptr(count), _ptr(key), n.value, C.byref(n)))
         return xyz4, count, key
 
     def read_sums(self):
@@ -1549,12 +1619,16 @@ class GlobalMapBuilder:
     correspond (docs/VOXEL_MAP.md section 5 states the deviations from the reference).  An error of the library raises
     SlamError here (C++ prints it and rejects the cloud); the scan keyframe is removed on every way out."""
 
-    def __init__(self, leaf=0.30, gate=2.0):
+    def __init__(self, leaf=0.30, gate=2.0, carve=False):
         # global_generate.cpp:21-29, :84-90: macros and setup_gicp's values there, members here.  The store and the map are made
         # with the fixed ones (read-only properties below); MAX_SCORE and CROP_DIST are read at every add_cloud
         self._fixed = dict(LEAF_SIZE=float(leaf), gate=float(gate), MAX_ITERATIONS=100, TRANSFORMATION_EPSILON=1e-6,
-                           FITNESS_EPSILON=1e-6, MAX_DIST=4.0)
+                           FITNESS_EPSILON=1e-6, MAX_DIST=4.0, carve=bool(carve))
         self.MAX_SCORE, self.CROP_DIST = 1.0, 100.0
+        # free-space carving (docs/VOXEL_MAP.md section 8): the switch is fixed here, the rest is read at every call
+        self.CARVE_NUM, self.CARVE_DEN = 1, 1
+        self.carve_params = vmap_default_carve_params()
+        self.last_carve = None  # the counters of the last accepted cloud's carve
         self.vmap = VoxelMap(leaf=self.LEAF_SIZE)
         self.store = KeyframeStore(leaf_size=self.LEAF_SIZE, gate=self.gate, transformation_epsilon=self.TRANSFORMATION_EPSILON,
                                    fitness_epsilon=self.FITNESS_EPSILON)
@@ -1573,6 +1647,10 @@ class GlobalMapBuilder:
     TRANSFORMATION_EPSILON = property(lambda self: self._fixed["TRANSFORMATION_EPSILON"])
     FITNESS_EPSILON = property(lambda self: self._fixed["FITNESS_EPSILON"])
     MAX_DIST = property(lambda self: self._fixed["MAX_DIST"])    # kept for the name, without effect: the store's gate rules
+    carve = property(lambda self: self._fixed["carve"])
+
+    def _max_miss(self):
+        return (self.CARVE_NUM, self.CARVE_DEN) if self.carve else None
 
     def pose(self):
         """trans_full: the accumulated transform of the last accepted cloud, 4 x 4 f32."""
@@ -1585,8 +1663,9 @@ class GlobalMapBuilder:
                 np.array([self.CROP_DIST + c[0], self.CROP_DIST + c[1]], np.float32))
 
     def map(self):
-        """The whole map as GlobalMatcher.set_map takes it: [n, 4] f32 (x, y, z, 0) in key order."""
-        return self.vmap.read()[0]
+        """The whole map as GlobalMatcher.set_map takes it: [n, 4] f32 (x, y, z, 0) in key order (the carved extraction
+        when carve is on)."""
+        return self.vmap.read(max_miss=self._max_miss())[0]
 
     def add_cloud(self, xyz):
         """One scan ([n, >= 3] f32, sensor frame): (accepted, result dict of register_gicp or None for the first cloud)."""
@@ -1595,6 +1674,8 @@ class GlobalMapBuilder:
         self.n_clouds += 1
         if self.vmap.info()["n_points"] == 0:      # :63-70: the first cloud is the map
             self.vmap.integrate(a)
+            if self.carve:
+                self.last_carve = self.vmap.carve(a, params=self.carve_params)
             self.n_accepted += 1
             self.last = None
             return True, None
@@ -1604,7 +1685,7 @@ class GlobalMapBuilder:
             lo, hi = self.crop_box()
             cap = max(self.vmap.info()["n_voxels"], 1)
             d_map = DeviceArray((cap, 4), np.float32)
-            n_map = self.vmap.extract_dev(d_map, cap, lo=lo, hi=hi)
+            n_map = self.vmap.extract_dev(d_map, cap, lo=lo, hi=hi, max_miss=self._max_miss())
             synchronize()
             if n_map == 0:                         # nothing of the map near the pose: nothing to register against
                 self.last = None
@@ -1620,6 +1701,8 @@ class GlobalMapBuilder:
             self.trans_full = np.array(r["transform"], np.float32).reshape(4, 4)
             T = self.trans_full.astype(np.float64)
             self.vmap.integrate_dev(d_scan, len(a), a.shape[1], R=T[:3, :3], t=T[:3, 3])
+            if self.carve:
+                self.last_carve = self.vmap.carve_dev(d_scan, len(a), a.shape[1], R=T[:3, :3], t=T[:3, 3], params=self.carve_params)
             self.n_accepted += 1
             return True, r
         finally:

@@ -15,6 +15,12 @@
 //              distinct, so plain stores).  Only ever launched by the host between integrate launches.
 //   extract    flag (count, box) per slot -> rocprim select of the slot indices -> gather their keys -> rocprim radix sort
 //              of (key, slot) -> one lane per voxel writes centroid, count and key.
+//   carve      free-space evidence for voxels that exist (docs/VOXEL_MAP.md section 8; the restatement is
+//              tests/cpp/vmap_carve_oracle.cpp): two u32 planes `seen` and `miss` in units of scans and a u32 `stamp` plane
+//              that makes a voxel count once per call, all three allocated at the first carve.  One lane per ray finds the
+//              endpoint's voxel (phase 1: seen) and the ray's visited length; a rocprim scan over chunks of 64 steps per ray;
+//              one wavefront per chunk, one lane per step, walks the closed form of the driving-axis Bresenham and charges
+//              `miss` (phase 2).  No key is written: the lookup only finds.
 // The hash is the 64-bit finaliser of MurmurHash3 (fmix64: two multiply-xorshift rounds), masked to the table: neighbouring
 // cells differ in the low bits of one 21-bit field, and fmix64 spreads any one-bit difference over the whole word.
 // The probe loop ends after `capacity` slots and then raises the handle's error word; the host keeps the load at one half
@@ -184,6 +190,188 @@ __global__ __launch_bounds__(256) void vmap_write_kernel(Table T, const uint32_t
     if (key_out) key_out[i] = key[i];
 }
 
+// ---------------------------------------------------------------- carve (docs/VOXEL_MAP.md section 8)
+struct Planes {
+    uint32_t *seen, *miss, *stamp;
+};
+struct Carve {
+    int      c0[3]; // the origin's cell
+    int      end_margin, tail_num, tail_den, max_ray_cells;
+    uint32_t tag; // 2 s of the call's serial s: phase 1 stamps 2 s + 1, phase 2 stamps 2 s
+};
+// the carve counters on the device, u64 each
+enum { kcDropped = 0, kcSkipped = 1, kcSteps = 2, kcSeen = 3, kcMissed = 4, kCarveCounters = 5 };
+constexpr int kChunk = 64; // steps per chunk: one wavefront
+
+// The slot that holds `key`, or -1 at the first empty slot (or after `capacity` probes): nothing is written.
+__device__ __forceinline__ long long find_slot(const Table &T, uint64_t key)
+{
+    uint64_t h = fmix64(key) & T.mask;
+    for (uint64_t probe = 0; probe <= T.mask; ++probe, h = (h + 1) & T.mask) {
+        const uint64_t cur = T.key[h];
+        if (cur == key) return (long long)h;
+        if (cur == kEmpty) return -1;
+    }
+    return -1;
+}
+
+// One lane per ray: the endpoint as integrate moves it, its cell, phase 1 (seen, once per voxel and call), the visited
+// length L = max(0, n - T) and the ray's number of chunks.  Lane n writes the scan's closing zero.
+__global__ __launch_bounds__(256) void vmap_carve_rays_kernel(const float *xyz, int n, int stride, Transform X, double leaf, Table T, Planes P,
+                                                              Carve A, int4 *ray, uint32_t *chunks, unsigned long long *ctr)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    uint32_t     L = 0;
+    if (i < (size_t)n) {
+        const float *p = xyz + i * stride;
+        float        q[3] = {p[0], p[1], p[2]};
+        if (X.on) {
+            const double px = q[0], py = q[1], pz = q[2];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                q[k] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(X.r[3 * k], px), __dmul_rn(X.r[3 * k + 1], py)), __dmul_rn(X.r[3 * k + 2], pz)),
+                                        X.t[k]);
+        }
+        uint64_t key = 0;
+        int      c1[3] = {0, 0, 0};
+        bool     keep = true;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float  v = q[k];
+            const double c = floor((double)v / leaf);
+            if (!(fabsf(v) < kCoordLimit) || !(fabs(c) < (double)kCellLimit)) { // written so that a NaN fails both tests
+                keep = false;
+                continue;
+            }
+            c1[k] = (int)c;
+            key |= (uint64_t)((int)c + kCellLimit) << (21 * k);
+        }
+        if (!keep) {
+            atomicAdd(&ctr[kcDropped], 1ull);
+        } else {
+            const long long h = find_slot(T, key);
+            if (h >= 0 && atomicMax(&P.stamp[h], A.tag + 1u) < A.tag + 1u) {
+                atomicAdd(&P.seen[h], 1u);
+                atomicAdd(&ctr[kcSeen], 1ull);
+            }
+            int nn = 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) nn = max(nn, abs(c1[k] - A.c0[k])); // both cells lie inside +-2^20
+            if (nn > A.max_ray_cells) {
+                atomicAdd(&ctr[kcSkipped], 1ull);
+            } else {
+                const long long tail = ((long long)nn * A.tail_num + A.tail_den - 1) / A.tail_den;
+                const long long t = tail > A.end_margin ? tail : (long long)A.end_margin;
+                L = t < nn ? (uint32_t)(nn - t) : 0u;
+            }
+        }
+        ray[i] = make_int4(c1[0], c1[1], c1[2], (int)L);
+        chunks[i] = (L + kChunk - 1) / kChunk;
+    } else if (i == (size_t)n) {
+        chunks[i] = 0;
+    }
+    uint32_t steps = L; // at most 2^21 a lane
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) steps += __shfl_xor(steps, o);
+    if ((threadIdx.x & 63) == 0 && steps) atomicAdd(&ctr[kcSteps], (unsigned long long)steps);
+}
+
+// The cell of step i on one axis: c0 + s floor((2 a i + n - 1) / (2 n)), the closed form of the driving-axis Bresenham
+// (error term 2 a - n, test `> 0` before the step); on the driving axis (a = n) it is c0 + s i.
+__device__ __forceinline__ int carve_cell(int c0, int c1, uint32_t i, uint32_t nn, bool small)
+{
+    const int      d = c1 - c0;
+    const uint32_t a = (uint32_t)abs(d);
+    const uint32_t k = small ? (2u * a * i + nn - 1u) / (2u * nn) : (uint32_t)((2ull * a * i + nn - 1ull) / (2ull * nn));
+    return d < 0 ? c0 - (int)k : c0 + (int)k;
+}
+
+// One wavefront per chunk of 64 steps, one lane per step (phase 2).  offs is the exclusive scan of the rays' chunk counts
+// (offs[n] their number); a wave finds its ray by bisection.  The key plane alone is probed; stamp and miss are touched on a
+// found key only.
+__global__ __launch_bounds__(256) void vmap_carve_walk_kernel(const int4 *ray, const uint32_t *offs, int n, uint32_t max_chunks, Table T, Planes P,
+                                                              Carve A, unsigned long long *ctr)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t n_waves = (uint64_t)gridDim.x * 4;
+    const uint32_t total = min(offs[n], max_chunks);
+    for (uint64_t c = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); c < total; c += n_waves) {
+        int lo = 0, hi = n; // offs[lo] <= c < offs[hi]
+        while (hi - lo > 1) {
+            const int mid = lo + (hi - lo) / 2;
+            if (offs[mid] <= c) lo = mid;
+            else hi = mid;
+        }
+        const int4     r = ray[lo];
+        const uint32_t i = ((uint32_t)c - offs[lo]) * kChunk + lane;
+        if (i >= (uint32_t)r.w) continue;
+        const int c1[3] = {r.x, r.y, r.z};
+        uint32_t  nn = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) nn = max(nn, (uint32_t)abs(c1[k] - A.c0[k]));
+        const bool small = nn < 32768u; // 2 a i + n - 1 < 2^31: the 32-bit division
+        uint64_t   key = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) key |= (uint64_t)(carve_cell(A.c0[k], c1[k], i, nn, small) + kCellLimit) << (21 * k);
+        const long long h = find_slot(T, key);
+        if (h < 0) continue;
+        if (__hip_atomic_load(&P.stamp[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == A.tag + 1u) continue; // an endpoint of this cloud
+        if (atomicMax(&P.stamp[h], A.tag) < A.tag) {
+            atomicAdd(&P.miss[h], 1u);
+            atomicAdd(&ctr[kcMissed], 1ull);
+        }
+    }
+}
+
+// vmap_rehash_kernel for a map that has been carved: seen and miss travel with the voxel (the new stamp plane is zero).
+__global__ __launch_bounds__(256) void vmap_rehash_carved_kernel(Table from, Planes pf, Table to, Planes pt, uint32_t *ctr)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > from.mask) return;
+    const uint64_t key = from.key[i];
+    if (key == kEmpty) return;
+    const long long h = find_or_claim(to, key, ctr + kClaimed);
+    if (h < 0) {
+        atomicExch(&ctr[kError], 1u);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) to.sum[k][h] = from.sum[k][i];
+    to.count[h] = from.count[i];
+    pt.seen[h] = pf.seen[i];
+    pt.miss[h] = pf.miss[i];
+}
+
+// vmap_flag_kernel with the carved rule on top: keep iff miss den <= max(seen, 1) num in u64, equality kept.
+__global__ __launch_bounds__(256) void vmap_flag_carved_kernel(Table T, Planes P, Box box, uint32_t min_count, uint32_t num, uint32_t den,
+                                                               uint8_t *flag)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > T.mask) return;
+    bool           keep = false;
+    const uint32_t c = T.count[i];
+    if (T.key[i] != kEmpty && c >= min_count && c > 0) {
+        const uint32_t seen = P.seen[i];
+        keep = (uint64_t)P.miss[i] * den <= (uint64_t)(seen > 1u ? seen : 1u) * num;
+        if (keep && box.on) {
+            const float x = centroid(T.sum[0][i], c), y = centroid(T.sum[1][i], c);
+            keep = box.lo[0] <= x && x <= box.hi[0] && box.lo[1] <= y && y <= box.hi[1];
+        }
+    }
+    flag[i] = keep ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void vmap_write_carve_kernel(Planes P, const uint32_t *slot, const uint64_t *key, int n, uint32_t *seen,
+                                                               uint32_t *miss, uint64_t *key_out)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)n) return;
+    const uint32_t s = slot[i];
+    if (seen) seen[i] = P.seen[s];
+    if (miss) miss[i] = P.miss[s];
+    if (key_out) key_out[i] = key[i];
+}
+
 inline unsigned blocks_for(uint64_t n) { return (unsigned)((n + 255) / 256); }
 constexpr size_t kSlotBytes = sizeof(uint64_t) + 3 * sizeof(long long) + sizeof(uint32_t);
 
@@ -197,6 +385,13 @@ struct slam_vmap {
     DevMem flag, sel, keys_in, keys_out, sel_sorted, tmp;
     // staging of the host forms
     DevMem stage_in, stage_out;
+    // carve: the three planes (capacity u32 each) and the counters exist from the first carve on; per call the rays' end
+    // cells and visited lengths, their chunk counts and the scan of those
+    DevMem   seen, miss, stamp, cctr, rays, chunks, offs;
+    uint32_t serial = 1; // of the next carve call: 1 .. 2^31 - 2
+
+    bool   carved() const { return stamp.p != nullptr; }
+    Planes planes() const { return Planes{seen.as<uint32_t>(), miss.as<uint32_t>(), stamp.as<uint32_t>()}; }
 
     static Table view(const DevMem &b, int64_t cap)
     {
@@ -239,8 +434,18 @@ int make_room(slam_vmap *m, int64_t n, hipStream_t st)
     DevMem        nt;
     SLAM_TRY(new_table(nt, cap, st));
     SLAM_HIP(hipMemsetAsync(m->ctr.p, 0, kCounters * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(vmap_rehash_kernel, dim3(blocks_for((uint64_t)m->capacity)), dim3(256), 0, st, m->view(), slam_vmap::view(nt, cap),
-                       m->ctr.as<uint32_t>());
+    DevMem np[3]; // seen, miss, stamp of the new table, when the map has been carved
+    if (m->carved()) {
+        for (DevMem &b : np) {
+            SLAM_TRY(b.alloc((size_t)cap * sizeof(uint32_t)));
+            SLAM_HIP(hipMemsetAsync(b.p, 0, (size_t)cap * sizeof(uint32_t), st));
+        }
+        hipLaunchKernelGGL(vmap_rehash_carved_kernel, dim3(blocks_for((uint64_t)m->capacity)), dim3(256), 0, st, m->view(), m->planes(),
+                           slam_vmap::view(nt, cap), Planes{np[0].as<uint32_t>(), np[1].as<uint32_t>(), np[2].as<uint32_t>()}, m->ctr.as<uint32_t>());
+    } else {
+        hipLaunchKernelGGL(vmap_rehash_kernel, dim3(blocks_for((uint64_t)m->capacity)), dim3(256), 0, st, m->view(), slam_vmap::view(nt, cap),
+                           m->ctr.as<uint32_t>());
+    }
     SLAM_HIP(hipGetLastError());
     uint32_t *h = static_cast<uint32_t *>(pinned_scratch(kCounters * sizeof(uint32_t)));
     SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
@@ -249,12 +454,14 @@ int make_room(slam_vmap *m, int64_t n, hipStream_t st)
     SLAM_REQUIRE(!h[kError] && (int64_t)h[kClaimed] == m->n_voxels, SLAM_E_HIP, "slam_vmap: the rehash moved %u of %lld voxels (error word %u)",
                  h[kClaimed], (long long)m->n_voxels, h[kError]);
     m->table = std::move(nt);
+    if (m->carved()) m->seen = std::move(np[0]), m->miss = std::move(np[1]), m->stamp = std::move(np[2]);
     m->capacity = cap;
     return SLAM_OK;
 }
 
 // The qualifying slots into m->sel and their number into *n: waits for st once.
-int select_slots(slam_vmap *m, const float lo[2], const float hi[2], int min_count, hipStream_t st, int64_t *n)
+// `ratio` = {num, den} adds the carved rule; a map never carved has miss = 0 everywhere, which every ratio keeps.
+int select_slots(slam_vmap *m, const float lo[2], const float hi[2], int min_count, hipStream_t st, int64_t *n, const uint32_t *ratio = nullptr)
 {
     const uint64_t cap = (uint64_t)m->capacity;
     SLAM_TRY(m->flag.reserve(cap));
@@ -263,7 +470,11 @@ int select_slots(slam_vmap *m, const float lo[2], const float hi[2], int min_cou
     box.on = lo != nullptr;
     if (lo) box.lo[0] = lo[0], box.lo[1] = lo[1], box.hi[0] = hi[0], box.hi[1] = hi[1];
     uint32_t *d_n = m->ctr.as<uint32_t>() + kSelected;
-    hipLaunchKernelGGL(vmap_flag_kernel, dim3(blocks_for(cap)), dim3(256), 0, st, m->view(), box, (uint32_t)min_count, m->flag.as<uint8_t>());
+    if (ratio && m->carved())
+        hipLaunchKernelGGL(vmap_flag_carved_kernel, dim3(blocks_for(cap)), dim3(256), 0, st, m->view(), m->planes(), box, (uint32_t)min_count, ratio[0],
+                           ratio[1], m->flag.as<uint8_t>());
+    else
+        hipLaunchKernelGGL(vmap_flag_kernel, dim3(blocks_for(cap)), dim3(256), 0, st, m->view(), box, (uint32_t)min_count, m->flag.as<uint8_t>());
     SLAM_HIP(hipGetLastError());
     size_t tb = 0;
     SLAM_HIP(rocprim::select(nullptr, tb, rocprim::counting_iterator<uint32_t>(0), m->flag.as<uint8_t>(), m->sel.as<uint32_t>(), d_n, (size_t)cap, st));
@@ -278,10 +489,9 @@ int select_slots(slam_vmap *m, const float lo[2], const float hi[2], int min_cou
     return SLAM_OK;
 }
 
-// The n selected slots in key order into the caller's device arrays: asynchronous.
-int sort_and_write(slam_vmap *m, int n, float *d_xyz4, uint32_t *d_count, uint64_t *d_key, hipStream_t st, int64_t *d_sums = nullptr)
+// The n selected slots in key order into m->sel_sorted, their keys into m->keys_out: asynchronous.
+int sort_slots(slam_vmap *m, int n, hipStream_t st)
 {
-    if (n == 0) return SLAM_OK;
     SLAM_TRY(reserve_quarter(m->keys_in, (size_t)n * sizeof(uint64_t)));
     SLAM_TRY(reserve_quarter(m->keys_out, (size_t)n * sizeof(uint64_t)));
     SLAM_TRY(reserve_quarter(m->sel_sorted, (size_t)n * sizeof(uint32_t)));
@@ -298,6 +508,14 @@ int sort_and_write(slam_vmap *m, int n, float *d_xyz4, uint32_t *d_count, uint64
     tb = m->tmp.cap;
     SLAM_HIP(rocprim::radix_sort_pairs(m->tmp.p, tb, m->keys_in.as<uint64_t>(), m->keys_out.as<uint64_t>(), m->sel.as<uint32_t>(),
                                        m->sel_sorted.as<uint32_t>(), (size_t)n, 0, 63, st));
+    return SLAM_OK;
+}
+
+// The n selected slots in key order into the caller's device arrays: asynchronous.
+int sort_and_write(slam_vmap *m, int n, float *d_xyz4, uint32_t *d_count, uint64_t *d_key, hipStream_t st, int64_t *d_sums = nullptr)
+{
+    if (n == 0) return SLAM_OK;
+    SLAM_TRY(sort_slots(m, n, st));
     hipLaunchKernelGGL(vmap_write_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, st, m->view(), m->sel_sorted.as<uint32_t>(),
                        m->keys_out.as<uint64_t>(), n, d_xyz4, d_count, d_key, d_sums);
     SLAM_HIP(hipGetLastError());
@@ -363,6 +581,8 @@ int slam_vmap_clear(slam_vmap_t *m, slam_stream_t stream)
     hipStream_t st = as_stream(stream);
     SLAM_HIP(hipMemsetAsync(m->table.p, 0xff, (size_t)m->capacity * 8, st));
     SLAM_HIP(hipMemsetAsync(m->table.as<uint8_t>() + (size_t)m->capacity * 8, 0, (size_t)m->capacity * (kSlotBytes - 8), st));
+    if (m->carved())
+        for (DevMem *b : {&m->seen, &m->miss, &m->stamp}) SLAM_HIP(hipMemsetAsync(b->p, 0, (size_t)m->capacity * sizeof(uint32_t), st));
     m->n_voxels = m->n_points = 0;
     return SLAM_OK;
 }
@@ -423,11 +643,11 @@ int slam_vmap_extract_dev(slam_vmap_t *m, const float lo_xy[2], const float hi_x
 }
 
 static int read_host(const char *who, slam_vmap_t *m, const float lo_xy[2], const float hi_xy[2], int min_count, float *xyz4, uint32_t *count,
-                     uint64_t *key, int64_t *sums, int cap, int *n_out)
+                     uint64_t *key, int64_t *sums, int cap, int *n_out, const uint32_t *ratio = nullptr)
 {
     SLAM_TRY(check_extract(who, m, lo_xy, hi_xy, min_count, cap, n_out));
     int64_t n = 0;
-    SLAM_TRY(select_slots(m, lo_xy, hi_xy, min_count, nullptr, &n));
+    SLAM_TRY(select_slots(m, lo_xy, hi_xy, min_count, nullptr, &n, ratio));
     *n_out = (int)n;
     SLAM_REQUIRE(n <= cap, SLAM_E_NOMEM, "%s: %lld voxels, room for %d", who, (long long)n, cap);
     if (n == 0) return SLAM_OK;
@@ -465,7 +685,193 @@ int slam_vmap_info(slam_vmap_t *m, int64_t *n_voxels, int64_t *capacity, int64_t
     if (n_points) *n_points = m->n_points;
     if (device_bytes)
         *device_bytes = m->table.cap + m->ctr.cap + m->flag.cap + m->sel.cap + m->keys_in.cap + m->keys_out.cap + m->sel_sorted.cap + m->tmp.cap +
-                        m->stage_in.cap + m->stage_out.cap;
+                        m->stage_in.cap + m->stage_out.cap + m->seen.cap + m->miss.cap + m->stamp.cap + m->cctr.cap + m->rays.cap + m->chunks.cap +
+                        m->offs.cap;
+    return SLAM_OK;
+}
+
+// ---------------------------------------------------------------- carve (docs/VOXEL_MAP.md section 8)
+void slam_vmap_default_carve_params(slam_vmap_carve_params *p)
+{
+    if (!p) return;
+    p->end_margin = 1;
+    p->tail_num = 1, p->tail_den = 8;
+    p->max_ray_cells = 512;
+}
+
+// Everything that can be refused without a handle, then the device, then the handle: a machine without a device answers
+// SLAM_E_NO_DEVICE to well-formed arguments (no handle can exist there).
+static int check_carve(const char *who, slam_vmap *m, const void *xyz, int n, int stride, const double *R, const double *t,
+                       const slam_vmap_carve_params &p)
+{
+    SLAM_REQUIRE(n >= 0 && stride >= 3 && (xyz || n == 0) && (R == nullptr) == (t == nullptr), SLAM_E_INVALID,
+                 "%s: n >= 0, stride >= 3, points, and R and t both or neither", who);
+    SLAM_REQUIRE(p.end_margin >= 0 && p.tail_num >= 0 && p.tail_den > 0 && p.max_ray_cells >= 1, SLAM_E_INVALID,
+                 "%s: end_margin >= 0, tail_num >= 0, tail_den > 0 and max_ray_cells >= 1", who);
+    SLAM_TRY(require_device());
+    SLAM_REQUIRE(m, SLAM_E_INVALID, "%s: map is NULL", who);
+    return SLAM_OK;
+}
+
+int slam_vmap_carve_dev(slam_vmap_t *m, const float *d_xyz, int n, int stride, const double R[9], const double t[3], const double origin[3],
+                        const slam_vmap_carve_params *params, slam_vmap_carve_result *result, slam_stream_t stream)
+{
+    slam_vmap_carve_params p;
+    slam_vmap_default_carve_params(&p);
+    if (params) p = *params;
+    SLAM_TRY(check_carve("slam_vmap_carve_dev", m, d_xyz, n, stride, R, t, p));
+    if (result) *result = slam_vmap_carve_result{};
+    Transform X{};
+    X.on = R != nullptr;
+    if (R) {
+        for (int k = 0; k < 9; ++k) X.r[k] = R[k];
+        for (int k = 0; k < 3; ++k) X.t[k] = t[k];
+    }
+    // the origin and its cell, with a point's arithmetic (this file is compiled without contraction): decided before any launch
+    Carve A{};
+    const double o[3] = {origin ? origin[0] : 0.0, origin ? origin[1] : 0.0, origin ? origin[2] : 0.0};
+    for (int k = 0; k < 3; ++k) {
+        float v = (float)o[k];
+        if (R) {
+            const double a = R[3 * k] * o[0], b = R[3 * k + 1] * o[1], c = R[3 * k + 2] * o[2];
+            v = (float)(((a + b) + c) + t[k]);
+        }
+        const double c = std::floor((double)v / m->P.leaf);
+        SLAM_REQUIRE(std::fabs(v) < kCoordLimit && std::fabs(c) < (double)kCellLimit, SLAM_E_INVALID,
+                     "slam_vmap_carve: the origin has no cell (axis %d: %g)", k, (double)v);
+        A.c0[k] = (int)c;
+    }
+    A.end_margin = p.end_margin, A.tail_num = p.tail_num, A.tail_den = p.tail_den, A.max_ray_cells = p.max_ray_cells;
+    if (n == 0) return SLAM_OK;
+    // chunks travel as u32 through the scan: a ray has at most 2^21 cells
+    const int64_t longest = p.max_ray_cells < 2 * kCellLimit ? p.max_ray_cells : 2 * kCellLimit;
+    const int64_t max_chunks = (int64_t)n * ((longest + kChunk - 1) / kChunk);
+    SLAM_REQUIRE(max_chunks < (1ll << 32), SLAM_E_NOMEM, "slam_vmap_carve: %d rays of up to %lld cells are more than 2^32 chunks of %d steps", n,
+                 (long long)longest, kChunk);
+
+    hipStream_t  st = as_stream(stream);
+    const size_t plane = (size_t)m->capacity * sizeof(uint32_t);
+    if (!m->carved()) {
+        SLAM_TRY(m->cctr.alloc(kCarveCounters * sizeof(unsigned long long)));
+        SLAM_TRY(m->seen.alloc(plane));
+        SLAM_TRY(m->miss.alloc(plane));
+        SLAM_HIP(hipMemsetAsync(m->seen.p, 0, plane, st));
+        SLAM_HIP(hipMemsetAsync(m->miss.p, 0, plane, st));
+        SLAM_TRY(m->stamp.alloc(plane)); // last: carved() is true only when all three stand
+        SLAM_HIP(hipMemsetAsync(m->stamp.p, 0, plane, st));
+    }
+    if (m->serial >= 0x7fffffffu) { // 2 s + 1 would no longer fit: forget every stamp and start again
+        SLAM_HIP(hipMemsetAsync(m->stamp.p, 0, plane, st));
+        m->serial = 1;
+    }
+    A.tag = 2u * m->serial++;
+    SLAM_TRY(reserve_quarter(m->rays, (size_t)n * sizeof(int4)));
+    SLAM_TRY(reserve_quarter(m->chunks, ((size_t)n + 1) * sizeof(uint32_t)));
+    SLAM_TRY(reserve_quarter(m->offs, ((size_t)n + 1) * sizeof(uint32_t)));
+    size_t tb = 0;
+    SLAM_HIP(rocprim::exclusive_scan(nullptr, tb, m->chunks.as<uint32_t>(), m->offs.as<uint32_t>(), 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
+    SLAM_TRY(m->tmp.reserve(tb + 16));
+    tb = m->tmp.cap;
+    unsigned long long *h = static_cast<unsigned long long *>(pinned_scratch(kCarveCounters * sizeof(unsigned long long)));
+    SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
+
+    unsigned long long *d_ctr = m->cctr.as<unsigned long long>();
+    SLAM_HIP(hipMemsetAsync(d_ctr, 0, kCarveCounters * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(vmap_carve_rays_kernel, dim3(blocks_for((uint64_t)n + 1)), dim3(256), 0, st, d_xyz, n, stride, X, m->P.leaf, m->view(),
+                       m->planes(), A, m->rays.as<int4>(), m->chunks.as<uint32_t>(), d_ctr);
+    SLAM_HIP(hipGetLastError());
+    SLAM_HIP(rocprim::exclusive_scan(m->tmp.p, tb, m->chunks.as<uint32_t>(), m->offs.as<uint32_t>(), 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
+    // one wave per chunk, four to a block; beyond 2048 blocks the waves stride over the chunks
+    const int64_t blocks = (max_chunks + 3) / 4;
+    hipLaunchKernelGGL(vmap_carve_walk_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, m->rays.as<int4>(),
+                       m->offs.as<uint32_t>(), n, (uint32_t)max_chunks, m->view(), m->planes(), A, d_ctr);
+    SLAM_HIP(hipGetLastError());
+    SLAM_HIP(hipMemcpyAsync(h, d_ctr, kCarveCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    SLAM_HIP(hipStreamSynchronize(st));
+    if (result) {
+        result->n_dropped = (int64_t)h[kcDropped];
+        result->n_rays = (int64_t)n - result->n_dropped;
+        result->n_skipped = (int64_t)h[kcSkipped];
+        result->n_steps = (int64_t)h[kcSteps];
+        result->n_seen = (int64_t)h[kcSeen];
+        result->n_missed = (int64_t)h[kcMissed];
+    }
+    return SLAM_OK;
+}
+
+int slam_vmap_carve(slam_vmap_t *m, const float *xyz, int n, int stride, const double R[9], const double t[3], const double origin[3],
+                    const slam_vmap_carve_params *params, slam_vmap_carve_result *result)
+{
+    slam_vmap_carve_params p;
+    slam_vmap_default_carve_params(&p);
+    if (params) p = *params;
+    SLAM_TRY(check_carve("slam_vmap_carve", m, xyz, n, stride, R, t, p));
+    const size_t bytes = (size_t)n * stride * sizeof(float);
+    if (n > 0) {
+        SLAM_TRY(reserve_quarter(m->stage_in, bytes));
+        SLAM_HIP(hipMemcpy(m->stage_in.p, xyz, bytes, hipMemcpyHostToDevice));
+    }
+    return slam_vmap_carve_dev(m, m->stage_in.as<float>(), n, stride, R, t, origin, params, result, nullptr);
+}
+
+static int check_carved(const char *who, slam_vmap *m, const float *lo, const float *hi, int min_count, int num, int den, int cap, int *n_out)
+{
+    SLAM_REQUIRE(n_out && cap >= 0 && min_count >= 0 && (lo == nullptr) == (hi == nullptr) && num >= 0 && den > 0, SLAM_E_INVALID,
+                 "%s: n_out, cap >= 0, min_count >= 0, lo_xy and hi_xy both or neither, max_miss_num >= 0 and max_miss_den > 0", who);
+    SLAM_TRY(require_device());
+    SLAM_REQUIRE(m, SLAM_E_INVALID, "%s: map is NULL", who);
+    return SLAM_OK;
+}
+
+int slam_vmap_extract_carved_dev(slam_vmap_t *m, const float lo_xy[2], const float hi_xy[2], int min_count, int max_miss_num, int max_miss_den,
+                                 float *d_xyz4, uint32_t *d_count, uint64_t *d_key, int cap, int *n_out, slam_stream_t stream)
+{
+    SLAM_TRY(check_carved("slam_vmap_extract_carved_dev", m, lo_xy, hi_xy, min_count, max_miss_num, max_miss_den, cap, n_out));
+    hipStream_t    st = as_stream(stream);
+    int64_t        n = 0;
+    const uint32_t ratio[2] = {(uint32_t)max_miss_num, (uint32_t)max_miss_den};
+    SLAM_TRY(select_slots(m, lo_xy, hi_xy, min_count, st, &n, ratio));
+    *n_out = (int)n;
+    SLAM_REQUIRE(n <= cap, SLAM_E_NOMEM, "slam_vmap_extract_carved_dev: %lld voxels, room for %d", (long long)n, cap);
+    return sort_and_write(m, (int)n, d_xyz4, d_count, d_key, st);
+}
+
+int slam_vmap_read_carved(slam_vmap_t *m, const float lo_xy[2], const float hi_xy[2], int min_count, int max_miss_num, int max_miss_den,
+                          float *xyz4, uint32_t *count, uint64_t *key, int cap, int *n_out)
+{
+    SLAM_TRY(check_carved("slam_vmap_read_carved", m, lo_xy, hi_xy, min_count, max_miss_num, max_miss_den, cap, n_out));
+    const uint32_t ratio[2] = {(uint32_t)max_miss_num, (uint32_t)max_miss_den};
+    return read_host("slam_vmap_read_carved", m, lo_xy, hi_xy, min_count, xyz4, count, key, nullptr, cap, n_out, ratio);
+}
+
+int slam_vmap_read_carve(slam_vmap_t *m, uint32_t *seen, uint32_t *miss, uint64_t *key, int cap, int *n_out)
+{
+    SLAM_REQUIRE(n_out && cap >= 0, SLAM_E_INVALID, "slam_vmap_read_carve: n_out and cap >= 0");
+    SLAM_TRY(require_device());
+    SLAM_REQUIRE(m, SLAM_E_INVALID, "slam_vmap_read_carve: map is NULL");
+    int64_t n = 0;
+    SLAM_TRY(select_slots(m, nullptr, nullptr, 0, nullptr, &n));
+    *n_out = (int)n;
+    SLAM_REQUIRE(n <= cap, SLAM_E_NOMEM, "slam_vmap_read_carve: %lld voxels, room for %d", (long long)n, cap);
+    if (n == 0) return SLAM_OK;
+    const size_t N = (size_t)n;
+    SLAM_TRY(reserve_quarter(m->stage_out, N * 16)); // keys, then seen, then miss
+    uint64_t *d_key = m->stage_out.as<uint64_t>();
+    uint32_t *d_seen = reinterpret_cast<uint32_t *>(d_key + N), *d_miss = d_seen + N;
+    SLAM_TRY(sort_slots(m, (int)n, nullptr));
+    if (m->carved()) {
+        hipLaunchKernelGGL(vmap_write_carve_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, nullptr, m->planes(), m->sel_sorted.as<uint32_t>(),
+                           m->keys_out.as<uint64_t>(), (int)n, d_seen, d_miss, d_key);
+        SLAM_HIP(hipGetLastError());
+        if (seen) SLAM_HIP(hipMemcpy(seen, d_seen, N * 4, hipMemcpyDeviceToHost));
+        if (miss) SLAM_HIP(hipMemcpy(miss, d_miss, N * 4, hipMemcpyDeviceToHost));
+        if (key) SLAM_HIP(hipMemcpy(key, d_key, N * 8, hipMemcpyDeviceToHost));
+    } else { // never carved: zeros, and the keys as the sort left them
+        if (seen) std::memset(seen, 0, N * 4);
+        if (miss) std::memset(miss, 0, N * 4);
+        if (key) SLAM_HIP(hipMemcpy(key, m->keys_out.p, N * 8, hipMemcpyDeviceToHost));
+    }
+    SLAM_HIP(hipStreamSynchronize(nullptr));
     return SLAM_OK;
 }
 
