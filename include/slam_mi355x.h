@@ -246,6 +246,13 @@ int slam_icp_build_info(slam_icp_t *icp, int *on_device, double ms[4]);
 /* The index as it lies in HBM: which = 0 the cell index, 1 the halo lists (0 bytes when the model has
  * none).  bytes (optional) receives the size; buf (optional, cap bytes) the content.  Synchronous. */
 int slam_icp_index_blob(slam_icp_t *icp, int which, void *buf, size_t cap, size_t *bytes);
+/* The model as the index holds it: the points of class cls (0 GA, 1 NGA) as f32 xy in their ORIGINAL order within the
+ * class -- the cell sort undone with the index's own original-index array -- into xy (room for cap points; null with
+ * cap = 0 to ask for the count).  *n receives the class's count; with cap < *n nothing is written and the call returns
+ * SLAM_E_NOMEM.  A point-to-line handle has one class (1: GA then NGA); its class 0 answers 0 points.  Copies the index to
+ * the host and scatters there: no kernel.  Waits for the whole device.  An index entry that names no point of its class
+ * (it cannot happen in a sound index) is SLAM_E_HIP. */
+int slam_icp_read_model(slam_icp_t *icp, int cls, float *xy, int cap, int *n);
 /* The default point-to-point schedule: two_forms = 1 when the halo lists fit LDS for this model (the ring
  * search then runs at least the first `first_iterations` iterations of a scan and the list sweeps the rest, in
  * one launch: the workgroup swaps its LDS contents); list lattice pitch, halo and certified radius in metres,

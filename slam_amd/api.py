@@ -168,7 +168,7 @@ EXPORTS = [
     "slam_device_synchronize", "slam_event_create", "slam_event_destroy", "slam_event_record",
     "slam_event_synchronize", "slam_event_query", "slam_event_elapsed_ms",
     "slam_icp_default_params", "slam_icp_create", "slam_icp_create_dev", "slam_icp_destroy",
-    "slam_icp_build_info", "slam_icp_index_blob",
+    "slam_icp_build_info", "slam_icp_index_blob", "slam_icp_read_model",
     "slam_icp_set_max_iterations", "slam_icp_set_min_delta", "slam_icp_set_subsampling_step",
     "slam_icp_fit", "slam_icp_fit_batch_dev", "slam_icp_fit_batch_from_dev", "slam_icp_nearest_dev", "slam_icp_get_edge_weight",
     "slam_icp_get_normals",
@@ -284,6 +284,7 @@ def lib():
     L.slam_icp_create_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(IcpParams), C.POINTER(_vp)]
     L.slam_icp_build_info.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.slam_icp_index_blob.argtypes = [_vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.slam_icp_read_model.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_int)]
     L.slam_icp_destroy.argtypes = [_vp]
     L.slam_icp_set_max_iterations.argtypes = [_vp, C.c_int]
     L.slam_icp_set_min_delta.argtypes = [_vp, C.c_double]
@@ -711,6 +712,17 @@ class Icp:
         if n.value:
             check(lib().slam_icp_index_blob(self.h, int(which), _ptr(buf), n.value, None))
         return buf
+
+    def read_model(self, cls):
+        """The points of class cls (0 GA, 1 NGA) as the index holds them: f32 xy in original order within the class."""
+        n = C.c_int(0)
+        rc = lib().slam_icp_read_model(self.h, int(cls), None, 0, C.byref(n))    # the count: E_NOMEM says "more than 0"
+        if rc not in (SLAM_OK, E_NOMEM):
+            check(rc)
+        out =np.zeros((n.value, 2), np.float32)
+        if n.value:
+            check(lib().slam_icp_read_model(self.h, int(cls), _ptr(out), n.value, C.byref(n)))
+        return out
 
     def set_max_iterations(self, v):
         check(lib().slam_icp_set_max_iterations(self.h, int(v)))
@@ -1890,15 +1902,31 @@ class Mapper:
         check(lib().slam_mapper_stats(self.h, C.byref(c), C.byref(m), C.byref(r), C.byref(ms), rows))
         return dict(chunks=c.value, merges=m.value, rebuilds=r.value, rebuild_ms=ms.value, last_merge_rows=(rows[0], rows[1]))
 
-    def target_index_info(self):
+    def _with_target(self, read):
+        """read(icp) on the current target, borrowed from the mapper: the handle is not closed here"""
         h = _vp()
         check(lib().slam_mapper_target(self.h, C.byref(h)))
         icp = object.__new__(Icp)
         icp.h = h.value
-        info = icp.index_info()
-        info["built_on_device"], info["build_host_ms"] = icp.build_info()
-        icp.h = None
-        return info
+        try:
+            return read(icp)
+        finally:
+            icp.h = None
+
+    def target_index_info(self):
+        def read(icp):
+            info = icp.index_info()
+            info["built_on_device"], info["build_host_ms"] = icp.build_info()
+            return info
+        return self._with_target(read)
+
+    def target_model(self):
+        """The current target's points as its index holds them: (ga[n,2] f32, nga[m,2] f32), each in original order."""
+        return self._with_target(lambda icp: (icp.read_model(0), icp.read_model(1)))
+
+    def target_index_blobs(self):
+        """The current target's cell index and halo lists as they lie in HBM (Icp.index_blob 0 and 1)."""
+        return self._with_target(lambda icp: (icp.index_blob(0), icp.index_blob(1)))
 
     def use_comm(self, comm):
         check(rccl_lib().slam_mapper_use_comm(self.h, comm.h))

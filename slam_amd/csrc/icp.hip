@@ -1494,6 +1494,39 @@ int slam_icp_index_blob(slam_icp_t *icp, int which, void *buf, size_t cap, size_
     return SLAM_OK;
 }
 
+int slam_icp_read_model(slam_icp_t *icp, int cls, float *xy, int cap, int *n)
+{
+    SLAM_REQUIRE(icp && (cls == 0 || cls == 1) && n && cap >= 0 && (xy || cap == 0), SLAM_E_INVALID, "slam_icp_read_model: bad arguments");
+    const ModelView &mv = icp->mv;
+    const int        cnt = mv.n_cls[cls];
+    *n = cnt;
+    if (cnt <= 0) return SLAM_OK;
+    SLAM_REQUIRE(cap >= cnt, SLAM_E_NOMEM, "slam_icp_read_model: room for %d points, class %d has %d", cap, cls, cnt);
+    SLAM_REQUIRE(icp->d_blob.p && mv.blob_bytes, SLAM_E_INVALID, "slam_icp_read_model: the handle has no index");
+    SLAM_HIP(hipDeviceSynchronize());
+    std::vector<unsigned char> blob(mv.blob_bytes);
+    SLAM_HIP(hipMemcpy(blob.data(), icp->d_blob.p, mv.blob_bytes, hipMemcpyDeviceToHost));
+    const size_t esz = icp->start32 ? 4 : 2, first = (size_t)mv.base[cls];
+    SLAM_REQUIRE(mv.off_pts + 8 * (first + (size_t)cnt) <= mv.blob_bytes && mv.off_oidx + esz * (first + (size_t)cnt) <= mv.blob_bytes, SLAM_E_HIP,
+                 "slam_icp_read_model: the index's layout does not hold its %d points", cnt);
+    const unsigned char *pts = blob.data() + mv.off_pts, *oidx = blob.data() + mv.off_oidx;
+    std::vector<unsigned char> seen((size_t)cnt, 0);
+    for (size_t pos = first; pos < first + (size_t)cnt; ++pos) {
+        uint32_t o32 = 0;
+        uint16_t o16 = 0;
+        if (icp->start32)
+            memcpy(&o32, oidx + 4 * pos, 4);
+        else
+            memcpy(&o16, oidx + 2 * pos, 2), o32 = o16;
+        // (every original index once: anything else is a broken index, and the caller's buffer ends at cap)
+        SLAM_REQUIRE(o32 < (uint32_t)cnt && !seen[o32], SLAM_E_HIP, "slam_icp_read_model: entry %zu of class %d names original index %u of %d",
+                     pos - first, cls, o32, cnt);
+        seen[o32] = 1;
+        memcpy(xy + 2 * (size_t)o32, pts + 8 * pos, 8);
+    }
+    return SLAM_OK;
+}
+
 int slam_icp_set_max_iterations(slam_icp_t *icp, int val)
 {
     SLAM_REQUIRE(icp, SLAM_E_INVALID, "null handle");

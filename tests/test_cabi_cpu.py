@@ -53,6 +53,17 @@ def test_argument_errors_do_not_need_a_device(L):
     assert L.slam_grid_create(0, 10, 0.1, None, C.byref(h)) == api.E_INVALID
 
 
+def test_read_model_is_exported_and_checks_its_arguments(L):
+    """slam_icp_read_model: declared, exported, bound with pointer signatures, and its argument errors need no device"""
+    assert "slam_icp_read_model" in header_functions() and "slam_icp_read_model" in api.EXPORTS
+    f = L.slam_icp_read_model
+    assert f.argtypes is not None and len(f.argtypes) == 5
+    n = C.c_int(-7)
+    assert f(None, 0, None, 0, C.byref(n)) == api.E_INVALID and b"slam_icp_read_model" in L.slam_last_error()
+    assert n.value == -7                                    # nothing written on a refused call
+    assert callable(api.Icp.read_model) and callable(api.Mapper.target_model)
+
+
 def _no_gpu():
     return api.device_count() == 0
 
