@@ -4,6 +4,9 @@
 //   graphSlamGetKNN         :72-106    getKNN
 //   calcEdgeIcp             :218-364   calcEdgeIcp / calcEdges (a batch in one device call)
 //   graph_slam.cpp:508-518             addEdgesForNewNode: the KNN edges and the edge to the previous keyframe, one call
+// getKNN picks by estimated pose ("FIXME: only based on distance", :70), which finds nothing once drift exceeds the distance
+// between revisits.  getLoopCandidates / calcEdgesFrom / addLoopEdgesForNewNode pick by appearance instead (slam_kf_sc_*,
+// docs/SCAN_CONTEXT.md) and have no counterpart in the reference.
 // A keyframe is filtered (pcl::VoxelGrid 0.5) and indexed once, when it is added; the reference filters both clouds again at
 // every edge, which gives the same clouds.  The device does the ICP and computeEdgeInformationLUM; what is left of
 // calcEdgeIcp runs here: the initial transform from the two poses, the edge pose and quaternion, the acceptance gate.
@@ -14,6 +17,8 @@
 // quaternion comes from the linear part of the f32 matrix instead of Affine3d::rotation()'s polar factor.
 #pragma once
 #include <algorithm>
+#include <array>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <utility>
@@ -26,6 +31,7 @@ namespace slam_amd {
 
 // graphSlamTools.h:27-34
 enum { CTYPE_HOME = 0, CTYPE_ODOM = 1, CTYPE_NN = 2 };
+enum { CTYPE_LOOP = 3 }; // an edge found by appearance (addLoopEdgesForNewNode); not the reference's
 
 struct GraphNode { // graph_slam.h Node: idx, pose (the keyframe cloud lives in the store)
     int  idx = 0;
@@ -41,6 +47,11 @@ struct GraphEdge { // graph_slam/Edge: from, to, ctype, edge (pose), edgeInf
     int    iterations = 0, state = 0, converged = 0, pairs = 0, numCorr = 0, singular = 0;
     double x_diff = 0, y_diff = 0, theta_diff = 0;
     bool   accepted = false;
+};
+
+struct LoopCandidate {
+    int    id = 0, distance = 0, shift = 0; // slam_kf_sc_match_t's: the candidate rolled by +shift sectors lies on the query
+    double yaw = 0.0;                       // -shift 2 pi / n_sectors in (-pi, pi]: Rz(yaw) takes the query's points into the candidate's frame
 };
 
 namespace graph_detail {
@@ -146,6 +157,11 @@ public:
     // information is still computeEdgeInformationLUM's block and the acceptance gate is the same.
     enum Registration { ICP = 0, GICP = 1 };
     Registration registration = ICP;
+
+    // Loop-closure candidates by appearance (docs/SCAN_CONTEXT.md)
+    int SC_MAX_DISTANCE = INT_MAX; // a candidate's descriptor distance is at most this; the scale depends on the scene, so no limit by default
+    int SC_MIN_GAP = 10;           // a query never matches itself or the SC_MIN_GAP keyframes before it
+    int SC_CANDIDATES = 3;         // candidates registered per new node
 
     std::vector<GraphNode> nodes; // PoseGraph
     std::vector<GraphEdge> edges;
@@ -260,6 +276,95 @@ public:
         int pushed = 0;
         for (const GraphEdge &e : got)
             if (e.accepted) edges.push_back(e), ++pushed;
+        if (tried) *tried = got;
+        return pushed;
+    }
+
+    // The K keyframes nearest to gN by descriptor among those more than SC_MIN_GAP before it, nearest first (equal
+    // distances by id).  One search on the device against every keyframe; missing descriptors are computed by it.
+    std::vector<LoopCandidate> getLoopCandidates(const GraphNode &gN, int K)
+    {
+        std::vector<LoopCandidate> out;
+        const int                  count = h_ ? slam_kf_count(h_) : 0, q = gN.idx;
+        if (q < 0 || q >= count || K <= 0) return out;
+        std::vector<slam_kf_sc_match_t> m((size_t)count);
+        int                             n_rings = 0, n_sectors = 0;
+        if (slam_kf_sc_match(h_, &q, 1, m.data(), nullptr) != SLAM_OK || slam_kf_sc_read(h_, q, nullptr, 0, &n_rings, &n_sectors) != SLAM_OK) {
+            warn();
+            return out;
+        }
+        for (int i = 0; i < q - SC_MIN_GAP; ++i) {
+            if (m[i].distance < 0 || m[i].distance > SC_MAX_DISTANCE) continue;
+            LoopCandidate c;
+            c.id = i, c.distance = m[i].distance, c.shift = m[i].shift;
+            c.yaw = -(double)c.shift * (2.0 * M_PI / n_sectors);
+            if (c.yaw <= -M_PI) c.yaw += 2.0 * M_PI;
+            out.push_back(c);
+        }
+        std::stable_sort(out.begin(), out.end(), [](const LoopCandidate &a, const LoopCandidate &b) { return a.distance < b.distance; });
+        if ((int)out.size() > K) out.resize((size_t)K);
+        return out;
+    }
+
+    // calcEdges with the initial transforms given (row-major 4 x 4, source `to` into target `from`) and not taken from the poses
+    bool calcEdgesFrom(const std::vector<std::pair<int, int>> &pairs, const std::vector<std::array<float, 16>> &inits, std::vector<GraphEdge> &out)
+    {
+        out.clear();
+        if (!h_ || pairs.size() != inits.size()) return false;
+        if (pairs.empty()) return true;
+        std::vector<slam_kf_edge_req>    req(pairs.size());
+        std::vector<slam_kf_edge_result> res(pairs.size());
+        for (size_t e = 0; e < pairs.size(); ++e) {
+            const int from = pairs[e].first, to = pairs[e].second;
+            if (from < 0 || to < 0 || from >= (int)nodes.size() || to >= (int)nodes.size()) return false;
+            req[e].from = from, req[e].to = to;
+            std::copy(inits[e].begin(), inits[e].end(), req[e].init);
+        }
+        int rc;
+        if (registration == GICP) {
+            std::vector<slam_kf_gicp_result> gres(pairs.size());
+            rc = slam_kf_register_gicp(h_, req.data(), (int)req.size(), gres.data(), nullptr);
+            for (size_t e = 0; e < pairs.size(); ++e) res[e] = gres[e].edge;
+        } else
+            rc = slam_kf_register_edges(h_, req.data(), (int)req.size(), res.data(), nullptr);
+        if (rc != SLAM_OK) {
+            warn();
+            return false;
+        }
+        out.resize(pairs.size());
+        for (size_t e = 0; e < pairs.size(); ++e) finish(req[e], res[e], &out[e]);
+        return true;
+    }
+
+    // Rz(yaw), zero translation: the transform a loop candidate's registration starts from
+    static std::array<float, 16> yawInit(double yaw)
+    {
+        const float           c = (float)std::cos(yaw), s = (float)std::sin(yaw);
+        std::array<float, 16> m = {c, -s, 0, 0, s, c, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        return m;
+    }
+
+    // For the node added last: its SC_CANDIDATES loop candidates registered in one device call, target = candidate (from),
+    // source = the node (to), from Rz(-shift 2 pi / n_sectors) with zero translation; the acceptance gate is calcEdgeIcp's,
+    // against that start.  Accepted edges are pushed with CTYPE_LOOP.  Returns the edges pushed; `tried` as addEdgesForNewNode.
+    int addLoopEdgesForNewNode(std::vector<GraphEdge> *tried = nullptr)
+    {
+        if (tried) tried->clear();
+        if (nodes.empty()) return 0;
+        const GraphNode                   &gN = nodes.back();
+        std::vector<std::pair<int, int>>   pairs;
+        std::vector<std::array<float, 16>> inits;
+        for (const LoopCandidate &c : getLoopCandidates(gN, SC_CANDIDATES)) {
+            pairs.push_back(std::make_pair(c.id, gN.idx));
+            inits.push_back(yawInit(c.yaw));
+        }
+        std::vector<GraphEdge> got;
+        if (pairs.empty() || !calcEdgesFrom(pairs, inits, got)) return 0;
+        int pushed = 0;
+        for (GraphEdge &e : got) {
+            e.ctype = CTYPE_LOOP;
+            if (e.accepted) edges.push_back(e), ++pushed;
+        }
         if (tried) *tried = got;
         return pushed;
     }

@@ -795,6 +795,40 @@ int  slam_kf_register_gicp(slam_kf_t *s, const slam_kf_edge_req *req, int n, sla
 int  slam_kf_register_gicp_traced(slam_kf_t *s, const slam_kf_edge_req *req, int n, slam_kf_gicp_result *out,
                                   int32_t *pairs_trace, int trace_cap, slam_stream_t stream);
 
+/* Appearance-based loop-closure candidates on the same store, in the spirit of Scan Context (Kim & Kim, IROS 2018): per
+ * keyframe a polar height descriptor of n_rings x n_sectors bytes (ring-major; 0 = empty cell, else 1 + the clamped height
+ * bin of the cell's highest point), built from the filtered cloud, and an exhaustive exact search over all keyframes and
+ * all yaw shifts.  Integer behind the binning: the device equals tests/cpp/sc_oracle.cpp bit for bit.  docs/SCAN_CONTEXT.md
+ * has the contract. */
+typedef struct {
+    int    n_rings;   /* 20; 1 .. 32 */
+    int    n_sectors; /* 64; a multiple of 4, 4 .. 128 */
+    double max_range; /* 80.0; > 0.  Ring k ends at (k + 1) max_range / n_rings, the edge belonging to the ring outside */
+    double z_min;     /* -2.0: the height of bin 0 */
+    double z_step;    /* 0.02; > 0.  Heights clamp to bins 0 .. 254 */
+} slam_kf_sc_params;
+
+typedef struct {
+    int distance; /* min over shifts of sum |a[r][c] - b[r][(c - shift) mod n_sectors]|; -1: removed keyframe, or the query */
+    int shift;    /* the lowest shift that reaches it: the candidate rolled by +shift sectors lies on the query */
+    int n_query, n_candidate, n_both; /* occupied cells of the query, of the candidate, of both at that shift */
+} slam_kf_sc_match_t;
+
+void slam_kf_sc_default_params(slam_kf_sc_params *p);
+/* fixed once the first descriptor exists: a later call that changes a field is refused (SLAM_E_INVALID) */
+int  slam_kf_set_sc_params(slam_kf_t *s, const slam_kf_sc_params *params);
+/* The descriptor of keyframe `id`, or with id = -1 of every live keyframe that has none: one workgroup per keyframe, one
+ * launch, one wait.  A second call does nothing; replacing a keyframe drops its descriptor. */
+int  slam_kf_sc_compute(slam_kf_t *s, int id, slam_stream_t stream);
+/* n_rings * n_sectors bytes into desc (room for cap); SLAM_E_INVALID before slam_kf_sc_compute */
+int  slam_kf_sc_read(slam_kf_t *s, int id, uint8_t *desc, int cap, int *n_rings, int *n_sectors);
+/* the tables the kernel bins by: edge2[n_rings] = squared ring edges, c[k], sn[k] = cos, sin(2 pi k / n_sectors) for
+ * k < n_sectors / 4 (entry 0 is not used) */
+int  slam_kf_sc_read_tables(slam_kf_t *s, double *edge2, double *c, double *sn);
+/* out[q * slam_kf_count + id] = keyframe queries[q] against keyframe id, every id issued.  Missing descriptors are
+ * computed first; then one upload, one launch (a workgroup per pair), one download, one wait. */
+int  slam_kf_sc_match(slam_kf_t *s, const int *queries, int nq, slam_kf_sc_match_t *out, slam_stream_t stream);
+
 /* -------------------------------------------------------------------------
  * Correlative scan matcher (Olson, ICRA 2009), class-constrained like the rest of ccicp2d: the best of N_theta x N_y x N_x
  * poses around a start pose by a score looked up in a rasterised model, found exactly by a two-level branch and bound.  The

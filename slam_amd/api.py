@@ -99,6 +99,16 @@ class KfGicpResult(C.Structure):
                 ("fitness_pairs", C.c_int), ("reserved", C.c_int)]
 
 
+class KfScParams(C.Structure):
+    _fields_ = [("n_rings", C.c_int), ("n_sectors", C.c_int), ("max_range", C.c_double), ("z_min", C.c_double),
+                ("z_step", C.c_double)]
+
+
+class KfScMatch(C.Structure):
+    _fields_ = [("distance", C.c_int), ("shift", C.c_int), ("n_query", C.c_int), ("n_candidate", C.c_int),
+                ("n_both", C.c_int)]
+
+
 class CsmParams(C.Structure):
     _fields_ = [("resolution", C.c_double), ("sigma", C.c_double), ("kernel_cells", C.c_int), ("block", C.c_int),
                 ("half_x", C.c_int), ("half_y", C.c_int), ("half_theta", C.c_int), ("theta_step", C.c_double),
@@ -198,6 +208,8 @@ EXPORTS = [
     "slam_kf_register_edges", "slam_kf_register_edges_traced", "slam_kf_remove_keyframe", "slam_kf_replace_keyframe_dev",
     "slam_kf_gicp_default_params", "slam_kf_set_gicp_params", "slam_kf_compute_covariances", "slam_kf_read_covariances",
     "slam_kf_read_neighbours", "slam_kf_register_gicp", "slam_kf_register_gicp_traced",
+    "slam_kf_sc_default_params", "slam_kf_set_sc_params", "slam_kf_sc_compute", "slam_kf_sc_read", "slam_kf_sc_read_tables",
+    "slam_kf_sc_match",
     "slam_csm_default_params", "slam_csm_create", "slam_csm_create_dev", "slam_csm_destroy", "slam_csm_reserve",
     "slam_csm_set_window", "slam_csm_set_exhaustive", "slam_csm_angles", "slam_csm_match_batch_dev", "slam_csm_match",
     "slam_csm_score_volume_dev", "slam_csm_read_table", "slam_csm_info",
@@ -404,6 +416,13 @@ def lib():
     L.slam_kf_read_neighbours.argtypes = [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
     L.slam_kf_register_gicp.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
     L.slam_kf_register_gicp_traced.argtypes = [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]
+    L.slam_kf_sc_default_params.argtypes = [C.POINTER(KfScParams)]
+    L.slam_kf_sc_default_params.restype = None
+    L.slam_kf_set_sc_params.argtypes = [_vp, C.POINTER(KfScParams)]
+    L.slam_kf_sc_compute.argtypes = [_vp, C.c_int, _vp]
+    L.slam_kf_sc_read.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.slam_kf_sc_read_tables.argtypes = [_vp, _vp, _vp, _vp]
+    L.slam_kf_sc_match.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
     L.slam_csm_default_params.argtypes = [C.POINTER(CsmParams)]
     L.slam_csm_default_params.restype = None
     L.slam_csm_create.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(CsmParams), C.POINTER(_vp)]
@@ -1402,6 +1421,17 @@ def kf_gicp_default_params(**kw):
     return p
 
 
+SC_MATCH_DTYPE = np.dtype([(f, np.int32) for f, _ in KfScMatch._fields_])
+
+
+def kf_sc_default_params(**kw):
+    p = KfScParams()
+    lib().slam_kf_sc_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 class KeyframeStore:
     """graph_slam's keyframes on the device (slam_kf_*): each one voxel-filtered once and indexed by a 3-D lattice; edges
     (calcEdgeIcp: 3-D point-to-point ICP, then computeEdgeInformationLUM) registered in batches."""
@@ -1543,6 +1573,54 @@ class KeyframeStore:
             self.set_gicp_params(params)
         L = lib()
         return self._register(L.slam_kf_register_gicp, L.slam_kf_register_gicp_traced, KfGicpResult, kf_gicp_result_dict, edges, trace, stream)
+
+    # ---- scan-context descriptors and loop-closure candidates (docs/SCAN_CONTEXT.md)
+    def set_sc_params(self, params=None, **kw):
+        p = params or kf_sc_default_params(**kw)
+        check(lib().slam_kf_set_sc_params(self.h, C.byref(p)))
+        self.sc_params = p
+
+    def sc_compute(self, kid=-1, stream=None):
+        """The descriptor of keyframe kid; -1: of every live keyframe that has none, in one launch."""
+        check(lib().slam_kf_sc_compute(self.h, int(kid), _sp(stream)))
+
+    def sc_read(self, kid):
+        """[n_rings, n_sectors] u8: 0 = empty cell, else 1 + the height bin of the cell's highest point."""
+        r, s = C.c_int(0), C.c_int(0)
+        check(lib().slam_kf_sc_read(self.h, int(kid), None, 0, C.byref(r), C.byref(s)))
+        out = np.zeros((r.value, s.value), np.uint8)
+        check(lib().slam_kf_sc_read(self.h, int(kid), _ptr(out), out.size, C.byref(r), C.byref(s)))
+        return out
+
+    def sc_tables(self):
+        """(edge2 [n_rings], cos [n_sectors / 4], sin [n_sectors / 4]) f64: the tables the kernel bins by."""
+        p = getattr(self, "sc_params", None) or kf_sc_default_params()
+        e, c, s = np.zeros(p.n_rings), np.zeros(p.n_sectors // 4), np.zeros(p.n_sectors // 4)
+        check(lib().slam_kf_sc_read_tables(self.h, _ptr(e), _ptr(c), _ptr(s)))
+        return e, c, s
+
+    def sc_match(self, queries, stream=None):
+        """[len(queries), len(self)] record array (distance, shift, n_query, n_candidate, n_both); distance -1 for a
+        removed keyframe and for the query itself."""
+        q = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
+        out = np.zeros((len(q), len(self)), SC_MATCH_DTYPE)
+        check(lib().slam_kf_sc_match(self.h, _ptr(q), len(q), _ptr(out), _sp(stream)))
+        return out
+
+    def loop_candidates(self, kid, k=3, min_gap=10, max_distance=None):
+        """Up to k keyframes before kid - min_gap, nearest by descriptor first (ties by id): [(id, distance, shift, yaw)],
+        yaw = -shift 2 pi / n_sectors wrapped to (-pi, pi], the rotation about z that seeds the registration
+        (target = candidate, source = kid)."""
+        m = self.sc_match([kid])[0]
+        n_sectors = (getattr(self, "sc_params", None) or kf_sc_default_params()).n_sectors
+        ids = [i for i in range(len(m)) if i < kid - min_gap and m["distance"][i] >= 0 and
+               (max_distance is None or m["distance"][i] <= max_distance)]
+        ids.sort(key=lambda i: (int(m["distance"][i]), i))
+        out = []
+        for i in ids[:k]:
+            yaw = -int(m["shift"][i]) * 2.0 * np.pi / n_sectors
+            out.append((i, int(m["distance"][i]), int(m["shift"][i]), yaw + 2.0 * np.pi if yaw <= -np.pi else yaw))
+        return out
 
 
 class Lcg:

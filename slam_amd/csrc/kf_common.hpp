@@ -393,6 +393,7 @@ struct Keyframe {
     int32_t *nbr_index = nullptr, *nbr_count = nullptr;
     float   *nbr_dist2 = nullptr;
     int      nbr_k = 0;
+    DevMem   sc; // the scan-context descriptor (kf_sc.hip), filled by slam_kf_sc_compute: n_rings x n_sectors bytes, ring-major
     bool     removed = false; // slam_kf_remove_keyframe: the id stays issued, the memory is gone, every call refuses it
 };
 
@@ -405,6 +406,12 @@ struct slam_kf {
     std::vector<Keyframe> kfs;
     bool                  lds_enabled = false, gicp_lds_enabled = false;
     int                   n_cov = 0; // keyframes that hold covariances: their parameters are fixed from the first on
+    // kf_sc.hip: the descriptor's parameters, fixed from the first descriptor on (n_sc counts the ones computed), and the
+    // host's tables of them -- squared ring edges, cos and sin of the sector boundaries of a quadrant
+    slam_kf_sc_params sp{20, 64, 80.0, -2.0, 0.02};
+    int               n_sc = 0;
+    bool              sc_tables_ready = false;
+    double            sc_edge2[32], sc_cos[32], sc_sin[32];
     DevMem                in, filtered, keys, sort_tmp, work, stats; // add_keyframe's; `work` also holds a call's tasks, results, pairs
     ~slam_kf() { slam_ccicp_destroy(cc); }
 };
