@@ -11,9 +11,9 @@
 //   doICPMatch(target, scene, pose)  :571-578               doICPMatch(target..., scene..., initPose)
 //   getResidual()                    :637-641 (returns -1)  getResidual()
 //
-// PCL and tf types are replaced by plain arrays and the Pose struct below (the pose part of
+// PCL and tf types are replaced by plain arrays and the Pose struct of slam_amd/pose.hpp (the pose part of
 // geometry_msgs::PoseStamped); the tf calls (getYaw, getEulerYPR, createQuaternionFromRPY: icpTools.cpp:174,205-212)
-// are restated here as tf defines them.
+// are restated there as tf defines them.
 //
 // What runs per scan (scan_registration.cpp:139-159: setSceneCloud, doICPMatch) is ONE device-resident chain on one
 // stream: the cloud goes up once, slam_ccicp_scene_dev (segmentGround + classifyPoints + voxel filter + class split
@@ -31,57 +31,13 @@
 #include <utility>
 #include <vector>
 
+#include "slam_amd/buffer.hpp"
+#include "slam_amd/pose.hpp"
 #include "slam_mi355x.h"
 
 namespace slam_amd {
 
 enum RegistrationType { SCAN_TO_SCAN = 0, SCAN_TO_MAP = 1 }; // icpTools.h
-
-#ifndef SLAM_AMD_POSE_DEFINED
-#define SLAM_AMD_POSE_DEFINED
-struct Pose { // geometry_msgs::Pose
-    double x = 0, y = 0, z = 0;
-    double qx = 0, qy = 0, qz = 0, qw = 1;
-};
-#endif
-
-namespace detail {
-// tf::Matrix3x3(q).getEulerYPR(yaw, pitch, roll, 1)
-inline void euler_ypr(const Pose &p, double &yaw, double &pitch, double &roll)
-{
-    const double d = p.qx * p.qx + p.qy * p.qy + p.qz * p.qz + p.qw * p.qw, s = 2.0 / d;
-    const double xs = p.qx * s, ys = p.qy * s, zs = p.qz * s, wx = p.qw * xs, wy = p.qw * ys, wz = p.qw * zs,
-                 xx = p.qx * xs, xy = p.qx * ys, xz = p.qx * zs, yy = p.qy * ys, yz = p.qy * zs, zz = p.qz * zs;
-    const double m00 = 1.0 - (yy + zz), m10 = xy + wz, m20 = xz - wy, m21 = yz + wx, m22 = 1.0 - (xx + yy),
-                 m01 = xy - wz, m02 = xz + wy;
-    if (std::fabs(m20) >= 1) { // gimbal lock branch of tf
-        yaw = 0;
-        const double delta = std::atan2(m01, m02);
-        if (m20 < 0) {
-            pitch = M_PI / 2.0;
-            roll = delta;
-        } else {
-            pitch = -M_PI / 2.0;
-            roll = delta;
-        }
-    } else {
-        pitch = -std::asin(m20);
-        roll = std::atan2(m21 / std::cos(pitch), m22 / std::cos(pitch));
-        yaw = std::atan2(m10 / std::cos(pitch), m00 / std::cos(pitch));
-    }
-}
-// tf::createQuaternionFromRPY
-inline void quat_from_rpy(double roll, double pitch, double yaw, Pose &p)
-{
-    const double hy = yaw * 0.5, hp = pitch * 0.5, hr = roll * 0.5;
-    const double cy = std::cos(hy), sy = std::sin(hy), cp = std::cos(hp), sp = std::sin(hp), cr = std::cos(hr),
-                 sr = std::sin(hr);
-    p.qx = sr * cp * cy - cr * sp * sy;
-    p.qy = cr * sp * cy + sr * cp * sy;
-    p.qz = cr * cp * sy - sr * sp * cy;
-    p.qw = cr * cp * cy + sr * sp * sy;
-}
-} // namespace detail
 
 class CCICP {
 public:
@@ -90,30 +46,23 @@ public:
     explicit CCICP(RegistrationType type_ = SCAN_TO_SCAN) : type(type_)
     {
         if (slam_gseg_create(nullptr, &gseg_) != SLAM_OK || slam_ccicp_create(&cc_) != SLAM_OK)
-            std::fprintf(stderr, "CCICP: %s\n", slam_last_error());
+            detail::warn("CCICP");
         ok(slam_stream_create(&stream_));
-        ok(slam_malloc((void **)&d_ga_, 16 * (size_t)ICP_MAX_PTS));
-        ok(slam_malloc((void **)&d_nga_, 16 * (size_t)ICP_MAX_PTS));
-        ok(slam_malloc((void **)&d_scene_pts_, 16 * 2 * (size_t)ICP_MAX_PTS));
-        ok(slam_malloc((void **)&d_io_, kIoBytes));
-        ok(slam_host_alloc((void **)&h_io_, kIoBytes));
+        if (!(d_ga_.alloc(16 * (size_t)ICP_MAX_PTS) && d_nga_.alloc(16 * (size_t)ICP_MAX_PTS) && d_scene_pts_.alloc(16 * 2 * (size_t)ICP_MAX_PTS) &&
+              d_io_.alloc(kIoBytes) && h_io_.alloc(kIoBytes)))
+            detail::warn("CCICP");
         if (h_io_) std::memset(h_io_, 0, kIoBytes);
         if (d_io_) ok(slam_memset(d_io_, 0, kIoBytes, stream_));
         reset_box();
     }
+    // What is not memory, in order; every block is a Buffer and goes with its member, behind this body (nothing is in flight
+    // after the wait below, and no block belongs to a handle or a stream)
     ~CCICP()
     {
         slam_device_synchronize();
         if (icp_) slam_icp_destroy(icp_);
-        for (Cloud *c : {&raw_, &scene_raw_, &scene_in_, &labels_, &obs_, &flags_, &seg_target_, &seg_scene_, &ground_target_, &ground_scene_, &scene_ground_})
-            slam_free(c->p);
         free_ahead();
         free_seq();
-        slam_free(d_ga_);
-        slam_free(d_nga_);
-        slam_free(d_scene_pts_);
-        slam_free(d_io_);
-        slam_host_free(h_io_);
         slam_ccicp_destroy(cc_);
         slam_gseg_destroy(gseg_);
         slam_stream_destroy(stream_);
@@ -135,8 +84,8 @@ public:
             // segmentGround + classifyPoints in bin order (no voxel filter) as one chain; the ground cloud is the new ground_target
             const bool had_scene = scene_ready_; // a scene set before this call stays the scene (:585-608 touch neither seg_scene nor ground_scene)
             upload(raw_, xyz, n, stride);
-            reserve(seg_target_, 16 * (size_t)(n + 1));
-            reserve(ground_target_, 16 * (size_t)(n + 1));
+            detail::reserve_quarter(seg_target_, 16 * (size_t)(n + 1));
+            detail::reserve_quarter(ground_target_, 16 * (size_t)(n + 1));
             seg_target_n_ = 0;
             set_ground_target_count(0);
             if (n > 0) {
@@ -181,7 +130,7 @@ public:
     {
         ahead_.pending = ahead_.deferred = false;
         upload(scene_in_, xyz, n, stride);
-        reserve(scene_raw_, sizeof(float) * 3 * (size_t)(n + 1));
+        detail::reserve_quarter(scene_raw_, sizeof(float) * 3 * (size_t)(n + 1));
         ok(slam_grid_transform_cloud_dev((const float *)scene_in_.p, n, stride, R, t, (float *)scene_raw_.p, stream_));
         scene_n_in_ = n;
         scene_stride_ = 3;
@@ -190,7 +139,7 @@ public:
     // the scene's chain from the cloud in scene_raw_ (setSceneCloud; again after a SCAN_TO_SCAN setTargetCloud borrowed its outputs)
     void enqueue_scene_chain()
     {
-        reserve(scene_ground_, 16 * (size_t)(scene_n_in_ + 1));
+        detail::reserve_quarter(scene_ground_, 16 * (size_t)(scene_n_in_ + 1));
         ok(slam_ccicp_scene_dev(cc_, gseg_, (const float *)scene_raw_.p, scene_n_in_, scene_stride_, 1, 0, 0.0, 0.0, 0.0, ICP_MAX_PTS, d_scene_pts_,
                                 io_scan(), (float *)scene_ground_.p, io_counts(), stream_));
         scene_ready_ = true;
@@ -211,7 +160,7 @@ public:
         Pose   result;
         double yaw0, pitch0, roll0;
         detail::euler_ypr(initPose, yaw0, pitch0, roll0); // tf::getYaw (:174)
-        double *hp = reinterpret_cast<double *>(h_io_);
+        double *hp = h_io_.as<double>();
         hp[0] = std::cos(yaw0), hp[1] = -std::sin(yaw0), hp[2] = std::sin(yaw0), hp[3] = std::cos(yaw0); // :168-176
         hp[4] = initPose.x, hp[5] = initPose.y;
         std::memset(h_io_ + kOffRes, 0, 32); // result and height: a scan below 5 points leaves them untouched
@@ -284,8 +233,8 @@ public:
     {
         Ahead &a = ahead_;
         a.deferred = false;
-        reserve_on(a.raw, sizeof(float) * (size_t)(n + 1) * stride, a.stream);
-        reserve_on(a.ground, 16 * (size_t)(n + 1), a.stream);
+        detail::reserve_quarter(a.raw, sizeof(float) * (size_t)(n + 1) * stride);
+        detail::reserve_quarter(a.ground, 16 * (size_t)(n + 1));
         if (n > 0) ok(slam_memcpy_h2d_async(a.raw.p, xyz, sizeof(float) * (size_t)n * stride, a.stream));
         ok(slam_ccicp_scene_dev(a.cc, a.gseg, (const float *)a.raw.p, n, stride, 1, 0, 0.0, 0.0, 0.0, ICP_MAX_PTS, a.d_pts,
                                 reinterpret_cast<int32_t *>(a.d_io + kOffScan), (float *)a.ground.p,
@@ -366,14 +315,15 @@ public:
     RegistrationType type;
 
 private:
-    struct Cloud {
-        void  *p = nullptr;
-        size_t cap = 0;
-    };
+    using Cloud = detail::DeviceBuffer; // grown with detail::reserve_quarter: clouds of a sequence differ by a few per cent
+    template <class T>
+    using Dev = detail::Array<T, detail::Kind::Device>;
+    template <class T>
+    using Pin = detail::Array<T, detail::Kind::Pinned>;
     // one device block and its pinned mirror: [R t | result | z, neighbours | scan {0, n, n_ga, -} | counts {obs, gnd, flt, err} | n ground target]
     static constexpr size_t kOffRes = 48, kOffZ = 64, kOffScan = 80, kOffCounts = 96, kOffNgt = 112, kIoBytes = 128;
-    double  *io_R() { return reinterpret_cast<double *>(d_io_); }
-    double  *io_t() { return reinterpret_cast<double *>(d_io_) + 4; }
+    double  *io_R() { return d_io_.as<double>(); }
+    double  *io_t() { return d_io_.as<double>() + 4; }
     int32_t *io_scan() { return reinterpret_cast<int32_t *>(d_io_ + kOffScan); }
     int32_t *io_counts() { return reinterpret_cast<int32_t *>(d_io_ + kOffCounts); }
     const int32_t *h_scan() const { return reinterpret_cast<const int32_t *>(h_io_ + kOffScan); }
@@ -393,21 +343,11 @@ private:
     }
     static void ok(int rc)
     {
-        if (rc != SLAM_OK) std::fprintf(stderr, "CCICP: %s\n", slam_last_error());
-    }
-    static void reserve(Cloud &c, size_t bytes)
-    {
-        if (bytes <= c.cap) return;
-        slam_device_synchronize(); // (the old block may be in use by enqueued work)
-        slam_free(c.p);
-        c.p = nullptr;
-        c.cap = 0;
-        const size_t want = bytes + bytes / 4; // clouds of a sequence differ by a few per cent: grow rarely
-        if (slam_malloc(&c.p, want) == SLAM_OK) c.cap = want;
+        if (rc != SLAM_OK) detail::warn("CCICP");
     }
     void upload(Cloud &dst, const float *xyz, int n, int stride)
     {
-        reserve(dst, sizeof(float) * (size_t)(n + 1) * stride);
+        detail::reserve_quarter(dst, sizeof(float) * (size_t)(n + 1) * stride);
         if (&dst == &raw_) raw_n_ = n, raw_stride_ = stride;
         if (n <= 0) return;
         // from pinned memory (slam_host_alloc) the copy only enqueues -- the caller keeps the cloud as it is until the match that uses
@@ -491,7 +431,7 @@ private:
     }
     Pose result_from_io(const Pose &initPose, double pitch0, double roll0)
     {
-        const double          *hp = reinterpret_cast<const double *>(h_io_);
+        const double          *hp = h_io_.as<double>();
         const slam_icp_result *res = reinterpret_cast<const slam_icp_result *>(h_io_ + kOffRes);
         num_corr_ = icp_ ? res->n_corr : 0;
         last_iters_ = icp_ ? res->iters : 0;
@@ -507,11 +447,11 @@ private:
     // the points of raw_ whose label is in `mask`, in cloud order, as (x, y, z, 0) records; 0xff = every point
     void select(unsigned mask, Cloud &dst, int &n_dst)
     {
-        reserve(dst, 16 * (size_t)(raw_n_ + 1));
+        detail::reserve_quarter(dst, 16 * (size_t)(raw_n_ + 1));
         n_dst = 0;
         if (raw_n_ == 0) return;
         if (mask == 0xffu) {
-            reserve(labels_, (size_t)raw_n_ + 16);
+            detail::reserve_quarter(labels_, (size_t)raw_n_ + 16);
             ok(slam_memset(labels_.p, 0, (size_t)raw_n_, stream_));
             mask = 1u;
         }
@@ -522,8 +462,8 @@ private:
     // (setSceneCloud) or in classifyPoints' own bin order (setTargetCloud)
     void classify_into(Cloud &dst, int &n_dst, bool voxel)
     {
-        reserve(flags_, (size_t)obs_n_ + 16);
-        reserve(dst, 16 * (size_t)(obs_n_ + 1));
+        detail::reserve_quarter(flags_, (size_t)obs_n_ + 16);
+        detail::reserve_quarter(dst, 16 * (size_t)(obs_n_ + 1));
         n_dst = 0;
         if (obs_n_ == 0) return;
         ok(slam_gseg_classify_ga_dev(gseg_, (const float *)obs_.p, obs_n_, 4, (uint8_t *)flags_.p, stream_));
@@ -544,13 +484,13 @@ private:
         know_scene();
         if (!seg_scene_valid_) {
             seg_scene_n_ = h_counts()[2];
-            reserve(seg_scene_, 16 * (size_t)(scene_n_in_ + 1));
+            detail::reserve_quarter(seg_scene_, 16 * (size_t)(scene_n_in_ + 1));
             ok(slam_ccicp_scene_cloud_dev(cc_, (float *)seg_scene_.p, scene_n_in_, stream_));
             seg_scene_valid_ = true;
         }
         if (!ground_scene_valid_) { // VoxelGrid 0.5 x 0.5 x 5 of the scene's ground cloud (:628-633)
             const int n_gnd = h_counts()[1];
-            reserve(ground_scene_, 16 * (size_t)(n_gnd + 1));
+            detail::reserve_quarter(ground_scene_, 16 * (size_t)(n_gnd + 1));
             ground_scene_n_ = 0;
             if (n_gnd > 0)
                 ok(slam_ccicp_voxel_downsample_dev(cc_, (const float *)scene_ground_.p, nullptr, n_gnd, 4, 0.5f, 0.5f, 5.0f,
@@ -565,7 +505,7 @@ private:
         ++stepwise_matches_;
         raw_n_ = scene_n_in_, raw_stride_ = scene_stride_;
         std::swap(raw_, scene_raw_);
-        reserve(labels_, (size_t)raw_n_ + 16);
+        detail::reserve_quarter(labels_, (size_t)raw_n_ + 16);
         int n_gnd = 0, sc[2] = {0, 0};
         ok(slam_gseg_segment_dev(gseg_, (const float *)raw_.p, raw_n_, raw_stride_, (uint8_t *)labels_.p, stream_));
         select((1u << SLAM_GSEG_OBSTACLE) | (1u << SLAM_GSEG_OVERHEAD), obs_, obs_n_);
@@ -579,7 +519,7 @@ private:
         hs[0] = 0, hs[1] = sc[0] + sc[1], hs[2] = sc[0], hs[3] = 0;
         hc[0] = obs_n_, hc[1] = n_gnd, hc[2] = seg_scene_n_, hc[3] = 0;
         n_scene_[0] = sc[0], n_scene_[1] = sc[1];
-        double *hp = reinterpret_cast<double *>(h_io_);
+        double *hp = h_io_.as<double>();
         hp[0] = std::cos(yaw0), hp[1] = -std::sin(yaw0), hp[2] = std::sin(yaw0), hp[3] = std::cos(yaw0);
         hp[4] = initPose.x, hp[5] = initPose.y;
         std::memset(h_io_ + kOffRes, 0, 32);
@@ -625,29 +565,18 @@ private:
         slam_stream_t stream = nullptr;
         slam_event_t  done = nullptr;
         Cloud         raw, ground;
-        double       *d_pts = nullptr;
-        unsigned char *d_io = nullptr;
+        Dev<double>   d_pts;
+        Dev<unsigned char> d_io;
         const float  *xyz = nullptr;
         int           n = 0, stride = 3;
     } ahead_;
-    static void reserve_on(Cloud &c, size_t bytes, slam_stream_t st)
-    {
-        if (bytes <= c.cap) return;
-        slam_stream_synchronize(st); // (the old block may be in use by work enqueued on its stream)
-        slam_free(c.p);
-        c.p = nullptr;
-        c.cap = 0;
-        const size_t want = bytes + bytes / 4;
-        if (slam_malloc(&c.p, want) == SLAM_OK) c.cap = want;
-    }
     bool make_ahead()
     {
         Ahead &a = ahead_;
         bool   good = slam_gseg_create(nullptr, &a.gseg) == SLAM_OK && slam_ccicp_create(&a.cc) == SLAM_OK && slam_stream_create(&a.stream) == SLAM_OK &&
-                    slam_event_create(&a.done) == SLAM_OK && slam_malloc((void **)&a.d_pts, 16 * 2 * (size_t)ICP_MAX_PTS) == SLAM_OK &&
-                    slam_malloc((void **)&a.d_io, kIoBytes) == SLAM_OK;
+                    slam_event_create(&a.done) == SLAM_OK && a.d_pts.alloc(16 * 2 * (size_t)ICP_MAX_PTS) && a.d_io.alloc(kIoBytes);
         if (good) good = slam_memset(a.d_io, 0, kIoBytes, a.stream) == SLAM_OK;
-        if (!good) std::fprintf(stderr, "CCICP: %s\n", slam_last_error());
+        if (!good) detail::warn("CCICP");
         a.made = good;
         return good;
     }
@@ -656,10 +585,6 @@ private:
         Ahead &a = ahead_;
         if (a.cc) slam_ccicp_destroy(a.cc);
         if (a.gseg) slam_gseg_destroy(a.gseg);
-        slam_free(a.raw.p);
-        slam_free(a.ground.p);
-        slam_free(a.d_pts);
-        slam_free(a.d_io);
         if (a.done) slam_event_destroy(a.done);
         if (a.stream) slam_stream_destroy(a.stream);
     }
@@ -709,11 +634,14 @@ private:
     bool          seq_made_ = false, use_graphs_ = false;
     int           seq_batches_ = 0;
     double        seq_ms_[3] = {0, 0, 0}, seq_up_ms_ = 0;
-    double       *d_seq_slots_ = nullptr, *d_seq_pack_ = nullptr; // [kSeqBatch][2 * ICP_MAX_PTS] points each
-    SeqIo        *d_seq_io_ = nullptr, *h_seq_io_ = nullptr;
-    double       *d_seq_pose_ = nullptr, *h_seq_pose_ = nullptr;  // [kSeqBatch][4] R, [kSeqBatch][2] t, [kSeqBatch][2] z + neighbours
-    slam_icp_result *d_seq_res_ = nullptr, *h_seq_res_ = nullptr;
-    int32_t      *d_seq_off_ = nullptr;                            // [kSeqBatch + 1] scan_off, [kSeqBatch] scan_nga
+    Dev<double>   d_seq_slots_, d_seq_pack_; // [kSeqBatch][2 * ICP_MAX_PTS] points each
+    Dev<SeqIo>    d_seq_io_;
+    Pin<SeqIo>    h_seq_io_;
+    Dev<double>   d_seq_pose_; // [kSeqBatch][4] R, [kSeqBatch][2] t, [kSeqBatch][2] z + neighbours
+    Pin<double>   h_seq_pose_;
+    Dev<slam_icp_result> d_seq_res_;
+    Pin<slam_icp_result> h_seq_res_;
+    Dev<int32_t>  d_seq_off_; // [kSeqBatch + 1] scan_off, [kSeqBatch] scan_nga
     slam_event_t  seq_ev_[kSeqBatch] = {}, seq_fit_ = nullptr, seq_lane_ev_[kSeqLanes] = {};
     static constexpr size_t kSlotPts = 2 * (size_t)ICP_MAX_PTS, kPoseDoubles = 8 * (size_t)kSeqBatch;
     bool make_seq()
@@ -728,20 +656,15 @@ private:
             // slam_stream_create_reserving_cus(.., 0), was measured: 1.85 -> 3.3-3.6 ms per batch of ten, and one run never came back)
             g(slam_stream_create(&l.stream));
         }
-        g(slam_malloc((void **)&d_seq_slots_, 16 * kSlotPts * kSeqBatch));
-        g(slam_malloc((void **)&d_seq_pack_, 16 * kSlotPts * kSeqBatch));
-        g(slam_malloc((void **)&d_seq_io_, sizeof(SeqIo) * kSeqBatch));
-        g(slam_host_alloc((void **)&h_seq_io_, sizeof(SeqIo) * kSeqBatch));
-        g(slam_malloc((void **)&d_seq_pose_, 8 * kPoseDoubles));
-        g(slam_host_alloc((void **)&h_seq_pose_, 8 * kPoseDoubles));
-        g(slam_malloc((void **)&d_seq_res_, sizeof(slam_icp_result) * kSeqBatch));
-        g(slam_host_alloc((void **)&h_seq_res_, sizeof(slam_icp_result) * kSeqBatch));
-        g(slam_malloc((void **)&d_seq_off_, 4 * (2 * (size_t)kSeqBatch + 1)));
+        good = good && d_seq_slots_.alloc(16 * kSlotPts * kSeqBatch) && d_seq_pack_.alloc(16 * kSlotPts * kSeqBatch) &&
+               d_seq_io_.alloc(sizeof(SeqIo) * kSeqBatch) && h_seq_io_.alloc(sizeof(SeqIo) * kSeqBatch) && d_seq_pose_.alloc(8 * kPoseDoubles) &&
+               h_seq_pose_.alloc(8 * kPoseDoubles) && d_seq_res_.alloc(sizeof(slam_icp_result) * kSeqBatch) &&
+               h_seq_res_.alloc(sizeof(slam_icp_result) * kSeqBatch) && d_seq_off_.alloc(4 * (2 * (size_t)kSeqBatch + 1));
         for (slam_event_t &e : seq_ev_) g(slam_event_create(&e));
         for (slam_event_t &e : seq_lane_ev_) g(slam_event_create(&e));
         g(slam_event_create(&seq_fit_));
         if (good) g(slam_memset(d_seq_io_, 0, sizeof(SeqIo) * kSeqBatch, stream_));
-        if (!good) std::fprintf(stderr, "CCICP: %s\n", slam_last_error());
+        if (!good) detail::warn("CCICP");
         seq_made_ = good;
         return good;
     }
@@ -752,19 +675,8 @@ private:
         for (SeqLane &l : lane_) {
             if (l.cc) slam_ccicp_destroy(l.cc);
             if (l.gseg) slam_gseg_destroy(l.gseg);
-            slam_free(l.raw.p);
-            slam_free(l.ground.p);
             if (l.stream) slam_stream_destroy(l.stream);
         }
-        slam_free(d_seq_slots_);
-        slam_free(d_seq_pack_);
-        slam_free(d_seq_io_);
-        slam_host_free(h_seq_io_);
-        slam_free(d_seq_pose_);
-        slam_host_free(h_seq_pose_);
-        slam_free(d_seq_res_);
-        slam_host_free(h_seq_res_);
-        slam_free(d_seq_off_);
         for (slam_event_t e : seq_ev_)
             if (e) slam_event_destroy(e);
         for (slam_event_t e : seq_lane_ev_)
@@ -787,8 +699,8 @@ private:
         auto enqueue_scene = [&](int k) {
             SeqLane &l = lane_[k % kSeqLanes];
             const int np = n_points[k];
-            reserve_on(l.raw, sizeof(float) * (size_t)(np + 1) * stride, l.stream);
-            reserve_on(l.ground, 16 * (size_t)(np + 1), l.stream);
+            detail::reserve_quarter(l.raw, sizeof(float) * (size_t)(np + 1) * stride);
+            detail::reserve_quarter(l.ground, 16 * (size_t)(np + 1));
             const auto t_up = std::chrono::steady_clock::now();
             if (np > 0) ok(slam_memcpy_h2d_async(l.raw.p, scenes[k], sizeof(float) * (size_t)np * stride, l.stream));
             seq_up_ms_ += since(t_up);
@@ -901,8 +813,9 @@ private:
     bool    target_dirty_ = true, scene_ready_ = false, scene_known_ = false, seg_scene_valid_ = false, ground_scene_valid_ = false;
     float   ext_[4] = {0, 0, 0, 0};       // x_lo, x_hi, y_lo, y_hi of the target's finite points
     float   box_[4], built_box_[4] = {0, 0, 0, 0}; // the crop so far (intersection of the windows); the one the index was built for
-    double *d_ga_ = nullptr, *d_nga_ = nullptr, *d_scene_pts_ = nullptr;
-    unsigned char *d_io_ = nullptr, *h_io_ = nullptr;
+    Dev<double>        d_ga_, d_nga_, d_scene_pts_;
+    Dev<unsigned char> d_io_;
+    Pin<unsigned char> h_io_;
 };
 
 } // namespace slam_amd

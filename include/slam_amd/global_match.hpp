@@ -23,6 +23,7 @@
 #include <functional>
 #include <vector>
 
+#include "slam_amd/buffer.hpp" // detail::warn
 #include "slam_mi355x.h"
 
 namespace slam_amd {
@@ -180,7 +181,7 @@ private:
         for (int k = 0; k < 9; ++k) e->covariance[k] = 0;
         e->covariance[0] = e->covariance[4] = COV_XY, e->covariance[8] = COV_YAW;
     }
-    static void warn() { std::fprintf(stderr, "GlobalMatcher: %s\n", slam_last_error()); }
+    static void warn() { detail::warn("GlobalMatcher"); }
 
     slam_kf_t *coarse_ = nullptr, *refine_ = nullptr;
     int        map_coarse_ = -1, map_refine_ = -1;

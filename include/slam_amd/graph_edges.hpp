@@ -24,7 +24,8 @@
 #include <utility>
 #include <vector>
 
-#include "slam_amd/mls.hpp" // Pose
+#include "slam_amd/buffer.hpp" // detail::warn
+#include "slam_amd/pose.hpp"
 #include "slam_mi355x.h"
 
 namespace slam_amd {
@@ -53,96 +54,6 @@ struct LoopCandidate {
     int    id = 0, distance = 0, shift = 0; // slam_kf_sc_match_t's: the candidate rolled by +shift sectors lies on the query
     double yaw = 0.0;                       // -shift 2 pi / n_sectors in (-pi, pi]: Rz(yaw) takes the query's points into the candidate's frame
 };
-
-namespace graph_detail {
-
-// Eigen::Quaterniond(w, x, y, z).toRotationMatrix(), the rotation of tf::poseMsgToEigen
-inline void quat_to_matrix(const Pose &q, double m[9])
-{
-    const double tx = 2.0 * q.qx, ty = 2.0 * q.qy, tz = 2.0 * q.qz;
-    const double twx = tx * q.qw, twy = ty * q.qw, twz = tz * q.qw, txx = tx * q.qx, txy = ty * q.qx, txz = tz * q.qx, tyy = ty * q.qy,
-                 tyz = tz * q.qy, tzz = tz * q.qz;
-    m[0] = 1.0 - (tyy + tzz), m[1] = txy - twz, m[2] = txz + twy;
-    m[3] = txy + twz, m[4] = 1.0 - (txx + tzz), m[5] = tyz - twx;
-    m[6] = txz - twy, m[7] = tyz + twx, m[8] = 1.0 - (txx + tyy);
-}
-
-// (Mfrom^-1 Mto).cast<float>(), graphSlamTools.cpp:258, row-major 4 x 4
-inline void relative_f32(const Pose &from, const Pose &to, float out[16])
-{
-    double Rf[9], Rt[9];
-    quat_to_matrix(from, Rf);
-    quat_to_matrix(to, Rt);
-    const double d[3] = {to.x - from.x, to.y - from.y, to.z - from.z};
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) out[4 * r + c] = (float)((Rf[r] * Rt[c] + Rf[3 + r] * Rt[3 + c]) + Rf[6 + r] * Rt[6 + c]);
-        out[4 * r + 3] = (float)((Rf[r] * d[0] + Rf[3 + r] * d[1]) + Rf[6 + r] * d[2]);
-    }
-    out[12] = out[13] = out[14] = 0.0f, out[15] = 1.0f;
-}
-
-// Eigen::Quaterniond(Matrix3d) (tf::poseEigenToMsg, which also makes w >= 0)
-inline void eigen_quaternion(const double m[9], Pose *p)
-{
-    double q[4]; // x y z w
-    double t = m[0] + m[4] + m[8];
-    if (t > 0.0) {
-        t = std::sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (m[7] - m[5]) * t, q[1] = (m[2] - m[6]) * t, q[2] = (m[3] - m[1]) * t;
-    } else {
-        int i = 0;
-        if (m[4] > m[0]) i = 1;
-        if (m[8] > m[4 * i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = std::sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
-        q[i] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
-        q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
-        q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
-    }
-    if (q[3] < 0) q[0] = -q[0], q[1] = -q[1], q[2] = -q[2], q[3] = -q[3];
-    p->qx = q[0], p->qy = q[1], p->qz = q[2], p->qw = q[3];
-}
-
-// tf::Matrix3x3::getRotation
-inline void tf_quaternion(const double m[9], Pose *p)
-{
-    const double trace = m[0] + m[4] + m[8];
-    double       temp[4];
-    if (trace > 0.0) {
-        double s = std::sqrt(trace + 1.0);
-        temp[3] = s * 0.5;
-        s = 0.5 / s;
-        temp[0] = (m[7] - m[5]) * s, temp[1] = (m[2] - m[6]) * s, temp[2] = (m[3] - m[1]) * s;
-    } else {
-        const int i = m[0] < m[4] ? (m[4] < m[8] ? 2 : 1) : (m[0] < m[8] ? 2 : 0);
-        const int j = (i + 1) % 3, k = (i + 2) % 3;
-        double    s = std::sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
-        temp[i] = s * 0.5;
-        s = 0.5 / s;
-        temp[3] = (m[3 * k + j] - m[3 * j + k]) * s;
-        temp[j] = (m[3 * j + i] + m[3 * i + j]) * s;
-        temp[k] = (m[3 * k + i] + m[3 * i + k]) * s;
-    }
-    p->qx = temp[0], p->qy = temp[1], p->qz = temp[2], p->qw = temp[3];
-}
-
-// tf::getYaw: Matrix3x3(q).getRPY's yaw (setRotation, then getEulerYPR's first solution)
-inline double tf_yaw(const Pose &q)
-{
-    const double d = q.qx * q.qx + q.qy * q.qy + q.qz * q.qz + q.qw * q.qw, s = 2.0 / d;
-    const double ys = q.qy * s, zs = q.qz * s, wy = q.qw * ys, wz = q.qw * zs, xy = q.qx * ys, xz = q.qx * zs, yy = q.qy * ys,
-                 zz = q.qz * zs;
-    const double m00 = 1.0 - (yy + zz), m10 = xy + wz, m20 = xz - wy;
-    if (std::fabs(m20) >= 1.0) return 0.0;
-    const double pitch = -std::asin(m20), cp = std::cos(pitch);
-    return std::atan2(m10 / cp, m00 / cp);
-}
-
-} // namespace graph_detail
 
 class KeyframeGraph {
 public:
@@ -234,7 +145,7 @@ public:
             const int from = pairs[e].first, to = pairs[e].second;
             if (from < 0 || to < 0 || from >= (int)nodes.size() || to >= (int)nodes.size()) return false;
             req[e].from = from, req[e].to = to;
-            graph_detail::relative_f32(nodes[from].pose, nodes[to].pose, req[e].init); // :258
+            detail::relative_f32(nodes[from].pose, nodes[to].pose, req[e].init); // :258
         }
         int rc;
         if (registration == GICP) {
@@ -372,7 +283,7 @@ public:
 private:
     void finish(const slam_kf_edge_req &req, const slam_kf_edge_result &res, GraphEdge *gE) const
     {
-        using namespace graph_detail;
+        using namespace detail;
         gE->from = req.from, gE->to = req.to, gE->ctype = CTYPE_NN;
         for (int k = 0; k < 16; ++k) gE->init[k] = req.init[k], gE->transform[k] = res.transform[k];
         for (int k = 0; k < 36; ++k) gE->edgeInf[k] = res.information[k];
@@ -403,7 +314,7 @@ private:
         // :355-360
         gE->accepted = !((gE->x_diff > DIST_MOVE_THRESH) || (gE->y_diff > DIST_MOVE_THRESH) || (theta_diff > ROT_MOVE_THRESH));
     }
-    static void warn() { std::fprintf(stderr, "KeyframeGraph: %s\n", slam_last_error()); }
+    static void warn() { detail::warn("KeyframeGraph"); }
 
     slam_kf_t *h_ = nullptr;
 };

@@ -27,6 +27,7 @@
 #include <cstdio>
 #include <vector>
 
+#include "slam_amd/buffer.hpp"
 #include "slam_mi355x.h"
 
 namespace slam_amd {
@@ -76,8 +77,6 @@ public:
     }
     ~GlobalMapBuilder()
     {
-        slam_free(d_scan_);
-        slam_free(d_map_);
         slam_kf_destroy(store_);
         slam_vmap_destroy(vmap_);
     }
@@ -113,9 +112,9 @@ public:
             return true;
         }
         const size_t scan_bytes = sizeof(float) * (size_t)n * stride;
-        if (!reserve(&d_scan_, &scan_cap_, scan_bytes) || slam_memcpy_h2d(d_scan_, xyz, scan_bytes, nullptr) != SLAM_OK) return warn(), false;
+        if (!detail::reserve_quarter(d_scan_, scan_bytes) || slam_memcpy_h2d(d_scan_.p, xyz, scan_bytes, nullptr) != SLAM_OK) return warn(), false;
         int scan = -1;
-        if (slam_kf_add_keyframe_dev(store_, static_cast<const float *>(d_scan_), n, stride, &scan, nullptr) != SLAM_OK) return warn(), false;
+        if (slam_kf_add_keyframe_dev(store_, d_scan_.as<float>(), n, stride, &scan, nullptr) != SLAM_OK) return warn(), false;
         const bool accepted = registerAndIntegrate(scan, n, stride, (int)n_voxels);
         if (slam_kf_remove_keyframe(store_, scan) != SLAM_OK) warn(); // the store holds two keyframes at most
         if (accepted) ++n_accepted;
@@ -144,15 +143,14 @@ private:
         cropBox(lo, hi);
         const int   cap = n_voxels > 0 ? n_voxels : 1;
         int         n_map = 0;
-        if (!reserve(&d_map_, &map_cap_, sizeof(float) * 4 * (size_t)cap)) return warn(), false;
-        const int rx = carve ? slam_vmap_extract_carved_dev(vmap_, lo, hi, 0, CARVE_NUM, CARVE_DEN, static_cast<float *>(d_map_), nullptr, nullptr, cap,
-                                                            &n_map, nullptr)
-                             : slam_vmap_extract_dev(vmap_, lo, hi, 0, static_cast<float *>(d_map_), nullptr, nullptr, cap, &n_map, nullptr);
+        if (!detail::reserve_quarter(d_map_, sizeof(float) * 4 * (size_t)cap)) return warn(), false;
+        const int rx = carve ? slam_vmap_extract_carved_dev(vmap_, lo, hi, 0, CARVE_NUM, CARVE_DEN, d_map_.as<float>(), nullptr, nullptr, cap, &n_map, nullptr)
+                             : slam_vmap_extract_dev(vmap_, lo, hi, 0, d_map_.as<float>(), nullptr, nullptr, cap, &n_map, nullptr);
         if (rx != SLAM_OK) return warn(), false;
         if (slam_device_synchronize() != SLAM_OK) return warn(), false;
         if (n_map == 0) return false; // nothing of the map near the pose: nothing to register against
-        const int rc = map_id_ < 0 ? slam_kf_add_keyframe_dev(store_, static_cast<const float *>(d_map_), n_map, 4, &map_id_, nullptr)
-                                   : slam_kf_replace_keyframe_dev(store_, map_id_, static_cast<const float *>(d_map_), n_map, 4, nullptr);
+        const int rc = map_id_ < 0 ? slam_kf_add_keyframe_dev(store_, d_map_.as<float>(), n_map, 4, &map_id_, nullptr)
+                                   : slam_kf_replace_keyframe_dev(store_, map_id_, d_map_.as<float>(), n_map, 4, nullptr);
         if (rc != SLAM_OK) return warn(), false;
         slam_kf_edge_req rq;
         rq.from = map_id_, rq.to = scan;
@@ -166,27 +164,17 @@ private:
             for (int c = 0; c < 3; ++c) R[3 * r + c] = (double)trans_full[4 * r + c];
             t[r] = (double)trans_full[4 * r + 3];
         }
-        if (slam_vmap_integrate_dev(vmap_, static_cast<const float *>(d_scan_), n, stride, R, t, nullptr, nullptr) != SLAM_OK) return warn(), false;
-        if (carve && slam_vmap_carve_dev(vmap_, static_cast<const float *>(d_scan_), n, stride, R, t, nullptr, &carve_params, &last_carve, nullptr) != SLAM_OK)
+        if (slam_vmap_integrate_dev(vmap_, d_scan_.as<float>(), n, stride, R, t, nullptr, nullptr) != SLAM_OK) return warn(), false;
+        if (carve && slam_vmap_carve_dev(vmap_, d_scan_.as<float>(), n, stride, R, t, nullptr, &carve_params, &last_carve, nullptr) != SLAM_OK)
             return warn(), false;
         return true;
     }
-    static bool reserve(void **p, size_t *cap, size_t bytes)
-    {
-        if (bytes <= *cap) return true;
-        slam_free(*p);
-        *p = nullptr, *cap = 0;
-        if (slam_malloc(p, bytes + bytes / 4) != SLAM_OK) return false;
-        *cap = bytes + bytes / 4;
-        return true;
-    }
-    static void warn() { std::fprintf(stderr, "GlobalMapBuilder: %s\n", slam_last_error()); }
+    static void warn() { detail::warn("GlobalMapBuilder"); }
 
-    slam_vmap_t *vmap_ = nullptr;
-    slam_kf_t   *store_ = nullptr;
-    void        *d_scan_ = nullptr, *d_map_ = nullptr;
-    size_t       scan_cap_ = 0, map_cap_ = 0;
-    int          map_id_ = -1;
+    slam_vmap_t         *vmap_ = nullptr;
+    slam_kf_t           *store_ = nullptr;
+    detail::DeviceBuffer d_scan_, d_map_;
+    int                  map_id_ = -1;
 };
 
 } // namespace slam_amd

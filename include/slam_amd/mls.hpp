@@ -10,7 +10,7 @@
 //                                                   drv cloud appended to global_cloud (:144-149);
 //   addToOccupancy(obstacle, n, ground, n, stride)  below the segmentation, for callers that have the
 //                                                   segmented clouds already (PointXYZGD = 8 floats).
-// Clouds are float arrays (x, y, z first, `stride` floats per point), poses the Pose struct below
+// Clouds are float arrays (x, y, z first, `stride` floats per point), poses the Pose struct of slam_amd/pose.hpp
 // (the pose part of geometry_msgs::PoseStamped).  getDrivability() fills a struct laid out like
 // nav_msgs/OccupancyGrid (mls.h:167-175): data[x + size_x*y] in {-1, 0, 100}, origin -res*size/2.
 // global_cloud lives on the host, as the reference's PCL cloud does.
@@ -22,17 +22,50 @@
 #include <map>
 #include <vector>
 
+#include "slam_amd/buffer.hpp"
+#include "slam_amd/pose.hpp"
 #include "slam_mi355x.h"
 
 namespace slam_amd {
 
-#ifndef SLAM_AMD_POSE_DEFINED
-#define SLAM_AMD_POSE_DEFINED
-struct Pose { // geometry_msgs::Pose
-    double x = 0, y = 0, z = 0;
-    double qx = 0, qy = 0, qz = 0, qw = 1;
-};
-#endif
+// pcl::VoxelGrid(xy, xy, z) on a host cloud (x, y, z per point): one centroid per occupied voxel, in increasing voxel index
+// (x fastest), the lattice anchored at the cloud's minimum as PCL anchors it -- what filterPointCloud (here and in
+// mls_map.hpp) falls back to for a lattice beyond the device filter's accumulator
+inline void voxel_filter_host(std::vector<float> &cloud, double xy, double z)
+{
+    const size_t n = cloud.size() / 3;
+    if (!n) return;
+    float mn[3] = {cloud[0], cloud[1], cloud[2]}, mx[3] = {mn[0], mn[1], mn[2]};
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k) {
+            mn[k] = std::min(mn[k], cloud[3 * i + k]);
+            mx[k] = std::max(mx[k], cloud[3 * i + k]);
+        }
+    const float inv[3] = {(float)(1.0 / xy), (float)(1.0 / xy), (float)(1.0 / z)};
+    long        lo[3], div[3];
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = (long)std::floor(mn[k] * inv[k]);
+        div[k] = (long)std::floor(mx[k] * inv[k]) - lo[k] + 1;
+    }
+    struct Acc {
+        double s[3] = {0, 0, 0};
+        long   n = 0;
+    };
+    std::map<long, Acc> vox;
+    for (size_t i = 0; i < n; ++i) {
+        long idx = 0, mul = 1;
+        for (int k = 0; k < 3; ++k) {
+            idx += ((long)std::floor(cloud[3 * i + k] * inv[k]) - lo[k]) * mul;
+            mul *= div[k];
+        }
+        Acc &a = vox[idx];
+        for (int k = 0; k < 3; ++k) a.s[k] += cloud[3 * i + k];
+        ++a.n;
+    }
+    cloud.clear();
+    for (const auto &kv : vox)
+        for (int k = 0; k < 3; ++k) cloud.push_back((float)(kv.second.s[k] / (double)kv.second.n));
+}
 
 struct OccupancyGrid { // the fields of nav_msgs::OccupancyGrid that MLS fills
     struct {
@@ -65,10 +98,7 @@ public:
     }
     ~MLS()
     {
-        slam_device_synchronize();
-        for (void *p : {d_cloud_, d_labels_, d_gnd_, d_obs_, d_counts_}) slam_free(p);
-        slam_host_free(h_pin_);
-        slam_free(d_gc_in_), slam_free(d_gc_out_);
+        slam_device_synchronize(); // (the buffers go with their members, behind this wait)
         slam_ccicp_destroy(cc_);
         slam_gseg_destroy(gseg_);
         slam_grid_destroy(h_);
@@ -114,47 +144,46 @@ public:
     {
         if (!h_ || n <= 0) return;
         if (!gseg_ && slam_gseg_create(nullptr, &gseg_) != SLAM_OK) return warn();
-        if (n > cap_) {
-            slam_device_synchronize();
-            for (void *p : {d_cloud_, d_labels_, d_gnd_, d_obs_}) slam_free(p);
-            d_cloud_ = d_labels_ = d_gnd_ = d_obs_ = nullptr;
-            cap_ = n + n / 4;
-            if (slam_malloc(&d_cloud_, sizeof(float) * (size_t)cap_ * 8) != SLAM_OK || slam_malloc(&d_labels_, (size_t)cap_) != SLAM_OK ||
-                slam_malloc(&d_gnd_, 16 * (size_t)cap_) != SLAM_OK || slam_malloc(&d_obs_, 16 * (size_t)cap_) != SLAM_OK) {
-                cap_ = 0;
+        if (n > cap_) { // one capacity, in points, for four blocks: they grow together or not at all
+            const int c = n + n / 4;
+            cap_ = 0;
+            if (!(d_cloud_.reserve(sizeof(float) * (size_t)c * 8) && d_labels_.reserve((size_t)c) && d_gnd_.reserve(16 * (size_t)c) &&
+                  d_obs_.reserve(16 * (size_t)c))) {
+                for (detail::DeviceBuffer *b : {&d_cloud_, &d_labels_, &d_gnd_, &d_obs_}) b->release();
                 return warn();
             }
+            cap_ = c;
         }
-        if (!d_counts_ && slam_malloc(&d_counts_, 16) != SLAM_OK) return warn();
+        if (!d_counts_.reserve(16)) return warn();
         if (stride > 8) return (void)std::fprintf(stderr, "MLS::addToOccupancy: stride %d > 8 floats\n", stride);
         // the cloud as it came, behind the place the segmentation reads (d_cloud_ holds 8 floats per point: a turned copy of at
         // most 3 in front, the upload of at most 5 ... 8 behind it when a transform is asked for)
         const bool turn = R != nullptr;
-        float     *d_up = turn ? static_cast<float *>(d_cloud_) + 3 * (size_t)cap_ : static_cast<float *>(d_cloud_);
+        float     *d_up = turn ? d_cloud_.as<float>() + 3 * (size_t)cap_ : d_cloud_.as<float>();
         if (turn && stride > 5) return (void)std::fprintf(stderr, "MLS::addToMap: stride %d > 5 floats\n", stride);
         if (slam_memcpy_h2d(d_up, cloud_xyz, sizeof(float) * (size_t)n * stride, nullptr) != SLAM_OK) return warn();
         if (turn) { // mls.cpp:34-53 on the device (round 6: the host loop was 0.15 of a cloud's 0.35 ms)
-            if (slam_grid_transform_cloud_dev(d_up, n, stride, R, t, static_cast<float *>(d_cloud_), nullptr) != SLAM_OK) return warn();
+            if (slam_grid_transform_cloud_dev(d_up, n, stride, R, t, d_cloud_.as<float>(), nullptr) != SLAM_OK) return warn();
             stride = 3;
         }
-        if (slam_gseg_segment_dev(gseg_, (const float *)d_cloud_, n, stride, (uint8_t *)d_labels_, nullptr) != SLAM_OK) return warn();
-        if (slam_gseg_split_dev(gseg_, (const float *)d_cloud_, n, stride, (const uint8_t *)d_labels_, (float *)d_gnd_, (float *)d_obs_,
-                                (int32_t *)d_counts_, nullptr) != SLAM_OK)
+        if (slam_gseg_segment_dev(gseg_, d_cloud_.as<float>(), n, stride, d_labels_.as<uint8_t>(), nullptr) != SLAM_OK) return warn();
+        if (slam_gseg_split_dev(gseg_, d_cloud_.as<float>(), n, stride, d_labels_.as<uint8_t>(), d_gnd_.as<float>(), d_obs_.as<float>(),
+                                d_counts_.as<int32_t>(), nullptr) != SLAM_OK)
             return warn();
         // the two counts, and the drv cloud where global_cloud is kept, come back into PINNED memory (a read-back into pageable
         // memory is staged by the runtime: 0.1 ms for the cloud's 300 KB)
-        if (!pin_reserve(64)) return warn();
-        int32_t *counts = static_cast<int32_t *>(h_pin_); // ground, obstacle
-        if (slam_memcpy_d2h(counts, d_counts_, 2 * sizeof(int32_t), nullptr) != SLAM_OK) return warn();
+        if (!detail::reserve_half(h_pin_, 64)) return warn();
+        int32_t *counts = h_pin_.as<int32_t>(); // ground, obstacle
+        if (slam_memcpy_d2h(counts, d_counts_.p, 2 * sizeof(int32_t), nullptr) != SLAM_OK) return warn();
         const int32_t n_gnd = counts[0], n_drv = counts[1];
         const float  *drv_ = nullptr;
         if (!disable_pointcloud_ && n_drv > 0) { // *global_cloud += drv_cloud (:144-149): read back BEFORE the grid update is
-            if (!pin_reserve(64 + 16 * (size_t)n_drv)) return warn(); // enqueued (it runs while the host appends)
-            drv_ = reinterpret_cast<const float *>(static_cast<unsigned char *>(h_pin_) + 64);
-            if (slam_memcpy_d2h(static_cast<unsigned char *>(h_pin_) + 64, d_obs_, 16 * (size_t)n_drv, nullptr) != SLAM_OK) return warn();
+            if (!detail::reserve_half(h_pin_, 64 + 16 * (size_t)n_drv)) return warn(); // enqueued (it runs while the host appends)
+            drv_ = reinterpret_cast<const float *>(h_pin_.as<unsigned char>() + 64);
+            if (slam_memcpy_d2h(h_pin_.as<unsigned char>() + 64, d_obs_.p, 16 * (size_t)n_drv, nullptr) != SLAM_OK) return warn();
         }
-        counts = nullptr; // (pin_reserve may have moved the block)
-        if (slam_grid_add_scan_inorder_dev(h_, (const float *)d_obs_, n_drv, (const float *)d_gnd_, n_gnd, 4, nullptr) != SLAM_OK)
+        counts = nullptr; // (the reserve may have moved the block)
+        if (slam_grid_add_scan_inorder_dev(h_, d_obs_.as<float>(), n_drv, d_gnd_.as<float>(), n_gnd, 4, nullptr) != SLAM_OK)
             return warn();
         if (drv_) {
             const size_t at = global_cloud_.size();
@@ -169,18 +198,6 @@ public:
         last_counts_[0] = n_drv;
         last_counts_[1] = n_gnd;
     }
-    bool pin_reserve(size_t bytes)
-    {
-        if (bytes <= pin_cap_) return true;
-        slam_device_synchronize();
-        slam_host_free(h_pin_);
-        h_pin_ = nullptr;
-        pin_cap_ = 0;
-        const size_t want = bytes + bytes / 2;
-        if (slam_host_alloc(&h_pin_, want) != SLAM_OK) return false;
-        pin_cap_ = want;
-        return true;
-    }
     // mls.cpp:34-53: setPose, then (rolling) the cloud turned into the global orientation and offset by the
     // sub-cell residual curPose - pose (tf::poseMsgToEigen + pcl::transformPointCloud: computed in double, stored
     // as float), then addToOccupancy of that cloud
@@ -192,10 +209,8 @@ public:
         double cx = 0, cy = 0;
         slam_grid_get_pose(h_, &cx, &cy);
         const double tx = cx - pose.x, ty = cy - pose.y, tz = pose.z;
-        const double d = pose.qx * pose.qx + pose.qy * pose.qy + pose.qz * pose.qz + pose.qw * pose.qw, s2 = d > 0 ? 2.0 / d : 0.0;
-        const double xs = pose.qx * s2, ys = pose.qy * s2, zs = pose.qz * s2, wx = pose.qw * xs, wy = pose.qw * ys, wz = pose.qw * zs,
-                     xx = pose.qx * xs, xy = pose.qx * ys, xz = pose.qx * zs, yy = pose.qy * ys, yz = pose.qy * zs, zz = pose.qz * zs;
-        const double r[9] = {1.0 - (yy + zz), xy - wz, xz + wy, xy + wz, 1.0 - (xx + zz), yz - wx, xz - wy, yz + wx, 1.0 - (xx + yy)};
+        double       r[9];
+        detail::tf_matrix(pose, r);
         // (float)(r0 x + r1 y + r2 z + t) per coordinate, in double: slam_grid_transform_cloud_dev, the same floats as the host loop
         // this was until round 6 (tests/test_gpu_cpp_adapters.py holds the map against the oracle's, which transforms on the host)
         const double t3[3] = {tx, ty, tz};
@@ -233,60 +248,21 @@ public:
         const size_t n = global_cloud_.size() / 3;
         if (n > (size_t)1 << 30) return false;
         if (!cc_ && slam_ccicp_create(&cc_) != SLAM_OK) return false;
-        if (n > gc_cap_) {
-            slam_device_synchronize();
-            slam_free(d_gc_in_), slam_free(d_gc_out_);
-            d_gc_in_ = d_gc_out_ = nullptr;
-            gc_cap_ = 0;
-            const size_t want = n + n / 2;
-            if (slam_malloc(&d_gc_in_, 12 * want) != SLAM_OK || slam_malloc(&d_gc_out_, 16 * want) != SLAM_OK) return false;
-            gc_cap_ = want;
-        }
-        if (!pin_reserve(64 + 16 * n)) return false;
-        if (slam_memcpy_h2d(d_gc_in_, global_cloud_.data(), 12 * n, nullptr) != SLAM_OK) return false;
+        if (!detail::reserve_half(d_gc_in_, 12 * n) || !detail::reserve_half(d_gc_out_, 16 * n)) return false;
+        if (!detail::reserve_half(h_pin_, 64 + 16 * n)) return false;
+        if (slam_memcpy_h2d(d_gc_in_.p, global_cloud_.data(), 12 * n, nullptr) != SLAM_OK) return false;
         int n_out = 0;
-        if (slam_ccicp_voxel_downsample_dev(cc_, (const float *)d_gc_in_, nullptr, (int)n, 3, (float)xy, (float)xy, (float)z, (float *)d_gc_out_,
+        if (slam_ccicp_voxel_downsample_dev(cc_, d_gc_in_.as<float>(), nullptr, (int)n, 3, (float)xy, (float)xy, (float)z, d_gc_out_.as<float>(),
                                             (int)n, &n_out, nullptr) != SLAM_OK)
             return false;
-        float *rec = reinterpret_cast<float *>(static_cast<unsigned char *>(h_pin_) + 64);
-        if (n_out > 0 && slam_memcpy_d2h(rec, d_gc_out_, 16 * (size_t)n_out, nullptr) != SLAM_OK) return false;
+        float *rec = reinterpret_cast<float *>(h_pin_.as<unsigned char>() + 64);
+        if (n_out > 0 && slam_memcpy_d2h(rec, d_gc_out_.p, 16 * (size_t)n_out, nullptr) != SLAM_OK) return false;
         global_cloud_.resize(3 * (size_t)n_out);
         for (int i = 0; i < n_out; ++i)
             for (int k = 0; k < 3; ++k) global_cloud_[3 * (size_t)i + k] = rec[4 * (size_t)i + k];
         return true;
     }
-    void filter_on_host(double xy, double z)
-    {
-        const size_t n = global_cloud_.size() / 3;
-        if (!n) return;
-        float mn[3] = {global_cloud_[0], global_cloud_[1], global_cloud_[2]}, mx[3] = {mn[0], mn[1], mn[2]};
-        for (size_t i = 0; i < n; ++i)
-            for (int k = 0; k < 3; ++k) {
-                mn[k] = std::min(mn[k], global_cloud_[3 * i + k]);
-                mx[k] = std::max(mx[k], global_cloud_[3 * i + k]);
-            }
-        const float inv[3] = {(float)(1.0 / xy), (float)(1.0 / xy), (float)(1.0 / z)};
-        long        lo[3], div[3];
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = (long)std::floor(mn[k] * inv[k]);
-            div[k] = (long)std::floor(mx[k] * inv[k]) - lo[k] + 1;
-        }
-        struct Acc { double s[3] = {0, 0, 0}; long n = 0; };
-        std::map<long, Acc> vox;
-        for (size_t i = 0; i < n; ++i) {
-            long idx = 0, mul = 1;
-            for (int k = 0; k < 3; ++k) {
-                idx += ((long)std::floor(global_cloud_[3 * i + k] * inv[k]) - lo[k]) * mul;
-                mul *= div[k];
-            }
-            Acc &a = vox[idx];
-            for (int k = 0; k < 3; ++k) a.s[k] += global_cloud_[3 * i + k];
-            ++a.n;
-        }
-        global_cloud_.clear();
-        for (const auto &kv : vox)
-            for (int k = 0; k < 3; ++k) global_cloud_.push_back((float)(kv.second.s[k] / (double)kv.second.n));
-    }
+    void filter_on_host(double xy, double z) { voxel_filter_host(global_cloud_, xy, z); }
     const std::vector<float> &getGlobalCloud() const { return global_cloud_; }                // mls.h:216 (x, y, z per point)
     void setDisablePointCloud(bool v) { disable_pointcloud_ = v; }                            // mls.h:223
     const int *lastSegmentCounts() const { return last_counts_; }                             // drv, ground points of the last cloud
@@ -314,19 +290,17 @@ public:
     slam_grid_t *handle() { return h_; }
 
 private:
-    void warn() const { std::fprintf(stderr, "MLS: %s\n", slam_last_error()); }
+    static void warn() { detail::warn("MLS"); }
     slam_grid_t  *h_ = nullptr;
     slam_gseg_t  *gseg_ = nullptr;
     OccupancyGrid grid_;
     bool          rolling_ = false, disable_pointcloud_ = false;
-    void         *d_cloud_ = nullptr, *d_labels_ = nullptr, *d_gnd_ = nullptr, *d_obs_ = nullptr, *d_counts_ = nullptr;
-    int           cap_ = 0, last_counts_[2] = {0, 0};
-    std::vector<float> global_cloud_, trans_;
-    void              *h_pin_ = nullptr; // pinned: [counts | drv cloud, or the filtered global cloud]
-    slam_ccicp_t      *cc_ = nullptr;    // filterPointCloud's voxel grid
-    void              *d_gc_in_ = nullptr, *d_gc_out_ = nullptr;
-    size_t             gc_cap_ = 0;
-    size_t             pin_cap_ = 0;
+    detail::DeviceBuffer d_cloud_, d_labels_, d_gnd_, d_obs_, d_counts_; // the first four hold cap_ points each
+    int                  cap_ = 0, last_counts_[2] = {0, 0};
+    std::vector<float>   global_cloud_, trans_;
+    detail::PinnedBuffer h_pin_;       // [counts | drv cloud, or the filtered global cloud]
+    slam_ccicp_t        *cc_ = nullptr; // filterPointCloud's voxel grid
+    detail::DeviceBuffer d_gc_in_, d_gc_out_;
 };
 
 } // namespace slam_amd

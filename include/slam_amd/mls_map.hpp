@@ -2,61 +2,22 @@
 // non-rolling, height-cluster mode: graph_slam's global map (graph_slam.cpp:71), over the C-ABI (slam_mi355x.h,
 // slam_mls_*).  The rolling / occupancy mode stays slam_amd::MLS (mls.hpp).
 //
-// Clouds are float arrays (x, y, z first, `stride` floats per point), poses the Pose struct of mls.hpp.  The clouds
+// Clouds are float arrays (x, y, z first, `stride` floats per point), poses the Pose struct of pose.hpp.  The clouds
 // come from host memory: addToMap and addKeyframe upload them with a copy that waits for the map's stream, so each
 // call waits for the previous call's device work before it enqueues its own (no pipelining across keyframes here;
 // slam_mls_add_cloud_dev with device-resident clouds enqueues without a wait).  global_cloud is kept on the device
 // and read back by getGlobalCloud.
 #pragma once
-#include <algorithm>
-#include <cmath>
 #include <cstdint>
 #include <cstdio>
-#include <map>
 #include <vector>
 
-#include "slam_amd/mls.hpp" // Pose, OccupancyGrid
+#include "slam_amd/buffer.hpp"
+#include "slam_amd/mls.hpp" // OccupancyGrid, voxel_filter_host
+#include "slam_amd/pose.hpp"
 #include "slam_mi355x.h"
 
 namespace slam_amd {
-
-// pcl::VoxelGrid(xy, xy, z) on a host cloud (x, y, z per point): one centroid per occupied voxel, in increasing voxel index
-// (x fastest), the lattice anchored at the cloud's minimum -- the host filter of slam_amd::MLS::filterPointCloud (mls.hpp)
-inline void voxel_filter_host(std::vector<float> &cloud, double xy, double z)
-{
-    const size_t n = cloud.size() / 3;
-    if (!n) return;
-    float mn[3] = {cloud[0], cloud[1], cloud[2]}, mx[3] = {mn[0], mn[1], mn[2]};
-    for (size_t i = 0; i < n; ++i)
-        for (int k = 0; k < 3; ++k) {
-            mn[k] = std::min(mn[k], cloud[3 * i + k]);
-            mx[k] = std::max(mx[k], cloud[3 * i + k]);
-        }
-    const float inv[3] = {(float)(1.0 / xy), (float)(1.0 / xy), (float)(1.0 / z)};
-    long        lo[3], div[3];
-    for (int k = 0; k < 3; ++k) {
-        lo[k] = (long)std::floor(mn[k] * inv[k]);
-        div[k] = (long)std::floor(mx[k] * inv[k]) - lo[k] + 1;
-    }
-    struct Acc {
-        double s[3] = {0, 0, 0};
-        long   n = 0;
-    };
-    std::map<long, Acc> vox;
-    for (size_t i = 0; i < n; ++i) {
-        long idx = 0, mul = 1;
-        for (int k = 0; k < 3; ++k) {
-            idx += ((long)std::floor(cloud[3 * i + k] * inv[k]) - lo[k]) * mul;
-            mul *= div[k];
-        }
-        Acc &a = vox[idx];
-        for (int k = 0; k < 3; ++k) a.s[k] += cloud[3 * i + k];
-        ++a.n;
-    }
-    cloud.clear();
-    for (const auto &kv : vox)
-        for (int k = 0; k < 3; ++k) cloud.push_back((float)(kv.second.s[k] / (double)kv.second.n));
-}
 
 class MLSMap {
 public:
@@ -85,8 +46,7 @@ public:
     }
     ~MLSMap()
     {
-        if (st_) slam_stream_synchronize(st_);
-        slam_free(d_cloud_), slam_free(d_kf_), slam_free(d_gc_), slam_free(d_filt_);
+        if (st_) slam_stream_synchronize(st_); // (the one stream that uses the buffers, which go with their members)
         slam_ccicp_destroy(cc_);
         slam_mls_destroy(h_);
         if (st_) slam_stream_destroy(st_);
@@ -116,7 +76,7 @@ public:
     void addToMap(const float *xyz, int n, int stride) // mls.cpp:345-402
     {
         if (!h_ || n <= 0) return;
-        float *d = stage(xyz, n, stride, d_cloud_, cap_cloud_);
+        float *d = stage(xyz, n, stride, d_cloud_);
         if (!d || slam_mls_add_cloud_dev(h_, d, n, stride, st_) != SLAM_OK) return warn();
         append_global(d, n, stride);
     }
@@ -126,14 +86,14 @@ public:
     {
         setPose(pose);
         if (!h_ || n <= 0) return;
-        float *d_in = stage(xyz, n, stride, d_kf_, cap_kf_);
+        float *d_in = stage(xyz, n, stride, d_kf_);
         if (!d_in) return warn();
-        if (!reserve(d_cloud_, cap_cloud_, sizeof(float) * 3 * (size_t)n)) return warn();
+        if (!detail::reserve_half(d_cloud_, sizeof(float) * 3 * (size_t)n)) return warn();
         double r[9], t[3] = {pose.x, pose.y, pose.z};
-        rotation(pose, r);
-        if (slam_grid_transform_cloud_dev(d_in, n, stride, r, t, (float *)d_cloud_, st_) != SLAM_OK) return warn();
-        if (slam_mls_add_cloud_dev(h_, (const float *)d_cloud_, n, 3, st_) != SLAM_OK) return warn();
-        append_global((const float *)d_cloud_, n, 3);
+        detail::tf_matrix(pose, r); // tf::poseMsgToEigen: the quaternion's matrix (as MLS::addToMap)
+        if (slam_grid_transform_cloud_dev(d_in, n, stride, r, t, d_cloud_.as<float>(), st_) != SLAM_OK) return warn();
+        if (slam_mls_add_cloud_dev(h_, d_cloud_.as<float>(), n, 3, st_) != SLAM_OK) return warn();
+        append_global(d_cloud_.as<float>(), n, 3);
     }
     // mls.cpp:481-505: clusters' mean z (device), global_cloud's z (+ (float)pose.z, float arithmetic)
     void offsetMap(const Pose &pose)
@@ -144,14 +104,14 @@ public:
         std::vector<float> gc = getGlobalCloud();
         const float        dz = (float)pose.z;
         for (size_t i = 2; i < gc.size(); i += 3) gc[i] = gc[i] + dz;
-        slam_memcpy_h2d(d_gc_, gc.data(), gc.size() * sizeof(float), st_);
+        slam_memcpy_h2d(d_gc_.p, gc.data(), gc.size() * sizeof(float), st_);
     }
     std::vector<float> getGlobalCloud() // mls.h:214 (x, y, z per point)
     {
         std::vector<float> out(3 * n_gc_);
         if (h_ && n_gc_) {
             slam_stream_synchronize(st_);
-            slam_memcpy_d2h(out.data(), d_gc_, out.size() * sizeof(float), st_);
+            slam_memcpy_d2h(out.data(), d_gc_.p, out.size() * sizeof(float), st_);
         }
         return out;
     }
@@ -167,17 +127,17 @@ public:
     {
         if (n_gc_ > ((size_t)1 << 30)) return false;
         if (!cc_ && slam_ccicp_create(&cc_) != SLAM_OK) return false;
-        if (!reserve(d_filt_, cap_filt_, 16 * n_gc_)) return false;
+        if (!detail::reserve_half(d_filt_, 16 * n_gc_)) return false;
         int n_out = 0;
-        if (slam_ccicp_voxel_downsample_dev(cc_, (const float *)d_gc_, nullptr, (int)n_gc_, 3, (float)xy, (float)xy, (float)z, (float *)d_filt_,
+        if (slam_ccicp_voxel_downsample_dev(cc_, d_gc_.as<float>(), nullptr, (int)n_gc_, 3, (float)xy, (float)xy, (float)z, d_filt_.as<float>(),
                                             (int)n_gc_, &n_out, st_) != SLAM_OK)
             return false;
         slam_stream_synchronize(st_);
         std::vector<float> rec(4 * (size_t)n_out), gc(3 * (size_t)n_out);
-        if (n_out) slam_memcpy_d2h(rec.data(), d_filt_, rec.size() * sizeof(float), st_);
+        if (n_out) slam_memcpy_d2h(rec.data(), d_filt_.p, rec.size() * sizeof(float), st_);
         for (int i = 0; i < n_out; ++i)
             for (int k = 0; k < 3; ++k) gc[3 * (size_t)i + k] = rec[4 * (size_t)i + k];
-        if (n_out) slam_memcpy_h2d(d_gc_, gc.data(), gc.size() * sizeof(float), st_);
+        if (n_out) slam_memcpy_h2d(d_gc_.p, gc.data(), gc.size() * sizeof(float), st_);
         n_gc_ = (size_t)n_out;
         return true;
     }
@@ -229,11 +189,11 @@ public:
         std::vector<float> gc = getGlobalCloud();
         voxel_filter_host(gc, xy, z);
         n_gc_ = gc.size() / 3;
-        if (n_gc_) slam_memcpy_h2d(d_gc_, gc.data(), gc.size() * sizeof(float), st_);
+        if (n_gc_) slam_memcpy_h2d(d_gc_.p, gc.data(), gc.size() * sizeof(float), st_);
     }
 
 private:
-    void warn() const { std::fprintf(stderr, "MLSMap: %s\n", slam_last_error()); }
+    static void warn() { detail::warn("MLSMap"); }
     template <class F>
     void with(F set)
     {
@@ -244,45 +204,24 @@ private:
         if (slam_mls_set_params(h_, &p) != SLAM_OK) return warn();
         slam_mls_info(h_, nullptr, nullptr, nullptr, nullptr, &p_, nullptr);
     }
-    static void rotation(const Pose &q, double r[9]) // tf::poseMsgToEigen: the quaternion's matrix (as mls.hpp)
-    {
-        const double d = q.qx * q.qx + q.qy * q.qy + q.qz * q.qz + q.qw * q.qw, s2 = d > 0 ? 2.0 / d : 0.0;
-        const double xs = q.qx * s2, ys = q.qy * s2, zs = q.qz * s2, wx = q.qw * xs, wy = q.qw * ys, wz = q.qw * zs, xx = q.qx * xs,
-                     xy = q.qx * ys, xz = q.qx * zs, yy = q.qy * ys, yz = q.qy * zs, zz = q.qz * zs;
-        const double m[9] = {1.0 - (yy + zz), xy - wz, xz + wy, xy + wz, 1.0 - (xx + zz), yz - wx, xz - wy, yz + wx, 1.0 - (xx + yy)};
-        for (int k = 0; k < 9; ++k) r[k] = m[k];
-    }
-    bool reserve(void *&d, size_t &cap, size_t bytes)
-    {
-        if (bytes <= cap) return true;
-        if (st_) slam_stream_synchronize(st_);
-        slam_device_synchronize();
-        slam_free(d);
-        d = nullptr;
-        cap = 0;
-        const size_t want = bytes + bytes / 2;
-        if (slam_malloc(&d, want) != SLAM_OK) return false;
-        cap = want;
-        return true;
-    }
     // the host cloud uploaded into a device buffer (the copy waits for the stream's earlier use of the buffer)
-    float *stage(const float *xyz, int n, int stride, void *&d, size_t &cap)
+    float *stage(const float *xyz, int n, int stride, detail::DeviceBuffer &d)
     {
         const size_t bytes = sizeof(float) * (size_t)n * stride;
-        if (!reserve(d, cap, bytes)) return nullptr;
-        if (slam_memcpy_h2d(d, xyz, bytes, st_) != SLAM_OK) return nullptr;
-        return static_cast<float *>(d);
+        if (!detail::reserve_half(d, bytes)) return nullptr;
+        if (slam_memcpy_h2d(d.p, xyz, bytes, st_) != SLAM_OK) return nullptr;
+        return d.as<float>();
     }
     // *global_cloud += *input_cloud (mls.cpp:397-400), on the device
     void append_global(const float *d, int n, int stride)
     {
         if (disable_pointcloud_) return;
-        if (3 * sizeof(float) * (n_gc_ + n) > cap_gc_) {
+        if (3 * sizeof(float) * (n_gc_ + n) > d_gc_.cap) {
             std::vector<float> keep = getGlobalCloud();
-            if (!reserve(d_gc_, cap_gc_, 3 * sizeof(float) * 2 * (n_gc_ + n))) return warn();
-            if (!keep.empty()) slam_memcpy_h2d(d_gc_, keep.data(), keep.size() * sizeof(float), st_);
+            if (!detail::reserve_half(d_gc_, 3 * sizeof(float) * 2 * (n_gc_ + n))) return warn(); // (twice what is there, on top of the half)
+            if (!keep.empty()) slam_memcpy_h2d(d_gc_.p, keep.data(), keep.size() * sizeof(float), st_);
         }
-        float *dst = static_cast<float *>(d_gc_) + 3 * n_gc_;
+        float *dst = d_gc_.as<float>() + 3 * n_gc_;
         if (stride == 3) {
             slam_memcpy_d2d(dst, d, 3 * sizeof(float) * (size_t)n, st_);
         } else { // the x, y, z of each point: the identity transform (exact in double) packs them
@@ -297,8 +236,8 @@ private:
     slam_mls_params p_{};
     OccupancyGrid   grid_;
     bool            disable_pointcloud_ = false;
-    void           *d_cloud_ = nullptr, *d_kf_ = nullptr, *d_gc_ = nullptr, *d_filt_ = nullptr;
-    size_t          cap_cloud_ = 0, cap_kf_ = 0, cap_gc_ = 0, cap_filt_ = 0, n_gc_ = 0;
+    detail::DeviceBuffer d_cloud_, d_kf_, d_gc_, d_filt_;
+    size_t          n_gc_ = 0;
     slam_ccicp_t   *cc_ = nullptr;
 };
 

@@ -82,7 +82,7 @@ public:
     // :356-384, as written
     static Pose poseOffset(const Pose &pre, const Pose &post, const Pose &curPose)
     {
-        using graph_detail::tf_yaw;
+        using detail::tf_yaw;
         const double vnx = post.x - pre.x, vny = post.y - pre.y, vnz = post.z - pre.z;
         double       vntheta = tf_yaw(post) - tf_yaw(pre);
         if (vntheta > M_PI)
@@ -110,7 +110,7 @@ private:
         if (rc != SLAM_OK) warn();
         return rc == SLAM_OK;
     }
-    static void warn() { std::fprintf(stderr, "PoseGraphOptimizer: %s\n", slam_last_error()); }
+    static void warn() { detail::warn("PoseGraphOptimizer"); }
 
     slam_pgo_t     *h_ = nullptr;
     slam_pgo_result last_ = {};

@@ -1053,7 +1053,7 @@ class PoseGraph:
 
     @staticmethod
     def _tf_yaw(p):
-        """tf::getYaw as slam_amd::graph_detail::tf_yaw computes it"""
+        """tf::getYaw as slam_amd::detail::tf_yaw (include/slam_amd/pose.hpp) computes it"""
         qx, qy, qz, qw = (float(v) for v in p[3:7])
         s = 2.0 / (qx * qx + qy * qy + qz * qz + qw * qw)
         ys, zs = qy * s, qz * s

@@ -183,7 +183,18 @@ def brute_force(points, queries, gate, strict):
 
 
 # ------------------------------------------------------------------ calcEdgeIcp's host parts (graphSlamTools.cpp:240-260, 318-360)
-# Python floats are IEEE doubles: the operations below are those of include/slam_amd/graph_edges.hpp in the same order.
+# Python floats are IEEE doubles: the operations below are those of include/slam_amd/pose.hpp in the same order.
+def tf_matrix(q):
+    """tf::Matrix3x3::setRotation; q = (x, y, z, w).  The zero quaternion gives the identity, as detail::tf_matrix does."""
+    x, y, z, w = (float(v) for v in q)
+    d = x * x + y * y + z * z + w * w
+    s = 2.0 / d if d > 0 else 0.0
+    xs, ys, zs = x * s, y * s, z * s
+    wx, wy, wz, xx, xy, xz, yy, yz, zz = w * xs, w * ys, w * zs, x * xs, x * ys, x * zs, y * ys, y * zs, z * zs
+    return [1.0 - (yy + zz), xy - wz, xz + wy, xy + wz, 1.0 - (xx + zz), yz - wx, xz - wy, yz + wx, 1.0 - (xx + yy)]
+
+
+
 def quat_to_matrix(q):
     """Eigen::Quaterniond(w, x, y, z).toRotationMatrix(); q = (x, y, z, w)."""
     x, y, z, w = (float(v) for v in q)
