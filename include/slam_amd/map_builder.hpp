@@ -14,6 +14,13 @@
 // `carve` (default false, fixed at construction; docs/VOXEL_MAP.md section 8): every accepted cloud, the first included, is
 // carved with trans_full right after it is integrated, and map() and the cropped map a scan registers against are the carved
 // extraction at CARVE_NUM / CARVE_DEN.  While it is false nothing here calls a carve entry point.
+// `direct` (default false, fixed at construction; docs/VOXEL_MAP.md section 9): the builder owns a second map of leaf DIST_LEAF
+// with plane distributions; every accepted cloud goes into both maps with the same transform, and a later scan is registered
+// with slam_vmap_register_gicp straight against the second map's plane voxels from init = trans_full: no extraction, no map
+// keyframe (mapKeyframe() stays -1), `last_direct` instead of `last`, and the fitness that is held against MAX_SCORE is the
+// point-to-plane score.  map() stays the LEAF_SIZE map.  With carve on as well the second map is carved too and the carved
+// rule at CARVE_NUM / CARVE_DEN (as they stand at construction) is part of its plane rule.  While it is false nothing here
+// calls an entry point of section 9.
 //
 // Stated deviations (docs/VOXEL_MAP.md section 5):
 //   * the start is passed to the solver as `init` instead of moving the source first (:144), so the solver's result is
@@ -49,14 +56,18 @@ public:
     int                    CARVE_NUM = 1, CARVE_DEN = 1; // a voxel stays while miss * CARVE_DEN <= max(seen, 1) * CARVE_NUM
     slam_vmap_carve_params carve_params;
     slam_vmap_carve_result last_carve; // of the last accepted cloud when carve is on
+    // registration straight against a second map's plane voxels: fixed at construction
+    const bool                direct;
+    static constexpr double   DIST_LEAF = 1.0;
+    slam_vmap_gicp_result     last_direct; // the last request's result when direct is on (last_valid as for `last`)
 
     float               trans_full[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     int                 n_clouds = 0, n_accepted = 0;
     slam_kf_gicp_result last;            // the last request's result
     bool                last_valid = false; // false for the first cloud and when nothing of the map was near the pose
 
-    explicit GlobalMapBuilder(double leaf = 0.30, double gate_ = 2.0, bool carve_ = false)
-        : LEAF_SIZE(leaf), gate(gate_), carve(carve_), last_carve(), last()
+    explicit GlobalMapBuilder(double leaf = 0.30, double gate_ = 2.0, bool carve_ = false, bool direct_ = false)
+        : LEAF_SIZE(leaf), gate(gate_), carve(carve_), last_carve(), direct(direct_), last_direct(), last()
     {
         slam_vmap_default_carve_params(&carve_params);
         slam_vmap_params vp;
@@ -74,16 +85,29 @@ public:
             slam_kf_destroy(store_);
             store_ = nullptr;
         }
+        if (direct) {
+            slam_vmap_dist_params dp;
+            slam_vmap_default_dist_params(&dp);
+            if (carve) dp.max_miss_num = CARVE_NUM, dp.max_miss_den = CARVE_DEN;
+            vp.leaf = DIST_LEAF;
+            if (slam_vmap_create(&vp, &dmap_) != SLAM_OK || slam_vmap_enable_distributions(dmap_, &dp) != SLAM_OK) {
+                warn();
+                slam_vmap_destroy(dmap_);
+                dmap_ = nullptr;
+            }
+        }
     }
     ~GlobalMapBuilder()
     {
         slam_kf_destroy(store_);
+        slam_vmap_destroy(dmap_);
         slam_vmap_destroy(vmap_);
     }
     GlobalMapBuilder(const GlobalMapBuilder &) = delete;
     GlobalMapBuilder &operator=(const GlobalMapBuilder &) = delete;
-    bool         ok() const { return vmap_ && store_; }
+    bool         ok() const { return vmap_ && store_ && (dmap_ || !direct); }
     slam_vmap_t *vmap() { return vmap_; }
+    slam_vmap_t *distMap() { return dmap_; } // the DIST_LEAF map of direct mode, NULL otherwise
     slam_kf_t   *store() { return store_; }
     int          mapKeyframe() const { return map_id_; }
     const float *pose() const { return trans_full; }
@@ -108,6 +132,10 @@ public:
         if (n_points == 0) { // :63-70: the first cloud is the map
             if (slam_vmap_integrate(vmap_, xyz, n, stride, nullptr, nullptr, nullptr) != SLAM_OK) return warn(), false;
             if (carve && slam_vmap_carve(vmap_, xyz, n, stride, nullptr, nullptr, nullptr, &carve_params, &last_carve) != SLAM_OK) return warn(), false;
+            if (direct) {
+                if (slam_vmap_integrate(dmap_, xyz, n, stride, nullptr, nullptr, nullptr) != SLAM_OK) return warn(), false;
+                if (carve && slam_vmap_carve(dmap_, xyz, n, stride, nullptr, nullptr, nullptr, &carve_params, nullptr) != SLAM_OK) return warn(), false;
+            }
             ++n_accepted;
             return true;
         }
@@ -137,8 +165,40 @@ public:
     }
 
 private:
+    // direct mode: the scan against the plane voxels of the DIST_LEAF map; fills last_direct and the verdict of :182
+    bool registerDirect(int scan)
+    {
+        slam_vmap_gicp_req rq;
+        rq.src = scan;
+        for (int k = 0; k < 16; ++k) rq.init[k] = trans_full[k];
+        slam_vmap_gicp_params gp;
+        slam_vmap_default_gicp_params(&gp);
+        gp.gate = gate, gp.max_iterations = MAX_ITERATIONS, gp.transformation_epsilon = TRANSFORMATION_EPSILON;
+        if (slam_vmap_register_gicp(dmap_, store_, &rq, 1, &gp, &last_direct, nullptr) != SLAM_OK) return warn(), false;
+        last_valid = true;
+        if (last_direct.fitness_pairs <= 0 || !last_direct.converged || last_direct.fitness > MAX_SCORE) return false;
+        for (int k = 0; k < 16; ++k) trans_full[k] = last_direct.transform[k];
+        return true;
+    }
+    // the accepted scan, moved by trans_full, into the map (and the second one of direct mode), carved when carve is on
+    bool integrateAccepted(int n, int stride)
+    {
+        double R[9], t[3];
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) R[3 * r + c] = (double)trans_full[4 * r + c];
+            t[r] = (double)trans_full[4 * r + 3];
+        }
+        if (slam_vmap_integrate_dev(vmap_, d_scan_.as<float>(), n, stride, R, t, nullptr, nullptr) != SLAM_OK) return warn(), false;
+        if (direct && slam_vmap_integrate_dev(dmap_, d_scan_.as<float>(), n, stride, R, t, nullptr, nullptr) != SLAM_OK) return warn(), false;
+        if (carve && slam_vmap_carve_dev(vmap_, d_scan_.as<float>(), n, stride, R, t, nullptr, &carve_params, &last_carve, nullptr) != SLAM_OK)
+            return warn(), false;
+        if (carve && direct && slam_vmap_carve_dev(dmap_, d_scan_.as<float>(), n, stride, R, t, nullptr, &carve_params, nullptr, nullptr) != SLAM_OK)
+            return warn(), false;
+        return true;
+    }
     bool registerAndIntegrate(int scan, int n, int stride, int n_voxels)
     {
+        if (direct) return registerDirect(scan) && integrateAccepted(n, stride);
         float lo[2], hi[2]; // the map inside the crop box
         cropBox(lo, hi);
         const int   cap = n_voxels > 0 ? n_voxels : 1;
@@ -158,20 +218,12 @@ private:
         if (slam_kf_register_gicp(store_, &rq, 1, &last, nullptr) != SLAM_OK) return warn(), false;
         last_valid = true;
         if (last.fitness_pairs <= 0 || !last.edge.converged || last.fitness > MAX_SCORE) return false; // :182
-        double R[9], t[3];
         for (int k = 0; k < 16; ++k) trans_full[k] = last.edge.transform[k];
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) R[3 * r + c] = (double)trans_full[4 * r + c];
-            t[r] = (double)trans_full[4 * r + 3];
-        }
-        if (slam_vmap_integrate_dev(vmap_, d_scan_.as<float>(), n, stride, R, t, nullptr, nullptr) != SLAM_OK) return warn(), false;
-        if (carve && slam_vmap_carve_dev(vmap_, d_scan_.as<float>(), n, stride, R, t, nullptr, &carve_params, &last_carve, nullptr) != SLAM_OK)
-            return warn(), false;
-        return true;
+        return integrateAccepted(n, stride);
     }
     static void warn() { detail::warn("GlobalMapBuilder"); }
 
-    slam_vmap_t         *vmap_ = nullptr;
+    slam_vmap_t         *vmap_ = nullptr, *dmap_ = nullptr;
     slam_kf_t           *store_ = nullptr;
     detail::DeviceBuffer d_scan_, d_map_;
     int                  map_id_ = -1;

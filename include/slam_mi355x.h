@@ -996,6 +996,83 @@ int  slam_vmap_read_carved(slam_vmap_t *m, const float lo_xy[2], const float hi_
 /* seen and miss of every occupied voxel in ascending key order, as slam_vmap_read_sums; zeros on a map never carved. */
 int  slam_vmap_read_carve(slam_vmap_t *m, uint32_t *seen, uint32_t *miss, uint64_t *key, int cap, int *n_out);
 
+/* Per-voxel plane distributions and Generalized ICP straight against the map (docs/VOXEL_MAP.md section 9; the device
+ * equals tests/cpp/vmap_gicp_oracle.cpp: moments and distributions bit for bit, the registration as docs/KF_GICP.md holds
+ * the store's).  Opt-in: nine more int64 accumulators per voxel, in units of 2^-16 m and 2^-32 m^2 from the cell's corner.
+ *   L         (int64) rint(leaf 2^20); fx = the point's term of the sums, rint((double) q 2^20)
+ *   e_k       floor((fx_k - cell_k L) / 16): an arithmetic shift by 4
+ *   moments   E_k += e_k (3), M_kl += e_k e_l for xx xy xz yy yz zz (6): exact while a voxel holds fewer than 2^21 points
+ *   plane     m_k = (double) E_k / n, C_kl = ((double) M_kl / n - m_k m_l) 2^-32, every operation rounded on its own; the
+ *             Jacobi decomposition of slam_kf_compute_covariances gives l0 >= l1 >= l2 and the normal; a voxel is a plane
+ *             voxel iff count >= min_points, l1 >= flat_ratio l2, l1 >= line_ratio l0 and, when max_miss_den > 0, it
+ *             passes slam_vmap_extract_carved_dev's rule; its covariance is (I - n n') + epsilon n n' */
+typedef struct {
+    int    min_points;   /* fewest points of a plane voxel (6) */
+    double flat_ratio;   /* l1 >= flat_ratio l2 (4.0) */
+    double line_ratio;   /* l1 >= line_ratio l0 (0.01) */
+    double epsilon;      /* the covariance along the normal, as slam_kf_gicp_params.gicp_epsilon (1e-3) */
+    int    max_miss_num; /* with max_miss_den > 0: a voxel failing the carved rule miss den <= max(seen, 1) num is no plane */
+    int    max_miss_den; /* voxel either; 0 (default): the carve planes are ignored */
+} slam_vmap_dist_params;
+
+void slam_vmap_default_dist_params(slam_vmap_dist_params *p);
+/* Legal only on a map with no voxels (after create or clear) and leaf <= 8 m: SLAM_E_INVALID otherwise.  params NULL: the
+ * defaults.  Allocates the planes at the table's size; slam_vmap_params is not touched.  A second call on an empty map
+ * replaces the parameters.  Synchronous: the planes are cleared on the null stream before it returns. */
+int  slam_vmap_enable_distributions(slam_vmap_t *m, const slam_vmap_dist_params *params);
+/* E[3 i ..] and M[6 i ..] of every occupied voxel in ascending key order, as slam_vmap_read_sums; SLAM_E_INVALID on a map
+ * without distributions.  Host arrays, each nullable; synchronous. */
+int  slam_vmap_read_moments(slam_vmap_t *m, int64_t *E3, int64_t *M6, uint64_t *key, int cap, int *n_out);
+/* One lane per slot: centroid, normal, covariance, eigenvalues and flag of every voxel from its moments.  Idempotent;
+ * does nothing when no integrate, clear, rehash or carve has happened since the last call.  Asynchronous on `stream`. */
+int  slam_vmap_compute_distributions(slam_vmap_t *m, slam_stream_t stream);
+/* Per occupied voxel in ascending key order: centroid (3 floats), normal (3 doubles), cov6 (xx xy xz yy yz zz), eigenvalues
+ * (l0 l1 l2) and flag (1: plane voxel; the normal and cov6 of other voxels are zero).  Computes the distributions when
+ * they are stale.  Host arrays, each nullable; synchronous. */
+int  slam_vmap_read_distributions(slam_vmap_t *m, float *centroid3, double *normal3, double *cov6, double *eig3, uint8_t *flag,
+                                  uint64_t *key, int cap, int *n_out);
+
+typedef struct {
+    int   src;      /* keyframe id of the store: its filtered cloud is the source */
+    float init[16]; /* 4 x 4 row-major, as slam_kf_edge_req */
+} slam_vmap_gicp_req;
+
+typedef struct {
+    double gate;                   /* a pair's centroid lies strictly inside this distance (2.0); the candidates are those of
+                                      the 27 cells around the moved point whatever the gate */
+    int    max_iterations;         /* 100 */
+    double transformation_epsilon; /* 1e-6 */
+    double rotation_epsilon;       /* 2e-3 */
+} slam_vmap_gicp_params;
+
+typedef struct {
+    float  transform[16];     /* the f64 result rounded once, row-major */
+    double transform64[16];
+    int    iterations, state; /* SLAM_KF_ITERATIONS, _TRANSFORM, _NO_CORRESPONDENCES (fewer than 3 pairs), _DEGENERATE */
+    int    converged, pairs;  /* pairs kept in the last iteration */
+    double mse;               /* mean f32 d^2 (to the centroid) of those pairs */
+    double cost;              /* sum r' M r / pairs of the last iteration */
+    double hessian[36];       /* sum J' M J of the last iteration */
+    double fitness;           /* one last pass with the f32 transform, points moved in f32: the mean over its pairs of
+                                 (n . (q - x))^2 in f64, a point-to-plane score */
+    int    fitness_pairs, reserved;
+} slam_vmap_gicp_result;
+
+void slam_vmap_default_gicp_params(slam_vmap_gicp_params *p);
+/* Registers keyframe req[e].src of `store` against the plane voxels of `m` by the plane-to-plane Gauss-Newton iteration of
+ * docs/KF_GICP.md section 1.2.  The pairs: x = the source point moved by T in f64, rounded to f32; candidates are the plane
+ * voxels among the 27 cells around cell(x); d^2 to the stored centroid in f32; the winner is the smallest (d^2, key) and is
+ * kept iff (double) d^2 < gate^2.  Source covariances are the store's, computed on demand.  One workgroup per request, one
+ * launch.  SLAM_E_INVALID before any launch for a map without distributions, a dead keyframe id, gate <= 0,
+ * max_iterations < 1, n < 0 or a null pointer.  WAITS ONCE for `stream`, for the results (and once per keyframe whose
+ * covariances are computed first); stale distributions are computed on `stream` before the launch, without a wait.
+ * pairs_trace (optional, host): trace_cap ints per request, the pairs of each iteration (-1 behind the last). */
+int  slam_vmap_register_gicp(slam_vmap_t *m, slam_kf_t *store, const slam_vmap_gicp_req *req, int n,
+                             const slam_vmap_gicp_params *params, slam_vmap_gicp_result *out, slam_stream_t stream);
+int  slam_vmap_register_gicp_traced(slam_vmap_t *m, slam_kf_t *store, const slam_vmap_gicp_req *req, int n,
+                                    const slam_vmap_gicp_params *params, slam_vmap_gicp_result *out, int32_t *pairs_trace,
+                                    int trace_cap, slam_stream_t stream);
+
 /* -------------------------------------------------------------------------
  * Pose-graph optimiser: graph_slam's optimizeGraph (graph_slam.cpp:322-390), i.e. g2o's VertexSE3 / EdgeSE3 under
  * OptimizationAlgorithmLevenberg, restated in docs/PGO.md (parity with g2o itself is unpinned; the yardstick is

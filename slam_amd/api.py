@@ -133,6 +133,26 @@ class VmapCarveResult(C.Structure):
                 ("n_seen", C.c_int64), ("n_missed", C.c_int64)]
 
 
+class VmapDistParams(C.Structure):
+    _fields_ = [("min_points", C.c_int), ("flat_ratio", C.c_double), ("line_ratio", C.c_double), ("epsilon", C.c_double),
+                ("max_miss_num", C.c_int), ("max_miss_den", C.c_int)]
+
+
+class VmapGicpReq(C.Structure):
+    _fields_ = [("src", C.c_int), ("init", C.c_float * 16)]
+
+
+class VmapGicpParams(C.Structure):
+    _fields_ = [("gate", C.c_double), ("max_iterations", C.c_int), ("transformation_epsilon", C.c_double),
+                ("rotation_epsilon", C.c_double)]
+
+
+class VmapGicpResult(C.Structure):
+    _fields_ = [("transform", C.c_float * 16), ("transform64", C.c_double * 16), ("iterations", C.c_int), ("state", C.c_int),
+                ("converged", C.c_int), ("pairs", C.c_int), ("mse", C.c_double), ("cost", C.c_double),
+                ("hessian", C.c_double * 36), ("fitness", C.c_double), ("fitness_pairs", C.c_int), ("reserved", C.c_int)]
+
+
 class PgoParams(C.Structure):
     _fields_ = [("max_trials", C.c_int), ("tau", C.c_double), ("good_lower", C.c_double), ("good_upper", C.c_double),
                 ("ordering", C.c_int), ("max_band_bytes", C.c_size_t)]
@@ -217,6 +237,8 @@ EXPORTS = [
     "slam_vmap_integrate_dev", "slam_vmap_extract_dev", "slam_vmap_read", "slam_vmap_read_sums", "slam_vmap_info",
     "slam_vmap_default_carve_params", "slam_vmap_carve_dev", "slam_vmap_carve", "slam_vmap_extract_carved_dev", "slam_vmap_read_carved",
     "slam_vmap_read_carve",
+    "slam_vmap_default_dist_params", "slam_vmap_enable_distributions", "slam_vmap_read_moments", "slam_vmap_compute_distributions",
+    "slam_vmap_read_distributions", "slam_vmap_default_gicp_params", "slam_vmap_register_gicp", "slam_vmap_register_gicp_traced",
     "slam_pgo_default_params", "slam_pgo_create", "slam_pgo_destroy", "slam_pgo_clear", "slam_pgo_add_vertex",
     "slam_pgo_set_vertex", "slam_pgo_add_edge", "slam_pgo_size", "slam_pgo_optimize", "slam_pgo_read_vertices", "slam_pgo_chi2",
     "slam_pgo_read_system", "slam_pgo_step",
@@ -458,6 +480,16 @@ def lib():
     L.slam_vmap_extract_carved_dev.argtypes = [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int), _vp]
     L.slam_vmap_read_carved.argtypes = [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
     L.slam_vmap_read_carve.argtypes = [_vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
+    L.slam_vmap_default_dist_params.argtypes = [C.POINTER(VmapDistParams)]
+    L.slam_vmap_default_dist_params.restype = None
+    L.slam_vmap_enable_distributions.argtypes = [_vp, C.POINTER(VmapDistParams)]
+    L.slam_vmap_read_moments.argtypes = [_vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
+    L.slam_vmap_compute_distributions.argtypes = [_vp, _vp]
+    L.slam_vmap_read_distributions.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
+    L.slam_vmap_default_gicp_params.argtypes = [C.POINTER(VmapGicpParams)]
+    L.slam_vmap_default_gicp_params.restype = None
+    L.slam_vmap_register_gicp.argtypes = [_vp, _vp, _vp, C.c_int, C.POINTER(VmapGicpParams), _vp, _vp]
+    L.slam_vmap_register_gicp_traced.argtypes = [_vp, _vp, _vp, C.c_int, C.POINTER(VmapGicpParams), _vp, _vp, C.c_int, _vp]
     _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
     L.slam_pgo_default_params.argtypes = [C.POINTER(PgoParams)]
     L.slam_pgo_default_params.restype = None
@@ -1113,6 +1145,29 @@ def vmap_default_carve_params(**kw):
     return p
 
 
+def vmap_default_dist_params(**kw):
+    p = VmapDistParams()
+    lib().slam_vmap_default_dist_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def vmap_default_gicp_params(**kw):
+    p = VmapGicpParams()
+    lib().slam_vmap_default_gicp_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def vmap_gicp_result_dict(r):
+    return {"transform": np.array(r.transform[:], np.float32).reshape(4, 4),
+            "transform64": np.array(r.transform64[:], np.float64).reshape(4, 4), "iterations": r.iterations, "state": r.state,
+            "converged": r.converged, "pairs": r.pairs, "mse": r.mse, "cost": r.cost,
+            "hessian": np.array(r.hessian[:], np.float64).reshape(6, 6), "fitness": r.fitness, "fitness_pairs": r.fitness_pairs}
+
+
 def vmap_carve_result_dict(r):
     return {f: int(getattr(r, f)) for f, _ in VmapCarveResult._fields_}
 
@@ -1235,6 +1290,63 @@ class VoxelMap:
         check(lib().slam_vmap_read_sums(self.h, _ptr(sums), _ptr(count), _ptr(key), n, C.byref(got)))
         assert got.value == n
         return sums, count, key
+
+    # ---- plane distributions and Generalized ICP against the map (docs/VOXEL_MAP.md section 9)
+    def enable_distributions(self, params=None, **kw):
+        """slam_vmap_enable_distributions: legal on a map without voxels only.  params: a VmapDistParams, or its fields as
+        keywords over the defaults."""
+        p = params or vmap_default_dist_params(**kw)
+        check(lib().slam_vmap_enable_distributions(self.h, C.byref(p)))
+        self.dist_params = p
+
+    def compute_distributions(self, stream=None):
+        check(lib().slam_vmap_compute_distributions(self.h, _sp(stream)))
+
+    def read_moments(self):
+        """slam_vmap_read_moments: (E [n, 3] i64, M [n, 6] i64 as xx xy xz yy yz zz, key [n] u64) of every voxel."""
+        n = self.info()["n_voxels"]
+        E, M, key = np.zeros((n, 3), np.int64), np.zeros((n, 6), np.int64), np.zeros(n, np.uint64)
+        got = C.c_int()
+        check(lib().slam_vmap_read_moments(self.h, _ptr(E), _ptr(M), _ptr(key), n, C.byref(got)))
+        assert got.value == n
+        return E, M, key
+
+    def read_distributions(self):
+        """slam_vmap_read_distributions: a dict of centroid [n, 3] f32, normal [n, 3], cov6 [n, 6], eig [n, 3] f64 (descending),
+        flag [n] u8 (1: plane voxel) and key [n] u64 of every voxel in key order."""
+        n = self.info()["n_voxels"]
+        d = dict(centroid=np.zeros((n, 3), np.float32), normal=np.zeros((n, 3)), cov6=np.zeros((n, 6)), eig=np.zeros((n, 3)),
+                 flag=np.zeros(n, np.uint8), key=np.zeros(n, np.uint64))
+        got = C.c_int()
+        check(lib().slam_vmap_read_distributions(self.h, _ptr(d["centroid"]), _ptr(d["normal"]), _ptr(d["cov6"]), _ptr(d["eig"]),
+                                                 _ptr(d["flag"]), _ptr(d["key"]), n, C.byref(got)))
+        assert got.value == n
+        return d
+
+    def register_gicp(self, store, src, init=None, params=None, trace=0, stream=None, **kw):
+        """slam_vmap_register_gicp[_traced]: keyframe `src` of the KeyframeStore `store` against the map's plane voxels from
+        the 4 x 4 `init`.  src may be a list of (src, init) pairs: one launch, a list of results.  Returns
+        vmap_gicp_result_dict's fields ('pairs_trace' when trace > 0).  params: a VmapGicpParams, or its fields as keywords."""
+        single = not isinstance(src, (list, tuple))
+        reqs = [(src, init)] if single else list(src)
+        n = len(reqs)
+        req = (VmapGicpReq * max(n, 1))()
+        for e, (kid, T) in enumerate(reqs):
+            req[e].src = int(kid)
+            req[e].init[:] = np.asarray(np.eye(4) if T is None else T, dtype=np.float32).reshape(16).tolist()
+        p = params or vmap_default_gicp_params(**kw)
+        res = (VmapGicpResult * max(n, 1))()
+        tr = np.full((max(n, 1), max(trace, 1)), -1, np.int32)
+        if trace > 0:
+            check(lib().slam_vmap_register_gicp_traced(self.h, store.h, C.addressof(req), n, C.byref(p), C.addressof(res), _ptr(tr),
+                                                       int(trace), _sp(stream)))
+        else:
+            check(lib().slam_vmap_register_gicp(self.h, store.h, C.addressof(req), n, C.byref(p), C.addressof(res), _sp(stream)))
+        out = [vmap_gicp_result_dict(res[e]) for e in range(n)]
+        if trace > 0:
+            for e in range(n):
+                out[e]["pairs_trace"] = tr[e].copy()
+        return out[0] if single else out
 
     def close(self):
         if getattr(self, "h", None):
@@ -1709,11 +1821,13 @@ class GlobalMapBuilder:
     correspond (docs/VOXEL_MAP.md section 5 states the deviations from the reference).  An error of the library raises
     SlamError here (C++ prints it and rejects the cloud); the scan keyframe is removed on every way out."""
 
-    def __init__(self, leaf=0.30, gate=2.0, carve=False):
+    DIST_LEAF = 1.0     # leaf of the map that direct mode registers against (docs/VOXEL_MAP.md section 9)
+
+    def __init__(self, leaf=0.30, gate=2.0, carve=False, direct=False):
         # global_generate.cpp:21-29, :84-90: macros and setup_gicp's values there, members here.  The store and the map are made
         # with the fixed ones (read-only properties below); MAX_SCORE and CROP_DIST are read at every add_cloud
         self._fixed = dict(LEAF_SIZE=float(leaf), gate=float(gate), MAX_ITERATIONS=100, TRANSFORMATION_EPSILON=1e-6,
-                           FITNESS_EPSILON=1e-6, MAX_DIST=4.0, carve=bool(carve))
+                           FITNESS_EPSILON=1e-6, MAX_DIST=4.0, carve=bool(carve), direct=bool(direct))
         self.MAX_SCORE, self.CROP_DIST = 1.0, 100.0
         # free-space carving (docs/VOXEL_MAP.md section 8): the switch is fixed here, the rest is read at every call
         self.CARVE_NUM, self.CARVE_DEN = 1, 1
@@ -1723,12 +1837,21 @@ class GlobalMapBuilder:
         self.store = KeyframeStore(leaf_size=self.LEAF_SIZE, gate=self.gate, transformation_epsilon=self.TRANSFORMATION_EPSILON,
                                    fitness_epsilon=self.FITNESS_EPSILON)
         self.store.set_gicp_params(max_iterations=self.MAX_ITERATIONS, transformation_epsilon=self.TRANSFORMATION_EPSILON)
+        # direct mode (section 9): a second map of leaf DIST_LEAF with distributions, registered against without extraction;
+        # fixed here like carve.  The carved rule is part of its plane rule when carve is on (CARVE_NUM / CARVE_DEN as they
+        # stand now: the distributions' parameters are fixed with the map)
+        self.dmap = None
+        if self.direct:
+            self.dmap = VoxelMap(leaf=self.DIST_LEAF)
+            self.dmap.enable_distributions(max_miss_num=self.CARVE_NUM if self.carve else 0, max_miss_den=self.CARVE_DEN if self.carve else 0)
         self.trans_full = np.eye(4, dtype=np.float32)
         self.map_id, self.n_clouds, self.n_accepted = -1, 0, 0
         self.last = None        # the last request's result
 
     def close(self):
         self.vmap.close()
+        if self.dmap is not None:
+            self.dmap.close()
         self.store.close()
 
     LEAF_SIZE = property(lambda self: self._fixed["LEAF_SIZE"])
@@ -1738,6 +1861,10 @@ class GlobalMapBuilder:
     FITNESS_EPSILON = property(lambda self: self._fixed["FITNESS_EPSILON"])
     MAX_DIST = property(lambda self: self._fixed["MAX_DIST"])    # kept for the name, without effect: the store's gate rules
     carve = property(lambda self: self._fixed["carve"])
+    direct = property(lambda self: self._fixed["direct"])
+
+    def _maps(self):
+        return (self.vmap,) if self.dmap is None else (self.vmap, self.dmap)
 
     def _max_miss(self):
         return (self.CARVE_NUM, self.CARVE_DEN) if self.carve else None
@@ -1758,41 +1885,52 @@ class GlobalMapBuilder:
         return self.vmap.read(max_miss=self._max_miss())[0]
 
     def add_cloud(self, xyz):
-        """One scan ([n, >= 3] f32, sensor frame): (accepted, result dict of register_gicp or None for the first cloud)."""
+        """One scan ([n, >= 3] f32, sensor frame): (accepted, result dict of register_gicp or None for the first cloud).
+        With `direct` the result is VoxelMap.register_gicp's: its fitness is the point-to-plane score."""
         a = np.ascontiguousarray(xyz, dtype=np.float32)
         a = a.reshape(-1, a.shape[1] if a.ndim == 2 else 3)
         self.n_clouds += 1
         if self.vmap.info()["n_points"] == 0:      # :63-70: the first cloud is the map
-            self.vmap.integrate(a)
+            for m in self._maps():
+                m.integrate(a)
             if self.carve:
                 self.last_carve = self.vmap.carve(a, params=self.carve_params)
+                if self.dmap is not None:
+                    self.dmap.carve(a, params=self.carve_params)
             self.n_accepted += 1
             self.last = None
             return True, None
         d_scan = DeviceArray.from_host(a)
         scan = self.store.add_keyframe_dev(d_scan, len(a), a.shape[1])
         try:
-            lo, hi = self.crop_box()
-            cap = max(self.vmap.info()["n_voxels"], 1)
-            d_map = DeviceArray((cap, 4), np.float32)
-            n_map = self.vmap.extract_dev(d_map, cap, lo=lo, hi=hi, max_miss=self._max_miss())
-            synchronize()
-            if n_map == 0:                         # nothing of the map near the pose: nothing to register against
-                self.last = None
-                return False, None
-            if self.map_id < 0:
-                self.map_id = self.store.add_keyframe_dev(d_map, n_map, 4)
+            if self.direct:                        # section 9: the scan against the plane voxels of the 1 m map, nothing extracted
+                r = self.dmap.register_gicp(self.store, scan, self.trans_full, gate=self.gate, max_iterations=self.MAX_ITERATIONS,
+                                            transformation_epsilon=self.TRANSFORMATION_EPSILON)
             else:
-                self.store.replace_keyframe_dev(self.map_id, d_map, n_map, 4)
-            r = self.store.register_gicp([(self.map_id, scan, self.trans_full)])[0]
+                lo, hi = self.crop_box()
+                cap = max(self.vmap.info()["n_voxels"], 1)
+                d_map = DeviceArray((cap, 4), np.float32)
+                n_map = self.vmap.extract_dev(d_map, cap, lo=lo, hi=hi, max_miss=self._max_miss())
+                synchronize()
+                if n_map == 0:                         # nothing of the map near the pose: nothing to register against
+                    self.last = None
+                    return False, None
+                if self.map_id < 0:
+                    self.map_id = self.store.add_keyframe_dev(d_map, n_map, 4)
+                else:
+                    self.store.replace_keyframe_dev(self.map_id, d_map, n_map, 4)
+                r = self.store.register_gicp([(self.map_id, scan, self.trans_full)])[0]
             self.last = r
             if r["fitness_pairs"] <= 0 or not r["converged"] or r["fitness"] > self.MAX_SCORE:      # :182
                 return False, r
             self.trans_full = np.array(r["transform"], np.float32).reshape(4, 4)
             T = self.trans_full.astype(np.float64)
-            self.vmap.integrate_dev(d_scan, len(a), a.shape[1], R=T[:3, :3], t=T[:3, 3])
+            for m in self._maps():
+                m.integrate_dev(d_scan, len(a), a.shape[1], R=T[:3, :3], t=T[:3, 3])
             if self.carve:
                 self.last_carve = self.vmap.carve_dev(d_scan, len(a), a.shape[1], R=T[:3, :3], t=T[:3, 3], params=self.carve_params)
+                if self.dmap is not None:
+                    self.dmap.carve_dev(d_scan, len(a), a.shape[1], R=T[:3, :3], t=T[:3, 3], params=self.carve_params)
             self.n_accepted += 1
             return True, r
         finally:

@@ -21,6 +21,11 @@
 //              endpoint's voxel (phase 1: seen) and the ray's visited length; a rocprim scan over chunks of 64 steps per ray;
 //              one wavefront per chunk, one lane per step, walks the closed form of the driving-axis Bresenham and charges
 //              `miss` (phase 2).  No key is written: the lookup only finds.
+//   moments    opt-in (docs/VOXEL_MAP.md section 9; the restatement is tests/cpp/vmap_gicp_oracle.cpp): nine i64 planes, the
+//              first and second moments of a voxel's points about the cell's corner in units of 2^-16 m.  A second
+//              integrate kernel adds them with nine more 64-bit integer atomicAdds; after a rehash one more launch moves the
+//              planes by looking every old key up in the new table.  One lane per slot turns them into a centroid, a normal,
+//              a regularised plane covariance and a flag (the distribution planes), which vmap_gicp.hip registers against.
 // The hash is the 64-bit finaliser of MurmurHash3 (fmix64: two multiply-xorshift rounds), masked to the table: neighbouring
 // cells differ in the low bits of one 21-bit field, and fmix64 spreads any one-bit difference over the whole word.
 // The probe loop ends after `capacity` slots and then raises the handle's error word; the host keeps the load at one half
@@ -32,6 +37,8 @@
 #include <rocprim/rocprim.hpp>
 
 #include "device_mem.hpp"
+#include "kf_gicp_math.hpp"
+#include "vmap_dist.hpp"
 
 using namespace slam;
 
@@ -372,8 +379,165 @@ __global__ __launch_bounds__(256) void vmap_write_carve_kernel(Planes P, const u
     if (key_out) key_out[i] = key[i];
 }
 
+// ---------------------------------------------------------------- moments and distributions (docs/VOXEL_MAP.md section 9)
+struct Moments {
+    unsigned long long *E[3], *M[6]; // first moments, then xx xy xz yy yz zz
+};
+struct Dist {
+    float4 *cen; // centroid; w = 1.0f for a plane voxel
+    double *nrm, *cov, *eig;
+};
+struct DistRule {
+    uint32_t min_points, miss_num, miss_den; // miss_den = 0: the carve planes are not asked
+    double   flat_ratio, line_ratio, eps;
+};
+
+// vmap_integrate_kernel with the moments: e = (fx - cell L) >> 4 per axis, |e| <= 2^20 (section 9 has the bound).
+__global__ __launch_bounds__(256) void vmap_integrate_moments_kernel(const float *xyz, int n, int stride, Transform X, double leaf, long long L,
+                                                                     Table T, Moments Q, uint32_t *ctr)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; // n may be close to 2^31
+    if (i >= (size_t)n) return;
+    const float *p = xyz + i * stride;
+    float        q[3] = {p[0], p[1], p[2]};
+    if (X.on) {
+        const double px = q[0], py = q[1], pz = q[2];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            q[k] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(X.r[3 * k], px), __dmul_rn(X.r[3 * k + 1], py)), __dmul_rn(X.r[3 * k + 2], pz)),
+                                    X.t[k]);
+    }
+    uint64_t  key = 0;
+    long long f[3], e[3];
+    bool      keep = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float v = q[k];
+        const double c = floor((double)v / leaf);
+        if (!(fabsf(v) < kCoordLimit) || !(fabs(c) < (double)kCellLimit)) { // written so that a NaN fails both tests
+            keep = false;
+            continue;
+        }
+        key |= (uint64_t)((int)c + kCellLimit) << (21 * k);
+        f[k] = (long long)rint((double)v * kFix);
+        e[k] = (f[k] - (long long)(int)c * L) >> 4; // arithmetic: floor
+    }
+    if (!keep) {
+        atomicAdd(&ctr[kDropped], 1u);
+        return;
+    }
+    const long long h = find_or_claim(T, key, &ctr[kClaimed]);
+    if (h < 0) {
+        atomicExch(&ctr[kError], 1u);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) atomicAdd(&T.sum[k][h], (unsigned long long)f[k]);
+    atomicAdd(&T.count[h], 1u);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) atomicAdd(&Q.E[k][h], (unsigned long long)e[k]);
+    atomicAdd(&Q.M[0][h], (unsigned long long)(e[0] * e[0]));
+    atomicAdd(&Q.M[1][h], (unsigned long long)(e[0] * e[1]));
+    atomicAdd(&Q.M[2][h], (unsigned long long)(e[0] * e[2]));
+    atomicAdd(&Q.M[3][h], (unsigned long long)(e[1] * e[1]));
+    atomicAdd(&Q.M[4][h], (unsigned long long)(e[1] * e[2]));
+    atomicAdd(&Q.M[5][h], (unsigned long long)(e[2] * e[2]));
+}
+
+// After either rehash kernel: every old voxel's extra planes of 8-byte words go to the slot its key has in the new table.
+// The lookup only finds; keys are distinct, so plain stores.
+constexpr int kMaxMoved = 9;
+struct MovedPlanes {
+    const unsigned long long *from[kMaxMoved];
+    unsigned long long       *to[kMaxMoved];
+    int                       n;
+};
+__global__ __launch_bounds__(256) void vmap_move_planes_kernel(Table from, Table to, MovedPlanes P, uint32_t *ctr)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > from.mask) return;
+    const uint64_t key = from.key[i];
+    if (key == kEmpty) return;
+    const long long h = find_slot(to, key);
+    if (h < 0) {
+        atomicExch(&ctr[kError], 1u);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < kMaxMoved; ++k)
+        if (k < P.n) P.to[k][h] = P.from[k][i];
+}
+
+// One lane per slot, sequential f64, every operation rounded on its own (the file is compiled without contraction).
+// `C` is the carve planes of a carved map when the rule asks for them, null pointers otherwise.
+__global__ __launch_bounds__(256) void vmap_distributions_kernel(Table T, Moments Q, Planes C, DistRule R, Dist D)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > T.mask) return;
+    const uint32_t count = T.count[i];
+    float4         cen = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    double         nrm[3] = {0.0, 0.0, 0.0}, cov[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, lam[3] = {0.0, 0.0, 0.0};
+    if (T.key[i] != kEmpty && count > 0) {
+        cen.x = centroid(T.sum[0][i], count), cen.y = centroid(T.sum[1][i], count), cen.z = centroid(T.sum[2][i], count);
+        const double n = (double)count;
+        double       m[3], s[6];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) m[k] = (double)(long long)Q.E[k][i] / n;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s[k] = (double)(long long)Q.M[k][i] / n;
+        const double scale = 1.0 / 4294967296.0; // 2^-32: e is in units of 2^-16 m
+        const double c6[6] = {(s[0] - m[0] * m[0]) * scale, (s[1] - m[0] * m[1]) * scale, (s[2] - m[0] * m[2]) * scale,
+                              (s[3] - m[1] * m[1]) * scale, (s[4] - m[1] * m[2]) * scale, (s[5] - m[2] * m[2]) * scale};
+        double       nn[3];
+        plane_eigen(c6, lam, nn);
+        bool plane = count >= R.min_points && lam[1] >= R.flat_ratio * lam[2] && lam[1] >= R.line_ratio * lam[0];
+        if (plane && R.miss_den > 0 && C.seen) {
+            const uint32_t seen = C.seen[i];
+            plane = (uint64_t)C.miss[i] * R.miss_den <= (uint64_t)(seen > 1u ? seen : 1u) * R.miss_num;
+        }
+        if (plane) {
+            cen.w = 1.0f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) nrm[k] = nn[k];
+            plane_from_normal(nn, R.eps, cov);
+        }
+    }
+    D.cen[i] = cen;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) D.nrm[3 * i + k] = nrm[k], D.eig[3 * i + k] = lam[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) D.cov[6 * i + k] = cov[k];
+}
+
+__global__ __launch_bounds__(256) void vmap_write_moments_kernel(Moments Q, const uint32_t *slot, const uint64_t *key, int n, int64_t *E3, int64_t *M6,
+                                                                 uint64_t *key_out)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)n) return;
+    const uint32_t s = slot[i];
+    for (int k = 0; k < 3; ++k) E3[3 * i + k] = (int64_t)Q.E[k][s];
+    for (int k = 0; k < 6; ++k) M6[6 * i + k] = (int64_t)Q.M[k][s];
+    key_out[i] = key[i];
+}
+
+__global__ __launch_bounds__(256) void vmap_write_dist_kernel(Dist D, const uint32_t *slot, const uint64_t *key, int n, double *nrm3, double *cov6,
+                                                              double *eig3, uint64_t *key_out, float *cen3, uint8_t *flag)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)n) return;
+    const uint32_t s = slot[i];
+    const float4   c = D.cen[s];
+    for (int k = 0; k < 3; ++k) nrm3[3 * i + k] = D.nrm[3 * (size_t)s + k], eig3[3 * i + k] = D.eig[3 * (size_t)s + k];
+    for (int k = 0; k < 6; ++k) cov6[6 * i + k] = D.cov[6 * (size_t)s + k];
+    key_out[i] = key[i];
+    cen3[3 * i] = c.x, cen3[3 * i + 1] = c.y, cen3[3 * i + 2] = c.z;
+    flag[i] = c.w != 0.0f ? 1 : 0;
+}
+
 inline unsigned blocks_for(uint64_t n) { return (unsigned)((n + 255) / 256); }
 constexpr size_t kSlotBytes = sizeof(uint64_t) + 3 * sizeof(long long) + sizeof(uint32_t);
+constexpr size_t kMomentBytes = 9 * sizeof(long long);                  // per slot, the moments' block
+constexpr size_t kDistBytes = sizeof(float4) + 12 * sizeof(double);     // per slot, the distributions' block
 
 } // namespace
 
@@ -389,6 +553,32 @@ struct slam_vmap {
     // cells and visited lengths, their chunk counts and the scan of those
     DevMem   seen, miss, stamp, cctr, rays, chunks, offs;
     uint32_t serial = 1; // of the next carve call: 1 .. 2^31 - 2
+    // distributions (section 9), from slam_vmap_enable_distributions on: the nine moment planes (capacity i64 each) in one
+    // block, the distribution planes (centroid and flag, normal, covariance, eigenvalues) in another, and whether the
+    // latter are behind the former; a registration's tasks, results and trace
+    slam_vmap_dist_params DP{};
+    DevMem                mom, dist, reg_work;
+    bool                  dist_on = false, dist_stale = true;
+
+    static Moments moments(const DevMem &b, int64_t cap)
+    {
+        Moments             Q;
+        unsigned long long *p = b.as<unsigned long long>();
+        for (int k = 0; k < 3; ++k) Q.E[k] = p + (size_t)cap * k;
+        for (int k = 0; k < 6; ++k) Q.M[k] = p + (size_t)cap * (3 + k);
+        return Q;
+    }
+    Moments moments() const { return moments(mom, capacity); }
+    Dist    dists() const
+    {
+        Dist     D;
+        uint8_t *p = dist.as<uint8_t>();
+        D.cen = reinterpret_cast<float4 *>(p);
+        D.nrm = reinterpret_cast<double *>(p + (size_t)capacity * 16);
+        D.cov = D.nrm + (size_t)capacity * 3;
+        D.eig = D.cov + (size_t)capacity * 6;
+        return D;
+    }
 
     bool   carved() const { return stamp.p != nullptr; }
     Planes planes() const { return Planes{seen.as<uint32_t>(), miss.as<uint32_t>(), stamp.as<uint32_t>()}; }
@@ -453,8 +643,27 @@ int make_room(slam_vmap *m, int64_t n, hipStream_t st)
     SLAM_HIP(hipStreamSynchronize(st));
     SLAM_REQUIRE(!h[kError] && (int64_t)h[kClaimed] == m->n_voxels, SLAM_E_HIP, "slam_vmap: the rehash moved %u of %lld voxels (error word %u)",
                  h[kClaimed], (long long)m->n_voxels, h[kError]);
+    DevMem nm, nd; // the moments and distributions of the new table, when the map has them
+    if (m->dist_on) {
+        SLAM_TRY(nm.alloc((size_t)cap * kMomentBytes));
+        SLAM_TRY(nd.alloc((size_t)cap * kDistBytes));
+        SLAM_HIP(hipMemsetAsync(nm.p, 0, (size_t)cap * kMomentBytes, st));
+        SLAM_HIP(hipMemsetAsync(m->ctr.p, 0, kCounters * sizeof(uint32_t), st));
+        MovedPlanes   P{};
+        const Moments qf = m->moments(), qt = slam_vmap::moments(nm, cap);
+        for (int k = 0; k < 3; ++k) P.from[k] = qf.E[k], P.to[k] = qt.E[k];
+        for (int k = 0; k < 6; ++k) P.from[3 + k] = qf.M[k], P.to[3 + k] = qt.M[k];
+        P.n = 9;
+        hipLaunchKernelGGL(vmap_move_planes_kernel, dim3(blocks_for((uint64_t)m->capacity)), dim3(256), 0, st, m->view(), slam_vmap::view(nt, cap), P,
+                           m->ctr.as<uint32_t>());
+        SLAM_HIP(hipGetLastError());
+        SLAM_HIP(hipMemcpyAsync(h, m->ctr.p, kCounters * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SLAM_HIP(hipStreamSynchronize(st));
+        SLAM_REQUIRE(!h[kError], SLAM_E_HIP, "slam_vmap: the rehash lost a voxel's moments");
+    }
     m->table = std::move(nt);
     if (m->carved()) m->seen = std::move(np[0]), m->miss = std::move(np[1]), m->stamp = std::move(np[2]);
+    if (m->dist_on) m->mom = std::move(nm), m->dist = std::move(nd), m->dist_stale = true;
     m->capacity = cap;
     return SLAM_OK;
 }
@@ -583,6 +792,10 @@ int slam_vmap_clear(slam_vmap_t *m, slam_stream_t stream)
     SLAM_HIP(hipMemsetAsync(m->table.as<uint8_t>() + (size_t)m->capacity * 8, 0, (size_t)m->capacity * (kSlotBytes - 8), st));
     if (m->carved())
         for (DevMem *b : {&m->seen, &m->miss, &m->stamp}) SLAM_HIP(hipMemsetAsync(b->p, 0, (size_t)m->capacity * sizeof(uint32_t), st));
+    if (m->dist_on) {
+        SLAM_HIP(hipMemsetAsync(m->mom.p, 0, (size_t)m->capacity * kMomentBytes, st));
+        m->dist_stale = true;
+    }
     m->n_voxels = m->n_points = 0;
     return SLAM_OK;
 }
@@ -605,8 +818,14 @@ int slam_vmap_integrate_dev(slam_vmap_t *m, const float *d_xyz, int n, int strid
     uint32_t *h = static_cast<uint32_t *>(pinned_scratch(kCounters * sizeof(uint32_t)));
     SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
     SLAM_HIP(hipMemsetAsync(m->ctr.p, 0, kCounters * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(vmap_integrate_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, st, d_xyz, n, stride, X, m->P.leaf, m->view(),
-                       m->ctr.as<uint32_t>());
+    if (m->dist_on) {
+        hipLaunchKernelGGL(vmap_integrate_moments_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, st, d_xyz, n, stride, X, m->P.leaf,
+                           (long long)std::rint(m->P.leaf * kFix), m->view(), m->moments(), m->ctr.as<uint32_t>());
+        m->dist_stale = true;
+    } else {
+        hipLaunchKernelGGL(vmap_integrate_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, st, d_xyz, n, stride, X, m->P.leaf, m->view(),
+                           m->ctr.as<uint32_t>());
+    }
     SLAM_HIP(hipGetLastError());
     SLAM_HIP(hipMemcpyAsync(h, m->ctr.p, kCounters * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     SLAM_HIP(hipStreamSynchronize(st));
@@ -686,7 +905,7 @@ int slam_vmap_info(slam_vmap_t *m, int64_t *n_voxels, int64_t *capacity, int64_t
     if (device_bytes)
         *device_bytes = m->table.cap + m->ctr.cap + m->flag.cap + m->sel.cap + m->keys_in.cap + m->keys_out.cap + m->sel_sorted.cap + m->tmp.cap +
                         m->stage_in.cap + m->stage_out.cap + m->seen.cap + m->miss.cap + m->stamp.cap + m->cctr.cap + m->rays.cap + m->chunks.cap +
-                        m->offs.cap;
+                        m->offs.cap + m->mom.cap + m->dist.cap + m->reg_work.cap;
     return SLAM_OK;
 }
 
@@ -765,6 +984,7 @@ int slam_vmap_carve_dev(slam_vmap_t *m, const float *d_xyz, int n, int stride, c
         m->serial = 1;
     }
     A.tag = 2u * m->serial++;
+    m->dist_stale = true; // the carved rule may be part of the plane rule
     SLAM_TRY(reserve_quarter(m->rays, (size_t)n * sizeof(int4)));
     SLAM_TRY(reserve_quarter(m->chunks, ((size_t)n + 1) * sizeof(uint32_t)));
     SLAM_TRY(reserve_quarter(m->offs, ((size_t)n + 1) * sizeof(uint32_t)));
@@ -875,4 +1095,132 @@ int slam_vmap_read_carve(slam_vmap_t *m, uint32_t *seen, uint32_t *miss, uint64_
     return SLAM_OK;
 }
 
+// ---------------------------------------------------------------- moments and distributions (docs/VOXEL_MAP.md section 9)
+void slam_vmap_default_dist_params(slam_vmap_dist_params *p)
+{
+    if (!p) return;
+    p->min_points = 6;
+    p->flat_ratio = 4.0, p->line_ratio = 0.01;
+    p->epsilon = 1e-3; // slam_kf_gicp_params.gicp_epsilon's
+    p->max_miss_num = 0, p->max_miss_den = 0;
+}
+
+int slam_vmap_enable_distributions(slam_vmap_t *m, const slam_vmap_dist_params *params)
+{
+    slam_vmap_dist_params p;
+    slam_vmap_default_dist_params(&p);
+    if (params) p = *params;
+    SLAM_REQUIRE(p.min_points >= 1 && p.flat_ratio >= 0 && p.line_ratio >= 0 && p.epsilon > 0 && p.max_miss_num >= 0 && p.max_miss_den >= 0,
+                 SLAM_E_INVALID, "slam_vmap_enable_distributions: min_points >= 1, ratios >= 0, epsilon > 0, max_miss_num and max_miss_den >= 0");
+    SLAM_TRY(require_device());
+    SLAM_REQUIRE(m, SLAM_E_INVALID, "slam_vmap_enable_distributions: map is NULL");
+    SLAM_REQUIRE(m->n_voxels == 0, SLAM_E_INVALID, "slam_vmap_enable_distributions: the map holds %lld voxels: legal only after create or clear",
+                 (long long)m->n_voxels);
+    SLAM_REQUIRE(m->P.leaf <= 8.0, SLAM_E_INVALID, "slam_vmap_enable_distributions: leaf %g is more than the 8 m the moments' bound allows", m->P.leaf);
+    if (!m->dist_on) {
+        SLAM_TRY(m->mom.alloc((size_t)m->capacity * kMomentBytes));
+        SLAM_TRY(m->dist.alloc((size_t)m->capacity * kDistBytes));
+    }
+    SLAM_HIP(hipMemsetAsync(m->mom.p, 0, (size_t)m->capacity * kMomentBytes, nullptr));
+    SLAM_HIP(hipStreamSynchronize(nullptr));
+    m->DP = p;
+    m->dist_on = true, m->dist_stale = true;
+    return SLAM_OK;
+}
+
+int slam_vmap_compute_distributions(slam_vmap_t *m, slam_stream_t stream)
+{
+    SLAM_TRY(require_device());
+    SLAM_REQUIRE(m && m->dist_on, SLAM_E_INVALID, "slam_vmap_compute_distributions: a map with distributions enabled");
+    if (!m->dist_stale) return SLAM_OK;
+    DistRule R;
+    R.min_points = (uint32_t)m->DP.min_points, R.miss_num = (uint32_t)m->DP.max_miss_num, R.miss_den = (uint32_t)m->DP.max_miss_den;
+    R.flat_ratio = m->DP.flat_ratio, R.line_ratio = m->DP.line_ratio, R.eps = m->DP.epsilon;
+    const Planes C = m->carved() ? m->planes() : Planes{nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(vmap_distributions_kernel, dim3(blocks_for((uint64_t)m->capacity)), dim3(256), 0, as_stream(stream), m->view(), m->moments(), C, R,
+                       m->dists());
+    SLAM_HIP(hipGetLastError());
+    m->dist_stale = false;
+    return SLAM_OK;
+}
+
+// every occupied voxel's slot in key order into m->sel_sorted (keys into m->keys_out) on the null stream; *n their number
+static int all_slots_sorted(const char *who, slam_vmap *m, int cap, int *n_out, int64_t *n)
+{
+    SLAM_TRY(select_slots(m, nullptr, nullptr, 0, nullptr, n));
+    *n_out = (int)*n;
+    SLAM_REQUIRE(*n <= cap, SLAM_E_NOMEM, "%s: %lld voxels, room for %d", who, (long long)*n, cap);
+    if (*n) SLAM_TRY(sort_slots(m, (int)*n, nullptr));
+    return SLAM_OK;
+}
+
+int slam_vmap_read_moments(slam_vmap_t *m, int64_t *E3, int64_t *M6, uint64_t *key, int cap, int *n_out)
+{
+    SLAM_REQUIRE(n_out && cap >= 0, SLAM_E_INVALID, "slam_vmap_read_moments: n_out and cap >= 0");
+    SLAM_TRY(require_device());
+    SLAM_REQUIRE(m && m->dist_on, SLAM_E_INVALID, "slam_vmap_read_moments: a map with distributions enabled");
+    int64_t n = 0;
+    SLAM_TRY(all_slots_sorted("slam_vmap_read_moments", m, cap, n_out, &n));
+    if (n == 0) return SLAM_OK;
+    const size_t N = (size_t)n;
+    SLAM_TRY(reserve_quarter(m->stage_out, N * 80)); // keys, E, M
+    uint64_t *d_key = m->stage_out.as<uint64_t>();
+    int64_t  *d_E = reinterpret_cast<int64_t *>(d_key + N), *d_M = d_E + 3 * N;
+    hipLaunchKernelGGL(vmap_write_moments_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, nullptr, m->moments(), m->sel_sorted.as<uint32_t>(),
+                       m->keys_out.as<uint64_t>(), (int)n, d_E, d_M, d_key);
+    SLAM_HIP(hipGetLastError());
+    if (E3) SLAM_HIP(hipMemcpy(E3, d_E, N * 24, hipMemcpyDeviceToHost));
+    if (M6) SLAM_HIP(hipMemcpy(M6, d_M, N * 48, hipMemcpyDeviceToHost));
+    if (key) SLAM_HIP(hipMemcpy(key, d_key, N * 8, hipMemcpyDeviceToHost));
+    SLAM_HIP(hipStreamSynchronize(nullptr));
+    return SLAM_OK;
+}
+
+int slam_vmap_read_distributions(slam_vmap_t *m, float *centroid3, double *normal3, double *cov6, double *eig3, uint8_t *flag, uint64_t *key, int cap,
+                                 int *n_out)
+{
+    SLAM_REQUIRE(n_out && cap >= 0, SLAM_E_INVALID, "slam_vmap_read_distributions: n_out and cap >= 0");
+    SLAM_TRY(require_device());
+    SLAM_REQUIRE(m && m->dist_on, SLAM_E_INVALID, "slam_vmap_read_distributions: a map with distributions enabled");
+    SLAM_TRY(slam_vmap_compute_distributions(m, nullptr));
+    int64_t n = 0;
+    SLAM_TRY(all_slots_sorted("slam_vmap_read_distributions", m, cap, n_out, &n));
+    if (n == 0) return SLAM_OK;
+    const size_t N = (size_t)n;
+    SLAM_TRY(reserve_quarter(m->stage_out, N * 120)); // normals, covariances, eigenvalues, keys, then centroids, then flags
+    double   *d_nrm = m->stage_out.as<double>(), *d_cov = d_nrm + 3 * N, *d_eig = d_cov + 6 * N;
+    uint64_t *d_key = reinterpret_cast<uint64_t *>(d_eig + 3 * N);
+    float    *d_cen = reinterpret_cast<float *>(d_key + N);
+    uint8_t  *d_flag = reinterpret_cast<uint8_t *>(d_cen + 3 * N);
+    hipLaunchKernelGGL(vmap_write_dist_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, nullptr, m->dists(), m->sel_sorted.as<uint32_t>(),
+                       m->keys_out.as<uint64_t>(), (int)n, d_nrm, d_cov, d_eig, d_key, d_cen, d_flag);
+    SLAM_HIP(hipGetLastError());
+    if (centroid3) SLAM_HIP(hipMemcpy(centroid3, d_cen, N * 12, hipMemcpyDeviceToHost));
+    if (normal3) SLAM_HIP(hipMemcpy(normal3, d_nrm, N * 24, hipMemcpyDeviceToHost));
+    if (cov6) SLAM_HIP(hipMemcpy(cov6, d_cov, N * 48, hipMemcpyDeviceToHost));
+    if (eig3) SLAM_HIP(hipMemcpy(eig3, d_eig, N * 24, hipMemcpyDeviceToHost));
+    if (flag) SLAM_HIP(hipMemcpy(flag, d_flag, N, hipMemcpyDeviceToHost));
+    if (key) SLAM_HIP(hipMemcpy(key, d_key, N * 8, hipMemcpyDeviceToHost));
+    SLAM_HIP(hipStreamSynchronize(nullptr));
+    return SLAM_OK;
+}
+
 } // extern "C"
+
+// ---------------------------------------------------------------- what vmap_gicp.hip sees of the handle (vmap_dist.hpp)
+namespace slam {
+
+int vmap_dist_view(slam_vmap *m, hipStream_t st, VmapDistView *out)
+{
+    SLAM_REQUIRE(m && m->dist_on, SLAM_E_INVALID, "slam_vmap_register_gicp: distributions were never enabled on this map");
+    SLAM_TRY(slam_vmap_compute_distributions(m, reinterpret_cast<slam_stream_t>(st)));
+    const Dist D = m->dists();
+    out->key = m->view().key, out->mask = (uint64_t)m->capacity - 1;
+    out->cen = D.cen, out->nrm = D.nrm, out->cov = D.cov;
+    out->leaf = m->P.leaf;
+    return SLAM_OK;
+}
+
+DevMem &vmap_register_work(slam_vmap *m) { return m->reg_work; }
+
+} // namespace slam
