@@ -21,6 +21,12 @@
 // point-to-plane score.  map() stays the LEAF_SIZE map.  With carve on as well the second map is carved too and the carved
 // rule at CARVE_NUM / CARVE_DEN (as they stand at construction) is part of its plane rule.  While it is false nothing here
 // calls an entry point of section 9.
+// save(prefix) / resume(prefix) (docs/VOXEL_MAP.md section 10.5): the builder's state as prefix.vmap (slam_vmap_save of the
+// map), prefix.dmap (the second map, with `direct`) and prefix.pose (trans_full as 16 little-endian floats, then n_clouds and
+// n_accepted as int32).  resume is legal only before the first addCloud and only when the files' leaves, carve state and
+// distribution parameters are this builder's; it loads with slam_vmap_load and the loaded handles take the place of the
+// builder's own empty ones.  A refusal is printed and returns false with nothing changed (Python raises SlamError).  While
+// neither is called nothing of section 10 is called.
 //
 // Stated deviations (docs/VOXEL_MAP.md section 5):
 //   * the start is passed to the solver as `init` instead of moving the source first (:144), so the solver's result is
@@ -32,6 +38,8 @@
 //   * the source is not cropped (:160-168): a scan reaches 100 m at most, so the crop around the pose keeps all of it.
 #pragma once
 #include <cstdio>
+#include <cstring>
+#include <string>
 #include <vector>
 
 #include "slam_amd/buffer.hpp"
@@ -164,7 +172,70 @@ public:
         return out;
     }
 
+    // prefix.vmap, prefix.dmap with `direct`, prefix.pose: the same bytes as the Python twin writes
+    bool save(const std::string &prefix)
+    {
+        if (!ok()) return false;
+        if (slam_vmap_save(vmap_, (prefix + ".vmap").c_str()) != SLAM_OK) return warn(), false;
+        if (direct && slam_vmap_save(dmap_, (prefix + ".dmap").c_str()) != SLAM_OK) return warn(), false;
+        unsigned char pose[72]; // little-endian hosts only, as the library
+        const int32_t n[2] = {n_clouds, n_accepted};
+        std::memcpy(pose, trans_full, 64), std::memcpy(pose + 64, n, 8);
+        std::FILE *f = std::fopen((prefix + ".pose").c_str(), "wb");
+        const bool written = f && std::fwrite(pose, 1, sizeof pose, f) == sizeof pose;
+        if ((f && std::fclose(f) != 0) || !written) return refuse(prefix, ".pose cannot be written");
+        return true;
+    }
+    bool resume(const std::string &prefix)
+    {
+        if (!ok()) return false;
+        if (n_clouds != 0) return refuse(prefix, ": resume is legal only on a builder that has added no cloud");
+        if (!direct) {
+            if (std::FILE *f = std::fopen((prefix + ".dmap").c_str(), "rb")) {
+                std::fclose(f);
+                return refuse(prefix, ".dmap exists: saved by a direct builder, this one is not");
+            }
+        }
+        unsigned char pose[73];
+        std::FILE    *f = std::fopen((prefix + ".pose").c_str(), "rb");
+        const size_t  got = f ? std::fread(pose, 1, sizeof pose, f) : 0;
+        if (f) std::fclose(f);
+        if (got != 72) return refuse(prefix, ".pose cannot be read or does not hold 72 bytes");
+        slam_vmap_t *loaded[2] = {nullptr, nullptr};
+        bool         good = slam_vmap_load((prefix + ".vmap").c_str(), &loaded[0]) == SLAM_OK && sameLayout(loaded[0], vmap_);
+        if (good && direct) good = slam_vmap_load((prefix + ".dmap").c_str(), &loaded[1]) == SLAM_OK && sameLayout(loaded[1], dmap_);
+        if (!good) {
+            slam_vmap_destroy(loaded[0]);
+            slam_vmap_destroy(loaded[1]);
+            return refuse(prefix, ": a file cannot be loaded, or was saved with another leaf, carve state or distribution parameters");
+        }
+        slam_vmap_destroy(vmap_);
+        vmap_ = loaded[0];
+        if (direct) slam_vmap_destroy(dmap_), dmap_ = loaded[1];
+        int32_t n[2];
+        std::memcpy(trans_full, pose, 64), std::memcpy(n, pose + 64, 8);
+        n_clouds = n[0], n_accepted = n[1];
+        return true;
+    }
+
 private:
+    // a loaded map against the builder's own empty one: the leaf's bits, the carve state of construction, the distributions
+    bool sameLayout(slam_vmap_t *file, slam_vmap_t *own) const
+    {
+        double                leaf[2];
+        int                   carved[2], dist[2];
+        slam_vmap_dist_params a, b;
+        if (slam_vmap_layout(file, &leaf[0], &carved[0], &dist[0], &a) != SLAM_OK || slam_vmap_layout(own, &leaf[1], &carved[1], &dist[1], &b) != SLAM_OK)
+            return warn(), false;
+        const bool same_dp = a.min_points == b.min_points && a.flat_ratio == b.flat_ratio && a.line_ratio == b.line_ratio && a.epsilon == b.epsilon &&
+                             a.max_miss_num == b.max_miss_num && a.max_miss_den == b.max_miss_den;
+        return std::memcmp(&leaf[0], &leaf[1], sizeof(double)) == 0 && (carved[0] != 0) == carve && dist[0] == dist[1] && same_dp;
+    }
+    static bool refuse(const std::string &prefix, const char *why)
+    {
+        std::fprintf(stderr, "GlobalMapBuilder: %s%s\n", prefix.c_str(), why);
+        return false;
+    }
     // direct mode: the scan against the plane voxels of the DIST_LEAF map; fills last_direct and the verdict of :182
     bool registerDirect(int scan)
     {

@@ -44,6 +44,7 @@ extern "C" {
 #define SLAM_E_UNSUPPORTED           -7
 #define SLAM_E_TIMEOUT               -8 /* slam_mi355x_rccl.h: a merge's united range did not arrive: another rank has stopped */
 #define SLAM_E_COMM                  -9 /* slam_mi355x_rccl.h: the communicator (or the host transport) reports a failure */
+#define SLAM_E_IO                    -10 /* a file could not be opened, read or written: slam_last_error() has the system's message */
 
 typedef void *slam_stream_t; /* a hipStream_t; NULL = the default stream */
 typedef void *slam_event_t;  /* a hipEvent_t */
@@ -942,7 +943,7 @@ int  slam_vmap_extract_dev(slam_vmap_t *m, const float lo_xy[2], const float hi_
 /* The same into host arrays (each nullable), synchronous. */
 int  slam_vmap_read(slam_vmap_t *m, const float lo_xy[2], const float hi_xy[2], int min_count, float *xyz4, uint32_t *count,
                     uint64_t *key, int cap, int *n_out);
-/* The accumulators themselves, for tests and for saving a map: every occupied voxel in ascending key order, sums[3 i ..] =
+/* The accumulators themselves, for tests and for saving a map (slam_vmap_save does): every occupied voxel in ascending key order, sums[3 i ..] =
  * the three int64 sums in units of 2^-20 m.  Host arrays, each nullable; synchronous; `cap` and *n_out as above. */
 int  slam_vmap_read_sums(slam_vmap_t *m, int64_t *sums, uint32_t *count, uint64_t *key, int cap, int *n_out);
 /* occupied voxels, slots of the table, points integrated (dropped ones not counted), bytes of device memory held */
@@ -1072,6 +1073,47 @@ int  slam_vmap_register_gicp(slam_vmap_t *m, slam_kf_t *store, const slam_vmap_g
 int  slam_vmap_register_gicp_traced(slam_vmap_t *m, slam_kf_t *store, const slam_vmap_gicp_req *req, int n,
                                     const slam_vmap_gicp_params *params, slam_vmap_gicp_result *out, int32_t *pairs_trace,
                                     int trace_cap, slam_stream_t stream);
+
+/* Snapshots and merging by the integer accumulators (docs/VOXEL_MAP.md section 10).  A voxel record is what the key-ordered
+ * readers return: key (section 1's packing), count >= 1, sums[3], optionally seen and miss (slam_vmap_read_carve), optionally
+ * E[3] and M[6] (slam_vmap_read_moments).  ABSORB adds records into a map by key: find or claim the key's slot as integrate
+ * does, then integer atomic adds of count and sums and, where the planes exist, of seen, miss, E and M.  Keys may repeat
+ * within a call and across calls: repeats add.  A record is rejected, counted in *n_rejected and nothing is written for it
+ * when its key is all ones, has bit 63 set or a 21-bit field above 2^21 - 2, or its count is 0; the call still returns SLAM_OK.
+ * n_voxels grows by the slots claimed, n_points by the counts accepted, the distributions become stale.  Two maps of equal leaf
+ * built from disjoint sets of (cloud, transform) pairs therefore absorb, in any order, into the bits of the map one handle
+ * would have built from all pairs.  seen and miss add as well; that sum is a joint carve's only for voxels every contributing
+ * map held when each carve ran (section 10.1).  Section 1's limits hold for the totals and are not checked.
+ * Moments travel exactly: records with E / M into a map without distributions, or without into a map with them, is
+ * SLAM_E_INVALID and nothing is launched.  seen / miss offered to a map never carved allocates the carve planes as a first
+ * carve does; records without them add nothing to a carved map's planes. */
+/* leaf, whether the carve planes exist, whether distributions are enabled and their parameters (zeros when not): each
+ * output nullable, no wait. */
+int  slam_vmap_layout(slam_vmap_t *m, double *leaf, int *carved, int *distributions, slam_vmap_dist_params *dp);
+/* n records on the device: d_sums[3 i + k], d_E3[3 i + k], d_M6[6 i + k]; d_seen / d_miss both or neither, d_E3 / d_M6
+ * likewise.  SLAM_E_INVALID before any launch for n < 0, a null key / count / sums with n > 0, half a pair, or the moment
+ * mismatch above; n == 0 is SLAM_OK and touches nothing.  Room is made by integrate's load rule with n the number of records,
+ * before the launch.  WAITS ONCE for `stream`, for the counters; a growing call waits as a growing integrate does.  One call
+ * at a time per handle.  The host form stages the arrays as slam_vmap_integrate does and is synchronous. */
+int  slam_vmap_absorb_dev(slam_vmap_t *m, const uint64_t *d_key, const uint32_t *d_count, const int64_t *d_sums, const uint32_t *d_seen,
+                          const uint32_t *d_miss, const int64_t *d_E3, const int64_t *d_M6, int n, int64_t *n_rejected, slam_stream_t stream);
+int  slam_vmap_absorb(slam_vmap_t *m, const uint64_t *key, const uint32_t *count, const int64_t *sums, const uint32_t *seen,
+                      const uint32_t *miss, const int64_t *E3, const int64_t *M6, int n, int64_t *n_rejected);
+/* Absorbs every occupied slot of `src` straight from its table (one lane per slot, no extraction, no sort); src's carve planes
+ * travel when it has them; src is unchanged.  SLAM_E_INVALID before any launch for dst == src, leaves whose doubles differ in
+ * any bit, or distributions on one side only.  Waits as slam_vmap_absorb_dev with n = src's n_voxels; both handles are busy
+ * for the call. */
+int  slam_vmap_merge(slam_vmap_t *dst, slam_vmap_t *src, int64_t *n_rejected, slam_stream_t stream);
+/* The map into the file of section 10.4 (96-byte header, then keys, counts, sums, seen and miss of a carved map, E and M of
+ * a map with distributions, all in ascending key order, little-endian, no checksum) through slam_vmap_read_sums,
+ * slam_vmap_read_carve and slam_vmap_read_moments.  Synchronous.  The bytes depend on the map's contents only, not on how it
+ * was built.  SLAM_E_IO when the file cannot be written; SLAM_E_INVALID for a map the format cannot hold (more than 2^30
+ * voxels, a cell of 2^20 - 1). */
+int  slam_vmap_save(slam_vmap_t *m, const char *path);
+/* Parses and validates the whole file on the host (SLAM_E_IO: unreadable; SLAM_E_INVALID: malformed, on a machine without a
+ * device as well), then asks for the device, creates a map of the file's leaf with room for its voxels at half load, enables
+ * distributions with the file's parameters when it has moments, and absorbs the records in one call. */
+int  slam_vmap_load(const char *path, slam_vmap_t **out);
 
 /* -------------------------------------------------------------------------
  * Pose-graph optimiser: graph_slam's optimizeGraph (graph_slam.cpp:322-390), i.e. g2o's VertexSE3 / EdgeSE3 under

@@ -17,8 +17,8 @@ LIB_PATH = os.path.join(HERE, "lib", "libslam_mi355x_measure.so" if os.environ.g
 RCCL_LIB_PATH = os.path.join(HERE, "lib", "libslam_mi355x_rccl.so")
 
 SLAM_OK = 0
-E_INVALID, E_NO_DEVICE, E_HIP, E_TOO_FEW_MODEL, E_TOO_FEW_SCENE, E_NOMEM, E_UNSUPPORTED, E_TIMEOUT, E_COMM = \
-    -1, -2, -3, -4, -5, -6, -7, -8, -9
+E_INVALID, E_NO_DEVICE, E_HIP, E_TOO_FEW_MODEL, E_TOO_FEW_SCENE, E_NOMEM, E_UNSUPPORTED, E_TIMEOUT, E_COMM, E_IO = \
+    -1, -2, -3, -4, -5, -6, -7, -8, -9, -10
 ICP_P2P, ICP_P2L = 0, 1
 RAYCAST_TILED, RAYCAST_GLOBAL, RAYCAST_TILED_MERGE = 0, 1, 2
 
@@ -239,6 +239,7 @@ EXPORTS = [
     "slam_vmap_read_carve",
     "slam_vmap_default_dist_params", "slam_vmap_enable_distributions", "slam_vmap_read_moments", "slam_vmap_compute_distributions",
     "slam_vmap_read_distributions", "slam_vmap_default_gicp_params", "slam_vmap_register_gicp", "slam_vmap_register_gicp_traced",
+    "slam_vmap_layout", "slam_vmap_absorb_dev", "slam_vmap_absorb", "slam_vmap_merge", "slam_vmap_save", "slam_vmap_load",
     "slam_pgo_default_params", "slam_pgo_create", "slam_pgo_destroy", "slam_pgo_clear", "slam_pgo_add_vertex",
     "slam_pgo_set_vertex", "slam_pgo_add_edge", "slam_pgo_size", "slam_pgo_optimize", "slam_pgo_read_vertices", "slam_pgo_chi2",
     "slam_pgo_read_system", "slam_pgo_step",
@@ -490,6 +491,12 @@ def lib():
     L.slam_vmap_default_gicp_params.restype = None
     L.slam_vmap_register_gicp.argtypes = [_vp, _vp, _vp, C.c_int, C.POINTER(VmapGicpParams), _vp, _vp]
     L.slam_vmap_register_gicp_traced.argtypes = [_vp, _vp, _vp, C.c_int, C.POINTER(VmapGicpParams), _vp, _vp, C.c_int, _vp]
+    L.slam_vmap_layout.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(VmapDistParams)]
+    L.slam_vmap_absorb_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int64), _vp]
+    L.slam_vmap_absorb.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int64)]
+    L.slam_vmap_merge.argtypes = [_vp, _vp, C.POINTER(C.c_int64), _vp]
+    L.slam_vmap_save.argtypes = [_vp, C.c_char_p]
+    L.slam_vmap_load.argtypes = [C.c_char_p, C.POINTER(_vp)]
     _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
     L.slam_pgo_default_params.argtypes = [C.POINTER(PgoParams)]
     L.slam_pgo_default_params.restype = None
@@ -1348,6 +1355,60 @@ class VoxelMap:
                 out[e]["pairs_trace"] = tr[e].copy()
         return out[0] if single else out
 
+    # ---- snapshots and merging by the integer accumulators (docs/VOXEL_MAP.md section 10)
+    def layout(self):
+        """slam_vmap_layout: what a snapshot needs and info() does not tell: a dict of leaf, carved, distributions and
+        dist_params (a VmapDistParams; the defaults' zeros of a map without distributions)."""
+        leaf, carved, dist, dp = C.c_double(), C.c_int(), C.c_int(), VmapDistParams()
+        check(lib().slam_vmap_layout(self.h, C.byref(leaf), C.byref(carved), C.byref(dist), C.byref(dp)))
+        return dict(leaf=leaf.value, carved=bool(carved.value), distributions=bool(dist.value), dist_params=dp)
+
+    def absorb(self, key, count, sums, seen=None, miss=None, E3=None, M6=None):
+        """slam_vmap_absorb: adds n voxel records (key [n] u64, count [n] u32, sums [n, 3] i64, optionally seen and miss [n] u32,
+        optionally E3 [n, 3] and M6 [n, 6] i64: what read_sums, read_carve and read_moments return) into the map by key.
+        The number of records rejected."""
+        key = np.ascontiguousarray(key, dtype=np.uint64).reshape(-1)
+        n = len(key)
+
+        def arr(a, dt, w):
+            return None if a is None else np.ascontiguousarray(a, dtype=dt).reshape(n * w)
+        a = [key, arr(count, np.uint32, 1), arr(sums, np.int64, 3), arr(seen, np.uint32, 1), arr(miss, np.uint32, 1),
+             arr(E3, np.int64, 3), arr(M6, np.int64, 6)]
+        rej = C.c_int64()
+        check(lib().slam_vmap_absorb(self.h, *[_ptr(x) for x in a], n, C.byref(rej)))
+        return rej.value
+
+    def absorb_dev(self, d_key, d_count, d_sums, n, d_seen=None, d_miss=None, d_E3=None, d_M6=None, stream=None):
+        """slam_vmap_absorb_dev: as absorb, on device arrays of n records."""
+        rej = C.c_int64()
+        check(lib().slam_vmap_absorb_dev(self.h, *[getattr(x, "ptr", x) for x in (d_key, d_count, d_sums, d_seen, d_miss, d_E3, d_M6)],
+                                         int(n), C.byref(rej), _sp(stream)))
+        return rej.value
+
+    def merge(self, other, stream=None):
+        """slam_vmap_merge: every voxel of `other` (same leaf, distributions on both or neither) added into this map straight
+        from its table; `other` is unchanged.  The number of records rejected (0 for a sound source)."""
+        rej = C.c_int64()
+        check(lib().slam_vmap_merge(self.h, other.h, C.byref(rej), _sp(stream)))
+        return rej.value
+
+    def save(self, path):
+        """slam_vmap_save: the map's accumulators into the file of section 10.4; the bytes depend on the contents alone."""
+        check(lib().slam_vmap_save(self.h, os.fsencode(path)))
+
+    @classmethod
+    def load(cls, path):
+        """slam_vmap_load: a new map from a file of section 10.4 (SlamError E_INVALID: malformed, E_IO: unreadable)."""
+        h = _vp()
+        check(lib().slam_vmap_load(os.fsencode(path), C.byref(h)))
+        m = cls.__new__(cls)
+        m.h = h.value
+        lay = m.layout()
+        m.params = VmapParams(leaf=lay["leaf"], initial_capacity=m.info()["capacity"])
+        if lay["distributions"]:
+            m.dist_params = lay["dist_params"]
+        return m
+
     def close(self):
         if getattr(self, "h", None):
             lib().slam_vmap_destroy(self.h)
@@ -1883,6 +1944,57 @@ class GlobalMapBuilder:
         """The whole map as GlobalMatcher.set_map takes it: [n, 4] f32 (x, y, z, 0) in key order (the carved extraction
         when carve is on)."""
         return self.vmap.read(max_miss=self._max_miss())[0]
+
+    def save(self, prefix):
+        """The builder's state into prefix.vmap (the map), prefix.dmap (the second map, with `direct`) and prefix.pose
+        (trans_full as 16 little-endian floats, then n_clouds and n_accepted as i32): docs/VOXEL_MAP.md section 10.5."""
+        prefix = os.fspath(prefix)
+        self.vmap.save(prefix + ".vmap")
+        if self.dmap is not None:
+            self.dmap.save(prefix + ".dmap")
+        with open(prefix + ".pose", "wb") as f:
+            f.write(np.ascontiguousarray(self.trans_full, dtype="<f4").tobytes())
+            f.write(np.array([self.n_clouds, self.n_accepted], "<i4").tobytes())
+
+    def resume(self, prefix):
+        """Takes up what save(prefix) left: legal only before the first add_cloud, and only when the files' leaves, carve
+        state and distribution parameters are those of this builder's construction (SlamError otherwise, nothing changed).
+        The maps are loaded by slam_vmap_load and take the place of the builder's own empty ones."""
+        prefix = os.fspath(prefix)
+        if self.n_clouds != 0:
+            raise SlamError(E_INVALID, "GlobalMapBuilder.resume: legal only on a builder that has added no cloud")
+        if not self.direct and os.path.exists(prefix + ".dmap"):
+            raise SlamError(E_INVALID, "GlobalMapBuilder.resume: %s.dmap exists: saved by a direct builder, this one is not" % prefix)
+        try:
+            pose = open(prefix + ".pose", "rb").read()
+        except OSError as e:
+            raise SlamError(E_IO, "GlobalMapBuilder.resume: %s" % e)
+        if len(pose) != 72:
+            raise SlamError(E_INVALID, "GlobalMapBuilder.resume: %s.pose holds %d bytes, not 72" % (prefix, len(pose)))
+        loaded = []
+        try:
+            for ext, own in ((".vmap", self.vmap), (".dmap", self.dmap)):
+                if own is None:
+                    continue
+                m = VoxelMap.load(prefix + ext)
+                loaded.append(m)
+                a, b = m.layout(), own.layout()
+                same = (np.float64(a["leaf"]).tobytes() == np.float64(b["leaf"]).tobytes() and a["carved"] == self.carve
+                        and a["distributions"] == b["distributions"]
+                        and all(getattr(a["dist_params"], f) == getattr(b["dist_params"], f) for f, _ in VmapDistParams._fields_))
+                if not same:
+                    raise SlamError(E_INVALID, "GlobalMapBuilder.resume: %s%s was saved with another leaf, carve state or "
+                                               "distribution parameters than this builder has" % (prefix, ext))
+        except SlamError:
+            for m in loaded:
+                m.close()
+            raise
+        for m in self._maps():
+            m.close()
+        self.vmap = loaded[0]
+        self.dmap = loaded[1] if self.direct else None
+        self.trans_full = np.frombuffer(pose[:64], "<f4").astype(np.float32).reshape(4, 4).copy()
+        self.n_clouds, self.n_accepted = (int(v) for v in np.frombuffer(pose[64:], "<i4"))
 
     def add_cloud(self, xyz):
         """One scan ([n, >= 3] f32, sensor frame): (accepted, result dict of register_gicp or None for the first cloud).

@@ -26,6 +26,10 @@
 //              integrate kernel adds them with nine more 64-bit integer atomicAdds; after a rehash one more launch moves the
 //              planes by looking every old key up in the new table.  One lane per slot turns them into a centroid, a normal,
 //              a regularised plane covariance and a flag (the distribution planes), which vmap_gicp.hip registers against.
+//   absorb     (docs/VOXEL_MAP.md section 10) one lane per voxel record (key, count, sums, optionally seen and miss, optionally
+//              the nine moments): validate, find or claim as integrate does, integer atomicAdds.  The records are packed
+//              arrays (a file, a caller) or another table's planes (merge: one lane per source slot, empty slots leave at
+//              once); one body serves both.  Load is this fed from vmap_file.hpp's parser, merge from another handle.
 // The hash is the 64-bit finaliser of MurmurHash3 (fmix64: two multiply-xorshift rounds), masked to the table: neighbouring
 // cells differ in the low bits of one 21-bit field, and fmix64 spreads any one-bit difference over the whole word.
 // The probe loop ends after `capacity` slots and then raises the handle's error word; the host keeps the load at one half
@@ -39,6 +43,7 @@
 #include "device_mem.hpp"
 #include "kf_gicp_math.hpp"
 #include "vmap_dist.hpp"
+#include "vmap_file.hpp"
 
 using namespace slam;
 
@@ -66,6 +71,9 @@ struct Box {
 };
 // the handle's counters on the device
 enum { kClaimed = 0, kDropped = 1, kError = 2, kSelected = 3, kCounters = 4 };
+// absorb's block of its own, allocated at the first absorb as carve's is (the handle's block stays four words): the first
+// three as above (kDropped counts the rejected records), then the points accepted as one u64
+enum { kPoints = 4, kAbsorbCounters = 6 };
 
 __device__ __forceinline__ uint64_t fmix64(uint64_t k)
 {
@@ -534,6 +542,62 @@ __global__ __launch_bounds__(256) void vmap_write_dist_kernel(Dist D, const uint
     flag[i] = c.w != 0.0f ? 1 : 0;
 }
 
+// ---------------------------------------------------------------- absorb (docs/VOXEL_MAP.md section 10)
+// Where a call's voxel records lie.  Packed arrays: sum[k] = sums + k with w3 = 3, E[k] = E3 + k with w3 = 3, M[k] = M6 + k
+// with w6 = 6.  Another table's planes: its own pointers with w3 = w6 = 1 and `slots` set, which makes an empty key a slot
+// to pass over instead of a record to reject.  seen / miss and E / M are null where the records have none.
+struct Records {
+    const uint64_t           *key;
+    const uint32_t           *count, *seen, *miss;
+    const unsigned long long *sum[3], *E[3], *M[6];
+    uint32_t                  w3, w6;
+    int                       slots;
+};
+
+// One lane per record.  No floating point; nothing waits for another lane; the probe is find_or_claim's, bounded by the
+// capacity.  P.seen is null on a map without carve planes; the host launches records with moments only onto a map that has
+// the planes Q (and never records without onto such a map).  A wave sums its accepted counts before the one atomic.
+__global__ __launch_bounds__(256) void vmap_absorb_kernel(Records S, uint64_t n, Table T, Planes P, Moments Q, uint32_t *ctr)
+{
+    const uint64_t     i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    unsigned long long points = 0;
+    if (i < n) {
+        const uint64_t key = S.key[i];
+        if (!(S.slots && key == kEmpty)) {
+            const uint32_t c = S.count[i];
+            bool           ok = c != 0u && !(key >> 63); // all ones has bit 63 set
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ok = ok && ((key >> (21 * k)) & 0x1fffffull) != 0x1fffffull;
+            if (!ok) {
+                atomicAdd(&ctr[kDropped], 1u);
+            } else {
+                const long long h = find_or_claim(T, key, &ctr[kClaimed]);
+                if (h < 0) {
+                    atomicExch(&ctr[kError], 1u);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) atomicAdd(&T.sum[k][h], S.sum[k][i * S.w3]);
+                    atomicAdd(&T.count[h], c);
+                    if (S.seen && P.seen) {
+                        atomicAdd(&P.seen[h], S.seen[i]);
+                        atomicAdd(&P.miss[h], S.miss[i]);
+                    }
+                    if (S.E[0]) {
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) atomicAdd(&Q.E[k][h], S.E[k][i * S.w3]);
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) atomicAdd(&Q.M[k][h], S.M[k][i * S.w6]);
+                    }
+                    points = c;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) points += __shfl_xor(points, o);
+    if ((threadIdx.x & 63) == 0 && points) atomicAdd(reinterpret_cast<unsigned long long *>(ctr + kPoints), points);
+}
+
 inline unsigned blocks_for(uint64_t n) { return (unsigned)((n + 255) / 256); }
 constexpr size_t kSlotBytes = sizeof(uint64_t) + 3 * sizeof(long long) + sizeof(uint32_t);
 constexpr size_t kMomentBytes = 9 * sizeof(long long);                  // per slot, the moments' block
@@ -552,6 +616,7 @@ struct slam_vmap {
     // carve: the three planes (capacity u32 each) and the counters exist from the first carve on; per call the rays' end
     // cells and visited lengths, their chunk counts and the scan of those
     DevMem   seen, miss, stamp, cctr, rays, chunks, offs;
+    DevMem   actr; // absorb's counters, from the first absorb on
     uint32_t serial = 1; // of the next carve call: 1 .. 2^31 - 2
     // distributions (section 9), from slam_vmap_enable_distributions on: the nine moment planes (capacity i64 each) in one
     // block, the distribution planes (centroid and flag, normal, covariance, eigenvalues) in another, and whether the
@@ -665,6 +730,21 @@ int make_room(slam_vmap *m, int64_t n, hipStream_t st)
     if (m->carved()) m->seen = std::move(np[0]), m->miss = std::move(np[1]), m->stamp = std::move(np[2]);
     if (m->dist_on) m->mom = std::move(nm), m->dist = std::move(nd), m->dist_stale = true;
     m->capacity = cap;
+    return SLAM_OK;
+}
+
+// The three carve planes and the carve counters, zeroed on st, when the map has none yet: what a first carve allocates.
+int ensure_carve_planes(slam_vmap *m, hipStream_t st)
+{
+    if (m->carved()) return SLAM_OK;
+    const size_t plane = (size_t)m->capacity * sizeof(uint32_t);
+    SLAM_TRY(m->cctr.alloc(kCarveCounters * sizeof(unsigned long long)));
+    SLAM_TRY(m->seen.alloc(plane));
+    SLAM_TRY(m->miss.alloc(plane));
+    SLAM_HIP(hipMemsetAsync(m->seen.p, 0, plane, st));
+    SLAM_HIP(hipMemsetAsync(m->miss.p, 0, plane, st));
+    SLAM_TRY(m->stamp.alloc(plane)); // last: carved() is true only when all three stand
+    SLAM_HIP(hipMemsetAsync(m->stamp.p, 0, plane, st));
     return SLAM_OK;
 }
 
@@ -905,7 +985,7 @@ int slam_vmap_info(slam_vmap_t *m, int64_t *n_voxels, int64_t *capacity, int64_t
     if (device_bytes)
         *device_bytes = m->table.cap + m->ctr.cap + m->flag.cap + m->sel.cap + m->keys_in.cap + m->keys_out.cap + m->sel_sorted.cap + m->tmp.cap +
                         m->stage_in.cap + m->stage_out.cap + m->seen.cap + m->miss.cap + m->stamp.cap + m->cctr.cap + m->rays.cap + m->chunks.cap +
-                        m->offs.cap + m->mom.cap + m->dist.cap + m->reg_work.cap;
+                        m->offs.cap + m->mom.cap + m->dist.cap + m->reg_work.cap + m->actr.cap;
     return SLAM_OK;
 }
 
@@ -970,15 +1050,7 @@ int slam_vmap_carve_dev(slam_vmap_t *m, const float *d_xyz, int n, int stride, c
 
     hipStream_t  st = as_stream(stream);
     const size_t plane = (size_t)m->capacity * sizeof(uint32_t);
-    if (!m->carved()) {
-        SLAM_TRY(m->cctr.alloc(kCarveCounters * sizeof(unsigned long long)));
-        SLAM_TRY(m->seen.alloc(plane));
-        SLAM_TRY(m->miss.alloc(plane));
-        SLAM_HIP(hipMemsetAsync(m->seen.p, 0, plane, st));
-        SLAM_HIP(hipMemsetAsync(m->miss.p, 0, plane, st));
-        SLAM_TRY(m->stamp.alloc(plane)); // last: carved() is true only when all three stand
-        SLAM_HIP(hipMemsetAsync(m->stamp.p, 0, plane, st));
-    }
+    SLAM_TRY(ensure_carve_planes(m, st));
     if (m->serial >= 0x7fffffffu) { // 2 s + 1 would no longer fit: forget every stamp and start again
         SLAM_HIP(hipMemsetAsync(m->stamp.p, 0, plane, st));
         m->serial = 1;
@@ -1202,6 +1274,227 @@ int slam_vmap_read_distributions(slam_vmap_t *m, float *centroid3, double *norma
     if (flag) SLAM_HIP(hipMemcpy(flag, d_flag, N, hipMemcpyDeviceToHost));
     if (key) SLAM_HIP(hipMemcpy(key, d_key, N * 8, hipMemcpyDeviceToHost));
     SLAM_HIP(hipStreamSynchronize(nullptr));
+    return SLAM_OK;
+}
+
+// ---------------------------------------------------------------- absorb, merge, save, load (docs/VOXEL_MAP.md section 10)
+// `lanes` records (or source slots) of S into m, with room made for `n_new` more voxels first: waits once for st.
+static int absorb_records(slam_vmap *m, Records S, uint64_t lanes, int64_t n_new, int64_t *n_rejected, hipStream_t st)
+{
+    SLAM_TRY(make_room(m, n_new, st));
+    if (S.seen) SLAM_TRY(ensure_carve_planes(m, st)); // after the growth: at the table's size
+    if (!m->actr.p) SLAM_TRY(m->actr.alloc(kAbsorbCounters * sizeof(uint32_t)));
+    uint32_t *h = static_cast<uint32_t *>(pinned_scratch(kAbsorbCounters * sizeof(uint32_t)));
+    SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
+    SLAM_HIP(hipMemsetAsync(m->actr.p, 0, kAbsorbCounters * sizeof(uint32_t), st));
+    const Planes  P = m->carved() ? m->planes() : Planes{nullptr, nullptr, nullptr};
+    const Moments Q = m->dist_on ? m->moments() : Moments{};
+    hipLaunchKernelGGL(vmap_absorb_kernel, dim3(blocks_for(lanes)), dim3(256), 0, st, S, lanes, m->view(), P, Q, m->actr.as<uint32_t>());
+    SLAM_HIP(hipGetLastError());
+    m->dist_stale = true;
+    SLAM_HIP(hipMemcpyAsync(h, m->actr.p, kAbsorbCounters * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SLAM_HIP(hipStreamSynchronize(st));
+    m->n_voxels += h[kClaimed];
+    m->n_points += (int64_t)((uint64_t)h[kPoints] | (uint64_t)h[kPoints + 1] << 32);
+    if (n_rejected) *n_rejected = (int64_t)h[kDropped];
+    SLAM_REQUIRE(!h[kError], SLAM_E_HIP, "slam_vmap_absorb: a probe ran through all %lld slots (%lld voxels): records were lost",
+                 (long long)m->capacity, (long long)m->n_voxels);
+    return SLAM_OK;
+}
+
+static Records packed_records(const uint64_t *key, const uint32_t *count, const int64_t *sums, const uint32_t *seen, const uint32_t *miss,
+                              const int64_t *E3, const int64_t *M6)
+{
+    Records S{};
+    S.key = key, S.count = count, S.seen = seen, S.miss = miss;
+    for (int k = 0; k < 3; ++k) S.sum[k] = reinterpret_cast<const unsigned long long *>(sums) + k;
+    if (E3) {
+        for (int k = 0; k < 3; ++k) S.E[k] = reinterpret_cast<const unsigned long long *>(E3) + k;
+        for (int k = 0; k < 6; ++k) S.M[k] = reinterpret_cast<const unsigned long long *>(M6) + k;
+    }
+    S.w3 = 3, S.w6 = 6, S.slots = 0;
+    return S;
+}
+
+// What can be refused without a handle, then the device, then the handle (the rule of check_carve).
+static int check_absorb(const char *who, slam_vmap *m, const void *key, const void *count, const void *sums, const void *seen, const void *miss,
+                        const void *E3, const void *M6, int n)
+{
+    SLAM_REQUIRE(n >= 0 && (n == 0 || (key && count && sums)) && (seen == nullptr) == (miss == nullptr) && (E3 == nullptr) == (M6 == nullptr),
+                 SLAM_E_INVALID, "%s: n >= 0, key, count and sums, seen and miss both or neither, E3 and M6 both or neither", who);
+    SLAM_TRY(require_device());
+    SLAM_REQUIRE(m, SLAM_E_INVALID, "%s: map is NULL", who);
+    return SLAM_OK;
+}
+
+int slam_vmap_layout(slam_vmap_t *m, double *leaf, int *carved, int *distributions, slam_vmap_dist_params *dp)
+{
+    SLAM_TRY(require_device());
+    SLAM_REQUIRE(m, SLAM_E_INVALID, "slam_vmap_layout: map is NULL");
+    if (leaf) *leaf = m->P.leaf;
+    if (carved) *carved = m->carved() ? 1 : 0;
+    if (distributions) *distributions = m->dist_on ? 1 : 0;
+    if (dp) *dp = m->dist_on ? m->DP : slam_vmap_dist_params{};
+    return SLAM_OK;
+}
+
+int slam_vmap_absorb_dev(slam_vmap_t *m, const uint64_t *d_key, const uint32_t *d_count, const int64_t *d_sums, const uint32_t *d_seen,
+                         const uint32_t *d_miss, const int64_t *d_E3, const int64_t *d_M6, int n, int64_t *n_rejected, slam_stream_t stream)
+{
+    SLAM_TRY(check_absorb("slam_vmap_absorb_dev", m, d_key, d_count, d_sums, d_seen, d_miss, d_E3, d_M6, n));
+    if (n_rejected) *n_rejected = 0;
+    if (n == 0) return SLAM_OK;
+    SLAM_REQUIRE((d_E3 != nullptr) == m->dist_on, SLAM_E_INVALID,
+                 "slam_vmap_absorb_dev: records %s moments into a map %s distributions: a half-filled moment plane would give wrong planes",
+                 d_E3 ? "with" : "without", m->dist_on ? "with" : "without");
+    return absorb_records(m, packed_records(d_key, d_count, d_sums, d_seen, d_miss, d_E3, d_M6), (uint64_t)n, n, n_rejected, as_stream(stream));
+}
+
+int slam_vmap_absorb(slam_vmap_t *m, const uint64_t *key, const uint32_t *count, const int64_t *sums, const uint32_t *seen, const uint32_t *miss,
+                     const int64_t *E3, const int64_t *M6, int n, int64_t *n_rejected)
+{
+    SLAM_TRY(check_absorb("slam_vmap_absorb", m, key, count, sums, seen, miss, E3, M6, n));
+    if (n_rejected) *n_rejected = 0;
+    if (n == 0) return SLAM_OK;
+    SLAM_REQUIRE((E3 != nullptr) == m->dist_on, SLAM_E_INVALID,
+                 "slam_vmap_absorb: records %s moments into a map %s distributions: a half-filled moment plane would give wrong planes",
+                 E3 ? "with" : "without", m->dist_on ? "with" : "without");
+    // staged as keys, sums, E, M (8-byte words), then count, seen, miss
+    const size_t N = (size_t)n;
+    SLAM_TRY(reserve_quarter(m->stage_in, N * (8 + 24 + (E3 ? 72 : 0) + 4 + (seen ? 8 : 0))));
+    uint64_t *d_key = m->stage_in.as<uint64_t>();
+    int64_t  *d_sums = reinterpret_cast<int64_t *>(d_key + N), *d_E = d_sums + 3 * N, *d_M = d_E + 3 * N;
+    uint32_t *d_count = reinterpret_cast<uint32_t *>(E3 ? d_M + 6 * N : d_E), *d_seen = d_count + N, *d_miss = d_seen + N;
+    SLAM_HIP(hipMemcpy(d_key, key, N * 8, hipMemcpyHostToDevice));
+    SLAM_HIP(hipMemcpy(d_sums, sums, N * 24, hipMemcpyHostToDevice));
+    SLAM_HIP(hipMemcpy(d_count, count, N * 4, hipMemcpyHostToDevice));
+    if (E3) {
+        SLAM_HIP(hipMemcpy(d_E, E3, N * 24, hipMemcpyHostToDevice));
+        SLAM_HIP(hipMemcpy(d_M, M6, N * 48, hipMemcpyHostToDevice));
+    }
+    if (seen) {
+        SLAM_HIP(hipMemcpy(d_seen, seen, N * 4, hipMemcpyHostToDevice));
+        SLAM_HIP(hipMemcpy(d_miss, miss, N * 4, hipMemcpyHostToDevice));
+    }
+    return absorb_records(m, packed_records(d_key, d_count, d_sums, seen ? d_seen : nullptr, seen ? d_miss : nullptr, E3 ? d_E : nullptr, E3 ? d_M : nullptr),
+                          (uint64_t)n, n, n_rejected, nullptr);
+}
+
+int slam_vmap_merge(slam_vmap_t *dst, slam_vmap_t *src, int64_t *n_rejected, slam_stream_t stream)
+{
+    SLAM_REQUIRE(dst != src || !dst, SLAM_E_INVALID, "slam_vmap_merge: a map cannot be merged into itself");
+    SLAM_TRY(require_device());
+    SLAM_REQUIRE(dst && src, SLAM_E_INVALID, "slam_vmap_merge: a map is NULL");
+    SLAM_REQUIRE(std::memcmp(&dst->P.leaf, &src->P.leaf, sizeof(double)) == 0, SLAM_E_INVALID,
+                 "slam_vmap_merge: leaves %.17g and %.17g differ: the integer sums of one cannot be moved into the other's voxels", dst->P.leaf,
+                 src->P.leaf);
+    SLAM_REQUIRE(dst->dist_on == src->dist_on, SLAM_E_INVALID, "slam_vmap_merge: distributions on one side only");
+    if (n_rejected) *n_rejected = 0;
+    if (src->n_voxels == 0) return SLAM_OK;
+    Records     S{};
+    const Table T = src->view();
+    S.key = T.key, S.count = T.count;
+    for (int k = 0; k < 3; ++k) S.sum[k] = T.sum[k];
+    if (src->carved()) S.seen = src->seen.as<uint32_t>(), S.miss = src->miss.as<uint32_t>();
+    if (src->dist_on) {
+        const Moments Q = src->moments();
+        for (int k = 0; k < 3; ++k) S.E[k] = Q.E[k];
+        for (int k = 0; k < 6; ++k) S.M[k] = Q.M[k];
+    }
+    S.w3 = S.w6 = 1, S.slots = 1;
+    return absorb_records(dst, S, (uint64_t)src->capacity, src->n_voxels, n_rejected, as_stream(stream));
+}
+
+int slam_vmap_save(slam_vmap_t *m, const char *path)
+{
+    SLAM_REQUIRE(path && path[0], SLAM_E_INVALID, "slam_vmap_save: path is NULL or empty");
+    SLAM_TRY(require_device());
+    SLAM_REQUIRE(m, SLAM_E_INVALID, "slam_vmap_save: map is NULL");
+    SLAM_REQUIRE(m->n_voxels <= vmap_file::kMaxVoxels, SLAM_E_INVALID, "slam_vmap_save: %lld voxels are more than the 2^30 a file holds",
+                 (long long)m->n_voxels);
+    try {
+        const size_t          N = (size_t)m->n_voxels;
+        const int             cap = (int)m->n_voxels;
+        int                   got = 0;
+        std::vector<uint64_t> key(N);
+        std::vector<uint32_t> count(N), seen, miss;
+        std::vector<int64_t>  sums(3 * N), E, M;
+        vmap_file::Meta       meta;
+        meta.leaf = m->P.leaf, meta.n = m->n_voxels, meta.n_points = m->n_points;
+        SLAM_TRY(slam_vmap_read_sums(m, sums.data(), count.data(), key.data(), cap, &got));
+        SLAM_REQUIRE(got == cap, SLAM_E_HIP, "slam_vmap_save: the table holds %d voxels, the handle counts %d", got, cap);
+        if (m->carved()) {
+            meta.flags |= vmap_file::kCarve;
+            seen.resize(N), miss.resize(N);
+            SLAM_TRY(slam_vmap_read_carve(m, seen.data(), miss.data(), nullptr, cap, &got));
+        }
+        if (m->dist_on) {
+            meta.flags |= vmap_file::kMoments;
+            meta.min_points = m->DP.min_points, meta.max_miss_num = m->DP.max_miss_num, meta.max_miss_den = m->DP.max_miss_den;
+            meta.flat_ratio = m->DP.flat_ratio, meta.line_ratio = m->DP.line_ratio, meta.epsilon = m->DP.epsilon;
+            E.resize(3 * N), M.resize(6 * N);
+            SLAM_TRY(slam_vmap_read_moments(m, E.data(), M.data(), nullptr, cap, &got));
+        }
+        const std::vector<uint8_t> bytes = vmap_file::build(meta, key.data(), count.data(), sums.data(), seen.data(), miss.data(), E.data(), M.data());
+        std::string                why;
+        // the writer is held to the reader: a map that slam_vmap_load would refuse (a cell of 2^20 - 1, a wrapped count) is not written
+        SLAM_REQUIRE(vmap_file::parse(bytes.data(), bytes.size(), nullptr, &why), SLAM_E_INVALID, "slam_vmap_save: the file format cannot hold this map: %s",
+                     why.c_str());
+        SLAM_REQUIRE(vmap_file::write_all(path, bytes, &why) == 0, SLAM_E_IO, "slam_vmap_save: %s", why.c_str());
+    } catch (const std::bad_alloc &) {
+        set_error("slam_vmap_save: out of host memory");
+        return SLAM_E_NOMEM;
+    }
+    return SLAM_OK;
+}
+
+int slam_vmap_load(const char *path, slam_vmap_t **out)
+{
+    SLAM_REQUIRE(path && path[0] && out, SLAM_E_INVALID, "slam_vmap_load: path is NULL or empty, or out is NULL");
+    try {
+        std::vector<uint8_t> bytes;
+        std::string          why;
+        vmap_file::View      v;
+        SLAM_REQUIRE(vmap_file::read_all(path, &bytes, &why) == 0, SLAM_E_IO, "slam_vmap_load: %s", why.c_str());
+        SLAM_REQUIRE(vmap_file::parse(bytes.data(), bytes.size(), &v, &why), SLAM_E_INVALID, "slam_vmap_load: %s: %s", path, why.c_str());
+        SLAM_TRY(require_device());
+        const vmap_file::Meta &f = v.meta;
+        slam_vmap_params       p;
+        p.leaf = f.leaf;
+        p.initial_capacity = (int)std::min<int64_t>(pow2_at_least(2 * f.n), 1ll << 30); // the absorb does not grow (beyond 2^29 voxels it does, once)
+        slam_vmap_t *m = nullptr;
+        SLAM_TRY(slam_vmap_create(&p, &m));
+        int rc = SLAM_OK;
+        if (f.flags & vmap_file::kMoments) {
+            slam_vmap_dist_params dp;
+            dp.min_points = f.min_points, dp.flat_ratio = f.flat_ratio, dp.line_ratio = f.line_ratio, dp.epsilon = f.epsilon;
+            dp.max_miss_num = f.max_miss_num, dp.max_miss_den = f.max_miss_den;
+            rc = slam_vmap_enable_distributions(m, &dp);
+        }
+        if (rc == SLAM_OK && (f.flags & vmap_file::kCarve)) { // also for a file without voxels: a carved map stays one
+            rc = ensure_carve_planes(m, nullptr);
+            if (rc == SLAM_OK && hipStreamSynchronize(nullptr) != hipSuccess) set_error("slam_vmap_load: clearing the carve planes failed"), rc = SLAM_E_HIP;
+        }
+        int64_t rejected = 0;
+        if (rc == SLAM_OK)
+            rc = slam_vmap_absorb(m, reinterpret_cast<const uint64_t *>(v.key), reinterpret_cast<const uint32_t *>(v.count),
+                                  reinterpret_cast<const int64_t *>(v.sums), reinterpret_cast<const uint32_t *>(v.seen),
+                                  reinterpret_cast<const uint32_t *>(v.miss), reinterpret_cast<const int64_t *>(v.E),
+                                  reinterpret_cast<const int64_t *>(v.M), (int)f.n, &rejected);
+        if (rc == SLAM_OK && (rejected != 0 || m->n_voxels != f.n || m->n_points != f.n_points)) {
+            set_error("slam_vmap_load: %lld records rejected, %lld voxels of %lld, %lld points of %lld", (long long)rejected, (long long)m->n_voxels,
+                      (long long)f.n, (long long)m->n_points, (long long)f.n_points);
+            rc = SLAM_E_HIP;
+        }
+        if (rc != SLAM_OK) {
+            slam_vmap_destroy(m);
+            return rc;
+        }
+        *out = m;
+    } catch (const std::bad_alloc &) {
+        set_error("slam_vmap_load: out of host memory");
+        return SLAM_E_NOMEM;
+    }
     return SLAM_OK;
 }
 
