@@ -210,6 +210,79 @@ __device__ inline void group_min(Best &b, const StartT *oidx)
     }
 }
 
+// the minimum of a float over the G lanes of a query's group, in every lane
+template <int G>
+__device__ inline float group_fmin(float v)
+{
+#pragma unroll
+    for (int o = 1; o < G; o <<= 1) v = fminf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// The cells of lattice row y that the closed disk of radius Rd CELLS (the lattice margin included) around the query at (fx, fy)
+// cells touches, within the level's [x_lo, x_hi]: a point of row y is at least dy rows from the query, so within Rd of it only if
+// no farther than sqrt(Rd^2 - dy^2) columns.  A cell outside [lo, hi] lies wholly outside the disk; a point AT the disk's
+// distance is on it and its cell is kept.  lo > hi: the disk does not reach the row.
+struct RowChord {
+    int lo, hi;
+};
+__device__ inline RowChord row_chord(float fx, float fy, int y, float Rd, int x_lo, int x_hi)
+{
+    const float dy = fmaxf(fmaxf((float)y - fy, fy - (float)(y + 1)), 0.0f);
+    const float half = __builtin_amdgcn_sqrtf(fmaxf(Rd * Rd - dy * dy, 0.0f)) + 1.0e-3f;
+    RowChord    c;
+    c.lo = max(x_lo, ifloor(fx - half));
+    c.hi = min(x_hi, ifloor(fx + half));
+    return c;
+}
+
+// A ring level entered WITHOUT a candidate (no seed, nothing in the levels inside): an upper bound of the nearest distance from
+// per lattice row the point(s) of the cells nearest the query's column, found through start[] -- the last point left and the
+// first right of the inner square in its rows, the two around the query's column elsewhere.  The rows of the level are dealt
+// over the G lanes of the group (lane `lig`); every lane returns the group's minimum, FLT_MAX when the level is empty.  The
+// bound only prunes: the nearest point lies inside its disk and is found by the scan itself, ties and all.
+template <int G, typename StartT>
+__device__ inline float probe_level(const StartT *start, const float2 *pts, int nx, int x_lo, int x_hi, int y_lo, int y_hi, int cx,
+                                    int cy, int rp, int lig, float qx, float qy)
+{
+    float pd = FLT_MAX;
+    for (int y0 = y_lo; y0 <= y_hi; y0 += G) {
+        const int y = y0 + lig, row = y * nx;
+        if (y <= y_hi) {
+            if (rp >= 0 && y >= cy - rp && y <= cy + rp) {
+                const int l1 = min(x_hi, cx - rp - 1), f2 = max(x_lo, cx + rp + 1);
+                if (x_lo <= l1) {
+                    const int a = (int)start[row + x_lo], e = (int)start[row + l1 + 1];
+                    if (e > a) pd = fminf(pd, dist2(pts[e - 1], qx, qy)); // the last point left of the inner square
+                }
+                if (f2 <= x_hi) {
+                    const int a = (int)start[row + f2], e = (int)start[row + x_hi + 1];
+                    if (e > a) pd = fminf(pd, dist2(pts[a], qx, qy)); // the first point right of it
+                }
+            } else if (x_lo <= x_hi) {
+                const int a = (int)start[row + x_lo], e = (int)start[row + x_hi + 1];
+                if (e > a) {
+                    const int c = (int)start[row + clampi(cx, x_lo, x_hi)]; // the first point at or right of the query's column
+                    pd = fminf(pd, fminf(dist2(pts[min(c, e - 1)], qx, qy), dist2(pts[max(c - 1, a)], qx, qy)));
+                }
+            }
+        }
+    }
+    return group_fmin<G>(pd);
+}
+
+// What the ring searches of the batch kernels (nn_search_impl, nn_search_seeded_impl) do about FAR queries beside the row
+// chords (the spread form has chords and probe since round 6; profiles/r08_ring_prune_ab.txt).  -D...=0 in a measurement build
+// (SLAM_MEASURE_DEFINES) takes a part out again for an A/B.
+#ifndef SLAM_RING_PROBE_LEVEL
+#define SLAM_RING_PROBE_LEVEL 2 // levels of this radius (cells) and beyond are probed before they are read when no candidate exists (0: never)
+#endif
+#ifndef SLAM_SEED_ROWS
+#define SLAM_SEED_ROWS 12 // a seeded query whose disk spans more than 3 x 3 cells and at most this many rows reads them in one pass (0: rings)
+#endif
+constexpr int  kProbeFromLevelBatch = SLAM_RING_PROBE_LEVEL > 0 ? SLAM_RING_PROBE_LEVEL : 0x40000000;
+constexpr int  kSeedRowsMax = SLAM_SEED_ROWS;
+
 template <int G, typename StartT, bool EXACT, bool PK = false>
 __device__ inline Best nn_search_impl(const IndexPtrs<StartT> &ix, const ModelView &mv, int cls, float qx, float qy,
                                       int sub, double gate, bool &tie);
@@ -237,9 +310,13 @@ __device__ inline Best nn_search(const IndexPtrs<StartT> &ix, const ModelView &m
 //
 // Order of visits: the query's own cell, then square rings of radius 1, 2, 4,
 // ... cells.  Inside a ring only the cells that intersect the disk of the
-// current best distance are read (a skipped cell lies entirely farther than
-// the best found so far, which only shrinks), and cells of the previous,
-// smaller square are not read again.  The search ends when the best distance
+// best distance the level was entered with are read -- per lattice row the
+// cells under the disk's chord (row_chord), not the disk's bounding square: a
+// skipped cell lies entirely farther than the best found so far, which only
+// shrinks -- and cells of the previous, smaller square are not read again.  A
+// level of radius >= kProbeFromLevelBatch entered with no candidate at all is
+// probed first (probe_level) and read under the disk of what the probe found.
+// The search ends when the best distance
 // is below the distance to the ring's outer edge (minus a margin that absorbs
 // the f32 rounding of the cell assignment), when that edge is beyond the
 // inlier gate, or when the ring covers the whole lattice.
@@ -270,27 +347,40 @@ __device__ inline Best nn_search_impl(const IndexPtrs<StartT> &ix, const ModelVi
             group_min_lean<G>(b, tie);
     }
 
-    int rp = 0; // radius of the square already visited
     for (int r = 1;; r *= 2) {
+        const int rp = r >> 1; // radius of the square already visited
         // the ring's own extent, then the disk of the current best distance
         int y_lo = max(cy - r, 0), y_hi = min(cy + r, L.ny - 1);
-        int x_lo = max(cx - r, 0), x_hi = min(cx + r, L.nx - 1);
-        const bool covers = (x_lo == 0) & (y_lo == 0) & (x_hi == L.nx - 1) & (y_hi == L.ny - 1);
-        if (b.d < FLT_MAX) {
-            // points of a column (row) above cell(q + R) have x (y) > q + R: the cell map is monotone
-            const float R = (disk_radius(b.d) + L.margin) * L.inv_h;
-            x_lo = max(x_lo, ifloor(fx - R));
-            x_hi = min(x_hi, ifloor(fx + R));
-            y_lo = max(y_lo, ifloor(fy - R));
-            y_hi = min(y_hi, ifloor(fy + R));
+        // the candidate the level is read under: the best so far (the same in every lane of the group: the lanes share a row's
+        // span by `sub`, so they need the same bounds), or, for a level entered with none, what a probe of it finds
+        float cand = b.d;
+        if (cand == FLT_MAX && r >= kProbeFromLevelBatch)
+            cand = probe_level<G, StartT>(start, pts, L.nx, max(cx - r, 0), min(cx + r, L.nx - 1), y_lo, y_hi, cx, cy, rp, sub, qx, qy);
+        float Rd = 1.0e30f; // its disk, in cells (none: every chord is the whole row)
+        if (cand < FLT_MAX) {
+            // points of a row above cell(q + R) have y > q + R: the cell map is monotone
+            Rd = (disk_radius(cand) + L.margin) * L.inv_h;
+            y_lo = max(y_lo, ifloor(fy - Rd));
+            y_hi = min(y_hi, ifloor(fy + Rd));
         }
-        for (int y = y_lo; y <= y_hi; ++y) {
-            const int row = y * L.nx;
-            if (y >= cy - rp && y <= cy + rp) {
-                scan_span<G, StartT, EXACT, PK>(b, tie, start, pts, oidx, row, x_lo, min(x_hi, cx - rp - 1), sub, qx, qy);
-                scan_span<G, StartT, EXACT, PK>(b, tie, start, pts, oidx, row, max(x_lo, cx + rp + 1), x_hi, sub, qx, qy);
+        // One row span per turn -- an inner row (the square already visited splits it) takes two, left then right, its chord worked
+        // out again for the second: ONE scan in the loop, and no chord end held across a scan (written with a scan per span the
+        // point-to-point pair kernels, at their 128 registers, spill three).
+        for (int y = y_lo, side = 0; y <= y_hi;) {
+            const bool inner = (y >= cy - rp) & (y <= cy + rp);
+            RowChord   c = row_chord(fx, fy, y, Rd, max(cx - r, 0), min(cx + r, L.nx - 1)); // (inside the disk's bounding columns by itself)
+            if (inner) {
+                if (side == 0)
+                    c.hi = min(c.hi, cx - rp - 1);
+                else
+                    c.lo = max(c.lo, cx + rp + 1);
+            }
+            scan_span<G, StartT, EXACT, PK>(b, tie, start, pts, oidx, y * L.nx, c.lo, c.hi, sub, qx, qy);
+            if (inner && side == 0) {
+                side = 1;
             } else {
-                scan_span<G, StartT, EXACT, PK>(b, tie, start, pts, oidx, row, x_lo, x_hi, sub, qx, qy);
+                side = 0;
+                ++y;
             }
         }
         if (G > 1) {
@@ -301,9 +391,9 @@ __device__ inline Best nn_search_impl(const IndexPtrs<StartT> &ix, const ModelVi
         }
         const float bound = (float)r * L.h - L.margin;
         const float b2 = bound * bound;
+        const bool  covers = (cx - r <= 0) & (cy - r <= 0) & (cx + r >= L.nx - 1) & (cy + r >= L.ny - 1);
         // every point outside the ring's square is farther than `bound` in x or in y
         if (covers || b.d < b2 || (double)b2 >= gate) break;
-        rp = r;
     }
     if (G == 1 || !EXACT) b.oidx = b.pos >= 0 ? (unsigned)oidx[b.pos] : 0xffffffffu;
     return b;
@@ -394,8 +484,10 @@ __device__ inline void scan_range_deep(Best &b, bool &tie, const float2 *pts, co
 // nn_search with last iteration's neighbour of the same scene point as the first candidate (seed = its position
 // in the sorted array, -1 = none): the disk of its distance prunes the search from the first cell on, where an
 // unseeded search reads its first non-empty ring whole.  When that disk touches at most 3 x 3 cells they are
-// read in one pass and the search is over (every cell the disk touches has been seen); otherwise the rings run
-// as usual from the seeded best.  Same result as nn_search.
+// read in one pass and the search is over (every cell the disk touches has been seen); a larger disk of at most
+// kSeedRowsMax rows is read in one pass too, row by row under its chord from the query's row outwards; beyond
+// that the rings run as usual from the seeded best (their rows under chords as in nn_search_impl).  Same result
+// as nn_search.
 template <int G, typename StartT, bool EXACT, bool PK = false>
 __device__ inline Best nn_search_seeded_impl(const IndexPtrs<StartT> &ix, const ModelView &mv, int cls, float qx, float qy,
                                              int sub, double gate, bool &tie, int seed, float empty_in, float move, float &empty_out)
@@ -435,6 +527,38 @@ __device__ inline Best nn_search_seeded_impl(const IndexPtrs<StartT> &ix, const 
             empty_out = __fsqrt_rn(b.d) * 0.999999f;
             return b;
         }
+        // A larger disk (a tenth of the queries at iteration 1, the far corners' beams for several more) of at most kSeedRowsMax
+        // rows: the rows of its box in ONE pass, each under its chord, from the query's row outwards -- the near rows hold the
+        // neighbour more often than not, and the group's best, refreshed after each pair of rows, narrows the chords of the rows
+        // farther out and drops those the disk no longer reaches.  Every cell the closed disk of the final best touches has
+        // been read (a row is read under the disk of the best of its time, which only shrinks), so the search is over:
+        // where the rings would read the query's cell and levels 1, 2, 4 under the bounding square with a reduction each.
+        if (kSeedRowsMax > 0 && y_hi - y_lo < kSeedRowsMax && x_lo <= x_hi && y_lo <= y_hi) {
+            const int ym = clampi(cy, y_lo, y_hi);
+            float     Rd = R;
+            for (int k = 0; ym - k >= y_lo || ym + k <= y_hi; ++k) {
+                // rows the disk of the best so far still reaches: [floor(fy - Rd), floor(fy + Rd)] within the box
+                const int yl = max(y_lo, ifloor(fy - Rd)), yh = min(y_hi, ifloor(fy + Rd));
+                if (ym - k < yl && ym + k > yh) break;
+                for (int s = 0; s < (k > 0 ? 2 : 1); ++s) {
+                    const int y = s ? ym + k : ym - k;
+                    if (y < yl || y > yh) continue;
+                    const RowChord c = row_chord(fx, fy, y, Rd, 0, L.nx - 1);
+                    if (c.lo <= c.hi)
+                        scan_range_rt<StartT, EXACT, PK>(b, tie, pts, oidx, (int)start[y * L.nx + c.lo], (int)start[y * L.nx + c.hi + 1], sub, G, qx, qy);
+                }
+                if (G > 1) {
+                    if (EXACT)
+                        group_min<G, StartT>(b, oidx);
+                    else
+                        group_min_lean<G>(b, tie);
+                }
+                Rd = (disk_radius(b.d) + L.margin) * L.inv_h;
+            }
+            if (G == 1 || !EXACT) b.oidx = (unsigned)oidx[b.pos];
+            empty_out = __fsqrt_rn(b.d) * 0.999999f;
+            return b;
+        }
     }
     // cells that lie inside the disk last iteration proved empty, shrunk by the query's move since, need no visit
     int rp = -1, r = 0;
@@ -458,21 +582,21 @@ __device__ inline Best nn_search_seeded_impl(const IndexPtrs<StartT> &ix, const 
         int y_lo = max(cy - r, 0), y_hi = min(cy + r, L.ny - 1);
         int x_lo = max(cx - r, 0), x_hi = min(cx + r, L.nx - 1);
         const bool covers = (x_lo == 0) & (y_lo == 0) & (x_hi == L.nx - 1) & (y_hi == L.ny - 1);
+        float Rd = 1.0e30f; // the disk of the best so far (the same in every lane of the group), in cells; none: whole rows
         if (b.d < FLT_MAX) {
-            const float R = (disk_radius(b.d) + L.margin) * L.inv_h;
-            x_lo = max(x_lo, ifloor(fx - R));
-            x_hi = min(x_hi, ifloor(fx + R));
-            y_lo = max(y_lo, ifloor(fy - R));
-            y_hi = min(y_hi, ifloor(fy + R));
+            Rd = (disk_radius(b.d) + L.margin) * L.inv_h;
+            y_lo = max(y_lo, ifloor(fy - Rd));
+            y_hi = min(y_hi, ifloor(fy + Rd));
         }
         for (int y = y_lo; y <= y_hi; ++y) {
-            const int row = y * L.nx;
+            const int      row = y * L.nx;
+            const RowChord c = row_chord(fx, fy, y, Rd, x_lo, x_hi);
             if (y >= cy - rp && y <= cy + rp) {
-                const int l1 = min(x_hi, cx - rp - 1), f2 = max(x_lo, cx + rp + 1);
-                if (x_lo <= l1) scan_range_rt<StartT, EXACT, PK>(b, tie, pts, oidx, (int)start[row + x_lo], (int)start[row + l1 + 1], sub, G, qx, qy);
-                if (f2 <= x_hi) scan_range_rt<StartT, EXACT, PK>(b, tie, pts, oidx, (int)start[row + f2], (int)start[row + x_hi + 1], sub, G, qx, qy);
-            } else if (x_lo <= x_hi) {
-                scan_range_rt<StartT, EXACT, PK>(b, tie, pts, oidx, (int)start[row + x_lo], (int)start[row + x_hi + 1], sub, G, qx, qy);
+                const int l1 = min(c.hi, cx - rp - 1), f2 = max(c.lo, cx + rp + 1);
+                if (c.lo <= l1) scan_range_rt<StartT, EXACT, PK>(b, tie, pts, oidx, (int)start[row + c.lo], (int)start[row + l1 + 1], sub, G, qx, qy);
+                if (f2 <= c.hi) scan_range_rt<StartT, EXACT, PK>(b, tie, pts, oidx, (int)start[row + f2], (int)start[row + c.hi + 1], sub, G, qx, qy);
+            } else if (c.lo <= c.hi) {
+                scan_range_rt<StartT, EXACT, PK>(b, tie, pts, oidx, (int)start[row + c.lo], (int)start[row + c.hi + 1], sub, G, qx, qy);
             }
         }
         if (G > 1) {
@@ -709,15 +833,6 @@ struct Seed {
 // lanes take in two steps (a lidar cloud holds hundreds of points per cell near the sensor) is left to the
 // whole group, one such row after the other.  The query's own cell is part of the first level.  Visits the same
 // cells as nn_search_impl, so the result is the same (ties: flagged by the fast form, resolved by the exact one).
-// the minimum of a float over the G lanes of a query's group, in every lane
-template <int G>
-__device__ inline float group_fmin(float v)
-{
-#pragma unroll
-    for (int o = 1; o < G; o <<= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 template <int G, typename StartT, bool EXACT>
 __device__ inline Best nn_search_rows_impl(const IndexPtrs<StartT> &ix, const ModelView &mv, int cls, float qx, float qy,
                                            int lig, double gate, bool &tie, const Seed seed, float move, float &empty_out)
@@ -779,32 +894,8 @@ __device__ inline Best nn_search_rows_impl(const IndexPtrs<StartT> &ix, const Mo
         // distance; the level then reads the cells under THAT disk only.  (The bound only prunes: the nearest point lies
         // inside its disk and is found by the scan itself, ties and all.)
         float cand = b.d;
-        if (cand == FLT_MAX && r >= kProbeFromLevel) {
-            float pd = FLT_MAX;
-            for (int y0 = y_lo; y0 <= y_hi; y0 += G) {
-                const int y = y0 + lig, row = y * L.nx;
-                if (y <= y_hi) {
-                    if (rp >= 0 && y >= cy - rp && y <= cy + rp) {
-                        const int l1 = min(x_hi, cx - rp - 1), f2 = max(x_lo, cx + rp + 1);
-                        if (x_lo <= l1) {
-                            const int a = (int)start[row + x_lo], e = (int)start[row + l1 + 1];
-                            if (e > a) pd = fminf(pd, dist2(pts[e - 1], qx, qy)); // the last point left of the inner square
-                        }
-                        if (f2 <= x_hi) {
-                            const int a = (int)start[row + f2], e = (int)start[row + x_hi + 1];
-                            if (e > a) pd = fminf(pd, dist2(pts[a], qx, qy)); // the first point right of it
-                        }
-                    } else if (x_lo <= x_hi) {
-                        const int a = (int)start[row + x_lo], e = (int)start[row + x_hi + 1];
-                        if (e > a) {
-                            const int c = (int)start[row + clampi(cx, x_lo, x_hi)]; // the first point at or right of the query's column
-                            pd = fminf(pd, fminf(dist2(pts[min(c, e - 1)], qx, qy), dist2(pts[max(c - 1, a)], qx, qy)));
-                        }
-                    }
-                }
-            }
-            cand = group_fmin<G>(pd);
-        }
+        if (cand == FLT_MAX && r >= kProbeFromLevel)
+            cand = probe_level<G, StartT>(start, pts, L.nx, x_lo, x_hi, y_lo, y_hi, cx, cy, rp, lig, qx, qy);
         if (cand < FLT_MAX) {
             const float R = (disk_radius(cand) + L.margin) * L.inv_h;
             Rd = R;
@@ -827,10 +918,8 @@ __device__ inline Best nn_search_rows_impl(const IndexPtrs<StartT> &ix, const Mo
                 // lidar points reads the one or two cells per row that the disk touches where its bounding square holds metres of wall
                 int xl = x_lo, xh = x_hi;
                 if (Rd < 1.0e29f) {
-                    const float dy = fmaxf(fmaxf((float)y - fy, fy - (float)(y + 1)), 0.0f);
-                    const float half = __builtin_amdgcn_sqrtf(fmaxf(Rd * Rd - dy * dy, 0.0f)) + 1.0e-3f;
-                    xl = max(xl, ifloor(fx - half));
-                    xh = min(xh, ifloor(fx + half));
+                    const RowChord c = row_chord(fx, fy, y, Rd, x_lo, x_hi);
+                    xl = c.lo, xh = c.hi;
                 }
                 if (rp >= 0 && y >= cy - rp && y <= cy + rp) {
                     const int l1 = min(xh, cx - rp - 1), f2 = max(xl, cx + rp + 1);
