@@ -28,10 +28,15 @@ def world():
     return m_ga, m_nga, O.IcpModel(m_ga, m_nga)
 
 
-def check(world, batch, max_iter, min_delta, pair, indist=5.0):
+def check(world, batch, max_iter, min_delta, pair, indist=5.0, certify=False):
+    """certify: additionally hold every executed step to the oracle's brute-force step from the device's own previous pose
+    (icp_step_certificate.py; the host's brute force costs scan x model x steps distance evaluations: for small inputs)"""
     m_ga, m_nga, model = world
     icp = api.Icp(m_ga, m_nga, max_iter=max_iter, min_delta=min_delta, pair_scans=pair, spread_scans=-1)
-    R, t, res, _ = icp.fit_batch(batch, indist=indist)
+    R, t, res, trace = icp.fit_batch(batch, indist=indist, trace=certify)
+    if certify:
+        import icp_step_certificate as C
+        C.certify(model, batch, trace, res, max_iter, min_delta, indist, O.MODE_P2P, R=R, t=t, fill=0.0)
     R2, t2, res2, _ = icp.fit_batch(batch, indist=indist)
     icp.close()
     assert np.array_equal(R, R2) and np.array_equal(t, t2) and np.array_equal(res["n_corr"], res2["n_corr"])   # reproducible

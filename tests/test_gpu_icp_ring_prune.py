@@ -257,4 +257,4 @@ def test_seeded_one_pass_and_probe_match_the_oracle(room, n_scans, pair, p2l):
     if p2l:
         check_p2l(room, batch, pair)
     else:
-        check((m_ga, m_nga, models[0]), batch, MAX_ITER, -1.0, pair)
+        check((m_ga, m_nga, models[0]), batch, MAX_ITER, -1.0, pair, certify=True)   # ... and every step to the brute-force step
