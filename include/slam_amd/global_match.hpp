@@ -16,6 +16,22 @@
 //     gate of `refine_gate` (1 m) instead of 10 m, which the coarse match is well inside;
 //   * scans stay in the stores: one filtered scan per match() and store, which a test reads back afterwards; a caller that
 //     minds frees them with slam_kf_remove_keyframe (docs/VOXEL_MAP.md section 4).
+//
+// MapLocalizer, below GlobalMatcher, relocalises a scan in a saved voxel map (docs/VOXEL_MAP.md section 11.3): the consumer
+// slam_vmap_save / slam_vmap_load were written for.  It stands where GlobalMatcher stands, on the map's own plane voxels:
+//   setMap / load   the fine map (borrowed / owned, through slam_vmap_load); it must have distributions.  Level k is an owned
+//                   map of leaf ldexp(leaf, k) with the fine map's distribution parameters, filled by slam_vmap_coarsen from
+//                   level k - 1: the bits of a map integrated at that leaf, derived after load, nothing of it in the file
+//   yawFan          n planar starts at one position, yaws 2 pi / n apart
+//   localize        the scan becomes a keyframe of the store; from the coarsest level down ONE slam_vmap_register_gicp call
+//                   carries every live start, gated at GATE_RATIO times the level's leaf, from the level above's f32
+//                   transform; a start that ends a level without pairs or degenerate is out; the winner is chosen at level 0
+// A 1 m map can be entered by the direct registration only from about a leaf away (its candidates are the 27 cells around the
+// moved point); at an 8 m leaf the same rule reaches 8 m.  No random numbers: the same call gives the same bits.
+// slam_amd.api.MapLocalizer is the same thing with Python's names and habits:
+//   setMap -> set_map, yawFan -> yaw_fan, localize(cloud, n, stride, starts) -> localize(cloud, starts) returning a dict where
+//   this fills a MapLocalizerResult; ok() has no twin (the constructor raises); an error of the library and a map that cannot
+//   be taken are printed here and return false, there they raise SlamError.  The scan keyframe is removed on every way out.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -185,6 +201,208 @@ private:
 
     slam_kf_t *coarse_ = nullptr, *refine_ = nullptr;
     int        map_coarse_ = -1, map_refine_ = -1;
+};
+
+// ---- MapLocalizer (the head of this file; docs/VOXEL_MAP.md section 11.3)
+struct MapLocalizerResult {
+    bool   found = false;
+    int    index = -1; // of the winning start
+    float  transform[16] = {0};
+    double transform64[16] = {0};
+    double x = 0, y = 0, theta = 0; // of the f32 transform, as GlobalMatcher fills its edge
+    int    n_source = 0;            // points of the filtered scan
+};
+
+class MapLocalizer {
+public:
+    // fixed at construction
+    const int    LEVELS;
+    const double LEAF_SIZE; // of the store's filter
+    const int    MAX_ITERATIONS = 100;
+    const double TRANSFORMATION_EPSILON = 1e-6, FITNESS_EPSILON = 1e-6;
+    // read at every call
+    double GATE_RATIO = 2.0;
+    int    N_YAW = 8;
+    double MIN_PAIR_SHARE = 0.5;
+    double MAX_SCORE = 0.03; // between the two level-0 fitness populations of section 11.3: sqrt(0.00745 * 0.0964)
+
+    // every start's result per level of the last localize(): last[level][start], valid where ran[level][start]
+    std::vector<std::vector<slam_vmap_gicp_result>> last;
+    std::vector<std::vector<char>>                  ran;
+
+    explicit MapLocalizer(int levels = 4, double leaf = 0.30) : LEVELS(levels), LEAF_SIZE(leaf)
+    {
+        slam_kf_params p;
+        slam_kf_default_params(&p);
+        p.leaf_size = leaf, p.gate = 2.0, p.transformation_epsilon = TRANSFORMATION_EPSILON, p.fitness_epsilon = FITNESS_EPSILON;
+        slam_kf_gicp_params gp;
+        slam_kf_gicp_default_params(&gp);
+        gp.max_iterations = MAX_ITERATIONS, gp.transformation_epsilon = TRANSFORMATION_EPSILON;
+        if (levels < 1 || slam_kf_create(&p, &store_) != SLAM_OK || slam_kf_set_gicp_params(store_, &gp) != SLAM_OK) {
+            if (levels >= 1) warn();
+            slam_kf_destroy(store_);
+            store_ = nullptr;
+        }
+    }
+    ~MapLocalizer()
+    {
+        dropMap();
+        slam_kf_destroy(store_);
+    }
+    MapLocalizer(const MapLocalizer &) = delete;
+    MapLocalizer &operator=(const MapLocalizer &) = delete;
+    bool         ok() const { return store_ != nullptr; }
+    slam_kf_t   *store() { return store_; }
+    slam_vmap_t *level(int k) { return k == 0 ? fine_ : coarse_[(size_t)k - 1]; } // 0: the fine map; k >= 1: the derived ones
+
+    // the fine map, borrowed: the caller keeps and destroys it
+    bool setMap(slam_vmap_t *fine) { return take(fine, false); }
+    // the fine map from a file of slam_vmap_save, owned
+    bool load(const char *path)
+    {
+        slam_vmap_t *fine = nullptr;
+        if (!ok() || slam_vmap_load(path, &fine) != SLAM_OK) return warn(), false;
+        if (take(fine, true)) return true;
+        slam_vmap_destroy(fine);
+        return false;
+    }
+    // clears and refills the derived levels, after the fine map has grown
+    bool rebuild()
+    {
+        if (!ok() || !fine_) return false;
+        slam_vmap_t *below = fine_;
+        for (slam_vmap_t *m : coarse_) {
+            if (slam_vmap_clear(m, nullptr) != SLAM_OK || slam_vmap_coarsen(m, below, nullptr) != SLAM_OK) return warn(), false;
+            below = m;
+        }
+        return true;
+    }
+
+    // n planar starts (16 floats each, row-major) at (x, y) with yaws (float)((double) yaw + 2 pi k / n)
+    static std::vector<float> yawFan(float x, float y, float yaw, int n)
+    {
+        std::vector<float> out(16 * (size_t)(n > 0 ? n : 0));
+        for (int k = 0; k < n; ++k) GlobalMatcher::planar(x, y, (float)((double)yaw + 2.0 * M_PI * (double)k / (double)n), &out[16 * (size_t)k]);
+        return out;
+    }
+
+    // One scan (sensor frame, `stride` >= 3 floats per point) from `starts` (16 floats each).  False on an error of the library
+    // or without a map; otherwise *out says whether a start won.  The winner among the level-0 results that converged with
+    // fitness <= MAX_SCORE and fitness_pairs >= MIN_PAIR_SHARE n_source has the most fitness_pairs, then the lowest index.
+    bool localize(const float *cloud, int n, int stride, const std::vector<float> &starts, MapLocalizerResult *out)
+    {
+        if (!ok() || !fine_ || !out || !cloud || n <= 0 || stride < 3) return false;
+        *out = MapLocalizerResult();
+        const int n_starts = (int)(starts.size() / 16);
+        last.assign((size_t)LEVELS, std::vector<slam_vmap_gicp_result>((size_t)n_starts, slam_vmap_gicp_result()));
+        ran.assign((size_t)LEVELS, std::vector<char>((size_t)n_starts, 0));
+        int scan = -1;
+        if (slam_kf_add_keyframe(store_, cloud, n, stride, &scan) != SLAM_OK) return warn(), false;
+        std::vector<char> alive((size_t)n_starts, 1);
+        const bool        done = slam_kf_keyframe_info(store_, scan, &out->n_source, 0, 0, 0, 0) == SLAM_OK && descend(scan, starts, alive);
+        if (!done) warn();
+        if (slam_kf_remove_keyframe(store_, scan) != SLAM_OK) warn();
+        if (!done) return false;
+        int best = -1;
+        for (int i = 0; i < n_starts; ++i) {
+            const slam_vmap_gicp_result &r = last[0][(size_t)i];
+            if (!ran[0][(size_t)i] || !alive[(size_t)i] || !r.converged || !(r.fitness <= MAX_SCORE)) continue;
+            if (!((double)r.fitness_pairs >= MIN_PAIR_SHARE * (double)out->n_source)) continue;
+            if (best < 0 || r.fitness_pairs > last[0][(size_t)best].fitness_pairs) best = i;
+        }
+        if (best >= 0) {
+            const slam_vmap_gicp_result &w = last[0][(size_t)best];
+            out->found = true, out->index = best;
+            for (int k = 0; k < 16; ++k) out->transform[k] = w.transform[k], out->transform64[k] = w.transform64[k];
+            const float *T = w.transform;
+            out->x = (double)T[3], out->y = (double)T[7], out->theta = std::atan2((double)T[4], (double)T[0]);
+        }
+        return true;
+    }
+
+private:
+    void dropMap()
+    {
+        for (slam_vmap_t *m : coarse_) slam_vmap_destroy(m);
+        coarse_.clear();
+        if (owned_) slam_vmap_destroy(fine_);
+        fine_ = nullptr, owned_ = false;
+    }
+    bool take(slam_vmap_t *fine, bool owned)
+    {
+        if (!ok() || !fine) return false;
+        double                leaf = 0;
+        int                   dist = 0;
+        slam_vmap_dist_params dp;
+        if (slam_vmap_layout(fine, &leaf, nullptr, &dist, &dp) != SLAM_OK) return warn(), false;
+        if (!dist) return refuse("the map has no distributions");
+        if (!(std::ldexp(leaf, LEVELS - 1) <= 8.0)) return refuse("the coarsest level's leaf is more than the 8 m a map with distributions may have");
+        std::vector<slam_vmap_t *> coarse;
+        slam_vmap_t               *below = fine;
+        bool                       good = true;
+        for (int k = 1; k < LEVELS && good; ++k) {
+            slam_vmap_params vp;
+            slam_vmap_default_params(&vp);
+            vp.leaf = std::ldexp(leaf, k);
+            slam_vmap_t *m = nullptr;
+            good = slam_vmap_create(&vp, &m) == SLAM_OK;
+            if (m) coarse.push_back(m);
+            good = good && slam_vmap_enable_distributions(m, &dp) == SLAM_OK && slam_vmap_coarsen(m, below, nullptr) == SLAM_OK;
+            below = m;
+        }
+        if (!good) {
+            warn();
+            for (slam_vmap_t *m : coarse) slam_vmap_destroy(m);
+            return false;
+        }
+        dropMap();
+        fine_ = fine, owned_ = owned, coarse_ = coarse;
+        return true;
+    }
+    // the levels from the coarsest down: one call per level carries every live start
+    bool descend(int scan, const std::vector<float> &starts, std::vector<char> &alive)
+    {
+        const int          n_starts = (int)alive.size();
+        std::vector<float> T(starts.begin(), starts.begin() + 16 * (size_t)n_starts);
+        for (int k = LEVELS - 1; k >= 0; --k) {
+            std::vector<int>                ids;
+            std::vector<slam_vmap_gicp_req> req;
+            for (int i = 0; i < n_starts; ++i) {
+                if (!alive[(size_t)i]) continue;
+                slam_vmap_gicp_req rq;
+                rq.src = scan;
+                for (int c = 0; c < 16; ++c) rq.init[c] = T[16 * (size_t)i + c];
+                ids.push_back(i), req.push_back(rq);
+            }
+            if (ids.empty()) break;
+            double leaf = 0;
+            if (slam_vmap_layout(level(k), &leaf, nullptr, nullptr, nullptr) != SLAM_OK) return false;
+            slam_vmap_gicp_params gp;
+            slam_vmap_default_gicp_params(&gp);
+            gp.gate = GATE_RATIO * leaf, gp.max_iterations = MAX_ITERATIONS, gp.transformation_epsilon = TRANSFORMATION_EPSILON;
+            std::vector<slam_vmap_gicp_result> res(ids.size());
+            if (slam_vmap_register_gicp(level(k), store_, req.data(), (int)req.size(), &gp, res.data(), nullptr) != SLAM_OK) return false;
+            for (size_t e = 0; e < ids.size(); ++e) {
+                const size_t i = (size_t)ids[e];
+                last[(size_t)k][i] = res[e], ran[(size_t)k][i] = 1;
+                if (res[e].state == SLAM_KF_NO_CORRESPONDENCES || res[e].state == SLAM_KF_DEGENERATE) alive[i] = 0;
+                else
+                    for (int c = 0; c < 16; ++c) T[16 * i + c] = res[e].transform[c];
+            }
+        }
+        return true;
+    }
+    static bool refuse(const char *why)
+    {
+        std::fprintf(stderr, "MapLocalizer: %s\n", why);
+        return false;
+    }
+    static void warn() { detail::warn("MapLocalizer"); }
+
+    slam_kf_t                 *store_ = nullptr;
+    slam_vmap_t               *fine_ = nullptr;
+    bool                       owned_ = false;
+    std::vector<slam_vmap_t *> coarse_;
 };
 
 } // namespace slam_amd

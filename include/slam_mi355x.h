@@ -1114,6 +1114,20 @@ int  slam_vmap_save(slam_vmap_t *m, const char *path);
  * device as well), then asks for the device, creates a map of the file's leaf with room for its voxels at half load, enables
  * distributions with the file's parameters when it has moments, and absorbs the records in one call. */
 int  slam_vmap_load(const char *path, slam_vmap_t **out);
+/* Exact coarser levels (docs/VOXEL_MAP.md section 11).  Adds every voxel of `src` into the voxel of `dst` that contains it:
+ * dst's leaf must equal ldexp(src's leaf, j) bit for bit for some 1 <= j <= 8.  Per axis the parent cell is cell >> j (an
+ * arithmetic shift: cell -1 goes to -1), the parent key section 1's packing; count and the three sums add unchanged; the
+ * moments are re-centred on the parent's corner in int64: with o_k = cell_k - (parent_k << j) and s_k = o_k (L / 16),
+ * E'_k += E_k + n s_k and M'_kl += M_kl + s_k E_l + s_l E_k + n s_k s_l.  Because doubling a leaf is exact, the result holds
+ * the keys, counts, sums and moments of a map that integrated the same (cloud, transform) pairs at dst's leaf, provided src's
+ * leaf dropped none of their points.  dst may hold voxels already (coarsen adds, as absorb does); n_voxels grows by the slots
+ * claimed, n_points by the counts, the distributions become stale; src is unchanged.  Carve planes are not derived (seen and
+ * miss count scans, and a scan seen in two children is one scan of the parent): dst's, if it has any, are not touched.
+ * SLAM_E_INVALID before any launch for dst == src, any other pair of leaves (equal leaves are a merge), distributions on one
+ * side only, and moments on a src leaf that is no multiple of 2^-16 m (floor(d / 16) does not split).  Room is made by
+ * integrate's load rule with n = src's n_voxels, before the launch.  Waits as slam_vmap_merge does; both handles are busy for
+ * the call. */
+int  slam_vmap_coarsen(slam_vmap_t *dst, slam_vmap_t *src, slam_stream_t stream);
 
 /* -------------------------------------------------------------------------
  * Pose-graph optimiser: graph_slam's optimizeGraph (graph_slam.cpp:322-390), i.e. g2o's VertexSE3 / EdgeSE3 under

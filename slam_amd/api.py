@@ -240,6 +240,7 @@ EXPORTS = [
     "slam_vmap_default_dist_params", "slam_vmap_enable_distributions", "slam_vmap_read_moments", "slam_vmap_compute_distributions",
     "slam_vmap_read_distributions", "slam_vmap_default_gicp_params", "slam_vmap_register_gicp", "slam_vmap_register_gicp_traced",
     "slam_vmap_layout", "slam_vmap_absorb_dev", "slam_vmap_absorb", "slam_vmap_merge", "slam_vmap_save", "slam_vmap_load",
+    "slam_vmap_coarsen",
     "slam_pgo_default_params", "slam_pgo_create", "slam_pgo_destroy", "slam_pgo_clear", "slam_pgo_add_vertex",
     "slam_pgo_set_vertex", "slam_pgo_add_edge", "slam_pgo_size", "slam_pgo_optimize", "slam_pgo_read_vertices", "slam_pgo_chi2",
     "slam_pgo_read_system", "slam_pgo_step",
@@ -497,6 +498,7 @@ def lib():
     L.slam_vmap_merge.argtypes = [_vp, _vp, C.POINTER(C.c_int64), _vp]
     L.slam_vmap_save.argtypes = [_vp, C.c_char_p]
     L.slam_vmap_load.argtypes = [C.c_char_p, C.POINTER(_vp)]
+    L.slam_vmap_coarsen.argtypes = [_vp, _vp, _vp]
     _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
     L.slam_pgo_default_params.argtypes = [C.POINTER(PgoParams)]
     L.slam_pgo_default_params.restype = None
@@ -1392,6 +1394,13 @@ class VoxelMap:
         check(lib().slam_vmap_merge(self.h, other.h, C.byref(rej), _sp(stream)))
         return rej.value
 
+    def coarsen(self, src, stream=None):
+        """slam_vmap_coarsen: every voxel of the finer map `src` (this map's leaf is src's times 2, 4 .. 256, bit for bit;
+        distributions on both or neither) added into the voxel of this map that contains it, the moments re-centred in
+        integers: the bits of a map that integrated src's clouds at this leaf (docs/VOXEL_MAP.md section 11).  `src` is
+        unchanged; carve planes are not derived."""
+        check(lib().slam_vmap_coarsen(self.h, src.h, _sp(stream)))
+
     def save(self, path):
         """slam_vmap_save: the map's accumulators into the file of section 10.4; the bytes depend on the contents alone."""
         check(lib().slam_vmap_save(self.h, os.fsencode(path)))
@@ -2047,6 +2056,154 @@ class GlobalMapBuilder:
             return True, r
         finally:
             self.store.remove_keyframe(scan)
+
+
+class MapLocalizer:
+    """Relocalises a scan in a voxel map with distributions by registering a set of starts down the map's own exact coarser
+    levels, one slam_vmap_register_gicp call per level (docs/VOXEL_MAP.md section 11.3): the same behaviour as
+    slam_amd::MapLocalizer of include/slam_amd/global_match.hpp, member for member.  Level k is a map of leaf
+    ldexp(leaf, k) filled by slam_vmap_coarsen from level k - 1; level 0 is the map itself.  No random numbers.  An error
+    of the library and a map the localiser cannot take raise SlamError here (C++ prints and returns false); the scan
+    keyframe is removed on every way out."""
+
+    # read at every call: set on the instance to change
+    GATE_RATIO, N_YAW, MIN_PAIR_SHARE = 2.0, 8, 0.5
+    MAX_SCORE = 0.03        # between the two level-0 fitness populations of section 11.3: sqrt(0.00745 * 0.0964)
+
+    def __init__(self, levels=4, leaf=0.30):
+        # fixed at construction: the number of levels, and the store with the builder's leaf and epsilons
+        self._fixed = dict(LEVELS=int(levels), LEAF_SIZE=float(leaf), MAX_ITERATIONS=100, TRANSFORMATION_EPSILON=1e-6, FITNESS_EPSILON=1e-6)
+        if self.LEVELS < 1:
+            raise SlamError(E_INVALID, "MapLocalizer: LEVELS must be at least 1")
+        self.store = KeyframeStore(leaf_size=self.LEAF_SIZE, gate=2.0, transformation_epsilon=self.TRANSFORMATION_EPSILON,
+                                   fitness_epsilon=self.FITNESS_EPSILON)
+        self.store.set_gicp_params(max_iterations=self.MAX_ITERATIONS, transformation_epsilon=self.TRANSFORMATION_EPSILON)
+        self.fine, self.owned = None, False
+        self.coarse = []        # levels 1 .. LEVELS - 1, owned
+        self.last, self.n_source = [], 0
+
+    LEVELS = property(lambda self: self._fixed["LEVELS"])
+    LEAF_SIZE = property(lambda self: self._fixed["LEAF_SIZE"])
+    MAX_ITERATIONS = property(lambda self: self._fixed["MAX_ITERATIONS"])
+    TRANSFORMATION_EPSILON = property(lambda self: self._fixed["TRANSFORMATION_EPSILON"])
+    FITNESS_EPSILON = property(lambda self: self._fixed["FITNESS_EPSILON"])
+
+    def _drop_map(self):
+        for m in self.coarse:
+            m.close()
+        self.coarse = []
+        if self.owned and self.fine is not None:
+            self.fine.close()
+        self.fine, self.owned = None, False
+
+    def close(self):
+        self._drop_map()
+        self.store.close()
+
+    def level(self, k):
+        """the map of level k: 0 is the fine map, k >= 1 the derived ones"""
+        return self.fine if k == 0 else self.coarse[k - 1]
+
+    def _take(self, fine, owned):
+        lay = fine.layout()
+        if not lay["distributions"]:
+            raise SlamError(E_INVALID, "MapLocalizer: the map has no distributions")
+        if not math.ldexp(lay["leaf"], self.LEVELS - 1) <= 8.0:
+            raise SlamError(E_INVALID, "MapLocalizer: leaf %g times 2^%d is more than the 8 m a map with distributions may have"
+                            % (lay["leaf"], self.LEVELS - 1))
+        coarse = []
+        try:
+            below = fine
+            for k in range(1, self.LEVELS):
+                m = VoxelMap(leaf=math.ldexp(lay["leaf"], k))
+                coarse.append(m)
+                m.enable_distributions(params=lay["dist_params"])
+                m.coarsen(below)
+                below = m
+        except SlamError:
+            for m in coarse:
+                m.close()
+            raise
+        self._drop_map()
+        self.fine, self.owned, self.coarse = fine, owned, coarse
+
+    def set_map(self, fine):
+        """The fine map (a VoxelMap with distributions, borrowed: the caller keeps and closes it) and its derived levels."""
+        self._take(fine, False)
+
+    def load(self, path):
+        """The fine map from a file of slam_vmap_save (owned) and its derived levels."""
+        fine = VoxelMap.load(path)
+        try:
+            self._take(fine, True)
+        except SlamError:
+            fine.close()
+            raise
+
+    def rebuild(self):
+        """Clears and refills the derived levels, after the fine map has grown."""
+        if self.fine is None:
+            raise SlamError(E_INVALID, "MapLocalizer.rebuild: no map")
+        below = self.fine
+        for m in self.coarse:
+            m.clear()
+            m.coarsen(below)
+            below = m
+
+    @staticmethod
+    def yaw_fan(x, y, yaw, n):
+        """n planar starts at (x, y) with yaws (float)((double) yaw + 2 pi k / n), each GlobalMatcher.planar's matrix."""
+        return [GlobalMatcher.planar(np.float32(x), np.float32(y), np.float32(float(np.float32(yaw)) + 2.0 * math.pi * k / n))
+                for k in range(int(n))]
+
+    def localize(self, cloud, starts=None, x=0.0, y=0.0, yaw=0.0):
+        """One scan ([n, >= 3] f32, sensor frame) from `starts` (4 x 4 f32 each; None: yaw_fan(x, y, yaw, N_YAW)).  From the
+        coarsest level down one register_gicp call carries every live start, gated at GATE_RATIO times the level's leaf, from
+        the level above's f32 transform; a start that ends a level without pairs or degenerate is out.  The winner among the
+        level-0 results that converged with fitness <= MAX_SCORE and fitness_pairs >= MIN_PAIR_SHARE n_source has the most
+        fitness_pairs, then the lowest index.  A dict of found, index (-1: nobody), transform, transform64, x, y, theta (of
+        the f32 transform, as GlobalMatcher fills its edge), n_source and last[level][start] (None where a start was out)."""
+        if self.fine is None:
+            raise SlamError(E_INVALID, "MapLocalizer.localize: no map")
+        if starts is None:
+            starts = self.yaw_fan(x, y, yaw, self.N_YAW)
+        T = [np.array(s, np.float32).reshape(4, 4) for s in starts]
+        scan = self.store.add_keyframe(cloud)
+        try:
+            self.n_source = self.store.info(scan)["n_points"]
+            alive = [True] * len(T)
+            self.last = [[None] * len(T) for _ in range(self.LEVELS)]
+            for k in range(self.LEVELS - 1, -1, -1):
+                ids = [i for i in range(len(T)) if alive[i]]
+                if not ids:
+                    break
+                m = self.level(k)
+                res = m.register_gicp(self.store, [(scan, T[i]) for i in ids], gate=self.GATE_RATIO * m.params.leaf,
+                                      max_iterations=self.MAX_ITERATIONS, transformation_epsilon=self.TRANSFORMATION_EPSILON)
+                for i, r in zip(ids, res):
+                    self.last[k][i] = r
+                    if r["state"] in (KF_NO_CORRESPONDENCES, KF_DEGENERATE):
+                        alive[i] = False
+                    else:
+                        T[i] = r["transform"]
+        finally:
+            self.store.remove_keyframe(scan)
+        best = -1
+        for i, r in enumerate(self.last[0]):
+            if r is None or not alive[i] or not r["converged"] or not r["fitness"] <= self.MAX_SCORE:
+                continue
+            if not r["fitness_pairs"] >= self.MIN_PAIR_SHARE * self.n_source:
+                continue
+            if best < 0 or r["fitness_pairs"] > self.last[0][best]["fitness_pairs"]:
+                best = i
+        out = dict(found=best >= 0, index=best, transform=None, transform64=None, x=0.0, y=0.0, theta=0.0, n_source=self.n_source,
+                   last=self.last)
+        if best >= 0:
+            w = self.last[0][best]
+            Tw = w["transform"]
+            out.update(transform=Tw, transform64=w["transform64"], x=float(Tw[0, 3]), y=float(Tw[1, 3]),
+                       theta=math.atan2(float(Tw[1, 0]), float(Tw[0, 0])))
+        return out
 
 
 def kf_gicp_result_dict(r):

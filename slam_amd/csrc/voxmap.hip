@@ -30,6 +30,9 @@
 //              the nine moments): validate, find or claim as integrate does, integer atomicAdds.  The records are packed
 //              arrays (a file, a caller) or another table's planes (merge: one lane per source slot, empty slots leave at
 //              once); one body serves both.  Load is this fed from vmap_file.hpp's parser, merge from another handle.
+//   coarsen    (docs/VOXEL_MAP.md section 11) one lane per slot of a finer map: the parent cell is the cell shifted right, count
+//              and sums add unchanged, the moments are re-centred on the parent's corner in integers; find or claim and
+//              integer atomicAdds as absorb.  The result is the bits of a map integrated at the coarser leaf.
 // The hash is the 64-bit finaliser of MurmurHash3 (fmix64: two multiply-xorshift rounds), masked to the table: neighbouring
 // cells differ in the low bits of one 21-bit field, and fmix64 spreads any one-bit difference over the whole word.
 // The probe loop ends after `capacity` slots and then raises the handle's error word; the host keeps the load at one half
@@ -590,6 +593,61 @@ __global__ __launch_bounds__(256) void vmap_absorb_kernel(Records S, uint64_t n,
                     }
                     points = c;
                 }
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) points += __shfl_xor(points, o);
+    if ((threadIdx.x & 63) == 0 && points) atomicAdd(reinterpret_cast<unsigned long long *>(ctr + kPoints), points);
+}
+
+// ---------------------------------------------------------------- coarsen (docs/VOXEL_MAP.md section 11)
+// One lane per slot of the finer table S; an empty slot leaves at once.  The parent cell is cell >> shift per axis (arithmetic:
+// it floors), its key section 1's packing, always valid.  count and the sums add unchanged.  With moments (SQ.E[0] set; the
+// host launches those only onto a map that has the planes Q) they are re-centred on the parent's corner in int64:
+// s_k = o_k unit with o_k = cell_k - (parent_k << shift) and unit = L / 16 of the finer map, E'_k = E_k + n s_k and
+// M'_kl = M_kl + s_k E_l + s_l E_k + n s_k s_l.  No floating point; nothing waits for another lane; the probe is
+// find_or_claim's, bounded by the capacity; ctr is absorb's block, used as absorb uses it.
+__global__ __launch_bounds__(256) void vmap_coarsen_kernel(Table S, Moments SQ, int shift, long long unit, Table T, Moments Q, uint32_t *ctr)
+{
+    const uint64_t     i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    unsigned long long points = 0;
+    if (i <= S.mask) {
+        const uint64_t key = S.key[i];
+        if (key != kEmpty) {
+            uint64_t  parent = 0;
+            long long s[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int cell = (int)((key >> (21 * k)) & 0x1fffffull) - kCellLimit;
+                const int up = cell >> shift; // arithmetic: floor
+                parent |= (uint64_t)(up + kCellLimit) << (21 * k);
+                s[k] = (long long)(cell - up * (1 << shift)) * unit;
+            }
+            const long long h = find_or_claim(T, parent, &ctr[kClaimed]);
+            if (h < 0) {
+                atomicExch(&ctr[kError], 1u);
+            } else {
+                const uint32_t c = S.count[i];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) atomicAdd(&T.sum[k][h], S.sum[k][i]);
+                atomicAdd(&T.count[h], c);
+                if (SQ.E[0]) {
+                    const long long n = (long long)c;
+                    long long       E[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        E[k] = (long long)SQ.E[k][i];
+                        atomicAdd(&Q.E[k][h], (unsigned long long)(E[k] + n * s[k]));
+                    }
+                    int m = 0;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+#pragma unroll
+                        for (int l = k; l < 3; ++l, ++m)
+                            atomicAdd(&Q.M[m][h], (unsigned long long)((long long)SQ.M[m][i] + s[k] * E[l] + s[l] * E[k] + n * s[k] * s[l]));
+                }
+                points = c;
             }
         }
     }
@@ -1403,6 +1461,46 @@ int slam_vmap_merge(slam_vmap_t *dst, slam_vmap_t *src, int64_t *n_rejected, sla
     }
     S.w3 = S.w6 = 1, S.slots = 1;
     return absorb_records(dst, S, (uint64_t)src->capacity, src->n_voxels, n_rejected, as_stream(stream));
+}
+
+// ---------------------------------------------------------------- coarsen (docs/VOXEL_MAP.md section 11)
+int slam_vmap_coarsen(slam_vmap_t *dst, slam_vmap_t *src, slam_stream_t stream)
+{
+    SLAM_REQUIRE(dst != src || !dst, SLAM_E_INVALID, "slam_vmap_coarsen: a map cannot be coarsened into itself");
+    SLAM_TRY(require_device());
+    SLAM_REQUIRE(dst && src, SLAM_E_INVALID, "slam_vmap_coarsen: a map is NULL");
+    int shift = 0;
+    for (int j = 1; j <= 8 && !shift; ++j) {
+        const double up = std::ldexp(src->P.leaf, j);
+        if (std::memcmp(&dst->P.leaf, &up, sizeof(double)) == 0) shift = j;
+    }
+    SLAM_REQUIRE(shift, SLAM_E_INVALID, "slam_vmap_coarsen: leaf %.17g is not leaf %.17g times 2, 4 .. 256: the finer cells do not nest in the coarser",
+                 dst->P.leaf, src->P.leaf);
+    SLAM_REQUIRE(dst->dist_on == src->dist_on, SLAM_E_INVALID, "slam_vmap_coarsen: distributions on one side only");
+    const double fine = std::ldexp(src->P.leaf, 16); // the leaf in units of 2^-16 m
+    SLAM_REQUIRE(!src->dist_on || fine == std::floor(fine), SLAM_E_INVALID,
+                 "slam_vmap_coarsen: leaf %.17g is no multiple of 2^-16 m: the moments' floor(d / 16) does not split over the finer cells", src->P.leaf);
+    if (src->n_voxels == 0) return SLAM_OK;
+    hipStream_t st = as_stream(stream);
+    SLAM_TRY(make_room(dst, src->n_voxels, st));
+    if (!dst->actr.p) SLAM_TRY(dst->actr.alloc(kAbsorbCounters * sizeof(uint32_t)));
+    uint32_t *h = static_cast<uint32_t *>(pinned_scratch(kAbsorbCounters * sizeof(uint32_t)));
+    SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
+    SLAM_HIP(hipMemsetAsync(dst->actr.p, 0, kAbsorbCounters * sizeof(uint32_t), st));
+    const Moments SQ = src->dist_on ? src->moments() : Moments{};
+    const Moments Q = dst->dist_on ? dst->moments() : Moments{};
+    const long long unit = src->dist_on ? (long long)fine : 0; // L / 16: L = leaf 2^20 exactly here
+    hipLaunchKernelGGL(vmap_coarsen_kernel, dim3(blocks_for((uint64_t)src->capacity)), dim3(256), 0, st, src->view(), SQ, shift, unit, dst->view(), Q,
+                       dst->actr.as<uint32_t>());
+    SLAM_HIP(hipGetLastError());
+    dst->dist_stale = true;
+    SLAM_HIP(hipMemcpyAsync(h, dst->actr.p, kAbsorbCounters * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SLAM_HIP(hipStreamSynchronize(st));
+    dst->n_voxels += h[kClaimed];
+    dst->n_points += (int64_t)((uint64_t)h[kPoints] | (uint64_t)h[kPoints + 1] << 32);
+    SLAM_REQUIRE(!h[kError], SLAM_E_HIP, "slam_vmap_coarsen: a probe ran through all %lld slots (%lld voxels): voxels were lost",
+                 (long long)dst->capacity, (long long)dst->n_voxels);
+    return SLAM_OK;
 }
 
 int slam_vmap_save(slam_vmap_t *m, const char *path)
