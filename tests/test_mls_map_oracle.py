@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import mls_map_oracle as MO
+from mls_store_cases import params
 from slam_amd import api, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,17 +30,6 @@ def make(request):
         if request.param == "device":
             m.check("end")
         m.close()
-
-
-def params(**kw):
-    p = api.MlsParams()
-    d = dict(max_range=75.0, update_dist=-1, max_clusters=50, max_cluster_points=200, min_cluster_points=10,
-             normal_threshold=0.15, height_threshold=0.4, cluster_sigma_factor=3.0, cluster_dist_threshold=0.5,
-             cluster_combine_dist=0.2, drive_dist_threshold=1.0, robot_height=1.45)
-    d.update(kw)
-    for k, v in d.items():
-        setattr(p, k, v)
-    return p
 
 
 def column(cx, cy, zs):
@@ -140,6 +130,82 @@ def test_out_of_window_closure_chain(make):
     for x in (11, 12, 13, 14):
         assert cell(m, x, 5)[1:] == (1, 0, 0, 0), x
     assert cell(m, 16, 5)[1:] == (-1, 0, 1, 12)
+
+
+# The walks below start in the window x 8..11, y 3..6 of pose (0, -5) with update_dist 2.  A cell's neighbours come in
+# the order (x-1, y-1), (x-1, y), (x-1, y+1), (x, y-1), (x, y+1), (x+1, y-1), (x+1, y), (x+1, y+1) (mls.cpp:308-309).
+
+def test_walk_that_waited_compares_with_the_neighbour_it_waited_for(make):
+    m = make(S, S, 1.0, params(update_dist=2))
+    # (11, 5) at 1.0 waits for (12, 5) outside the window; once that is updated it lies 1.0 > height_threshold lower
+    m.add_cloud(np.concatenate([column(11, 5, [1.0] * 12), column(12, 5, [0.0] * 12)]), (0.0, -5.0))
+    assert cell(m, 11, 5)[1:] == (0, 100, 0, 0)
+    assert cell(m, 12, 5)[1:] == (1, 0, 0, 0)              # its own walk: (11, 5) is higher, which passes
+    # the other way round: the neighbour is the higher one, and gets 100 through its own walk
+    m = make(S, S, 1.0, params(update_dist=2))
+    m.add_cloud(np.concatenate([column(11, 5, [0.0] * 12), column(12, 5, [1.0] * 12)]), (0.0, -5.0))
+    assert cell(m, 11, 5)[1:] == (1, 0, 0, 0)
+    assert cell(m, 12, 5)[1:] == (0, 100, 0, 0)
+
+
+def test_early_return_leaves_a_later_neighbour_flagged(make):
+    m = make(S, S, 1.0, params(update_dist=2))
+    # (11, 5) at 1.0 returns at its second neighbour (10, 5), 1.0 lower, and never looks at (12, 5), its seventh
+    m.add_cloud(np.concatenate([column(10, 5, [0.0] * 12), column(11, 5, [1.0] * 12), column(12, 5, [0.0] * 12)]), (0.0, -5.0))
+    assert cell(m, 10, 5)[1:] == (1, 0, 0, 0)
+    assert cell(m, 11, 5)[1:] == (0, 100, 0, 0)
+    cl, drv, byte, upd, pend = cell(m, 12, 5)
+    assert len(cl) == 0 and (drv, byte, upd, pend) == (-1, 0, 1, 12)
+
+
+def test_claimed_cell_without_ground_is_passed(make):
+    m = make(S, S, 1.0, params(update_dist=2))
+    # (12, 5) is claimed for (11, 5)'s walk, but its 5 points make no ground cluster: the flag clears, the points stay,
+    # and the walk goes on to (12, 6), which is claimed next and turns out 1.0 lower
+    m.add_cloud(np.concatenate([column(11, 5, [0.0] * 12), column(12, 5, [0.0] * 5), column(12, 6, [-1.0] * 12)]), (0.0, -5.0))
+    cl, drv, byte, upd, pend = cell(m, 12, 5)
+    assert cl[:, 2:].tolist() == [[0.0, 0.001, 5.0]] and (drv, byte, upd, pend) == (-1, 0, 0, 5)
+    assert cell(m, 11, 5)[1:] == (0, 100, 0, 0)
+    assert cell(m, 12, 6)[1:] == (1, 0, 0, 0)
+    # seven more points in the next call: the five are replayed ahead of them, the cluster reaches 5 + 5 + 7 and is
+    # ground now -- and (12, 6) lies 1.0 below it
+    m.add_cloud(column(12, 5, [0.0] * 7), (2.0, -5.0))     # window x 10..13: (12, 5) is inside
+    cl, drv, byte, upd, pend = cell(m, 12, 5)
+    assert cl[:, 2:].tolist() == [[0.0, 0.001, 17.0]] and (drv, byte, upd, pend) == (0, 100, 0, 0)
+
+
+def test_chain_reaches_a_flag_raised_a_call_earlier(make):
+    m = make(S, S, 1.0, params(update_dist=2))
+    m.add_cloud(np.concatenate([column(x, 5, [0.0] * 12) for x in (11, 12, 13, 14, 16)]), (0.0, -5.0))
+    assert cell(m, 16, 5)[1:] == (-1, 0, 1, 12)             # test_out_of_window_closure_chain
+    # Points for (15, 5) only.  A chain starts at a flagged cell of the window, so the window moves to x 12..15:
+    # (15, 5) is its last column, and its walk meets (16, 5), flagged by the first call, whose points are carried ones
+    m.add_cloud(column(15, 5, [0.0] * 12), (4.0, -5.0))
+    assert cell(m, 15, 5)[1:] == (1, 0, 0, 0)
+    cl, drv, byte, upd, pend = cell(m, 16, 5)
+    assert cl[:, 2:].tolist() == [[0.0, 0.001, 12.0]] and (drv, byte, upd, pend) == (1, 0, 0, 0)
+
+
+def pending_total(m):
+    return int(m.read_cells(np.arange(S * S), clusters=False)["pending"].sum())
+
+
+def test_window_moved_over_pending_cells_and_an_empty_cloud(make):
+    m = make(S, S, 1.0, params(update_dist=2))
+    where = [(15, 12), (15, 13), (16, 12), (16, 13)]
+    cloud = np.concatenate([column(x, y, [0.0] * 12) for x, y in where] + [column(14, 11, [0.0] * 5)])
+    m.add_cloud(cloud, (0.0, -5.0))                         # wholly outside x 8..11, y 3..6, and next to nothing in it
+    for x, y in where:
+        assert cell(m, x, y)[1:] == (-1, 0, 1, 12)
+    assert pending_total(m) == 4 * 12 + 5
+    m.add_cloud(np.zeros((0, 3), np.float32), (5.0, 2.0))   # window x 13..16, y 10..13, no new point
+    for x, y in where:
+        assert cell(m, x, y)[1:] == (1, 0, 0, 0)
+    cl, drv, byte, upd, pend = cell(m, 14, 11)              # processed, no ground: its five points stay
+    assert cl[:, 2:].tolist() == [[0.0, 0.001, 5.0]] and (drv, byte, upd, pend) == (-1, 0, 0, 5)
+    assert pending_total(m) == 5
+    if hasattr(m, "dev"):
+        assert m.dev.info()["pending_points"] == 5
 
 
 # ---------------------------------------------------------------- C-ABI without a GPU
