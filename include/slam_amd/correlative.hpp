@@ -10,6 +10,7 @@
 // Conventions of icp.hpp: a failed construction logs and leaves an unusable object; match() is synchronous and leaves R, t
 // alone where it cannot answer (fewer than 5 scene points).
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 
@@ -17,6 +18,49 @@
 #include "slam_mi355x.h"
 
 namespace slam_amd {
+
+// The posterior of a match (slam_csm_posterior, docs/CSM.md section 6) with what a consumer asks of it.  Index 0 is x, 1 is
+// y, 2 is theta; matrices are 3 x 3 row-major.
+struct Posterior {
+    slam_csm_posterior p = {};
+    double             u[3] = {0.0, 0.0, 0.0}; // resolution, resolution, theta_step
+    int                score = 0, n_points = 0; // of the match
+
+    // floor: u_i^2 / 12 on the diagonal -- the matcher cannot know a pose better than one cell
+    void covariance(double out[9], bool floor = true) const
+    {
+        const double *c = p.cov;
+        const double  m[9] = {c[0], c[1], c[2], c[1], c[3], c[4], c[2], c[4], c[5]};
+        for (int i = 0; i < 9; ++i) out[i] = m[i];
+        if (floor)
+            for (int i = 0; i < 3; ++i) {
+                const double uu = u[i] * u[i];
+                out[4 * i] = out[4 * i] + uu / 12.0;
+            }
+    }
+    // the inverse of the floored covariance by the symmetric adjugate; false: the determinant is not positive and finite
+    bool information(double out[9]) const
+    {
+        double m[9];
+        covariance(m, true);
+        const double a = m[0], b = m[1], c = m[2], d = m[4], e = m[5], f = m[8];
+        const double de = d * f, ee = e * e, ce = c * e, bf = b * f, be = b * e, cd = c * d;
+        const double af = a * f, cc = c * c, bc = b * c, ae = a * e, ad = a * d, bb = b * b;
+        const double A = de - ee, B = ce - bf, C = be - cd, D = af - cc, E = bc - ae, F = ad - bb;
+        const double aA = a * A, bB = b * B, cC = c * C;
+        const double s = aA + bB, det = s + cC;
+        if (!(det > 0.0 && std::isfinite(det))) return false;
+        out[0] = A / det, out[1] = B / det, out[2] = C / det;
+        out[3] = B / det, out[4] = D / det, out[5] = E / det;
+        out[6] = C / det, out[7] = E / det, out[8] = F / det;
+        return true;
+    }
+    // a second, separate pose scores within max_deficit_per_point * n_points of the winner
+    bool ambiguous(int max_deficit_per_point) const
+    {
+        return p.valid && p.second_score >= 0 && score - p.second_score <= max_deficit_per_point * n_points;
+    }
+};
 
 class CorrelativeMatcher {
 public:
@@ -55,6 +99,36 @@ public:
             std::fprintf(stderr, "%s\n", slam_last_error());
             return -1.0;
         }
+        R.val[0][0] = Rr[0];
+        R.val[0][1] = Rr[1];
+        R.val[1][0] = Rr[2];
+        R.val[1][1] = Rr[3];
+        t.val[0][0] = tt[0];
+        t.val[1][0] = tt[1];
+        return last_.max_score > 0 ? (double)last_.score / (double)last_.max_score : 0.0;
+    }
+    // the posterior parameters (nullptr: the defaults); matchPosterior needs it first
+    bool setPosterior(const slam_csm_post_params *params = nullptr)
+    {
+        slam_csm_post_params p;
+        slam_csm_default_post_params(&p);
+        if (params) p = *params;
+        return h_ && slam_csm_set_post_params(h_, &p) == SLAM_OK;
+    }
+    bool setPosterior(const slam_csm_post_params &params) { return setPosterior(&params); }
+    // match() with the posterior of its answer
+    double matchPosterior(double *T_GA, double *T_NGA, const int32_t T_GA_num, const int32_t T_NGA_num, Matrix &R, Matrix &t, Posterior &post)
+    {
+        slam_csm_params P;
+        if (!h_ || slam_csm_info(h_, &P, nullptr, nullptr, nullptr, nullptr) != SLAM_OK) return -1.0;
+        double Rr[4] = {R.val[0][0], R.val[0][1], R.val[1][0], R.val[1][1]};
+        double tt[2] = {t.val[0][0], t.val[1][0]};
+        if (slam_csm_match_post(h_, T_GA, T_GA_num, T_NGA, T_NGA_num, Rr, tt, &last_, &post.p) != SLAM_OK) {
+            std::fprintf(stderr, "%s\n", slam_last_error());
+            return -1.0;
+        }
+        post.u[0] = post.u[1] = P.resolution, post.u[2] = P.theta_step;
+        post.score = last_.score, post.n_points = last_.n_points;
         R.val[0][0] = Rr[0];
         R.val[0][1] = Rr[1];
         R.val[1][0] = Rr[2];

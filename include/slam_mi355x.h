@@ -895,6 +895,47 @@ int  slam_csm_read_table(slam_csm_t *csm, int cls, int level, int *origin_x, int
 /* the parameters in force (kernel_cells resolved), N_theta N_x N_y and blocks per axis in dims[5], bytes of tables and scratch */
 int  slam_csm_info(slam_csm_t *csm, slam_csm_params *params, int dims[5], size_t *table_bytes, size_t *scratch_bytes, int *max_scans);
 
+/* The match's posterior (docs/CSM.md section 6): every candidate whose score lies within a margin M of the winner's S* is
+ * weighted by a table of exp(-beta d / M) in 16.16 fixed point, and the weights' integer moments about the winner give a
+ * mean offset and a 3 x 3 covariance (index 0 = x, 1 = y, 2 = theta); the best candidate outside an exclusion box around
+ * the winner is the second mode.  The set is enumerated exactly from the bound table (a block with U < S* - M holds no
+ * member), the sums are int64, so the device equals tests/csm_post_oracle.py bit for bit in any order of evaluation. */
+typedef struct {
+    int    margin_per_point; /* M = margin_per_point * n_points, 0 .. 255 (16) */
+    double beta;             /* the weight at deficit d is exp(-beta d / M); finite, 0 .. 64 (8.0) */
+    int    excl_xy;          /* the second mode lies more than excl_xy cells off the winner along x or y ... (2) */
+    int    excl_theta;       /* ... or more than excl_theta angular steps (2) */
+} slam_csm_post_params;
+
+typedef struct {
+    int     valid;            /* 0 = scan of fewer than 5 points: everything else 0, second_score -1 */
+    int     n_within;         /* candidates with S >= S* - M */
+    int     margin;           /* M */
+    int     blocks_evaluated; /* blocks evaluated at full resolution by the posterior pass (all of them with exhaustive = 1) */
+    int     second_score;     /* the second mode: its score, -1 = none; the lowest flat index among equals */
+    int     second_k, second_a, second_b;
+    int64_t m0, m1[3], m2[6]; /* sums of w, w o_i, w o_i o_j over the set; o = (a - a*, b - b*, k - k*); m2: xx xy xt yy yt tt */
+    double  mean[3];          /* the weighted mean's offset from the winner's pose: metres, metres, radians */
+    double  cov[6];           /* xx xy xt yy yt tt in those units; no floor for the lattice's pitch (the adapters add it) */
+} slam_csm_posterior;
+
+void slam_csm_default_post_params(slam_csm_post_params *p);
+/* Computes and uploads the 257 weights wtab[j] = rint(65536 exp(-(beta j) / 256)) (host libm, as the stamp) and sizes the
+ * per-scan posterior scratch, which slam_csm_reserve sizes from then on as well.  May wait. */
+int  slam_csm_set_post_params(slam_csm_t *csm, const slam_csm_post_params *p);
+/* The table in force, 257 entries (cap >= 257); SLAM_E_INVALID before slam_csm_set_post_params. */
+int  slam_csm_read_post_table(slam_csm_t *csm, uint32_t *wtab, int cap);
+/* slam_csm_match_batch_dev (the same bits in d_R, d_t, d_result), then d_post[s] for every scan.  d_R may be d_R0, but d_t
+ * may not be d_t0: the posterior pass reads the start translations again.  Asynchronous; allocates, frees and waits for
+ * nothing.  SLAM_E_INVALID before slam_csm_set_post_params, beyond the reserved number of scans, and for
+ * a window with 65536 (max(N_x, N_y, N_theta) - 1)^2 N_x N_y N_theta >= 2^63 (the int64 sums could overflow). */
+int  slam_csm_match_post_batch_dev(slam_csm_t *csm, const double *d_pts, const int32_t *d_scan_off, const int32_t *d_scan_nga,
+                                   int n_scans, const double *d_R0, const double *d_t0, const double *d_cs, double *d_R, double *d_t,
+                                   slam_csm_result *d_result, slam_csm_posterior *d_post, slam_stream_t stream);
+/* slam_csm_match with the posterior of its answer. */
+int  slam_csm_match_post(slam_csm_t *csm, const double *t_ga, int n_tga, const double *t_nga, int n_tnga, double R[4], double t[2],
+                         slam_csm_result *result, slam_csm_posterior *post);
+
 /* -------------------------------------------------------------------------
  * Exact sparse voxel map: the growing prior map of global_generate.cpp (the reference keeps it as a point cloud that is
  * voxel-filtered again every round, global_generate.cpp:122-232).  Clouds are integrated in place into an open-addressing

@@ -120,6 +120,47 @@ class CsmResult(C.Structure):
                 ("n_points", C.c_int), ("blocks_evaluated", C.c_int)]
 
 
+class CsmPostParams(C.Structure):
+    _fields_ = [("margin_per_point", C.c_int), ("beta", C.c_double), ("excl_xy", C.c_int), ("excl_theta", C.c_int)]
+
+
+class CsmPosterior(C.Structure):
+    """slam_csm_posterior (docs/CSM.md section 6).  The helpers mirror slam_amd::Posterior of correlative.hpp operation for
+    operation; `u` is (resolution, resolution, theta_step), which CorrelativeMatcher.match_post fills in."""
+    _fields_ = [("valid", C.c_int), ("n_within", C.c_int), ("margin", C.c_int), ("blocks_evaluated", C.c_int),
+                ("second_score", C.c_int), ("second_k", C.c_int), ("second_a", C.c_int), ("second_b", C.c_int),
+                ("m0", C.c_int64), ("m1", C.c_int64 * 3), ("m2", C.c_int64 * 6), ("mean", C.c_double * 3),
+                ("cov", C.c_double * 6)]
+    u = (0.0, 0.0, 0.0)
+    score = n_points = 0
+
+    def covariance(self, floor=True):
+        """3 x 3, row-major x y theta; floor: u_i^2 / 12 on the diagonal, a pose is not known better than one cell"""
+        c = self.cov
+        out = np.array([c[0], c[1], c[2], c[1], c[3], c[4], c[2], c[4], c[5]], np.float64)
+        if floor:
+            for i in range(3):
+                out[4 * i] = out[4 * i] + (np.float64(self.u[i]) * np.float64(self.u[i])) / np.float64(12.0)
+        return out.reshape(3, 3)
+
+    def information(self):
+        """the inverse of the floored covariance by the symmetric adjugate, or None when the determinant is not positive
+        and finite"""
+        m = self.covariance(True).reshape(9)
+        a, b, c, d, e, f = (np.float64(m[i]) for i in (0, 1, 2, 4, 5, 8))
+        A, B, Cc = d * f - e * e, c * e - b * f, b * e - c * d
+        D, E, F = a * f - c * c, b * c - a * e, a * d - b * b
+        det = (a * A + b * B) + c * Cc
+        if not (det > 0.0 and np.isfinite(det)):
+            return None
+        return np.array([A / det, B / det, Cc / det, B / det, D / det, E / det, Cc / det, E / det, F / det]).reshape(3, 3)
+
+    def ambiguous(self, max_deficit_per_point):
+        """a second, separate pose scores within max_deficit_per_point * n_points of the winner"""
+        return bool(self.valid and self.second_score >= 0 and
+                    self.score - self.second_score <= int(max_deficit_per_point) * self.n_points)
+
+
 class VmapParams(C.Structure):
     _fields_ = [("leaf", C.c_double), ("initial_capacity", C.c_int)]
 
@@ -175,6 +216,9 @@ PGO_ORDER_RCM, PGO_ORDER_NATURAL = 0, 1
 PGO_STOP_ITERATIONS, PGO_STOP_MAX_TRIALS, PGO_STOP_RHO_ZERO = 0, 1, 2
 
 CSM_RESULT_DTYPE = np.dtype([(f, np.int32) for f, _ in CsmResult._fields_])
+CSM_POST_DTYPE = np.dtype([(f, np.int32) for f, _ in CsmPosterior._fields_[:8]] +
+                          [("m0", np.int64), ("m1", np.int64, (3,)), ("m2", np.int64, (6,)), ("mean", np.float64, (3,)),
+                           ("cov", np.float64, (6,))])
 
 KF_NOT_CONVERGED, KF_ITERATIONS, KF_TRANSFORM, KF_ABS_MSE, KF_REL_MSE, KF_NO_CORRESPONDENCES = 0, 1, 2, 3, 4, 5
 KF_DEGENERATE = 6   # Generalized ICP only: the step's 6 x 6 has a pivot that is not positive and finite
@@ -233,6 +277,8 @@ EXPORTS = [
     "slam_csm_default_params", "slam_csm_create", "slam_csm_create_dev", "slam_csm_destroy", "slam_csm_reserve",
     "slam_csm_set_window", "slam_csm_set_exhaustive", "slam_csm_angles", "slam_csm_match_batch_dev", "slam_csm_match",
     "slam_csm_score_volume_dev", "slam_csm_read_table", "slam_csm_info",
+    "slam_csm_default_post_params", "slam_csm_set_post_params", "slam_csm_read_post_table", "slam_csm_match_post_batch_dev",
+    "slam_csm_match_post",
     "slam_vmap_default_params", "slam_vmap_create", "slam_vmap_destroy", "slam_vmap_clear", "slam_vmap_integrate",
     "slam_vmap_integrate_dev", "slam_vmap_extract_dev", "slam_vmap_read", "slam_vmap_read_sums", "slam_vmap_info",
     "slam_vmap_default_carve_params", "slam_vmap_carve_dev", "slam_vmap_carve", "slam_vmap_extract_carved_dev", "slam_vmap_read_carved",
@@ -461,6 +507,12 @@ def lib():
     L.slam_csm_match.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.POINTER(CsmResult)]
     L.slam_csm_score_volume_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]
     L.slam_csm_read_table.argtypes = [_vp, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4 + [_vp, C.c_size_t]
+    L.slam_csm_default_post_params.argtypes = [C.POINTER(CsmPostParams)]
+    L.slam_csm_default_post_params.restype = None
+    L.slam_csm_set_post_params.argtypes = [_vp, C.POINTER(CsmPostParams)]
+    L.slam_csm_read_post_table.argtypes = [_vp, _vp, C.c_int]
+    L.slam_csm_match_post_batch_dev.argtypes = [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.slam_csm_match_post.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.POINTER(CsmResult), C.POINTER(CsmPosterior)]
     L.slam_csm_info.argtypes = [_vp, C.POINTER(CsmParams), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                 C.POINTER(C.c_int)]
     L.slam_vmap_default_params.argtypes = [C.POINTER(VmapParams)]
@@ -891,6 +943,14 @@ def csm_default_params(**kw):
     return p
 
 
+def csm_default_post_params(**kw):
+    p = CsmPostParams()
+    lib().slam_csm_default_post_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 class CorrelativeMatcher:
     """The correlative scan matcher (slam_csm_*, docs/CSM.md): the best of N_theta x N_y x N_x poses around a start pose,
     the wide-basin start for Icp.fit.  The model arrays are Icp's."""
@@ -979,6 +1039,55 @@ class CorrelativeMatcher:
         self.match_batch_dev(d_pts, d_off, d_nga, S, d_R0, d_t0, d_cs, d_R, d_t, d_res)
         synchronize()
         return d_R.download(), d_t.download(), d_res.download()
+
+    # ---- the posterior of a match (docs/CSM.md section 6)
+    def set_post_params(self, params=None, **kw):
+        """slam_csm_set_post_params: the weight table and the per-scan scratch; the match_post calls need it first"""
+        self.post_params = params or csm_default_post_params(**kw)
+        check(lib().slam_csm_set_post_params(self.h, C.byref(self.post_params)))
+
+    def post_table(self):
+        """the 257 weights in force, uint32"""
+        w = np.zeros(257, np.uint32)
+        check(lib().slam_csm_read_post_table(self.h, _ptr(w), 257))
+        return w
+
+    def _units(self):
+        return (self.params.resolution, self.params.resolution, self.params.theta_step)
+
+    def match_post(self, t_ga, t_nga, R, t):
+        """slam_csm_match_post, host arrays: (R, t, CsmResult, CsmPosterior)"""
+        t_ga = np.ascontiguousarray(t_ga, dtype=np.float64).reshape(-1, 2)
+        t_nga = np.ascontiguousarray(t_nga, dtype=np.float64).reshape(-1, 2)
+        R = np.ascontiguousarray(R, dtype=np.float64).reshape(4).copy()
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(2).copy()
+        res, post = CsmResult(), CsmPosterior()
+        check(lib().slam_csm_match_post(self.h, _ptr(t_ga), len(t_ga), _ptr(t_nga), len(t_nga), _ptr(R), _ptr(t), C.byref(res),
+                                        C.byref(post)))
+        post.u, post.score, post.n_points = self._units(), res.score, res.n_points
+        return R.reshape(2, 2), t, res, post
+
+    def match_post_batch_dev(self, d_pts, d_off, d_nga, n_scans, d_R0, d_t0, d_cs, d_R, d_t, d_result, d_post, stream=None):
+        check(lib().slam_csm_match_post_batch_dev(self.h, d_pts.ptr, d_off.ptr, d_nga.ptr, int(n_scans), d_R0.ptr, d_t0.ptr,
+                                                  d_cs.ptr, d_R.ptr, d_t.ptr, d_result.ptr if d_result is not None else None,
+                                                  d_post.ptr, _sp(stream)))
+
+    def match_post_batch(self, batch, R0=None, t0=None):
+        """match_batch with the posteriors: (R [S, 4], t [S, 2], result [S], posterior [S] of CSM_POST_DTYPE)."""
+        S = batch.n_scans
+        R0 = np.ascontiguousarray(batch.R if R0 is None else R0, dtype=np.float64).reshape(S, 4)
+        t0 = np.ascontiguousarray(batch.t if t0 is None else t0, dtype=np.float64).reshape(S, 2)
+        self.reserve(S)
+        d_pts = DeviceArray.from_host(batch.pts, np.float64)
+        d_off = DeviceArray.from_host(batch.scan_off, np.int32)
+        d_nga = DeviceArray.from_host(batch.scan_nga, np.int32)
+        d_R0, d_t0 = DeviceArray.from_host(R0), DeviceArray.from_host(t0)
+        d_cs = DeviceArray.from_host(np.stack([self.angles(R0[s]) for s in range(S)]))
+        d_R, d_t = DeviceArray((S, 4), np.float64), DeviceArray((S, 2), np.float64)
+        d_res, d_post = DeviceArray((S,), CSM_RESULT_DTYPE), DeviceArray((S,), CSM_POST_DTYPE)
+        self.match_post_batch_dev(d_pts, d_off, d_nga, S, d_R0, d_t0, d_cs, d_R, d_t, d_res, d_post)
+        synchronize()
+        return d_R.download(), d_t.download(), d_res.download(), d_post.download()
 
     def score_volume(self, t_ga, t_nga, R0, t0):
         """Every score of one scan: int32 [N_theta, N_y, N_x] (slam_csm_score_volume_dev)."""

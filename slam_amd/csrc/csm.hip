@@ -8,6 +8,9 @@
 // an atomicMax on score << 32 | ~flat_index, so neither the list's order nor the order of the workgroups shows in the result.
 // The one floating-point step, point -> cell at an angle, is spelled with __dmul_rn / __dadd_rn and an IEEE division; cos and
 // sin come from the host (slam_csm_angles).
+//
+// slam_csm_match_post* add the posterior of that answer (docs/CSM.md section 6) in four more launches: the candidates within
+// a score margin of the winner, enumerated exactly from the same bounds, summed into int64 moments and a second-mode key.
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -376,6 +379,190 @@ __global__ __launch_bounds__(256) void csm_finish_kernel(Geom G, Scans S, const 
     }
 }
 
+// ---------------------------------------------------------------- the posterior (docs/CSM.md section 6)
+// After a match: the margin M from the points counted at the winning angle (csm_post_prepare_kernel), every block whose bound
+// reaches S* - M (csm_post_select_kernel), those blocks at full resolution into eleven int64 sums and the second mode's key
+// (csm_post_accumulate_kernel), and the f64 finish (csm_post_finish_kernel).  Integer sums: any order gives the same bits.
+constexpr int kPostSums = 11; // n_within, m0, m1[3], m2[6]
+constexpr int kPostTable = 257; // weights: deficit d of margin M reads entry d * 256 / M
+
+struct PostAcc {
+    long long          sum[kPostSums];
+    unsigned long long second; // score << 32 | ~flat of the best candidate outside the exclusion box; 0 = none
+    int                margin, pad;
+};
+
+struct PostCfg {
+    int    margin_per_point, excl_xy, excl_theta, all_blocks;
+    double theta_step;
+};
+
+__device__ inline long long wave_sum(long long v)
+{
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// scan s: clears its sums, its second-mode key and its list counter, and sets M = margin_per_point * n_points
+__global__ __launch_bounds__(256) void csm_post_prepare_kernel(Geom G, Scans S, PostCfg C, const unsigned long long *best, PostAcc *acc, int32_t *count)
+{
+    __shared__ int counted;
+    const int      s = blockIdx.x;
+    int            first, n, n_ga;
+    scan_range(S, s, first, n, n_ga);
+    if (threadIdx.x == 0) counted = 0;
+    __syncthreads();
+    if (n >= 5) {
+        const int    k = (int)(~(unsigned)best[s] / (unsigned)(G.nx * G.ny));
+        const double c = S.cs[((size_t)s * G.nth + k) * 2], sn = S.cs[((size_t)s * G.nth + k) * 2 + 1];
+        const double tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
+        int          mine = 0;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            int cx, cy;
+            mine += point_cell(G.T, S.pts, first, i, n_ga, c, sn, tx, ty, G.res, cx, cy) ? 1 : 0;
+        }
+        atomicAdd(&counted, mine);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        PostAcc z;
+        for (int i = 0; i < kPostSums; ++i) z.sum[i] = 0;
+        z.second = 0, z.margin = C.margin_per_point * counted, z.pad = 0;
+        acc[s] = z;
+        count[s] = 0;
+    }
+}
+
+// every block that can hold a candidate with S >= S* - M: U >= S* - M, the top block included; all_blocks: every block
+__global__ void csm_post_select_kernel(Geom G, Scans S, PostCfg C, const int32_t *U, const unsigned long long *best, const PostAcc *acc, int32_t *list,
+                                       int32_t *count)
+{
+    const int per = G.nth * G.nbx * G.nby, s = blockIdx.y;
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    int       first, n, n_ga;
+    scan_range(S, s, first, n, n_ga);
+    if (n < 5 || f >= per) return;
+    const long long low = (long long)(int)(best[s] >> 32) - acc[s].margin;
+    if (C.all_blocks || U[(size_t)s * per + f] >= low) list[(size_t)s * per + atomicAdd(&count[s], 1)] = f;
+}
+
+// csm_blocks_kernel's wave per listed block, then every lane's candidates into the weight and the eleven terms.  A wave keeps
+// the sums of all the items it strides over and adds them to the scan's once.
+__global__ __launch_bounds__(64) void csm_post_accumulate_kernel(Geom G, Scans S, PostCfg C, const unsigned long long *best, const int32_t *list,
+                                                                 const int32_t *count, const uint32_t *wtab, PostAcc *acc)
+{
+    __shared__ int2 cells[kChunk];
+    const int       nb = G.nbx * G.nby, s = blockIdx.y;
+    int             first, n, n_ga;
+    scan_range(S, s, first, n, n_ga);
+    if (n < 5) return;
+    const int items = count[s];
+    if ((int)blockIdx.x >= items) return;
+    const double   tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
+    const unsigned wflat = ~(unsigned)best[s];
+    const int      wk = wflat / (G.nx * G.ny), wb = wflat / G.nx % G.ny, wa = wflat % G.nx, top = (int)(best[s] >> 32);
+    const int      M = acc[s].margin;
+    long long          sum[kPostSums];
+    unsigned long long key = 0;
+#pragma unroll
+    for (int i = 0; i < kPostSums; ++i) sum[i] = 0;
+    for (int it = blockIdx.x; it < items; it += gridDim.x) {
+        const unsigned f = (unsigned)list[(size_t)s * G.nth * nb + it];
+        const int      k = f / nb, A = (f % nb) % G.nbx, B = (f % nb) / G.nbx;
+        const double   c = S.cs[((size_t)s * G.nth + k) * 2], sn = S.cs[((size_t)s * G.nth + k) * 2 + 1];
+        int            a[kBlockPer], b[kBlockPer], sc[kBlockPer];
+#pragma unroll
+        for (int r = 0; r < kBlockPer; ++r) {
+            const int cnd = r * 64 + threadIdx.x;
+            a[r] = A * G.D + cnd % G.D, b[r] = B * G.D + cnd / G.D, sc[r] = 0;
+            if (cnd >= G.D * G.D || a[r] >= G.nx || b[r] >= G.ny) a[r] = -1; // a ragged block's missing candidates take no part
+        }
+        for (int base = 0; base < n; base += kChunk) {
+            const int cn = n - base < kChunk ? n - base : kChunk;
+            __syncthreads();
+            stage(G, G.T, S.pts, first, base, cn, n_ga, c, sn, tx, ty, cells, 64);
+            __syncthreads();
+            const int split = n_ga - base < 0 ? 0 : (n_ga - base > cn ? cn : n_ga - base);
+            for (int cl = 0; cl < 2; ++cl) {
+                const Tab t = G.T[cl];
+                const int j1 = cl ? cn : split;
+                for (int j = cl ? split : 0; j < j1; ++j) {
+                    const int2 q = cells[j];
+#pragma unroll
+                    for (int r = 0; r < kBlockPer; ++r) {
+                        const int col = q.x + a[r], row = q.y + b[r];
+                        if (a[r] >= 0 && (unsigned)col < (unsigned)t.w && (unsigned)row < (unsigned)t.h) sc[r] += t.v[(size_t)row * t.w + col];
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < kBlockPer; ++r) {
+            const int d = top - sc[r];
+            if (a[r] < 0 || d > M) continue;
+            const int       j = M > 0 && d > 0 ? (int)(((long long)d * 256) / M) : 0;
+            const long long w = wtab[j], o[3] = {a[r] - wa, b[r] - wb, k - wk};
+            sum[0] += 1, sum[1] += w;
+            sum[2] += w * o[0], sum[3] += w * o[1], sum[4] += w * o[2];
+            sum[5] += w * o[0] * o[0], sum[6] += w * o[0] * o[1], sum[7] += w * o[0] * o[2];
+            sum[8] += w * o[1] * o[1], sum[9] += w * o[1] * o[2], sum[10] += w * o[2] * o[2];
+            if (o[0] > C.excl_xy || o[0] < -C.excl_xy || o[1] > C.excl_xy || o[1] < -C.excl_xy || o[2] > C.excl_theta || o[2] < -C.excl_theta) {
+                const unsigned long long kk = key_of(sc[r], ((unsigned)k * G.ny + b[r]) * G.nx + a[r]);
+                key = kk > key ? kk : key;
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < kPostSums; ++i) sum[i] = wave_sum(sum[i]);
+    key = wave_max(key);
+    if (threadIdx.x == 0) {
+        for (int i = 0; i < kPostSums; ++i)
+            if (sum[i]) atomicAdd(reinterpret_cast<unsigned long long *>(&acc[s].sum[i]), (unsigned long long)sum[i]);
+        if (key) atomicMax(&acc[s].second, key);
+    }
+}
+
+// one lane per scan: the sums into mean and covariance, every operation rounded on its own
+__global__ void csm_post_finish_kernel(Geom G, Scans S, PostCfg C, int n_scans, const unsigned long long *best, const PostAcc *acc, const int32_t *count,
+                                       slam_csm_posterior *post)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_scans) return;
+    int first, n, n_ga;
+    scan_range(S, s, first, n, n_ga);
+    slam_csm_posterior out;
+    out.valid = 0, out.n_within = 0, out.margin = 0, out.blocks_evaluated = 0;
+    out.second_score = -1, out.second_k = 0, out.second_a = 0, out.second_b = 0;
+    out.m0 = 0;
+    for (int i = 0; i < 3; ++i) out.m1[i] = 0, out.mean[i] = 0.0;
+    for (int i = 0; i < 6; ++i) out.m2[i] = 0, out.cov[i] = 0.0;
+    if (n >= 5) {
+        const PostAcc &a = acc[s];
+        out.valid = 1, out.n_within = (int)a.sum[0], out.margin = a.margin, out.blocks_evaluated = count[s];
+        if (a.second) {
+            const unsigned flat = ~(unsigned)a.second;
+            out.second_score = (int)(a.second >> 32);
+            out.second_k = flat / (G.nx * G.ny), out.second_b = flat / G.nx % G.ny, out.second_a = flat % G.nx;
+        }
+        out.m0 = a.sum[1];
+        for (int i = 0; i < 3; ++i) out.m1[i] = a.sum[2 + i];
+        for (int i = 0; i < 6; ++i) out.m2[i] = a.sum[5 + i];
+        const double f0 = (double)out.m0, u[3] = {G.res, G.res, C.theta_step};
+        double       mc[3];
+        for (int i = 0; i < 3; ++i) {
+            mc[i] = (double)out.m1[i] / f0;
+            out.mean[i] = __dmul_rn(mc[i], u[i]);
+        }
+        int ij = 0;
+        for (int i = 0; i < 3; ++i)
+            for (int j = i; j < 3; ++j, ++ij) {
+                const double cc = __dsub_rn((double)out.m2[ij] / f0, __dmul_rn(mc[i], mc[j]));
+                out.cov[ij] = __dmul_rn(__dmul_rn(cc, u[i]), u[j]);
+            }
+    }
+    post[s] = out;
+}
+
 inline unsigned blocks_for(size_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 } // namespace
@@ -391,6 +578,10 @@ struct slam_csm {
     int    max_scans = 0;
     // staging of the host form
     DevMem pts, small;
+    // the posterior (slam_csm_set_post_params): the 257 weights and one PostAcc per scan
+    slam_csm_post_params PP = {0, 0.0, 0, 0};
+    bool                 post_set = false;
+    DevMem               wtab, post;
 
     int  nth() const { return 2 * P.half_theta + 1; }
     int  nx() const { return 2 * P.half_x + 1; }
@@ -480,6 +671,7 @@ int reserve_scans(slam_csm *s, int max_scans)
     SLAM_TRY(s->U.reserve(sizeof(int32_t) * per * max_scans));
     SLAM_TRY(s->list.reserve(sizeof(int32_t) * per * max_scans));
     SLAM_TRY(s->keys.reserve((2 * sizeof(unsigned long long) + sizeof(int32_t)) * (size_t)max_scans));
+    if (s->post_set) SLAM_TRY(s->post.reserve(sizeof(PostAcc) * (size_t)max_scans));
     s->max_scans = max_scans;
     return SLAM_OK;
 }
@@ -635,20 +827,21 @@ int slam_csm_match_batch_dev(slam_csm_t *csm, const double *d_pts, const int32_t
     return SLAM_OK;
 }
 
-int slam_csm_match(slam_csm_t *csm, const double *t_ga, int n_tga, const double *t_nga, int n_tnga, double R[4], double t[2],
-                   slam_csm_result *result)
+// slam_csm_match and slam_csm_match_post: one scan from host pointers through the batch call, one wait
+static int match_host(slam_csm_t *csm, const char *who, const double *t_ga, int n_tga, const double *t_nga, int n_tnga, double R[4], double t[2],
+                      slam_csm_result *result, slam_csm_posterior *post)
 {
-    SLAM_REQUIRE(csm && R && t && n_tga >= 0 && n_tnga >= 0 && (n_tga == 0 || t_ga) && (n_tnga == 0 || t_nga), SLAM_E_INVALID,
-                 "slam_csm_match: bad arguments");
+    SLAM_REQUIRE(csm && R && t && n_tga >= 0 && n_tnga >= 0 && (n_tga == 0 || t_ga) && (n_tnga == 0 || t_nga), SLAM_E_INVALID, "%s: bad arguments", who);
     const int n = n_tga + n_tnga;
-    SLAM_REQUIRE(n >= 5, SLAM_E_TOO_FEW_SCENE_POINTS, "slam_csm_match: %d scene points, at least 5 are needed", n);
-    // one block behind the points: offsets, class count, R0, t0, the angles, R, t, the result
+    SLAM_REQUIRE(n >= 5, SLAM_E_TOO_FEW_SCENE_POINTS, "%s: %d scene points, at least 5 are needed", who, n);
+    // one block behind the points: offsets, class count, R0, t0, the angles, R, t, the result (and the posterior)
     const size_t cs_b = sizeof(double) * 2 * (size_t)csm->nth();
-    const size_t small_b = 16 + sizeof(double) * 12 + cs_b + sizeof(slam_csm_result);
+    const size_t res_at = 16 + sizeof(double) * 12 + cs_b, post_at = res_at + 32; // (the result is 28 bytes; the posterior holds int64)
+    const size_t small_b = post ? post_at + sizeof(slam_csm_posterior) : res_at + sizeof(slam_csm_result);
     SLAM_TRY(reserve_quarter(csm->pts, sizeof(double) * 2 * (size_t)n));
     SLAM_TRY(csm->small.reserve(small_b));
     char *host = static_cast<char *>(pinned_scratch(small_b));
-    SLAM_REQUIRE(host, SLAM_E_NOMEM, "slam_csm_match: no pinned staging memory");
+    SLAM_REQUIRE(host, SLAM_E_NOMEM, "%s: no pinned staging memory", who);
     int32_t *h_off = reinterpret_cast<int32_t *>(host);
     double  *h_pose = reinterpret_cast<double *>(host + 16), *h_cs = h_pose + 12;
     h_off[0] = 0, h_off[1] = n, h_off[2] = n_tga, h_off[3] = 0;
@@ -657,19 +850,107 @@ int slam_csm_match(slam_csm_t *csm, const double *t_ga, int n_tga, const double 
     SLAM_TRY(slam_csm_angles(csm, R, h_cs));
     char    *dev = csm->small.as<char>();
     double  *d_pose = reinterpret_cast<double *>(dev + 16);
-    auto    *d_res = reinterpret_cast<slam_csm_result *>(dev + 16 + sizeof(double) * 12 + cs_b);
+    auto    *d_res = reinterpret_cast<slam_csm_result *>(dev + res_at);
     double  *d_pts = csm->pts.as<double>();
     if (n_tga) SLAM_HIP(hipMemcpyAsync(d_pts, t_ga, sizeof(double) * 2 * (size_t)n_tga, hipMemcpyHostToDevice, nullptr));
     if (n_tnga) SLAM_HIP(hipMemcpyAsync(d_pts + 2 * (size_t)n_tga, t_nga, sizeof(double) * 2 * (size_t)n_tnga, hipMemcpyHostToDevice, nullptr));
-    SLAM_HIP(hipMemcpyAsync(dev, host, 16 + sizeof(double) * 12 + cs_b, hipMemcpyHostToDevice, nullptr));
-    SLAM_TRY(slam_csm_match_batch_dev(csm, d_pts, reinterpret_cast<int32_t *>(dev), reinterpret_cast<int32_t *>(dev) + 2, 1, d_pose, d_pose + 4,
-                                      d_pose + 12, d_pose + 6, d_pose + 10, d_res, nullptr));
+    SLAM_HIP(hipMemcpyAsync(dev, host, res_at, hipMemcpyHostToDevice, nullptr));
+    if (post)
+        SLAM_TRY(slam_csm_match_post_batch_dev(csm, d_pts, reinterpret_cast<int32_t *>(dev), reinterpret_cast<int32_t *>(dev) + 2, 1, d_pose, d_pose + 4,
+                                               d_pose + 12, d_pose + 6, d_pose + 10, d_res, reinterpret_cast<slam_csm_posterior *>(dev + post_at), nullptr));
+    else
+        SLAM_TRY(slam_csm_match_batch_dev(csm, d_pts, reinterpret_cast<int32_t *>(dev), reinterpret_cast<int32_t *>(dev) + 2, 1, d_pose, d_pose + 4,
+                                          d_pose + 12, d_pose + 6, d_pose + 10, d_res, nullptr));
     SLAM_HIP(hipMemcpyAsync(host, dev, small_b, hipMemcpyDeviceToHost, nullptr));
     SLAM_HIP(hipStreamSynchronize(nullptr));
     std::memcpy(R, h_pose + 6, 4 * sizeof(double));
     std::memcpy(t, h_pose + 10, 2 * sizeof(double));
-    if (result) std::memcpy(result, host + 16 + sizeof(double) * 12 + cs_b, sizeof *result);
+    if (result) std::memcpy(result, host + res_at, sizeof *result);
+    if (post) std::memcpy(post, host + post_at, sizeof *post);
     return SLAM_OK;
+}
+
+int slam_csm_match(slam_csm_t *csm, const double *t_ga, int n_tga, const double *t_nga, int n_tnga, double R[4], double t[2],
+                   slam_csm_result *result)
+{
+    return match_host(csm, "slam_csm_match", t_ga, n_tga, t_nga, n_tnga, R, t, result, nullptr);
+}
+
+void slam_csm_default_post_params(slam_csm_post_params *p)
+{
+    if (!p) return;
+    p->margin_per_point = 16, p->beta = 8.0, p->excl_xy = 2, p->excl_theta = 2;
+}
+
+int slam_csm_set_post_params(slam_csm_t *csm, const slam_csm_post_params *p)
+{
+    SLAM_REQUIRE(csm && p, SLAM_E_INVALID, "slam_csm_set_post_params: null argument");
+    SLAM_REQUIRE(p->margin_per_point >= 0 && p->margin_per_point <= 255 && std::isfinite(p->beta) && p->beta >= 0.0 && p->beta <= 64.0 &&
+                     p->excl_xy >= 0 && p->excl_theta >= 0,
+                 SLAM_E_INVALID, "slam_csm_set_post_params: margin_per_point lies in 0 .. 255, beta in 0 .. 64, the exclusion is not negative");
+    uint32_t wtab[kPostTable];
+    for (int j = 0; j < kPostTable; ++j) wtab[j] = (uint32_t)std::rint(65536.0 * std::exp(-(p->beta * (double)j) / 256.0));
+    SLAM_TRY(csm->wtab.reserve(sizeof wtab));
+    SLAM_TRY(csm->post.reserve(sizeof(PostAcc) * (size_t)csm->max_scans));
+    SLAM_HIP(hipDeviceSynchronize()); // an earlier call may still read the table
+    SLAM_HIP(hipMemcpy(csm->wtab.p, wtab, sizeof wtab, hipMemcpyHostToDevice));
+    csm->PP = *p, csm->post_set = true;
+    return SLAM_OK;
+}
+
+int slam_csm_read_post_table(slam_csm_t *csm, uint32_t *wtab, int cap)
+{
+    SLAM_REQUIRE(csm && wtab && cap >= kPostTable, SLAM_E_INVALID, "slam_csm_read_post_table: bad arguments (the table has %d entries)", kPostTable);
+    SLAM_REQUIRE(csm->post_set, SLAM_E_INVALID, "slam_csm_read_post_table: slam_csm_set_post_params comes first");
+    SLAM_HIP(hipMemcpy(wtab, csm->wtab.p, sizeof(uint32_t) * kPostTable, hipMemcpyDeviceToHost));
+    return SLAM_OK;
+}
+
+int slam_csm_match_post_batch_dev(slam_csm_t *csm, const double *d_pts, const int32_t *d_scan_off, const int32_t *d_scan_nga, int n_scans,
+                                  const double *d_R0, const double *d_t0, const double *d_cs, double *d_R, double *d_t, slam_csm_result *d_result,
+                                  slam_csm_posterior *d_post, slam_stream_t stream)
+{
+    SLAM_REQUIRE(csm && n_scans >= 0, SLAM_E_INVALID, "slam_csm_match_post_batch_dev: bad arguments");
+    SLAM_REQUIRE(csm->post_set, SLAM_E_INVALID, "slam_csm_match_post_batch_dev: slam_csm_set_post_params comes first");
+    const Geom G = csm->geom();
+    {
+        // the int64 sums: 65536 Dmax^2 per candidate at the most
+        const unsigned __int128 dmax = (unsigned)(std::max(G.nx, std::max(G.ny, G.nth)) - 1);
+        const unsigned __int128 worst = (unsigned __int128)65536 * dmax * dmax * ((unsigned __int128)G.nx * G.ny * G.nth);
+        SLAM_REQUIRE(worst < ((unsigned __int128)1 << 63), SLAM_E_INVALID,
+                     "slam_csm_match_post_batch_dev: a window of %d x %d x %d candidates could overflow the posterior's 64-bit sums", G.nx, G.ny, G.nth);
+    }
+    if (n_scans == 0) return SLAM_OK;
+    // the posterior pass reads the start translations again after the match has written its answer (the angles come from d_cs)
+    SLAM_REQUIRE(d_post && d_t0 && d_t != d_t0, SLAM_E_INVALID, "slam_csm_match_post_batch_dev: null d_post, or d_t is d_t0");
+    SLAM_TRY(slam_csm_match_batch_dev(csm, d_pts, d_scan_off, d_scan_nga, n_scans, d_R0, d_t0, d_cs, d_R, d_t, d_result, stream));
+    hipStream_t   st = as_stream(stream);
+    const Scans   S{d_pts, d_scan_off, d_scan_nga, 0, 0, d_t0, d_cs};
+    const PostCfg C{csm->PP.margin_per_point, csm->PP.excl_xy, csm->PP.excl_theta, csm->P.exhaustive ? 1 : 0, csm->P.theta_step};
+    const int     per = G.nth * G.nbx * G.nby;
+    auto         *best = csm->keys.as<unsigned long long>() + csm->max_scans;
+    int32_t      *count = reinterpret_cast<int32_t *>(best + csm->max_scans);
+    PostAcc      *acc = csm->post.as<PostAcc>();
+    int           stride = 4096 / n_scans;
+    stride = stride < 8 ? 8 : (stride > 1024 ? 1024 : stride);
+    hipLaunchKernelGGL(csm_post_prepare_kernel, dim3(n_scans), dim3(256), 0, st, G, S, C, best, acc, count);
+    SLAM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(csm_post_select_kernel, dim3(blocks_for(per, 256), n_scans), dim3(256), 0, st, G, S, C, csm->U.as<int32_t>(), best, acc,
+                       csm->list.as<int32_t>(), count);
+    SLAM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(csm_post_accumulate_kernel, dim3(stride, n_scans), dim3(64), 0, st, G, S, C, best, csm->list.as<int32_t>(), count,
+                       csm->wtab.as<uint32_t>(), acc);
+    SLAM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(csm_post_finish_kernel, dim3(blocks_for(n_scans, 64)), dim3(64), 0, st, G, S, C, n_scans, best, acc, count, d_post);
+    SLAM_HIP(hipGetLastError());
+    return SLAM_OK;
+}
+
+int slam_csm_match_post(slam_csm_t *csm, const double *t_ga, int n_tga, const double *t_nga, int n_tnga, double R[4], double t[2],
+                        slam_csm_result *result, slam_csm_posterior *post)
+{
+    SLAM_REQUIRE(post, SLAM_E_INVALID, "slam_csm_match_post: null posterior");
+    return match_host(csm, "slam_csm_match_post", t_ga, n_tga, t_nga, n_tnga, R, t, result, post);
 }
 
 int slam_csm_score_volume_dev(slam_csm_t *csm, const double *d_pts, int n, int n_ga, const double *d_t0, const double *d_cs, int32_t *d_volume,
@@ -707,7 +988,7 @@ int slam_csm_info(slam_csm_t *csm, slam_csm_params *params, int dims[5], size_t 
     if (params) *params = csm->P;
     if (dims) dims[0] = csm->nth(), dims[1] = csm->nx(), dims[2] = csm->ny(), dims[3] = csm->nbx(), dims[4] = csm->nby();
     if (table_bytes) *table_bytes = csm->tab[0].T.cap + csm->tab[0].W.cap + csm->tab[1].T.cap + csm->tab[1].W.cap;
-    if (scratch_bytes) *scratch_bytes = csm->U.cap + csm->list.cap + csm->keys.cap;
+    if (scratch_bytes) *scratch_bytes = csm->U.cap + csm->list.cap + csm->keys.cap + csm->wtab.cap + csm->post.cap;
     if (max_scans) *max_scans = csm->max_scans;
     return SLAM_OK;
 }

@@ -7,6 +7,11 @@ Device events around each region and the host clock around it, after a warm-up, 
 calls each.  The inputs of a batch call are resident; the call is the asynchronous slam_csm_match_batch_dev.
 
     python tools/csm_time.py [--reps 7] [--inner 3] [--batch 256] [--no-cpu]
+
+--post measures the posterior instead (docs/CSM.md section 6): slam_csm_match_batch_dev alone against
+slam_csm_match_post_batch_dev on the same resident scans at the default post parameters, two-level, with the blocks each
+evaluates at full resolution.  The difference of the two is the posterior's four kernels; for the split by kernel run it
+once under `rocprofv3 --kernel-trace --stats -- python tools/csm_time.py --post --no-cpu`.
 """
 import argparse
 import json
@@ -54,16 +59,57 @@ def resident_batch(cm, n_scans):
     return cases, d
 
 
+def time_posterior(a, m_ga, m_nga, out):
+    """match alone against match + posterior on the basin scans at the defaults"""
+    cm = api.CorrelativeMatcher(m_ga, m_nga)
+    cm.reserve(a.batch)
+    cm.set_post_params()
+    info = cm.info()
+    n_blocks = info["n_theta"] * info["blocks_x"] * info["blocks_y"]
+    out["info"] = {k: v for k, v in info.items() if k != "params"}
+    for n_scans, name in ((1, "one_scan"), (a.batch, "batch_%d" % a.batch)):
+        cases, d = resident_batch(cm, n_scans)
+        d_post = api.DeviceArray((n_scans,), api.CSM_POST_DTYPE)
+
+        def match():
+            cm.match_batch_dev(d[0], d[1], d[2], n_scans, d[3], d[4], d[5], d[6], d[7], d[8])
+
+        def match_post():
+            cm.match_post_batch_dev(d[0], d[1], d[2], n_scans, d[3], d[4], d[5], d[6], d[7], d[8], d_post)
+
+        row = {}
+        for key, fn in (("match", match), ("match_post", match_post), ("match_again", match)):
+            fn()
+            ev, wall = zip(*[region(fn, a.inner) for _ in range(a.reps)])
+            row[key + "_ms"] = {"device": stats(ev), "wall": stats(wall), "per_scan_device": float(np.median(ev)) / n_scans}
+        res, post = d[8].download(), d_post.download()
+        base = row["match_ms"]["device"]["median"]
+        row["posterior_over_match"] = (row["match_post_ms"]["device"]["median"] - base) / base
+        row["blocks_evaluated"] = {"match_median": float(np.median(res["blocks_evaluated"])), "match_max": int(res["blocks_evaluated"].max()),
+                                   "posterior_median": float(np.median(post["blocks_evaluated"])),
+                                   "posterior_max": int(post["blocks_evaluated"].max()), "of": n_blocks}
+        row["n_within"] = {"median": float(np.median(post["n_within"])), "max": int(post["n_within"].max())}
+        row["second_modes"] = int(np.count_nonzero(post["second_score"] >= 0))
+        out["post_" + name] = row
+    cm.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--inner", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--post", action="store_true")
     a = ap.parse_args()
     api.set_device(0)
     m_ga, m_nga = CO.synth_map()
     out = {"device": api.device_info()[0], "model_points": [len(m_ga), len(m_nga)]}
+
+    if a.post:
+        time_posterior(a, m_ga, m_nga, out)
+        print(json.dumps(out))
+        return
 
     def create():
         api.CorrelativeMatcher(m_ga, m_nga).close()
