@@ -8,6 +8,10 @@
 //                     PCL GICP's stop rule follow as in kf_gicp.hip.  A last pass with the f32 transform gives the
 //                     point-to-plane fitness.  Lookups only find; nothing is written to the map; no workgroup waits for
 //                     another; every loop is bounded by the source's size, max_iterations or the table's capacity.
+// The map's rules come from vmap_dist.hpp: the hash, the limits and the key packing (vmap_cell_key).  The point-to-cell test in
+// nearest_plane27 is still written out here and must follow vmap_point_cell: the kernel stands at 256 VGPRs with spills, and
+// with the shared function its SGPR spills came out at 55 instead of 58 -- no worse, but not the kernel that was measured
+// (docs/VOXEL_MAP.md section 9.3), so its body stays.
 // The restatement is tests/cpp/vmap_gicp_oracle.cpp.
 #include "kf_common.hpp"
 #include "kf_gicp_math.hpp"
@@ -42,7 +46,7 @@ __device__ __forceinline__ long long nearest_plane27(const VmapDistView &V, cons
     // The 27 keys and their first probes, issued together.  A neighbour's key is the centre's plus a constant (the fields do
     // not carry: the cell is in range); slots fit 32 bits (a table has at most 2^31).  Only the 27 words read and their slots
     // stay in registers between the two passes.
-    const uint64_t base = ((uint64_t)(c[2] + kVmapCellLimit) << 42) | ((uint64_t)(c[1] + kVmapCellLimit) << 21) | (uint64_t)(c[0] + kVmapCellLimit);
+    const uint64_t base = vmap_cell_key(c);
     const uint32_t mask = (uint32_t)V.mask;
     uint32_t       slot[27];
     uint64_t       cur[27];

@@ -11,10 +11,14 @@
 //              slot's sums are zero from the moment the table is cleared, so an add may land before or after any other.
 //              Integer adds commute, so no order of lanes shows in the sums; where a key sits does not show in any result
 //              because extraction sorts by key.
-//   rehash     one lane per old slot: claims the key's slot in the larger table and stores sums and count (keys are
-//              distinct, so plain stores).  Only ever launched by the host between integrate launches.
-//   extract    flag (count, box) per slot -> rocprim select of the slot indices -> gather their keys -> rocprim radix sort
-//              of (key, slot) -> one lane per voxel writes centroid, count and key.
+//              One kernel, a template on "with moments" (below), instantiated twice: the host picks.
+//   rehash     one lane per old slot: claims the key's slot in the larger table and stores everything the map has -- sums
+//              and count, seen and miss of a carved map, the nine moment planes -- in one launch (keys are distinct, so plain
+//              stores; planes the map has not are null pointers).  Only ever launched by the host between integrate launches.
+//   extract    flag (count, box, and the carved rule where a ratio is given) per slot -> rocprim select of the slot indices
+//              -> gather their keys -> rocprim radix sort of (key, slot) -> one lane per voxel writes centroid, count and key.
+//              Every host reader is read_columns: one select, one sort, the wanted columns laid out in stage_out by a bump
+//              allocator, the families' write kernels, the copies back.
 //   carve      free-space evidence for voxels that exist (docs/VOXEL_MAP.md section 8; the restatement is
 //              tests/cpp/vmap_carve_oracle.cpp): two u32 planes `seen` and `miss` in units of scans and a u32 `stamp` plane
 //              that makes a voxel count once per call, all three allocated at the first carve.  One lane per ray finds the
@@ -22,10 +26,10 @@
 //              one wavefront per chunk, one lane per step, walks the closed form of the driving-axis Bresenham and charges
 //              `miss` (phase 2).  No key is written: the lookup only finds.
 //   moments    opt-in (docs/VOXEL_MAP.md section 9; the restatement is tests/cpp/vmap_gicp_oracle.cpp): nine i64 planes, the
-//              first and second moments of a voxel's points about the cell's corner in units of 2^-16 m.  A second
-//              integrate kernel adds them with nine more 64-bit integer atomicAdds; after a rehash one more launch moves the
-//              planes by looking every old key up in the new table.  One lane per slot turns them into a centroid, a normal,
-//              a regularised plane covariance and a flag (the distribution planes), which vmap_gicp.hip registers against.
+//              first and second moments of a voxel's points about the cell's corner in units of 2^-16 m.  The integrate
+//              instantiation with moments adds them with nine more 64-bit integer atomicAdds; they travel with the voxel
+//              through a rehash.  One lane per slot turns them into a centroid, a normal, a regularised plane covariance
+//              and a flag (the distribution planes), which vmap_gicp.hip registers against.
 //   absorb     (docs/VOXEL_MAP.md section 10) one lane per voxel record (key, count, sums, optionally seen and miss, optionally
 //              the nine moments): validate, find or claim as integrate does, integer atomicAdds.  The records are packed
 //              arrays (a file, a caller) or another table's planes (merge: one lane per source slot, empty slots leave at
@@ -33,6 +37,10 @@
 //   coarsen    (docs/VOXEL_MAP.md section 11) one lane per slot of a finer map: the parent cell is the cell shifted right, count
 //              and sums add unchanged, the moments are re-centred on the parent's corner in integers; find or claim and
 //              integer atomicAdds as absorb.  The result is the bits of a map integrated at the coarser leaf.
+// Each rule stands once.  The cell rule (point -> cell -> key -> cell) and the hash are vmap_dist.hpp's, shared with
+// vmap_gicp.hip; the f64 move of a point is moved_point, for the kernels and for the host's carve origin alike; the carved
+// rule is carve_keeps; "zero the counters, launch, fetch them, wait" is Counters; the host half of absorb, merge and coarsen is
+// absorb_with.
 // The hash is the 64-bit finaliser of MurmurHash3 (fmix64: two multiply-xorshift rounds), masked to the table: neighbouring
 // cells differ in the low bits of one 21-bit field, and fmix64 spreads any one-bit difference over the whole word.
 // The probe loop ends after `capacity` slots and then raises the handle's error word; the host keeps the load at one half
@@ -55,14 +63,19 @@ namespace {
 constexpr uint64_t kEmpty = ~0ull;
 constexpr int64_t  kMaxSlots = 1ll << 31; // slot indices travel as u32 through select and sort
 constexpr double   kFix = 1048576.0;      // 2^20: sums are in units of 2^-20 m
-constexpr int      kCellLimit = 1 << 20;
-constexpr float    kCoordLimit = 4194304.0f; // 2^22
 
 struct Table {
     uint64_t           *key;
     unsigned long long *sum[3];
     uint32_t           *count;
     uint64_t            mask; // slots - 1
+};
+// the carve planes (section 8) and the moment planes (section 9): null pointers on a map that has none
+struct Planes {
+    uint32_t *seen, *miss, *stamp;
+};
+struct Moments {
+    unsigned long long *E[3], *M[6]; // first moments, then xx xy xz yy yz zz
 };
 struct Transform {
     double r[9], t[3];
@@ -78,20 +91,10 @@ enum { kClaimed = 0, kDropped = 1, kError = 2, kSelected = 3, kCounters = 4 };
 // three as above (kDropped counts the rejected records), then the points accepted as one u64
 enum { kPoints = 4, kAbsorbCounters = 6 };
 
-__device__ __forceinline__ uint64_t fmix64(uint64_t k)
-{
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return k;
-}
-
 // The slot that holds `key`, claimed if nobody had; -1 when `capacity` probes found neither (the error word's case).
 __device__ __forceinline__ long long find_or_claim(const Table &T, uint64_t key, uint32_t *claimed)
 {
-    uint64_t h = fmix64(key) & T.mask;
+    uint64_t h = vmap_fmix64(key) & T.mask;
     for (uint64_t probe = 0; probe <= T.mask; ++probe, h = (h + 1) & T.mask) {
         uint64_t cur = __hip_atomic_load(&T.key[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (cur == kEmpty) {
@@ -106,33 +109,51 @@ __device__ __forceinline__ long long find_or_claim(const Table &T, uint64_t key,
     return -1;
 }
 
-__global__ __launch_bounds__(256) void vmap_integrate_kernel(const float *xyz, int n, int stride, Transform X, double leaf, Table T,
-                                                             uint32_t *ctr)
+// A point as the map sees it: p (f32 from a cloud, f64 for a carve's origin) moved by X in f64, every product and sum rounded
+// on its own, then rounded to f32.  The kernels spell the rounding with the intrinsics; the host's plain operators round the
+// same way because the file is compiled without contraction.  X by value and the statements in this order: so the integrate
+// kernels compile to their predecessors' instructions (docs/VOXEL_MAP.md section 12.2).
+template <class S>
+__host__ __device__ __forceinline__ void moved_point(const S *p, const Transform X, float q[3])
+{
+    q[0] = (float)p[0], q[1] = (float)p[1], q[2] = (float)p[2];
+    if (X.on) {
+        const double px = p[0], py = p[1], pz = p[2];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+#ifdef __HIP_DEVICE_COMPILE__ // the rounding spelled out: the kernels do not lean on the build's flags
+            q[k] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(X.r[3 * k], px), __dmul_rn(X.r[3 * k + 1], py)), __dmul_rn(X.r[3 * k + 2], pz)),
+                                    X.t[k]);
+#else
+            q[k] = (float)((((X.r[3 * k] * px) + (X.r[3 * k + 1] * py)) + (X.r[3 * k + 2] * pz)) + X.t[k]);
+#endif
+        }
+    }
+}
+
+// kMoments adds the moments about the cell's corner: e = (fx - cell L) >> 4 per axis, |e| <= 2^20 (section 9 has the bound).
+// L and Q are read by that instantiation alone.
+template <bool kMoments>
+__global__ __launch_bounds__(256) void vmap_integrate_kernel(const float *xyz, int n, int stride, Transform X, double leaf, long long L, Table T,
+                                                             Moments Q, uint32_t *ctr)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; // n may be close to 2^31
     if (i >= (size_t)n) return;
-    const float *p = xyz + i * stride;
-    float        q[3] = {p[0], p[1], p[2]};
-    if (X.on) {
-        const double px = q[0], py = q[1], pz = q[2];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            q[k] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(X.r[3 * k], px), __dmul_rn(X.r[3 * k + 1], py)), __dmul_rn(X.r[3 * k + 2], pz)),
-                                    X.t[k]);
-    }
+    float q[3];
+    int   cell[3];
+    moved_point(xyz + i * stride, X, q);
+    long long f[3], e[3];
     uint64_t  key = 0;
-    long long f[3];
     bool      keep = true;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float v = q[k];
-        const double c = floor((double)v / leaf);
-        if (!(fabsf(v) < kCoordLimit) || !(fabs(c) < (double)kCellLimit)) { // written so that a NaN fails both tests
+    for (int k = 0; k < 3; ++k) { // axis by axis, the fixed-point value beside the cell: the order the kernel was measured in
+        if (!vmap_axis_cell(q[k], leaf, &cell[k])) {
             keep = false;
             continue;
         }
-        key |= (uint64_t)((int)c + kCellLimit) << (21 * k);
-        f[k] = (long long)rint((double)v * kFix);
+        key |= vmap_key_field(cell[k], k);
+        f[k] = (long long)rint((double)q[k] * kFix);
+        e[k] = (f[k] - (long long)cell[k] * L) >> 4; // arithmetic: floor
     }
     if (!keep) {
         atomicAdd(&ctr[kDropped], 1u);
@@ -146,9 +167,21 @@ __global__ __launch_bounds__(256) void vmap_integrate_kernel(const float *xyz, i
 #pragma unroll
     for (int k = 0; k < 3; ++k) atomicAdd(&T.sum[k][h], (unsigned long long)f[k]);
     atomicAdd(&T.count[h], 1u);
+    if (kMoments) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) atomicAdd(&Q.E[k][h], (unsigned long long)e[k]);
+        atomicAdd(&Q.M[0][h], (unsigned long long)(e[0] * e[0]));
+        atomicAdd(&Q.M[1][h], (unsigned long long)(e[0] * e[1]));
+        atomicAdd(&Q.M[2][h], (unsigned long long)(e[0] * e[2]));
+        atomicAdd(&Q.M[3][h], (unsigned long long)(e[1] * e[1]));
+        atomicAdd(&Q.M[4][h], (unsigned long long)(e[1] * e[2]));
+        atomicAdd(&Q.M[5][h], (unsigned long long)(e[2] * e[2]));
+    }
 }
 
-__global__ __launch_bounds__(256) void vmap_rehash_kernel(Table from, Table to, uint32_t *ctr)
+// One lane per old slot: the voxel's slot in the new table, then everything the map has (keys are distinct, so plain
+// stores).  Pf and Qf are null pointers on a map without carve planes or moments; the new stamp plane stays zero.
+__global__ __launch_bounds__(256) void vmap_rehash_kernel(Table from, Planes Pf, Moments Qf, Table to, Planes Pt, Moments Qt, uint32_t *ctr)
 {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i > from.mask) return;
@@ -162,6 +195,13 @@ __global__ __launch_bounds__(256) void vmap_rehash_kernel(Table from, Table to, 
 #pragma unroll
     for (int k = 0; k < 3; ++k) to.sum[k][h] = from.sum[k][i];
     to.count[h] = from.count[i];
+    if (Pf.seen) Pt.seen[h] = Pf.seen[i], Pt.miss[h] = Pf.miss[i];
+    if (Qf.E[0]) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Qt.E[k][h] = Qf.E[k][i];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) Qt.M[k][h] = Qf.M[k][i];
+    }
 }
 
 __device__ __forceinline__ float centroid(unsigned long long s, uint32_t count)
@@ -169,15 +209,24 @@ __device__ __forceinline__ float centroid(unsigned long long s, uint32_t count)
     return (float)(((double)(long long)s / (double)count) * (1.0 / kFix));
 }
 
-__global__ __launch_bounds__(256) void vmap_flag_kernel(Table T, Box box, uint32_t min_count, uint8_t *flag)
+// The carved rule (section 8) for slot i: keep iff miss den <= max(seen, 1) num in u64, equality kept.
+__device__ __forceinline__ bool carve_keeps(const Planes &P, uint64_t i, uint32_t num, uint32_t den)
+{
+    const uint32_t seen = P.seen[i];
+    return (uint64_t)P.miss[i] * den <= (uint64_t)(seen > 1u ? seen : 1u) * num;
+}
+
+// P is null pointers when no ratio is given or the map was never carved: no carved rule then (a map never carved has
+// miss = 0 everywhere, which every ratio keeps).
+__global__ __launch_bounds__(256) void vmap_flag_kernel(Table T, Planes P, Box box, uint32_t min_count, uint32_t num, uint32_t den, uint8_t *flag)
 {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i > T.mask) return;
     bool           keep = false;
     const uint32_t c = T.count[i];
     if (T.key[i] != kEmpty && c >= min_count && c > 0) {
-        keep = true;
-        if (box.on) {
+        keep = !P.seen || carve_keeps(P, i, num, den);
+        if (keep && box.on) {
             const float x = centroid(T.sum[0][i], c), y = centroid(T.sum[1][i], c);
             keep = box.lo[0] <= x && x <= box.hi[0] && box.lo[1] <= y && y <= box.hi[1];
         }
@@ -209,9 +258,6 @@ __global__ __launch_bounds__(256) void vmap_write_kernel(Table T, const uint32_t
 }
 
 // ---------------------------------------------------------------- carve (docs/VOXEL_MAP.md section 8)
-struct Planes {
-    uint32_t *seen, *miss, *stamp;
-};
 struct Carve {
     int      c0[3]; // the origin's cell
     int      end_margin, tail_num, tail_den, max_ray_cells;
@@ -224,7 +270,7 @@ constexpr int kChunk = 64; // steps per chunk: one wavefront
 // The slot that holds `key`, or -1 at the first empty slot (or after `capacity` probes): nothing is written.
 __device__ __forceinline__ long long find_slot(const Table &T, uint64_t key)
 {
-    uint64_t h = fmix64(key) & T.mask;
+    uint64_t h = vmap_fmix64(key) & T.mask;
     for (uint64_t probe = 0; probe <= T.mask; ++probe, h = (h + 1) & T.mask) {
         const uint64_t cur = T.key[h];
         if (cur == key) return (long long)h;
@@ -241,33 +287,13 @@ __global__ __launch_bounds__(256) void vmap_carve_rays_kernel(const float *xyz, 
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t     L = 0;
     if (i < (size_t)n) {
-        const float *p = xyz + i * stride;
-        float        q[3] = {p[0], p[1], p[2]};
-        if (X.on) {
-            const double px = q[0], py = q[1], pz = q[2];
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                q[k] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(X.r[3 * k], px), __dmul_rn(X.r[3 * k + 1], py)), __dmul_rn(X.r[3 * k + 2], pz)),
-                                        X.t[k]);
-        }
-        uint64_t key = 0;
-        int      c1[3] = {0, 0, 0};
-        bool     keep = true;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float  v = q[k];
-            const double c = floor((double)v / leaf);
-            if (!(fabsf(v) < kCoordLimit) || !(fabs(c) < (double)kCellLimit)) { // written so that a NaN fails both tests
-                keep = false;
-                continue;
-            }
-            c1[k] = (int)c;
-            key |= (uint64_t)((int)c + kCellLimit) << (21 * k);
-        }
-        if (!keep) {
+        float q[3];
+        int   c1[3] = {0, 0, 0};
+        moved_point(xyz + i * stride, X, q);
+        if (!vmap_point_cell(q, leaf, c1)) {
             atomicAdd(&ctr[kcDropped], 1ull);
         } else {
-            const long long h = find_slot(T, key);
+            const long long h = find_slot(T, vmap_cell_key(c1));
             if (h >= 0 && atomicMax(&P.stamp[h], A.tag + 1u) < A.tag + 1u) {
                 atomicAdd(&P.seen[h], 1u);
                 atomicAdd(&ctr[kcSeen], 1ull);
@@ -328,10 +354,10 @@ __global__ __launch_bounds__(256) void vmap_carve_walk_kernel(const int4 *ray, c
 #pragma unroll
         for (int k = 0; k < 3; ++k) nn = max(nn, (uint32_t)abs(c1[k] - A.c0[k]));
         const bool small = nn < 32768u; // 2 a i + n - 1 < 2^31: the 32-bit division
-        uint64_t   key = 0;
+        int        cell[3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) key |= (uint64_t)(carve_cell(A.c0[k], c1[k], i, nn, small) + kCellLimit) << (21 * k);
-        const long long h = find_slot(T, key);
+        for (int k = 0; k < 3; ++k) cell[k] = carve_cell(A.c0[k], c1[k], i, nn, small);
+        const long long h = find_slot(T, vmap_cell_key(cell));
         if (h < 0) continue;
         if (__hip_atomic_load(&P.stamp[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == A.tag + 1u) continue; // an endpoint of this cloud
         if (atomicMax(&P.stamp[h], A.tag) < A.tag) {
@@ -341,59 +367,18 @@ __global__ __launch_bounds__(256) void vmap_carve_walk_kernel(const int4 *ray, c
     }
 }
 
-// vmap_rehash_kernel for a map that has been carved: seen and miss travel with the voxel (the new stamp plane is zero).
-__global__ __launch_bounds__(256) void vmap_rehash_carved_kernel(Table from, Planes pf, Table to, Planes pt, uint32_t *ctr)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i > from.mask) return;
-    const uint64_t key = from.key[i];
-    if (key == kEmpty) return;
-    const long long h = find_or_claim(to, key, ctr + kClaimed);
-    if (h < 0) {
-        atomicExch(&ctr[kError], 1u);
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) to.sum[k][h] = from.sum[k][i];
-    to.count[h] = from.count[i];
-    pt.seen[h] = pf.seen[i];
-    pt.miss[h] = pf.miss[i];
-}
-
-// vmap_flag_kernel with the carved rule on top: keep iff miss den <= max(seen, 1) num in u64, equality kept.
-__global__ __launch_bounds__(256) void vmap_flag_carved_kernel(Table T, Planes P, Box box, uint32_t min_count, uint32_t num, uint32_t den,
-                                                               uint8_t *flag)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i > T.mask) return;
-    bool           keep = false;
-    const uint32_t c = T.count[i];
-    if (T.key[i] != kEmpty && c >= min_count && c > 0) {
-        const uint32_t seen = P.seen[i];
-        keep = (uint64_t)P.miss[i] * den <= (uint64_t)(seen > 1u ? seen : 1u) * num;
-        if (keep && box.on) {
-            const float x = centroid(T.sum[0][i], c), y = centroid(T.sum[1][i], c);
-            keep = box.lo[0] <= x && x <= box.hi[0] && box.lo[1] <= y && y <= box.hi[1];
-        }
-    }
-    flag[i] = keep ? 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void vmap_write_carve_kernel(Planes P, const uint32_t *slot, const uint64_t *key, int n, uint32_t *seen,
-                                                               uint32_t *miss, uint64_t *key_out)
+// The three write kernels below serve the host readers alone, which take the keys from the sort's output: a null column
+// is one the caller did not ask for.
+__global__ __launch_bounds__(256) void vmap_write_carve_kernel(Planes P, const uint32_t *slot, int n, uint32_t *seen, uint32_t *miss)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)n) return;
     const uint32_t s = slot[i];
     if (seen) seen[i] = P.seen[s];
     if (miss) miss[i] = P.miss[s];
-    if (key_out) key_out[i] = key[i];
 }
 
 // ---------------------------------------------------------------- moments and distributions (docs/VOXEL_MAP.md section 9)
-struct Moments {
-    unsigned long long *E[3], *M[6]; // first moments, then xx xy xz yy yz zz
-};
 struct Dist {
     float4 *cen; // centroid; w = 1.0f for a plane voxel
     double *nrm, *cov, *eig;
@@ -402,82 +387,6 @@ struct DistRule {
     uint32_t min_points, miss_num, miss_den; // miss_den = 0: the carve planes are not asked
     double   flat_ratio, line_ratio, eps;
 };
-
-// vmap_integrate_kernel with the moments: e = (fx - cell L) >> 4 per axis, |e| <= 2^20 (section 9 has the bound).
-__global__ __launch_bounds__(256) void vmap_integrate_moments_kernel(const float *xyz, int n, int stride, Transform X, double leaf, long long L,
-                                                                     Table T, Moments Q, uint32_t *ctr)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; // n may be close to 2^31
-    if (i >= (size_t)n) return;
-    const float *p = xyz + i * stride;
-    float        q[3] = {p[0], p[1], p[2]};
-    if (X.on) {
-        const double px = q[0], py = q[1], pz = q[2];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            q[k] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(X.r[3 * k], px), __dmul_rn(X.r[3 * k + 1], py)), __dmul_rn(X.r[3 * k + 2], pz)),
-                                    X.t[k]);
-    }
-    uint64_t  key = 0;
-    long long f[3], e[3];
-    bool      keep = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float v = q[k];
-        const double c = floor((double)v / leaf);
-        if (!(fabsf(v) < kCoordLimit) || !(fabs(c) < (double)kCellLimit)) { // written so that a NaN fails both tests
-            keep = false;
-            continue;
-        }
-        key |= (uint64_t)((int)c + kCellLimit) << (21 * k);
-        f[k] = (long long)rint((double)v * kFix);
-        e[k] = (f[k] - (long long)(int)c * L) >> 4; // arithmetic: floor
-    }
-    if (!keep) {
-        atomicAdd(&ctr[kDropped], 1u);
-        return;
-    }
-    const long long h = find_or_claim(T, key, &ctr[kClaimed]);
-    if (h < 0) {
-        atomicExch(&ctr[kError], 1u);
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) atomicAdd(&T.sum[k][h], (unsigned long long)f[k]);
-    atomicAdd(&T.count[h], 1u);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) atomicAdd(&Q.E[k][h], (unsigned long long)e[k]);
-    atomicAdd(&Q.M[0][h], (unsigned long long)(e[0] * e[0]));
-    atomicAdd(&Q.M[1][h], (unsigned long long)(e[0] * e[1]));
-    atomicAdd(&Q.M[2][h], (unsigned long long)(e[0] * e[2]));
-    atomicAdd(&Q.M[3][h], (unsigned long long)(e[1] * e[1]));
-    atomicAdd(&Q.M[4][h], (unsigned long long)(e[1] * e[2]));
-    atomicAdd(&Q.M[5][h], (unsigned long long)(e[2] * e[2]));
-}
-
-// After either rehash kernel: every old voxel's extra planes of 8-byte words go to the slot its key has in the new table.
-// The lookup only finds; keys are distinct, so plain stores.
-constexpr int kMaxMoved = 9;
-struct MovedPlanes {
-    const unsigned long long *from[kMaxMoved];
-    unsigned long long       *to[kMaxMoved];
-    int                       n;
-};
-__global__ __launch_bounds__(256) void vmap_move_planes_kernel(Table from, Table to, MovedPlanes P, uint32_t *ctr)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i > from.mask) return;
-    const uint64_t key = from.key[i];
-    if (key == kEmpty) return;
-    const long long h = find_slot(to, key);
-    if (h < 0) {
-        atomicExch(&ctr[kError], 1u);
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < kMaxMoved; ++k)
-        if (k < P.n) P.to[k][h] = P.from[k][i];
-}
 
 // One lane per slot, sequential f64, every operation rounded on its own (the file is compiled without contraction).
 // `C` is the carve planes of a carved map when the rule asks for them, null pointers otherwise.
@@ -502,10 +411,7 @@ __global__ __launch_bounds__(256) void vmap_distributions_kernel(Table T, Moment
         double       nn[3];
         plane_eigen(c6, lam, nn);
         bool plane = count >= R.min_points && lam[1] >= R.flat_ratio * lam[2] && lam[1] >= R.line_ratio * lam[0];
-        if (plane && R.miss_den > 0 && C.seen) {
-            const uint32_t seen = C.seen[i];
-            plane = (uint64_t)C.miss[i] * R.miss_den <= (uint64_t)(seen > 1u ? seen : 1u) * R.miss_num;
-        }
+        if (plane && R.miss_den > 0 && C.seen) plane = carve_keeps(C, i, R.miss_num, R.miss_den);
         if (plane) {
             cen.w = 1.0f;
 #pragma unroll
@@ -520,29 +426,32 @@ __global__ __launch_bounds__(256) void vmap_distributions_kernel(Table T, Moment
     for (int k = 0; k < 6; ++k) D.cov[6 * i + k] = cov[k];
 }
 
-__global__ __launch_bounds__(256) void vmap_write_moments_kernel(Moments Q, const uint32_t *slot, const uint64_t *key, int n, int64_t *E3, int64_t *M6,
-                                                                 uint64_t *key_out)
+__global__ __launch_bounds__(256) void vmap_write_moments_kernel(Moments Q, const uint32_t *slot, int n, int64_t *E3, int64_t *M6)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)n) return;
     const uint32_t s = slot[i];
-    for (int k = 0; k < 3; ++k) E3[3 * i + k] = (int64_t)Q.E[k][s];
-    for (int k = 0; k < 6; ++k) M6[6 * i + k] = (int64_t)Q.M[k][s];
-    key_out[i] = key[i];
+    if (E3)
+        for (int k = 0; k < 3; ++k) E3[3 * i + k] = (int64_t)Q.E[k][s];
+    if (M6)
+        for (int k = 0; k < 6; ++k) M6[6 * i + k] = (int64_t)Q.M[k][s];
 }
 
-__global__ __launch_bounds__(256) void vmap_write_dist_kernel(Dist D, const uint32_t *slot, const uint64_t *key, int n, double *nrm3, double *cov6,
-                                                              double *eig3, uint64_t *key_out, float *cen3, uint8_t *flag)
+__global__ __launch_bounds__(256) void vmap_write_dist_kernel(Dist D, const uint32_t *slot, int n, double *nrm3, double *cov6, double *eig3,
+                                                              float *cen3, uint8_t *flag)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)n) return;
     const uint32_t s = slot[i];
     const float4   c = D.cen[s];
-    for (int k = 0; k < 3; ++k) nrm3[3 * i + k] = D.nrm[3 * (size_t)s + k], eig3[3 * i + k] = D.eig[3 * (size_t)s + k];
-    for (int k = 0; k < 6; ++k) cov6[6 * i + k] = D.cov[6 * (size_t)s + k];
-    key_out[i] = key[i];
-    cen3[3 * i] = c.x, cen3[3 * i + 1] = c.y, cen3[3 * i + 2] = c.z;
-    flag[i] = c.w != 0.0f ? 1 : 0;
+    for (int k = 0; k < 3; ++k) {
+        if (nrm3) nrm3[3 * i + k] = D.nrm[3 * (size_t)s + k];
+        if (eig3) eig3[3 * i + k] = D.eig[3 * (size_t)s + k];
+    }
+    if (cov6)
+        for (int k = 0; k < 6; ++k) cov6[6 * i + k] = D.cov[6 * (size_t)s + k];
+    if (cen3) cen3[3 * i] = c.x, cen3[3 * i + 1] = c.y, cen3[3 * i + 2] = c.z;
+    if (flag) flag[i] = c.w != 0.0f ? 1 : 0;
 }
 
 // ---------------------------------------------------------------- absorb (docs/VOXEL_MAP.md section 10)
@@ -557,6 +466,14 @@ struct Records {
     int                       slots;
 };
 
+// The points a lane of absorb or coarsen took in, summed over its wave before the one atomic: every lane of the block calls it.
+__device__ __forceinline__ void add_points(uint32_t *ctr, unsigned long long points)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) points += __shfl_xor(points, o);
+    if ((threadIdx.x & 63) == 0 && points) atomicAdd(reinterpret_cast<unsigned long long *>(ctr + kPoints), points);
+}
+
 // One lane per record.  No floating point; nothing waits for another lane; the probe is find_or_claim's, bounded by the
 // capacity.  P.seen is null on a map without carve planes; the host launches records with moments only onto a map that has
 // the planes Q (and never records without onto such a map).  A wave sums its accepted counts before the one atomic.
@@ -568,10 +485,8 @@ __global__ __launch_bounds__(256) void vmap_absorb_kernel(Records S, uint64_t n,
         const uint64_t key = S.key[i];
         if (!(S.slots && key == kEmpty)) {
             const uint32_t c = S.count[i];
-            bool           ok = c != 0u && !(key >> 63); // all ones has bit 63 set
-#pragma unroll
-            for (int k = 0; k < 3; ++k) ok = ok && ((key >> (21 * k)) & 0x1fffffull) != 0x1fffffull;
-            if (!ok) {
+            int            cell[3];
+            if (c == 0u || !vmap_key_cell(key, cell)) {
                 atomicAdd(&ctr[kDropped], 1u);
             } else {
                 const long long h = find_or_claim(T, key, &ctr[kClaimed]);
@@ -596,9 +511,7 @@ __global__ __launch_bounds__(256) void vmap_absorb_kernel(Records S, uint64_t n,
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) points += __shfl_xor(points, o);
-    if ((threadIdx.x & 63) == 0 && points) atomicAdd(reinterpret_cast<unsigned long long *>(ctr + kPoints), points);
+    add_points(ctr, points);
 }
 
 // ---------------------------------------------------------------- coarsen (docs/VOXEL_MAP.md section 11)
@@ -615,16 +528,15 @@ __global__ __launch_bounds__(256) void vmap_coarsen_kernel(Table S, Moments SQ, 
     if (i <= S.mask) {
         const uint64_t key = S.key[i];
         if (key != kEmpty) {
-            uint64_t  parent = 0;
+            int       cell[3], up[3];
             long long s[3];
+            vmap_key_cell(key, cell);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                const int cell = (int)((key >> (21 * k)) & 0x1fffffull) - kCellLimit;
-                const int up = cell >> shift; // arithmetic: floor
-                parent |= (uint64_t)(up + kCellLimit) << (21 * k);
-                s[k] = (long long)(cell - up * (1 << shift)) * unit;
+                up[k] = cell[k] >> shift; // arithmetic: floor
+                s[k] = (long long)(cell[k] - up[k] * (1 << shift)) * unit;
             }
-            const long long h = find_or_claim(T, parent, &ctr[kClaimed]);
+            const long long h = find_or_claim(T, vmap_cell_key(up), &ctr[kClaimed]);
             if (h < 0) {
                 atomicExch(&ctr[kError], 1u);
             } else {
@@ -651,9 +563,7 @@ __global__ __launch_bounds__(256) void vmap_coarsen_kernel(Table S, Moments SQ, 
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) points += __shfl_xor(points, o);
-    if ((threadIdx.x & 63) == 0 && points) atomicAdd(reinterpret_cast<unsigned long long *>(ctr + kPoints), points);
+    add_points(ctr, points);
 }
 
 inline unsigned blocks_for(uint64_t n) { return (unsigned)((n + 255) / 256); }
@@ -691,7 +601,7 @@ struct slam_vmap {
         for (int k = 0; k < 6; ++k) Q.M[k] = p + (size_t)cap * (3 + k);
         return Q;
     }
-    Moments moments() const { return moments(mom, capacity); }
+    Moments moments() const { return dist_on ? moments(mom, capacity) : Moments{}; } // null pointers without distributions
     Dist    dists() const
     {
         Dist     D;
@@ -704,7 +614,10 @@ struct slam_vmap {
     }
 
     bool   carved() const { return stamp.p != nullptr; }
-    Planes planes() const { return Planes{seen.as<uint32_t>(), miss.as<uint32_t>(), stamp.as<uint32_t>()}; }
+    Planes planes() const // null pointers on a map never carved
+    {
+        return carved() ? Planes{seen.as<uint32_t>(), miss.as<uint32_t>(), stamp.as<uint32_t>()} : Planes{nullptr, nullptr, nullptr};
+    }
 
     static Table view(const DevMem &b, int64_t cap)
     {
@@ -721,15 +634,48 @@ struct slam_vmap {
 
 namespace {
 
+// One call's use of a block of device counters (words W).  open() names the pinned words they will be fetched into and zeroes
+// the block on st; fetch() copies the whole block there and waits for st.  The calls that change the map open before their
+// launches, so that nothing runs whose outcome could not be read; select_slots, which changes nothing and whose rocprim call
+// writes its word itself, opens without zeroing just before it fetches.  The pinned words are the thread's scratch: they hold
+// until the next call that asks for it.
+template <class W>
+struct Counters {
+    const DevMem &dev;
+    hipStream_t   st;
+    W            *h = nullptr;
+
+    int open(bool zero = true)
+    {
+        h = static_cast<W *>(pinned_scratch(dev.cap));
+        SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
+        if (zero) SLAM_HIP(hipMemsetAsync(dev.p, 0, dev.cap, st));
+        return SLAM_OK;
+    }
+    int fetch()
+    {
+        SLAM_HIP(hipMemcpyAsync(h, dev.p, dev.cap, hipMemcpyDeviceToHost, st));
+        SLAM_HIP(hipStreamSynchronize(st));
+        return SLAM_OK;
+    }
+    W operator[](int k) const { return h[k]; }
+};
+
+// every slot of the table in `b` empty, its sums and counts zero: enqueued on st
+int clear_table(const DevMem &b, int64_t cap, hipStream_t st)
+{
+    SLAM_HIP(hipMemsetAsync(b.p, 0xff, (size_t)cap * 8, st));
+    SLAM_HIP(hipMemsetAsync(b.as<uint8_t>() + (size_t)cap * 8, 0, (size_t)cap * (kSlotBytes - 8), st));
+    return SLAM_OK;
+}
+
 // an empty table of `cap` slots in `b`, enqueued on st
 int new_table(DevMem &b, int64_t cap, hipStream_t st)
 {
     SLAM_REQUIRE(cap <= kMaxSlots, SLAM_E_NOMEM, "slam_vmap: a table of %lld slots is more than the %lld a map may have", (long long)cap,
                  (long long)kMaxSlots);
     SLAM_TRY(b.alloc((size_t)cap * kSlotBytes));
-    SLAM_HIP(hipMemsetAsync(b.p, 0xff, (size_t)cap * 8, st));
-    SLAM_HIP(hipMemsetAsync(b.as<uint8_t>() + (size_t)cap * 8, 0, (size_t)cap * (kSlotBytes - 8), st));
-    return SLAM_OK;
+    return clear_table(b, cap, st);
 }
 
 int64_t pow2_at_least(int64_t v)
@@ -739,51 +685,39 @@ int64_t pow2_at_least(int64_t v)
     return c;
 }
 
-// Room for n more points under the load rule; waits for st when it grows (the old table is freed afterwards).
+// `bytes` of zeros in `b`, enqueued on st
+int new_zeroed(DevMem &b, size_t bytes, hipStream_t st)
+{
+    SLAM_TRY(b.alloc(bytes));
+    SLAM_HIP(hipMemsetAsync(b.p, 0, bytes, st));
+    return SLAM_OK;
+}
+
+// Room for n more points under the load rule; waits for st when it grows (the old blocks are freed afterwards).  Every new
+// block is allocated and cleared first, one launch moves whatever the map has, and only a rehash that placed every voxel
+// puts the new blocks into the handle: a failure leaves the old map as it was.
 int make_room(slam_vmap *m, int64_t n, hipStream_t st)
 {
     if (m->n_voxels + n <= m->capacity / 2) return SLAM_OK;
     const int64_t cap = pow2_at_least(2 * (m->n_voxels + n));
-    DevMem        nt;
+    DevMem        nt, np[3], nm, nd; // the table; seen, miss, stamp; the moments and the distributions
     SLAM_TRY(new_table(nt, cap, st));
-    SLAM_HIP(hipMemsetAsync(m->ctr.p, 0, kCounters * sizeof(uint32_t), st));
-    DevMem np[3]; // seen, miss, stamp of the new table, when the map has been carved
-    if (m->carved()) {
-        for (DevMem &b : np) {
-            SLAM_TRY(b.alloc((size_t)cap * sizeof(uint32_t)));
-            SLAM_HIP(hipMemsetAsync(b.p, 0, (size_t)cap * sizeof(uint32_t), st));
-        }
-        hipLaunchKernelGGL(vmap_rehash_carved_kernel, dim3(blocks_for((uint64_t)m->capacity)), dim3(256), 0, st, m->view(), m->planes(),
-                           slam_vmap::view(nt, cap), Planes{np[0].as<uint32_t>(), np[1].as<uint32_t>(), np[2].as<uint32_t>()}, m->ctr.as<uint32_t>());
-    } else {
-        hipLaunchKernelGGL(vmap_rehash_kernel, dim3(blocks_for((uint64_t)m->capacity)), dim3(256), 0, st, m->view(), slam_vmap::view(nt, cap),
-                           m->ctr.as<uint32_t>());
-    }
-    SLAM_HIP(hipGetLastError());
-    uint32_t *h = static_cast<uint32_t *>(pinned_scratch(kCounters * sizeof(uint32_t)));
-    SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
-    SLAM_HIP(hipMemcpyAsync(h, m->ctr.p, kCounters * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    SLAM_HIP(hipStreamSynchronize(st));
-    SLAM_REQUIRE(!h[kError] && (int64_t)h[kClaimed] == m->n_voxels, SLAM_E_HIP, "slam_vmap: the rehash moved %u of %lld voxels (error word %u)",
-                 h[kClaimed], (long long)m->n_voxels, h[kError]);
-    DevMem nm, nd; // the moments and distributions of the new table, when the map has them
+    if (m->carved())
+        for (DevMem &b : np) SLAM_TRY(new_zeroed(b, (size_t)cap * sizeof(uint32_t), st));
     if (m->dist_on) {
-        SLAM_TRY(nm.alloc((size_t)cap * kMomentBytes));
+        SLAM_TRY(new_zeroed(nm, (size_t)cap * kMomentBytes, st));
         SLAM_TRY(nd.alloc((size_t)cap * kDistBytes));
-        SLAM_HIP(hipMemsetAsync(nm.p, 0, (size_t)cap * kMomentBytes, st));
-        SLAM_HIP(hipMemsetAsync(m->ctr.p, 0, kCounters * sizeof(uint32_t), st));
-        MovedPlanes   P{};
-        const Moments qf = m->moments(), qt = slam_vmap::moments(nm, cap);
-        for (int k = 0; k < 3; ++k) P.from[k] = qf.E[k], P.to[k] = qt.E[k];
-        for (int k = 0; k < 6; ++k) P.from[3 + k] = qf.M[k], P.to[3 + k] = qt.M[k];
-        P.n = 9;
-        hipLaunchKernelGGL(vmap_move_planes_kernel, dim3(blocks_for((uint64_t)m->capacity)), dim3(256), 0, st, m->view(), slam_vmap::view(nt, cap), P,
-                           m->ctr.as<uint32_t>());
-        SLAM_HIP(hipGetLastError());
-        SLAM_HIP(hipMemcpyAsync(h, m->ctr.p, kCounters * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        SLAM_HIP(hipStreamSynchronize(st));
-        SLAM_REQUIRE(!h[kError], SLAM_E_HIP, "slam_vmap: the rehash lost a voxel's moments");
     }
+    Counters<uint32_t> c{m->ctr, st};
+    SLAM_TRY(c.open());
+    const Planes  pt = m->carved() ? Planes{np[0].as<uint32_t>(), np[1].as<uint32_t>(), np[2].as<uint32_t>()} : Planes{nullptr, nullptr, nullptr};
+    const Moments qt = m->dist_on ? slam_vmap::moments(nm, cap) : Moments{};
+    hipLaunchKernelGGL(vmap_rehash_kernel, dim3(blocks_for((uint64_t)m->capacity)), dim3(256), 0, st, m->view(), m->planes(), m->moments(),
+                       slam_vmap::view(nt, cap), pt, qt, m->ctr.as<uint32_t>());
+    SLAM_HIP(hipGetLastError());
+    SLAM_TRY(c.fetch());
+    SLAM_REQUIRE(!c[kError] && (int64_t)c[kClaimed] == m->n_voxels, SLAM_E_HIP, "slam_vmap: the rehash moved %u of %lld voxels (error word %u)",
+                 c[kClaimed], (long long)m->n_voxels, c[kError]);
     m->table = std::move(nt);
     if (m->carved()) m->seen = std::move(np[0]), m->miss = std::move(np[1]), m->stamp = std::move(np[2]);
     if (m->dist_on) m->mom = std::move(nm), m->dist = std::move(nd), m->dist_stale = true;
@@ -797,13 +731,9 @@ int ensure_carve_planes(slam_vmap *m, hipStream_t st)
     if (m->carved()) return SLAM_OK;
     const size_t plane = (size_t)m->capacity * sizeof(uint32_t);
     SLAM_TRY(m->cctr.alloc(kCarveCounters * sizeof(unsigned long long)));
-    SLAM_TRY(m->seen.alloc(plane));
-    SLAM_TRY(m->miss.alloc(plane));
-    SLAM_HIP(hipMemsetAsync(m->seen.p, 0, plane, st));
-    SLAM_HIP(hipMemsetAsync(m->miss.p, 0, plane, st));
-    SLAM_TRY(m->stamp.alloc(plane)); // last: carved() is true only when all three stand
-    SLAM_HIP(hipMemsetAsync(m->stamp.p, 0, plane, st));
-    return SLAM_OK;
+    SLAM_TRY(new_zeroed(m->seen, plane, st));
+    SLAM_TRY(new_zeroed(m->miss, plane, st));
+    return new_zeroed(m->stamp, plane, st); // last: carved() is true only when all three stand
 }
 
 // The qualifying slots into m->sel and their number into *n: waits for st once.
@@ -816,23 +746,20 @@ int select_slots(slam_vmap *m, const float lo[2], const float hi[2], int min_cou
     Box box{};
     box.on = lo != nullptr;
     if (lo) box.lo[0] = lo[0], box.lo[1] = lo[1], box.hi[0] = hi[0], box.hi[1] = hi[1];
-    uint32_t *d_n = m->ctr.as<uint32_t>() + kSelected;
-    if (ratio && m->carved())
-        hipLaunchKernelGGL(vmap_flag_carved_kernel, dim3(blocks_for(cap)), dim3(256), 0, st, m->view(), m->planes(), box, (uint32_t)min_count, ratio[0],
-                           ratio[1], m->flag.as<uint8_t>());
-    else
-        hipLaunchKernelGGL(vmap_flag_kernel, dim3(blocks_for(cap)), dim3(256), 0, st, m->view(), box, (uint32_t)min_count, m->flag.as<uint8_t>());
+    uint32_t    *d_n = m->ctr.as<uint32_t>() + kSelected;
+    const Planes P = ratio ? m->planes() : Planes{nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(vmap_flag_kernel, dim3(blocks_for(cap)), dim3(256), 0, st, m->view(), P, box, (uint32_t)min_count, ratio ? ratio[0] : 0u,
+                       ratio ? ratio[1] : 0u, m->flag.as<uint8_t>());
     SLAM_HIP(hipGetLastError());
     size_t tb = 0;
     SLAM_HIP(rocprim::select(nullptr, tb, rocprim::counting_iterator<uint32_t>(0), m->flag.as<uint8_t>(), m->sel.as<uint32_t>(), d_n, (size_t)cap, st));
     SLAM_TRY(m->tmp.reserve(tb + 16));
     tb = m->tmp.cap;
     SLAM_HIP(rocprim::select(m->tmp.p, tb, rocprim::counting_iterator<uint32_t>(0), m->flag.as<uint8_t>(), m->sel.as<uint32_t>(), d_n, (size_t)cap, st));
-    uint32_t *h = static_cast<uint32_t *>(pinned_scratch(sizeof(uint32_t)));
-    SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
-    SLAM_HIP(hipMemcpyAsync(h, d_n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    SLAM_HIP(hipStreamSynchronize(st));
-    *n = (int64_t)*h;
+    Counters<uint32_t> c{m->ctr, st};
+    SLAM_TRY(c.open(false)); // the select wrote its word
+    SLAM_TRY(c.fetch());
+    *n = (int64_t)c[kSelected];
     return SLAM_OK;
 }
 
@@ -859,12 +786,12 @@ int sort_slots(slam_vmap *m, int n, hipStream_t st)
 }
 
 // The n selected slots in key order into the caller's device arrays: asynchronous.
-int sort_and_write(slam_vmap *m, int n, float *d_xyz4, uint32_t *d_count, uint64_t *d_key, hipStream_t st, int64_t *d_sums = nullptr)
+int sort_and_write(slam_vmap *m, int n, float *d_xyz4, uint32_t *d_count, uint64_t *d_key, hipStream_t st)
 {
     if (n == 0) return SLAM_OK;
     SLAM_TRY(sort_slots(m, n, st));
     hipLaunchKernelGGL(vmap_write_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, st, m->view(), m->sel_sorted.as<uint32_t>(),
-                       m->keys_out.as<uint64_t>(), n, d_xyz4, d_count, d_key, d_sums);
+                       m->keys_out.as<uint64_t>(), n, d_xyz4, d_count, d_key, (int64_t *)nullptr);
     SLAM_HIP(hipGetLastError());
     return SLAM_OK;
 }
@@ -873,6 +800,124 @@ int check_extract(const char *who, slam_vmap *m, const float *lo, const float *h
 {
     SLAM_REQUIRE(m && n_out && cap >= 0 && min_count >= 0 && (lo == nullptr) == (hi == nullptr), SLAM_E_INVALID,
                  "%s: a map, n_out, cap >= 0, min_count >= 0, and lo_xy and hi_xy both or neither", who);
+    return SLAM_OK;
+}
+
+// What a host reader asks for, one array per column in key order: a null pointer is a column not wanted.
+struct Wanted {
+    float    *xyz4;
+    uint32_t *count;
+    uint64_t *key;
+    int64_t  *sums;
+    uint32_t *seen, *miss; // zeros from a map never carved
+    int64_t  *E3, *M6;     // the caller has made sure of the moments,
+    float    *cen3;        // and has brought the distributions up to date
+    double   *nrm3, *cov6, *eig3;
+    uint8_t  *flag;
+};
+struct Column {
+    void    *host;
+    size_t   width, align; // bytes a voxel; what the write kernel's stores need
+    uint8_t *dev;
+    template <class T>
+    T *as() const
+    {
+        return reinterpret_cast<T *>(dev);
+    }
+};
+
+// Every host reader: check, select, sort, then the wanted columns laid out in stage_out one behind the other, each aligned
+// to its type, written by their families' kernels and copied back.  All on the null stream; waits for it.
+int read_columns(const char *who, slam_vmap *m, const float *lo, const float *hi, int min_count, const uint32_t *ratio, Wanted w, int cap, int *n_out)
+{
+    SLAM_TRY(check_extract(who, m, lo, hi, min_count, cap, n_out));
+    int64_t n = 0;
+    SLAM_TRY(select_slots(m, lo, hi, min_count, nullptr, &n, ratio));
+    *n_out = (int)n;
+    SLAM_REQUIRE(n <= cap, SLAM_E_NOMEM, "%s: %lld voxels, room for %d", who, (long long)n, cap);
+    if (n == 0) return SLAM_OK;
+    const size_t N = (size_t)n;
+    SLAM_TRY(sort_slots(m, (int)n, nullptr));
+    if (!m->carved()) {
+        if (w.seen) std::memset(w.seen, 0, N * sizeof(uint32_t));
+        if (w.miss) std::memset(w.miss, 0, N * sizeof(uint32_t));
+        w.seen = w.miss = nullptr;
+    }
+    enum { cSums, cE, cM, cNrm, cCov, cEig, cXyz4, cCen, cCount, cSeen, cMiss, cFlag, kColumns };
+    Column col[kColumns] = {{w.sums, 24, 8, nullptr}, {w.E3, 24, 8, nullptr},   {w.M6, 48, 8, nullptr},  {w.nrm3, 24, 8, nullptr},
+                            {w.cov6, 48, 8, nullptr}, {w.eig3, 24, 8, nullptr}, {w.xyz4, 16, 16, nullptr}, {w.cen3, 12, 4, nullptr},
+                            {w.count, 4, 4, nullptr}, {w.seen, 4, 4, nullptr},  {w.miss, 4, 4, nullptr}, {w.flag, 1, 1, nullptr}};
+    size_t end = 0, at[kColumns];
+    for (int k = 0; k < kColumns; ++k)
+        if (col[k].host) {
+            at[k] = (end + col[k].align - 1) / col[k].align * col[k].align;
+            end = at[k] + N * col[k].width;
+        }
+    SLAM_TRY(reserve_quarter(m->stage_out, end));
+    for (int k = 0; k < kColumns; ++k)
+        if (col[k].host) col[k].dev = m->stage_out.as<uint8_t>() + at[k];
+    const uint32_t *slot = m->sel_sorted.as<uint32_t>();
+    const dim3      grid(blocks_for((uint64_t)n)), block(256);
+    if (w.sums || w.xyz4 || w.count)
+        hipLaunchKernelGGL(vmap_write_kernel, grid, block, 0, nullptr, m->view(), slot, m->keys_out.as<uint64_t>(), (int)n, col[cXyz4].as<float>(),
+                           col[cCount].as<uint32_t>(), (uint64_t *)nullptr, col[cSums].as<int64_t>());
+    if (w.seen || w.miss)
+        hipLaunchKernelGGL(vmap_write_carve_kernel, grid, block, 0, nullptr, m->planes(), slot, (int)n, col[cSeen].as<uint32_t>(), col[cMiss].as<uint32_t>());
+    if (w.E3 || w.M6)
+        hipLaunchKernelGGL(vmap_write_moments_kernel, grid, block, 0, nullptr, m->moments(), slot, (int)n, col[cE].as<int64_t>(), col[cM].as<int64_t>());
+    if (w.cen3 || w.nrm3 || w.cov6 || w.eig3 || w.flag)
+        hipLaunchKernelGGL(vmap_write_dist_kernel, grid, block, 0, nullptr, m->dists(), slot, (int)n, col[cNrm].as<double>(), col[cCov].as<double>(),
+                           col[cEig].as<double>(), col[cCen].as<float>(), col[cFlag].as<uint8_t>());
+    SLAM_HIP(hipGetLastError());
+    for (const Column &c : col)
+        if (c.host) SLAM_HIP(hipMemcpy(c.host, c.dev, N * c.width, hipMemcpyDeviceToHost));
+    if (w.key) SLAM_HIP(hipMemcpy(w.key, m->keys_out.p, N * sizeof(uint64_t), hipMemcpyDeviceToHost)); // as the sort left them
+    SLAM_HIP(hipStreamSynchronize(nullptr));
+    return SLAM_OK;
+}
+
+Transform make_transform(const double *R, const double *t)
+{
+    Transform X{};
+    X.on = R != nullptr;
+    if (R) {
+        for (int k = 0; k < 9; ++k) X.r[k] = R[k];
+        for (int k = 0; k < 3; ++k) X.t[k] = t[k];
+    }
+    return X;
+}
+
+// a host cloud into stage_in (nothing for n = 0): synchronous
+int stage_cloud(slam_vmap *m, const float *xyz, int n, int stride)
+{
+    const size_t bytes = (size_t)n * stride * sizeof(float);
+    if (!bytes) return SLAM_OK;
+    SLAM_TRY(reserve_quarter(m->stage_in, bytes));
+    SLAM_HIP(hipMemcpy(m->stage_in.p, xyz, bytes, hipMemcpyHostToDevice));
+    return SLAM_OK;
+}
+
+// The host half of absorb, merge and coarsen: room in m for `n_new` more voxels, the carve planes when the records bring seen
+// and miss (after the growth: at the table's size), absorb's counter block, the launch -- the one thing that differs, so
+// `launch(ctr)` is the caller's -- and the handle's counts.  Waits once for st.  `lost` names what a full table would lose.
+template <class Launch>
+int absorb_with(const char *who, const char *lost, slam_vmap *m, bool with_carve, int64_t n_new, int64_t *n_rejected, hipStream_t st,
+                Launch launch)
+{
+    SLAM_TRY(make_room(m, n_new, st));
+    if (with_carve) SLAM_TRY(ensure_carve_planes(m, st));
+    if (!m->actr.p) SLAM_TRY(m->actr.alloc(kAbsorbCounters * sizeof(uint32_t)));
+    Counters<uint32_t> c{m->actr, st};
+    SLAM_TRY(c.open());
+    launch(m->actr.as<uint32_t>());
+    SLAM_HIP(hipGetLastError());
+    m->dist_stale = true;
+    SLAM_TRY(c.fetch());
+    m->n_voxels += c[kClaimed];
+    m->n_points += (int64_t)((uint64_t)c[kPoints] | (uint64_t)c[kPoints + 1] << 32);
+    if (n_rejected) *n_rejected = (int64_t)c[kDropped];
+    SLAM_REQUIRE(!c[kError], SLAM_E_HIP, "%s: a probe ran through all %lld slots (%lld voxels): %s were lost", who, (long long)m->capacity,
+                 (long long)m->n_voxels, lost);
     return SLAM_OK;
 }
 
@@ -926,8 +971,7 @@ int slam_vmap_clear(slam_vmap_t *m, slam_stream_t stream)
 {
     SLAM_REQUIRE(m, SLAM_E_INVALID, "slam_vmap_clear: map is NULL");
     hipStream_t st = as_stream(stream);
-    SLAM_HIP(hipMemsetAsync(m->table.p, 0xff, (size_t)m->capacity * 8, st));
-    SLAM_HIP(hipMemsetAsync(m->table.as<uint8_t>() + (size_t)m->capacity * 8, 0, (size_t)m->capacity * (kSlotBytes - 8), st));
+    SLAM_TRY(clear_table(m->table, m->capacity, st));
     if (m->carved())
         for (DevMem *b : {&m->seen, &m->miss, &m->stamp}) SLAM_HIP(hipMemsetAsync(b->p, 0, (size_t)m->capacity * sizeof(uint32_t), st));
     if (m->dist_on) {
@@ -947,30 +991,18 @@ int slam_vmap_integrate_dev(slam_vmap_t *m, const float *d_xyz, int n, int strid
     if (n == 0) return SLAM_OK;
     hipStream_t st = as_stream(stream);
     SLAM_TRY(make_room(m, n, st));
-    Transform X{};
-    X.on = R != nullptr;
-    if (R) {
-        for (int k = 0; k < 9; ++k) X.r[k] = R[k];
-        for (int k = 0; k < 3; ++k) X.t[k] = t[k];
-    }
-    uint32_t *h = static_cast<uint32_t *>(pinned_scratch(kCounters * sizeof(uint32_t)));
-    SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
-    SLAM_HIP(hipMemsetAsync(m->ctr.p, 0, kCounters * sizeof(uint32_t), st));
-    if (m->dist_on) {
-        hipLaunchKernelGGL(vmap_integrate_moments_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, st, d_xyz, n, stride, X, m->P.leaf,
-                           (long long)std::rint(m->P.leaf * kFix), m->view(), m->moments(), m->ctr.as<uint32_t>());
-        m->dist_stale = true;
-    } else {
-        hipLaunchKernelGGL(vmap_integrate_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, st, d_xyz, n, stride, X, m->P.leaf, m->view(),
-                           m->ctr.as<uint32_t>());
-    }
+    Counters<uint32_t> c{m->ctr, st};
+    SLAM_TRY(c.open());
+    const auto kernel = m->dist_on ? vmap_integrate_kernel<true> : vmap_integrate_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, st, d_xyz, n, stride, make_transform(R, t), m->P.leaf,
+                       (long long)std::rint(m->P.leaf * kFix), m->view(), m->moments(), m->ctr.as<uint32_t>());
+    if (m->dist_on) m->dist_stale = true;
     SLAM_HIP(hipGetLastError());
-    SLAM_HIP(hipMemcpyAsync(h, m->ctr.p, kCounters * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    SLAM_HIP(hipStreamSynchronize(st));
-    m->n_voxels += h[kClaimed];
-    m->n_points += (int64_t)n - h[kDropped];
-    if (n_dropped) *n_dropped = (int)h[kDropped];
-    SLAM_REQUIRE(!h[kError], SLAM_E_HIP, "slam_vmap_integrate: a probe ran through all %lld slots (%lld voxels): points were lost",
+    SLAM_TRY(c.fetch());
+    m->n_voxels += c[kClaimed];
+    m->n_points += (int64_t)n - c[kDropped];
+    if (n_dropped) *n_dropped = (int)c[kDropped];
+    SLAM_REQUIRE(!c[kError], SLAM_E_HIP, "slam_vmap_integrate: a probe ran through all %lld slots (%lld voxels): points were lost",
                  (long long)m->capacity, (long long)m->n_voxels);
     return SLAM_OK;
 }
@@ -981,9 +1013,7 @@ int slam_vmap_integrate(slam_vmap_t *m, const float *xyz, int n, int stride, con
                  "slam_vmap_integrate: a map, n >= 0, stride >= 3, points, and R and t both or neither");
     if (n_dropped) *n_dropped = 0;
     if (n == 0) return SLAM_OK;
-    const size_t bytes = (size_t)n * stride * sizeof(float);
-    SLAM_TRY(reserve_quarter(m->stage_in, bytes));
-    SLAM_HIP(hipMemcpy(m->stage_in.p, xyz, bytes, hipMemcpyHostToDevice));
+    SLAM_TRY(stage_cloud(m, xyz, n, stride));
     return slam_vmap_integrate_dev(m, m->stage_in.as<float>(), n, stride, R, t, n_dropped, nullptr);
 }
 
@@ -999,39 +1029,19 @@ int slam_vmap_extract_dev(slam_vmap_t *m, const float lo_xy[2], const float hi_x
     return sort_and_write(m, (int)n, d_xyz4, d_count, d_key, st);
 }
 
-static int read_host(const char *who, slam_vmap_t *m, const float lo_xy[2], const float hi_xy[2], int min_count, float *xyz4, uint32_t *count,
-                     uint64_t *key, int64_t *sums, int cap, int *n_out, const uint32_t *ratio = nullptr)
-{
-    SLAM_TRY(check_extract(who, m, lo_xy, hi_xy, min_count, cap, n_out));
-    int64_t n = 0;
-    SLAM_TRY(select_slots(m, lo_xy, hi_xy, min_count, nullptr, &n, ratio));
-    *n_out = (int)n;
-    SLAM_REQUIRE(n <= cap, SLAM_E_NOMEM, "%s: %lld voxels, room for %d", who, (long long)n, cap);
-    if (n == 0) return SLAM_OK;
-    const size_t N = (size_t)n;
-    SLAM_TRY(reserve_quarter(m->stage_out, N * 52)); // keys, sums, then centroids, then counts: each aligned to its type
-    uint64_t *d_key = m->stage_out.as<uint64_t>();
-    int64_t  *d_sums = reinterpret_cast<int64_t *>(d_key + N);
-    float    *d_xyz4 = reinterpret_cast<float *>(d_sums + 3 * N);
-    uint32_t *d_count = reinterpret_cast<uint32_t *>(d_xyz4 + 4 * N);
-    SLAM_TRY(sort_and_write(m, (int)n, xyz4 ? d_xyz4 : nullptr, count ? d_count : nullptr, key ? d_key : nullptr, nullptr, sums ? d_sums : nullptr));
-    if (xyz4) SLAM_HIP(hipMemcpy(xyz4, d_xyz4, N * 16, hipMemcpyDeviceToHost));
-    if (count) SLAM_HIP(hipMemcpy(count, d_count, N * 4, hipMemcpyDeviceToHost));
-    if (key) SLAM_HIP(hipMemcpy(key, d_key, N * 8, hipMemcpyDeviceToHost));
-    if (sums) SLAM_HIP(hipMemcpy(sums, d_sums, N * 24, hipMemcpyDeviceToHost));
-    SLAM_HIP(hipStreamSynchronize(nullptr));
-    return SLAM_OK;
-}
-
 int slam_vmap_read(slam_vmap_t *m, const float lo_xy[2], const float hi_xy[2], int min_count, float *xyz4, uint32_t *count, uint64_t *key,
                    int cap, int *n_out)
 {
-    return read_host("slam_vmap_read", m, lo_xy, hi_xy, min_count, xyz4, count, key, nullptr, cap, n_out);
+    Wanted w{};
+    w.xyz4 = xyz4, w.count = count, w.key = key;
+    return read_columns("slam_vmap_read", m, lo_xy, hi_xy, min_count, nullptr, w, cap, n_out);
 }
 
 int slam_vmap_read_sums(slam_vmap_t *m, int64_t *sums, uint32_t *count, uint64_t *key, int cap, int *n_out)
 {
-    return read_host("slam_vmap_read_sums", m, nullptr, nullptr, 0, nullptr, count, key, sums, cap, n_out);
+    Wanted w{};
+    w.sums = sums, w.count = count, w.key = key;
+    return read_columns("slam_vmap_read_sums", m, nullptr, nullptr, 0, nullptr, w, cap, n_out);
 }
 
 int slam_vmap_info(slam_vmap_t *m, int64_t *n_voxels, int64_t *capacity, int64_t *n_points, size_t *device_bytes)
@@ -1078,30 +1088,18 @@ int slam_vmap_carve_dev(slam_vmap_t *m, const float *d_xyz, int n, int stride, c
     if (params) p = *params;
     SLAM_TRY(check_carve("slam_vmap_carve_dev", m, d_xyz, n, stride, R, t, p));
     if (result) *result = slam_vmap_carve_result{};
-    Transform X{};
-    X.on = R != nullptr;
-    if (R) {
-        for (int k = 0; k < 9; ++k) X.r[k] = R[k];
-        for (int k = 0; k < 3; ++k) X.t[k] = t[k];
-    }
-    // the origin and its cell, with a point's arithmetic (this file is compiled without contraction): decided before any launch
-    Carve A{};
+    const Transform X = make_transform(R, t);
+    // the origin (f64, not rounded before it is moved) and its cell, with a point's arithmetic: decided before any launch
+    Carve        A{};
     const double o[3] = {origin ? origin[0] : 0.0, origin ? origin[1] : 0.0, origin ? origin[2] : 0.0};
-    for (int k = 0; k < 3; ++k) {
-        float v = (float)o[k];
-        if (R) {
-            const double a = R[3 * k] * o[0], b = R[3 * k + 1] * o[1], c = R[3 * k + 2] * o[2];
-            v = (float)(((a + b) + c) + t[k]);
-        }
-        const double c = std::floor((double)v / m->P.leaf);
-        SLAM_REQUIRE(std::fabs(v) < kCoordLimit && std::fabs(c) < (double)kCellLimit, SLAM_E_INVALID,
-                     "slam_vmap_carve: the origin has no cell (axis %d: %g)", k, (double)v);
-        A.c0[k] = (int)c;
-    }
+    float        O[3];
+    moved_point(o, X, O);
+    for (int k = 0; k < 3; ++k)
+        SLAM_REQUIRE(vmap_axis_cell(O[k], m->P.leaf, &A.c0[k]), SLAM_E_INVALID, "slam_vmap_carve: the origin has no cell (axis %d: %g)", k, (double)O[k]);
     A.end_margin = p.end_margin, A.tail_num = p.tail_num, A.tail_den = p.tail_den, A.max_ray_cells = p.max_ray_cells;
     if (n == 0) return SLAM_OK;
     // chunks travel as u32 through the scan: a ray has at most 2^21 cells
-    const int64_t longest = p.max_ray_cells < 2 * kCellLimit ? p.max_ray_cells : 2 * kCellLimit;
+    const int64_t longest = p.max_ray_cells < 2 * kVmapCellLimit ? p.max_ray_cells : 2 * kVmapCellLimit;
     const int64_t max_chunks = (int64_t)n * ((longest + kChunk - 1) / kChunk);
     SLAM_REQUIRE(max_chunks < (1ll << 32), SLAM_E_NOMEM, "slam_vmap_carve: %d rays of up to %lld cells are more than 2^32 chunks of %d steps", n,
                  (long long)longest, kChunk);
@@ -1122,11 +1120,10 @@ int slam_vmap_carve_dev(slam_vmap_t *m, const float *d_xyz, int n, int stride, c
     SLAM_HIP(rocprim::exclusive_scan(nullptr, tb, m->chunks.as<uint32_t>(), m->offs.as<uint32_t>(), 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
     SLAM_TRY(m->tmp.reserve(tb + 16));
     tb = m->tmp.cap;
-    unsigned long long *h = static_cast<unsigned long long *>(pinned_scratch(kCarveCounters * sizeof(unsigned long long)));
-    SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
 
-    unsigned long long *d_ctr = m->cctr.as<unsigned long long>();
-    SLAM_HIP(hipMemsetAsync(d_ctr, 0, kCarveCounters * sizeof(unsigned long long), st));
+    unsigned long long          *d_ctr = m->cctr.as<unsigned long long>();
+    Counters<unsigned long long> c{m->cctr, st};
+    SLAM_TRY(c.open());
     hipLaunchKernelGGL(vmap_carve_rays_kernel, dim3(blocks_for((uint64_t)n + 1)), dim3(256), 0, st, d_xyz, n, stride, X, m->P.leaf, m->view(),
                        m->planes(), A, m->rays.as<int4>(), m->chunks.as<uint32_t>(), d_ctr);
     SLAM_HIP(hipGetLastError());
@@ -1136,15 +1133,14 @@ int slam_vmap_carve_dev(slam_vmap_t *m, const float *d_xyz, int n, int stride, c
     hipLaunchKernelGGL(vmap_carve_walk_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, m->rays.as<int4>(),
                        m->offs.as<uint32_t>(), n, (uint32_t)max_chunks, m->view(), m->planes(), A, d_ctr);
     SLAM_HIP(hipGetLastError());
-    SLAM_HIP(hipMemcpyAsync(h, d_ctr, kCarveCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    SLAM_HIP(hipStreamSynchronize(st));
+    SLAM_TRY(c.fetch());
     if (result) {
-        result->n_dropped = (int64_t)h[kcDropped];
+        result->n_dropped = (int64_t)c[kcDropped];
         result->n_rays = (int64_t)n - result->n_dropped;
-        result->n_skipped = (int64_t)h[kcSkipped];
-        result->n_steps = (int64_t)h[kcSteps];
-        result->n_seen = (int64_t)h[kcSeen];
-        result->n_missed = (int64_t)h[kcMissed];
+        result->n_skipped = (int64_t)c[kcSkipped];
+        result->n_steps = (int64_t)c[kcSteps];
+        result->n_seen = (int64_t)c[kcSeen];
+        result->n_missed = (int64_t)c[kcMissed];
     }
     return SLAM_OK;
 }
@@ -1156,11 +1152,7 @@ int slam_vmap_carve(slam_vmap_t *m, const float *xyz, int n, int stride, const d
     slam_vmap_default_carve_params(&p);
     if (params) p = *params;
     SLAM_TRY(check_carve("slam_vmap_carve", m, xyz, n, stride, R, t, p));
-    const size_t bytes = (size_t)n * stride * sizeof(float);
-    if (n > 0) {
-        SLAM_TRY(reserve_quarter(m->stage_in, bytes));
-        SLAM_HIP(hipMemcpy(m->stage_in.p, xyz, bytes, hipMemcpyHostToDevice));
-    }
+    SLAM_TRY(stage_cloud(m, xyz, n, stride));
     return slam_vmap_carve_dev(m, m->stage_in.as<float>(), n, stride, R, t, origin, params, result, nullptr);
 }
 
@@ -1191,7 +1183,9 @@ int slam_vmap_read_carved(slam_vmap_t *m, const float lo_xy[2], const float hi_x
 {
     SLAM_TRY(check_carved("slam_vmap_read_carved", m, lo_xy, hi_xy, min_count, max_miss_num, max_miss_den, cap, n_out));
     const uint32_t ratio[2] = {(uint32_t)max_miss_num, (uint32_t)max_miss_den};
-    return read_host("slam_vmap_read_carved", m, lo_xy, hi_xy, min_count, xyz4, count, key, nullptr, cap, n_out, ratio);
+    Wanted         w{};
+    w.xyz4 = xyz4, w.count = count, w.key = key;
+    return read_columns("slam_vmap_read_carved", m, lo_xy, hi_xy, min_count, ratio, w, cap, n_out);
 }
 
 int slam_vmap_read_carve(slam_vmap_t *m, uint32_t *seen, uint32_t *miss, uint64_t *key, int cap, int *n_out)
@@ -1199,30 +1193,9 @@ int slam_vmap_read_carve(slam_vmap_t *m, uint32_t *seen, uint32_t *miss, uint64_
     SLAM_REQUIRE(n_out && cap >= 0, SLAM_E_INVALID, "slam_vmap_read_carve: n_out and cap >= 0");
     SLAM_TRY(require_device());
     SLAM_REQUIRE(m, SLAM_E_INVALID, "slam_vmap_read_carve: map is NULL");
-    int64_t n = 0;
-    SLAM_TRY(select_slots(m, nullptr, nullptr, 0, nullptr, &n));
-    *n_out = (int)n;
-    SLAM_REQUIRE(n <= cap, SLAM_E_NOMEM, "slam_vmap_read_carve: %lld voxels, room for %d", (long long)n, cap);
-    if (n == 0) return SLAM_OK;
-    const size_t N = (size_t)n;
-    SLAM_TRY(reserve_quarter(m->stage_out, N * 16)); // keys, then seen, then miss
-    uint64_t *d_key = m->stage_out.as<uint64_t>();
-    uint32_t *d_seen = reinterpret_cast<uint32_t *>(d_key + N), *d_miss = d_seen + N;
-    SLAM_TRY(sort_slots(m, (int)n, nullptr));
-    if (m->carved()) {
-        hipLaunchKernelGGL(vmap_write_carve_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, nullptr, m->planes(), m->sel_sorted.as<uint32_t>(),
-                           m->keys_out.as<uint64_t>(), (int)n, d_seen, d_miss, d_key);
-        SLAM_HIP(hipGetLastError());
-        if (seen) SLAM_HIP(hipMemcpy(seen, d_seen, N * 4, hipMemcpyDeviceToHost));
-        if (miss) SLAM_HIP(hipMemcpy(miss, d_miss, N * 4, hipMemcpyDeviceToHost));
-        if (key) SLAM_HIP(hipMemcpy(key, d_key, N * 8, hipMemcpyDeviceToHost));
-    } else { // never carved: zeros, and the keys as the sort left them
-        if (seen) std::memset(seen, 0, N * 4);
-        if (miss) std::memset(miss, 0, N * 4);
-        if (key) SLAM_HIP(hipMemcpy(key, m->keys_out.p, N * 8, hipMemcpyDeviceToHost));
-    }
-    SLAM_HIP(hipStreamSynchronize(nullptr));
-    return SLAM_OK;
+    Wanted w{};
+    w.seen = seen, w.miss = miss, w.key = key;
+    return read_columns("slam_vmap_read_carve", m, nullptr, nullptr, 0, nullptr, w, cap, n_out);
 }
 
 // ---------------------------------------------------------------- moments and distributions (docs/VOXEL_MAP.md section 9)
@@ -1266,21 +1239,10 @@ int slam_vmap_compute_distributions(slam_vmap_t *m, slam_stream_t stream)
     DistRule R;
     R.min_points = (uint32_t)m->DP.min_points, R.miss_num = (uint32_t)m->DP.max_miss_num, R.miss_den = (uint32_t)m->DP.max_miss_den;
     R.flat_ratio = m->DP.flat_ratio, R.line_ratio = m->DP.line_ratio, R.eps = m->DP.epsilon;
-    const Planes C = m->carved() ? m->planes() : Planes{nullptr, nullptr, nullptr};
-    hipLaunchKernelGGL(vmap_distributions_kernel, dim3(blocks_for((uint64_t)m->capacity)), dim3(256), 0, as_stream(stream), m->view(), m->moments(), C, R,
-                       m->dists());
+    hipLaunchKernelGGL(vmap_distributions_kernel, dim3(blocks_for((uint64_t)m->capacity)), dim3(256), 0, as_stream(stream), m->view(), m->moments(),
+                       m->planes(), R, m->dists());
     SLAM_HIP(hipGetLastError());
     m->dist_stale = false;
-    return SLAM_OK;
-}
-
-// every occupied voxel's slot in key order into m->sel_sorted (keys into m->keys_out) on the null stream; *n their number
-static int all_slots_sorted(const char *who, slam_vmap *m, int cap, int *n_out, int64_t *n)
-{
-    SLAM_TRY(select_slots(m, nullptr, nullptr, 0, nullptr, n));
-    *n_out = (int)*n;
-    SLAM_REQUIRE(*n <= cap, SLAM_E_NOMEM, "%s: %lld voxels, room for %d", who, (long long)*n, cap);
-    if (*n) SLAM_TRY(sort_slots(m, (int)*n, nullptr));
     return SLAM_OK;
 }
 
@@ -1289,21 +1251,9 @@ int slam_vmap_read_moments(slam_vmap_t *m, int64_t *E3, int64_t *M6, uint64_t *k
     SLAM_REQUIRE(n_out && cap >= 0, SLAM_E_INVALID, "slam_vmap_read_moments: n_out and cap >= 0");
     SLAM_TRY(require_device());
     SLAM_REQUIRE(m && m->dist_on, SLAM_E_INVALID, "slam_vmap_read_moments: a map with distributions enabled");
-    int64_t n = 0;
-    SLAM_TRY(all_slots_sorted("slam_vmap_read_moments", m, cap, n_out, &n));
-    if (n == 0) return SLAM_OK;
-    const size_t N = (size_t)n;
-    SLAM_TRY(reserve_quarter(m->stage_out, N * 80)); // keys, E, M
-    uint64_t *d_key = m->stage_out.as<uint64_t>();
-    int64_t  *d_E = reinterpret_cast<int64_t *>(d_key + N), *d_M = d_E + 3 * N;
-    hipLaunchKernelGGL(vmap_write_moments_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, nullptr, m->moments(), m->sel_sorted.as<uint32_t>(),
-                       m->keys_out.as<uint64_t>(), (int)n, d_E, d_M, d_key);
-    SLAM_HIP(hipGetLastError());
-    if (E3) SLAM_HIP(hipMemcpy(E3, d_E, N * 24, hipMemcpyDeviceToHost));
-    if (M6) SLAM_HIP(hipMemcpy(M6, d_M, N * 48, hipMemcpyDeviceToHost));
-    if (key) SLAM_HIP(hipMemcpy(key, d_key, N * 8, hipMemcpyDeviceToHost));
-    SLAM_HIP(hipStreamSynchronize(nullptr));
-    return SLAM_OK;
+    Wanted w{};
+    w.E3 = E3, w.M6 = M6, w.key = key;
+    return read_columns("slam_vmap_read_moments", m, nullptr, nullptr, 0, nullptr, w, cap, n_out);
 }
 
 int slam_vmap_read_distributions(slam_vmap_t *m, float *centroid3, double *normal3, double *cov6, double *eig3, uint8_t *flag, uint64_t *key, int cap,
@@ -1313,51 +1263,19 @@ int slam_vmap_read_distributions(slam_vmap_t *m, float *centroid3, double *norma
     SLAM_TRY(require_device());
     SLAM_REQUIRE(m && m->dist_on, SLAM_E_INVALID, "slam_vmap_read_distributions: a map with distributions enabled");
     SLAM_TRY(slam_vmap_compute_distributions(m, nullptr));
-    int64_t n = 0;
-    SLAM_TRY(all_slots_sorted("slam_vmap_read_distributions", m, cap, n_out, &n));
-    if (n == 0) return SLAM_OK;
-    const size_t N = (size_t)n;
-    SLAM_TRY(reserve_quarter(m->stage_out, N * 120)); // normals, covariances, eigenvalues, keys, then centroids, then flags
-    double   *d_nrm = m->stage_out.as<double>(), *d_cov = d_nrm + 3 * N, *d_eig = d_cov + 6 * N;
-    uint64_t *d_key = reinterpret_cast<uint64_t *>(d_eig + 3 * N);
-    float    *d_cen = reinterpret_cast<float *>(d_key + N);
-    uint8_t  *d_flag = reinterpret_cast<uint8_t *>(d_cen + 3 * N);
-    hipLaunchKernelGGL(vmap_write_dist_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, nullptr, m->dists(), m->sel_sorted.as<uint32_t>(),
-                       m->keys_out.as<uint64_t>(), (int)n, d_nrm, d_cov, d_eig, d_key, d_cen, d_flag);
-    SLAM_HIP(hipGetLastError());
-    if (centroid3) SLAM_HIP(hipMemcpy(centroid3, d_cen, N * 12, hipMemcpyDeviceToHost));
-    if (normal3) SLAM_HIP(hipMemcpy(normal3, d_nrm, N * 24, hipMemcpyDeviceToHost));
-    if (cov6) SLAM_HIP(hipMemcpy(cov6, d_cov, N * 48, hipMemcpyDeviceToHost));
-    if (eig3) SLAM_HIP(hipMemcpy(eig3, d_eig, N * 24, hipMemcpyDeviceToHost));
-    if (flag) SLAM_HIP(hipMemcpy(flag, d_flag, N, hipMemcpyDeviceToHost));
-    if (key) SLAM_HIP(hipMemcpy(key, d_key, N * 8, hipMemcpyDeviceToHost));
-    SLAM_HIP(hipStreamSynchronize(nullptr));
-    return SLAM_OK;
+    Wanted w{};
+    w.cen3 = centroid3, w.nrm3 = normal3, w.cov6 = cov6, w.eig3 = eig3, w.flag = flag, w.key = key;
+    return read_columns("slam_vmap_read_distributions", m, nullptr, nullptr, 0, nullptr, w, cap, n_out);
 }
 
+
 // ---------------------------------------------------------------- absorb, merge, save, load (docs/VOXEL_MAP.md section 10)
-// `lanes` records (or source slots) of S into m, with room made for `n_new` more voxels first: waits once for st.
+// `lanes` records (or source slots) of S into m, with room made for `n_new` more voxels first
 static int absorb_records(slam_vmap *m, Records S, uint64_t lanes, int64_t n_new, int64_t *n_rejected, hipStream_t st)
 {
-    SLAM_TRY(make_room(m, n_new, st));
-    if (S.seen) SLAM_TRY(ensure_carve_planes(m, st)); // after the growth: at the table's size
-    if (!m->actr.p) SLAM_TRY(m->actr.alloc(kAbsorbCounters * sizeof(uint32_t)));
-    uint32_t *h = static_cast<uint32_t *>(pinned_scratch(kAbsorbCounters * sizeof(uint32_t)));
-    SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
-    SLAM_HIP(hipMemsetAsync(m->actr.p, 0, kAbsorbCounters * sizeof(uint32_t), st));
-    const Planes  P = m->carved() ? m->planes() : Planes{nullptr, nullptr, nullptr};
-    const Moments Q = m->dist_on ? m->moments() : Moments{};
-    hipLaunchKernelGGL(vmap_absorb_kernel, dim3(blocks_for(lanes)), dim3(256), 0, st, S, lanes, m->view(), P, Q, m->actr.as<uint32_t>());
-    SLAM_HIP(hipGetLastError());
-    m->dist_stale = true;
-    SLAM_HIP(hipMemcpyAsync(h, m->actr.p, kAbsorbCounters * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    SLAM_HIP(hipStreamSynchronize(st));
-    m->n_voxels += h[kClaimed];
-    m->n_points += (int64_t)((uint64_t)h[kPoints] | (uint64_t)h[kPoints + 1] << 32);
-    if (n_rejected) *n_rejected = (int64_t)h[kDropped];
-    SLAM_REQUIRE(!h[kError], SLAM_E_HIP, "slam_vmap_absorb: a probe ran through all %lld slots (%lld voxels): records were lost",
-                 (long long)m->capacity, (long long)m->n_voxels);
-    return SLAM_OK;
+    return absorb_with("slam_vmap_absorb", "records", m, S.seen != nullptr, n_new, n_rejected, st, [&](uint32_t *ctr) {
+        hipLaunchKernelGGL(vmap_absorb_kernel, dim3(blocks_for(lanes)), dim3(256), 0, st, S, lanes, m->view(), m->planes(), m->moments(), ctr);
+    });
 }
 
 static Records packed_records(const uint64_t *key, const uint32_t *count, const int64_t *sums, const uint32_t *seen, const uint32_t *miss,
@@ -1482,25 +1400,11 @@ int slam_vmap_coarsen(slam_vmap_t *dst, slam_vmap_t *src, slam_stream_t stream)
                  "slam_vmap_coarsen: leaf %.17g is no multiple of 2^-16 m: the moments' floor(d / 16) does not split over the finer cells", src->P.leaf);
     if (src->n_voxels == 0) return SLAM_OK;
     hipStream_t st = as_stream(stream);
-    SLAM_TRY(make_room(dst, src->n_voxels, st));
-    if (!dst->actr.p) SLAM_TRY(dst->actr.alloc(kAbsorbCounters * sizeof(uint32_t)));
-    uint32_t *h = static_cast<uint32_t *>(pinned_scratch(kAbsorbCounters * sizeof(uint32_t)));
-    SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_vmap: no pinned memory for the counters");
-    SLAM_HIP(hipMemsetAsync(dst->actr.p, 0, kAbsorbCounters * sizeof(uint32_t), st));
-    const Moments SQ = src->dist_on ? src->moments() : Moments{};
-    const Moments Q = dst->dist_on ? dst->moments() : Moments{};
     const long long unit = src->dist_on ? (long long)fine : 0; // L / 16: L = leaf 2^20 exactly here
-    hipLaunchKernelGGL(vmap_coarsen_kernel, dim3(blocks_for((uint64_t)src->capacity)), dim3(256), 0, st, src->view(), SQ, shift, unit, dst->view(), Q,
-                       dst->actr.as<uint32_t>());
-    SLAM_HIP(hipGetLastError());
-    dst->dist_stale = true;
-    SLAM_HIP(hipMemcpyAsync(h, dst->actr.p, kAbsorbCounters * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    SLAM_HIP(hipStreamSynchronize(st));
-    dst->n_voxels += h[kClaimed];
-    dst->n_points += (int64_t)((uint64_t)h[kPoints] | (uint64_t)h[kPoints + 1] << 32);
-    SLAM_REQUIRE(!h[kError], SLAM_E_HIP, "slam_vmap_coarsen: a probe ran through all %lld slots (%lld voxels): voxels were lost",
-                 (long long)dst->capacity, (long long)dst->n_voxels);
-    return SLAM_OK;
+    return absorb_with("slam_vmap_coarsen", "voxels", dst, false, src->n_voxels, nullptr, st, [&](uint32_t *ctr) {
+        hipLaunchKernelGGL(vmap_coarsen_kernel, dim3(blocks_for((uint64_t)src->capacity)), dim3(256), 0, st, src->view(), src->moments(), shift, unit,
+                           dst->view(), dst->moments(), ctr);
+    });
 }
 
 int slam_vmap_save(slam_vmap_t *m, const char *path)
@@ -1519,20 +1423,23 @@ int slam_vmap_save(slam_vmap_t *m, const char *path)
         std::vector<int64_t>  sums(3 * N), E, M;
         vmap_file::Meta       meta;
         meta.leaf = m->P.leaf, meta.n = m->n_voxels, meta.n_points = m->n_points;
-        SLAM_TRY(slam_vmap_read_sums(m, sums.data(), count.data(), key.data(), cap, &got));
-        SLAM_REQUIRE(got == cap, SLAM_E_HIP, "slam_vmap_save: the table holds %d voxels, the handle counts %d", got, cap);
+        Wanted w{};
+        w.sums = sums.data(), w.count = count.data(), w.key = key.data();
         if (m->carved()) {
             meta.flags |= vmap_file::kCarve;
             seen.resize(N), miss.resize(N);
-            SLAM_TRY(slam_vmap_read_carve(m, seen.data(), miss.data(), nullptr, cap, &got));
+            w.seen = seen.data(), w.miss = miss.data();
         }
         if (m->dist_on) {
             meta.flags |= vmap_file::kMoments;
             meta.min_points = m->DP.min_points, meta.max_miss_num = m->DP.max_miss_num, meta.max_miss_den = m->DP.max_miss_den;
             meta.flat_ratio = m->DP.flat_ratio, meta.line_ratio = m->DP.line_ratio, meta.epsilon = m->DP.epsilon;
             E.resize(3 * N), M.resize(6 * N);
-            SLAM_TRY(slam_vmap_read_moments(m, E.data(), M.data(), nullptr, cap, &got));
+            w.E3 = E.data(), w.M6 = M.data();
         }
+        // every column with one select and one sort; a refusal reads as it did when the first of three reads was read_sums
+        SLAM_TRY(read_columns("slam_vmap_read_sums", m, nullptr, nullptr, 0, nullptr, w, cap, &got));
+        SLAM_REQUIRE(got == cap, SLAM_E_HIP, "slam_vmap_save: the table holds %d voxels, the handle counts %d", got, cap);
         const std::vector<uint8_t> bytes = vmap_file::build(meta, key.data(), count.data(), sums.data(), seen.data(), miss.data(), E.data(), M.data());
         std::string                why;
         // the writer is held to the reader: a map that slam_vmap_load would refuse (a cell of 2^20 - 1, a wrapped count) is not written

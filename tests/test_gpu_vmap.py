@@ -71,6 +71,11 @@ def test_two_thousand_points_in_one_voxel():
     dm.close()
 
 
+# (points, dropped, voxels) of the four edge clouds, and what carving the dropped cloud from (0.1, 0.1, 0.1) counts
+EDGE_CLOUDS = ((K.boundary_points()[0], 0, 3), (K.negative_points()[0], 0, 3), (K.rounding_points()[0], 0, 1), (K.dropped_points()[0], 7, 2))
+DROPPED_CARVE = dict(n_rays=2, n_dropped=7, n_skipped=1)
+
+
 def test_boundaries_rounding_and_dropped_points():
     for pts in (K.boundary_points()[0], K.negative_points()[0], K.rounding_points()[0]):
         dm, om = both([(pts, None, None)])
@@ -84,6 +89,23 @@ def test_boundaries_rounding_and_dropped_points():
     assert dm.integrate(pts[:1], np.eye(3), (0, 5e6, 0)) == om.integrate(pts[:1], np.eye(3), (0, 5e6, 0)) == 1
     check_equal(dm, om)
     dm.close()
+    # the same four clouds through the other users of the cell rule: the integrate with moments, and carve
+    from test_gpu_vmap_carve import Pair
+    from test_gpu_vmap_gicp import check_equal as check_dist_equal, dist_map
+    for pts, dropped, voxels in EDGE_CLOUDS:
+        dm, om = dist_map(K.LEAF)
+        assert dm.integrate(pts) == om.integrate(pts) == dropped
+        assert len(check_dist_equal(dm, om)["key"]) == voxels
+        dm.close()
+        p = Pair(leaf=K.LEAF)
+        p.integrate(pts)
+        r = p.carve(pts, origin=(0.1, 0.1, 0.1))
+        assert r["n_dropped"] == dropped and r["n_rays"] == len(pts) - dropped
+        if dropped:
+            assert {k: r[k] for k in DROPPED_CARVE} == DROPPED_CARVE
+        seen, miss, key = p.check()
+        assert len(key) == voxels
+        p.close()
 
 
 def four(order, **kw):
