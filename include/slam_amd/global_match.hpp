@@ -26,10 +26,15 @@
 //   localize        the scan becomes a keyframe of the store; from the coarsest level down ONE slam_vmap_register_gicp call
 //                   carries every live start, gated at GATE_RATIO times the level's leaf, from the level above's f32
 //                   transform; a start that ends a level without pairs or degenerate is out; the winner is chosen at level 0
+//   search          the scan becomes a keyframe and slam_vmap_search_keyframe scores it against one derived level: every pose
+//                   of a lattice of rotations and whole-cell offsets, no prior (docs/VOXEL_MAP.md section 13)
+//   relocalize      the cold start: SEARCH_YAWS rotations and every offset within `radius` at level SEARCH_LEVEL, the
+//                   SEARCH_STARTS best hits' init are the starts, and localize descends from that level
 // A 1 m map can be entered by the direct registration only from about a leaf away (its candidates are the 27 cells around the
 // moved point); at an 8 m leaf the same rule reaches 8 m.  No random numbers: the same call gives the same bits.
 // slam_amd.api.MapLocalizer is the same thing with Python's names and habits:
 //   setMap -> set_map, yawFan -> yaw_fan, localize(cloud, n, stride, starts) -> localize(cloud, starts) returning a dict where
+//   search(cloud, n, stride, params, level) -> search(cloud, params, level) returning the list of hits, relocalize alike, where
 //   this fills a MapLocalizerResult; ok() has no twin (the constructor raises); an error of the library and a map that cannot
 //   be taken are printed here and return false, there they raise SlamError.  The scan keyframe is removed on every way out.
 #pragma once
@@ -225,7 +230,10 @@ public:
     int    N_YAW = 8;
     double MIN_PAIR_SHARE = 0.5;
     double MAX_SCORE = 0.03; // between the two level-0 fitness populations of section 11.3: sqrt(0.00745 * 0.0964)
+    // relocalize's (section 13.4): the level searched and descended from, the rotations scored, the hits taken as starts
+    int SEARCH_LEVEL = 1, SEARCH_YAWS = 64, SEARCH_STARTS = 4;
 
+    std::vector<slam_vmap_search_hit> hits; // of the last search() or relocalize(), best first
     // every start's result per level of the last localize(): last[level][start], valid where ran[level][start]
     std::vector<std::vector<slam_vmap_gicp_result>> last;
     std::vector<std::vector<char>>                  ran;
@@ -289,9 +297,10 @@ public:
     // One scan (sensor frame, `stride` >= 3 floats per point) from `starts` (16 floats each).  False on an error of the library
     // or without a map; otherwise *out says whether a start won.  The winner among the level-0 results that converged with
     // fitness <= MAX_SCORE and fitness_pairs >= MIN_PAIR_SHARE n_source has the most fitness_pairs, then the lowest index.
-    bool localize(const float *cloud, int n, int stride, const std::vector<float> &starts, MapLocalizerResult *out)
+    // from_level: the level the descent begins at (the levels above it are not run); -1, the default, is the coarsest.
+    bool localize(const float *cloud, int n, int stride, const std::vector<float> &starts, MapLocalizerResult *out, int from_level = -1)
     {
-        if (!ok() || !fine_ || !out || !cloud || n <= 0 || stride < 3) return false;
+        if (!ok() || !fine_ || !out || !cloud || n <= 0 || stride < 3 || from_level >= LEVELS) return false;
         *out = MapLocalizerResult();
         const int n_starts = (int)(starts.size() / 16);
         last.assign((size_t)LEVELS, std::vector<slam_vmap_gicp_result>((size_t)n_starts, slam_vmap_gicp_result()));
@@ -299,7 +308,8 @@ public:
         int scan = -1;
         if (slam_kf_add_keyframe(store_, cloud, n, stride, &scan) != SLAM_OK) return warn(), false;
         std::vector<char> alive((size_t)n_starts, 1);
-        const bool        done = slam_kf_keyframe_info(store_, scan, &out->n_source, 0, 0, 0, 0) == SLAM_OK && descend(scan, starts, alive);
+        const bool        done = slam_kf_keyframe_info(store_, scan, &out->n_source, 0, 0, 0, 0) == SLAM_OK &&
+                                 descend(scan, starts, alive, from_level < 0 ? LEVELS - 1 : from_level);
         if (!done) warn();
         if (slam_kf_remove_keyframe(store_, scan) != SLAM_OK) warn();
         if (!done) return false;
@@ -318,6 +328,47 @@ public:
             out->x = (double)T[3], out->y = (double)T[7], out->theta = std::atan2((double)T[4], (double)T[0]);
         }
         return true;
+    }
+
+    // The scan becomes a keyframe, as in localize, and slam_vmap_search_keyframe scores it against level `level` (-1:
+    // SEARCH_LEVEL) with `params`: `hits` holds what was found, best first.  False on an error of the library or without a map.
+    bool search(const float *cloud, int n, int stride, const slam_vmap_search_params &params, int level = -1)
+    {
+        hits.clear();
+        if (level < 0) level = SEARCH_LEVEL;
+        if (!ok() || !fine_ || !cloud || n <= 0 || stride < 3 || level >= LEVELS || params.top_m < 0) return false;
+        int scan = -1, found = 0;
+        if (slam_kf_add_keyframe(store_, cloud, n, stride, &scan) != SLAM_OK) return warn(), false;
+        hits.resize((size_t)params.top_m);
+        const bool done = slam_vmap_search_keyframe(this->level(level), store_, scan, &params, hits.data(), &found, nullptr, nullptr) == SLAM_OK;
+        if (!done) warn();
+        if (slam_kf_remove_keyframe(store_, scan) != SLAM_OK) warn();
+        hits.resize(done ? (size_t)found : 0);
+        return done;
+    }
+
+    // The cold start: no yaw, and no position closer than `radius` metres around (cx, cy), is asked for.  The window is
+    // ceil(radius / leaf) cells of level SEARCH_LEVEL in x and y and none in z.  False on an error; otherwise *out says
+    // whether a hit's descent won (found is false when there is no hit), and out->index is the hit's.
+    bool relocalize(const float *cloud, int n, int stride, float cx, float cy, float cz, double radius, MapLocalizerResult *out)
+    {
+        if (!ok() || !fine_ || !out || SEARCH_LEVEL < 0 || SEARCH_LEVEL >= LEVELS) return false;
+        *out = MapLocalizerResult();
+        double leaf = 0;
+        if (slam_vmap_layout(level(SEARCH_LEVEL), &leaf, nullptr, nullptr, nullptr) != SLAM_OK) return warn(), false;
+        slam_vmap_search_params p;
+        slam_vmap_default_search_params(&p);
+        p.n_yaw = SEARCH_YAWS, p.top_m = SEARCH_STARTS, p.cx = cx, p.cy = cy, p.cz = cz;
+        p.wx = p.wy = (int)std::ceil(radius / leaf), p.wz = 0;
+        if (!search(cloud, n, stride, p, SEARCH_LEVEL)) return false;
+        if (hits.empty()) {
+            last.assign((size_t)LEVELS, std::vector<slam_vmap_gicp_result>());
+            ran.assign((size_t)LEVELS, std::vector<char>());
+            return true;
+        }
+        std::vector<float> starts;
+        for (const slam_vmap_search_hit &h : hits) starts.insert(starts.end(), h.init, h.init + 16);
+        return localize(cloud, n, stride, starts, out, SEARCH_LEVEL);
     }
 
 private:
@@ -360,11 +411,11 @@ private:
         return true;
     }
     // the levels from the coarsest down: one call per level carries every live start
-    bool descend(int scan, const std::vector<float> &starts, std::vector<char> &alive)
+    bool descend(int scan, const std::vector<float> &starts, std::vector<char> &alive, int top)
     {
         const int          n_starts = (int)alive.size();
         std::vector<float> T(starts.begin(), starts.begin() + 16 * (size_t)n_starts);
-        for (int k = LEVELS - 1; k >= 0; --k) {
+        for (int k = top; k >= 0; --k) {
             std::vector<int>                ids;
             std::vector<slam_vmap_gicp_req> req;
             for (int i = 0; i < n_starts; ++i) {

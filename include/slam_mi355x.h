@@ -1170,6 +1170,60 @@ int  slam_vmap_load(const char *path, slam_vmap_t **out);
  * the call. */
 int  slam_vmap_coarsen(slam_vmap_t *dst, slam_vmap_t *src, slam_stream_t stream);
 
+/* Exhaustive lattice pose search (docs/VOXEL_MAP.md section 13; the device equals tests/vmap_search_cases.py bit for bit):
+ * "here is a scan, here is the map, where am I?" without a prior.  Opt-in; the map is not written.
+ *   rotation  k of n_yaw is the f32 matrix planar(cx, cy, yaw_k) with cz as its z translation, yaw_k =
+ *             (float)((double) yaw0 + 2 pi k / n_yaw), cos and sin in double of the float angle and rounded to float; the
+ *             kernels see its entries promoted to double
+ *   cell      point i under rotation k is moved by section 1's rule, q = (float)(((r0 x + r1 y) + r2 z) + t) in double, and
+ *             takes section 1's cell at the map's leaf; a point without a cell counts nowhere for that rotation
+ *   pose      (k, dx, dy, dz) with |dx| <= wx, |dy| <= wy, |dz| <= wz whole cells; its score is the number of points i whose
+ *             cell c_ik + d holds a qualifying voxel (a cell with |c + d| >= 2^20 on an axis holds none)
+ *   qualify   planes_only = 1: the voxel's distribution flag is 1 (section 9's plane rule, stale distributions are computed
+ *             first on the stream); planes_only = 0: count >= min_count, legal on any map
+ *   volume    int32 [n_yaw][2 wz + 1][2 wy + 1][2 wx + 1], dx fastest; it stays on the device unless the caller asks for it
+ *   hits      up to top_m, greedily: the best remaining pose has the highest score, then the lowest flat index; once chosen
+ *             it suppresses every pose with cyclic |dk| <= nms_yaw and |dd| <= nms_cells on all three axes; a pose of
+ *             score 0 is never a hit */
+typedef struct {
+    float yaw0;         /* 0 */
+    int   n_yaw;        /* 64 */
+    float cx, cy, cz;   /* the window's centre: the translation of every rotation (0, 0, 0) */
+    int   wx, wy, wz;   /* half-widths in cells (24, 24, 0) */
+    int   planes_only;  /* 1 */
+    int   min_count;    /* with planes_only = 0 (6) */
+    int   top_m;        /* 4; at most 4096 */
+    int   nms_yaw;      /* 2 */
+    int   nms_cells;    /* 2 */
+} slam_vmap_search_params;
+
+typedef struct {
+    int   score;        /* points whose cell holds a qualifying voxel */
+    int   k, dx, dy, dz;
+    int   n_with_cell;  /* points that had a cell under rotation k */
+    float init[16];     /* planar((float)((double) cx + dx leaf), (float)((double) cy + dy leaf), yaw_k) with z
+                           (float)((double) cz + dz leaf), row-major: the pose the offset stands for.  Moving the cloud by it
+                           need not reproduce c + d for every point: the floats round */
+} slam_vmap_search_hit;
+
+void slam_vmap_default_search_params(slam_vmap_search_params *p);
+/* n device points `stride` floats apart.  hits: room for top_m (nullable when top_m is 0); *n_hits: how many were found;
+ * volume (optional, host): the whole score volume.  SLAM_E_INVALID before any launch for a null map, n < 0, stride < 3, null
+ * points with n > 0, n_yaw < 1, a negative half-width, top_m < 0 or above 4096, negative nms_yaw or nms_cells, a null n_hits,
+ * null hits with top_m > 0, n_yaw (2 wx + 1)(2 wy + 1)(2 wz + 1) > 2^26, and planes_only on a map without distributions.  The
+ * occupancy brick is sized by the box of the moved cells plus the window, and by as much again behind it for the points
+ * without a cell: above 2^31 bits it is SLAM_E_NOMEM and nothing has changed.  A map of no voxels or a source of no points
+ * gives a zero volume and no hits.  WAITS TWICE for `stream`: for the box of the moved cells, which sizes the brick, and for
+ * the hits (and the volume, when asked for).  One call at a time per handle. */
+int  slam_vmap_search_dev(slam_vmap_t *m, const float *d_xyz, int n, int stride, const slam_vmap_search_params *params,
+                          slam_vmap_search_hit *hits, int *n_hits, int32_t *volume, slam_stream_t stream);
+/* Host points: staged as slam_vmap_integrate stages them (synchronously), then the same path on the null stream. */
+int  slam_vmap_search(slam_vmap_t *m, const float *xyz, int n, int stride, const slam_vmap_search_params *params,
+                      slam_vmap_search_hit *hits, int *n_hits, int32_t *volume);
+/* The filtered cloud of keyframe `id` of `store` is the source; a null store or a dead id is SLAM_E_INVALID. */
+int  slam_vmap_search_keyframe(slam_vmap_t *m, slam_kf_t *store, int id, const slam_vmap_search_params *params,
+                               slam_vmap_search_hit *hits, int *n_hits, int32_t *volume, slam_stream_t stream);
+
 /* -------------------------------------------------------------------------
  * Pose-graph optimiser: graph_slam's optimizeGraph (graph_slam.cpp:322-390), i.e. g2o's VertexSE3 / EdgeSE3 under
  * OptimizationAlgorithmLevenberg, restated in docs/PGO.md (parity with g2o itself is unpinned; the yardstick is

@@ -194,6 +194,17 @@ class VmapGicpResult(C.Structure):
                 ("hessian", C.c_double * 36), ("fitness", C.c_double), ("fitness_pairs", C.c_int), ("reserved", C.c_int)]
 
 
+class VmapSearchParams(C.Structure):
+    _fields_ = [("yaw0", C.c_float), ("n_yaw", C.c_int), ("cx", C.c_float), ("cy", C.c_float), ("cz", C.c_float),
+                ("wx", C.c_int), ("wy", C.c_int), ("wz", C.c_int), ("planes_only", C.c_int), ("min_count", C.c_int),
+                ("top_m", C.c_int), ("nms_yaw", C.c_int), ("nms_cells", C.c_int)]
+
+
+class VmapSearchHit(C.Structure):
+    _fields_ = [("score", C.c_int), ("k", C.c_int), ("dx", C.c_int), ("dy", C.c_int), ("dz", C.c_int), ("n_with_cell", C.c_int),
+                ("init", C.c_float * 16)]
+
+
 class PgoParams(C.Structure):
     _fields_ = [("max_trials", C.c_int), ("tau", C.c_double), ("good_lower", C.c_double), ("good_upper", C.c_double),
                 ("ordering", C.c_int), ("max_band_bytes", C.c_size_t)]
@@ -287,6 +298,7 @@ EXPORTS = [
     "slam_vmap_read_distributions", "slam_vmap_default_gicp_params", "slam_vmap_register_gicp", "slam_vmap_register_gicp_traced",
     "slam_vmap_layout", "slam_vmap_absorb_dev", "slam_vmap_absorb", "slam_vmap_merge", "slam_vmap_save", "slam_vmap_load",
     "slam_vmap_coarsen",
+    "slam_vmap_default_search_params", "slam_vmap_search_dev", "slam_vmap_search", "slam_vmap_search_keyframe",
     "slam_pgo_default_params", "slam_pgo_create", "slam_pgo_destroy", "slam_pgo_clear", "slam_pgo_add_vertex",
     "slam_pgo_set_vertex", "slam_pgo_add_edge", "slam_pgo_size", "slam_pgo_optimize", "slam_pgo_read_vertices", "slam_pgo_chi2",
     "slam_pgo_read_system", "slam_pgo_step",
@@ -551,6 +563,11 @@ def lib():
     L.slam_vmap_save.argtypes = [_vp, C.c_char_p]
     L.slam_vmap_load.argtypes = [C.c_char_p, C.POINTER(_vp)]
     L.slam_vmap_coarsen.argtypes = [_vp, _vp, _vp]
+    L.slam_vmap_default_search_params.argtypes = [C.POINTER(VmapSearchParams)]
+    L.slam_vmap_default_search_params.restype = None
+    L.slam_vmap_search_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, C.POINTER(VmapSearchParams), _vp, C.POINTER(C.c_int), _vp, _vp]
+    L.slam_vmap_search.argtypes = [_vp, _vp, C.c_int, C.c_int, C.POINTER(VmapSearchParams), _vp, C.POINTER(C.c_int), _vp]
+    L.slam_vmap_search_keyframe.argtypes = [_vp, _vp, C.c_int, C.POINTER(VmapSearchParams), _vp, C.POINTER(C.c_int), _vp, _vp]
     _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
     L.slam_pgo_default_params.argtypes = [C.POINTER(PgoParams)]
     L.slam_pgo_default_params.restype = None
@@ -1279,6 +1296,19 @@ def vmap_default_gicp_params(**kw):
     return p
 
 
+def vmap_default_search_params(**kw):
+    p = VmapSearchParams()
+    lib().slam_vmap_default_search_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def vmap_search_hit_dict(h):
+    return {"score": h.score, "k": h.k, "dx": h.dx, "dy": h.dy, "dz": h.dz, "n_with_cell": h.n_with_cell,
+            "init": np.array(h.init[:], np.float32).reshape(4, 4)}
+
+
 def vmap_gicp_result_dict(r):
     return {"transform": np.array(r.transform[:], np.float32).reshape(4, 4),
             "transform64": np.array(r.transform64[:], np.float64).reshape(4, 4), "iterations": r.iterations, "state": r.state,
@@ -1465,6 +1495,29 @@ class VoxelMap:
             for e in range(n):
                 out[e]["pairs_trace"] = tr[e].copy()
         return out[0] if single else out
+
+    # ---- exhaustive lattice pose search (docs/VOXEL_MAP.md section 13)
+    def search(self, xyz=None, params=None, volume=False, store=None, kid=None, d_xyz=None, n=0, stride=3, stream=None, **kw):
+        """slam_vmap_search (xyz: host array [n, >= 3] f32), slam_vmap_search_keyframe (store and kid: the keyframe's filtered
+        cloud) or slam_vmap_search_dev (d_xyz: n device points `stride` floats apart): every pose (k, dx, dy, dz) of the window
+        scored by the number of points whose cell, moved by whole cells, holds a qualifying voxel.  (hits, volume): hits is a
+        list of vmap_search_hit_dict's fields, best first; volume is the int32 [n_yaw, 2 wz + 1, 2 wy + 1, 2 wx + 1] scores
+        when asked for, else None.  params: a VmapSearchParams, or its fields as keywords over the defaults."""
+        p = params or vmap_default_search_params(**kw)
+        hits, got = (VmapSearchHit * max(p.top_m, 1))(), C.c_int()
+        vol = None
+        if volume:
+            vol = np.zeros((max(p.n_yaw, 0), 2 * p.wz + 1, 2 * p.wy + 1, 2 * p.wx + 1), np.int32)
+        tail = (C.byref(p), C.addressof(hits), C.byref(got), _ptr(vol))
+        if store is not None:
+            check(lib().slam_vmap_search_keyframe(self.h, store.h, int(kid), *tail, _sp(stream)))
+        elif d_xyz is not None:
+            check(lib().slam_vmap_search_dev(self.h, getattr(d_xyz, "ptr", d_xyz), int(n), int(stride), *tail, _sp(stream)))
+        else:
+            xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+            xyz = xyz.reshape(-1, xyz.shape[-1] if xyz.ndim > 1 else 3)
+            check(lib().slam_vmap_search(self.h, _ptr(xyz), len(xyz), xyz.shape[1], *tail))
+        return [vmap_search_hit_dict(hits[e]) for e in range(got.value)], vol
 
     # ---- snapshots and merging by the integer accumulators (docs/VOXEL_MAP.md section 10)
     def layout(self):
@@ -2178,6 +2231,8 @@ class MapLocalizer:
     # read at every call: set on the instance to change
     GATE_RATIO, N_YAW, MIN_PAIR_SHARE = 2.0, 8, 0.5
     MAX_SCORE = 0.03        # between the two level-0 fitness populations of section 11.3: sqrt(0.00745 * 0.0964)
+    # relocalize's (section 13.4): the level searched and descended from, the rotations scored and the hits taken as starts
+    SEARCH_LEVEL, SEARCH_YAWS, SEARCH_STARTS = 1, 64, 4
 
     def __init__(self, levels=4, leaf=0.30):
         # fixed at construction: the number of levels, and the store with the builder's leaf and epsilons
@@ -2265,9 +2320,42 @@ class MapLocalizer:
         return [GlobalMatcher.planar(np.float32(x), np.float32(y), np.float32(float(np.float32(yaw)) + 2.0 * math.pi * k / n))
                 for k in range(int(n))]
 
-    def localize(self, cloud, starts=None, x=0.0, y=0.0, yaw=0.0):
+    def search(self, cloud, params=None, level=None, **kw):
+        """The scan becomes a keyframe, as in localize, and VoxelMap.search scores it against the derived level `level` (None:
+        SEARCH_LEVEL): the hits, best first."""
+        if self.fine is None:
+            raise SlamError(E_INVALID, "MapLocalizer.search: no map")
+        level = self.SEARCH_LEVEL if level is None else int(level)
+        if not 0 <= level < self.LEVELS:
+            raise SlamError(E_INVALID, "MapLocalizer.search: level %d of %d" % (level, self.LEVELS))
+        scan = self.store.add_keyframe(cloud)
+        try:
+            return self.level(level).search(store=self.store, kid=scan, params=params, **kw)[0]
+        finally:
+            self.store.remove_keyframe(scan)
+
+    def relocalize(self, cloud, cx=0.0, cy=0.0, cz=0.0, radius=24.0):
+        """The cold start: no yaw and no position closer than `radius` metres around (cx, cy) is asked for.  SEARCH_YAWS
+        rotations over the full circle and every offset of ceil(radius / leaf) cells in x and y (none in z) are scored at level
+        SEARCH_LEVEL, the SEARCH_STARTS best hits' `init` are the starts, and localize descends from that level.  localize's
+        dict with 'hits' added; found is False when there is no hit."""
+        if self.fine is None:
+            raise SlamError(E_INVALID, "MapLocalizer.relocalize: no map")
+        if not 0 <= self.SEARCH_LEVEL < self.LEVELS:
+            raise SlamError(E_INVALID, "MapLocalizer.relocalize: SEARCH_LEVEL %d of %d levels" % (self.SEARCH_LEVEL, self.LEVELS))
+        w = int(math.ceil(float(radius) / self.level(self.SEARCH_LEVEL).params.leaf))
+        hits = self.search(cloud, n_yaw=self.SEARCH_YAWS, top_m=self.SEARCH_STARTS, cx=cx, cy=cy, cz=cz, wx=w, wy=w, wz=0)
+        if not hits:
+            self.last, self.n_source = [[] for _ in range(self.LEVELS)], 0
+            return dict(found=False, index=-1, transform=None, transform64=None, x=0.0, y=0.0, theta=0.0, n_source=0, last=self.last,
+                        hits=hits)
+        out = self.localize(cloud, [h["init"] for h in hits], from_level=self.SEARCH_LEVEL)
+        out["hits"] = hits
+        return out
+
+    def localize(self, cloud, starts=None, x=0.0, y=0.0, yaw=0.0, from_level=None):
         """One scan ([n, >= 3] f32, sensor frame) from `starts` (4 x 4 f32 each; None: yaw_fan(x, y, yaw, N_YAW)).  From the
-        coarsest level down one register_gicp call carries every live start, gated at GATE_RATIO times the level's leaf, from
+        coarsest level (from_level, where given: the levels above it are not run) down one register_gicp call carries every live start, gated at GATE_RATIO times the level's leaf, from
         the level above's f32 transform; a start that ends a level without pairs or degenerate is out.  The winner among the
         level-0 results that converged with fitness <= MAX_SCORE and fitness_pairs >= MIN_PAIR_SHARE n_source has the most
         fitness_pairs, then the lowest index.  A dict of found, index (-1: nobody), transform, transform64, x, y, theta (of
@@ -2276,13 +2364,16 @@ class MapLocalizer:
             raise SlamError(E_INVALID, "MapLocalizer.localize: no map")
         if starts is None:
             starts = self.yaw_fan(x, y, yaw, self.N_YAW)
+        top = self.LEVELS - 1 if from_level is None else int(from_level)
+        if not 0 <= top < self.LEVELS:
+            raise SlamError(E_INVALID, "MapLocalizer.localize: from_level %d of %d levels" % (top, self.LEVELS))
         T = [np.array(s, np.float32).reshape(4, 4) for s in starts]
         scan = self.store.add_keyframe(cloud)
         try:
             self.n_source = self.store.info(scan)["n_points"]
             alive = [True] * len(T)
             self.last = [[None] * len(T) for _ in range(self.LEVELS)]
-            for k in range(self.LEVELS - 1, -1, -1):
+            for k in range(top, -1, -1):
                 ids = [i for i in range(len(T)) if alive[i]]
                 if not ids:
                     break

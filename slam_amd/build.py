@@ -19,7 +19,8 @@ RCCL_LIB = os.path.join(LIBDIR, "libslam_mi355x_rccl.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SOURCES = ["runtime.hip", "icp.hip", "icp_build.hip", "icp_single.hip", "grid.hip", "gseg.hip", "ccicp.hip",
-           "mapper.hip", "mls.hip", "kf_edge.hip", "kf_gicp.hip", "csm.hip", "voxmap.hip", "kf_store.hip", "pgo.hip", "kf_sc.hip", "vmap_gicp.hip"]
+           "mapper.hip", "mls.hip", "kf_edge.hip", "kf_gicp.hip", "csm.hip", "voxmap.hip", "kf_store.hip", "pgo.hip", "kf_sc.hip", "vmap_gicp.hip",
+           "vmap_search.hip"]
 RCCL_SOURCES = ["rccl.hip"]
 # -ffp-contract=off: the reference arithmetic (x86-64, no FMA) rounds every
 # product before the add; the kernels additionally spell the parity-critical

@@ -1,6 +1,6 @@
-// vmap_dist.hpp -- what the voxel map (voxmap.hip) shows of itself to the registration against it (vmap_gicp.hip): the key
-// plane of the table, the distribution planes, and the two rules both must follow alike: the cell rule and the hash.  The
-// handle itself stays voxmap.hip's.
+// vmap_dist.hpp -- what the voxel map (voxmap.hip) shows of itself to the registration against it (vmap_gicp.hip) and to the
+// pose search over it (vmap_search.hip): the key plane of the table, the distribution planes, and the rules all must follow
+// alike: the f64 move of a point, the cell rule and the hash.  The handle itself stays voxmap.hip's.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -61,6 +61,58 @@ __host__ __device__ __forceinline__ bool vmap_point_cell(const float q[3], doubl
     for (int k = 0; k < 3; ++k) has = vmap_axis_cell(q[k], leaf, &cell[k]) && has;
     return has;
 }
+// A cloud's transform as the kernels take it: q = R p + t in f64 (below); `on` = 0 leaves the points as they are.
+struct VmapTransform {
+    double r[9], t[3];
+    int    on;
+};
+
+// A point as the map sees it: p (f32 from a cloud, f64 for a carve's origin) moved by X in f64, every product and sum rounded
+// on its own, then rounded to f32 (docs/VOXEL_MAP.md section 1).  It stands here, once, for integrate, carve and the pose
+// search (vmap_search.hip) alike.  The kernels spell the rounding with the intrinsics; the host's plain operators round the
+// same way because the file is compiled without contraction.  X by value and the statements in this order: so the integrate
+// kernels compile to their predecessors' instructions (docs/VOXEL_MAP.md section 12.2).
+template <class S>
+__host__ __device__ __forceinline__ void moved_point(const S *p, const VmapTransform X, float q[3])
+{
+    q[0] = (float)p[0], q[1] = (float)p[1], q[2] = (float)p[2];
+    if (X.on) {
+        const double px = p[0], py = p[1], pz = p[2];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+#ifdef __HIP_DEVICE_COMPILE__ // the rounding spelled out: the kernels do not lean on the build's flags
+            q[k] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(X.r[3 * k], px), __dmul_rn(X.r[3 * k + 1], py)), __dmul_rn(X.r[3 * k + 2], pz)),
+                                    X.t[k]);
+#else
+            q[k] = (float)((((X.r[3 * k] * px) + (X.r[3 * k + 1] * py)) + (X.r[3 * k + 2] * pz)) + X.t[k]);
+#endif
+        }
+    }
+}
+
+// What the pose search (vmap_search.hip, docs/VOXEL_MAP.md section 13) sees of the handle: the key and count planes, the
+// distribution plane that carries the plane flag (null unless asked for), and the call's blocks, which the handle owns.
+struct VmapSearchView {
+    const uint64_t *key;
+    const uint32_t *count;
+    const float4   *cen; // w = 1.0f for a plane voxel; null when the view was taken without planes
+    uint64_t        mask;
+    double          leaf;
+    int64_t         n_voxels;
+};
+struct VmapSearchWork {
+    DevMem stage;  // the host form's points
+    DevMem rot;    // the rotations: 12 doubles each
+    DevMem cells;  // three int32 planes of n_yaw n cells
+    DevMem brick;  // the occupancy bits
+    DevMem volume; // the scores
+    DevMem small;  // the box, the points with a cell per rotation, the arg-max partials and the hit list
+};
+// The view of `m`; with `planes` the distributions are brought up to date on `st` first (enqueued, not waited for), and a map on
+// which they were never enabled is SLAM_E_INVALID (error text set).  Nothing of the map is written.
+int             vmap_search_view(slam_vmap *m, bool planes, hipStream_t st, VmapSearchView *out);
+VmapSearchWork &vmap_search_work(slam_vmap *m);
+
 // a cell's key: 21 bits an axis, x lowest, each field the cell plus 2^20 (1 .. 2^21 - 1)
 __host__ __device__ __forceinline__ uint64_t vmap_key_field(int cell, int axis) { return (uint64_t)(cell + kVmapCellLimit) << (21 * axis); }
 __host__ __device__ __forceinline__ uint64_t vmap_cell_key(const int cell[3])

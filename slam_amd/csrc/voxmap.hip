@@ -77,10 +77,7 @@ struct Planes {
 struct Moments {
     unsigned long long *E[3], *M[6]; // first moments, then xx xy xz yy yz zz
 };
-struct Transform {
-    double r[9], t[3];
-    int    on;
-};
+using Transform = VmapTransform; // the f64 move of a point and moved_point are vmap_dist.hpp's, shared with vmap_search.hip
 struct Box {
     float lo[2], hi[2];
     int   on;
@@ -107,28 +104,6 @@ __device__ __forceinline__ long long find_or_claim(const Table &T, uint64_t key,
         if (cur == key) return (long long)h;
     }
     return -1;
-}
-
-// A point as the map sees it: p (f32 from a cloud, f64 for a carve's origin) moved by X in f64, every product and sum rounded
-// on its own, then rounded to f32.  The kernels spell the rounding with the intrinsics; the host's plain operators round the
-// same way because the file is compiled without contraction.  X by value and the statements in this order: so the integrate
-// kernels compile to their predecessors' instructions (docs/VOXEL_MAP.md section 12.2).
-template <class S>
-__host__ __device__ __forceinline__ void moved_point(const S *p, const Transform X, float q[3])
-{
-    q[0] = (float)p[0], q[1] = (float)p[1], q[2] = (float)p[2];
-    if (X.on) {
-        const double px = p[0], py = p[1], pz = p[2];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-#ifdef __HIP_DEVICE_COMPILE__ // the rounding spelled out: the kernels do not lean on the build's flags
-            q[k] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(X.r[3 * k], px), __dmul_rn(X.r[3 * k + 1], py)), __dmul_rn(X.r[3 * k + 2], pz)),
-                                    X.t[k]);
-#else
-            q[k] = (float)((((X.r[3 * k] * px) + (X.r[3 * k + 1] * py)) + (X.r[3 * k + 2] * pz)) + X.t[k]);
-#endif
-        }
-    }
 }
 
 // kMoments adds the moments about the cell's corner: e = (fx - cell L) >> 4 per axis, |e| <= 2^20 (section 9 has the bound).
@@ -591,6 +566,7 @@ struct slam_vmap {
     // latter are behind the former; a registration's tasks, results and trace
     slam_vmap_dist_params DP{};
     DevMem                mom, dist, reg_work;
+    VmapSearchWork        search; // a pose search's blocks (section 13)
     bool                  dist_on = false, dist_stale = true;
 
     static Moments moments(const DevMem &b, int64_t cap)
@@ -1053,7 +1029,8 @@ int slam_vmap_info(slam_vmap_t *m, int64_t *n_voxels, int64_t *capacity, int64_t
     if (device_bytes)
         *device_bytes = m->table.cap + m->ctr.cap + m->flag.cap + m->sel.cap + m->keys_in.cap + m->keys_out.cap + m->sel_sorted.cap + m->tmp.cap +
                         m->stage_in.cap + m->stage_out.cap + m->seen.cap + m->miss.cap + m->stamp.cap + m->cctr.cap + m->rays.cap + m->chunks.cap +
-                        m->offs.cap + m->mom.cap + m->dist.cap + m->reg_work.cap + m->actr.cap;
+                        m->offs.cap + m->mom.cap + m->dist.cap + m->reg_work.cap + m->actr.cap + m->search.stage.cap + m->search.rot.cap +
+                        m->search.cells.cap + m->search.brick.cap + m->search.volume.cap + m->search.small.cap;
     return SLAM_OK;
 }
 
@@ -1520,5 +1497,18 @@ int vmap_dist_view(slam_vmap *m, hipStream_t st, VmapDistView *out)
 }
 
 DevMem &vmap_register_work(slam_vmap *m) { return m->reg_work; }
+
+int vmap_search_view(slam_vmap *m, bool planes, hipStream_t st, VmapSearchView *out)
+{
+    SLAM_REQUIRE(!planes || m->dist_on, SLAM_E_INVALID, "slam_vmap_search: planes_only on a map on which distributions were never enabled");
+    if (planes) SLAM_TRY(slam_vmap_compute_distributions(m, reinterpret_cast<slam_stream_t>(st)));
+    const Table T = m->view();
+    out->key = T.key, out->count = T.count, out->mask = T.mask;
+    out->cen = planes ? m->dists().cen : nullptr;
+    out->leaf = m->P.leaf, out->n_voxels = m->n_voxels;
+    return SLAM_OK;
+}
+
+VmapSearchWork &vmap_search_work(slam_vmap *m) { return m->search; }
 
 } // namespace slam
