@@ -1,7 +1,8 @@
 // kf_common.hpp -- what the keyframe store's two solvers share (kf_edge.hip: point-to-point ICP; kf_gicp.hip: covariances
 // and Generalized ICP): the lattice view and its gated search, the fixed-order block reduction, the register-resident 3 x 3
-// SVD and 6 x 6 inverse, the two ways a point is moved, computeEdgeInformationLUM's pass, the store itself, and the one
-// host path of a batch of registrations (kf_register_batch, at the end).
+// SVD and 6 x 6 inverse, the two ways a point is moved, the write of a result's transform, computeEdgeInformationLUM's pass,
+// the store itself, the staging of a batch (BatchStage, which vmap_gicp.hip uses too) and the one host path of a batch of
+// registrations between keyframes (kf_register_batch, at the end).
 // Device code sits in an unnamed namespace on purpose: every translation unit compiles its own copy with internal linkage.
 // Putting the host path here left the device code of all kernels of both files as it was (docs/KF_GICP.md section 2).
 #pragma once
@@ -297,6 +298,16 @@ __device__ inline void move_f32(const float M[12], const float4 p, float m[3])
     for (int r = 0; r < 3; ++r)
         m[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(M[4 * r], p.x), __fmul_rn(M[4 * r + 1], p.y)), __fmul_rn(M[4 * r + 2], p.z)), M[4 * r + 3]);
 }
+// Thread 0's, once a registration's loop has ended: the total transform sT as the result's f64 and f32 4 x 4, and the f32
+// rows in sTf for the passes that follow
+__device__ __forceinline__ void write_transform(const double *sT, float *sTf, double *transform64, float *transform)
+{
+    for (int k = 0; k < 12; ++k) {
+        transform64[k] = sT[k];
+        transform[k] = sTf[k] = (float)sT[k];
+    }
+    for (int k = 12; k < 16; ++k) transform64[k] = k == 15 ? 1.0 : 0.0, transform[k] = k == 15 ? 1.0f : 0.0f;
+}
 // computeEdgeInformationLUM on the f32 transform sTf (:108-214), by the whole workgroup; the LUM fields of `out` are thread
 // 0's to write.  corr[i] is left holding the sorted slot of source point i's partner strictly inside the gate, or -1.
 __device__ __forceinline__ void lum_pass(const KfView &src, const KfView &tgt, int32_t *corr, double inv_cell, double gate2, const float *sTf,
@@ -423,14 +434,56 @@ inline bool     kf_live(const slam_kf *s, int id) { return s && id >= 0 && id < 
 inline double   inv_cell(const slam_kf_params &p) { return 1.0 / ((p.cell_size > 0 ? p.cell_size : p.gate) * kLatticeMargin); }
 inline unsigned blocks(size_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
+// ---------------------------------------------------------------- the staging of one batch of registrations
+// A work buffer holds tasks | results | trace | extra, each from a multiple of 256 bytes; all but `extra` (device only, the
+// caller's) are mirrored in pinned memory.  lay_out, the caller writes the tasks into the mirror, upload, the caller's one
+// launch, download: one upload, one download, one wait.  Between lay_out and download nobody else may touch the work buffer
+// or call pinned_scratch.
+template <typename Task, typename Result>
+struct BatchStage {
+    hipStream_t st;
+    size_t      task_b, res_b, trace_b, res_off, trace_off, extra_off;
+    char       *host, *dev;
+
+    int lay_out(DevMem &work, const char *who, int n, int trace_cap, size_t extra_b, hipStream_t stream)
+    {
+        st = stream;
+        task_b = sizeof(Task) * (size_t)n, res_b = sizeof(Result) * (size_t)n, trace_b = sizeof(int32_t) * (size_t)n * trace_cap;
+        res_off = (task_b + 255) & ~(size_t)255, trace_off = res_off + ((res_b + 255) & ~(size_t)255);
+        extra_off = trace_off + ((trace_b + 255) & ~(size_t)255);
+        SLAM_TRY(reserve_quarter(work, extra_off + extra_b));
+        host = static_cast<char *>(pinned_scratch(extra_off));
+        SLAM_REQUIRE(host, SLAM_E_NOMEM, "%s: no pinned staging memory", who);
+        dev = static_cast<char *>(work.p);
+        return SLAM_OK;
+    }
+    Task       *tasks() const { return reinterpret_cast<Task *>(host); }
+    const Task *dev_tasks() const { return reinterpret_cast<const Task *>(dev); }
+    Result     *dev_results() const { return reinterpret_cast<Result *>(dev + res_off); }
+    int32_t    *dev_trace() const { return trace_b ? reinterpret_cast<int32_t *>(dev + trace_off) : nullptr; } // null without a trace
+    char       *dev_extra() const { return dev + extra_off; }
+    int         upload() const
+    {
+        SLAM_HIP(hipMemcpyAsync(dev, host, task_b, hipMemcpyHostToDevice, st));
+        return SLAM_OK;
+    }
+    int download(Result *out, int32_t *pairs_trace) const
+    {
+        SLAM_HIP(hipMemcpyAsync(host + res_off, dev + res_off, (trace_off - res_off) + trace_b, hipMemcpyDeviceToHost, st));
+        SLAM_HIP(hipStreamSynchronize(st));
+        std::memcpy(out, host + res_off, res_b);
+        if (trace_b) std::memcpy(pairs_trace, host + trace_off, trace_b);
+        return SLAM_OK;
+    }
+};
+
 // ---------------------------------------------------------------- one batch of registrations, from the requests to the results
-// The host path of both solvers: `who` is the entry point's name and `what` its word for a request (both for the error
-// texts), `kernel` runs one workgroup per request, `lds_enabled` is that kernel's flag in the store (its dynamic LDS limit
-// is raised at most once per store), `fill(task, request)` adds what the task holds beyond the views, `corr` and `init` (which every task type has under these names) and may refuse.  It runs
-// after the work buffer and the pinned staging are laid out: it may launch work on the stream and wait for it (Generalized
-// ICP computes missing covariances there), but must not touch s->work or call pinned_scratch.
-// s->work holds tasks | results | trace | corr, each from a multiple of 256 bytes; all but corr are mirrored in pinned
-// memory.  One upload, one launch, one download, one wait.
+// The host path of both of the store's solvers: `who` is the entry point's name and `what` its word for a request (both for
+// the error texts), `kernel` runs one workgroup per request, `lds_enabled` is that kernel's flag in the store (its dynamic
+// LDS limit is raised at most once per store), `fill(task, request)` adds what the task holds beyond the views, `corr` and
+// `init` (which every task type has under these names) and may refuse.  It runs after the staging is laid out: it may launch
+// work on the stream and wait for it (Generalized ICP computes missing covariances there), but must not touch s->work or
+// call pinned_scratch.  The staging's `extra` is corr: one int per source point of every request.
 template <typename Task, typename Result, typename Params, typename Fill>
 int kf_register_batch(slam_kf *s, const char *who, const char *what, void (*kernel)(const Task *, Params, Result *, int32_t *, int, int),
                       bool &lds_enabled, const Params &P, Fill fill, const slam_kf_edge_req *req, int n, Result *out, int32_t *pairs_trace,
@@ -445,17 +498,10 @@ int kf_register_batch(slam_kf *s, const char *who, const char *what, void (*kern
     }
     if (n == 0) return SLAM_OK;
     if (!pairs_trace) trace_cap = 0;
-    hipStream_t  st = as_stream(stream);
-    const size_t task_b = sizeof(Task) * (size_t)n, res_b = sizeof(Result) * (size_t)n;
-    const size_t trace_b = sizeof(int32_t) * (size_t)n * trace_cap, corr_b = sizeof(int32_t) * n_corr;
-    const size_t res_off = (task_b + 255) & ~(size_t)255, trace_off = res_off + ((res_b + 255) & ~(size_t)255);
-    const size_t corr_off = trace_off + ((trace_b + 255) & ~(size_t)255);
-    SLAM_TRY(reserve_quarter(s->work, corr_off + corr_b));
-    char *host = static_cast<char *>(pinned_scratch(corr_off));
-    SLAM_REQUIRE(host, SLAM_E_NOMEM, "%s: no pinned staging memory", who);
-    char    *dev = static_cast<char *>(s->work.p);
-    Task    *tasks = reinterpret_cast<Task *>(host);
-    int32_t *corr = reinterpret_cast<int32_t *>(dev + corr_off);
+    BatchStage<Task, Result> stage;
+    SLAM_TRY(stage.lay_out(s->work, who, n, trace_cap, sizeof(int32_t) * n_corr, as_stream(stream)));
+    Task    *tasks = stage.tasks();
+    int32_t *corr = reinterpret_cast<int32_t *>(stage.dev_extra());
     int      lds_points = 0;
     for (int e = 0; e < n; ++e) {
         const Keyframe &src = s->kfs[req[e].to], &tgt = s->kfs[req[e].from];
@@ -471,16 +517,11 @@ int kf_register_batch(slam_kf *s, const char *who, const char *what, void (*kern
                                      (int)(sizeof(float4) * kLdsPoints)));
         lds_enabled = true;
     }
-    SLAM_HIP(hipMemcpyAsync(dev, host, task_b, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(kernel, dim3(n), dim3(kEdgeThreads), sizeof(float4) * (size_t)lds_points, st, reinterpret_cast<const Task *>(dev), P,
-                       reinterpret_cast<Result *>(dev + res_off), trace_cap ? reinterpret_cast<int32_t *>(dev + trace_off) : nullptr, trace_cap,
-                       lds_points);
+    SLAM_TRY(stage.upload());
+    hipLaunchKernelGGL(kernel, dim3(n), dim3(kEdgeThreads), sizeof(float4) * (size_t)lds_points, stage.st, stage.dev_tasks(), P, stage.dev_results(),
+                       stage.dev_trace(), trace_cap, lds_points);
     SLAM_HIP(hipGetLastError());
-    SLAM_HIP(hipMemcpyAsync(host + res_off, dev + res_off, (trace_off - res_off) + trace_b, hipMemcpyDeviceToHost, st));
-    SLAM_HIP(hipStreamSynchronize(st));
-    std::memcpy(out, host + res_off, res_b);
-    if (trace_cap) std::memcpy(pairs_trace, host + trace_off, trace_b);
-    return SLAM_OK;
+    return stage.download(out, pairs_trace);
 }
 
 } // namespace

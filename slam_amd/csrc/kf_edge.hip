@@ -223,11 +223,7 @@ __global__ __launch_bounds__(kEdgeThreads) void kf_edge_kernel(const EdgeTask *t
     }
     __syncthreads();
     if (tid == 0) {
-        for (int k = 0; k < 12; ++k) {
-            out->transform64[k] = sT[k];
-            out->transform[k] = sTf[k] = (float)sT[k];
-        }
-        for (int k = 12; k < 16; ++k) out->transform64[k] = k == 15 ? 1.0 : 0.0, out->transform[k] = k == 15 ? 1.0f : 0.0f;
+        write_transform(sT, sTf, out->transform64, out->transform);
         out->iterations = iterations, out->state = sState, out->converged = sState != SLAM_KF_NO_CORRESPONDENCES;
         out->pairs = pairs, out->mse = mse, out->reserved = 0;
     }

@@ -5,9 +5,10 @@
 //                    sums in list order, so the covariances are the restatement's bit for bit.
 //   kf_gicp_kernel   one workgroup per request: gated 1-NN pairs, M = (C'q + R C'p R')^-1 per pair, one Gauss-Newton step per
 //                    iteration by a 6 x 6 Cholesky on thread 0, PCL GICP's stop rule, then the fitness and the LUM block of
-//                    kf_edge.hip on the f32 transform.  Sums are f64, reduced by block_sum in a fixed order.
-#include "kf_common.hpp"
-#include "kf_gicp_math.hpp"
+//                    kf_edge.hip on the f32 transform.  Sums are f64, reduced by block_sum in a fixed order.  The iteration's
+//                    pieces (a pair's share, the three block sums, thread 0's step and stop rule) are kf_gicp_solve.hpp's,
+//                    which vmap_gicp.hip runs too; this file keeps the search in the lattice, the gate and the passes after.
+#include "kf_gicp_solve.hpp"
 
 namespace {
 
@@ -140,7 +141,9 @@ __global__ __launch_bounds__(kEdgeThreads) void kf_gicp_kernel(const GicpTask *t
     slam_kf_gicp_result *out = results + blockIdx.x;
     const int            tid = threadIdx.x;
 
-    if (tgt.n <= lds_points) { // as kf_edge_kernel: the target's points in LDS when they fit, the table and the covariances through L2
+    // The prologue of kf_edge_kernel, kept in both: shared as one function it took this kernel's SGPR spills from 7 to 9
+    // (docs/VOXEL_MAP.md section 14).  The target's points in LDS when they fit, the table and the covariances through L2.
+    if (tgt.n <= lds_points) {
         for (int i = tid; i < tgt.n; i += kEdgeThreads) lds_sorted[i] = tgt.sorted[i];
         tgt.sorted = lds_sorted;
     }
@@ -165,72 +168,13 @@ __global__ __launch_bounds__(kEdgeThreads) void kf_gicp_kernel(const GicpTask *t
             move_f64(T, p, m);
             const int j = nearest27(tgt, P.inv_cell, P.gate2, m[0], m[1], m[2], &d2, &slot);
             if (!(j >= 0 && (double)d2 < P.gate2)) continue; // strict: GICP drops a pair at the gate
-            const float4 q = tgt.sorted[slot];
-            const float  pf[3] = {p.x, p.y, p.z}, qf[3] = {q.x, q.y, q.z};
-            double       Cp[6], Cq[6], h[21] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, g[6] = {0, 0, 0, 0, 0, 0}, c = 0.0;
-#pragma unroll
-            for (int e = 0; e < 6; ++e) Cp[e] = src_cov[6 * (size_t)i + e], Cq[e] = tgt_cov[6 * (size_t)j + e];
-            gicp_pair(T, pf, qf, Cp, Cq, h, g, &c);
-            acc[0] += 1.0, acc[1] += (double)d2, acc[2] += c;
-#pragma unroll
-            for (int e = 0; e < 6; ++e) acc[3 + e] += g[e];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) h16[e] += h[e];
-#pragma unroll
-            for (int e = 0; e < 5; ++e) h5[e] += h[16 + e];
+            gicp_accumulate(T, p, tgt.sorted[slot], d2, src_cov + 6 * (size_t)i, tgt_cov + 6 * (size_t)j, acc, h16, h5);
         }
-        block_sum<double, 9>(acc, red, tot);
-        const double n = tot[0];
-        pairs = (int)n;
-        mse = pairs ? tot[1] / n : 0.0;
-        cost = pairs ? tot[2] / n : 0.0;
         double g[6], hu[21];
-#pragma unroll
-        for (int e = 0; e < 6; ++e) g[e] = tot[3 + e];
-        block_sum<double, 16>(h16, red, tot);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) hu[e] = tot[e];
-        block_sum<double, 5>(h5, red, tot);
-#pragma unroll
-        for (int e = 0; e < 5; ++e) hu[16 + e] = tot[e];
+        gicp_reduce(acc, h16, h5, red, tot, &pairs, &mse, &cost, g, hu);
         if (tid == 0) {
             if (trace && iterations < trace_cap) trace[(size_t)blockIdx.x * trace_cap + iterations] = pairs;
-            double H[36];
-            int    at = 0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int b = a; b < 6; ++b, ++at) H[6 * a + b] = H[6 * b + a] = hu[at];
-#pragma unroll
-            for (int k = 0; k < 36; ++k) sH[k] = H[k];
-            int state = 0;
-            if (pairs < 3)
-                state = SLAM_KF_NO_CORRESPONDENCES;
-            else {
-                double N[12];
-                if (!gicp_step(H, g, T, N))
-                    state = SLAM_KF_DEGENERATE;
-                else {
-#pragma unroll
-                    for (int k = 0; k < 12; ++k) sT[k] = N[k];
-                    ++iterations;
-                    if (iterations >= P.max_iter)
-                        state = SLAM_KF_ITERATIONS;
-                    else { // PCL GICP's rule: no entry of the rotation moved by more than eps_r, none of the translation by more than eps_t
-                        double dr = 0.0, dt = 0.0;
-#pragma unroll
-                        for (int k = 0; k < 12; ++k) {
-                            const double d = fabs(N[k] - T[k]);
-                            if (k % 4 == 3)
-                                dt = d > dt ? d : dt;
-                            else
-                                dr = d > dr ? d : dr;
-                        }
-                        if (dr <= P.eps_r && dt <= P.eps_t) state = SLAM_KF_TRANSFORM;
-                    }
-                }
-            }
-            sState = state;
+            sState = gicp_advance(hu, g, T, pairs, P.max_iter, P.eps_r, P.eps_t, sH, sT, iterations);
         }
         __syncthreads();
         if (sState) break;
@@ -238,11 +182,7 @@ __global__ __launch_bounds__(kEdgeThreads) void kf_gicp_kernel(const GicpTask *t
     __syncthreads();
     if (tid == 0) {
         slam_kf_edge_result *e = &out->edge;
-        for (int k = 0; k < 12; ++k) {
-            e->transform64[k] = sT[k];
-            e->transform[k] = sTf[k] = (float)sT[k];
-        }
-        for (int k = 12; k < 16; ++k) e->transform64[k] = k == 15 ? 1.0 : 0.0, e->transform[k] = k == 15 ? 1.0f : 0.0f;
+        write_transform(sT, sTf, e->transform64, e->transform);
         e->iterations = iterations, e->state = sState;
         e->converged = sState == SLAM_KF_ITERATIONS || sState == SLAM_KF_TRANSFORM;
         e->pairs = pairs, e->mse = mse, e->reserved = 0;

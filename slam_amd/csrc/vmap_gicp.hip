@@ -1,20 +1,20 @@
 // vmap_gicp.hip -- Generalized ICP of a keyframe of the store straight against the voxel map's plane distributions
 // (slam_vmap_register_gicp, docs/VOXEL_MAP.md section 9): no extraction, no lattice of the map, no neighbour search over it.
-//   vmap_gicp_kernel  one workgroup per request, in the frame of kf_gicp_kernel: per iteration every source point is moved by
-//                     T in f64 and rounded to f32, its cell found by the map's rule, and the 27 cells around it looked up in
-//                     the map's own hash table -- the 27 first probes are issued together, a collision (rare below half
-//                     load) is followed alone.  The plane voxel with the smallest (f32 d^2 to its centroid, key) strictly
-//                     inside the gate is the pair; gicp_pair, the f64 block sums in a fixed order, gicp_step on thread 0 and
-//                     PCL GICP's stop rule follow as in kf_gicp.hip.  A last pass with the f32 transform gives the
-//                     point-to-plane fitness.  Lookups only find; nothing is written to the map; no workgroup waits for
-//                     another; every loop is bounded by the source's size, max_iterations or the table's capacity.
+//   vmap_gicp_kernel  one workgroup per request: per iteration every source point is moved by T in f64 and rounded to f32,
+//                     its cell found by the map's rule, and the 27 cells around it looked up in the map's own hash table --
+//                     the 27 first probes are issued together, a collision (rare below half load) is followed alone.  The
+//                     plane voxel with the smallest (f32 d^2 to its centroid, key) strictly inside the gate is the pair.  The
+//                     pair's share of the sums, the f64 block sums in a fixed order and thread 0's step and stop rule are
+//                     kf_gicp_solve.hpp's, the ones kf_gicp_kernel runs; the transform's write and the host's staging of a
+//                     batch are kf_common.hpp's.  A last pass with the f32 transform gives the point-to-plane fitness.
+//                     Lookups only find; nothing is written to the map; no workgroup waits for another; every loop is
+//                     bounded by the source's size, max_iterations or the table's capacity.
 // The map's rules come from vmap_dist.hpp: the hash, the limits and the key packing (vmap_cell_key).  The point-to-cell test in
-// nearest_plane27 is still written out here and must follow vmap_point_cell: the kernel stands at 256 VGPRs with spills, and
-// with the shared function its SGPR spills came out at 55 instead of 58 -- no worse, but not the kernel that was measured
-// (docs/VOXEL_MAP.md section 9.3), so its body stays.
+// nearest_plane27 is still written out here and must follow vmap_point_cell: the kernel stands at 256 VGPRs, and with the
+// shared function its SGPR spills came out three fewer -- no worse, but not the kernel that was measured (docs/VOXEL_MAP.md
+// sections 9.3 and 14), so its body stays.
 // The restatement is tests/cpp/vmap_gicp_oracle.cpp.
-#include "kf_common.hpp"
-#include "kf_gicp_math.hpp"
+#include "kf_gicp_solve.hpp"
 #include "vmap_dist.hpp"
 
 namespace {
@@ -128,82 +128,20 @@ __global__ __launch_bounds__(kEdgeThreads) void vmap_gicp_kernel(const VgTask *t
             move_f64(T, p, m);
             const long long slot = nearest_plane27(V, m, &d2, &q);
             if (!(slot >= 0 && (double)d2 < P.gate2)) continue; // strict
-            const float pf[3] = {p.x, p.y, p.z}, qf[3] = {q.x, q.y, q.z};
-            double      Cp[6], Cq[6], h[21] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, g[6] = {0, 0, 0, 0, 0, 0}, c = 0.0;
-#pragma unroll
-            for (int e = 0; e < 6; ++e) Cp[e] = src_cov[6 * (size_t)i + e], Cq[e] = V.cov[6 * (size_t)slot + e];
-            gicp_pair(T, pf, qf, Cp, Cq, h, g, &c);
-            acc[0] += 1.0, acc[1] += (double)d2, acc[2] += c;
-#pragma unroll
-            for (int e = 0; e < 6; ++e) acc[3 + e] += g[e];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) h16[e] += h[e];
-#pragma unroll
-            for (int e = 0; e < 5; ++e) h5[e] += h[16 + e];
+            gicp_accumulate(T, p, q, d2, src_cov + 6 * (size_t)i, V.cov + 6 * (size_t)slot, acc, h16, h5);
         }
-        block_sum<double, 9>(acc, red, tot);
-        const double n = tot[0];
-        pairs = (int)n;
-        mse = pairs ? tot[1] / n : 0.0;
-        cost = pairs ? tot[2] / n : 0.0;
         double g[6], hu[21];
-#pragma unroll
-        for (int e = 0; e < 6; ++e) g[e] = tot[3 + e];
-        block_sum<double, 16>(h16, red, tot);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) hu[e] = tot[e];
-        block_sum<double, 5>(h5, red, tot);
-#pragma unroll
-        for (int e = 0; e < 5; ++e) hu[16 + e] = tot[e];
+        gicp_reduce(acc, h16, h5, red, tot, &pairs, &mse, &cost, g, hu);
         if (tid == 0) {
             if (trace && iterations < trace_cap) trace[(size_t)blockIdx.x * trace_cap + iterations] = pairs;
-            double H[36];
-            int    at = 0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int b = a; b < 6; ++b, ++at) H[6 * a + b] = H[6 * b + a] = hu[at];
-#pragma unroll
-            for (int k = 0; k < 36; ++k) sH[k] = H[k];
-            int state = 0;
-            if (pairs < 3)
-                state = SLAM_KF_NO_CORRESPONDENCES;
-            else {
-                double N[12];
-                if (!gicp_step(H, g, T, N))
-                    state = SLAM_KF_DEGENERATE;
-                else {
-#pragma unroll
-                    for (int k = 0; k < 12; ++k) sT[k] = N[k];
-                    ++iterations;
-                    if (iterations >= P.max_iter)
-                        state = SLAM_KF_ITERATIONS;
-                    else { // PCL GICP's rule, as kf_gicp_kernel
-                        double dr = 0.0, dt = 0.0;
-#pragma unroll
-                        for (int k = 0; k < 12; ++k) {
-                            const double d = fabs(N[k] - T[k]);
-                            if (k % 4 == 3)
-                                dt = d > dt ? d : dt;
-                            else
-                                dr = d > dr ? d : dr;
-                        }
-                        if (dr <= P.eps_r && dt <= P.eps_t) state = SLAM_KF_TRANSFORM;
-                    }
-                }
-            }
-            sState = state;
+            sState = gicp_advance(hu, g, T, pairs, P.max_iter, P.eps_r, P.eps_t, sH, sT, iterations);
         }
         __syncthreads();
         if (sState) break;
     }
     __syncthreads();
     if (tid == 0) {
-        for (int k = 0; k < 12; ++k) {
-            out->transform64[k] = sT[k];
-            out->transform[k] = sTf[k] = (float)sT[k];
-        }
-        for (int k = 12; k < 16; ++k) out->transform64[k] = k == 15 ? 1.0 : 0.0, out->transform[k] = k == 15 ? 1.0f : 0.0f;
+        write_transform(sT, sTf, out->transform64, out->transform);
         out->iterations = iterations, out->state = sState;
         out->converged = sState == SLAM_KF_ITERATIONS || sState == SLAM_KF_TRANSFORM;
         out->pairs = pairs, out->mse = mse, out->cost = cost;
@@ -268,17 +206,9 @@ int slam_vmap_register_gicp_traced(slam_vmap_t *m, slam_kf_t *store, const slam_
     if (n == 0) return SLAM_OK;
     for (int e = 0; e < n; ++e) SLAM_TRY(slam_kf_compute_covariances(store, req[e].src, stream)); // a second call does nothing
     if (!pairs_trace) trace_cap = 0;
-    // tasks | results | trace, each from a multiple of 256 bytes, mirrored in pinned memory: one upload, one launch, one
-    // download, one wait
-    const size_t task_b = sizeof(VgTask) * (size_t)n, res_b = sizeof(slam_vmap_gicp_result) * (size_t)n;
-    const size_t trace_b = sizeof(int32_t) * (size_t)n * trace_cap;
-    const size_t res_off = (task_b + 255) & ~(size_t)255, trace_off = res_off + ((res_b + 255) & ~(size_t)255), total = trace_off + trace_b;
-    DevMem      &work = vmap_register_work(m);
-    SLAM_TRY(reserve_quarter(work, total));
-    char *host = static_cast<char *>(pinned_scratch(total));
-    SLAM_REQUIRE(host, SLAM_E_NOMEM, "slam_vmap_register_gicp: no pinned staging memory");
-    char   *dev = static_cast<char *>(work.p);
-    VgTask *tasks = reinterpret_cast<VgTask *>(host);
+    BatchStage<VgTask, slam_vmap_gicp_result> stage; // in the map's own work buffer; nothing beyond tasks | results | trace
+    SLAM_TRY(stage.lay_out(vmap_register_work(m), "slam_vmap_register_gicp", n, trace_cap, 0, st));
+    VgTask *tasks = stage.tasks();
     for (int e = 0; e < n; ++e) {
         const Keyframe &kf = store->kfs[req[e].src];
         tasks[e].src = kf.view, tasks[e].src_cov = kf.cov6;
@@ -286,16 +216,10 @@ int slam_vmap_register_gicp_traced(slam_vmap_t *m, slam_kf_t *store, const slam_
     }
     VgParams P;
     P.gate2 = p.gate * p.gate, P.eps_t = p.transformation_epsilon, P.eps_r = p.rotation_epsilon, P.max_iter = p.max_iterations;
-    SLAM_HIP(hipMemcpyAsync(dev, host, task_b, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(vmap_gicp_kernel, dim3(n), dim3(kEdgeThreads), 0, st, reinterpret_cast<const VgTask *>(dev), V, P,
-                       reinterpret_cast<slam_vmap_gicp_result *>(dev + res_off), trace_cap ? reinterpret_cast<int32_t *>(dev + trace_off) : nullptr,
-                       trace_cap);
+    SLAM_TRY(stage.upload());
+    hipLaunchKernelGGL(vmap_gicp_kernel, dim3(n), dim3(kEdgeThreads), 0, st, stage.dev_tasks(), V, P, stage.dev_results(), stage.dev_trace(), trace_cap);
     SLAM_HIP(hipGetLastError());
-    SLAM_HIP(hipMemcpyAsync(host + res_off, dev + res_off, total - res_off, hipMemcpyDeviceToHost, st));
-    SLAM_HIP(hipStreamSynchronize(st));
-    std::memcpy(out, host + res_off, res_b);
-    if (trace_cap) std::memcpy(pairs_trace, host + trace_off, trace_b);
-    return SLAM_OK;
+    return stage.download(out, pairs_trace);
 }
 
 int slam_vmap_register_gicp(slam_vmap_t *m, slam_kf_t *store, const slam_vmap_gicp_req *req, int n, const slam_vmap_gicp_params *params,

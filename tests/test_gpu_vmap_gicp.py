@@ -1,7 +1,8 @@
 """The voxel map's moments, plane distributions and Generalized ICP against them on the device (slam_vmap_enable_distributions
 .. slam_vmap_register_gicp; slam_amd/csrc/voxmap.hip, vmap_gicp.hip) against their scalar restatement
 (tests/cpp/vmap_gicp_oracle.cpp): moments, sums, counts, keys and distributions bit for bit whatever the table's size and the
-order; the registration of the builder's sequence against the growing map step by step; the edges; a batch; handle lifetime.
+order; the registration of the builder's sequence against the growing map step by step; the edges; a batch; the exits the
+sequence never takes (a degenerate step, the iteration cap, a trace shorter than the run, a NaN start); handle lifetime.
 A map on which distributions were never enabled answers what it answered before."""
 import ctypes as C
 import signal
@@ -373,6 +374,102 @@ def test_edges_too_few_pairs_and_no_plane_voxel(sequence):
     for m in (lines, patches, plain):
         m.close()
     small.close()
+
+
+# ------------------------------------------------------------------ the exits the sequence never takes
+@pytest.fixture(scope="module")
+def exits():
+    """Eight plane voxels in a row (normal z, centroids at (c + 1/2, 1/2, 1/2)) on the device and in the restatement, and two
+    small sources, each in a store whose filter keeps every point: a line along x with y = z = 0 exactly, 32 points each in the
+    middle of a 0.25 m filter voxel, and 64 points of a fixed seed in the box x 0 .. 8, y 0 .. 1, z 0.3 .. 0.7.  A source is
+    (store, keyframe id, the store's own filtered cloud, its covariances)."""
+    dm, om = dist_map(1.0)
+    patches = np.concatenate([G.plane_patch((c, 0, 0), 2, n=4) for c in range(8)])
+    dm.integrate(patches)
+    om.integrate(patches)
+    assert check_equal(dm, om)["flag"].sum() == 8
+    rng = np.random.default_rng(20261020)
+    clouds = {"line": (0.25, np.float32([(0.25 * i + 0.125, 0, 0) for i in range(32)])),
+              "box": (0.05, (rng.random((64, 3)) * [8, 1, 0.4] + [0, 0, 0.3]).astype(np.float32))}
+    src = {}
+    for name, (leaf, xyz) in clouds.items():
+        store = api.KeyframeStore(leaf_size=leaf, gate=2.0)
+        kid = store.add_keyframe(xyz)
+        store.compute_covariances(kid)
+        src[name] = (store, kid, store.read_keyframe(kid)[:, :3].copy(), store.covariances(kid))
+        assert len(src[name][2]) == len(xyz) >= 20
+    yield dm, om, src
+    dm.close()
+    for store, *_ in src.values():
+        store.close()
+
+
+def test_degenerate_line_returns_the_start(exits):
+    """no pair constrains the roll about the line: H(0, 0) is an exact zero and the first pivot fails"""
+    dm, om, src = exits
+    store, kid, xyz, cov = src["line"]
+    assert not xyz[:, 1:].any()
+    ro = om.register(xyz, cov, np.eye(4), gate=2.0, trace=4)
+    assert (ro["state"], ro["iterations"], ro["converged"]) == (api.KF_DEGENERATE, 0, 0) and ro["pairs"] >= 3      # the input's guard
+    r = dm.register_gicp(store, kid, np.eye(4), gate=2.0, trace=4)
+    print("degenerate: state %d iterations %d pairs %d trace %s H00 %g" % (r["state"], r["iterations"], r["pairs"], list(r["pairs_trace"]),
+                                                                         r["hessian"][0, 0]))
+    assert (r["state"], r["iterations"], r["converged"], r["pairs"]) == (api.KF_DEGENERATE, 0, 0, ro["pairs"])
+    assert np.array_equal(r["pairs_trace"], ro["pairs_trace"]) and r["pairs_trace"][0] == ro["pairs"]
+    assert VG.same_bits(r["transform"], np.eye(4, dtype=np.float32)) and VG.same_bits(r["transform64"], np.eye(4))
+
+
+@pytest.mark.parametrize("cap", (1, 2))
+def test_iteration_cap(exits, cap):
+    dm, om, src = exits
+    store, kid, xyz, cov = src["box"]
+    ro = om.register(xyz, cov, np.eye(4), gate=2.0, max_iterations=cap, trace=4)
+    assert (ro["state"], ro["iterations"]) == (api.KF_ITERATIONS, cap) and ro["pairs"] >= 3                        # the input's guard
+    r = dm.register_gicp(store, kid, np.eye(4), gate=2.0, max_iterations=cap, trace=4)
+    dp, da = V.pose_error(r["transform64"], ro["transform64"])
+    print("cap %d: state %d iterations %d pairs %d trace %s; device - restatement %.3g m %.3g rad; margin %.3g" %
+          (cap, r["state"], r["iterations"], r["pairs"], list(r["pairs_trace"]), dp, da, ro["margin"]))
+    if not ro["margin"] < MARGIN_TOL:
+        assert (r["state"], r["iterations"], r["converged"]) == (api.KF_ITERATIONS, cap, 1)
+        assert r["pairs"] == ro["pairs"] and np.array_equal(r["pairs_trace"], ro["pairs_trace"])
+    assert dp <= POS_TOL and da <= ANG_TOL
+    dp, da = V.pose_error(r["transform"], ro["transform"])
+    assert dp <= POS_TOL and da <= ANG_TOL
+
+
+def test_a_trace_shorter_than_the_run(exits):
+    """trace_cap 2 of a run of more than two iterations: two entries are written and not a word beyond them, and the result
+    is that of the same call with a long trace"""
+    dm, om, src = exits
+    store, kid, xyz, cov = src["box"]
+    ro = om.register(xyz, cov, np.eye(4), gate=2.0, trace=128)
+    assert ro["iterations"] > 2                                                                                   # the input's guard
+    full = dm.register_gicp(store, kid, np.eye(4), gate=2.0, trace=128)
+    assert full["iterations"] > 2 and (full["pairs_trace"][:full["iterations"]] >= 0).all()
+    req, res, p = api.VmapGicpReq(), api.VmapGicpResult(), api.vmap_default_gicp_params(gate=2.0)
+    req.src = kid
+    req.init[:] = np.eye(4, dtype=np.float32).reshape(16).tolist()
+    tr = np.full(8, -7, np.int32)
+    api.check(api.lib().slam_vmap_register_gicp_traced(dm.h, store.h, C.byref(req), 1, C.byref(p), C.byref(res), tr.ctypes.data_as(C.c_void_p), 2, None))
+    r = api.vmap_gicp_result_dict(res)
+    print("short trace: %s of %s, iterations %d / %d" % (list(tr), list(full["pairs_trace"][:4]), r["iterations"], full["iterations"]))
+    assert np.array_equal(tr[:2], full["pairs_trace"][:2]) and (tr[2:] == -7).all()
+    for f in ("transform", "transform64", "hessian"):
+        assert VG.same_bits(r[f], full[f]), f
+    assert all(r[f] == full[f] for f in ("iterations", "state", "converged", "pairs", "mse", "cost", "fitness", "fitness_pairs"))
+
+
+def test_nan_start_is_returned_as_it_came(exits):
+    dm, om, src = exits
+    store, kid, xyz, cov = src["box"]
+    init = np.full((4, 4), np.nan, np.float32)
+    ro = om.register(xyz, cov, init, gate=2.0, trace=4)
+    assert (ro["state"], ro["iterations"], ro["pairs"]) == (api.KF_NO_CORRESPONDENCES, 0, 0)                      # the input's guard
+    r = dm.register_gicp(store, kid, init, gate=2.0, trace=4)
+    assert (r["state"], r["iterations"], r["converged"], r["pairs"], r["fitness_pairs"]) == (api.KF_NO_CORRESPONDENCES, 0, 0, 0, 0)
+    assert list(r["pairs_trace"]) == [0, -1, -1, -1]
+    assert VG.same_bits(r["transform"][:3], init[:3]) and VG.same_bits(r["transform64"][:3], init[:3].astype(np.float64))
+    assert VG.same_bits(r["transform"][3], np.float32([0, 0, 0, 1])) and VG.same_bits(r["transform64"][3], np.float64([0, 0, 0, 1]))
 
 
 def test_create_enable_integrate_register_destroy_cycles_keep_device_memory_flat(sequence):
