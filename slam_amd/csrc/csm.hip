@@ -51,6 +51,21 @@ struct Scans {
     const double  *t0, *cs;
 };
 
+// the posterior (docs/CSM.md section 6)
+constexpr int kPostSums = 11; // n_within, m0, m1[3], m2[6]
+constexpr int kPostTable = 257; // weights: deficit d of margin M reads entry d * 256 / M
+
+struct PostAcc {
+    long long          sum[kPostSums];
+    unsigned long long second; // score << 32 | ~flat of the best candidate outside the exclusion box; 0 = none
+    int                margin, pad;
+};
+
+struct PostCfg {
+    int    margin_per_point, excl_xy, excl_theta;
+    double theta_step;
+};
+
 __device__ inline bool cell_of(double v, double res, int &c)
 {
     const double f = floor(v / res);
@@ -98,6 +113,37 @@ __device__ inline void stage(const Geom &G, const Tab *tabs, const double *pts, 
         cells[j] = out;
     }
 }
+
+// The walk every search kernel makes over a scan at (c, s, t0): the points staged kChunk at a time by the workgroup's
+// `threads` lanes, then every lane over all of them, class GA before class NGA: body(cell, table of its class).
+template <class Body>
+__device__ __forceinline__ void walk(const Geom &G, const Tab *tabs, const double *pts, int first, int n, int n_ga, double c, double s, double tx,
+                                     double ty, int2 *cells, int threads, Body body)
+{
+    for (int base = 0; base < n; base += kChunk) {
+        const int cn = n - base < kChunk ? n - base : kChunk;
+        __syncthreads();
+        stage(G, tabs, pts, first, base, cn, n_ga, c, s, tx, ty, cells, threads);
+        __syncthreads();
+        const int split = n_ga - base < 0 ? 0 : (n_ga - base > cn ? cn : n_ga - base);
+        for (int cl = 0; cl < 2; ++cl) {
+            const Tab t = tabs[cl];
+            const int j1 = cl ? cn : split;
+            for (int j = cl ? split : 0; j < j1; ++j) body(cells[j], t);
+        }
+    }
+}
+
+// (cos, sin) of angle k of scan s
+__device__ inline double2 cos_sin(const Geom &G, const Scans &S, int s, int k)
+{
+    return make_double2(S.cs[((size_t)s * G.nth + k) * 2], S.cs[((size_t)s * G.nth + k) * 2 + 1]);
+}
+
+// the flat index of candidate (k, b, a) and back
+__device__ inline unsigned flat_of(const Geom &G, int k, int b, int a) { return ((unsigned)k * G.ny + b) * G.nx + a; }
+
+__device__ inline void unflat(const Geom &G, unsigned flat, int &k, int &b, int &a) { k = flat / (G.nx * G.ny), b = flat / G.nx % G.ny, a = flat % G.nx; }
 
 __device__ inline unsigned long long key_of(int score, unsigned flat) { return ((unsigned long long)(unsigned)score << 32) | (unsigned)~flat; }
 
@@ -174,39 +220,27 @@ __global__ __launch_bounds__(256) void csm_tiles_kernel(Geom G, Scans S, int32_t
     int             first, n, n_ga;
     scan_range(S, s, first, n, n_ga);
     if (n < 5) return;
-    const int    a = (blockIdx.x % tiles_x) * kTileW + (threadIdx.x & 63);
-    const int    b0 = (blockIdx.x / tiles_x) * kTileH + (threadIdx.x >> 6) * kTileRows;
-    const double c = S.cs[((size_t)s * G.nth + k) * 2], sn = S.cs[((size_t)s * G.nth + k) * 2 + 1];
-    const double tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
-    int          acc[kTileRows];
+    const int     a = (blockIdx.x % tiles_x) * kTileW + (threadIdx.x & 63);
+    const int     b0 = (blockIdx.x / tiles_x) * kTileH + (threadIdx.x >> 6) * kTileRows;
+    const double  tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
+    const double2 cs = cos_sin(G, S, s, k);
+    int           acc[kTileRows];
 #pragma unroll
     for (int r = 0; r < kTileRows; ++r) acc[r] = 0;
-    for (int base = 0; base < n; base += kChunk) {
-        const int cn = n - base < kChunk ? n - base : kChunk;
-        __syncthreads();
-        stage(G, G.T, S.pts, first, base, cn, n_ga, c, sn, tx, ty, cells, 256);
-        __syncthreads();
-        const int split = n_ga - base < 0 ? 0 : (n_ga - base > cn ? cn : n_ga - base);
-        for (int cl = 0; cl < 2; ++cl) {
-            const Tab t = G.T[cl];
-            const int j1 = cl ? cn : split;
-            for (int j = cl ? split : 0; j < j1; ++j) {
-                const int2 q = cells[j];
-                const int  col = q.x + a, row0 = q.y + b0;
-                if ((unsigned)col < (unsigned)t.w) {
+    walk(G, G.T, S.pts, first, n, n_ga, cs.x, cs.y, tx, ty, cells, 256, [&](int2 q, const Tab &t) {
+        const int col = q.x + a, row0 = q.y + b0;
+        if ((unsigned)col < (unsigned)t.w) {
 #pragma unroll
-                    for (int r = 0; r < kTileRows; ++r)
-                        if ((unsigned)(row0 + r) < (unsigned)t.h) acc[r] += t.v[(size_t)(row0 + r) * t.w + col];
-                }
-            }
+            for (int r = 0; r < kTileRows; ++r)
+                if ((unsigned)(row0 + r) < (unsigned)t.h) acc[r] += t.v[(size_t)(row0 + r) * t.w + col];
         }
-    }
+    });
     unsigned long long key = 0;
     if (a < G.nx) {
 #pragma unroll
         for (int r = 0; r < kTileRows; ++r)
             if (b0 + r < G.ny) {
-                const unsigned flat = ((unsigned)k * G.ny + (b0 + r)) * G.nx + a;
+                const unsigned flat = flat_of(G, k, b0 + r, a);
                 if (vol) vol[flat] = acc[r];
                 const unsigned long long kk = key_of(acc[r], flat);
                 key = kk > key ? kk : key;
@@ -228,34 +262,22 @@ __global__ __launch_bounds__(64) void csm_coarse_kernel(Geom G, Scans S, int32_t
     int             first, n, n_ga;
     scan_range(S, s, first, n, n_ga);
     if (n < 5) return;
-    const double c = S.cs[((size_t)s * G.nth + k) * 2], sn = S.cs[((size_t)s * G.nth + k) * 2 + 1];
-    const double tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
-    int          blk[kCoarsePer], dx[kCoarsePer], dy[kCoarsePer], acc[kCoarsePer];
+    const double  tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
+    const double2 cs = cos_sin(G, S, s, k);
+    int           blk[kCoarsePer], dx[kCoarsePer], dy[kCoarsePer], acc[kCoarsePer];
 #pragma unroll
     for (int r = 0; r < kCoarsePer; ++r) {
         blk[r] = (grp * kCoarsePer + r) * 64 + threadIdx.x;
         dx[r] = (blk[r] % G.nbx) * G.D, dy[r] = (blk[r] / G.nbx) * G.D; // (a block beyond nb reads rows that may exist: it is not written)
         acc[r] = 0;
     }
-    for (int base = 0; base < n; base += kChunk) {
-        const int cn = n - base < kChunk ? n - base : kChunk;
-        __syncthreads();
-        stage(G, G.W, S.pts, first, base, cn, n_ga, c, sn, tx, ty, cells, 64);
-        __syncthreads();
-        const int split = n_ga - base < 0 ? 0 : (n_ga - base > cn ? cn : n_ga - base);
-        for (int cl = 0; cl < 2; ++cl) {
-            const Tab t = G.W[cl];
-            const int j1 = cl ? cn : split;
-            for (int j = cl ? split : 0; j < j1; ++j) {
-                const int2 q = cells[j];
+    walk(G, G.W, S.pts, first, n, n_ga, cs.x, cs.y, tx, ty, cells, 64, [&](int2 q, const Tab &t) {
 #pragma unroll
-                for (int r = 0; r < kCoarsePer; ++r) {
-                    const int col = q.x + dx[r], row = q.y + dy[r];
-                    if ((unsigned)col < (unsigned)t.w && (unsigned)row < (unsigned)t.h) acc[r] += t.v[(size_t)row * t.w + col];
-                }
-            }
+        for (int r = 0; r < kCoarsePer; ++r) {
+            const int col = q.x + dx[r], row = q.y + dy[r];
+            if ((unsigned)col < (unsigned)t.w && (unsigned)row < (unsigned)t.h) acc[r] += t.v[(size_t)row * t.w + col];
         }
-    }
+    });
     unsigned long long key = 0;
 #pragma unroll
     for (int r = 0; r < kCoarsePer; ++r)
@@ -269,53 +291,51 @@ __global__ __launch_bounds__(64) void csm_coarse_kernel(Geom G, Scans S, int32_t
     if (threadIdx.x == 0 && key) atomicMax(&top[s], key);
 }
 
-// One wave per block at full resolution.  list == nullptr: the scan's top block alone (grid.x = 1); else the wave strides over
-// the scan's list.  Lane c of D * D: candidate (A D + c % D, B D + c / D); a ragged block's missing candidates are left out.
+// Block f = (k N_by + B) N_bx + A at full resolution by one wave: lane c of D * D holds candidates c, c + 64, ... in its
+// kBlockPer registers, candidate (a, b) = (A D + c % D, B D + c / D) with score sc; a = -1: there is none (beyond D * D, or
+// missing from a ragged block).
+__device__ __forceinline__ void eval_block(const Geom &G, const Scans &S, int s, int first, int n, int n_ga, double tx, double ty, unsigned f,
+                                           int2 *cells, int &k, int (&a)[kBlockPer], int (&b)[kBlockPer], int (&sc)[kBlockPer])
+{
+    const int nb = G.nbx * G.nby, A = (f % nb) % G.nbx, B = (f % nb) / G.nbx;
+    k = f / nb;
+    const double2 cs = cos_sin(G, S, s, k);
+#pragma unroll
+    for (int r = 0; r < kBlockPer; ++r) {
+        const int cnd = r * 64 + threadIdx.x;
+        a[r] = A * G.D + cnd % G.D, b[r] = B * G.D + cnd / G.D, sc[r] = 0;
+        if (cnd >= G.D * G.D || a[r] >= G.nx || b[r] >= G.ny) a[r] = -1;
+    }
+    walk(G, G.T, S.pts, first, n, n_ga, cs.x, cs.y, tx, ty, cells, 64, [&](int2 q, const Tab &t) {
+#pragma unroll
+        for (int r = 0; r < kBlockPer; ++r) {
+            const int col = q.x + a[r], row = q.y + b[r];
+            if (a[r] >= 0 && (unsigned)col < (unsigned)t.w && (unsigned)row < (unsigned)t.h) sc[r] += t.v[(size_t)row * t.w + col];
+        }
+    });
+}
+
+// One wave per block (eval_block), its best candidate offered to the scan's key.  list == nullptr: the scan's top block alone
+// (grid.x = 1); else the wave strides over the scan's list.
 __global__ __launch_bounds__(64) void csm_blocks_kernel(Geom G, Scans S, const unsigned long long *top, const int32_t *list, const int32_t *count,
                                                         unsigned long long *best)
 {
     __shared__ int2 cells[kChunk];
-    const int       nb = G.nbx * G.nby, s = blockIdx.y;
+    const int       s = blockIdx.y;
     int             first, n, n_ga;
     scan_range(S, s, first, n, n_ga);
     if (n < 5) return;
     const int    items = list ? count[s] : 1;
     const double tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
     for (int it = blockIdx.x; it < items; it += gridDim.x) {
-        const unsigned f = list ? (unsigned)list[(size_t)s * G.nth * nb + it] : ~(unsigned)top[s];
-        const int      k = f / nb, A = (f % nb) % G.nbx, B = (f % nb) / G.nbx;
-        const double   c = S.cs[((size_t)s * G.nth + k) * 2], sn = S.cs[((size_t)s * G.nth + k) * 2 + 1];
-        int            a[kBlockPer], b[kBlockPer], acc[kBlockPer];
-#pragma unroll
-        for (int r = 0; r < kBlockPer; ++r) {
-            const int cnd = r * 64 + threadIdx.x;
-            a[r] = A * G.D + cnd % G.D, b[r] = B * G.D + cnd / G.D, acc[r] = 0;
-            if (cnd >= G.D * G.D || a[r] >= G.nx || b[r] >= G.ny) a[r] = -1;
-        }
-        for (int base = 0; base < n; base += kChunk) {
-            const int cn = n - base < kChunk ? n - base : kChunk;
-            __syncthreads();
-            stage(G, G.T, S.pts, first, base, cn, n_ga, c, sn, tx, ty, cells, 64);
-            __syncthreads();
-            const int split = n_ga - base < 0 ? 0 : (n_ga - base > cn ? cn : n_ga - base);
-            for (int cl = 0; cl < 2; ++cl) {
-                const Tab t = G.T[cl];
-                const int j1 = cl ? cn : split;
-                for (int j = cl ? split : 0; j < j1; ++j) {
-                    const int2 q = cells[j];
-#pragma unroll
-                    for (int r = 0; r < kBlockPer; ++r) {
-                        const int col = q.x + a[r], row = q.y + b[r];
-                        if (a[r] >= 0 && (unsigned)col < (unsigned)t.w && (unsigned)row < (unsigned)t.h) acc[r] += t.v[(size_t)row * t.w + col];
-                    }
-                }
-            }
-        }
+        int k, a[kBlockPer], b[kBlockPer], sc[kBlockPer];
+        const unsigned f = list ? (unsigned)list[(size_t)s * G.nth * G.nbx * G.nby + it] : ~(unsigned)top[s];
+        eval_block(G, S, s, first, n, n_ga, tx, ty, f, cells, k, a, b, sc);
         unsigned long long key = 0;
 #pragma unroll
         for (int r = 0; r < kBlockPer; ++r)
             if (a[r] >= 0) {
-                const unsigned long long kk = key_of(acc[r], ((unsigned)k * G.ny + b[r]) * G.nx + a[r]);
+                const unsigned long long kk = key_of(sc[r], flat_of(G, k, b[r], a[r]));
                 key = kk > key ? kk : key;
             }
         key = wave_max(key);
@@ -323,56 +343,69 @@ __global__ __launch_bounds__(64) void csm_blocks_kernel(Geom G, Scans S, const u
     }
 }
 
-// every block whose bound reaches the lower bound L (>=: a tie with the best so far must survive), the top block excepted
-__global__ void csm_select_kernel(Geom G, Scans S, const int32_t *U, const unsigned long long *top, const unsigned long long *best, int32_t *list,
-                                  int32_t *count)
+// The blocks of every scan that are evaluated next, appended to its list in any order.  kKeepMatch: every block whose bound
+// reaches the lower bound L = best (>=: a tie with the best so far must survive), the top block excepted: it gave L.
+// kKeepWithin: every block that can hold a candidate with S >= S* - M, that is U >= S* - M, the top block included.
+// kKeepAll: every block (the exhaustive form has no bounds to read).
+enum Keep { kKeepMatch, kKeepWithin, kKeepAll };
+
+__global__ void csm_select_kernel(Geom G, Scans S, Keep keep, const int32_t *U, const unsigned long long *top, const unsigned long long *best,
+                                  const PostAcc *acc, int32_t *list, int32_t *count)
 {
     const int per = G.nth * G.nbx * G.nby, s = blockIdx.y;
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     int       first, n, n_ga;
     scan_range(S, s, first, n, n_ga);
     if (n < 5 || f >= per) return;
-    const int L = (int)(best[s] >> 32);
-    if (U[(size_t)s * per + f] >= L && (unsigned)f != ~(unsigned)top[s]) list[(size_t)s * per + atomicAdd(&count[s], 1)] = f;
+    const int score = (int)(best[s] >> 32);
+    bool      in = true;
+    if (keep == kKeepMatch) in = U[(size_t)s * per + f] >= score && (unsigned)f != ~(unsigned)top[s];
+    if (keep == kKeepWithin) in = U[(size_t)s * per + f] >= (long long)score - acc[s].margin;
+    if (in) list[(size_t)s * per + atomicAdd(&count[s], 1)] = f;
+}
+
+// The points of the scan that have a cell at (c, s, t0), counted by a workgroup of 256; every lane gets the count.
+__device__ inline int points_counted(const Geom &G, const Scans &S, int first, int n, int n_ga, double2 cs, double tx, double ty)
+{
+    __shared__ int counted;
+    if (threadIdx.x == 0) counted = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        int cx, cy;
+        mine += point_cell(G.T, S.pts, first, i, n_ga, cs.x, cs.y, tx, ty, G.res, cx, cy) ? 1 : 0;
+    }
+    atomicAdd(&counted, mine);
+    __syncthreads();
+    return counted;
 }
 
 // the answer of scan s: the winner's indices, the points counted at its angle, the pose
 __global__ __launch_bounds__(256) void csm_finish_kernel(Geom G, Scans S, const unsigned long long *best, const int32_t *count, int all_blocks,
                                                          const double *R0, double *R, double *t, slam_csm_result *res)
 {
-    __shared__ int counted;
-    const int      s = blockIdx.x;
-    int            first, n, n_ga;
+    const int s = blockIdx.x;
+    int       first, n, n_ga;
     scan_range(S, s, first, n, n_ga);
-    const double tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
-    double       r0[4];
-    for (int i = 0; i < 4; ++i) r0[i] = R0[4 * s + i];
-    if (threadIdx.x == 0) counted = 0;
-    __syncthreads(); // (also: every read of the initial pose is behind us when R and t, which may be the same arrays, are written)
     slam_csm_result out = {0, 0, 0, -1, 0, 0, 0};
     if (n < 5) {
-        if (threadIdx.x == 0) {
-            for (int i = 0; i < 4; ++i) R[4 * s + i] = r0[i];
-            t[2 * s] = tx, t[2 * s + 1] = ty;
+        if (threadIdx.x == 0) { // (R and t may be the arrays of the initial pose)
+            for (int i = 0; i < 4; ++i) R[4 * s + i] = R0[4 * s + i];
+            t[2 * s] = S.t0[2 * s], t[2 * s + 1] = S.t0[2 * s + 1];
             if (res) res[s] = out;
         }
         return;
     }
-    const unsigned long long key = best[s];
-    const unsigned           flat = ~(unsigned)key;
-    out.k = flat / (G.nx * G.ny), out.b = flat / G.nx % G.ny, out.a = flat % G.nx, out.score = (int)(key >> 32);
-    const double c = S.cs[((size_t)s * G.nth + out.k) * 2], sn = S.cs[((size_t)s * G.nth + out.k) * 2 + 1];
-    int          mine = 0;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        int cx, cy;
-        mine += point_cell(G.T, S.pts, first, i, n_ga, c, sn, tx, ty, G.res, cx, cy) ? 1 : 0;
-    }
-    atomicAdd(&counted, mine);
-    __syncthreads();
+    unflat(G, ~(unsigned)best[s], out.k, out.b, out.a);
+    out.score = (int)(best[s] >> 32);
+    const double  tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
+    const double2 cs = cos_sin(G, S, s, out.k);
+    // (its barriers also put every lane's read of t0 before the write of t, which may be the same array)
+    out.n_points = points_counted(G, S, first, n, n_ga, cs, tx, ty);
     if (threadIdx.x == 0) {
-        out.n_points = counted, out.max_score = 255 * counted;
+        out.max_score = 255 * out.n_points;
         out.blocks_evaluated = all_blocks ? all_blocks : count[s] + 1;
-        R[4 * s] = c, R[4 * s + 1] = -sn, R[4 * s + 2] = sn, R[4 * s + 3] = c;
+        R[4 * s] = cs.x, R[4 * s + 1] = -cs.y, R[4 * s + 2] = cs.y, R[4 * s + 3] = cs.x;
         t[2 * s] = __dadd_rn(tx, __dmul_rn((double)(out.a - G.half_x), G.res));
         t[2 * s + 1] = __dadd_rn(ty, __dmul_rn((double)(out.b - G.half_y), G.res));
         if (res) res[s] = out;
@@ -381,22 +414,8 @@ __global__ __launch_bounds__(256) void csm_finish_kernel(Geom G, Scans S, const 
 
 // ---------------------------------------------------------------- the posterior (docs/CSM.md section 6)
 // After a match: the margin M from the points counted at the winning angle (csm_post_prepare_kernel), every block whose bound
-// reaches S* - M (csm_post_select_kernel), those blocks at full resolution into eleven int64 sums and the second mode's key
+// reaches S* - M (csm_select_kernel), those blocks at full resolution into eleven int64 sums and the second mode's key
 // (csm_post_accumulate_kernel), and the f64 finish (csm_post_finish_kernel).  Integer sums: any order gives the same bits.
-constexpr int kPostSums = 11; // n_within, m0, m1[3], m2[6]
-constexpr int kPostTable = 257; // weights: deficit d of margin M reads entry d * 256 / M
-
-struct PostAcc {
-    long long          sum[kPostSums];
-    unsigned long long second; // score << 32 | ~flat of the best candidate outside the exclusion box; 0 = none
-    int                margin, pad;
-};
-
-struct PostCfg {
-    int    margin_per_point, excl_xy, excl_theta, all_blocks;
-    double theta_step;
-};
-
 __device__ inline long long wave_sum(long long v)
 {
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
@@ -406,24 +425,14 @@ __device__ inline long long wave_sum(long long v)
 // scan s: clears its sums, its second-mode key and its list counter, and sets M = margin_per_point * n_points
 __global__ __launch_bounds__(256) void csm_post_prepare_kernel(Geom G, Scans S, PostCfg C, const unsigned long long *best, PostAcc *acc, int32_t *count)
 {
-    __shared__ int counted;
-    const int      s = blockIdx.x;
-    int            first, n, n_ga;
+    const int s = blockIdx.x;
+    int       first, n, n_ga, counted = 0;
     scan_range(S, s, first, n, n_ga);
-    if (threadIdx.x == 0) counted = 0;
-    __syncthreads();
     if (n >= 5) {
-        const int    k = (int)(~(unsigned)best[s] / (unsigned)(G.nx * G.ny));
-        const double c = S.cs[((size_t)s * G.nth + k) * 2], sn = S.cs[((size_t)s * G.nth + k) * 2 + 1];
-        const double tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
-        int          mine = 0;
-        for (int i = threadIdx.x; i < n; i += 256) {
-            int cx, cy;
-            mine += point_cell(G.T, S.pts, first, i, n_ga, c, sn, tx, ty, G.res, cx, cy) ? 1 : 0;
-        }
-        atomicAdd(&counted, mine);
+        int k, b, a;
+        unflat(G, ~(unsigned)best[s], k, b, a);
+        counted = points_counted(G, S, first, n, n_ga, cos_sin(G, S, s, k), S.t0[2 * s], S.t0[2 * s + 1]);
     }
-    __syncthreads();
     if (threadIdx.x == 0) {
         PostAcc z;
         for (int i = 0; i < kPostSums; ++i) z.sum[i] = 0;
@@ -433,69 +442,29 @@ __global__ __launch_bounds__(256) void csm_post_prepare_kernel(Geom G, Scans S, 
     }
 }
 
-// every block that can hold a candidate with S >= S* - M: U >= S* - M, the top block included; all_blocks: every block
-__global__ void csm_post_select_kernel(Geom G, Scans S, PostCfg C, const int32_t *U, const unsigned long long *best, const PostAcc *acc, int32_t *list,
-                                       int32_t *count)
-{
-    const int per = G.nth * G.nbx * G.nby, s = blockIdx.y;
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    int       first, n, n_ga;
-    scan_range(S, s, first, n, n_ga);
-    if (n < 5 || f >= per) return;
-    const long long low = (long long)(int)(best[s] >> 32) - acc[s].margin;
-    if (C.all_blocks || U[(size_t)s * per + f] >= low) list[(size_t)s * per + atomicAdd(&count[s], 1)] = f;
-}
-
-// csm_blocks_kernel's wave per listed block, then every lane's candidates into the weight and the eleven terms.  A wave keeps
+// One wave per listed block (eval_block), then every lane's candidates into the weight and the eleven terms.  A wave keeps
 // the sums of all the items it strides over and adds them to the scan's once.
 __global__ __launch_bounds__(64) void csm_post_accumulate_kernel(Geom G, Scans S, PostCfg C, const unsigned long long *best, const int32_t *list,
                                                                  const int32_t *count, const uint32_t *wtab, PostAcc *acc)
 {
     __shared__ int2 cells[kChunk];
-    const int       nb = G.nbx * G.nby, s = blockIdx.y;
+    const int       s = blockIdx.y;
     int             first, n, n_ga;
     scan_range(S, s, first, n, n_ga);
     if (n < 5) return;
     const int items = count[s];
     if ((int)blockIdx.x >= items) return;
-    const double   tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
-    const unsigned wflat = ~(unsigned)best[s];
-    const int      wk = wflat / (G.nx * G.ny), wb = wflat / G.nx % G.ny, wa = wflat % G.nx, top = (int)(best[s] >> 32);
-    const int      M = acc[s].margin;
+    const double tx = S.t0[2 * s], ty = S.t0[2 * s + 1];
+    const int    top = (int)(best[s] >> 32), M = acc[s].margin;
+    int          wk, wb, wa;
+    unflat(G, ~(unsigned)best[s], wk, wb, wa);
     long long          sum[kPostSums];
     unsigned long long key = 0;
 #pragma unroll
     for (int i = 0; i < kPostSums; ++i) sum[i] = 0;
     for (int it = blockIdx.x; it < items; it += gridDim.x) {
-        const unsigned f = (unsigned)list[(size_t)s * G.nth * nb + it];
-        const int      k = f / nb, A = (f % nb) % G.nbx, B = (f % nb) / G.nbx;
-        const double   c = S.cs[((size_t)s * G.nth + k) * 2], sn = S.cs[((size_t)s * G.nth + k) * 2 + 1];
-        int            a[kBlockPer], b[kBlockPer], sc[kBlockPer];
-#pragma unroll
-        for (int r = 0; r < kBlockPer; ++r) {
-            const int cnd = r * 64 + threadIdx.x;
-            a[r] = A * G.D + cnd % G.D, b[r] = B * G.D + cnd / G.D, sc[r] = 0;
-            if (cnd >= G.D * G.D || a[r] >= G.nx || b[r] >= G.ny) a[r] = -1; // a ragged block's missing candidates take no part
-        }
-        for (int base = 0; base < n; base += kChunk) {
-            const int cn = n - base < kChunk ? n - base : kChunk;
-            __syncthreads();
-            stage(G, G.T, S.pts, first, base, cn, n_ga, c, sn, tx, ty, cells, 64);
-            __syncthreads();
-            const int split = n_ga - base < 0 ? 0 : (n_ga - base > cn ? cn : n_ga - base);
-            for (int cl = 0; cl < 2; ++cl) {
-                const Tab t = G.T[cl];
-                const int j1 = cl ? cn : split;
-                for (int j = cl ? split : 0; j < j1; ++j) {
-                    const int2 q = cells[j];
-#pragma unroll
-                    for (int r = 0; r < kBlockPer; ++r) {
-                        const int col = q.x + a[r], row = q.y + b[r];
-                        if (a[r] >= 0 && (unsigned)col < (unsigned)t.w && (unsigned)row < (unsigned)t.h) sc[r] += t.v[(size_t)row * t.w + col];
-                    }
-                }
-            }
-        }
+        int k, a[kBlockPer], b[kBlockPer], sc[kBlockPer];
+        eval_block(G, S, s, first, n, n_ga, tx, ty, (unsigned)list[(size_t)s * G.nth * G.nbx * G.nby + it], cells, k, a, b, sc);
 #pragma unroll
         for (int r = 0; r < kBlockPer; ++r) {
             const int d = top - sc[r];
@@ -507,7 +476,7 @@ __global__ __launch_bounds__(64) void csm_post_accumulate_kernel(Geom G, Scans S
             sum[5] += w * o[0] * o[0], sum[6] += w * o[0] * o[1], sum[7] += w * o[0] * o[2];
             sum[8] += w * o[1] * o[1], sum[9] += w * o[1] * o[2], sum[10] += w * o[2] * o[2];
             if (o[0] > C.excl_xy || o[0] < -C.excl_xy || o[1] > C.excl_xy || o[1] < -C.excl_xy || o[2] > C.excl_theta || o[2] < -C.excl_theta) {
-                const unsigned long long kk = key_of(sc[r], ((unsigned)k * G.ny + b[r]) * G.nx + a[r]);
+                const unsigned long long kk = key_of(sc[r], flat_of(G, k, b[r], a[r]));
                 key = kk > key ? kk : key;
             }
         }
@@ -540,9 +509,8 @@ __global__ void csm_post_finish_kernel(Geom G, Scans S, PostCfg C, int n_scans, 
         const PostAcc &a = acc[s];
         out.valid = 1, out.n_within = (int)a.sum[0], out.margin = a.margin, out.blocks_evaluated = count[s];
         if (a.second) {
-            const unsigned flat = ~(unsigned)a.second;
             out.second_score = (int)(a.second >> 32);
-            out.second_k = flat / (G.nx * G.ny), out.second_b = flat / G.nx % G.ny, out.second_a = flat % G.nx;
+            unflat(G, ~(unsigned)a.second, out.second_k, out.second_b, out.second_a);
         }
         out.m0 = a.sum[1];
         for (int i = 0; i < 3; ++i) out.m1[i] = a.sum[2 + i];
@@ -565,6 +533,15 @@ __global__ void csm_post_finish_kernel(Geom G, Scans S, PostCfg C, int n_scans, 
 
 inline unsigned blocks_for(size_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
+inline int tile_count(const Geom &G) { return ((G.nx + kTileW - 1) / kTileW) * ((G.ny + kTileH - 1) / kTileH); }
+
+// workgroups striding over one scan's list in csm_blocks_kernel and csm_post_accumulate_kernel
+inline int list_stride(int n_scans)
+{
+    const int stride = 4096 / n_scans;
+    return stride < 8 ? 8 : (stride > 1024 ? 1024 : stride);
+}
+
 } // namespace
 
 struct slam_csm {
@@ -573,7 +550,8 @@ struct slam_csm {
         int    ox = 0, oy = 0, w = 0, h = 0;
         DevMem T, W;
     } tab[2];
-    // scratch of a match, for max_scans scans: the bounds, the survivor list, then top and best keys and the list counters
+    // scratch of a match, for max_scans scans: the bounds, the survivor list, and the keys: every scan's top key, then every
+    // scan's best key, then the list counters
     DevMem U, list, keys;
     int    max_scans = 0;
     // staging of the host form
@@ -582,6 +560,11 @@ struct slam_csm {
     slam_csm_post_params PP = {0, 0.0, 0, 0};
     bool                 post_set = false;
     DevMem               wtab, post;
+
+    static size_t       key_bytes(int scans) { return (2 * sizeof(unsigned long long) + sizeof(int32_t)) * (size_t)scans; }
+    unsigned long long *top() const { return keys.as<unsigned long long>(); }
+    unsigned long long *best() const { return top() + max_scans; }
+    int32_t            *count() const { return reinterpret_cast<int32_t *>(best() + max_scans); }
 
     int  nth() const { return 2 * P.half_theta + 1; }
     int  nx() const { return 2 * P.half_x + 1; }
@@ -670,10 +653,23 @@ int reserve_scans(slam_csm *s, int max_scans)
     SLAM_REQUIRE((double)per * max_scans * sizeof(int32_t) < 4e9, SLAM_E_INVALID, "slam_csm_reserve: %d scans of %zu blocks are too many", max_scans, per);
     SLAM_TRY(s->U.reserve(sizeof(int32_t) * per * max_scans));
     SLAM_TRY(s->list.reserve(sizeof(int32_t) * per * max_scans));
-    SLAM_TRY(s->keys.reserve((2 * sizeof(unsigned long long) + sizeof(int32_t)) * (size_t)max_scans));
+    SLAM_TRY(s->keys.reserve(slam_csm::key_bytes(max_scans)));
     if (s->post_set) SLAM_TRY(s->post.reserve(sizeof(PostAcc) * (size_t)max_scans));
     s->max_scans = max_scans;
     return SLAM_OK;
+}
+
+// what both create calls check before they touch the device; p: the parameters in force
+int create_arguments(const double *m_ga, int n_ga, const double *m_nga, int n_nga, const slam_csm_params *params, slam_csm_t **out,
+                     slam_csm_params &p)
+{
+    SLAM_REQUIRE(out, SLAM_E_INVALID, "slam_csm_create: null out pointer");
+    *out = nullptr;
+    SLAM_REQUIRE(n_ga >= 0 && n_nga >= 0 && (n_ga == 0 || m_ga) && (n_nga == 0 || m_nga), SLAM_E_INVALID, "slam_csm_create: bad model arrays");
+    slam_csm_default_params(&p);
+    if (params) p = *params;
+    SLAM_TRY(check_params(p));
+    return require_device();
 }
 
 int create_common(const double *d_ga, int n_ga, const double *d_nga, int n_nga, const slam_csm_params &p, slam_csm_t **out)
@@ -718,27 +714,15 @@ void slam_csm_default_params(slam_csm_params *p)
 
 int slam_csm_create_dev(const double *d_m_ga, int n_ga, const double *d_m_nga, int n_nga, const slam_csm_params *params, slam_csm_t **out)
 {
-    SLAM_REQUIRE(out, SLAM_E_INVALID, "slam_csm_create: null out pointer");
-    *out = nullptr;
-    SLAM_REQUIRE(n_ga >= 0 && n_nga >= 0 && (n_ga == 0 || d_m_ga) && (n_nga == 0 || d_m_nga), SLAM_E_INVALID, "slam_csm_create: bad model arrays");
     slam_csm_params p;
-    slam_csm_default_params(&p);
-    if (params) p = *params;
-    SLAM_TRY(check_params(p));
-    SLAM_TRY(require_device());
+    SLAM_TRY(create_arguments(d_m_ga, n_ga, d_m_nga, n_nga, params, out, p));
     return create_common(d_m_ga, n_ga, d_m_nga, n_nga, p, out);
 }
 
 int slam_csm_create(const double *m_ga, int n_ga, const double *m_nga, int n_nga, const slam_csm_params *params, slam_csm_t **out)
 {
-    SLAM_REQUIRE(out, SLAM_E_INVALID, "slam_csm_create: null out pointer");
-    *out = nullptr;
-    SLAM_REQUIRE(n_ga >= 0 && n_nga >= 0 && (n_ga == 0 || m_ga) && (n_nga == 0 || m_nga), SLAM_E_INVALID, "slam_csm_create: bad model arrays");
     slam_csm_params p;
-    slam_csm_default_params(&p);
-    if (params) p = *params;
-    SLAM_TRY(check_params(p));
-    SLAM_TRY(require_device());
+    SLAM_TRY(create_arguments(m_ga, n_ga, m_nga, n_nga, params, out, p));
     DevMem       model;
     const size_t b_ga = sizeof(double) * 2 * (size_t)n_ga, b_nga = sizeof(double) * 2 * (size_t)n_nga;
     SLAM_TRY(model.alloc(b_ga + b_nga));
@@ -800,26 +784,22 @@ int slam_csm_match_batch_dev(slam_csm_t *csm, const double *d_pts, const int32_t
     const Geom   G = csm->geom();
     const Scans  S{d_pts, d_scan_off, d_scan_nga, 0, 0, d_t0, d_cs};
     const int    nb = G.nbx * G.nby, per = G.nth * nb;
-    auto        *top = csm->keys.as<unsigned long long>(), *best = top + csm->max_scans;
-    int32_t     *count = reinterpret_cast<int32_t *>(best + csm->max_scans);
-    const size_t key_bytes = (2 * sizeof(unsigned long long) + sizeof(int32_t)) * (size_t)csm->max_scans;
-    SLAM_HIP(hipMemsetAsync(csm->keys.p, 0, key_bytes, st));
+    auto        *top = csm->top(), *best = csm->best();
+    int32_t     *count = csm->count();
+    SLAM_HIP(hipMemsetAsync(csm->keys.p, 0, slam_csm::key_bytes(csm->max_scans), st));
     if (csm->P.exhaustive) {
-        const int tiles = ((G.nx + kTileW - 1) / kTileW) * ((G.ny + kTileH - 1) / kTileH);
-        hipLaunchKernelGGL(csm_tiles_kernel, dim3(tiles, G.nth, n_scans), dim3(256), 0, st, G, S, (int32_t *)nullptr, best);
+        hipLaunchKernelGGL(csm_tiles_kernel, dim3(tile_count(G), G.nth, n_scans), dim3(256), 0, st, G, S, (int32_t *)nullptr, best);
         SLAM_HIP(hipGetLastError());
     } else {
         const int groups = (nb + 64 * kCoarsePer - 1) / (64 * kCoarsePer);
-        int       stride = 4096 / n_scans; // workgroups striding over a scan's list
-        stride = stride < 8 ? 8 : (stride > 1024 ? 1024 : stride);
         hipLaunchKernelGGL(csm_coarse_kernel, dim3(G.nth * groups, n_scans), dim3(64), 0, st, G, S, csm->U.as<int32_t>(), top);
         SLAM_HIP(hipGetLastError());
         hipLaunchKernelGGL(csm_blocks_kernel, dim3(1, n_scans), dim3(64), 0, st, G, S, top, (const int32_t *)nullptr, (const int32_t *)nullptr, best);
         SLAM_HIP(hipGetLastError());
-        hipLaunchKernelGGL(csm_select_kernel, dim3(blocks_for(per, 256), n_scans), dim3(256), 0, st, G, S, csm->U.as<int32_t>(), top, best,
-                           csm->list.as<int32_t>(), count);
+        hipLaunchKernelGGL(csm_select_kernel, dim3(blocks_for(per, 256), n_scans), dim3(256), 0, st, G, S, kKeepMatch, csm->U.as<int32_t>(), top,
+                           best, (const PostAcc *)nullptr, csm->list.as<int32_t>(), count);
         SLAM_HIP(hipGetLastError());
-        hipLaunchKernelGGL(csm_blocks_kernel, dim3(stride, n_scans), dim3(64), 0, st, G, S, top, csm->list.as<int32_t>(), count, best);
+        hipLaunchKernelGGL(csm_blocks_kernel, dim3(list_stride(n_scans), n_scans), dim3(64), 0, st, G, S, top, csm->list.as<int32_t>(), count, best);
         SLAM_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(csm_finish_kernel, dim3(n_scans), dim3(256), 0, st, G, S, best, count, csm->P.exhaustive ? per : 0, d_R0, d_R, d_t, d_result);
@@ -926,19 +906,17 @@ int slam_csm_match_post_batch_dev(slam_csm_t *csm, const double *d_pts, const in
     SLAM_TRY(slam_csm_match_batch_dev(csm, d_pts, d_scan_off, d_scan_nga, n_scans, d_R0, d_t0, d_cs, d_R, d_t, d_result, stream));
     hipStream_t   st = as_stream(stream);
     const Scans   S{d_pts, d_scan_off, d_scan_nga, 0, 0, d_t0, d_cs};
-    const PostCfg C{csm->PP.margin_per_point, csm->PP.excl_xy, csm->PP.excl_theta, csm->P.exhaustive ? 1 : 0, csm->P.theta_step};
+    const PostCfg C{csm->PP.margin_per_point, csm->PP.excl_xy, csm->PP.excl_theta, csm->P.theta_step};
     const int     per = G.nth * G.nbx * G.nby;
-    auto         *best = csm->keys.as<unsigned long long>() + csm->max_scans;
-    int32_t      *count = reinterpret_cast<int32_t *>(best + csm->max_scans);
+    auto         *best = csm->best();
+    int32_t      *count = csm->count();
     PostAcc      *acc = csm->post.as<PostAcc>();
-    int           stride = 4096 / n_scans;
-    stride = stride < 8 ? 8 : (stride > 1024 ? 1024 : stride);
     hipLaunchKernelGGL(csm_post_prepare_kernel, dim3(n_scans), dim3(256), 0, st, G, S, C, best, acc, count);
     SLAM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(csm_post_select_kernel, dim3(blocks_for(per, 256), n_scans), dim3(256), 0, st, G, S, C, csm->U.as<int32_t>(), best, acc,
-                       csm->list.as<int32_t>(), count);
+    hipLaunchKernelGGL(csm_select_kernel, dim3(blocks_for(per, 256), n_scans), dim3(256), 0, st, G, S, csm->P.exhaustive ? kKeepAll : kKeepWithin,
+                       csm->U.as<int32_t>(), csm->top(), best, acc, csm->list.as<int32_t>(), count);
     SLAM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(csm_post_accumulate_kernel, dim3(stride, n_scans), dim3(64), 0, st, G, S, C, best, csm->list.as<int32_t>(), count,
+    hipLaunchKernelGGL(csm_post_accumulate_kernel, dim3(list_stride(n_scans), n_scans), dim3(64), 0, st, G, S, C, best, csm->list.as<int32_t>(), count,
                        csm->wtab.as<uint32_t>(), acc);
     SLAM_HIP(hipGetLastError());
     hipLaunchKernelGGL(csm_post_finish_kernel, dim3(blocks_for(n_scans, 64)), dim3(64), 0, st, G, S, C, n_scans, best, acc, count, d_post);
@@ -960,8 +938,7 @@ int slam_csm_score_volume_dev(slam_csm_t *csm, const double *d_pts, int n, int n
                  "slam_csm_score_volume_dev: bad arguments (a scan has at least 5 points)");
     const Geom  G = csm->geom();
     const Scans S{d_pts, nullptr, nullptr, n, n_ga, d_t0, d_cs};
-    const int   tiles = ((G.nx + kTileW - 1) / kTileW) * ((G.ny + kTileH - 1) / kTileH);
-    hipLaunchKernelGGL(csm_tiles_kernel, dim3(tiles, G.nth, 1), dim3(256), 0, as_stream(stream), G, S, d_volume, (unsigned long long *)nullptr);
+    hipLaunchKernelGGL(csm_tiles_kernel, dim3(tile_count(G), G.nth, 1), dim3(256), 0, as_stream(stream), G, S, d_volume, (unsigned long long *)nullptr);
     SLAM_HIP(hipGetLastError());
     return SLAM_OK;
 }

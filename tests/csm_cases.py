@@ -99,6 +99,22 @@ def volume_cases():
     return out
 
 
+BLOCK_SIZES = (2, 11, 16)                          # candidates of a block per lane of 64: 4 lanes busy; 121 (two, the second
+#                                                    ragged); 256 (all four).  The default 8 gives every lane exactly one.
+BLOCK_VOLUME_CASES = ("n5_w8x8_t4", "n65_w8x8_t4", "n1081_w2x16_t0", "n65_w0x8_t4", "half_outside", "winner_in_ragged_block")
+
+
+def block_cases():
+    """(name, D, t_ga, t_nga, R0, t0, (half_x, half_y), half_theta) against box_model(), a matcher of its own per D: some of
+    volume_cases() and one winner at candidate 218 of a 16 x 16 block, (a, b) = (10, 13), which only a lane's fourth holds."""
+    cases = [c for c in volume_cases() if c[0] in BLOCK_VOLUME_CASES]
+    assert len(cases) == len(BLOCK_VOLUME_CASES)
+    ga, nga = scan_of(box_model(), 200, TRUE_POSE, 200)
+    R0, t0 = pose_Rt(TRUE_POSE[0] - 0.2, TRUE_POSE[1] - 0.5, TRUE_POSE[2])
+    cases.append(("winner_in_fourth_register", ga, nga, R0, t0, (8, 8), 0))
+    return [(c[0], D) + c[1:] for D in BLOCK_SIZES for c in cases]
+
+
 def tie_case():
     """An exact tie whose winner is NOT in the block the search evaluates first.  Five scan points on cell centres, one angle
     (R0 = identity: cos 1, sin 0 exactly), N = 17 x 17, D = 8, K = 1.  The model is the scan shifted to candidate (a, b) = (0, 1)

@@ -39,6 +39,16 @@ def test_cases_reach_the_edges():
     assert seen["nonfinite"][1].max() == 64 - 3
     vol = seen["winner_in_ragged_block"][0]
     assert np.unravel_index(int(np.argmax(vol)), vol.shape) == (0, 16, 16)
+    # other block sizes: a lane of the block kernels holds candidate r * 64 + lane of its block in register r
+    regs = {D: set() for D in K.BLOCK_SIZES}
+    for name, D, ga, nga, R0, t0, win, ht in K.block_cases():
+        om.set_window(win[0], win[1], ht, 0.01)
+        vol = om.volume(ga, nga, R0, t0)
+        k, b, a = np.unravel_index(int(np.argmax(vol)), vol.shape)
+        regs[D].add(((b % D) * D + a % D) // 64)
+        if name == "winner_in_fourth_register":
+            assert (a, b) == (10, 13) and (D != 16 or (b % D) * D + a % D == 218)
+    assert regs[2] == {0} and 1 in regs[11] and {2, 3} <= regs[16], regs
 
 
 # ------------------------------------------------------------------ tables
@@ -99,6 +109,24 @@ def test_volumes_and_answers_equal_the_restatement(box):
         assert a[0][3] == a[1][3] and a[2][3] == a[3][3], name     # the same blocks survive on both sides (a diagnostic)
         if name == "all_outside":
             assert a[0][0][:4] == (0, 0, 0, 0)
+
+
+@gpu
+def test_blocks_of_other_sizes():
+    m = K.box_model()
+    made = {}
+    for name, D, ga, nga, R0, t0, win, ht in K.block_cases():
+        if D not in made:
+            made[D] = (CO.OracleMatcher(m[0], m[1], block=D), api.CorrelativeMatcher(m[0], m[1], block=D))
+        om, cm = made[D]
+        om.set_window(win[0], win[1], ht, 0.01)
+        cm.set_window(win[0], win[1], ht, 0.01)
+        assert np.array_equal(cm.score_volume(ga, nga, R0, t0), om.volume(ga, nga, R0, t0)), (name, D)
+        a = answers(cm, om, ga, nga, R0, t0)
+        assert all(x[:3] == a[0][:3] for x in a), (name, D, [x[0] for x in a])
+        assert a[0][3] == a[1][3] and a[2][3] == a[3][3], (name, D)
+    for _, cm in made.values():
+        cm.close()
 
 
 @gpu

@@ -98,6 +98,26 @@ def test_posterior_equals_the_restatement(box, mpp):
 
 
 @gpu
+@pytest.mark.parametrize("mpp", PC.MARGINS)
+def test_posterior_at_other_block_sizes(mpp):
+    m = K.box_model()
+    made = {}
+    for name, D, ga, nga, R0, t0, win, ht in K.block_cases():
+        if D not in made:
+            made[D] = (CO.OracleMatcher(m[0], m[1], block=D), api.CorrelativeMatcher(m[0], m[1], block=D))
+            made[D][1].set_post_params(margin_per_point=mpp)
+        om, cm = made[D]
+        om.set_window(win[0], win[1], ht, 0.01)
+        cm.set_window(win[0], win[1], ht, 0.01)
+        post = held(cm, om, ga, nga, R0, t0, "%s_D%d" % (name, D))
+        assert post.valid == 1 and post.m0 >= 65536
+        if mpp == 255:
+            assert post.n_within == (2 * win[0] + 1) * (2 * win[1] + 1) * (2 * ht + 1), (name, D)
+    for _, cm in made.values():
+        cm.close()
+
+
+@gpu
 def test_other_weights_and_exclusions(box):
     _, om, cm = box
     name, ga, nga, R0, t0, win, ht = K.volume_cases()[7]          # 63 points, 17 x 17 x 9
