@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <map>
+#include <memory>
 #include <vector>
 
 #include "slam_amd/buffer.hpp"
@@ -67,13 +68,77 @@ inline void voxel_filter_host(std::vector<float> &cloud, double xy, double z)
         for (int k = 0; k < 3; ++k) cloud.push_back((float)(kv.second.s[k] / (double)kv.second.n));
 }
 
+struct GridInfo { // nav_msgs::MapMetaData, what MLS fills of it
+    double   resolution = 0;
+    uint32_t width = 0, height = 0;
+    double   origin_x = 0, origin_y = 0;
+};
+
 struct OccupancyGrid { // the fields of nav_msgs::OccupancyGrid that MLS fills
-    struct {
-        double   resolution = 0;
-        uint32_t width = 0, height = 0;
-        double   origin_x = 0, origin_y = 0;
-    } info;
+    GridInfo            info;
     std::vector<int8_t> data;
+};
+
+// The costmap of a drivability plane (slam_gdist_*, docs/GRID_DIST.md; the reference has none): per cell, data[x + width*y], the
+// squared distance in cells to the nearest obstacle cell (SLAM_GDIST_FAR beyond max_cells) and the inflated cost byte
+// (costmap_2d's scale: 254 lethal, 253 inscribed, 255 unknown, 0 free).
+struct Costmap {
+    GridInfo              info;
+    std::vector<uint8_t>  cost;
+    std::vector<uint16_t> dist2;
+};
+
+// RAII over slam_gdist_t.  A failed construction logs and leaves an unusable object (ok() == false), as the other adapters do.
+class DistanceField {
+public:
+    DistanceField(int size_x, int size_y, const slam_gdist_params *params = nullptr)
+    {
+        if (slam_gdist_create(size_x, size_y, params, &h_) != SLAM_OK) {
+            std::fprintf(stderr, "%s\n", slam_last_error());
+            h_ = nullptr;
+            return;
+        }
+        slam_gdist_default_params(&prm_);
+        if (params) prm_ = *params;
+        cells_ = (size_t)size_x * size_y;
+    }
+    ~DistanceField() { slam_gdist_destroy(h_); }
+    DistanceField(const DistanceField &) = delete;
+    DistanceField &operator=(const DistanceField &) = delete;
+
+    bool ok() const { return h_ != nullptr; }
+    bool setTable(const std::vector<uint8_t> &table) { return h_ && good(slam_gdist_set_table(h_, table.data(), (int)table.size())); }
+    // costmap_2d's inflation curve for this handle's max_cells (slam_grid_inflation_table)
+    bool setInflation(double resolution, double inscribed_radius, double inflation_radius, double cost_scaling)
+    {
+        if (!h_) return false;
+        std::vector<uint8_t> t((size_t)prm_.max_cells * prm_.max_cells + 2);
+        return good(slam_grid_inflation_table(resolution, inscribed_radius, inflation_radius, cost_scaling, prm_.max_cells, t.data(), (int)t.size())) &&
+               setTable(t);
+    }
+    bool compute(const int8_t *occ) { return h_ && good(slam_gdist_compute(h_, occ)); }
+    bool computeDev(const int8_t *d_occ, slam_stream_t stream) { return h_ && good(slam_gdist_compute_dev(h_, d_occ, stream)); }
+    bool computeFromGrid(slam_grid_t *grid, slam_stream_t stream = nullptr) { return h_ && grid && good(slam_grid_distance_field(grid, h_, stream)); }
+    // either vector may be null; they are sized here
+    bool read(std::vector<uint16_t> *dist2, std::vector<uint8_t> *cost)
+    {
+        if (!h_) return false;
+        if (dist2) dist2->resize(cells_);
+        if (cost) cost->resize(cells_);
+        return good(slam_gdist_read(h_, dist2 ? dist2->data() : nullptr, cost ? cost->data() : nullptr));
+    }
+    const slam_gdist_params &params() const { return prm_; }
+    slam_gdist_t            *handle() { return h_; }
+
+private:
+    static bool good(int rc)
+    {
+        if (rc != SLAM_OK) std::fprintf(stderr, "%s\n", slam_last_error());
+        return rc == SLAM_OK;
+    }
+    slam_gdist_t     *h_ = nullptr;
+    slam_gdist_params prm_ = {};
+    size_t            cells_ = 0;
 };
 
 class MLS {
@@ -285,6 +350,30 @@ public:
         if (h_) slam_grid_read_occupancy(h_, grid_.data.data());
         return grid_;
     }
+    // Opt-in costmap (not in the reference, where robot_size only sets a height): from here on getCostmap() inflates the
+    // drivability plane by costmap_2d's curve, radii in metres, distances capped at max_cells cells.  Nothing is allocated and
+    // nothing changes without this call; false (logged) when the arguments or the device refuse.
+    bool enableCostmap(double inscribed_radius, double inflation_radius, double cost_scaling, int max_cells = 32)
+    {
+        if (!h_) return false;
+        slam_gdist_params p;
+        slam_gdist_default_params(&p);
+        p.max_cells = max_cells;
+        std::unique_ptr<DistanceField> df(new DistanceField((int)grid_.info.width, (int)grid_.info.height, &p));
+        if (!df->ok() || !df->setInflation(grid_.info.resolution, inscribed_radius, inflation_radius, cost_scaling)) return false;
+        df_ = std::move(df);
+        costmap_.info = grid_.info;
+        return true;
+    }
+    // getDrivability()'s state -> slam_grid_distance_field -> slam_gdist_read; empty planes before enableCostmap
+    const Costmap &getCostmap()
+    {
+        if (!(h_ && df_ && df_->computeFromGrid(h_) && df_->read(&costmap_.dist2, &costmap_.cost))) {
+            costmap_.dist2.clear();
+            costmap_.cost.clear();
+        }
+        return costmap_;
+    }
     void setMinClusterPoints(double v) { if (h_) slam_grid_set_min_cluster_points(h_, (int)v); } // mls.h:235
     void setMaxRange(double v) { if (h_) slam_grid_set_max_range(h_, v); }                     // mls.h:237
     slam_grid_t *handle() { return h_; }
@@ -294,6 +383,8 @@ private:
     slam_grid_t  *h_ = nullptr;
     slam_gseg_t  *gseg_ = nullptr;
     OccupancyGrid grid_;
+    std::unique_ptr<DistanceField> df_; // enableCostmap
+    Costmap       costmap_;
     bool          rolling_ = false, disable_pointcloud_ = false;
     detail::DeviceBuffer d_cloud_, d_labels_, d_gnd_, d_obs_, d_counts_; // the first four hold cap_ points each
     int                  cap_ = 0, last_counts_[2] = {0, 0};

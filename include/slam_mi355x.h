@@ -392,6 +392,55 @@ int slam_grid_dirty_rows_dev(slam_grid_t *g, int32_t **d_range);
 int slam_grid_enable_accumulator(slam_grid_t *g);
 int slam_grid_fold(slam_grid_t *g, int row_lo, int row_hi, slam_stream_t stream);
 
+/* ------------------------------------------------ grid distance field and costmap
+ * What every consumer of the occupancy plane computes next (docs/GRID_DIST.md): the exact squared distance, in cells, from
+ * every cell to the nearest obstacle cell, capped at R = max_cells, and the costmap that inflates obstacles by the robot's
+ * footprint.  Not in the reference (MLS's robot_size only sets a height): a north-star extension like the raycast, defined by
+ * the project's own brute-force restatement (tests/grid_dist_cases.py) and equal to it bit for bit.
+ *
+ * Planes are in WINDOW coordinates, data[x + size_x*y], as slam_grid_read_occupancy returns them.  Obstacles are the cells
+ * with occ == 100, and those with occ == -1 when unknown_is_obstacle is set; cells outside the window are never obstacles
+ * and distance does not wrap across its edges.
+ *   dist2 (uint16)  min over obstacles of (x-x')^2 + (y-y')^2 where that is <= R*R, SLAM_GDIST_FAR otherwise (and when there
+ *                   is no obstacle at all)
+ *   cost  (uint8)   only with a table T of exactly R*R + 2 bytes: T[min(dist2, R*R + 1)] -- the last entry answers FAR; a
+ *                   cell with occ == -1 (unknown_is_obstacle == 0) keeps that byte if it is >= unknown_keep_from and
+ *                   becomes unknown_cost otherwise. */
+typedef struct slam_gdist slam_gdist_t;
+#define SLAM_GDIST_FAR 0xFFFFu
+typedef struct {
+    int max_cells;            /* R, 1..254; default 32 (a starting value, not tuned) */
+    int unknown_is_obstacle;  /* default 0 */
+    int unknown_cost;         /* 0..255, default 255 (costmap_2d NO_INFORMATION) */
+    int unknown_keep_from;    /* 0..255, default 253 (costmap_2d INSCRIBED_INFLATED_OBSTACLE) */
+} slam_gdist_params;
+void slam_gdist_default_params(slam_gdist_params *p);
+/* The inflation table of ROS costmap_2d's inflation layer, on the host (no device is touched): table[0] = 254; for
+ * k = 1 .. R*R with d = sqrt(k) * resolution: 253 where d <= inscribed_radius, 0 where d > inflation_radius, else
+ * (uint8_t)(252 * exp(-cost_scaling * (d - inscribed_radius))); table[R*R + 1] = 0.  SLAM_E_INVALID: n != R*R + 2, a
+ * non-finite or negative argument, resolution == 0, inscribed_radius > inflation_radius, or inflation_radius >
+ * max_cells * resolution (the distance cap would cut the inflation short). */
+int  slam_grid_inflation_table(double resolution, double inscribed_radius, double inflation_radius,
+                               double cost_scaling, int max_cells, uint8_t *table, int n);
+/* outputs, scratch and the table's room are allocated here; nothing is allocated later */
+int  slam_gdist_create(int size_x, int size_y, const slam_gdist_params *p, slam_gdist_t **out);
+void slam_gdist_destroy(slam_gdist_t *h);
+/* n == R*R + 2 bytes of any table (the inflation table above, a likelihood-field table for a matcher ...); NULL, 0 removes
+ * it.  Synchronous.  The cost plane belongs to the table it was computed with: compute again before reading it. */
+int  slam_gdist_set_table(slam_gdist_t *h, const uint8_t *table, int n);
+/* d_occ: a device plane of size_x*size_y bytes, borrowed until the stream reaches this point.  Only enqueues kernels on
+ * `stream`: no host wait, no allocation -- it can stand behind slam_grid_finalize on the grid's stream. */
+int  slam_gdist_compute_dev(slam_gdist_t *h, const int8_t *d_occ, slam_stream_t stream);
+int  slam_gdist_compute(slam_gdist_t *h, const int8_t *occ);               /* host plane; synchronous */
+/* host planes of size_x*size_y elements; either may be NULL; waits for the device.  cost without a table, or with a table
+ * set after the last compute: SLAM_E_INVALID */
+int  slam_gdist_read(slam_gdist_t *h, uint16_t *dist2, uint8_t *cost);
+int  slam_gdist_planes_dev(slam_gdist_t *h, uint16_t **d_dist2, uint8_t **d_cost); /* *d_cost = NULL without a table */
+/* slam_gdist_compute_dev over the grid's own occupancy: exactly the plane slam_grid_read_occupancy would return at this
+ * point of the stream (after the in-order mode, that mode's state; otherwise what the last finalize left -- this call does
+ * not finalize).  Grid and handle must have the same size. */
+int  slam_grid_distance_field(slam_grid_t *g, slam_gdist_t *h, slam_stream_t stream);
+
 /* ------------------------------------------------------------ height-cluster map
  * Stands for class MLS in its non-rolling, height-cluster mode (mls.h:154-237, mls.cpp:18-53, 152-402, 481-556):
  * graph_slam's global map (graph_slam.cpp:71).  Every cell holds up to `capacity` z clusters (mean x, y, z, cov_zz,

@@ -48,6 +48,12 @@ class GridParams(C.Structure):
                 ("raycast_wg_per_cu", C.c_int), ("raycast_max_workgroups", C.c_int)]
 
 
+class GdistParams(C.Structure):
+    _fields_ = [("max_cells", C.c_int), ("unknown_is_obstacle", C.c_int), ("unknown_cost", C.c_int), ("unknown_keep_from", C.c_int)]
+
+
+GDIST_FAR = 0xFFFF
+
 class MapperParams(C.Structure):
     _fields_ = [("grid_size_x", C.c_int), ("grid_size_y", C.c_int), ("resolution", C.c_double), ("grid", GridParams),
                 ("icp", IcpParams), ("indist", C.c_double), ("max_scans", C.c_int), ("max_points", C.c_int),
@@ -266,6 +272,8 @@ EXPORTS = [
     "slam_grid_read_occupancy", "slam_grid_read_num_pts", "slam_grid_total_updates",
     "slam_grid_info", "slam_grid_window_cell", "slam_grid_counts_dev", "slam_grid_mark_rows", "slam_grid_raycast_stats", "slam_grid_dirty_rows", "slam_grid_dirty_rows_dev",
     "slam_grid_enable_accumulator", "slam_grid_fold",
+    "slam_gdist_default_params", "slam_grid_inflation_table", "slam_gdist_create", "slam_gdist_destroy", "slam_gdist_set_table",
+    "slam_gdist_compute_dev", "slam_gdist_compute", "slam_gdist_read", "slam_gdist_planes_dev", "slam_grid_distance_field",
     "slam_gseg_default_params", "slam_gseg_create", "slam_gseg_destroy", "slam_gseg_reserve",
     "slam_gseg_segment", "slam_gseg_segment_dev", "slam_gseg_split_dev", "slam_gseg_read_model",
     "slam_gseg_classify_ga_dev", "slam_gseg_classify_ga_counted_dev", "slam_gseg_classify_ga_extent_dev",
@@ -430,6 +438,18 @@ def lib():
     L.slam_grid_dirty_rows_dev.argtypes = [_vp, C.POINTER(_vp)]
     L.slam_grid_enable_accumulator.argtypes = [_vp]
     L.slam_grid_fold.argtypes = [_vp, C.c_int, C.c_int, _vp]
+    L.slam_gdist_default_params.restype = None
+    L.slam_gdist_default_params.argtypes = [C.POINTER(GdistParams)]
+    L.slam_grid_inflation_table.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _vp, C.c_int]
+    L.slam_gdist_create.argtypes = [C.c_int, C.c_int, C.POINTER(GdistParams), C.POINTER(_vp)]
+    L.slam_gdist_destroy.restype = None
+    L.slam_gdist_destroy.argtypes = [_vp]
+    L.slam_gdist_set_table.argtypes = [_vp, _vp, C.c_int]
+    L.slam_gdist_compute_dev.argtypes = [_vp, _vp, _vp]
+    L.slam_gdist_compute.argtypes = [_vp, _vp]
+    L.slam_gdist_read.argtypes = [_vp, _vp, _vp]
+    L.slam_gdist_planes_dev.argtypes = [_vp, C.POINTER(_vp), C.POINTER(_vp)]
+    L.slam_grid_distance_field.argtypes = [_vp, _vp, _vp]
     L.slam_gseg_default_params.restype = None
     L.slam_gseg_default_params.argtypes = [C.POINTER(GsegParams)]
     L.slam_gseg_create.argtypes = [C.POINTER(GsegParams), C.POINTER(_vp)]
@@ -1729,9 +1749,90 @@ class Grid:
         check(lib().slam_grid_counts_dev(self.h, C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    def distance_field(self, df, stream=None):
+        """df (a DistanceField of this grid's size) computed over the plane read_occupancy() returns; enqueues on `stream`"""
+        check(lib().slam_grid_distance_field(self.h, df.h, _sp(stream)))
+
     def close(self):
         if getattr(self, "h", None):
             lib().slam_grid_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gdist_default_params(**kw):
+    p = GdistParams()
+    lib().slam_gdist_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def inflation_table(resolution, inscribed_radius, inflation_radius, cost_scaling, max_cells):
+    """costmap_2d's inflation curve as the byte table a DistanceField looks its costs up in: np.uint8[max_cells**2 + 2],
+    indexed by the squared distance in cells (slam_grid_inflation_table; host only)"""
+    n = max(int(max_cells), 0) ** 2 + 2
+    t = np.zeros(n, dtype=np.uint8)
+    check(lib().slam_grid_inflation_table(float(resolution), float(inscribed_radius), float(inflation_radius), float(cost_scaling),
+                                          int(max_cells), _ptr(t), n))
+    return t
+
+
+class DistanceField:
+    """Exact squared distance to the nearest obstacle cell of an occupancy plane, capped at max_cells, and the costmap read
+    off it through a byte table (slam_gdist_*, docs/GRID_DIST.md).  Planes are window order, data[x + size_x * y]."""
+
+    def __init__(self, size_x, size_y, params=None, **kw):
+        self.size_x, self.size_y = int(size_x), int(size_y)
+        self.params = params or gdist_default_params(**kw)
+        self.cells = self.size_x * self.size_y
+        self.has_table = False
+        h = _vp()
+        check(lib().slam_gdist_create(self.size_x, self.size_y, C.byref(self.params), C.byref(h)))
+        self.h = h.value
+
+    def set_table(self, table, n=None):
+        """np.uint8[max_cells**2 + 2] (n: its length, if given), or None (and 0) to remove the table (no cost plane)"""
+        if table is None:
+            check(lib().slam_gdist_set_table(self.h, None, int(n or 0)))
+            self.has_table = False
+            return
+        t = np.ascontiguousarray(table, dtype=np.uint8).ravel()
+        assert n is None or int(n) == len(t)
+        check(lib().slam_gdist_set_table(self.h, t.ctypes.data_as(_vp), len(t)))
+        self.has_table = True
+
+    def set_inflation(self, resolution, inscribed_radius, inflation_radius, cost_scaling):
+        self.set_table(inflation_table(resolution, inscribed_radius, inflation_radius, cost_scaling, self.params.max_cells))
+
+    def compute(self, occ):
+        occ = np.ascontiguousarray(occ, dtype=np.int8).ravel()
+        assert occ.size == self.cells
+        check(lib().slam_gdist_compute(self.h, _ptr(occ)))
+
+    def compute_dev(self, d_occ, stream=None):
+        check(lib().slam_gdist_compute_dev(self.h, getattr(d_occ, "ptr", d_occ), _sp(stream)))
+
+    def read(self, cost=None):
+        """(dist2 np.uint16[cells], cost np.uint8[cells] or None without a table); cost=True asks for the cost plane regardless"""
+        d = np.empty(self.cells, dtype=np.uint16)
+        c = np.empty(self.cells, dtype=np.uint8) if (self.has_table if cost is None else cost) else None
+        check(lib().slam_gdist_read(self.h, _ptr(d), _ptr(c) if c is not None else None))
+        return d, c
+
+    def planes_dev(self):
+        d, c = _vp(), _vp()
+        check(lib().slam_gdist_planes_dev(self.h, C.byref(d), C.byref(c)))
+        return d.value, c.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().slam_gdist_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -32,6 +32,7 @@
 
 #include "device_mem.hpp"
 #include "grid_cell.hpp"
+#include "grid_dist.hpp"
 
 using namespace slam;
 
@@ -1681,10 +1682,10 @@ int slam_grid_read_counts(slam_grid_t *g, int32_t *hits, int32_t *misses)
     return SLAM_OK;
 }
 
-static int sync_window_state(slam_grid *g)
+static int sync_window_state(slam_grid *g, hipStream_t st = nullptr)
 {
     if (g->state_from_inorder) {
-        hipLaunchKernelGGL(window_from_storage_kernel, grid2d(g), dim3(256), 0, nullptr, g->gv, g->d_num_s,
+        hipLaunchKernelGGL(window_from_storage_kernel, grid2d(g), dim3(256), 0, st, g->gv, g->d_num_s,
                            g->d_occ_s, g->d_num_w, g->d_occ_w);
         SLAM_HIP(hipGetLastError());
     }
@@ -1698,6 +1699,19 @@ int slam_grid_read_occupancy(slam_grid_t *g, int8_t *occ)
     SLAM_TRY(sync_window_state(g));
     SLAM_HIP(hipMemcpy(occ, g->d_occ_w, g->cells, hipMemcpyDeviceToHost));
     return SLAM_OK;
+}
+
+// The distance field (grid_dist.hip) of the plane slam_grid_read_occupancy returns: after the in-order mode that mode's state,
+// brought into window order on `stream` first, otherwise what the last finalize left.
+int slam_grid_distance_field(slam_grid_t *g, slam_gdist_t *h, slam_stream_t stream)
+{
+    SLAM_REQUIRE(g && h, SLAM_E_INVALID, "slam_grid_distance_field: null handle");
+    int sx = 0, sy = 0;
+    gdist_size(h, &sx, &sy);
+    SLAM_REQUIRE(sx == g->gv.sx && sy == g->gv.sy, SLAM_E_INVALID, "slam_grid_distance_field: the grid is %d x %d cells, the distance field %d x %d",
+                 g->gv.sx, g->gv.sy, sx, sy);
+    SLAM_TRY(sync_window_state(g, as_stream(stream)));
+    return gdist_compute_on(h, g->d_occ_w, as_stream(stream));
 }
 
 int slam_grid_read_num_pts(slam_grid_t *g, double *num_pts)
