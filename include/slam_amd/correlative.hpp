@@ -9,12 +9,18 @@
 //
 // Conventions of icp.hpp: a failed construction logs and leaves an unusable object; match() is synchronous and leaves R, t
 // alone where it cannot answer (fewer than 5 scene points).
+//
+// fromPlane / fromPlaneDev make a matcher whose table is a byte plane (docs/GRID_MATCH.md): a likelihood field computed from an
+// occupancy grid, a saved map.  slam_amd::GridMatcher (below) puts grid, field and such a matcher together.
 #pragma once
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <memory>
+#include <vector>
 
 #include "slam_amd/icp.hpp"
+#include "slam_amd/mls.hpp"
 #include "slam_mi355x.h"
 
 namespace slam_amd {
@@ -71,6 +77,24 @@ public:
             h_ = nullptr;
         }
     }
+    // slam_csm_create_from_plane[_dev]: the table is the w x h byte plane itself, element (0, 0) at lattice cell (origin_x, origin_y)
+    static CorrelativeMatcher fromPlane(const uint8_t *plane, int w, int h, int origin_x, int origin_y, const slam_csm_params *params = nullptr)
+    {
+        return CorrelativeMatcher(plane, w, h, origin_x, origin_y, false, params);
+    }
+    static CorrelativeMatcher fromPlaneDev(const uint8_t *d_plane, int w, int h, int origin_x, int origin_y, const slam_csm_params *params = nullptr)
+    {
+        return CorrelativeMatcher(d_plane, w, h, origin_x, origin_y, true, params);
+    }
+    CorrelativeMatcher(const uint8_t *plane, int w, int h, int origin_x, int origin_y, bool on_device, const slam_csm_params *params = nullptr)
+    {
+        const int rc = on_device ? slam_csm_create_from_plane_dev(plane, w, h, origin_x, origin_y, params, &h_)
+                                 : slam_csm_create_from_plane(plane, w, h, origin_x, origin_y, params, &h_);
+        if (rc != SLAM_OK) {
+            std::fprintf(stderr, "%s\n", slam_last_error());
+            h_ = nullptr;
+        }
+    }
     ~CorrelativeMatcher() { slam_csm_destroy(h_); }
     CorrelativeMatcher(const CorrelativeMatcher &) = delete;
     CorrelativeMatcher &operator=(const CorrelativeMatcher &) = delete;
@@ -88,6 +112,34 @@ public:
         return setWindow((int32_t)(x / p.resolution + 0.5), (int32_t)(y / p.resolution + 0.5), (int32_t)(theta / p.theta_step + 0.5), p.theta_step);
     }
     void setExhaustive(bool on) { if (h_) slam_csm_set_exhaustive(h_, on ? 1 : 0); }
+    // slam_csm_set_plane_dev: another device plane of the same size at any origin, a copy and the slide enqueued on `stream`;
+    // false (logged) on a matcher made from a model
+    bool setPlane(const uint8_t *d_plane, int origin_x, int origin_y, slam_stream_t stream = nullptr)
+    {
+        if (!h_) return false;
+        if (slam_csm_set_plane_dev(h_, d_plane, origin_x, origin_y, stream) != SLAM_OK) {
+            std::fprintf(stderr, "%s\n", slam_last_error());
+            return false;
+        }
+        return true;
+    }
+    // slam_csm_score_poses: poses = n_poses x (cos, sin, tx, ty); score and counted are sized here.  false (logged): refused
+    bool scorePoses(const double *T_GA, const double *T_NGA, const int32_t T_GA_num, const int32_t T_NGA_num, const double *poses, int32_t n_poses,
+                    std::vector<int32_t> &score, std::vector<int32_t> &counted)
+    {
+        if (!h_ || T_GA_num < 0 || T_NGA_num < 0 || n_poses < 0) return false;
+        std::vector<double> pts;
+        pts.reserve(2 * ((size_t)T_GA_num + T_NGA_num));
+        pts.insert(pts.end(), T_GA, T_GA + 2 * (size_t)T_GA_num);
+        pts.insert(pts.end(), T_NGA, T_NGA + 2 * (size_t)T_NGA_num);
+        score.assign((size_t)n_poses, 0);
+        counted.assign((size_t)n_poses, 0);
+        if (slam_csm_score_poses(h_, pts.data(), T_GA_num + T_NGA_num, T_GA_num, poses, n_poses, score.data(), counted.data()) != SLAM_OK) {
+            std::fprintf(stderr, "%s\n", slam_last_error());
+            return false;
+        }
+        return true;
+    }
 
     // R (2 x 2) and t (2 x 1) in/out; returns the score's share of the most the scan could score, or -1 (R, t untouched)
     double match(double *T_GA, double *T_NGA, const int32_t T_GA_num, const int32_t T_NGA_num, Matrix &R, Matrix &t)
@@ -144,5 +196,135 @@ private:
     slam_csm_t     *h_ = nullptr;
     slam_csm_result last_ = {0, 0, 0, -1, 0, 0, 0};
 };
+
+// GridMatcher localises a scan in an occupancy grid itself (docs/GRID_MATCH.md): the twin of slam_amd.api.GridMatcher over
+// slam_amd::MLS (mls.hpp), slam_amd::DistanceField and a plane-built CorrelativeMatcher.
+//
+//     slam_amd::MLS         mls(500, 500, 0.1, true);            // ... the mapper fills it
+//     slam_amd::GridMatcher gm(mls, 0.2);                        // sigma 0.2 m; R = ceil(3 sigma / res - 1e-9) cells
+//     gm.update();                                               // grid -> likelihood field -> the matcher's table; waits for nothing
+//     gm.match(T_GA, T_NGA, tGA, tNGA, R, t);                    // the best pose of the window around (R, t), map frame
+//     gm.relocalize(T_GA, T_NGA, tGA, tNGA, 0.05, R, t);         // no prior: the whole grid, all angles
+//
+// The field is created with slam_grid_likelihood_table and unknown_keep_from = 0, so that unknown cells keep their likelihood
+// byte; the matcher is created at the grid's resolution and its plane element (0, 0) is lattice cell (-size_x / 2, -size_y / 2),
+// the grid's own cell_coord.  The window's frame is centred on the grid's pose when the grid rolls (slam_grid_get_pose) and on
+// (0, 0) when it does not: the adapter subtracts that centre from a start translation and adds it to the answer, one double
+// operation each; the C-ABI underneath stays in the window's frame.  The matcher keeps its cell rule (floor, double), the grid's
+// is (int) truncation on float points: inside the window they agree.  A failure logs and leaves ok() == false.
+class GridMatcher {
+public:
+    // params: the matcher's (window, block; resolution is the grid's, sigma and kernel_cells are the field's business)
+    GridMatcher(MLS &grid, double sigma, int max_cells = 0, const slam_csm_params *params = nullptr) : grid_(grid)
+    {
+        double res = 0.0;
+        if (!grid.handle() || slam_grid_info(grid.handle(), &sx_, &sy_, &res, nullptr, nullptr) != SLAM_OK) {
+            std::fprintf(stderr, "GridMatcher: the grid is not usable\n");
+            return;
+        }
+        const double cells = std::ceil(3.0 * sigma / res - 1e-9);
+        const int    R = max_cells > 0 ? max_cells : (cells >= 1.0 && cells <= 254.0 ? (int)cells : 0);
+        std::vector<uint8_t> table(R > 0 ? (size_t)R * R + 2 : 1);
+        if (slam_grid_likelihood_table(res, sigma, R, table.data(), (int)table.size()) != SLAM_OK) {
+            std::fprintf(stderr, "%s\n", slam_last_error());
+            return;
+        }
+        slam_gdist_params gp;
+        slam_gdist_default_params(&gp);
+        gp.max_cells = R, gp.unknown_keep_from = 0;
+        std::unique_ptr<DistanceField> field(new DistanceField(sx_, sy_, &gp));
+        // a plane to make the matcher from: the empty grid's; update() brings the grid's own
+        const std::vector<int8_t> empty((size_t)sx_ * sy_, (int8_t)0);
+        uint8_t                  *d_cost = nullptr;
+        if (!field->ok() || !field->setTable(table) || !field->compute(empty.data()) ||
+            slam_gdist_planes_dev(field->handle(), nullptr, &d_cost) != SLAM_OK || !d_cost)
+            return;
+        slam_csm_params p;
+        slam_csm_default_params(&p);
+        if (params) p = *params;
+        p.resolution = res;
+        std::unique_ptr<CorrelativeMatcher> matcher(new CorrelativeMatcher(d_cost, sx_, sy_, -(sx_ / 2), -(sy_ / 2), true, &p));
+        if (!matcher->valid()) return;
+        field_ = std::move(field), matcher_ = std::move(matcher);
+        max_cells_ = R, d_cost_ = d_cost;
+        readCentre();
+    }
+    GridMatcher(const GridMatcher &) = delete;
+    GridMatcher &operator=(const GridMatcher &) = delete;
+
+    bool ok() const { return matcher_ && field_; }
+    int  maxCells() const { return max_cells_; }
+    // slam_grid_distance_field, then slam_csm_set_plane_dev, on `stream`; waits for nothing
+    bool update(slam_stream_t stream = nullptr)
+    {
+        if (!ok()) return false;
+        if (!field_->computeFromGrid(grid_.handle(), stream) || !matcher_->setPlane(d_cost_, -(sx_ / 2), -(sy_ / 2), stream)) return false;
+        readCentre();
+        return true;
+    }
+    // CorrelativeMatcher::match with R, t in the map frame
+    double match(double *T_GA, double *T_NGA, const int32_t T_GA_num, const int32_t T_NGA_num, Matrix &R, Matrix &t)
+    {
+        if (!ok()) return -1.0;
+        Matrix       tw = toWindow(t);
+        const double share = matcher_->match(T_GA, T_NGA, T_GA_num, T_NGA_num, R, tw);
+        if (share >= 0.0) toMap(tw, t);
+        return share;
+    }
+    bool   setPosterior(const slam_csm_post_params *params = nullptr) { return ok() && matcher_->setPosterior(params); }
+    double matchPosterior(double *T_GA, double *T_NGA, const int32_t T_GA_num, const int32_t T_NGA_num, Matrix &R, Matrix &t, Posterior &post)
+    {
+        if (!ok()) return -1.0;
+        Matrix       tw = toWindow(t);
+        const double share = matcher_->matchPosterior(T_GA, T_NGA, T_GA_num, T_NGA_num, R, tw, post);
+        if (share >= 0.0) toMap(tw, t);
+        return share;
+    }
+    // poses = n_poses x (cos, sin, tx, ty) in the map frame
+    bool scorePoses(const double *T_GA, const double *T_NGA, const int32_t T_GA_num, const int32_t T_NGA_num, const double *poses, int32_t n_poses,
+                    std::vector<int32_t> &score, std::vector<int32_t> &counted)
+    {
+        if (!ok() || n_poses < 0) return false;
+        std::vector<double> w(poses, poses + 4 * (size_t)n_poses);
+        for (int32_t i = 0; i < n_poses; ++i) w[4 * (size_t)i + 2] = w[4 * (size_t)i + 2] - cx_, w[4 * (size_t)i + 3] = w[4 * (size_t)i + 3] - cy_;
+        return matcher_->scorePoses(T_GA, T_NGA, T_GA_num, T_NGA_num, w.data(), n_poses, score, counted);
+    }
+    // No prior: the window covers the whole grid and all angles and starts from the window's centre; R, t are outputs
+    double relocalize(double *T_GA, double *T_NGA, const int32_t T_GA_num, const int32_t T_NGA_num, double theta_step, Matrix &R, Matrix &t)
+    {
+        if (!ok() || !matcher_->setWindow(sx_ / 2, sy_ / 2, (int32_t)std::ceil(M_PI / theta_step), theta_step)) return -1.0;
+        Matrix R0 = Matrix::eye(2), t0(2, 1);
+        t0.val[0][0] = cx_, t0.val[1][0] = cy_;
+        const double share = match(T_GA, T_NGA, T_GA_num, T_NGA_num, R0, t0);
+        if (share >= 0.0) R = R0, t = t0;
+        return share;
+    }
+    const slam_csm_result &result() const { return matcher_->result(); }
+    CorrelativeMatcher    &matcher() { return *matcher_; }
+    DistanceField         &field() { return *field_; }
+    void                   centre(double &x, double &y) const { x = cx_, y = cy_; }
+
+private:
+    void readCentre()
+    {
+        cx_ = cy_ = 0.0;
+        if (grid_.rolling()) slam_grid_get_pose(grid_.handle(), &cx_, &cy_);
+    }
+    Matrix toWindow(const Matrix &t) const
+    {
+        Matrix w(2, 1);
+        w.val[0][0] = t.val[0][0] - cx_, w.val[1][0] = t.val[1][0] - cy_;
+        return w;
+    }
+    void toMap(const Matrix &w, Matrix &t) const { t.val[0][0] = w.val[0][0] + cx_, t.val[1][0] = w.val[1][0] + cy_; }
+
+    MLS                                &grid_;
+    std::unique_ptr<DistanceField>      field_;
+    std::unique_ptr<CorrelativeMatcher> matcher_;
+    uint8_t                            *d_cost_ = nullptr;
+    int                                 sx_ = 0, sy_ = 0, max_cells_ = 0;
+    double                              cx_ = 0.0, cy_ = 0.0;
+};
+
 
 } // namespace slam_amd

@@ -377,6 +377,7 @@ public:
     void setMinClusterPoints(double v) { if (h_) slam_grid_set_min_cluster_points(h_, (int)v); } // mls.h:235
     void setMaxRange(double v) { if (h_) slam_grid_set_max_range(h_, v); }                     // mls.h:237
     slam_grid_t *handle() { return h_; }
+    bool         rolling() const { return rolling_; }
 
 private:
     static void warn() { detail::warn("MLS"); }

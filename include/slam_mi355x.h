@@ -422,6 +422,11 @@ void slam_gdist_default_params(slam_gdist_params *p);
  * max_cells * resolution (the distance cap would cut the inflation short). */
 int  slam_grid_inflation_table(double resolution, double inscribed_radius, double inflation_radius,
                                double cost_scaling, int max_cells, uint8_t *table, int n);
+/* The likelihood-field table of a grid matcher (docs/GRID_MATCH.md), on the host: table[k] = (uint8_t)rint(255 *
+ * exp(-(k * resolution^2) / (2 * sigma^2))) for k = 0 .. R*R -- the expression of the correlative matcher's stamp, so entry
+ * i*i + j*j is stamp entry (i, j) -- and table[R*R + 1] = 0.  SLAM_E_INVALID: n != R*R + 2, a non-finite or non-positive
+ * resolution or sigma (or one whose square is 0 or infinite in a double), max_cells outside 1 .. 254. */
+int  slam_grid_likelihood_table(double resolution, double sigma, int max_cells, uint8_t *table, int n);
 /* outputs, scratch and the table's room are allocated here; nothing is allocated later */
 int  slam_gdist_create(int size_x, int size_y, const slam_gdist_params *p, slam_gdist_t **out);
 void slam_gdist_destroy(slam_gdist_t *h);
@@ -943,6 +948,35 @@ int  slam_csm_score_volume_dev(slam_csm_t *csm, const double *d_pts, int n, int 
 int  slam_csm_read_table(slam_csm_t *csm, int cls, int level, int *origin_x, int *origin_y, int *w, int *h, uint8_t *buf, size_t cap);
 /* the parameters in force (kernel_cells resolved), N_theta N_x N_y and blocks per axis in dims[5], bytes of tables and scratch */
 int  slam_csm_info(slam_csm_t *csm, slam_csm_params *params, int dims[5], size_t *table_bytes, size_t *scratch_bytes, int *max_scans);
+
+/* A matcher whose table IS a byte plane (docs/GRID_MATCH.md): the cost plane a distance field computed with a likelihood table
+ * (slam_grid_likelihood_table, slam_gdist_set_table), a saved map, any u8 image.  One table, read by both classes:
+ * T[u, v] = plane[(u - origin_x) + w (v - origin_y)] inside the window and 0 outside; (origin_x, origin_y) is the lattice
+ * cell of plane element (0, 0).  W is the same D x D slide.  sigma and kernel_cells are ignored (slam_csm_info reports 0:
+ * the plane carries the kernel), the GA / NGA split of a scan makes no difference, and every search, posterior and volume
+ * call runs as on a model-built handle.  The plane is copied; both wait for the tables.  SLAM_E_INVALID before the device is
+ * touched: w or h < 1, (w + D)(h + D) beyond 2^28 bytes, a cell of T or W beyond +-2^30. */
+int  slam_csm_create_from_plane(const uint8_t *plane, int w, int h, int origin_x, int origin_y, const slam_csm_params *params,
+                                slam_csm_t **out);
+int  slam_csm_create_from_plane_dev(const uint8_t *d_plane, int w, int h, int origin_x, int origin_y, const slam_csm_params *params,
+                                    slam_csm_t **out);
+/* Another plane of the SAME w x h (the call cannot see its size) at any origin: one copy and the slide, enqueued on `stream`.
+ * Allocates nothing and waits for nothing, so it can stand behind slam_grid_distance_field on the grid's stream; a graph may
+ * capture it (the origin is then the captured one, like every argument).  The origin takes effect for the calls made after
+ * this one.  One call at a time per handle.  SLAM_E_INVALID on a handle made from a model. */
+int  slam_csm_set_plane_dev(slam_csm_t *csm, const uint8_t *d_plane, int origin_x, int origin_y, slam_stream_t stream);
+/* Scores of arbitrary poses (particles, hypotheses from elsewhere), on either kind of handle.  d_poses: n_poses x 4 doubles
+ * (cos, sin, tx, ty), cos and sin from the host as with slam_csm_angles.  d_score[p] = sum over the scan's points of the
+ * table byte of their class at cell(q), q = (c px - s py) + tx, (s px + c py) + ty, every operation rounded on its own;
+ * d_counted[p] = the points that have a cell and a table (slam_csm_result's n_points): a point outside the table is counted
+ * and scores 0, a non-finite pose counts 0 and scores 0.  n <= 2^23; n = 0 gives 0, 0 (no five-point rule); n_poses = 0
+ * does nothing.  Asynchronous; allocates, frees and waits for nothing.  Where the poses form a lattice, the search calls
+ * above are the faster tool: they share one rotation's cells between all translations. */
+int  slam_csm_score_poses_dev(slam_csm_t *csm, const double *d_pts, int n, int n_ga, const double *d_poses, int n_poses,
+                              int32_t *d_score, int32_t *d_counted, slam_stream_t stream);
+/* the same on host pointers: stages and waits */
+int  slam_csm_score_poses(slam_csm_t *csm, const double *pts, int n, int n_ga, const double *poses, int n_poses, int32_t *score,
+                          int32_t *counted);
 
 /* The match's posterior (docs/CSM.md section 6): every candidate whose score lies within a margin M of the winner's S* is
  * weighted by a table of exp(-beta d / M) in 16.16 fixed point, and the weights' integer moments about the winner give a

@@ -274,6 +274,7 @@ EXPORTS = [
     "slam_grid_enable_accumulator", "slam_grid_fold",
     "slam_gdist_default_params", "slam_grid_inflation_table", "slam_gdist_create", "slam_gdist_destroy", "slam_gdist_set_table",
     "slam_gdist_compute_dev", "slam_gdist_compute", "slam_gdist_read", "slam_gdist_planes_dev", "slam_grid_distance_field",
+    "slam_grid_likelihood_table",
     "slam_gseg_default_params", "slam_gseg_create", "slam_gseg_destroy", "slam_gseg_reserve",
     "slam_gseg_segment", "slam_gseg_segment_dev", "slam_gseg_split_dev", "slam_gseg_read_model",
     "slam_gseg_classify_ga_dev", "slam_gseg_classify_ga_counted_dev", "slam_gseg_classify_ga_extent_dev",
@@ -298,6 +299,8 @@ EXPORTS = [
     "slam_csm_score_volume_dev", "slam_csm_read_table", "slam_csm_info",
     "slam_csm_default_post_params", "slam_csm_set_post_params", "slam_csm_read_post_table", "slam_csm_match_post_batch_dev",
     "slam_csm_match_post",
+    "slam_csm_create_from_plane", "slam_csm_create_from_plane_dev", "slam_csm_set_plane_dev", "slam_csm_score_poses_dev",
+    "slam_csm_score_poses",
     "slam_vmap_default_params", "slam_vmap_create", "slam_vmap_destroy", "slam_vmap_clear", "slam_vmap_integrate",
     "slam_vmap_integrate_dev", "slam_vmap_extract_dev", "slam_vmap_read", "slam_vmap_read_sums", "slam_vmap_info",
     "slam_vmap_default_carve_params", "slam_vmap_carve_dev", "slam_vmap_carve", "slam_vmap_extract_carved_dev", "slam_vmap_read_carved",
@@ -450,6 +453,7 @@ def lib():
     L.slam_gdist_read.argtypes = [_vp, _vp, _vp]
     L.slam_gdist_planes_dev.argtypes = [_vp, C.POINTER(_vp), C.POINTER(_vp)]
     L.slam_grid_distance_field.argtypes = [_vp, _vp, _vp]
+    L.slam_grid_likelihood_table.argtypes = [C.c_double, C.c_double, C.c_int, _vp, C.c_int]
     L.slam_gseg_default_params.restype = None
     L.slam_gseg_default_params.argtypes = [C.POINTER(GsegParams)]
     L.slam_gseg_create.argtypes = [C.POINTER(GsegParams), C.POINTER(_vp)]
@@ -545,6 +549,11 @@ def lib():
     L.slam_csm_read_post_table.argtypes = [_vp, _vp, C.c_int]
     L.slam_csm_match_post_batch_dev.argtypes = [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     L.slam_csm_match_post.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.POINTER(CsmResult), C.POINTER(CsmPosterior)]
+    L.slam_csm_create_from_plane.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CsmParams), C.POINTER(_vp)]
+    L.slam_csm_create_from_plane_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CsmParams), C.POINTER(_vp)]
+    L.slam_csm_set_plane_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp]
+    L.slam_csm_score_poses_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp]
+    L.slam_csm_score_poses.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]
     L.slam_csm_info.argtypes = [_vp, C.POINTER(CsmParams), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                 C.POINTER(C.c_int)]
     L.slam_vmap_default_params.argtypes = [C.POINTER(VmapParams)]
@@ -1012,6 +1021,58 @@ class CorrelativeMatcher:
         self.h = h.value
         self.params = self.info()["params"]
         return self
+
+    @classmethod
+    def from_plane(cls, plane, origin_x, origin_y, params=None, shape=None, **kw):
+        """slam_csm_create_from_plane[_dev] (docs/GRID_MATCH.md): the table is the u8 plane itself, [h, w] with element (0, 0) at
+        lattice cell (origin_x, origin_y).  plane: a host array, or a DeviceArray / device pointer with shape=(h, w)."""
+        self = object.__new__(cls)
+        self.params = params or csm_default_params(**kw)
+        h = _vp()
+        if isinstance(plane, DeviceArray) or isinstance(plane, int):
+            ph, pw = shape if shape is not None else plane.shape
+            check(lib().slam_csm_create_from_plane_dev(getattr(plane, "ptr", plane), int(pw), int(ph), int(origin_x), int(origin_y),
+                                                       C.byref(self.params), C.byref(h)))
+        else:
+            plane = np.ascontiguousarray(plane, dtype=np.uint8)
+            assert plane.ndim == 2
+            ph, pw = plane.shape
+            check(lib().slam_csm_create_from_plane(plane.ctypes.data_as(_vp), int(pw), int(ph), int(origin_x), int(origin_y),
+                                                   C.byref(self.params), C.byref(h)))
+        self.h = h.value
+        self.plane_shape = (int(ph), int(pw))
+        self.params = self.info()["params"]
+        return self
+
+    def set_plane_dev(self, d_plane, origin_x, origin_y, stream=None):
+        """slam_csm_set_plane_dev: another plane of the same size (a DeviceArray is held to it; a bare pointer cannot be) at
+        any origin, a copy and the slide enqueued on `stream`"""
+        if isinstance(d_plane, DeviceArray) and getattr(self, "plane_shape", None) is not None \
+                and d_plane.nbytes != self.plane_shape[0] * self.plane_shape[1]:
+            raise SlamError(E_INVALID, "CorrelativeMatcher.set_plane_dev: a plane of %d bytes, the handle's has %d x %d"
+                            % (d_plane.nbytes, self.plane_shape[1], self.plane_shape[0]))
+        check(lib().slam_csm_set_plane_dev(self.h, getattr(d_plane, "ptr", d_plane), int(origin_x), int(origin_y), _sp(stream)))
+
+    @staticmethod
+    def poses(theta, tx, ty):
+        """[P, 4] f64 (cos, sin, tx, ty) of poses given by angle and translation: what score_poses reads (host libm)"""
+        theta = np.asarray(theta, np.float64).ravel()
+        return np.ascontiguousarray(np.stack([np.cos(theta), np.sin(theta), np.asarray(tx, np.float64).ravel(),
+                                              np.asarray(ty, np.float64).ravel()], axis=1))
+
+    def score_poses_dev(self, d_pts, n, n_ga, d_poses, n_poses, d_score, d_counted, stream=None):
+        check(lib().slam_csm_score_poses_dev(self.h, getattr(d_pts, "ptr", d_pts), int(n), int(n_ga), getattr(d_poses, "ptr", d_poses),
+                                             int(n_poses), getattr(d_score, "ptr", d_score), getattr(d_counted, "ptr", d_counted),
+                                             _sp(stream)))
+
+    def score_poses(self, t_ga, t_nga, poses):
+        """slam_csm_score_poses, host arrays; poses [P, 4] (cos, sin, tx, ty): (score int32 [P], counted int32 [P])"""
+        t_ga, t_nga = np.reshape(t_ga, (-1, 2)), np.reshape(t_nga, (-1, 2))
+        pts = np.ascontiguousarray(np.concatenate([t_ga, t_nga]), dtype=np.float64)
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4)
+        score, counted = np.zeros(len(poses), np.int32), np.zeros(len(poses), np.int32)
+        check(lib().slam_csm_score_poses(self.h, _ptr(pts), len(pts), len(t_ga), _ptr(poses), len(poses), _ptr(score), _ptr(counted)))
+        return score, counted
 
     def info(self):
         p, dims, tb, sb, ms = CsmParams(), (C.c_int * 5)(), C.c_size_t(), C.c_size_t(), C.c_int()
@@ -1783,6 +1844,15 @@ def inflation_table(resolution, inscribed_radius, inflation_radius, cost_scaling
     return t
 
 
+def likelihood_table(resolution, sigma, max_cells):
+    """the correlative matcher's Gaussian stamp as the byte table a DistanceField looks its plane up in: np.uint8[max_cells**2 + 2]
+    indexed by the squared distance in cells (slam_grid_likelihood_table; host only)"""
+    n = max(int(max_cells), 0) ** 2 + 2
+    t = np.zeros(n, dtype=np.uint8)
+    check(lib().slam_grid_likelihood_table(float(resolution), float(sigma), int(max_cells), _ptr(t), n))
+    return t
+
+
 class DistanceField:
     """Exact squared distance to the nearest obstacle cell of an occupancy plane, capped at max_cells, and the costmap read
     off it through a byte table (slam_gdist_*, docs/GRID_DIST.md).  Planes are window order, data[x + size_x * y]."""
@@ -1840,6 +1910,81 @@ class DistanceField:
             self.close()
         except Exception:
             pass
+
+
+class GridMatcher:
+    """Localises a scan in an occupancy grid itself (docs/GRID_MATCH.md): a DistanceField with a likelihood table
+    (unknown_keep_from = 0: unknown cells keep their likelihood byte) whose cost plane is the table of a plane-built
+    CorrelativeMatcher at the grid's resolution.  max_cells = 0: ceil(3 sigma / resolution - 1e-9), the matcher's own rule.
+
+    Frames: the grid's window is centred on grid.get_pose() (0, 0 unless it rolls); the matcher works in the window's frame,
+    whose cell (u, v) is plane element (u + size_x // 2, v + size_y // 2), the grid's own cell_coord.  This adapter subtracts the
+    centre from a start translation and adds it to the answer, one f64 operation each; the C-ABI stays in the window's frame.
+    The matcher keeps its cell rule (floor, f64), the grid's is (int) truncation on f32 points: inside the window they agree."""
+
+    def __init__(self, grid, sigma, max_cells=0, params=None, **kw):
+        self.grid = grid
+        res = grid.resolution
+        R = int(max_cells) if max_cells else int(np.ceil(3.0 * float(sigma) / res - 1e-9))
+        self.sigma, self.max_cells = float(sigma), R
+        self.table = likelihood_table(res, sigma, R)
+        self.field = DistanceField(grid.size_x, grid.size_y, max_cells=R, unknown_keep_from=0)
+        self.field.set_table(self.table)
+        self.origin = (-(grid.size_x // 2), -(grid.size_y // 2))
+        params = params or csm_default_params(**kw)
+        params.resolution = res
+        self.field.compute(np.zeros(grid.cells, np.int8))        # a plane to make the matcher from: update() brings the grid's
+        self.matcher = CorrelativeMatcher.from_plane(self.field.planes_dev()[1], self.origin[0], self.origin[1], params,
+                                                     shape=(grid.size_y, grid.size_x))
+        self.centre = self._centre()
+
+    def _centre(self):
+        """the window's centre in the map frame: a rolling grid's pose (whole cells from 0, 0); a fixed grid stays at 0, 0"""
+        return self.grid.get_pose() if self.grid.params.rolling else (0.0, 0.0)
+
+    def update(self, stream=None):
+        """slam_grid_distance_field then slam_csm_set_plane_dev on `stream`; waits for nothing"""
+        self.grid.distance_field(self.field, stream)
+        self.matcher.set_plane_dev(self.field.planes_dev()[1], self.origin[0], self.origin[1], stream)
+        self.centre = self._centre()
+
+    def _to_window(self, t):
+        t = np.asarray(t, np.float64)
+        return t - np.asarray(self.centre, np.float64)
+
+    def _to_map(self, t):
+        return np.asarray(t, np.float64) + np.asarray(self.centre, np.float64)
+
+    def match(self, t_ga, t_nga, R, t):
+        R, t, res = self.matcher.match(t_ga, t_nga, R, self._to_window(np.reshape(t, 2)))
+        return R, self._to_map(t), res
+
+    def match_post(self, t_ga, t_nga, R, t):
+        R, t, res, post = self.matcher.match_post(t_ga, t_nga, R, self._to_window(np.reshape(t, 2)))
+        return R, self._to_map(t), res, post
+
+    def match_batch(self, batch, R0=None, t0=None):
+        t0 = np.reshape(batch.t if t0 is None else t0, (batch.n_scans, 2))
+        R, t, res = self.matcher.match_batch(batch, R0, self._to_window(t0))
+        return R, self._to_map(t), res
+
+    def score_poses(self, t_ga, t_nga, poses):
+        """poses [P, 4] (cos, sin, tx, ty) in the map frame"""
+        poses = np.array(poses, dtype=np.float64).reshape(-1, 4)
+        poses[:, 2:] = self._to_window(poses[:, 2:])
+        return self.matcher.score_poses(t_ga, t_nga, poses)
+
+    def relocalize(self, t_ga, t_nga, theta_step):
+        """No prior: the window covers the whole grid and all angles, the start is the window's centre.  (R, t, CsmResult)"""
+        half_theta = int(np.ceil(np.pi / float(theta_step)))
+        self.matcher.set_window(self.grid.size_x // 2, self.grid.size_y // 2, half_theta, theta_step)
+        return self.match(t_ga, t_nga, np.eye(2), np.asarray(self.centre, np.float64))
+
+    def close(self):
+        for o in (getattr(self, "matcher", None), getattr(self, "field", None)):
+            if o is not None:
+                o.close()
+        self.matcher = self.field = None
 
 
 def mls_default_params(**kw):

@@ -531,6 +531,59 @@ __global__ void csm_post_finish_kernel(Geom G, Scans S, PostCfg C, int n_scans, 
     post[s] = out;
 }
 
+// ---------------------------------------------------------------- the pose-set scorer (docs/GRID_MATCH.md section 3)
+// Every pose has a rotation of its own, so no cell is shared between poses as walk shares them between translations: the raw
+// points are staged instead, kChunk at a time (16 KB), lanes lie along poses with (c, s, tx, ty) in registers, and a point is
+// an LDS broadcast.  One wave per workgroup: no cross-lane reduction, no atomics, the same bits on every run.  A lane takes
+// kPosePer points at a time: their cells first, then their table bytes together, so that kPosePer loads are in flight and not
+// one (a point without a byte -- no cell, or a cell outside the table -- reads byte 0 of the table and adds nothing).
+constexpr int kPosePer = 4;
+
+__global__ __launch_bounds__(64) void csm_score_poses_kernel(Geom G, const double *pts, int n, int n_ga, const double *poses, int n_poses,
+                                                             int32_t *score, int32_t *counted)
+{
+    __shared__ double raw[2 * kChunk];
+    const int  p = blockIdx.x * 64 + threadIdx.x;
+    const bool live = p < n_poses;
+    double     c = 0.0, s = 0.0, tx = 0.0, ty = 0.0;
+    if (live) c = poses[4 * (size_t)p], s = poses[4 * (size_t)p + 1], tx = poses[4 * (size_t)p + 2], ty = poses[4 * (size_t)p + 3];
+    int acc = 0, cnt = 0;
+    for (int base = 0; base < n; base += kChunk) {
+        const int cn = n - base < kChunk ? n - base : kChunk;
+        __syncthreads();
+        for (int j = threadIdx.x; j < 2 * cn; j += 64) raw[j] = pts[2 * (size_t)base + j];
+        __syncthreads();
+        if (!live) continue;
+        const int split = n_ga - base < 0 ? 0 : (n_ga - base > cn ? cn : n_ga - base);
+        for (int cl = 0; cl < 2; ++cl) {
+            const Tab t = G.T[cl];
+            const int j1 = cl ? cn : split;
+            if (t.w == 0) continue; // a class without a table: point_cell counts none of its points
+            for (int j = cl ? split : 0; j < j1; j += kPosePer) {
+                unsigned at[kPosePer];
+                bool     in[kPosePer];
+#pragma unroll
+                for (int r = 0; r < kPosePer; ++r) {
+                    int cx, cy;
+                    at[r] = 0, in[r] = false;
+                    if (j + r < j1 && point_cell(G.T, raw, 0, j + r, split, c, s, tx, ty, G.res, cx, cy)) {
+                        ++cnt;
+                        const long long col = (long long)cx - t.ox, row = (long long)cy - t.oy;
+                        if ((unsigned long long)col < (unsigned long long)t.w && (unsigned long long)row < (unsigned long long)t.h)
+                            at[r] = (unsigned)row * (unsigned)t.w + (unsigned)col, in[r] = true; // w h <= 2^28
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < kPosePer; ++r) {
+                    const int v = t.v[at[r]];
+                    acc += in[r] ? v : 0;
+                }
+            }
+        }
+    }
+    if (live) score[p] = acc, counted[p] = cnt;
+}
+
 inline unsigned blocks_for(size_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 inline int tile_count(const Geom &G) { return ((G.nx + kTileW - 1) / kTileW) * ((G.ny + kTileH - 1) / kTileH); }
@@ -550,12 +603,13 @@ struct slam_csm {
         int    ox = 0, oy = 0, w = 0, h = 0;
         DevMem T, W;
     } tab[2];
+    bool plane = false; // made from a byte plane (slam_csm_create_from_plane*): tab[0] alone exists and both classes read it
     // scratch of a match, for max_scans scans: the bounds, the survivor list, and the keys: every scan's top key, then every
     // scan's best key, then the list counters
     DevMem U, list, keys;
     int    max_scans = 0;
-    // staging of the host form
-    DevMem pts, small;
+    // staging of the host forms
+    DevMem pts, small, poses;
     // the posterior (slam_csm_set_post_params): the 257 weights and one PostAcc per scan
     slam_csm_post_params PP = {0, 0.0, 0, 0};
     bool                 post_set = false;
@@ -576,8 +630,9 @@ struct slam_csm {
         Geom g;
         for (int c = 0; c < 2; ++c) {
             const int D1 = P.block - 1;
-            g.T[c] = Tab{tab[c].T.as<uint8_t>(), tab[c].ox, tab[c].oy, tab[c].w, tab[c].h};
-            g.W[c] = tab[c].w ? Tab{tab[c].W.as<uint8_t>(), tab[c].ox - D1, tab[c].oy - D1, tab[c].w + D1, tab[c].h + D1} : Tab{nullptr, 0, 0, 0, 0};
+            const Table &t = tab[plane ? 0 : c];
+            g.T[c] = Tab{t.T.as<uint8_t>(), t.ox, t.oy, t.w, t.h};
+            g.W[c] = t.w ? Tab{t.W.as<uint8_t>(), t.ox - D1, t.oy - D1, t.w + D1, t.h + D1} : Tab{nullptr, 0, 0, 0, 0};
         }
         g.res = P.resolution, g.half_x = P.half_x, g.half_y = P.half_y, g.nx = nx(), g.ny = ny(), g.nth = nth(), g.D = P.block;
         g.nbx = nbx(), g.nby = nby();
@@ -701,6 +756,71 @@ int create_common(const double *d_ga, int n_ga, const double *d_nga, int n_nga, 
     return SLAM_OK;
 }
 
+// the lattice holds every cell of a w x h plane at (ox, oy) and of its W, which reaches D - 1 cells further down
+bool plane_origin_ok(int ox, int oy, int w, int h, int D)
+{
+    const long long lim = (long long)kCellLimit;
+    return (long long)ox - (D - 1) >= -lim && (long long)oy - (D - 1) >= -lim && (long long)ox + w - 1 <= lim && (long long)oy + h - 1 <= lim;
+}
+
+// what both plane create calls check before they touch the device; p: the parameters in force (sigma and kernel_cells 0:
+// the plane carries the kernel)
+int plane_arguments(const char *who, const uint8_t *plane, int w, int h, int ox, int oy, const slam_csm_params *params, slam_csm_t **out,
+                    slam_csm_params &p)
+{
+    SLAM_REQUIRE(out, SLAM_E_INVALID, "%s: null out pointer", who);
+    *out = nullptr;
+    SLAM_REQUIRE(plane, SLAM_E_INVALID, "%s: null plane", who);
+    SLAM_REQUIRE(w >= 1 && h >= 1, SLAM_E_INVALID, "%s: a plane of %d x %d cells", who, w, h);
+    slam_csm_default_params(&p);
+    if (params) p = *params;
+    p.sigma = 0.0, p.kernel_cells = 0;
+    SLAM_REQUIRE(p.resolution > 0 && std::isfinite(p.resolution), SLAM_E_INVALID, "%s: resolution must be positive", who);
+    SLAM_REQUIRE(p.block >= 1 && p.block <= kMaxD, SLAM_E_INVALID, "%s: block lies in 1 .. %d", who, kMaxD);
+    if (check_window(p.half_x, p.half_y, p.half_theta, p.theta_step, p.block) != SLAM_OK) {
+        set_error("%s: half_x, half_y and half_theta lie in 0 .. 16383, theta_step is finite, and the candidates fit a 31-bit index", who);
+        return SLAM_E_INVALID;
+    }
+    SLAM_REQUIRE(((double)w + p.block) * ((double)h + p.block) <= (double)kMaxTableBytes, SLAM_E_INVALID,
+                 "%s: a plane of %d x %d cells is more than %zu bytes of table", who, w, h, kMaxTableBytes);
+    SLAM_REQUIRE(plane_origin_ok(ox, oy, w, h, p.block), SLAM_E_INVALID, "%s: origin (%d, %d) puts cells of the table beyond +-2^30", who, ox, oy);
+    return require_device();
+}
+
+// T = the plane (a copy on `st`), W = its slide; enqueues only
+int plane_tables(slam_csm *s, const uint8_t *plane, hipMemcpyKind kind, int ox, int oy, hipStream_t st)
+{
+    slam_csm::Table &t = s->tab[0];
+    const size_t     nT = (size_t)t.w * t.h, nW = (size_t)(t.w + s->P.block - 1) * (t.h + s->P.block - 1);
+    SLAM_HIP(hipMemcpyAsync(t.T.p, plane, nT, kind, st));
+    t.ox = ox, t.oy = oy;
+    hipLaunchKernelGGL(csm_slide_kernel, dim3(blocks_for(nW, 256)), dim3(256), 0, st, t.T.as<uint8_t>(), t.w, t.h, s->P.block, t.W.as<uint8_t>());
+    SLAM_HIP(hipGetLastError());
+    return SLAM_OK;
+}
+
+int create_plane_common(const uint8_t *plane, hipMemcpyKind kind, int w, int h, int ox, int oy, const slam_csm_params &p, slam_csm_t **out)
+{
+    slam_csm *s = new (std::nothrow) slam_csm();
+    SLAM_REQUIRE(s, SLAM_E_NOMEM, "slam_csm_create_from_plane: out of host memory");
+    s->P = p, s->plane = true;
+    s->tab[0].w = w, s->tab[0].h = h;
+    int rc = s->tab[0].T.alloc((size_t)w * h);
+    if (rc == SLAM_OK) rc = s->tab[0].W.alloc((size_t)(w + p.block - 1) * (h + p.block - 1));
+    if (rc == SLAM_OK) rc = plane_tables(s, plane, kind, ox, oy, nullptr);
+    if (rc == SLAM_OK && hipStreamSynchronize(nullptr) != hipSuccess) {
+        set_error("slam_csm_create_from_plane: the tables' construction failed");
+        rc = SLAM_E_HIP;
+    }
+    if (rc == SLAM_OK) rc = reserve_scans(s, 1);
+    if (rc != SLAM_OK) {
+        delete s;
+        return rc;
+    }
+    *out = s;
+    return SLAM_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -729,6 +849,64 @@ int slam_csm_create(const double *m_ga, int n_ga, const double *m_nga, int n_nga
     if (b_ga) SLAM_HIP(hipMemcpy(model.p, m_ga, b_ga, hipMemcpyHostToDevice));
     if (b_nga) SLAM_HIP(hipMemcpy(model.as<char>() + b_ga, m_nga, b_nga, hipMemcpyHostToDevice));
     return create_common(model.as<double>(), n_ga, model.as<double>() + 2 * (size_t)n_ga, n_nga, p, out);
+}
+
+int slam_csm_create_from_plane_dev(const uint8_t *d_plane, int w, int h, int origin_x, int origin_y, const slam_csm_params *params,
+                                   slam_csm_t **out)
+{
+    slam_csm_params p;
+    SLAM_TRY(plane_arguments("slam_csm_create_from_plane_dev", d_plane, w, h, origin_x, origin_y, params, out, p));
+    return create_plane_common(d_plane, hipMemcpyDeviceToDevice, w, h, origin_x, origin_y, p, out);
+}
+
+int slam_csm_create_from_plane(const uint8_t *plane, int w, int h, int origin_x, int origin_y, const slam_csm_params *params, slam_csm_t **out)
+{
+    slam_csm_params p;
+    SLAM_TRY(plane_arguments("slam_csm_create_from_plane", plane, w, h, origin_x, origin_y, params, out, p));
+    return create_plane_common(plane, hipMemcpyHostToDevice, w, h, origin_x, origin_y, p, out);
+}
+
+int slam_csm_set_plane_dev(slam_csm_t *csm, const uint8_t *d_plane, int origin_x, int origin_y, slam_stream_t stream)
+{
+    SLAM_REQUIRE(csm && d_plane, SLAM_E_INVALID, "slam_csm_set_plane_dev: null argument");
+    SLAM_REQUIRE(csm->plane, SLAM_E_INVALID, "slam_csm_set_plane_dev: the handle was made from a model, not from a plane");
+    SLAM_REQUIRE(plane_origin_ok(origin_x, origin_y, csm->tab[0].w, csm->tab[0].h, csm->P.block), SLAM_E_INVALID,
+                 "slam_csm_set_plane_dev: origin (%d, %d) puts cells of the table beyond +-2^30", origin_x, origin_y);
+    return plane_tables(csm, d_plane, hipMemcpyDeviceToDevice, origin_x, origin_y, as_stream(stream));
+}
+
+int slam_csm_score_poses_dev(slam_csm_t *csm, const double *d_pts, int n, int n_ga, const double *d_poses, int n_poses, int32_t *d_score,
+                             int32_t *d_counted, slam_stream_t stream)
+{
+    SLAM_REQUIRE(csm && n >= 0 && n <= (1 << 23) && n_poses >= 0, SLAM_E_INVALID,
+                 "slam_csm_score_poses_dev: bad arguments (at most 2^23 points, so that the sum fits)");
+    if (n_poses == 0) return SLAM_OK;
+    SLAM_REQUIRE((n == 0 || d_pts) && d_poses && d_score && d_counted, SLAM_E_INVALID, "slam_csm_score_poses_dev: null array");
+    n_ga = n_ga < 0 ? 0 : (n_ga > n ? n : n_ga);
+    hipLaunchKernelGGL(csm_score_poses_kernel, dim3(blocks_for((size_t)n_poses, 64)), dim3(64), 0, as_stream(stream), csm->geom(), d_pts, n, n_ga,
+                       d_poses, n_poses, d_score, d_counted);
+    SLAM_HIP(hipGetLastError());
+    return SLAM_OK;
+}
+
+int slam_csm_score_poses(slam_csm_t *csm, const double *pts, int n, int n_ga, const double *poses, int n_poses, int32_t *score, int32_t *counted)
+{
+    SLAM_REQUIRE(csm && n >= 0 && n <= (1 << 23) && n_poses >= 0, SLAM_E_INVALID,
+                 "slam_csm_score_poses: bad arguments (at most 2^23 points, so that the sum fits)");
+    if (n_poses == 0) return SLAM_OK;
+    SLAM_REQUIRE((n == 0 || pts) && poses && score && counted, SLAM_E_INVALID, "slam_csm_score_poses: null array");
+    const size_t pts_b = sizeof(double) * 2 * (size_t)n, pose_b = sizeof(double) * 4 * (size_t)n_poses, out_b = sizeof(int32_t) * (size_t)n_poses;
+    SLAM_TRY(reserve_quarter(csm->pts, pts_b));
+    SLAM_TRY(reserve_quarter(csm->poses, pose_b + 2 * out_b));
+    double  *d_poses = csm->poses.as<double>();
+    int32_t *d_score = reinterpret_cast<int32_t *>(csm->poses.as<char>() + pose_b), *d_counted = d_score + n_poses;
+    if (n) SLAM_HIP(hipMemcpyAsync(csm->pts.p, pts, pts_b, hipMemcpyHostToDevice, nullptr));
+    SLAM_HIP(hipMemcpyAsync(d_poses, poses, pose_b, hipMemcpyHostToDevice, nullptr));
+    SLAM_TRY(slam_csm_score_poses_dev(csm, csm->pts.as<double>(), n, n_ga, d_poses, n_poses, d_score, d_counted, nullptr));
+    SLAM_HIP(hipMemcpyAsync(score, d_score, out_b, hipMemcpyDeviceToHost, nullptr));
+    SLAM_HIP(hipMemcpyAsync(counted, d_counted, out_b, hipMemcpyDeviceToHost, nullptr));
+    SLAM_HIP(hipStreamSynchronize(nullptr));
+    return SLAM_OK;
 }
 
 void slam_csm_destroy(slam_csm_t *csm)

@@ -1,6 +1,7 @@
 // grid_cost_table.hpp -- the inflation byte table of the occupancy grid's costmap (docs/GRID_DIST.md section 1): the only
 // floating point of the distance field, and it stays on the host.  Plain C++: no HIP, no device, no library state, so that it
-// can be compiled alone (tests/cpp/grid_cost_table_check.cpp runs it under the host sanitizers).
+// can be compiled alone (tests/cpp/grid_cost_table_check.cpp runs it under the host sanitizers).  Below it the likelihood-field
+// table of a grid matcher (docs/GRID_MATCH.md), under the same terms (tests/cpp/grid_likelihood_table_check.cpp).
 //
 // The curve is the one of ROS costmap_2d's inflation layer, restated from its definition: a table T of R*R + 2 bytes indexed by
 // the squared distance in cells,
@@ -47,6 +48,32 @@ inline int grid_inflation_table(double resolution, double inscribed_radius, doub
             c = (uint8_t)(252.0 * std::exp(-cost_scaling * (d - inscribed_radius))); // in [0, 252]: d > inscribed_radius here
         table[k] = c;
     }
+    table[far] = 0;
+    return 0;
+}
+
+// The likelihood-field table of a grid matcher (docs/GRID_MATCH.md section 2): the correlative matcher's Gaussian stamp
+// (csm.hip, create_common) indexed by the squared distance in cells, so that entry i*i + j*j is stamp entry (i, j):
+//   T[k]       = (uint8_t)rint(255 * exp(-(k * resolution^2) / (2 * sigma^2)))      k = 0 .. R*R
+//   T[R*R + 1] = 0                                                                   what a cell beyond R cells reads
+// Same answers as above.  resolution^2 and 2 sigma^2 must themselves be positive and finite doubles: where a square
+// underflows to 0 or overflows, the quotient has no value.
+inline int grid_likelihood_table(double resolution, double sigma, int max_cells, uint8_t *table, int n, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (!table) return *why = "null table", -1;
+    if (max_cells < 1 || max_cells > kGdistMaxCells) return *why = "max_cells must be 1..254", -1;
+    const int R = max_cells, far = R * R + 1;
+    if (n != far + 1) return *why = "the table has max_cells * max_cells + 2 entries", -1;
+    if (!std::isfinite(resolution) || !std::isfinite(sigma)) return *why = "non-finite argument", -1;
+    if (!(resolution > 0.0)) return *why = "resolution must be positive", -1;
+    if (!(sigma > 0.0)) return *why = "sigma must be positive", -1;
+    const double r2 = resolution * resolution, s2 = 2.0 * (sigma * sigma);
+    if (!(r2 > 0.0) || !std::isfinite(r2) || !(s2 > 0.0) || !std::isfinite(s2))
+        return *why = "resolution squared or sigma squared leaves the range of a double", -1;
+    for (int k = 0; k < far; ++k) table[k] = (uint8_t)std::rint(255.0 * std::exp(-((double)k * r2) / s2)); // in [0, 255]
     table[far] = 0;
     return 0;
 }

@@ -233,6 +233,16 @@ int slam_grid_inflation_table(double resolution, double inscribed_radius, double
     return SLAM_OK;
 }
 
+int slam_grid_likelihood_table(double resolution, double sigma, int max_cells, uint8_t *table, int n)
+{
+    const char *why = "";
+    if (grid_likelihood_table(resolution, sigma, max_cells, table, n, &why) != 0) {
+        set_error("slam_grid_likelihood_table: %s", why);
+        return SLAM_E_INVALID;
+    }
+    return SLAM_OK;
+}
+
 int slam_gdist_create(int size_x, int size_y, const slam_gdist_params *p, slam_gdist_t **out)
 {
     SLAM_REQUIRE(out, SLAM_E_INVALID, "slam_gdist_create: null out pointer");
