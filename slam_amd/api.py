@@ -10,17 +10,56 @@ import os
 
 import numpy as np
 
+from . import cdecl
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 # SLAM_AMD_MEASURE=1 loads the measurement build (python -m slam_amd.build --measure) for the tools/ scripts
 LIB_PATH = os.path.join(HERE, "lib", "libslam_mi355x_measure.so" if os.environ.get("SLAM_AMD_MEASURE") == "1"
                         else "libslam_mi355x.so")
 RCCL_LIB_PATH = os.path.join(HERE, "lib", "libslam_mi355x_rccl.so")
 
-SLAM_OK = 0
+# Everything the headers declare comes from them (slam_amd/cdecl.py): the symbol lists, every restype / argtypes, the
+# structs and the #defines.  A new entry point is declared in the header and nowhere else; a struct gets a line in
+# STRUCTS only if Python needs it by name.
+_H = cdecl.Header()
+EXPORTS = _H.read("slam_mi355x.h")                  # every symbol include/slam_mi355x.h declares (tests check the .so exports them all)
+RCCL_EXPORTS = _H.read("slam_mi355x_rccl.h")        # those of include/slam_mi355x_rccl.h alone
+_MEASURE_EXPORTS = _H.read("slam_mi355x_measure.h") if os.environ.get("SLAM_AMD_MEASURE") == "1" else []
+
+_D = _H.defines
+SLAM_OK = _D["SLAM_OK"]
 E_INVALID, E_NO_DEVICE, E_HIP, E_TOO_FEW_MODEL, E_TOO_FEW_SCENE, E_NOMEM, E_UNSUPPORTED, E_TIMEOUT, E_COMM, E_IO = \
-    -1, -2, -3, -4, -5, -6, -7, -8, -9, -10
-ICP_P2P, ICP_P2L = 0, 1
-RAYCAST_TILED, RAYCAST_GLOBAL, RAYCAST_TILED_MERGE = 0, 1, 2
+    (_D["SLAM_E_" + n] for n in ("INVALID", "NO_DEVICE", "HIP", "TOO_FEW_MODEL_POINTS", "TOO_FEW_SCENE_POINTS", "NOMEM",
+                                 "UNSUPPORTED", "TIMEOUT", "COMM", "IO"))
+ICP_P2P, ICP_P2L = _D["SLAM_ICP_P2P"], _D["SLAM_ICP_P2L"]
+RAYCAST_TILED, RAYCAST_GLOBAL, RAYCAST_TILED_MERGE = (_D["SLAM_RAYCAST_" + n] for n in ("TILED", "GLOBAL", "TILED_MERGE"))
+GDIST_FAR = _D["SLAM_GDIST_FAR"]
+GSEG_DROPPED, GSEG_GROUND, GSEG_OBSTACLE, GSEG_OVERHEAD = (_D["SLAM_GSEG_" + n] for n in ("DROPPED", "GROUND", "OBSTACLE", "OVERHEAD"))
+KF_NOT_CONVERGED, KF_ITERATIONS, KF_TRANSFORM, KF_ABS_MSE, KF_REL_MSE, KF_NO_CORRESPONDENCES, KF_DEGENERATE = \
+    (_D["SLAM_KF_" + n] for n in ("NOT_CONVERGED", "ITERATIONS", "TRANSFORM", "ABS_MSE", "REL_MSE", "NO_CORRESPONDENCES", "DEGENERATE"))
+PGO_ORDER_RCM, PGO_ORDER_NATURAL, PGO_TRACE = _D["SLAM_PGO_ORDER_RCM"], _D["SLAM_PGO_ORDER_NATURAL"], _D["SLAM_PGO_TRACE"]
+PGO_STOP_ITERATIONS, PGO_STOP_MAX_TRIALS, PGO_STOP_RHO_ZERO = (_D["SLAM_PGO_STOP_" + n] for n in ("ITERATIONS", "MAX_TRIALS", "RHO_ZERO"))
+COMM_SUM, COMM_MIN = _D["SLAM_COMM_SUM"], _D["SLAM_COMM_MIN"]
+MERGE_THEN_NOTHING, MERGE_THEN_FINALIZE_RESET, MERGE_THEN_FOLD_FINALIZE = \
+    (_D["SLAM_MERGE_THEN_" + n] for n in ("NOTHING", "FINALIZE_RESET", "FOLD_FINALIZE"))
+HOST_ALLREDUCE_FN = _H.callbacks["slam_host_allreduce_fn"]
+
+# Python name -> the header's struct.  Two fields carry a trailing underscore because the header's names are Python
+# keywords: KfEdgeReq.from_ and PgoTrial.lambda_.
+STRUCTS = {
+    "IcpParams": "slam_icp_params", "IcpResult": "slam_icp_result", "GridParams": "slam_grid_params",
+    "GdistParams": "slam_gdist_params", "MapperParams": "slam_mapper_params", "GsegParams": "slam_gseg_params",
+    "MlsParams": "slam_mls_params", "KfParams": "slam_kf_params", "KfEdgeReq": "slam_kf_edge_req",
+    "KfEdgeResult": "slam_kf_edge_result", "KfGicpParams": "slam_kf_gicp_params", "KfGicpResult": "slam_kf_gicp_result",
+    "KfScParams": "slam_kf_sc_params", "KfScMatch": "slam_kf_sc_match_t", "CsmParams": "slam_csm_params",
+    "CsmResult": "slam_csm_result", "CsmPostParams": "slam_csm_post_params", "VmapParams": "slam_vmap_params",
+    "VmapCarveParams": "slam_vmap_carve_params", "VmapCarveResult": "slam_vmap_carve_result",
+    "VmapDistParams": "slam_vmap_dist_params", "VmapGicpReq": "slam_vmap_gicp_req", "VmapGicpParams": "slam_vmap_gicp_params",
+    "VmapGicpResult": "slam_vmap_gicp_result", "VmapSearchParams": "slam_vmap_search_params",
+    "VmapSearchHit": "slam_vmap_search_hit", "PgoParams": "slam_pgo_params", "PgoTrial": "slam_pgo_trial",
+    "PgoResult": "slam_pgo_result", "CommStats": "slam_comm_stats",
+}
+globals().update((py, _H.structs[c]) for py, c in STRUCTS.items())
 
 
 class SlamError(RuntimeError):
@@ -29,114 +68,9 @@ class SlamError(RuntimeError):
         self.code = code
 
 
-class IcpParams(C.Structure):
-    _fields_ = [("max_iter", C.c_int), ("min_delta", C.c_double), ("mode", C.c_int),
-                ("normals_k", C.c_int), ("lanes_per_point", C.c_int), ("cell_size", C.c_double),
-                ("force_global", C.c_int), ("build_on_host", C.c_int), ("first_iterations", C.c_int),
-                ("far_div", C.c_int), ("split_launch", C.c_int), ("spread_scans", C.c_int), ("pair_scans", C.c_int),
-                ("spread_wait_us", C.c_int), ("wave_tiles", C.c_int), ("list_min_halo", C.c_double), ("spread_tile", C.c_int)]
-
-
-class IcpResult(C.Structure):
-    _fields_ = [("iters", C.c_int), ("n_corr", C.c_int), ("delta", C.c_double)]
-
-
-class GridParams(C.Structure):
-    _fields_ = [("max_range", C.c_double), ("occupancy_increment", C.c_double),
-                ("occupancy_decrement", C.c_double), ("min_cluster_points", C.c_int),
-                ("rolling", C.c_int), ("raycast_impl", C.c_int), ("raycast_seg_items", C.c_int),
-                ("raycast_wg_per_cu", C.c_int), ("raycast_max_workgroups", C.c_int)]
-
-
-class GdistParams(C.Structure):
-    _fields_ = [("max_cells", C.c_int), ("unknown_is_obstacle", C.c_int), ("unknown_cost", C.c_int), ("unknown_keep_from", C.c_int)]
-
-
-GDIST_FAR = 0xFFFF
-
-class MapperParams(C.Structure):
-    _fields_ = [("grid_size_x", C.c_int), ("grid_size_y", C.c_int), ("resolution", C.c_double), ("grid", GridParams),
-                ("icp", IcpParams), ("indist", C.c_double), ("max_scans", C.c_int), ("max_points", C.c_int),
-                ("window_chunks", C.c_int), ("rebuild_every", C.c_int), ("target_points", C.c_int),
-                ("keep_prior", C.c_int), ("merge_every", C.c_int), ("pipelined", C.c_int), ("strict_window", C.c_int),
-                ("slots", C.c_int), ("thin_res", C.c_double), ("background_rebuild", C.c_int), ("registration_streams", C.c_int)]
-
-
-class GsegParams(C.Structure):
-    _fields_ = [("rmax", C.c_double), ("num_seedpoints", C.c_int), ("gp_lengthparameter", C.c_double),
-                ("gp_covariancescale", C.c_double), ("gp_modelnoise", C.c_double),
-                ("gp_groundmodelconfidence", C.c_double), ("gp_grounddataconfidence", C.c_double),
-                ("gp_groundthreshold", C.c_double), ("robotheight", C.c_double),
-                ("seeding_maxrange", C.c_double), ("seeding_maxheight", C.c_double)]
-
-
-class MlsParams(C.Structure):
-    _fields_ = [("max_range", C.c_double), ("update_dist", C.c_int), ("max_clusters", C.c_int),
-                ("max_cluster_points", C.c_int), ("min_cluster_points", C.c_int), ("normal_threshold", C.c_double),
-                ("height_threshold", C.c_double), ("cluster_sigma_factor", C.c_double),
-                ("cluster_dist_threshold", C.c_double), ("cluster_combine_dist", C.c_double),
-                ("drive_dist_threshold", C.c_double), ("robot_height", C.c_double)]
-
-
-class KfParams(C.Structure):
-    _fields_ = [("leaf_size", C.c_double), ("gate", C.c_double), ("cell_size", C.c_double), ("max_iterations", C.c_int),
-                ("transformation_epsilon", C.c_double), ("fitness_epsilon", C.c_double), ("target_in_lds", C.c_int)]
-
-
-class KfEdgeReq(C.Structure):
-    _fields_ = [("from_", C.c_int), ("to", C.c_int), ("init", C.c_float * 16)]
-
-
-class KfEdgeResult(C.Structure):
-    _fields_ = [("transform", C.c_float * 16), ("transform64", C.c_double * 16), ("iterations", C.c_int),
-                ("state", C.c_int), ("converged", C.c_int), ("pairs", C.c_int), ("mse", C.c_double),
-                ("information", C.c_double * 36), ("num_corr", C.c_int), ("singular", C.c_int), ("ss", C.c_float),
-                ("reserved", C.c_int)]
-
-
-class KfGicpParams(C.Structure):
-    _fields_ = [("k_correspondences", C.c_int), ("cov_radius", C.c_double), ("gicp_epsilon", C.c_double),
-                ("max_iterations", C.c_int), ("transformation_epsilon", C.c_double), ("rotation_epsilon", C.c_double),
-                ("cov_min_neighbours", C.c_int)]
-
-
-class KfGicpResult(C.Structure):
-    _fields_ = [("edge", KfEdgeResult), ("cost", C.c_double), ("hessian", C.c_double * 36), ("fitness", C.c_double),
-                ("fitness_pairs", C.c_int), ("reserved", C.c_int)]
-
-
-class KfScParams(C.Structure):
-    _fields_ = [("n_rings", C.c_int), ("n_sectors", C.c_int), ("max_range", C.c_double), ("z_min", C.c_double),
-                ("z_step", C.c_double)]
-
-
-class KfScMatch(C.Structure):
-    _fields_ = [("distance", C.c_int), ("shift", C.c_int), ("n_query", C.c_int), ("n_candidate", C.c_int),
-                ("n_both", C.c_int)]
-
-
-class CsmParams(C.Structure):
-    _fields_ = [("resolution", C.c_double), ("sigma", C.c_double), ("kernel_cells", C.c_int), ("block", C.c_int),
-                ("half_x", C.c_int), ("half_y", C.c_int), ("half_theta", C.c_int), ("theta_step", C.c_double),
-                ("exhaustive", C.c_int)]
-
-
-class CsmResult(C.Structure):
-    _fields_ = [("k", C.c_int), ("a", C.c_int), ("b", C.c_int), ("score", C.c_int), ("max_score", C.c_int),
-                ("n_points", C.c_int), ("blocks_evaluated", C.c_int)]
-
-
-class CsmPostParams(C.Structure):
-    _fields_ = [("margin_per_point", C.c_int), ("beta", C.c_double), ("excl_xy", C.c_int), ("excl_theta", C.c_int)]
-
-
-class CsmPosterior(C.Structure):
+class CsmPosterior(_H.structs["slam_csm_posterior"]):
     """slam_csm_posterior (docs/CSM.md section 6).  The helpers mirror slam_amd::Posterior of correlative.hpp operation for
     operation; `u` is (resolution, resolution, theta_step), which CorrelativeMatcher.match_post fills in."""
-    _fields_ = [("valid", C.c_int), ("n_within", C.c_int), ("margin", C.c_int), ("blocks_evaluated", C.c_int),
-                ("second_score", C.c_int), ("second_k", C.c_int), ("second_a", C.c_int), ("second_b", C.c_int),
-                ("m0", C.c_int64), ("m1", C.c_int64 * 3), ("m2", C.c_int64 * 6), ("mean", C.c_double * 3),
-                ("cov", C.c_double * 6)]
     u = (0.0, 0.0, 0.0)
     score = n_points = 0
 
@@ -167,153 +101,17 @@ class CsmPosterior(C.Structure):
                     self.score - self.second_score <= int(max_deficit_per_point) * self.n_points)
 
 
-class VmapParams(C.Structure):
-    _fields_ = [("leaf", C.c_double), ("initial_capacity", C.c_int)]
-
-
-class VmapCarveParams(C.Structure):
-    _fields_ = [("end_margin", C.c_int), ("tail_num", C.c_int), ("tail_den", C.c_int), ("max_ray_cells", C.c_int)]
-
-
-class VmapCarveResult(C.Structure):
-    _fields_ = [("n_rays", C.c_int64), ("n_dropped", C.c_int64), ("n_skipped", C.c_int64), ("n_steps", C.c_int64),
-                ("n_seen", C.c_int64), ("n_missed", C.c_int64)]
-
-
-class VmapDistParams(C.Structure):
-    _fields_ = [("min_points", C.c_int), ("flat_ratio", C.c_double), ("line_ratio", C.c_double), ("epsilon", C.c_double),
-                ("max_miss_num", C.c_int), ("max_miss_den", C.c_int)]
-
-
-class VmapGicpReq(C.Structure):
-    _fields_ = [("src", C.c_int), ("init", C.c_float * 16)]
-
-
-class VmapGicpParams(C.Structure):
-    _fields_ = [("gate", C.c_double), ("max_iterations", C.c_int), ("transformation_epsilon", C.c_double),
-                ("rotation_epsilon", C.c_double)]
-
-
-class VmapGicpResult(C.Structure):
-    _fields_ = [("transform", C.c_float * 16), ("transform64", C.c_double * 16), ("iterations", C.c_int), ("state", C.c_int),
-                ("converged", C.c_int), ("pairs", C.c_int), ("mse", C.c_double), ("cost", C.c_double),
-                ("hessian", C.c_double * 36), ("fitness", C.c_double), ("fitness_pairs", C.c_int), ("reserved", C.c_int)]
-
-
-class VmapSearchParams(C.Structure):
-    _fields_ = [("yaw0", C.c_float), ("n_yaw", C.c_int), ("cx", C.c_float), ("cy", C.c_float), ("cz", C.c_float),
-                ("wx", C.c_int), ("wy", C.c_int), ("wz", C.c_int), ("planes_only", C.c_int), ("min_count", C.c_int),
-                ("top_m", C.c_int), ("nms_yaw", C.c_int), ("nms_cells", C.c_int)]
-
-
-class VmapSearchHit(C.Structure):
-    _fields_ = [("score", C.c_int), ("k", C.c_int), ("dx", C.c_int), ("dy", C.c_int), ("dz", C.c_int), ("n_with_cell", C.c_int),
-                ("init", C.c_float * 16)]
-
-
-class PgoParams(C.Structure):
-    _fields_ = [("max_trials", C.c_int), ("tau", C.c_double), ("good_lower", C.c_double), ("good_upper", C.c_double),
-                ("ordering", C.c_int), ("max_band_bytes", C.c_size_t)]
-
-
-class PgoTrial(C.Structure):
-    _fields_ = [("lambda_", C.c_double), ("rho", C.c_double), ("chi2", C.c_double), ("accepted", C.c_int), ("reserved", C.c_int)]
-
-
-PGO_TRACE = 64
-
-
-class PgoResult(C.Structure):
-    _fields_ = [("iterations", C.c_int), ("stop_reason", C.c_int), ("half_bandwidth", C.c_int), ("free_vertices", C.c_int),
-                ("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("band_bytes", C.c_size_t), ("n_trials", C.c_int),
-                ("reserved", C.c_int), ("trace", PgoTrial * PGO_TRACE)]
-
-
-PGO_ORDER_RCM, PGO_ORDER_NATURAL = 0, 1
-PGO_STOP_ITERATIONS, PGO_STOP_MAX_TRIALS, PGO_STOP_RHO_ZERO = 0, 1, 2
-
 CSM_RESULT_DTYPE = np.dtype([(f, np.int32) for f, _ in CsmResult._fields_])
 CSM_POST_DTYPE = np.dtype([(f, np.int32) for f, _ in CsmPosterior._fields_[:8]] +
                           [("m0", np.int64), ("m1", np.int64, (3,)), ("m2", np.int64, (6,)), ("mean", np.float64, (3,)),
                            ("cov", np.float64, (6,))])
 
-KF_NOT_CONVERGED, KF_ITERATIONS, KF_TRANSFORM, KF_ABS_MSE, KF_REL_MSE, KF_NO_CORRESPONDENCES = 0, 1, 2, 3, 4, 5
-KF_DEGENERATE = 6   # Generalized ICP only: the step's 6 x 6 has a pivot that is not positive and finite
 KF_LATTICE_MARGIN = 1.0 + 2.0 ** -16   # the search lattice's edge is cell_size (or the gate) times this
-
-GSEG_DROPPED, GSEG_GROUND, GSEG_OBSTACLE, GSEG_OVERHEAD = 0, 1, 2, 3
 
 RESULT_DTYPE = np.dtype([("iters", np.int32), ("n_corr", np.int32), ("delta", np.float64)])
 
 _vp = C.c_void_p
 _lib = None
-
-# every symbol include/slam_mi355x.h declares (tests check the .so exports them all)
-EXPORTS = [
-    "slam_last_error", "slam_version", "slam_device_count", "slam_set_device", "slam_device_info",
-    "slam_malloc", "slam_free", "slam_memset", "slam_memcpy_h2d", "slam_memcpy_d2h",
-    "slam_memcpy_d2d", "slam_host_is_pinned", "slam_host_alloc", "slam_host_free", "slam_memcpy_h2d_async",
-    "slam_memcpy_d2h_async", "slam_stream_wait_event", "slam_graph_begin_capture", "slam_graph_end_capture",
-    "slam_graph_launch", "slam_graph_destroy",
-    "slam_stream_create", "slam_stream_create_with_priority", "slam_stream_create_reserving_cus", "slam_stream_destroy", "slam_stream_synchronize",
-    "slam_device_synchronize", "slam_event_create", "slam_event_destroy", "slam_event_record",
-    "slam_event_synchronize", "slam_event_query", "slam_event_elapsed_ms",
-    "slam_icp_default_params", "slam_icp_create", "slam_icp_create_dev", "slam_icp_destroy",
-    "slam_icp_build_info", "slam_icp_index_blob", "slam_icp_read_model",
-    "slam_icp_set_max_iterations", "slam_icp_set_min_delta", "slam_icp_set_subsampling_step",
-    "slam_icp_fit", "slam_icp_fit_batch_dev", "slam_icp_fit_batch_from_dev", "slam_icp_nearest_dev", "slam_icp_get_edge_weight",
-    "slam_icp_get_normals",
-    "slam_icp_index_info", "slam_icp_list_info",
-    "slam_grid_default_params", "slam_grid_create", "slam_grid_destroy", "slam_grid_clear", "slam_grid_reset_counts",
-    "slam_grid_set_min_cluster_points", "slam_grid_set_max_range", "slam_grid_set_pose",
-    "slam_grid_get_pose", "slam_grid_add_endpoints", "slam_grid_add_endpoints_dev",
-    "slam_grid_raycast", "slam_grid_raycast_dev", "slam_grid_raycast_scans_dev", "slam_grid_reserve",
-    "slam_grid_finalize", "slam_grid_finalize_reset", "slam_grid_add_scan_inorder", "slam_grid_add_scan_inorder_dev", "slam_grid_transform_cloud_dev", "slam_grid_read_counts",
-    "slam_grid_read_occupancy", "slam_grid_read_num_pts", "slam_grid_total_updates",
-    "slam_grid_info", "slam_grid_window_cell", "slam_grid_counts_dev", "slam_grid_mark_rows", "slam_grid_raycast_stats", "slam_grid_dirty_rows", "slam_grid_dirty_rows_dev",
-    "slam_grid_enable_accumulator", "slam_grid_fold",
-    "slam_gdist_default_params", "slam_grid_inflation_table", "slam_gdist_create", "slam_gdist_destroy", "slam_gdist_set_table",
-    "slam_gdist_compute_dev", "slam_gdist_compute", "slam_gdist_read", "slam_gdist_planes_dev", "slam_grid_distance_field",
-    "slam_grid_likelihood_table",
-    "slam_gseg_default_params", "slam_gseg_create", "slam_gseg_destroy", "slam_gseg_reserve",
-    "slam_gseg_segment", "slam_gseg_segment_dev", "slam_gseg_split_dev", "slam_gseg_read_model",
-    "slam_gseg_classify_ga_dev", "slam_gseg_classify_ga_counted_dev", "slam_gseg_classify_ga_extent_dev",
-    "slam_ccicp_create", "slam_ccicp_destroy", "slam_ccicp_voxel_downsample_dev", "slam_ccicp_split_dev",
-    "slam_ccicp_height_dev", "slam_ccicp_bin_order_dev", "slam_ccicp_select_dev", "slam_ccicp_scene_dev",
-    "slam_ccicp_height_pose_dev", "slam_ccicp_split_box_dev", "slam_ccicp_height_rpy_pose_dev", "slam_ccicp_height_rpy_pose_mirror_dev", "slam_ccicp_scene_cloud_dev", "slam_ccicp_pack_scans_dev",
-    "slam_mapper_default_params", "slam_mapper_create", "slam_mapper_destroy", "slam_mapper_next_slot", "slam_mapper_slots",
-    "slam_mapper_chunk_buffers", "slam_mapper_push", "slam_mapper_wait", "slam_mapper_finish", "slam_mapper_grid",
-    "slam_mapper_target", "slam_mapper_stats", "slam_mapper_set_merge",
-    "slam_mls_default_params", "slam_mls_create", "slam_mls_destroy", "slam_mls_clear", "slam_mls_set_pose",
-    "slam_mls_set_params", "slam_mls_add_cloud", "slam_mls_add_cloud_dev", "slam_mls_offset_z",
-    "slam_mls_read_drivability", "slam_mls_segmented_clouds", "slam_mls_read_cells", "slam_mls_info",
-    "slam_kf_default_params", "slam_kf_create", "slam_kf_destroy", "slam_kf_set_params", "slam_kf_add_keyframe",
-    "slam_kf_add_keyframe_dev", "slam_kf_keyframe_info", "slam_kf_count", "slam_kf_read_keyframe", "slam_kf_nearest_dev",
-    "slam_kf_register_edges", "slam_kf_register_edges_traced", "slam_kf_remove_keyframe", "slam_kf_replace_keyframe_dev",
-    "slam_kf_gicp_default_params", "slam_kf_set_gicp_params", "slam_kf_compute_covariances", "slam_kf_read_covariances",
-    "slam_kf_read_neighbours", "slam_kf_register_gicp", "slam_kf_register_gicp_traced",
-    "slam_kf_sc_default_params", "slam_kf_set_sc_params", "slam_kf_sc_compute", "slam_kf_sc_read", "slam_kf_sc_read_tables",
-    "slam_kf_sc_match",
-    "slam_csm_default_params", "slam_csm_create", "slam_csm_create_dev", "slam_csm_destroy", "slam_csm_reserve",
-    "slam_csm_set_window", "slam_csm_set_exhaustive", "slam_csm_angles", "slam_csm_match_batch_dev", "slam_csm_match",
-    "slam_csm_score_volume_dev", "slam_csm_read_table", "slam_csm_info",
-    "slam_csm_default_post_params", "slam_csm_set_post_params", "slam_csm_read_post_table", "slam_csm_match_post_batch_dev",
-    "slam_csm_match_post",
-    "slam_csm_create_from_plane", "slam_csm_create_from_plane_dev", "slam_csm_set_plane_dev", "slam_csm_score_poses_dev",
-    "slam_csm_score_poses",
-    "slam_vmap_default_params", "slam_vmap_create", "slam_vmap_destroy", "slam_vmap_clear", "slam_vmap_integrate",
-    "slam_vmap_integrate_dev", "slam_vmap_extract_dev", "slam_vmap_read", "slam_vmap_read_sums", "slam_vmap_info",
-    "slam_vmap_default_carve_params", "slam_vmap_carve_dev", "slam_vmap_carve", "slam_vmap_extract_carved_dev", "slam_vmap_read_carved",
-    "slam_vmap_read_carve",
-    "slam_vmap_default_dist_params", "slam_vmap_enable_distributions", "slam_vmap_read_moments", "slam_vmap_compute_distributions",
-    "slam_vmap_read_distributions", "slam_vmap_default_gicp_params", "slam_vmap_register_gicp", "slam_vmap_register_gicp_traced",
-    "slam_vmap_layout", "slam_vmap_absorb_dev", "slam_vmap_absorb", "slam_vmap_merge", "slam_vmap_save", "slam_vmap_load",
-    "slam_vmap_coarsen",
-    "slam_vmap_default_search_params", "slam_vmap_search_dev", "slam_vmap_search", "slam_vmap_search_keyframe",
-    "slam_pgo_default_params", "slam_pgo_create", "slam_pgo_destroy", "slam_pgo_clear", "slam_pgo_add_vertex",
-    "slam_pgo_set_vertex", "slam_pgo_add_edge", "slam_pgo_size", "slam_pgo_optimize", "slam_pgo_read_vertices", "slam_pgo_chi2",
-    "slam_pgo_read_system", "slam_pgo_step",
-]
 
 
 def lib():
@@ -325,294 +123,7 @@ def lib():
         raise SlamError(E_NO_DEVICE, "HIP library not built: %s is missing "
                         "(run `python -m slam_amd.build`); there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    L.slam_last_error.restype = C.c_char_p
-    L.slam_version.restype = C.c_char_p
-    L.slam_icp_destroy.restype = None
-    L.slam_ccicp_destroy.restype = None
-    L.slam_ccicp_destroy.argtypes = [C.c_void_p]
-    L.slam_ccicp_voxel_downsample_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float,
-                                                  C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.slam_ccicp_split_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
-                                       C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.slam_ccicp_select_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]
-    L.slam_ccicp_bin_order_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                           C.c_void_p]
-    L.slam_ccicp_height_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]
-    L.slam_ccicp_scene_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
-                                       C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.slam_ccicp_height_pose_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                             C.c_double, C.c_void_p, C.c_void_p]
-    L.slam_ccicp_split_box_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]
-    L.slam_ccicp_height_rpy_pose_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                                 C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
-    L.slam_ccicp_scene_cloud_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.slam_ccicp_pack_scans_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.slam_gseg_classify_ga_counted_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.slam_gseg_classify_ga_extent_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.slam_ccicp_height_rpy_pose_mirror_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                                        C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                                        C.c_void_p]
-    L.slam_grid_destroy.restype = None
-    L.slam_icp_default_params.restype = None
-    L.slam_grid_default_params.restype = None
-    L.slam_malloc.argtypes = [C.POINTER(_vp), C.c_size_t]
-    L.slam_free.argtypes = [_vp]
-    L.slam_memset.argtypes = [_vp, C.c_int, C.c_size_t, _vp]
-    L.slam_memcpy_h2d.argtypes = [_vp, _vp, C.c_size_t, _vp]
-    L.slam_memcpy_d2h.argtypes = [_vp, _vp, C.c_size_t, _vp]
-    L.slam_memcpy_d2d.argtypes = [_vp, _vp, C.c_size_t, _vp]
-    L.slam_host_alloc.argtypes = [C.POINTER(_vp), C.c_size_t]
-    L.slam_host_free.argtypes = [_vp]
-    L.slam_memcpy_h2d_async.argtypes = [_vp, _vp, C.c_size_t, _vp]
-    L.slam_memcpy_d2h_async.argtypes = [_vp, _vp, C.c_size_t, _vp]
-    L.slam_stream_wait_event.argtypes = [_vp, _vp]
-    L.slam_graph_begin_capture.argtypes = [_vp]
-    L.slam_graph_end_capture.argtypes = [_vp, C.POINTER(_vp)]
-    L.slam_graph_launch.argtypes = [_vp, _vp]
-    L.slam_graph_destroy.argtypes = [_vp]
-    L.slam_stream_create.argtypes = [C.POINTER(_vp)]
-    L.slam_stream_create_with_priority.argtypes = [C.POINTER(_vp), C.c_int]
-    L.slam_stream_create_reserving_cus.argtypes = [C.POINTER(_vp), C.c_int]
-    L.slam_stream_destroy.argtypes = [_vp]
-    L.slam_stream_synchronize.argtypes = [_vp]
-    L.slam_event_create.argtypes = [C.POINTER(_vp)]
-    L.slam_event_destroy.argtypes = [_vp]
-    L.slam_event_record.argtypes = [_vp, _vp]
-    L.slam_event_synchronize.argtypes = [_vp]
-    L.slam_event_query.argtypes = [_vp, C.POINTER(C.c_int)]
-    L.slam_event_elapsed_ms.argtypes = [_vp, _vp, C.POINTER(C.c_float)]
-    L.slam_device_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
-    L.slam_icp_create.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(IcpParams), C.POINTER(_vp)]
-    L.slam_icp_create_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(IcpParams), C.POINTER(_vp)]
-    L.slam_icp_build_info.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]
-    L.slam_icp_index_blob.argtypes = [_vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.slam_icp_read_model.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_int)]
-    L.slam_icp_destroy.argtypes = [_vp]
-    L.slam_icp_set_max_iterations.argtypes = [_vp, C.c_int]
-    L.slam_icp_set_min_delta.argtypes = [_vp, C.c_double]
-    L.slam_icp_set_subsampling_step.argtypes = [_vp, C.c_int]
-    L.slam_icp_fit.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_double,
-                               C.POINTER(IcpResult)]
-    L.slam_icp_fit_batch_dev.argtypes = [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_double, _vp,
-                                         _vp, _vp]
-    L.slam_icp_fit_batch_from_dev.argtypes = [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_double, _vp,
-                                              _vp, _vp]
-    L.slam_icp_nearest_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]
-    L.slam_icp_get_edge_weight.argtypes = [_vp, _vp]
-    L.slam_icp_get_normals.argtypes = [_vp, _vp]
-    L.slam_icp_list_info.argtypes = [_vp] + [C.c_void_p] * 6
-    L.slam_icp_index_info.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                      C.POINTER(C.c_double), C.POINTER(C.c_int),
-                                      C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
-    L.slam_grid_create.argtypes = [C.c_int, C.c_int, C.c_double, C.POINTER(GridParams),
-                                   C.POINTER(_vp)]
-    L.slam_grid_destroy.argtypes = [_vp]
-    L.slam_grid_clear.argtypes = [_vp, _vp]
-    L.slam_grid_reset_counts.argtypes = [_vp, _vp]
-    L.slam_grid_set_min_cluster_points.argtypes = [_vp, C.c_int]
-    L.slam_grid_set_max_range.argtypes = [_vp, C.c_double]
-    L.slam_grid_set_pose.argtypes = [_vp, C.c_double, C.c_double, _vp]
-    L.slam_grid_get_pose.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.slam_grid_add_endpoints.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int]
-    L.slam_grid_add_endpoints_dev.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp]
-    L.slam_grid_raycast.argtypes = [_vp, _vp, _vp, C.c_int]
-    L.slam_grid_raycast_dev.argtypes = [_vp, _vp, _vp, C.c_int, _vp]
-    L.slam_grid_raycast_scans_dev.argtypes = [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]
-    L.slam_grid_reserve.argtypes = [_vp, C.c_int]
-    L.slam_grid_finalize.argtypes = [_vp, _vp]
-    L.slam_grid_finalize_reset.argtypes = [_vp, _vp]
-    L.slam_grid_add_scan_inorder.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int]
-    L.slam_grid_add_scan_inorder_dev.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp]
-    L.slam_host_is_pinned.argtypes = [_vp]
-    L.slam_grid_transform_cloud_dev.argtypes = [_vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _vp]
-    L.slam_grid_read_counts.argtypes = [_vp, _vp, _vp]
-    L.slam_grid_read_occupancy.argtypes = [_vp, _vp]
-    L.slam_grid_read_num_pts.argtypes = [_vp, _vp]
-    L.slam_grid_total_updates.argtypes = [_vp, C.POINTER(C.c_uint64)]
-    L.slam_grid_info.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
-                                 C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.slam_grid_window_cell.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.slam_grid_counts_dev.argtypes = [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]
-    L.slam_grid_mark_rows.argtypes = [_vp, C.c_int, C.c_int, _vp]
-    L.slam_grid_dirty_rows.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.slam_grid_dirty_rows_dev.argtypes = [_vp, C.POINTER(_vp)]
-    L.slam_grid_enable_accumulator.argtypes = [_vp]
-    L.slam_grid_fold.argtypes = [_vp, C.c_int, C.c_int, _vp]
-    L.slam_gdist_default_params.restype = None
-    L.slam_gdist_default_params.argtypes = [C.POINTER(GdistParams)]
-    L.slam_grid_inflation_table.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _vp, C.c_int]
-    L.slam_gdist_create.argtypes = [C.c_int, C.c_int, C.POINTER(GdistParams), C.POINTER(_vp)]
-    L.slam_gdist_destroy.restype = None
-    L.slam_gdist_destroy.argtypes = [_vp]
-    L.slam_gdist_set_table.argtypes = [_vp, _vp, C.c_int]
-    L.slam_gdist_compute_dev.argtypes = [_vp, _vp, _vp]
-    L.slam_gdist_compute.argtypes = [_vp, _vp]
-    L.slam_gdist_read.argtypes = [_vp, _vp, _vp]
-    L.slam_gdist_planes_dev.argtypes = [_vp, C.POINTER(_vp), C.POINTER(_vp)]
-    L.slam_grid_distance_field.argtypes = [_vp, _vp, _vp]
-    L.slam_grid_likelihood_table.argtypes = [C.c_double, C.c_double, C.c_int, _vp, C.c_int]
-    L.slam_gseg_default_params.restype = None
-    L.slam_gseg_default_params.argtypes = [C.POINTER(GsegParams)]
-    L.slam_gseg_create.argtypes = [C.POINTER(GsegParams), C.POINTER(_vp)]
-    L.slam_gseg_destroy.restype = None
-    L.slam_gseg_destroy.argtypes = [_vp]
-    L.slam_gseg_reserve.argtypes = [_vp, C.c_int]
-    L.slam_gseg_segment.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp]
-    L.slam_gseg_segment_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp]
-    L.slam_gseg_split_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]
-    L.slam_gseg_read_model.argtypes = [_vp, _vp, _vp, _vp]
-    L.slam_gseg_classify_ga_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp]
-    L.slam_grid_raycast_stats.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.slam_mapper_default_params.restype = None
-    L.slam_mapper_default_params.argtypes = [C.POINTER(MapperParams)]
-    L.slam_mapper_create.argtypes = [C.POINTER(MapperParams), _vp, C.c_int, _vp, C.c_int, C.POINTER(_vp)]
-    L.slam_mapper_destroy.restype = None
-    L.slam_mapper_destroy.argtypes = [_vp]
-    L.slam_mapper_next_slot.argtypes = [_vp, C.POINTER(C.c_int)]
-    L.slam_mapper_slots.argtypes = [_vp, C.POINTER(C.c_int)]
-    L.slam_mapper_chunk_buffers.argtypes = [_vp, C.c_int] + [C.POINTER(_vp)] * 5
-    L.slam_mapper_push.argtypes = [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int)]
-    L.slam_mapper_wait.argtypes = [_vp, C.c_int, _vp, _vp]
-    L.slam_mapper_finish.argtypes = [_vp]
-    L.slam_mapper_grid.argtypes = [_vp, C.POINTER(_vp)]
-    L.slam_mapper_target.argtypes = [_vp, C.POINTER(_vp)]
-    L.slam_mapper_stats.argtypes = [_vp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_double),
-                                    C.POINTER(C.c_int)]
-    L.slam_mapper_set_merge.argtypes = [_vp, _vp, _vp, _vp]
-    L.slam_mls_default_params.restype = None
-    L.slam_mls_default_params.argtypes = [C.POINTER(MlsParams)]
-    L.slam_mls_create.argtypes = [C.c_int, C.c_int, C.c_double, C.POINTER(MlsParams), C.POINTER(_vp)]
-    L.slam_mls_destroy.restype = None
-    L.slam_mls_destroy.argtypes = [_vp]
-    L.slam_mls_clear.argtypes = [_vp, _vp]
-    L.slam_mls_set_pose.argtypes = [_vp, C.c_double, C.c_double]
-    L.slam_mls_set_params.argtypes = [_vp, C.POINTER(MlsParams)]
-    L.slam_mls_add_cloud.argtypes = [_vp, _vp, C.c_int, C.c_int]
-    L.slam_mls_add_cloud_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp]
-    L.slam_mls_offset_z.argtypes = [_vp, C.c_double, _vp]
-    L.slam_mls_read_drivability.argtypes = [_vp, _vp]
-    L.slam_mls_segmented_clouds.argtypes = [_vp, _vp, C.c_int, C.POINTER(C.c_int), _vp, C.c_int, C.POINTER(C.c_int)]
-    L.slam_mls_read_cells.argtypes = [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
-    L.slam_mls_info.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int),
-                                C.POINTER(MlsParams), C.POINTER(C.c_int)]
-    L.slam_kf_default_params.argtypes = [C.POINTER(KfParams)]
-    L.slam_kf_default_params.restype = None
-    L.slam_kf_create.argtypes = [C.POINTER(KfParams), C.POINTER(_vp)]
-    L.slam_kf_destroy.argtypes = [_vp]
-    L.slam_kf_destroy.restype = None
-    L.slam_kf_set_params.argtypes = [_vp, C.POINTER(KfParams)]
-    L.slam_kf_add_keyframe.argtypes = [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_int)]
-    L.slam_kf_add_keyframe_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_int), _vp]
-    L.slam_kf_remove_keyframe.argtypes = [_vp, C.c_int]
-    L.slam_kf_replace_keyframe_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp]
-    L.slam_kf_keyframe_info.argtypes = [_vp, C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_long)]
-    L.slam_kf_count.argtypes = [_vp]
-    L.slam_kf_read_keyframe.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_int)]
-    L.slam_kf_nearest_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]
-    L.slam_kf_register_edges.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
-    L.slam_kf_register_edges_traced.argtypes = [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]
-    L.slam_kf_gicp_default_params.argtypes = [C.POINTER(KfGicpParams)]
-    L.slam_kf_gicp_default_params.restype = None
-    L.slam_kf_set_gicp_params.argtypes = [_vp, C.POINTER(KfGicpParams)]
-    L.slam_kf_compute_covariances.argtypes = [_vp, C.c_int, _vp]
-    L.slam_kf_read_covariances.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_int)]
-    L.slam_kf_read_neighbours.argtypes = [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
-    L.slam_kf_register_gicp.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
-    L.slam_kf_register_gicp_traced.argtypes = [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]
-    L.slam_kf_sc_default_params.argtypes = [C.POINTER(KfScParams)]
-    L.slam_kf_sc_default_params.restype = None
-    L.slam_kf_set_sc_params.argtypes = [_vp, C.POINTER(KfScParams)]
-    L.slam_kf_sc_compute.argtypes = [_vp, C.c_int, _vp]
-    L.slam_kf_sc_read.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.slam_kf_sc_read_tables.argtypes = [_vp, _vp, _vp, _vp]
-    L.slam_kf_sc_match.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
-    L.slam_csm_default_params.argtypes = [C.POINTER(CsmParams)]
-    L.slam_csm_default_params.restype = None
-    L.slam_csm_create.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(CsmParams), C.POINTER(_vp)]
-    L.slam_csm_create_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.POINTER(CsmParams), C.POINTER(_vp)]
-    L.slam_csm_destroy.argtypes = [_vp]
-    L.slam_csm_destroy.restype = None
-    L.slam_csm_reserve.argtypes = [_vp, C.c_int]
-    L.slam_csm_set_window.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_double]
-    L.slam_csm_set_exhaustive.argtypes = [_vp, C.c_int]
-    L.slam_csm_angles.argtypes = [_vp, _vp, _vp]
-    L.slam_csm_match_batch_dev.argtypes = [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-    L.slam_csm_match.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.POINTER(CsmResult)]
-    L.slam_csm_score_volume_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]
-    L.slam_csm_read_table.argtypes = [_vp, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4 + [_vp, C.c_size_t]
-    L.slam_csm_default_post_params.argtypes = [C.POINTER(CsmPostParams)]
-    L.slam_csm_default_post_params.restype = None
-    L.slam_csm_set_post_params.argtypes = [_vp, C.POINTER(CsmPostParams)]
-    L.slam_csm_read_post_table.argtypes = [_vp, _vp, C.c_int]
-    L.slam_csm_match_post_batch_dev.argtypes = [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-    L.slam_csm_match_post.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.POINTER(CsmResult), C.POINTER(CsmPosterior)]
-    L.slam_csm_create_from_plane.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CsmParams), C.POINTER(_vp)]
-    L.slam_csm_create_from_plane_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CsmParams), C.POINTER(_vp)]
-    L.slam_csm_set_plane_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp]
-    L.slam_csm_score_poses_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp]
-    L.slam_csm_score_poses.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]
-    L.slam_csm_info.argtypes = [_vp, C.POINTER(CsmParams), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
-                                C.POINTER(C.c_int)]
-    L.slam_vmap_default_params.argtypes = [C.POINTER(VmapParams)]
-    L.slam_vmap_default_params.restype = None
-    L.slam_vmap_create.argtypes = [C.POINTER(VmapParams), C.POINTER(_vp)]
-    L.slam_vmap_destroy.argtypes = [_vp]
-    L.slam_vmap_destroy.restype = None
-    L.slam_vmap_clear.argtypes = [_vp, _vp]
-    L.slam_vmap_integrate.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_int)]
-    L.slam_vmap_integrate_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_int), _vp]
-    L.slam_vmap_extract_dev.argtypes = [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int), _vp]
-    L.slam_vmap_read.argtypes = [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
-    L.slam_vmap_read_sums.argtypes = [_vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
-    L.slam_vmap_info.argtypes = [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]
-    L.slam_vmap_default_carve_params.argtypes = [C.POINTER(VmapCarveParams)]
-    L.slam_vmap_default_carve_params.restype = None
-    L.slam_vmap_carve_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(VmapCarveParams), C.POINTER(VmapCarveResult), _vp]
-    L.slam_vmap_carve.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(VmapCarveParams), C.POINTER(VmapCarveResult)]
-    L.slam_vmap_extract_carved_dev.argtypes = [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int), _vp]
-    L.slam_vmap_read_carved.argtypes = [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
-    L.slam_vmap_read_carve.argtypes = [_vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
-    L.slam_vmap_default_dist_params.argtypes = [C.POINTER(VmapDistParams)]
-    L.slam_vmap_default_dist_params.restype = None
-    L.slam_vmap_enable_distributions.argtypes = [_vp, C.POINTER(VmapDistParams)]
-    L.slam_vmap_read_moments.argtypes = [_vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
-    L.slam_vmap_compute_distributions.argtypes = [_vp, _vp]
-    L.slam_vmap_read_distributions.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)]
-    L.slam_vmap_default_gicp_params.argtypes = [C.POINTER(VmapGicpParams)]
-    L.slam_vmap_default_gicp_params.restype = None
-    L.slam_vmap_register_gicp.argtypes = [_vp, _vp, _vp, C.c_int, C.POINTER(VmapGicpParams), _vp, _vp]
-    L.slam_vmap_register_gicp_traced.argtypes = [_vp, _vp, _vp, C.c_int, C.POINTER(VmapGicpParams), _vp, _vp, C.c_int, _vp]
-    L.slam_vmap_layout.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(VmapDistParams)]
-    L.slam_vmap_absorb_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int64), _vp]
-    L.slam_vmap_absorb.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int64)]
-    L.slam_vmap_merge.argtypes = [_vp, _vp, C.POINTER(C.c_int64), _vp]
-    L.slam_vmap_save.argtypes = [_vp, C.c_char_p]
-    L.slam_vmap_load.argtypes = [C.c_char_p, C.POINTER(_vp)]
-    L.slam_vmap_coarsen.argtypes = [_vp, _vp, _vp]
-    L.slam_vmap_default_search_params.argtypes = [C.POINTER(VmapSearchParams)]
-    L.slam_vmap_default_search_params.restype = None
-    L.slam_vmap_search_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, C.POINTER(VmapSearchParams), _vp, C.POINTER(C.c_int), _vp, _vp]
-    L.slam_vmap_search.argtypes = [_vp, _vp, C.c_int, C.c_int, C.POINTER(VmapSearchParams), _vp, C.POINTER(C.c_int), _vp]
-    L.slam_vmap_search_keyframe.argtypes = [_vp, _vp, C.c_int, C.POINTER(VmapSearchParams), _vp, C.POINTER(C.c_int), _vp, _vp]
-    _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
-    L.slam_pgo_default_params.argtypes = [C.POINTER(PgoParams)]
-    L.slam_pgo_default_params.restype = None
-    L.slam_pgo_create.argtypes = [C.POINTER(PgoParams), C.POINTER(_vp)]
-    L.slam_pgo_destroy.argtypes = [_vp]
-    L.slam_pgo_destroy.restype = None
-    L.slam_pgo_clear.argtypes = [_vp]
-    L.slam_pgo_add_vertex.argtypes = [_vp, C.c_int, _vp, C.c_int]
-    L.slam_pgo_set_vertex.argtypes = [_vp, C.c_int, _vp]
-    L.slam_pgo_add_edge.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp]
-    L.slam_pgo_size.argtypes = [_vp, _ip, _ip]
-    L.slam_pgo_optimize.argtypes = [_vp, C.c_int, C.POINTER(PgoResult), _vp]
-    L.slam_pgo_read_vertices.argtypes = [_vp, _vp, C.c_int, _ip]
-    L.slam_pgo_chi2.argtypes = [_vp, _dp, _vp, _vp, _vp]
-    L.slam_pgo_read_system.argtypes = [_vp, _vp, _vp, _vp, C.c_int, _ip, _vp, _vp, _ip, _ip, _vp]
-    L.slam_pgo_step.argtypes = [_vp, C.c_double, _vp, _dp, _dp, _dp, _ip, _vp]
+    _H.bind(L, EXPORTS + _MEASURE_EXPORTS)
     _lib = L
     return L
 
@@ -739,7 +250,37 @@ class PinnedArray:
             pass
 
 
-class Stream:
+class _Handle:
+    """What the library creates and Python owns.  A subclass names, once, the entry point that frees it (`_destroy`) and,
+    if it is not `h`, the attribute that holds it (`_field`).  close() may be called any number of times, also on an object
+    whose constructor raised before the handle existed; `with` closes."""
+    _destroy = None
+    _field = "h"
+    _library = staticmethod(lib)
+
+    def close(self):
+        p = getattr(self, self._field, None)
+        if p:
+            getattr(self._library(), self._destroy)(p)
+            setattr(self, self._field, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class Stream(_Handle):
+    _destroy, _field = "slam_stream_destroy", "ptr"
+
     def __init__(self, priority=None, reserve_cus_per_xcd=0, private_queue=False):
         """reserve_cus_per_xcd > 0: a stream whose kernels leave that many CUs of every XCD alone; private_queue: a stream with a
         hardware queue of its own (slam_stream_create_reserving_cus with 0; such streams have no priority of their own)."""
@@ -758,14 +299,9 @@ class Stream:
     def wait_event(self, ev):
         check(lib().slam_stream_wait_event(self.ptr, ev.ptr))
 
-    def __del__(self):
-        if getattr(self, "ptr", None):
-            lib().slam_stream_destroy(self.ptr)
-            self.ptr = None
-
-
 class Graph:
-    """hipGraph of the library calls issued on `stream` inside the with-block (record once, replay)."""
+    """hipGraph of the library calls issued on `stream` inside the with-block (record once, replay).  Not a _Handle: its
+    with-block records, it does not close."""
 
     def __init__(self, stream):
         self.stream, self.ptr = stream, None
@@ -791,7 +327,9 @@ class Graph:
             self.ptr = None
 
 
-class Event:
+class Event(_Handle):
+    _destroy, _field = "slam_event_destroy", "ptr"
+
     def __init__(self):
         p = _vp()
         check(lib().slam_event_create(C.byref(p)))
@@ -814,26 +352,32 @@ class Event:
         check(lib().slam_event_elapsed_ms(self.ptr, later.ptr, C.byref(ms)))
         return ms.value
 
-    def __del__(self):
-        if getattr(self, "ptr", None):
-            lib().slam_event_destroy(self.ptr)
-            self.ptr = None
-
 
 def _sp(stream):
     return stream.ptr if isinstance(stream, Stream) else stream
 
 
-def icp_default_params(**kw):
-    p = IcpParams()
-    lib().slam_icp_default_params(C.byref(p))
+def _defaults(struct, entry_point, kw):
+    """the library's defaults of a parameter struct, with the fields named in kw set over them"""
+    p = struct()
+    getattr(lib(), entry_point)(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
 
 
-class Icp:
+def _as(struct, address):
+    """an address (a device array of structs, or None) for a parameter the header types as `struct *`"""
+    return C.cast(address, C.POINTER(struct))
+
+
+def icp_default_params(**kw):
+    return _defaults(IcpParams, "slam_icp_default_params", kw)
+
+
+class Icp(_Handle):
     """IcpPointToPoint-shaped handle (icpPointToPoint.h:26-40) over the C-ABI."""
+    _destroy = "slam_icp_destroy"
 
     def __init__(self, m_ga, m_nga, params=None, **kw):
         self.m_ga = np.ascontiguousarray(m_ga, dtype=np.float64).reshape(-1, 2)
@@ -917,7 +461,7 @@ class Icp:
                       d_trace=None, stream=None):
         check(lib().slam_icp_fit_batch_dev(
             self.h, d_pts.ptr, d_off.ptr, d_nga.ptr, int(n_scans), d_R.ptr, d_t.ptr, float(indist),
-            d_result.ptr if d_result is not None else None,
+            _as(IcpResult, d_result.ptr if d_result is not None else None),
             d_trace.ptr if d_trace is not None else None, _sp(stream)))
 
     def fit_batch_from_dev(self, d_pts, d_off, d_nga, n_scans, d_R0, d_t0, d_R, d_t, indist=5.0, d_result=None,
@@ -925,7 +469,7 @@ class Icp:
         """Initial poses read from d_R0 / d_t0, registered poses written to d_R / d_t."""
         check(lib().slam_icp_fit_batch_from_dev(
             self.h, d_pts.ptr, d_off.ptr, d_nga.ptr, int(n_scans), d_R0.ptr, d_t0.ptr, d_R.ptr, d_t.ptr, float(indist),
-            d_result.ptr if d_result is not None else None,
+            _as(IcpResult, d_result.ptr if d_result is not None else None),
             d_trace.ptr if d_trace is not None else None, _sp(stream)))
 
     def fit_batch(self, batch, indist=5.0, trace=False):
@@ -969,37 +513,19 @@ class Icp:
         synchronize()
         return d_d.download(), d_i.download()
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().slam_icp_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def csm_default_params(**kw):
-    p = CsmParams()
-    lib().slam_csm_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(CsmParams, "slam_csm_default_params", kw)
 
 
 def csm_default_post_params(**kw):
-    p = CsmPostParams()
-    lib().slam_csm_default_post_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(CsmPostParams, "slam_csm_default_post_params", kw)
 
 
-class CorrelativeMatcher:
+class CorrelativeMatcher(_Handle):
     """The correlative scan matcher (slam_csm_*, docs/CSM.md): the best of N_theta x N_y x N_x poses around a start pose,
     the wide-basin start for Icp.fit.  The model arrays are Icp's."""
+    _destroy = "slam_csm_destroy"
 
     def __init__(self, m_ga, m_nga, params=None, **kw):
         m_ga = np.ascontiguousarray(m_ga, dtype=np.float64).reshape(-1, 2)
@@ -1119,7 +645,7 @@ class CorrelativeMatcher:
 
     def match_batch_dev(self, d_pts, d_off, d_nga, n_scans, d_R0, d_t0, d_cs, d_R, d_t, d_result=None, stream=None):
         check(lib().slam_csm_match_batch_dev(self.h, d_pts.ptr, d_off.ptr, d_nga.ptr, int(n_scans), d_R0.ptr, d_t0.ptr, d_cs.ptr,
-                                             d_R.ptr, d_t.ptr, d_result.ptr if d_result is not None else None, _sp(stream)))
+                                             d_R.ptr, d_t.ptr, _as(CsmResult, d_result.ptr if d_result is not None else None), _sp(stream)))
 
     def match_batch(self, batch, R0=None, t0=None):
         """Host convenience over a synth.ScanBatch: (R [S, 4], t [S, 2], result [S] of CSM_RESULT_DTYPE)."""
@@ -1167,8 +693,8 @@ class CorrelativeMatcher:
 
     def match_post_batch_dev(self, d_pts, d_off, d_nga, n_scans, d_R0, d_t0, d_cs, d_R, d_t, d_result, d_post, stream=None):
         check(lib().slam_csm_match_post_batch_dev(self.h, d_pts.ptr, d_off.ptr, d_nga.ptr, int(n_scans), d_R0.ptr, d_t0.ptr,
-                                                  d_cs.ptr, d_R.ptr, d_t.ptr, d_result.ptr if d_result is not None else None,
-                                                  d_post.ptr, _sp(stream)))
+                                                  d_cs.ptr, d_R.ptr, d_t.ptr, _as(CsmResult, d_result.ptr if d_result is not None else None),
+                                                  _as(CsmPosterior, d_post.ptr), _sp(stream)))
 
     def match_post_batch(self, batch, R0=None, t0=None):
         """match_batch with the posteriors: (R [S, 4], t [S, 2], result [S], posterior [S] of CSM_POST_DTYPE)."""
@@ -1200,30 +726,16 @@ class CorrelativeMatcher:
         synchronize()
         return d_vol.download()
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().slam_csm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def pgo_default_params(**kw):
-    p = PgoParams()
-    lib().slam_pgo_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(PgoParams, "slam_pgo_default_params", kw)
 
 
-class PoseGraph:
+class PoseGraph(_Handle):
     """The pose-graph optimiser (slam_pgo_*, docs/PGO.md): SE3 vertices (x y z, quaternion x y z w) and edges with a 6 x 6
     information, Levenberg-Marquardt as graph_slam's optimizeGraph runs it.  The graph is host state; optimize, chi2,
     read_system and step run on the device."""
+    _destroy = "slam_pgo_destroy"
 
     def __init__(self, params=None, **kw):
         self.params = params or pgo_default_params(**kw)
@@ -1333,56 +845,25 @@ class PoseGraph:
         est = self.read_vertices()[:len(node_poses)]
         return est, self.pose_offset(node_poses[-1], est[-1], cur_pose), res
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().slam_pgo_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def vmap_default_params(**kw):
-    p = VmapParams()
-    lib().slam_vmap_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(VmapParams, "slam_vmap_default_params", kw)
 
 
 def vmap_default_carve_params(**kw):
-    p = VmapCarveParams()
-    lib().slam_vmap_default_carve_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(VmapCarveParams, "slam_vmap_default_carve_params", kw)
 
 
 def vmap_default_dist_params(**kw):
-    p = VmapDistParams()
-    lib().slam_vmap_default_dist_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(VmapDistParams, "slam_vmap_default_dist_params", kw)
 
 
 def vmap_default_gicp_params(**kw):
-    p = VmapGicpParams()
-    lib().slam_vmap_default_gicp_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(VmapGicpParams, "slam_vmap_default_gicp_params", kw)
 
 
 def vmap_default_search_params(**kw):
-    p = VmapSearchParams()
-    lib().slam_vmap_default_search_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(VmapSearchParams, "slam_vmap_default_search_params", kw)
 
 
 def vmap_search_hit_dict(h):
@@ -1401,9 +882,10 @@ def vmap_carve_result_dict(r):
     return {f: int(getattr(r, f)) for f, _ in VmapCarveResult._fields_}
 
 
-class VoxelMap:
+class VoxelMap(_Handle):
     """The exact sparse voxel map (slam_vmap_*, docs/VOXEL_MAP.md): clouds are integrated in place, each with its own
     transform; a voxel's centroid is the exact mean of its points in units of 2^-20 m, the same bits in any order."""
+    _destroy = "slam_vmap_destroy"
 
     def __init__(self, params=None, **kw):
         self.params = params or vmap_default_params(**kw)
@@ -1567,10 +1049,10 @@ class VoxelMap:
         res = (VmapGicpResult * max(n, 1))()
         tr = np.full((max(n, 1), max(trace, 1)), -1, np.int32)
         if trace > 0:
-            check(lib().slam_vmap_register_gicp_traced(self.h, store.h, C.addressof(req), n, C.byref(p), C.addressof(res), _ptr(tr),
+            check(lib().slam_vmap_register_gicp_traced(self.h, store.h, req, n, C.byref(p), res, _ptr(tr),
                                                        int(trace), _sp(stream)))
         else:
-            check(lib().slam_vmap_register_gicp(self.h, store.h, C.addressof(req), n, C.byref(p), C.addressof(res), _sp(stream)))
+            check(lib().slam_vmap_register_gicp(self.h, store.h, req, n, C.byref(p), res, _sp(stream)))
         out = [vmap_gicp_result_dict(res[e]) for e in range(n)]
         if trace > 0:
             for e in range(n):
@@ -1589,7 +1071,7 @@ class VoxelMap:
         vol = None
         if volume:
             vol = np.zeros((max(p.n_yaw, 0), 2 * p.wz + 1, 2 * p.wy + 1, 2 * p.wx + 1), np.int32)
-        tail = (C.byref(p), C.addressof(hits), C.byref(got), _ptr(vol))
+        tail = (C.byref(p), hits, C.byref(got), _ptr(vol))
         if store is not None:
             check(lib().slam_vmap_search_keyframe(self.h, store.h, int(kid), *tail, _sp(stream)))
         elif d_xyz is not None:
@@ -1661,28 +1143,14 @@ class VoxelMap:
             m.dist_params = lay["dist_params"]
         return m
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().slam_vmap_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def grid_default_params(**kw):
-    p = GridParams()
-    lib().slam_grid_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(GridParams, "slam_grid_default_params", kw)
 
 
-class Grid:
+class Grid(_Handle):
     """MLS-in-occupancy-mode-shaped handle (mls.h:104-242) over the C-ABI."""
+    _destroy = "slam_grid_destroy"
 
     def __init__(self, size_x, size_y, resolution, params=None, **kw):
         self.size_x, self.size_y, self.resolution = int(size_x), int(size_y), float(resolution)
@@ -1814,24 +1282,9 @@ class Grid:
         """df (a DistanceField of this grid's size) computed over the plane read_occupancy() returns; enqueues on `stream`"""
         check(lib().slam_grid_distance_field(self.h, df.h, _sp(stream)))
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().slam_grid_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def gdist_default_params(**kw):
-    p = GdistParams()
-    lib().slam_gdist_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(GdistParams, "slam_gdist_default_params", kw)
 
 
 def inflation_table(resolution, inscribed_radius, inflation_radius, cost_scaling, max_cells):
@@ -1853,9 +1306,10 @@ def likelihood_table(resolution, sigma, max_cells):
     return t
 
 
-class DistanceField:
+class DistanceField(_Handle):
     """Exact squared distance to the nearest obstacle cell of an occupancy plane, capped at max_cells, and the costmap read
     off it through a byte table (slam_gdist_*, docs/GRID_DIST.md).  Planes are window order, data[x + size_x * y]."""
+    _destroy = "slam_gdist_destroy"
 
     def __init__(self, size_x, size_y, params=None, **kw):
         self.size_x, self.size_y = int(size_x), int(size_y)
@@ -1899,17 +1353,6 @@ class DistanceField:
         d, c = _vp(), _vp()
         check(lib().slam_gdist_planes_dev(self.h, C.byref(d), C.byref(c)))
         return d.value, c.value
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().slam_gdist_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class GridMatcher:
@@ -1988,43 +1431,28 @@ class GridMatcher:
 
 
 def mls_default_params(**kw):
-    p = MlsParams()
-    lib().slam_mls_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(MlsParams, "slam_mls_default_params", kw)
 
 
 def kf_default_params(**kw):
-    p = KfParams()
-    lib().slam_kf_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(KfParams, "slam_kf_default_params", kw)
 
 
 def kf_gicp_default_params(**kw):
-    p = KfGicpParams()
-    lib().slam_kf_gicp_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(KfGicpParams, "slam_kf_gicp_default_params", kw)
 
 
 SC_MATCH_DTYPE = np.dtype([(f, np.int32) for f, _ in KfScMatch._fields_])
 
 
 def kf_sc_default_params(**kw):
-    p = KfScParams()
-    lib().slam_kf_sc_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(KfScParams, "slam_kf_sc_default_params", kw)
 
 
-class KeyframeStore:
+class KeyframeStore(_Handle):
     """graph_slam's keyframes on the device (slam_kf_*): each one voxel-filtered once and indexed by a 3-D lattice; edges
     (calcEdgeIcp: 3-D point-to-point ICP, then computeEdgeInformationLUM) registered in batches."""
+    _destroy = "slam_kf_destroy"
 
     def __init__(self, params=None, **kw):
         self.h = None
@@ -2033,17 +1461,6 @@ class KeyframeStore:
         check(lib().slam_kf_create(C.byref(p), C.byref(h)))
         self.h = h.value
         self.params = p
-
-    def close(self):
-        if self.h:
-            lib().slam_kf_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __len__(self):
         return int(lib().slam_kf_count(self.h))
@@ -2114,9 +1531,9 @@ class KeyframeStore:
         res = (result_type * max(n, 1))()
         tr = np.full((max(n, 1), max(trace, 1)), -1, np.int32)
         if trace > 0:
-            check(traced(self.h, C.addressof(req), n, C.addressof(res), _ptr(tr), int(trace), _sp(stream)))
+            check(traced(self.h, req, n, res, _ptr(tr), int(trace), _sp(stream)))
         else:
-            check(plain(self.h, C.addressof(req), n, C.addressof(res), _sp(stream)))
+            check(plain(self.h, req, n, res, _sp(stream)))
         out = [to_dict(res[e]) for e in range(n)]
         if trace > 0:
             for e in range(n):
@@ -2194,7 +1611,7 @@ class KeyframeStore:
         removed keyframe and for the query itself."""
         q = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
         out = np.zeros((len(q), len(self)), SC_MATCH_DTYPE)
-        check(lib().slam_kf_sc_match(self.h, _ptr(q), len(q), _ptr(out), _sp(stream)))
+        check(lib().slam_kf_sc_match(self.h, _ptr(q), len(q), _as(KfScMatch, _ptr(out)), _sp(stream)))
         return out
 
     def loop_candidates(self, kid, k=3, min_gap=10, max_distance=None):
@@ -2667,8 +2084,9 @@ def kf_result_dict(r):
             "singular": r.singular, "ss": np.float32(r.ss)}
 
 
-class MlsMap:
+class MlsMap(_Handle):
     """The height-cluster MLS map (class MLS, non-rolling: mls.h:154-237) over the C-ABI: graph_slam's global map."""
+    _destroy = "slam_mls_destroy"
 
     def __init__(self, size_x, size_y, resolution, params=None, **kw):
         self.size_x, self.size_y, self.resolution = int(size_x), int(size_y), float(resolution)
@@ -2678,17 +2096,6 @@ class MlsMap:
         self.h = h.value
         self.cells = self.size_x * self.size_y
         self.capacity = self.info()["capacity"]
-
-    def close(self):
-        if self.h:
-            lib().slam_mls_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def info(self):
         sx, sy, cap, pend = C.c_int(), C.c_int(), C.c_int(), C.c_int()
@@ -2757,19 +2164,17 @@ class MlsMap:
         return out
 
 
-class Mapper:
+class Mapper(_Handle):
     """slam_mapper_t: the streaming form of the path (BASELINE config 5).  push() copies a chunk of a ScanBatch into
     the next slot's pinned buffers and enqueues it; wait() returns its registered poses."""
+    _destroy = "slam_mapper_destroy"
 
     def __init__(self, m_ga, m_nga, grid=None, icp=None, **kw):
-        p = MapperParams()
-        lib().slam_mapper_default_params(C.byref(p))
+        p = _defaults(MapperParams, "slam_mapper_default_params", kw)
         for k, v in (grid or {}).items():
             setattr(p.grid, k, v)
         for k, v in (icp or {}).items():
             setattr(p.icp, k, v)
-        for k, v in kw.items():
-            setattr(p, k, v)
         self.params = p
         m_ga = np.ascontiguousarray(m_ga, dtype=np.float64).reshape(-1, 2)
         m_nga = np.ascontiguousarray(m_nga, dtype=np.float64).reshape(-1, 2)
@@ -2863,26 +2268,13 @@ class Mapper:
         check(rccl_lib().slam_mapper_use_comm(self.h, comm.h))
         self._comm = comm
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().slam_mapper_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class GroundSegmentation:
+class GroundSegmentation(_Handle):
     """groundSegmentation-shaped handle (groundSegmentation.h:67-128) over the C-ABI."""
+    _destroy = "slam_gseg_destroy"
 
     def __init__(self, **kw):
-        self.params = GsegParams()
-        lib().slam_gseg_default_params(C.byref(self.params))
-        for k, v in kw.items():
-            setattr(self.params, k, v)
+        self.params = _defaults(GsegParams, "slam_gseg_default_params", kw)
         h = _vp()
         check(lib().slam_gseg_create(C.byref(self.params), C.byref(h)))
         self.h = h.value
@@ -2921,20 +2313,10 @@ class GroundSegmentation:
         check(lib().slam_gseg_read_model(self.h, _ptr(state), _ptr(value), _ptr(iters)))
         return state, value, iters
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().slam_gseg_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Ccicp:
+class Ccicp(_Handle):
     """The CCICP facade steps either side of the ICP (icpTools.cpp:222-381, 611-634) over the C-ABI."""
+    _destroy = "slam_ccicp_destroy"
     ICP_MAX_PTS = 20000  # icpTools.h:21
 
     def __init__(self):
@@ -2997,29 +2379,9 @@ class Ccicp:
                                           idx, None))
         return z.value, nc.value, list(idx)
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().slam_ccicp_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ------------------------------------------------------------------ RCCL merge
 _rccl = None
-RCCL_EXPORTS = ["slam_comm_unique_id", "slam_comm_create", "slam_comm_create_host", "slam_comm_adopt", "slam_comm_destroy",
-                "slam_comm_info", "slam_comm_get_stats", "slam_comm_stats_reset", "slam_grid_allreduce", "slam_grid_allreduce_rows", "slam_grid_merge_begin",
-                "slam_grid_merge_finish", "slam_grid_merge_async", "slam_comm_ticket_wait", "slam_comm_drain", "slam_comm_set_timeout",
-                "slam_comm_check", "slam_mapper_use_comm"]
-
-
-COMM_SUM, COMM_MIN = 0, 1
-MERGE_THEN_NOTHING, MERGE_THEN_FINALIZE_RESET, MERGE_THEN_FOLD_FINALIZE = 0, 1, 2
-HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, _vp, C.POINTER(C.c_int32), C.c_size_t, C.c_int)
 
 
 def rccl_lib():
@@ -3031,40 +2393,17 @@ def rccl_lib():
     if not os.path.exists(RCCL_LIB_PATH):
         raise SlamError(E_UNSUPPORTED, "RCCL merge library not built: %s is missing" % RCCL_LIB_PATH)
     R = C.CDLL(RCCL_LIB_PATH, mode=C.RTLD_GLOBAL)
-    R.slam_comm_unique_id.argtypes = [C.c_char_p]
-    R.slam_comm_create.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(_vp)]
-    R.slam_comm_adopt.argtypes = [_vp, C.POINTER(_vp)]
-    R.slam_comm_create_host.argtypes = [C.c_int, C.c_int, HOST_ALLREDUCE_FN, _vp, C.POINTER(_vp)]
-    R.slam_comm_destroy.argtypes = [_vp]
-    R.slam_comm_destroy.restype = None
-    R.slam_comm_info.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    R.slam_comm_get_stats.argtypes = [_vp, C.POINTER(CommStats)]
-    R.slam_comm_stats_reset.argtypes = [_vp]
-    R.slam_grid_allreduce.argtypes = [_vp, _vp, _vp]
-    R.slam_grid_allreduce_rows.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp]
-    R.slam_grid_merge_begin.argtypes = [_vp, _vp, _vp]
-    R.slam_grid_merge_finish.argtypes = [_vp, _vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    R.slam_grid_merge_async.argtypes = [_vp, _vp, _vp, C.c_int, _vp, C.POINTER(C.c_ulonglong)]
-    R.slam_comm_ticket_wait.argtypes = [_vp, C.c_ulonglong, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    R.slam_comm_drain.argtypes = [_vp]
-    R.slam_comm_set_timeout.argtypes = [_vp, C.c_double]
-    R.slam_comm_check.argtypes = [_vp]
-    R.slam_mapper_use_comm.argtypes = [_vp, _vp]
+    _H.bind(R, RCCL_EXPORTS)
     _rccl = R
     return R
 
 
-class CommStats(C.Structure):
-    _fields_ = [("rank", C.c_int), ("n_ranks", C.c_int), ("transport", C.c_int), ("rccl_version", C.c_int),
-                ("merges", C.c_longlong), ("rows", C.c_longlong), ("bytes", C.c_longlong), ("wait_ms", C.c_double),
-                ("allreduce_ms", C.c_double), ("timed", C.c_longlong), ("helper_wait_ms", C.c_double), ("async_merges", C.c_longlong)]
-
-
-class Comm:
+class Comm(_Handle):
     """One RCCL communicator per process/GPU.  `id_bytes` comes from Comm.unique_id()
     on rank 0 and is handed to the other ranks out of band (e.g. a torch.distributed
     broadcast or a file)."""
-    ID_BYTES = 128
+    _destroy, _library = "slam_comm_destroy", staticmethod(rccl_lib)
+    ID_BYTES = _D["SLAM_COMM_ID_BYTES"]
 
     @staticmethod
     def unique_id():
@@ -3149,14 +2488,3 @@ class Comm:
 
     def check(self):
         check(rccl_lib().slam_comm_check(self.h))
-
-    def close(self):
-        if getattr(self, "h", None):
-            rccl_lib().slam_comm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -107,41 +107,169 @@ def test_device_memory_has_one_owner():
             assert what not in txt or f in allowed, "%s holds '%s'" % (f, what)
 
 
-def test_python_binding_declares_pointer_signatures():
+HEADERS = ("slam_mi355x.h", "slam_mi355x_rccl.h")
+
+
+def header_text(name):
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
+
+
+def header_arities(name):
+    """function -> number of parameters, by this file's own regex over the header (not by slam_amd/cdecl.py)"""
+    protos = re.findall(r"\b(slam_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header_text(name))
+    return {n: 0 if a.strip() == "void" else a.count(",") + 1 for n, a in protos}
+
+
+def test_python_binding_declares_pointer_signatures(L):
     """ctypes passes an undeclared Python int as a 32-bit C int: a device pointer handed to an entry point
-    without argtypes would be truncated (a GPU fault, not an error code).  Only calls that take no pointer
-    from Python, or a byref() struct, may go undeclared."""
-    from slam_amd import api
-    L = api.lib()
-    undeclared = {n for n in api.EXPORTS if getattr(L, n).argtypes is None}
-    assert undeclared <= {"slam_last_error", "slam_version", "slam_device_count", "slam_set_device",
-                          "slam_device_synchronize", "slam_icp_default_params", "slam_grid_default_params",
-                          "slam_ccicp_create"}
+    without argtypes would be truncated (a GPU fault, not an error code).  So every export of both libraries is
+    declared, with as many arguments as its prototype has, and the mapping rules hold where each one applies.
+    The RCCL library is not loaded here (ahead of torch's own ROCm libraries it ends the process in a double free at exit):
+    its side is the table rccl_lib() binds from, and tests/test_multi_rank.py holds the loaded library to that table."""
+    class Unloaded:
+        def __getattr__(self, n):
+            return self.__dict__.setdefault(n, type("F", (), {"argtypes": None, "restype": C.c_int})())
+
+    R = Unloaded()
+    api._H.bind(R, api.RCCL_EXPORTS)
+    for lib_, exports, header in ((L, api.EXPORTS, HEADERS[0]), (R, api.RCCL_EXPORTS, HEADERS[1])):
+        arity = header_arities(header)
+        assert sorted(arity) == sorted(exports)
+        for n in exports:
+            f = getattr(lib_, n)
+            assert f.argtypes is not None, n
+            assert len(f.argtypes) == arity[n], (n, len(f.argtypes), arity[n])
+    vp, i, f32, f64, P = C.c_void_p, C.c_int, C.c_float, C.c_double, C.POINTER
+    expected = {
+        "slam_grid_transform_cloud_dev": (i, [vp, i, i, vp, vp, vp, vp]),                       # R[9], t[3]
+        "slam_icp_index_blob": (i, [vp, i, vp, C.c_size_t, vp]),                                # size_t, size_t *
+        "slam_ccicp_voxel_downsample_dev": (i, [vp, vp, vp, i, i, f32, f32, f32, vp, i, vp, vp]),
+        "slam_ccicp_select_dev": (i, [vp, vp, i, i, vp, C.c_uint, vp, vp, vp]),
+        "slam_grid_total_updates": (i, [vp, vp]),                                               # uint64_t *
+        "slam_comm_ticket_wait": (i, [vp, C.c_ulonglong, vp, vp]),
+        "slam_grid_merge_async": (i, [vp, vp, vp, i, vp, vp]),                                  # unsigned long long *
+        "slam_device_info": (i, [C.c_char_p, i, vp, vp]),
+        "slam_vmap_save": (i, [vp, C.c_char_p]),                                                # const char *
+        "slam_version": (C.c_char_p, []),
+        "slam_icp_destroy": (None, [vp]),
+        "slam_icp_set_min_delta": (i, [vp, f64]),
+        "slam_pgo_optimize": (i, [vp, i, P(api.PgoResult), vp]),
+        "slam_csm_match_post": (i, [vp, vp, i, vp, i, vp, vp, P(api.CsmResult), P(api._H.structs["slam_csm_posterior"])]),
+        "slam_comm_get_stats": (i, [vp, P(api.CommStats)]),
+        "slam_comm_create_host": (i, [i, i, api.HOST_ALLREDUCE_FN, vp, vp]),
+        "slam_comm_unique_id": (i, [vp]),                                                       # char id[SLAM_COMM_ID_BYTES]
+        "slam_device_synchronize": (i, []),
+    }
+    for n, (restype, argtypes) in expected.items():
+        f = getattr(R if n in api.RCCL_EXPORTS else L, n)
+        assert f.restype is restype and list(f.argtypes) == argtypes, (n, f.restype, f.argtypes)
+    assert api.HOST_ALLREDUCE_FN._restype_ is i and api.HOST_ALLREDUCE_FN._argtypes_ == (vp, P(C.c_int32), C.c_size_t, i)
+    # a struct position takes the struct by reference, an array of it and NULL, and nothing else
+    assert L.slam_pgo_optimize(None, 1, C.byref(api.PgoResult()), None) == api.E_INVALID
+    with pytest.raises(C.ArgumentError):
+        L.slam_pgo_optimize(None, 1, C.byref(api.PgoParams()), None)
+    with pytest.raises(C.ArgumentError):
+        L.slam_pgo_optimize(None, 1, C.addressof(api.PgoResult()), None)
+
+
+def header_structs(name):
+    """struct -> [(C field name, is an array)], by this file's own regex"""
+    out = {}
+    for body, struct in re.findall(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;", header_text(name), flags=re.S):
+        out[struct] = [(re.sub(r"\[.*", "", d).split()[-1], "[" in d) for decl in body.split(";") if decl.strip()
+                       for d in decl.split(",")]
+    return out
 
 
 def test_python_structs_mirror_the_header(tmp_path):
-    """slam_amd/api.py restates the parameter structs of include/slam_mi355x.h for ctypes: a field added on one side only
-    would shift everything behind it.  A C program prints sizeof and every field's offset; ctypes must agree."""
-    import ctypes as C
+    """Every struct of both headers, as ctypes has it after slam_amd/cdecl.py read the header, against the compiler: a C
+    program prints sizeof and every field's offset, size and element count; ctypes must agree.  The field names are this
+    file's own reading of the header; two are Python keywords and carry an underscore in Python."""
     import subprocess
-    from slam_amd import api
-    structs = {"slam_icp_params": api.IcpParams, "slam_grid_params": api.GridParams, "slam_mapper_params": api.MapperParams,
-               "slam_gseg_params": api.GsegParams, "slam_icp_result": api.IcpResult}
-    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "slam_mi355x.h"', "int main(void) {"]
-    for name, cls in structs.items():
+    structs = {s: f for h in HEADERS for s, f in header_structs(h).items()}
+    classes = dict({c: getattr(api, py) for py, c in api.STRUCTS.items()}, slam_csm_posterior=api.CsmPosterior)
+    assert sorted(structs) == sorted(classes) == sorted(api._H.structs) and len(structs) == 31
+    for py, c in api.STRUCTS.items():
+        assert getattr(api, py) is api._H.structs[c]
+    assert issubclass(api.CsmPosterior, api._H.structs["slam_csm_posterior"])
+    trace = dict(api.PgoResult._fields_)["trace"]
+    assert trace._type_ is api.PgoTrial and trace._length_ == api.PGO_TRACE == 64
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "slam_mi355x_rccl.h"', "int main(void) {"]
+    for name, fields in structs.items():
         lines.append('printf("%s %%zu", sizeof(%s));' % (name, name))
-        for f, _ in cls._fields_:
-            lines.append('printf(" %s=%%zu", offsetof(%s, %s));' % (f, name, f))
+        for f, is_array in fields:
+            member = "((%s *)0)->%s" % (name, f)
+            count = "sizeof(%s) / sizeof(%s[0])" % (member, member) if is_array else "(size_t)0"
+            lines.append('printf(" %s=%%zu:%%zu:%%zu", offsetof(%s, %s), sizeof(%s), %s);' % (f, name, f, member, count))
         lines.append('printf("\\n");')
     lines += ["return 0;", "}"]
     src, exe = tmp_path / "sizes.c", tmp_path / "sizes"
     src.write_text("\n".join(lines))
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
     out = subprocess.check_output([str(exe)], text=True)
+    assert len(out.strip().splitlines()) == len(structs)
     for line in out.strip().splitlines():
         parts = line.split()
-        cls = structs[parts[0]]
+        cls = classes[parts[0]]
         assert int(parts[1]) == C.sizeof(cls), (parts[0], parts[1], C.sizeof(cls))
-        for p in parts[2:]:
-            f, off = p.split("=")
-            assert getattr(cls, f).offset == int(off), (parts[0], f, off, getattr(cls, f).offset)
+        c_names = [p.split("=")[0] for p in parts[2:]]
+        assert [f[:-1] if f in ("from_", "lambda_") else f for f, _ in cls._fields_] == c_names, parts[0]
+        for (f, ctype), p in zip(cls._fields_, parts[2:]):
+            off, size, count = (int(v) for v in p.split("=")[1].split(":"))
+            d = getattr(cls, f)
+            assert (d.offset, d.size, getattr(ctype, "_length_", 0)) == (off, size, count), (parts[0], f, p)
+
+
+@pytest.mark.parametrize("text, named", [
+    ("typedef struct slam_icp slam_icp_t;\nint slam_icp_frob(slam_icp_t *icp, widget_t *w);\n", "widget_t *w"),
+    ("typedef struct {\n    int n; widget_t w;\n} slam_frob_params;\n", "widget_t w"),
+    ("typedef struct {\n    int n; double trace[SLAM_FROB_TRACE];\n} slam_frob_result;\n", "SLAM_FROB_TRACE"),
+    ("int slam_frob(int n);\nunion slam_frob_u { int a; float b; };\n", "union slam_frob_u"),
+    ("int slam_frob(int n);\n#define SLAM_FROB(x) ((x) + 1)\n", "SLAM_FROB(x)"),
+])
+def test_the_header_reader_refuses_what_it_does_not_know(text, named):
+    """An unknown parameter type, an unknown field type, an array bound that is neither a literal nor a defined constant,
+    and declarations outside the dialect: an exception that names the text, never a function left unbound."""
+    from slam_amd import cdecl
+    with pytest.raises(cdecl.CDeclError) as e:
+        cdecl.Header().parse(text)
+    assert named in str(e.value)
+    h = cdecl.Header()
+    assert h.parse("#define SLAM_FROB_TRACE 4\ntypedef struct {\n    int n; double trace[SLAM_FROB_TRACE], one[2];\n} slam_frob_result;\n"
+                   "int slam_frob(const slam_frob_result *r, double out[3]);\n") == ["slam_frob"]
+    assert h.functions["slam_frob"] == (C.c_int, [C.POINTER(h.structs["slam_frob_result"]), C.c_void_p])
+    assert [(f, getattr(t, "_length_", 0)) for f, t in h.structs["slam_frob_result"]._fields_] == [("n", 0), ("trace", 4), ("one", 2)]
+
+
+def test_a_handle_closes_once_however_often_it_is_asked(L):
+    """close() is safe twice and on an object whose constructor raised before the handle existed; `with` closes."""
+    freed = []
+
+    class FakeLibrary:
+        slam_thing_destroy = staticmethod(freed.append)
+
+    class Thing(api._Handle):
+        _destroy, _library = "slam_thing_destroy", staticmethod(lambda: FakeLibrary)
+
+    with Thing() as t:
+        t.h = 1234
+    assert freed == [1234] and t.h is None
+    t.close()
+    t.__del__()
+    assert freed == [1234]
+    for cls in (api.Icp, api.CorrelativeMatcher, api.PoseGraph, api.VoxelMap, api.Grid, api.DistanceField, api.KeyframeStore,
+                api.MlsMap, api.Mapper, api.GroundSegmentation, api.Ccicp, api.Comm, api.Stream, api.Event):
+        assert issubclass(cls, api._Handle) and cls._destroy in api.EXPORTS + api.RCCL_EXPORTS, cls
+        assert "close" not in vars(cls) and "__del__" not in vars(cls), cls
+    half = object.__new__(api.Grid)          # what a constructor that raised before the handle existed leaves behind
+    half.close()
+    half.close()
+    if _no_gpu():
+        with pytest.raises(api.SlamError) as e:
+            half.__init__(100, 100, 0.1)
+        assert e.value.code == api.E_NO_DEVICE and not getattr(half, "h", None)
+        half.close()
+        half.close()
+        half.__del__()
+
+

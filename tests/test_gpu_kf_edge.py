@@ -259,15 +259,15 @@ def test_bad_arguments_are_error_codes(scene):
     req = (api.KfEdgeReq * 1)()
     res = (api.KfEdgeResult * 1)()
     req[0].from_, req[0].to = 0, len(K.EDGE_KS)
-    assert L.slam_kf_register_edges(h, C.addressof(req), 1, C.addressof(res), None) == api.E_INVALID
+    assert L.slam_kf_register_edges(h, req, 1, res, None) == api.E_INVALID
     assert b"names keyframes" in L.slam_last_error()
     req[0].from_, req[0].to = -1, 0
-    assert L.slam_kf_register_edges(h, C.addressof(req), 1, C.addressof(res), None) == api.E_INVALID
+    assert L.slam_kf_register_edges(h, req, 1, res, None) == api.E_INVALID
     req[0].from_ = 0
-    assert L.slam_kf_register_edges(h, None, 1, C.addressof(res), None) == api.E_INVALID
-    assert L.slam_kf_register_edges(h, C.addressof(req), 1, None, None) == api.E_INVALID
-    assert L.slam_kf_register_edges(None, C.addressof(req), 1, C.addressof(res), None) == api.E_INVALID
-    assert L.slam_kf_register_edges(h, C.addressof(req), 0, C.addressof(res), None) == api.SLAM_OK
+    assert L.slam_kf_register_edges(h, None, 1, res, None) == api.E_INVALID
+    assert L.slam_kf_register_edges(h, req, 1, None, None) == api.E_INVALID
+    assert L.slam_kf_register_edges(None, req, 1, res, None) == api.E_INVALID
+    assert L.slam_kf_register_edges(h, req, 0, res, None) == api.SLAM_OK
     kid = C.c_int()
     assert L.slam_kf_add_keyframe(h, None, 10, 3, C.byref(kid)) == api.E_INVALID
     assert L.slam_kf_add_keyframe(h, C.addressof(req), 10, 2, C.byref(kid)) == api.E_INVALID

@@ -168,7 +168,7 @@ def test_refusals_leave_everything_as_it_was():
     out = np.full((2, len(store)), -9, api.SC_MATCH_DTYPE)
     for queries in ([0, 2], [-1, 0], [0, 7]):
         q = np.array(queries, np.int32)
-        assert L.slam_kf_sc_match(store.h, q.ctypes.data_as(C.c_void_p), 2, out.ctypes.data_as(C.c_void_p), None) == api.E_INVALID
+        assert L.slam_kf_sc_match(store.h, q.ctypes.data_as(C.c_void_p), 2, out.ctypes.data_as(C.POINTER(api.KfScMatch)), None) == api.E_INVALID
     assert all((out[f] == -9).all() for f in out.dtype.names)
     assert refused(store.sc_compute, 2) and refused(store.sc_compute, -2)
     store.set_sc_params(**dict(p.dict(), n_rings=7))     # no descriptor yet: free to change

@@ -165,6 +165,8 @@ def test_rccl_library_exports_header_symbols():
     R = api.rccl_lib()
     for n in names:
         assert hasattr(R, n)
+        f = getattr(R, n)                                   # bound from the header, every one (tests/test_cabi_cpu.py checks the table)
+        assert (f.restype, list(f.argtypes)) == (api._H.functions[n][0], api._H.functions[n][1]), n
 
 
 @pytest.mark.gpu

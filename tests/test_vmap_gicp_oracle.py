@@ -298,19 +298,19 @@ def test_entry_points_without_a_device_and_argument_errors():
     assert L.slam_vmap_compute_distributions(None, None) == want
     assert L.slam_vmap_read_moments(None, p(out), p(out), p(out), 4, C.byref(n)) == want
     assert L.slam_vmap_read_distributions(None, None, None, None, None, None, p(out), 4, C.byref(n)) == want
-    assert L.slam_vmap_register_gicp(None, None, C.addressof(req), 1, None, C.addressof(res), None) == want
-    assert L.slam_vmap_register_gicp_traced(None, None, C.addressof(req), 1, None, C.addressof(res), p(tr), 8, None) == want
+    assert L.slam_vmap_register_gicp(None, None, req, 1, None, res, None) == want
+    assert L.slam_vmap_register_gicp_traced(None, None, req, 1, None, res, p(tr), 8, None) == want
     # broken arguments, whatever the machine
     assert L.slam_vmap_enable_distributions(None, C.byref(api.vmap_default_dist_params(epsilon=0.0))) == api.E_INVALID
     assert L.slam_vmap_enable_distributions(None, C.byref(api.vmap_default_dist_params(min_points=0))) == api.E_INVALID
     assert L.slam_vmap_read_moments(None, None, None, None, -1, C.byref(n)) == api.E_INVALID
     assert L.slam_vmap_read_moments(None, None, None, None, 0, None) == api.E_INVALID
     assert L.slam_vmap_read_distributions(None, None, None, None, None, None, None, -1, C.byref(n)) == api.E_INVALID
-    assert L.slam_vmap_register_gicp(None, None, C.addressof(req), -1, None, C.addressof(res), None) == api.E_INVALID
+    assert L.slam_vmap_register_gicp(None, None, req, -1, None, res, None) == api.E_INVALID
     assert b"slam_vmap_register_gicp" in L.slam_last_error()
-    assert L.slam_vmap_register_gicp(None, None, None, 1, None, C.addressof(res), None) == api.E_INVALID
-    assert L.slam_vmap_register_gicp(None, None, C.addressof(req), 1, None, None, None) == api.E_INVALID
+    assert L.slam_vmap_register_gicp(None, None, None, 1, None, res, None) == api.E_INVALID
+    assert L.slam_vmap_register_gicp(None, None, req, 1, None, None, None) == api.E_INVALID
     for bad in (dict(gate=0.0), dict(gate=-1.0), dict(max_iterations=0)):
         gp = api.vmap_default_gicp_params(**bad)
-        assert L.slam_vmap_register_gicp(None, None, C.addressof(req), 1, C.byref(gp), C.addressof(res), None) == api.E_INVALID, bad
-    assert L.slam_vmap_register_gicp_traced(None, None, C.addressof(req), 1, None, C.addressof(res), p(tr), 0, None) == api.E_INVALID
+        assert L.slam_vmap_register_gicp(None, None, req, 1, C.byref(gp), res, None) == api.E_INVALID, bad
+    assert L.slam_vmap_register_gicp_traced(None, None, req, 1, None, res, p(tr), 0, None) == api.E_INVALID

@@ -246,7 +246,7 @@ def calls(L, m, p, n=0, pts=None, stride=3, top=True):
     """the three forms with one set of arguments: their return codes"""
     hits, got = (api.VmapSearchHit * 4096)(), C.c_int(-1)
     store = np.zeros(64, np.uint64).ctypes.data_as(C.c_void_p)
-    tail = (C.byref(p), C.addressof(hits) if top else None, C.byref(got), None)
+    tail = (C.byref(p), hits if top else None, C.byref(got), None)
     return (L.slam_vmap_search_dev(m, pts, n, stride, *tail, None), L.slam_vmap_search(m, pts, n, stride, *tail),
             L.slam_vmap_search_keyframe(m, store, 0, *tail, None))
 
