@@ -12,6 +12,7 @@
 //
 // fromPlane / fromPlaneDev make a matcher whose table is a byte plane (docs/GRID_MATCH.md): a likelihood field computed from an
 // occupancy grid, a saved map.  slam_amd::GridMatcher (below) puts grid, field and such a matcher together.
+// slam_amd::ParticleFilter (at the end) keeps a belief between scans over a GridMatcher (docs/PARTICLE_FILTER.md).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -19,6 +20,7 @@
 #include <memory>
 #include <vector>
 
+#include "slam_amd/buffer.hpp"
 #include "slam_amd/icp.hpp"
 #include "slam_amd/mls.hpp"
 #include "slam_mi355x.h"
@@ -191,6 +193,7 @@ public:
     }
     const slam_csm_result &result() const { return last_; } // of the last match()
     bool                   valid() const { return h_ != nullptr; }
+    slam_csm_t            *handle() const { return h_; }
 
 private:
     slam_csm_t     *h_ = nullptr;
@@ -326,5 +329,163 @@ private:
     double                              cx_ = 0.0, cy_ = 0.0;
 };
 
+// ParticleFilter keeps a belief between scans over a GridMatcher (docs/PARTICLE_FILTER.md): the twin of
+// slam_amd.api.ParticleFilter over slam_pf_*.  Its update scores the particles against the grid's likelihood plane with the
+// matcher's own scorer and passes the centre of a rolling window, which GridMatcher::update keeps.
+//
+//     slam_amd::GridMatcher    gm(mls, 0.2);
+//     slam_amd::ParticleFilter pf(gm, 4096);                     // 4 096 particles, the other parameters at their defaults
+//     pf.initGaussian(x, y, k, 0.1, 0.1, 8.0);                   // around a start pose; k in heading steps of 2 pi / n_angles
+//     ... per scan:  gm.update();  pf.predict(motion);  pf.update(T_GA, T_NGA, tGA, tNGA);  pf.state(s);   // s.x, s.y, s.theta
+//
+// A failure logs the library's error and answers false; a failed construction leaves ok() == false.
+// The C-ABI takes the parameters as plain arguments, the motion as 48 bytes and gives the state back as two arrays
+// (slam_mi355x.h); these three carry them by name.
+struct PfParams {
+    int      n_particles, n_angles, gauss_bits, weight_len, weight_shift;
+    double   weight_scale;
+    int      resample_num, resample_den;
+    uint64_t seed;
+    PfParams()
+    {
+        slam_pf_default_params(&n_particles, &n_angles, &gauss_bits, &weight_len, &weight_shift, &weight_scale, &resample_num, &resample_den, &seed);
+    }
+};
+struct PfMotion { // the layout slam_pf_predict_dev reads on the device
+    double  dx, dy, sx, sy, sk;
+    int32_t dk, unused;
+};
+static_assert(sizeof(PfMotion) == SLAM_PF_MOTION_BYTES, "a motion is SLAM_PF_MOTION_BYTES on the device");
+struct PfState {
+    uint32_t t = 0;
+    int      n = 0, resampled = 0, degenerate = 0, best = -1, refused = 0;
+    int64_t  n_resamples = 0, A_max = 0;
+    uint64_t W = 0, S2 = 0;
+    int64_t  MX = 0, MY = 0, MC = 0, MS = 0;
+    double   x = 0.0, y = 0.0, theta = 0.0;
+};
+
+class ParticleFilter {
+public:
+    ParticleFilter(GridMatcher &gm, int n_particles, const PfParams *params = nullptr) : gm_(gm)
+    {
+        if (params) p_ = *params;
+        p_.n_particles = n_particles;
+        if (!gm.ok()) {
+            std::fprintf(stderr, "ParticleFilter: the grid matcher is not usable\n");
+            return;
+        }
+        if (slam_pf_create(p_.n_particles, p_.n_angles, p_.gauss_bits, p_.weight_len, p_.weight_shift, p_.weight_scale, p_.resample_num,
+                           p_.resample_den, p_.seed, &h_) != SLAM_OK) {
+            detail::warn("ParticleFilter");
+            h_ = nullptr;
+        }
+    }
+    ~ParticleFilter() { slam_pf_destroy(h_); }
+    ParticleFilter(const ParticleFilter &) = delete;
+    ParticleFilter &operator=(const ParticleFilter &) = delete;
+
+    bool                  ok() const { return h_ != nullptr; }
+    slam_pf_t            *handle() const { return h_; }
+    const PfParams        &params() const { return p_; }
+    int                   size() const { return p_.n_particles; }
+
+    // the host-made tables (no device is touched); each vector is sized here
+    static bool angleTable(int n_angles, std::vector<double> &cs)
+    {
+        cs.assign(n_angles > 0 && n_angles <= (1 << 16) ? 2 * (size_t)n_angles : 1, 0.0);
+        return done(slam_pf_angle_table(n_angles, cs.data(), (int)cs.size()));
+    }
+    static bool gaussTable(int bits, std::vector<double> &G)
+    {
+        G.assign(bits >= 0 && bits <= 16 ? (size_t)1 << bits : 1, 0.0);
+        return done(slam_pf_gauss_table(bits, G.data(), (int)G.size()));
+    }
+    static bool weightTable(double scale, int shift, int L, std::vector<uint32_t> &wtab)
+    {
+        wtab.assign(L > 0 && L <= (1 << 16) ? (size_t)L : 1, 0u);
+        return done(slam_pf_weight_table(scale, shift, L, wtab.data()));
+    }
+    // other tables of the right lengths; an empty vector leaves that table as it is
+    bool setTables(const std::vector<double> &cs, const std::vector<double> &G, const std::vector<uint32_t> &wtab)
+    {
+        return h_ && done(slam_pf_set_tables(h_, cs.empty() ? nullptr : cs.data(), (int)cs.size(), G.empty() ? nullptr : G.data(), (int)G.size(),
+                                             wtab.empty() ? nullptr : wtab.data(), (int)wtab.size()));
+    }
+    bool setParticles(const std::vector<double> &x, const std::vector<double> &y, const std::vector<int32_t> &k)
+    {
+        if (!h_ || x.size() != y.size() || x.size() != k.size()) return false;
+        return done(slam_pf_set_particles(h_, x.data(), y.data(), k.data(), (int)x.size()));
+    }
+    bool particles(std::vector<double> &x, std::vector<double> &y, std::vector<int32_t> &k)
+    {
+        if (!h_) return false;
+        x.assign((size_t)size(), 0.0), y.assign((size_t)size(), 0.0), k.assign((size_t)size(), 0);
+        return done(slam_pf_read_particles(h_, x.data(), y.data(), k.data()));
+    }
+    bool weights(std::vector<int64_t> &acc, std::vector<uint32_t> &w)
+    {
+        if (!h_) return false;
+        acc.assign((size_t)size(), 0), w.assign((size_t)size(), 0u);
+        return done(slam_pf_read_weights(h_, acc.data(), w.data()));
+    }
+    bool initGaussian(double x, double y, int k, double sx, double sy, double sk) { return h_ && done(slam_pf_init_gaussian(h_, x, y, k, sx, sy, sk)); }
+    // the motion model: host form (an invalid motion is refused, logged) and device form (the motion is read on the device)
+    bool predict(const PfMotion &m) { return h_ && done(slam_pf_predict(h_, m.dx, m.dy, m.sx, m.sy, m.sk, m.dk)); }
+    bool predictDev(const PfMotion *d_motion, slam_stream_t stream = nullptr) { return h_ && done(slam_pf_predict_dev(h_, d_motion, stream)); }
+    // the measurement step against the grid's plane as GridMatcher::update left it; the rolling centre is the matcher's
+    bool update(const double *T_GA, const double *T_NGA, const int32_t T_GA_num, const int32_t T_NGA_num)
+    {
+        if (!h_ || !gm_.ok() || T_GA_num < 0 || T_NGA_num < 0) return false;
+        std::vector<double> pts;
+        pts.reserve(2 * ((size_t)T_GA_num + T_NGA_num));
+        pts.insert(pts.end(), T_GA, T_GA + 2 * (size_t)T_GA_num);
+        pts.insert(pts.end(), T_NGA, T_NGA + 2 * (size_t)T_NGA_num);
+        double cx, cy;
+        gm_.centre(cx, cy);
+        return done(slam_pf_update(h_, gm_.matcher().handle(), pts.data(), T_GA_num + T_NGA_num, T_GA_num, cx, cy));
+    }
+    // d_pts: n points on the device, the first n_ga of class GA; enqueued on `stream`, waits for nothing
+    bool updateDev(const double *d_pts, int n, int n_ga, slam_stream_t stream = nullptr)
+    {
+        if (!h_ || !gm_.ok()) return false;
+        double cx, cy;
+        gm_.centre(cx, cy);
+        return done(slam_pf_update_dev(h_, gm_.matcher().handle(), d_pts, n, n_ga, cx, cy, stream));
+    }
+    // the resampling rule alone: src[j] = min { i : C_i n > j W + (r mod W) } over w.size() <= size() weights
+    bool resampleIndices(const std::vector<uint32_t> &w, uint64_t r, std::vector<int32_t> &src)
+    {
+        if (!h_ || w.empty()) return false;
+        detail::DeviceBuffer d_w, d_src;
+        src.assign(w.size(), 0);
+        if (!d_w.alloc(sizeof(uint32_t) * w.size()) || !d_src.alloc(sizeof(int32_t) * w.size())) return done(SLAM_E_NOMEM);
+        return done(slam_memcpy_h2d(d_w.p, w.data(), d_w.cap, nullptr)) &&
+               done(slam_pf_resample_indices_dev(h_, d_w.as<uint32_t>(), (int)w.size(), r, d_src.as<int32_t>(), nullptr)) &&
+               done(slam_memcpy_d2h(src.data(), d_src.p, d_src.cap, nullptr));
+    }
+    // the counter, the last update's sums and flags, and the estimate (x, y, theta); waits
+    bool state(PfState &s)
+    {
+        int64_t v[SLAM_PF_STATE_INTS];
+        double  e[3];
+        if (!h_ || !done(slam_pf_read_state(h_, v, e))) return false;
+        s.t = (uint32_t)v[0], s.n = (int)v[1], s.resampled = (int)v[2], s.degenerate = (int)v[3], s.best = (int)v[4], s.refused = (int)v[5];
+        s.n_resamples = v[6], s.A_max = v[7], s.W = (uint64_t)v[8], s.S2 = (uint64_t)v[9], s.MX = v[10], s.MY = v[11], s.MC = v[12], s.MS = v[13];
+        s.x = e[0], s.y = e[1], s.theta = e[2];
+        return true;
+    }
+
+private:
+    static bool done(int rc)
+    {
+        if (rc != SLAM_OK) detail::warn("ParticleFilter");
+        return rc == SLAM_OK;
+    }
+
+    GridMatcher   &gm_;
+    PfParams       p_;
+    slam_pf_t     *h_ = nullptr;
+};
 
 } // namespace slam_amd

@@ -1020,6 +1020,115 @@ int  slam_csm_match_post(slam_csm_t *csm, const double *t_ga, int n_tga, const d
                          slam_csm_result *result, slam_csm_posterior *post);
 
 /* -------------------------------------------------------------------------
+ * Monte Carlo localisation over a grid matcher (docs/PARTICLE_FILTER.md): a particle filter whose likelihood step is
+ * slam_csm_score_poses_dev as it stands.  The reference has no such filter (its ekf package fuses the scan matcher's pose), and
+ * parity with AMCL or any outside filter is not claimed: the yardstick is the numpy restatement of tests/pf_cases.py, which
+ * the device equals bit for bit, random numbers included.  Behind three host-made tables everything is integer or singly
+ * rounded f64:
+ *   state     per particle x, y (f64, world metres), k (int32 heading index in [0, A)), acc (int64 log-weight), as a
+ *             structure of arrays on the device; the step counter t lives on the device too, so that a replayed graph advances it
+ *   random    Philox-4x32-10, stateless: key = (low, high half of seed), counter = (p, t, purpose, 0); purpose 0 = predict,
+ *             1 = init, 2 = the resampling offset (p = 0)
+ *   limits    1 <= n_particles <= 2^18 and weights <= 2^16, chosen so that every integer sum below fits 64 bits:
+ *             W < 2^35, S2 < 2^51, |MX|, |MY| < 2^63 (|q| < 2^29), |MC|, |MS| < 2^59, and C_i n, j W + r < 2^54
+ * ---------------------------------------------------------------------- */
+typedef struct slam_pf slam_pf_t;
+
+/* The parameters are plain arguments, in this order wherever they appear (defaults in brackets):
+ *   n_particles   1 .. 2^18 (1024)
+ *   n_angles      A: headings per turn, a power of two from 2^6 to 2^16 (4096)
+ *   gauss_bits    b: the Gaussian table has 2^b entries, 4 .. 16 (12)
+ *   weight_len    L: entries of the weight table, 2 .. 65536 (1024)
+ *   weight_shift  a weight is looked up at (A_max - acc) >> weight_shift, 0 .. 14 (4)
+ *   weight_scale  the weight at deficit d is exp(-d / weight_scale); positive and finite (1024.0)
+ *   resample_num  resample iff N_eff < (num / den) n; 0 never, num > den always; 0 .. 65535 (1)
+ *   resample_den  1 .. 65535 (2)
+ *   seed          the Philox key (1)
+ * A motion on the device is 48 bytes: five f64 and one int32 (then four unused bytes),
+ *   dx, dy        the odometry increment in the particle's own frame, metres
+ *   sx, sy        standard deviations of its noise, metres; finite, >= 0
+ *   sk            standard deviation of the heading noise in heading steps; finite, 0 <= sk < 2^20
+ *   dk (int32)    the heading increment in heading steps, |dk| < 2^20
+ * The state read back is SLAM_PF_STATE_INTS int64 and three f64:
+ *   ints[0] t            the step counter: predicts done (mod 2^32)
+ *   ints[1] n            n_particles
+ *   ints[2] resampled    the last update resampled
+ *   ints[3] degenerate   the last update found no finite particle: nothing moved, every sum is 0, best is -1
+ *   ints[4] best         the lowest index whose acc reached A_max (before a resample zeroed it)
+ *   ints[5] refused      motions slam_pf_predict_dev found invalid on the device and skipped (the step did not advance)
+ *   ints[6] n_resamples  updates that resampled since creation
+ *   ints[7] A_max        the largest acc among the finite particles
+ *   ints[8] W, [9] S2    sum w, sum w^2
+ *   ints[10] MX, [11] MY sum w q(x), sum w q(y); q(v) = llrint(65536 v) saturated to +-(2^29 - 1)
+ *   ints[12] MC, [13] MS sum w llrint(2^24 cos), sum w llrint(2^24 sin) of the heading
+ *   est[0..2]            the estimate x, y, theta, formed on the host: MX / (W 65536), MY / (W 65536), atan2(MS, MC); NaN when W = 0 */
+#define SLAM_PF_STATE_INTS 14
+#define SLAM_PF_MOTION_BYTES 48
+
+/* the defaults above; each pointer nullable */
+void slam_pf_default_params(int *n_particles, int *n_angles, int *gauss_bits, int *weight_len, int *weight_shift, double *weight_scale,
+                            int *resample_num, int *resample_den, uint64_t *seed);
+/* The table makers (slam_amd/csrc/pf_tables.hpp; host only, no device is touched).  SLAM_E_INVALID and nothing written:
+ *   angle   n_angles not a power of two in 2^6 .. 2^16, n != 2 n_angles.  cs[2 k], cs[2 k + 1] = cos, sin(2 pi k / n_angles);
+ *           the four quadrant entries are exactly (+-1, 0) and (0, +-1)
+ *   gauss   bits outside 4 .. 16, n != 2^bits.  G[i] = Phi^-1((i + 1/2) / 2^bits); G[i] == -G[2^bits - 1 - i] exactly.  No bit
+ *           contract against any library: |Phi(G[i]) - (i + 1/2) / 2^bits| <= 1e-12
+ *   weight  L outside 2 .. 65536, shift outside 0 .. 14, a scale that is not positive and finite.
+ *           wtab[j] = (uint32_t)rint(65536 exp(-(double)(j << shift) / scale)); wtab[0] == 65536 and no entry above it */
+int  slam_pf_angle_table(int n_angles, double *cs, int n);
+int  slam_pf_gauss_table(int bits, double *G, int n);
+int  slam_pf_weight_table(double scale, int shift, int L, uint32_t *wtab);
+/* A filter with the three tables made from its parameters; the particles are all at (0, 0, 0) with acc 0, t = 0.  Every
+ * refusal of a parameter is SLAM_E_INVALID before a device is touched. */
+int  slam_pf_create(int n_particles, int n_angles, int gauss_bits, int weight_len, int weight_shift, double weight_scale, int resample_num,
+                    int resample_den, uint64_t seed, slam_pf_t **out);
+void slam_pf_destroy(slam_pf_t *pf);
+/* Other tables of the right lengths (2 n_angles, 2^gauss_bits, weight_len); a null table stays as it is.  cs and G must be
+ * finite, wtab[0] == 65536 with no entry above it.  Synchronous. */
+int  slam_pf_set_tables(slam_pf_t *pf, const double *cs, int n_cs, const double *G, int n_G, const uint32_t *wtab, int n_w);
+/* Particles from and to the host, n == n_particles, synchronous.  set: every k in [0, A), every acc becomes 0 (x, y may be
+ * non-finite: such a particle takes no part in an update).  read: each array nullable. */
+int  slam_pf_set_particles(slam_pf_t *pf, const double *x, const double *y, const int32_t *k, int n);
+int  slam_pf_read_particles(slam_pf_t *pf, double *x, double *y, int32_t *k);
+/* acc (int64) and the weights w (uint32) of the last update, each nullable; synchronous */
+int  slam_pf_read_weights(slam_pf_t *pf, int64_t *acc, uint32_t *w);
+/* The step counter, the last update's sums and flags, and the estimate; synchronous */
+int  slam_pf_read_state(slam_pf_t *pf, int64_t ints[SLAM_PF_STATE_INTS], double est[3]);
+/* Debug: d_words[4 i ..] = the four Philox words of counter (p0 + i, t, purpose, 0), i < n <= 2^20, under the filter's key.
+ * Enqueued on the null stream. */
+int  slam_pf_random_words_dev(slam_pf_t *pf, uint32_t p0, int n, uint32_t t, uint32_t purpose, uint32_t *d_words);
+/* The motion model.  With (w0 .. w3) the particle's words of purpose 0, g(w) = G[w >> (32 - b)] and c, s = cs[k] of the OLD
+ * heading, every product and sum rounded on its own:
+ *     ex = dx + sx g(w0)          x' = x + (c ex - s ey)
+ *     ey = dy + sy g(w1)          y' = y + (s ex + c ey)          k' = (k + dk + (int)rint(sk g(w2))) mod A
+ * and t advances by one at the end.  The motion is read from the device, so that a graph can be fed new odometry; one that
+ * breaks the motion's rules above is found on the device: nothing moves, t stays, and the state's `refused` counts it.
+ * Asynchronous on `stream`; allocates, frees and waits for nothing.  One call at a time per handle. */
+int  slam_pf_predict_dev(slam_pf_t *pf, const void *d_motion, slam_stream_t stream);
+/* the same from the host: an invalid motion is SLAM_E_INVALID before a device is touched; stages and waits */
+int  slam_pf_predict(slam_pf_t *pf, double dx, double dy, double sx, double sy, double sk, int dk);
+/* Every particle becomes the pose (x, y, k) moved by the motion {0, 0, sx, sy, sk, 0} drawn with purpose 1 at the current t
+ * (the noise lies in the pose's own frame); acc = 0; t stays.  Synchronous. */
+int  slam_pf_init_gaussian(slam_pf_t *pf, double x, double y, int k, double sx, double sy, double sk);
+/* The measurement step against a matcher's table, the scan as for slam_csm_score_poses_dev (n <= 2^23 points, the first n_ga
+ * of class GA); (cx, cy), finite, is the centre of the matcher's window in the world frame.  In order:
+ *   1  poses (c, s, x - cx, y - cy) per particle          2  slam_csm_score_poses_dev as it is          3  acc += score
+ *   4  a particle whose x or y is not finite takes no part and has weight 0; A_max = max acc over the others, best = the
+ *      lowest index that reaches it
+ *   5  w_p = wtab[min((A_max - acc_p) >> shift, L - 1)]   6  the sums of the state
+ *   7  resample iff W W den < num n S2 (128-bit); no finite particle: degenerate, nothing moves
+ *   8  when decided: r = ((w0 << 32) | w1) mod W from purpose 2 at the current t, C_i = the inclusive prefix sum of w, output j
+ *      copies x, y, k of src(j) = min { i : C_i n > j W + r }, every acc becomes 0; when not decided nothing changes.
+ * Asynchronous on `stream`; allocates, frees and waits for nothing; a graph may capture predict + update.  One call at a
+ * time per handle and per matcher. */
+int  slam_pf_update_dev(slam_pf_t *pf, slam_csm_t *csm, const double *d_pts, int n, int n_ga, double cx, double cy, slam_stream_t stream);
+/* the same on host points: stages and waits */
+int  slam_pf_update(slam_pf_t *pf, slam_csm_t *csm, const double *pts, int n, int n_ga, double cx, double cy);
+/* The resampling rule alone: d_src[j] = min { i : C_i n > j W + (r mod W) } for j < n, from n <= n_particles weights
+ * (uint32; one above 65536 is read as 65536).  W = 0: d_src[j] = j.  Shares the filter's scratch.  Asynchronous. */
+int  slam_pf_resample_indices_dev(slam_pf_t *pf, const uint32_t *d_w, int n, uint64_t r, int32_t *d_src, slam_stream_t stream);
+
+/* -------------------------------------------------------------------------
  * Exact sparse voxel map: the growing prior map of global_generate.cpp (the reference keeps it as a point cloud that is
  * voxel-filtered again every round, global_generate.cpp:122-232).  Clouds are integrated in place into an open-addressing
  * table in HBM; a voxel holds a point count and three integer sums of the coordinates in units of 2^-20 m, so the map of a

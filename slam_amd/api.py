@@ -106,6 +106,12 @@ CSM_POST_DTYPE = np.dtype([(f, np.int32) for f, _ in CsmPosterior._fields_[:8]] 
                           [("m0", np.int64), ("m1", np.int64, (3,)), ("m2", np.int64, (6,)), ("mean", np.float64, (3,)),
                            ("cov", np.float64, (6,))])
 
+# one motion in a device buffer, as slam_pf_predict_dev reads it there: SLAM_PF_MOTION_BYTES
+PF_MOTION_DTYPE = np.dtype({"names": ["dx", "dy", "sx", "sy", "sk", "dk"], "formats": ["<f8"] * 5 + ["<i4"], "offsets": [0, 8, 16, 24, 32, 40],
+                            "itemsize": _D["SLAM_PF_MOTION_BYTES"]})
+PF_PARAMS = ("n_particles", "n_angles", "gauss_bits", "weight_len", "weight_shift", "weight_scale", "resample_num", "resample_den", "seed")
+PF_STATE_INTS = ("t", "n", "resampled", "degenerate", "best", "refused", "n_resamples", "A_max", "W", "S2", "MX", "MY", "MC", "MS")
+
 KF_LATTICE_MARGIN = 1.0 + 2.0 ** -16   # the search lattice's edge is cell_size (or the gate) times this
 
 RESULT_DTYPE = np.dtype([("iters", np.int32), ("n_corr", np.int32), ("delta", np.float64)])
@@ -1423,11 +1429,168 @@ class GridMatcher:
         self.matcher.set_window(self.grid.size_x // 2, self.grid.size_y // 2, half_theta, theta_step)
         return self.match(t_ga, t_nga, np.eye(2), np.asarray(self.centre, np.float64))
 
+    def particle_filter(self, n, params=None, **kw):
+        """A ParticleFilter of n particles bound to this matcher: its update scores against the grid's plane, at the grid's
+        resolution, and passes the rolling centre (docs/PARTICLE_FILTER.md)"""
+        return ParticleFilter(n, params, matcher=self, **kw)
+
     def close(self):
         for o in (getattr(self, "matcher", None), getattr(self, "field", None)):
             if o is not None:
                 o.close()
         self.matcher = self.field = None
+
+
+class PfParams:
+    """the particle filter's parameters by name, in the order the C-ABI takes them (PF_PARAMS)"""
+
+    def __init__(self, **kw):
+        c = [C.c_double() if n == "weight_scale" else C.c_uint64() if n == "seed" else C.c_int() for n in PF_PARAMS]
+        lib().slam_pf_default_params(*(C.byref(v) for v in c))
+        for n, v in zip(PF_PARAMS, c):
+            setattr(self, n, v.value)
+        for n, v in kw.items():
+            if n not in PF_PARAMS:
+                raise TypeError("no particle filter parameter %r" % n)
+            setattr(self, n, v)
+
+    def args(self):
+        return [float(self.weight_scale) if n == "weight_scale" else int(getattr(self, n)) for n in PF_PARAMS]
+
+
+class PfState:
+    """what slam_pf_read_state returns, by name: PF_STATE_INTS as int, and the estimate x, y, theta"""
+
+    def __init__(self, ints, est):
+        for n, v in zip(PF_STATE_INTS, ints):
+            setattr(self, n, int(v))
+        self.x, self.y, self.theta = (float(v) for v in est)
+
+
+def pf_default_params(**kw):
+    return PfParams(**kw)
+
+
+def pf_angle_table(n_angles):
+    """np.float64[2 n_angles]: cos, sin(2 pi k / n_angles), the quadrants exact (slam_pf_angle_table; host only)"""
+    cs = np.zeros(2 * max(int(n_angles), 0), np.float64)
+    check(lib().slam_pf_angle_table(int(n_angles), _ptr(cs), len(cs)))
+    return cs
+
+
+def pf_gauss_table(bits):
+    """np.float64[2^bits]: the standard normal quantiles of (i + 1/2) / 2^bits (slam_pf_gauss_table; host only)"""
+    G = np.zeros(1 << min(max(int(bits), 0), 20), np.float64)
+    check(lib().slam_pf_gauss_table(int(bits), _ptr(G), len(G)))
+    return G
+
+
+def pf_weight_table(scale, shift, L):
+    """np.uint32[L]: rint(65536 exp(-(j << shift) / scale)) (slam_pf_weight_table; host only)"""
+    w = np.zeros(min(max(int(L), 1), 1 << 20), np.uint32)
+    check(lib().slam_pf_weight_table(float(scale), int(shift), int(L), _ptr(w)))
+    return w
+
+
+class ParticleFilter(_Handle):
+    """Monte Carlo localisation over a grid matcher (slam_pf_*, docs/PARTICLE_FILTER.md).  matcher: a GridMatcher (update
+    then passes its rolling centre) or a CorrelativeMatcher (centre 0, 0), or None: update takes one."""
+    _destroy = "slam_pf_destroy"
+
+    def __init__(self, n=None, params=None, matcher=None, **kw):
+        self.params = params or pf_default_params(**kw)
+        if n is not None:
+            self.params.n_particles = int(n)
+        self.matcher = matcher
+        h = _vp()
+        check(lib().slam_pf_create(*self.params.args(), C.byref(h)))
+        self.h = h.value
+        self.n = self.params.n_particles
+        self._motion = None
+
+    def tables(self):
+        """the tables a filter of these parameters is created with: (cs, G, wtab)"""
+        p = self.params
+        return pf_angle_table(p.n_angles), pf_gauss_table(p.gauss_bits), pf_weight_table(p.weight_scale, p.weight_shift, p.weight_len)
+
+    def set_tables(self, cs=None, G=None, wtab=None):
+        cs = None if cs is None else np.ascontiguousarray(cs, np.float64).ravel()
+        G = None if G is None else np.ascontiguousarray(G, np.float64).ravel()
+        wtab = None if wtab is None else np.ascontiguousarray(wtab, np.uint32).ravel()
+        check(lib().slam_pf_set_tables(self.h, *(v for a in (cs, G, wtab) for v in ((None, 0) if a is None else (a.ctypes.data_as(_vp), len(a))))))
+
+    def set_particles(self, x, y, k):
+        x, y, k = np.ascontiguousarray(x, np.float64), np.ascontiguousarray(y, np.float64), np.ascontiguousarray(k, np.int32)
+        assert len(x) == len(y) == len(k)
+        check(lib().slam_pf_set_particles(self.h, _ptr(x), _ptr(y), _ptr(k), len(x)))
+
+    def particles(self):
+        """(x f64 [n], y f64 [n], k int32 [n])"""
+        x, y, k = np.empty(self.n, np.float64), np.empty(self.n, np.float64), np.empty(self.n, np.int32)
+        check(lib().slam_pf_read_particles(self.h, _ptr(x), _ptr(y), _ptr(k)))
+        return x, y, k
+
+    def weights(self):
+        """(acc int64 [n], w uint32 [n]) as the last update left them"""
+        acc, w = np.empty(self.n, np.int64), np.empty(self.n, np.uint32)
+        check(lib().slam_pf_read_weights(self.h, _ptr(acc), _ptr(w)))
+        return acc, w
+
+    def state(self):
+        ints, est = np.zeros(_D["SLAM_PF_STATE_INTS"], np.int64), np.zeros(3, np.float64)
+        check(lib().slam_pf_read_state(self.h, _ptr(ints), _ptr(est)))
+        return PfState(ints, est)
+
+    def random_words(self, p0, n, t, purpose):
+        """[n, 4] uint32: the device's Philox words of counters (p0 + i, t, purpose, 0)"""
+        d = DeviceArray((max(int(n), 1), 4), np.uint32)
+        check(lib().slam_pf_random_words_dev(self.h, int(p0), int(n), int(t), int(purpose), d.ptr))
+        return d.download()[:int(n)]
+
+    def init_gaussian(self, x, y, k, sx, sy, sk):
+        check(lib().slam_pf_init_gaussian(self.h, float(x), float(y), int(k), float(sx), float(sy), float(sk)))
+
+    @staticmethod
+    def motion(dx, dy, sx, sy, sk, dk):
+        """one motion as a host array of PF_MOTION_DTYPE, ready for a device buffer"""
+        return np.array([(float(dx), float(dy), float(sx), float(sy), float(sk), int(dk))], PF_MOTION_DTYPE)
+
+    def predict(self, motion):
+        """motion: (dx, dy, sx, sy, sk, dk); synchronous"""
+        dx, dy, sx, sy, sk, dk = motion
+        check(lib().slam_pf_predict(self.h, float(dx), float(dy), float(sx), float(sy), float(sk), int(dk)))
+
+    def predict_dev(self, d_motion, stream=None):
+        """d_motion: a device buffer holding one motion (PF_MOTION_DTYPE)"""
+        check(lib().slam_pf_predict_dev(self.h, getattr(d_motion, "ptr", d_motion), _sp(stream)))
+
+    def _centre(self, matcher, centre):
+        """(the CorrelativeMatcher, the window's centre): a GridMatcher brings its own centre, anything else has (0, 0)
+        unless `centre` says otherwise"""
+        m = matcher if matcher is not None else self.matcher
+        if isinstance(m, GridMatcher):
+            return m.matcher, (m.centre if centre is None else centre)
+        return m, ((0.0, 0.0) if centre is None else centre)
+
+    def update(self, t_ga, t_nga, matcher=None, centre=None):
+        """slam_pf_update, host arrays; returns state()"""
+        pts = np.ascontiguousarray(np.concatenate([np.reshape(t_ga, (-1, 2)), np.reshape(t_nga, (-1, 2))]), dtype=np.float64)
+        m, c = self._centre(matcher, centre)
+        check(lib().slam_pf_update(self.h, m.h, _ptr(pts), len(pts), len(np.reshape(t_ga, (-1, 2))), float(c[0]), float(c[1])))
+        return self.state()
+
+    def update_dev(self, d_pts, n, n_ga, matcher=None, centre=None, stream=None):
+        m, c = self._centre(matcher, centre)
+        check(lib().slam_pf_update_dev(self.h, m.h, getattr(d_pts, "ptr", d_pts), int(n), int(n_ga), float(c[0]), float(c[1]), _sp(stream)))
+
+    def resample_indices(self, w, r, stream=None):
+        """the resampling rule alone over uint32 weights (len(w) <= n): src int32 [len(w)]"""
+        w = np.ascontiguousarray(w, np.uint32)
+        d_w, d_src = DeviceArray.from_host(w), DeviceArray((len(w),), np.int32)
+        check(lib().slam_pf_resample_indices_dev(self.h, d_w.ptr, len(w), int(r), d_src.ptr, _sp(stream)))
+        if stream is not None:
+            stream.synchronize()
+        return d_src.download()
 
 
 def mls_default_params(**kw):
