@@ -141,6 +141,100 @@ private:
     size_t            cells_ = 0;
 };
 
+// A path down a navigation field (slam_gnav_*, docs/GRID_NAV.md; the reference has no planner): window cells (x, y) from the
+// start to the goal, the same cells as world points at their centres, and the status of slam_mi355x.h: 0 reached a goal, 1 the
+// start is outside the plane, closed or unreachable, 2 cut at max_len, 3 the field is not converged.
+struct NavPath {
+    int                  status = 3;
+    std::vector<int32_t> cells;  // 2 per cell
+    std::vector<double>  points; // 2 per cell
+};
+
+// RAII over slam_gnav_t.  A failed construction logs and leaves an unusable object (ok() == false), as the other adapters do.
+class NavField {
+public:
+    NavField(int size_x, int size_y, int orth_w = 12, int diag_w = 17)
+    {
+        if (slam_gnav_create(size_x, size_y, orth_w, diag_w, &h_) != SLAM_OK) {
+            std::fprintf(stderr, "%s\n", slam_last_error());
+            h_ = nullptr;
+            return;
+        }
+        cells_ = (size_t)size_x * size_y;
+    }
+    ~NavField()
+    {
+        slam_device_synchronize(); // (the goal block goes with its member, behind this wait)
+        slam_gnav_destroy(h_);
+    }
+    NavField(const NavField &) = delete;
+    NavField &operator=(const NavField &) = delete;
+
+    bool ok() const { return h_ != nullptr; }
+    bool setTable(const std::vector<uint32_t> &table) { return h_ && good(slam_gnav_set_table(h_, table.data(), (int)table.size())); }
+    // the default curve: neutral + cost below lethal_from, closed from there on, unknown cells (255) at unknown_step (0: closed)
+    bool setSteps(int neutral, int lethal_from, int unknown_step)
+    {
+        std::vector<uint32_t> t(256);
+        return h_ && good(slam_grid_step_table(neutral, lethal_from, unknown_step, t.data(), (int)t.size())) && setTable(t);
+    }
+    // host plane and host goals (x, y pairs), to convergence
+    bool compute(const uint8_t *cost, const std::vector<int32_t> &goals, int max_rounds = 0)
+    {
+        return h_ && good(slam_gnav_compute(h_, cost, goals.data(), (int)(goals.size() / 2), max_rounds));
+    }
+    bool computeDev(const uint8_t *d_cost, const int32_t *d_goals, int n_goals, int rounds, bool restart, slam_stream_t stream)
+    {
+        return h_ && good(slam_gnav_compute_dev(h_, d_cost, d_goals, n_goals, rounds, restart ? 1 : 0, stream));
+    }
+    // over the cost plane of a distance field computed on `grid`, to convergence: rounds in batches, the state read per batch
+    bool computeFromGrid(slam_grid_t *grid, DistanceField &df, const std::vector<int32_t> &goals)
+    {
+        const int n = (int)(goals.size() / 2), batch = 16;
+        if (!h_ || !grid || !df.ok() || n < 1 || !d_goals_.reserve(sizeof(int32_t) * goals.size())) return false;
+        if (!good(slam_memcpy_h2d(d_goals_.p, goals.data(), sizeof(int32_t) * 2 * (size_t)n, nullptr))) return false;
+        if (!good(slam_grid_nav_field(grid, df.handle(), h_, d_goals_.as<int32_t>(), n, batch, nullptr))) return false;
+        for (size_t done = batch;; done += batch) {
+            int64_t st[SLAM_GNAV_STATE_INTS];
+            if (!good(slam_gnav_read_state(h_, st))) return false;
+            if (st[1]) return true;
+            if (done > cells_) return false; // (cells + 1 rounds always suffice)
+            uint8_t *d_cost = nullptr;
+            if (!good(slam_gdist_planes_dev(df.handle(), nullptr, &d_cost)) || !d_cost) return false;
+            if (!computeDev(d_cost, d_goals_.as<int32_t>(), n, batch, false, nullptr)) return false;
+        }
+    }
+    bool read(std::vector<uint32_t> *pot)
+    {
+        if (!h_ || !pot) return false;
+        pot->resize(cells_);
+        return good(slam_gnav_read(h_, pot->data()));
+    }
+    // window cells from (sx, sy) down the field; max_len 0: the plane's cell count, which no path exceeds
+    bool path(int sx, int sy, std::vector<int32_t> *cells, int *status, int max_len = 0)
+    {
+        if (!h_ || !cells || !status) return false;
+        const size_t room = max_len > 0 ? (size_t)max_len : cells_;
+        cells->resize(2 * room);
+        int len = 0;
+        if (!good(slam_gnav_path(h_, sx, sy, (int)room, cells->data(), &len, status))) return false;
+        cells->resize(2 * (size_t)len);
+        return true;
+    }
+    bool state(int64_t ints[SLAM_GNAV_STATE_INTS]) { return h_ && good(slam_gnav_read_state(h_, ints)); }
+    slam_gnav_t *handle() { return h_; }
+
+private:
+    static bool good(int rc)
+    {
+        if (rc != SLAM_OK) std::fprintf(stderr, "%s\n", slam_last_error());
+        return rc == SLAM_OK;
+    }
+    slam_gnav_t         *h_ = nullptr;
+    size_t               cells_ = 0;
+    detail::DeviceBuffer d_goals_;
+};
+
 class MLS {
 public:
     // mls.h:154: MLS(int size_x_, int size_y_, double res, bool roll, double robot_size = 1.45)
@@ -374,6 +468,61 @@ public:
         }
         return costmap_;
     }
+    // Opt-in planner over the costmap (not in the reference): needs enableCostmap first.  Moves cost orth_w / diag_w times the
+    // sum of the two cells' steps; a cell's step is neutral + its cost byte, cells from lethal_from on are closed, unknown cells
+    // (255) take unknown_step (0: closed).  false (logged) when the arguments or the device refuse.
+    bool enablePlanner(int orth_w = 12, int diag_w = 17, int neutral = 50, int lethal_from = 253, int unknown_step = 0)
+    {
+        if (!h_ || !df_) return false;
+        std::unique_ptr<NavField> nav(new NavField((int)grid_.info.width, (int)grid_.info.height, orth_w, diag_w));
+        if (!nav->ok() || !nav->setSteps(neutral, lethal_from, unknown_step)) return false;
+        nav_ = std::move(nav);
+        return true;
+    }
+    // The window cell of a world point, by the grid's own binning (mls.cpp:77-78, grid_cell.hpp): with p the point in the window's
+    // frame -- the world point minus the grid's pose when the map rolls, the world point itself otherwise -- stored as a float
+    // as the clouds are, cell = (int)(p / resolution + size / 2), truncated toward zero, size / 2 the integer half.  false when
+    // the cell lies outside the plane.  cellCentre is its inverse on the cell centres.
+    bool worldToCell(double wx, double wy, int *cx, int *cy) const
+    {
+        double px = 0, py = 0;
+        if (h_ && rolling_) slam_grid_get_pose(h_, &px, &py);
+        const int    sx = (int)grid_.info.width, sy = (int)grid_.info.height;
+        const double fx = (double)(float)(wx - px) / grid_.info.resolution + (double)(sx / 2);
+        const double fy = (double)(float)(wy - py) / grid_.info.resolution + (double)(sy / 2);
+        if (!(fx > -2147483648.0 && fx < 2147483648.0 && fy > -2147483648.0 && fy < 2147483648.0)) return false;
+        *cx = (int)fx, *cy = (int)fy;
+        return *cx >= 0 && *cy >= 0 && *cx < sx && *cy < sy;
+    }
+    void cellCentre(int cx, int cy, double *wx, double *wy) const
+    {
+        double px = 0, py = 0;
+        if (h_ && rolling_) slam_grid_get_pose(h_, &px, &py);
+        *wx = ((double)(cx - (int)grid_.info.width / 2) + 0.5) * grid_.info.resolution + px;
+        *wy = ((double)(cy - (int)grid_.info.height / 2) + 0.5) * grid_.info.resolution + py;
+    }
+    // getCostmap()'s plane -> slam_grid_nav_field from the goal's cell, to convergence -> slam_gnav_path from the start's
+    // cell.  World points in, world points at cell centres out; status 1 with no cells when either point lies outside the
+    // window, 3 before enablePlanner or when the device refuses.
+    NavPath planPath(double from_x, double from_y, double to_x, double to_y)
+    {
+        NavPath out;
+        if (!(h_ && df_ && nav_)) return out;
+        int sx, sy, gx, gy;
+        if (!worldToCell(from_x, from_y, &sx, &sy) || !worldToCell(to_x, to_y, &gx, &gy)) {
+            out.status = 1;
+            return out;
+        }
+        if (!(df_->computeFromGrid(h_) && nav_->computeFromGrid(h_, *df_, {gx, gy}) && nav_->path(sx, sy, &out.cells, &out.status))) {
+            out.status = 3;
+            out.cells.clear();
+            return out;
+        }
+        out.points.resize(out.cells.size());
+        for (size_t i = 0; i + 1 < out.cells.size(); i += 2) cellCentre(out.cells[i], out.cells[i + 1], &out.points[i], &out.points[i + 1]);
+        return out;
+    }
+    NavField *planner() { return nav_.get(); }
     void setMinClusterPoints(double v) { if (h_) slam_grid_set_min_cluster_points(h_, (int)v); } // mls.h:235
     void setMaxRange(double v) { if (h_) slam_grid_set_max_range(h_, v); }                     // mls.h:237
     slam_grid_t *handle() { return h_; }
@@ -385,6 +534,7 @@ private:
     slam_gseg_t  *gseg_ = nullptr;
     OccupancyGrid grid_;
     std::unique_ptr<DistanceField> df_; // enableCostmap
+    std::unique_ptr<NavField>      nav_; // enablePlanner
     Costmap       costmap_;
     bool          rolling_ = false, disable_pointcloud_ = false;
     detail::DeviceBuffer d_cloud_, d_labels_, d_gnd_, d_obs_, d_counts_; // the first four hold cap_ points each

@@ -446,6 +446,65 @@ int  slam_gdist_planes_dev(slam_gdist_t *h, uint16_t **d_dist2, uint8_t **d_cost
  * not finalize).  Grid and handle must have the same size. */
 int  slam_grid_distance_field(slam_grid_t *g, slam_gdist_t *h, slam_stream_t stream);
 
+/* ------------------------------------------------ grid navigation field and path
+ * What a planner computes from the cost plane (docs/GRID_NAV.md): the exact cost-to-go from every cell to the nearest of a
+ * set of goal cells, and the path down it.  Not in the reference, and parity with navfn or any outside planner is not
+ * claimed: the yardstick is the project's own restatement (tests/grid_nav_cases.py), which the device equals bit for bit.
+ * All integer.  Planes are in WINDOW coordinates, data[x + size_x*y]; nothing wraps across the window's edges.
+ *   step table  S[256] uint32, indexed by a cost byte: 0 closes the cell, otherwise 1 <= S[c] <= 2^20
+ *   moves       8-connected; direction d = 0..7 is (dx, dy) = (1,0) (1,1) (0,1) (-1,1) (-1,0) (-1,-1) (0,-1) (1,-1).  A move
+ *               between u and v costs m(u, v) = w * (S[cost[u]] + S[cost[v]]), w = orth_w for d even, diag_w for d odd, both
+ *               1..255.  A diagonal move needs both cells that share an edge with u and with v traversable (no corner
+ *               cutting); cells outside the plane are not traversable
+ *   potential   uint32: the least sum of m over paths to any valid goal where that is < 0xFFFFFFFF, SLAM_GNAV_FAR otherwise
+ *               (saturated, never wrapped); 0 on goals, FAR on closed and unreachable cells
+ *   goals       int32 pairs (x, y); one outside the plane or on a closed cell is skipped and counted
+ *   path        from a start: the next cell is the allowed neighbour of lowest d with pot[v] + m(u, v) == pot[u]; int32 pairs,
+ *               the start first, the goal last.  Status: 0 reached a goal; 1 the start is outside the plane, closed or FAR
+ *               (length 0); 2 cut at max_len (max_len cells are valid); 3 the field is not converged (nothing walked)
+ * The state read back is SLAM_GNAV_STATE_INTS int64:
+ *   ints[0] rounds           rounds enqueued since the last restart
+ *   ints[1] converged        a round has flagged nothing (or no goal was valid): the field is exact
+ *   ints[2] goals_used       ints[3] goals_skipped
+ *   ints[4] tiles_processed  tiles relaxed since the last restart
+ *   ints[5] last_path_len    ints[6] last_path_status */
+typedef struct slam_gnav slam_gnav_t;
+#define SLAM_GNAV_FAR 0xFFFFFFFFu
+#define SLAM_GNAV_STATE_INTS 7
+/* the defaults: 12, 17, 50, 253, 0; each pointer nullable */
+void slam_gnav_default_params(int *orth_w, int *diag_w, int *neutral, int *lethal_from, int *unknown_step);
+/* The step table, on the host (slam_amd/csrc/grid_nav_table.hpp; no device is touched): table[c] = neutral + c for
+ * c < lethal_from, 0 from there on, table[255] = unknown_step (0 keeps unknown cells closed).  SLAM_E_INVALID and nothing
+ * written: n != 256, neutral outside 1 .. 2^19, lethal_from outside 1 .. 256, unknown_step outside 0 .. 2^20, a null table. */
+int  slam_grid_step_table(int neutral, int lethal_from, int unknown_step, uint32_t *table, int n);
+/* Everything is allocated here, nothing later; the default table is installed.  Sizes 1 .. 32767, weights 1 .. 255. */
+int  slam_gnav_create(int size_x, int size_y, int orth_w, int diag_w, slam_gnav_t **out);
+void slam_gnav_destroy(slam_gnav_t *h);
+/* any 256 entries of 0 .. 2^20.  Synchronous.  The field belongs to the table it was computed with: restart afterwards. */
+int  slam_gnav_set_table(slam_gnav_t *h, const uint32_t *table, int n);
+/* d_cost: a device plane of size_x*size_y cost bytes; d_goals: n_goals >= 1 int32 pairs on the device; both borrowed until
+ * the stream reaches this point.  restart != 0: the handle takes a copy of the cost plane and the field starts from the
+ * goals; restart == 0 continues on the plane of the last restart (d_cost and d_goals are not read, but must still be non-null and
+ * n_goals >= 1: one rule for both forms).  Then exactly `rounds`
+ * rounds are enqueued.  No host wait, no allocation: a graph may capture it.  SLAM_E_INVALID: a null pointer, n_goals < 1,
+ * rounds < 0. */
+int  slam_gnav_compute_dev(slam_gnav_t *h, const uint8_t *d_cost, const int32_t *d_goals, int n_goals, int rounds, int restart,
+                           slam_stream_t stream);
+/* Host plane and host goals; synchronous.  Rounds in batches until the field has converged, one pinned word read per batch;
+ * SLAM_E_TIMEOUT when max_rounds rounds did not suffice.  max_rounds == 0: size_x*size_y + 1, which always suffices. */
+int  slam_gnav_compute(slam_gnav_t *h, const uint8_t *cost, const int32_t *goals, int n_goals, int max_rounds);
+int  slam_gnav_read(slam_gnav_t *h, uint32_t *pot);                         /* size_x*size_y words; waits for the device */
+int  slam_gnav_potential_dev(slam_gnav_t *h, uint32_t **d_pot);
+/* One wave walks the path on the device: d_path has room for max_len int32 pairs, d_len_status is two int32 (length,
+ * status).  Bounded by max_len whatever the field holds.  Asynchronous on `stream`. */
+int  slam_gnav_path_dev(slam_gnav_t *h, int sx, int sy, int max_len, int32_t *d_path, int32_t *d_len_status, slam_stream_t stream);
+int  slam_gnav_path(slam_gnav_t *h, int sx, int sy, int max_len, int32_t *path, int *len, int *status); /* host twin; synchronous */
+int  slam_gnav_read_state(slam_gnav_t *h, int64_t ints[SLAM_GNAV_STATE_INTS]);  /* synchronous */
+/* slam_gnav_compute_dev with restart over the cost plane slam_gdist_planes_dev hands out, as it lies at this point of the
+ * stream.  Grid, distance field and navigation field must have the same size, and the distance field a table. */
+int  slam_grid_nav_field(slam_grid_t *g, slam_gdist_t *gdist, slam_gnav_t *gnav, const int32_t *d_goals, int n_goals, int rounds,
+                         slam_stream_t stream);
+
 /* ------------------------------------------------------------ height-cluster map
  * Stands for class MLS in its non-rolling, height-cluster mode (mls.h:154-237, mls.cpp:18-53, 152-402, 481-556):
  * graph_slam's global map (graph_slam.cpp:71).  Every cell holds up to `capacity` z clusters (mean x, y, z, cov_zz,

@@ -34,6 +34,7 @@ E_INVALID, E_NO_DEVICE, E_HIP, E_TOO_FEW_MODEL, E_TOO_FEW_SCENE, E_NOMEM, E_UNSU
 ICP_P2P, ICP_P2L = _D["SLAM_ICP_P2P"], _D["SLAM_ICP_P2L"]
 RAYCAST_TILED, RAYCAST_GLOBAL, RAYCAST_TILED_MERGE = (_D["SLAM_RAYCAST_" + n] for n in ("TILED", "GLOBAL", "TILED_MERGE"))
 GDIST_FAR = _D["SLAM_GDIST_FAR"]
+GNAV_FAR = _D["SLAM_GNAV_FAR"]
 GSEG_DROPPED, GSEG_GROUND, GSEG_OBSTACLE, GSEG_OVERHEAD = (_D["SLAM_GSEG_" + n] for n in ("DROPPED", "GROUND", "OBSTACLE", "OVERHEAD"))
 KF_NOT_CONVERGED, KF_ITERATIONS, KF_TRANSFORM, KF_ABS_MSE, KF_REL_MSE, KF_NO_CORRESPONDENCES, KF_DEGENERATE = \
     (_D["SLAM_KF_" + n] for n in ("NOT_CONVERGED", "ITERATIONS", "TRANSFORM", "ABS_MSE", "REL_MSE", "NO_CORRESPONDENCES", "DEGENERATE"))
@@ -111,6 +112,10 @@ PF_MOTION_DTYPE = np.dtype({"names": ["dx", "dy", "sx", "sy", "sk", "dk"], "form
                             "itemsize": _D["SLAM_PF_MOTION_BYTES"]})
 PF_PARAMS = ("n_particles", "n_angles", "gauss_bits", "weight_len", "weight_shift", "weight_scale", "resample_num", "resample_den", "seed")
 PF_STATE_INTS = ("t", "n", "resampled", "degenerate", "best", "refused", "n_resamples", "A_max", "W", "S2", "MX", "MY", "MC", "MS")
+
+GNAV_PARAMS = ("orth_w", "diag_w", "neutral", "lethal_from", "unknown_step")
+GNAV_STATE_INTS = ("rounds", "converged", "goals_used", "goals_skipped", "tiles_processed", "last_path_len", "last_path_status")
+GNAV_REACHED, GNAV_NO_START, GNAV_CUT, GNAV_NOT_CONVERGED = 0, 1, 2, 3   # a path's status
 
 KF_LATTICE_MARGIN = 1.0 + 2.0 ** -16   # the search lattice's edge is cell_size (or the gate) times this
 
@@ -1288,6 +1293,12 @@ class Grid(_Handle):
         """df (a DistanceField of this grid's size) computed over the plane read_occupancy() returns; enqueues on `stream`"""
         check(lib().slam_grid_distance_field(self.h, df.h, _sp(stream)))
 
+    def nav_field(self, distance_field, nav, goals, rounds=0, stream=None):
+        """nav (a NavField of this grid's size) restarted from `goals` over distance_field's cost plane as it lies at this
+        point of `stream`, then `rounds` rounds; goals: a device buffer of int32 pairs, or a host array (uploaded first)"""
+        d_goals, n = nav._goals(goals)
+        check(lib().slam_grid_nav_field(self.h, distance_field.h, nav.h, d_goals.ptr, n, int(rounds), _sp(stream)))
+
 
 def gdist_default_params(**kw):
     return _defaults(GdistParams, "slam_gdist_default_params", kw)
@@ -1359,6 +1370,99 @@ class DistanceField(_Handle):
         d, c = _vp(), _vp()
         check(lib().slam_gdist_planes_dev(self.h, C.byref(d), C.byref(c)))
         return d.value, c.value
+
+
+def gnav_default_params():
+    """the navigation field's defaults by name (GNAV_PARAMS)"""
+    c = [C.c_int() for _ in GNAV_PARAMS]
+    lib().slam_gnav_default_params(*(C.byref(v) for v in c))
+    return {n: v.value for n, v in zip(GNAV_PARAMS, c)}
+
+
+def step_table(neutral=None, lethal_from=None, unknown_step=None):
+    """np.uint32[256] indexed by a cost byte: neutral + c below lethal_from, 0 (closed) from there on, [255] = unknown_step
+    (slam_grid_step_table; host only).  None: the library's default."""
+    d = gnav_default_params()
+    t = np.zeros(256, np.uint32)
+    check(lib().slam_grid_step_table(int(d["neutral"] if neutral is None else neutral), int(d["lethal_from"] if lethal_from is None else lethal_from),
+                                     int(d["unknown_step"] if unknown_step is None else unknown_step), _ptr(t), len(t)))
+    return t
+
+
+class NavState:
+    """what slam_gnav_read_state returns, by name (GNAV_STATE_INTS)"""
+
+    def __init__(self, ints):
+        for n, v in zip(GNAV_STATE_INTS, ints):
+            setattr(self, n, int(v))
+
+
+class NavField(_Handle):
+    """Exact cost-to-go from every cell of a cost plane to the nearest goal cell, and the path down it (slam_gnav_*,
+    docs/GRID_NAV.md).  Planes are window order, data[x + size_x * y]; goals and paths are int32 (x, y) pairs."""
+    _destroy = "slam_gnav_destroy"
+
+    def __init__(self, size_x, size_y, orth_w=None, diag_w=None):
+        d = gnav_default_params()
+        self.size_x, self.size_y = int(size_x), int(size_y)
+        self.orth_w, self.diag_w = int(d["orth_w"] if orth_w is None else orth_w), int(d["diag_w"] if diag_w is None else diag_w)
+        self.cells = self.size_x * self.size_y
+        h = _vp()
+        check(lib().slam_gnav_create(self.size_x, self.size_y, self.orth_w, self.diag_w, C.byref(h)))
+        self.h = h.value
+        self._d_goals = None
+
+    def set_table(self, table):
+        t = np.ascontiguousarray(table, dtype=np.uint32).ravel()
+        check(lib().slam_gnav_set_table(self.h, _ptr(t), len(t)))
+
+    def _goals(self, goals):
+        """(device buffer, n) of goals given as a DeviceArray of int32 pairs or as a host array (kept until the next call)"""
+        if isinstance(goals, DeviceArray):
+            return goals, goals.nbytes // 8
+        g = np.ascontiguousarray(goals, dtype=np.int32).reshape(-1, 2)
+        self._d_goals = DeviceArray.from_host(g) if len(g) else DeviceArray((1, 2), np.int32)
+        return self._d_goals, len(g)
+
+    def compute(self, cost, goals, max_rounds=0):
+        """host plane and goals; synchronous, to convergence (SlamError E_TIMEOUT when max_rounds rounds did not suffice)"""
+        cost = np.ascontiguousarray(cost, dtype=np.uint8).ravel()
+        g = np.ascontiguousarray(goals, dtype=np.int32).reshape(-1, 2)
+        assert cost.size == self.cells
+        check(lib().slam_gnav_compute(self.h, _ptr(cost), _ptr(g), len(g), int(max_rounds)))
+
+    def compute_dev(self, d_cost, goals, rounds, restart=True, stream=None):
+        d_goals, n = self._goals(goals)
+        check(lib().slam_gnav_compute_dev(self.h, getattr(d_cost, "ptr", d_cost), d_goals.ptr, n, int(rounds), int(bool(restart)), _sp(stream)))
+
+    def potential(self):
+        """np.uint32[cells]; waits for the device"""
+        p = np.empty(self.cells, np.uint32)
+        check(lib().slam_gnav_read(self.h, _ptr(p)))
+        return p
+
+    def potential_dev(self):
+        p = _vp()
+        check(lib().slam_gnav_potential_dev(self.h, C.byref(p)))
+        return p.value
+
+    def path(self, start, max_len=None):
+        """(int32 [len, 2] from the start to the goal, status); max_len None: the plane's cell count, which no path exceeds"""
+        max_len = self.cells if max_len is None else int(max_len)
+        out = np.zeros((max(max_len, 1), 2), np.int32)
+        n, st = C.c_int(), C.c_int()
+        check(lib().slam_gnav_path(self.h, int(start[0]), int(start[1]), max_len, _ptr(out), C.byref(n), C.byref(st)))
+        return out[:n.value].copy(), st.value
+
+    def path_dev(self, start, max_len, d_path, d_len_status, stream=None):
+        """d_path: room for max_len int32 pairs; d_len_status: two int32 (length, status); enqueues on `stream`"""
+        check(lib().slam_gnav_path_dev(self.h, int(start[0]), int(start[1]), int(max_len), getattr(d_path, "ptr", d_path),
+                                       getattr(d_len_status, "ptr", d_len_status), _sp(stream)))
+
+    def state(self):
+        ints = np.zeros(_D["SLAM_GNAV_STATE_INTS"], np.int64)
+        check(lib().slam_gnav_read_state(self.h, _ptr(ints)))
+        return NavState(ints)
 
 
 class GridMatcher:

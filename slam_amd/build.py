@@ -20,7 +20,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SOURCES = ["runtime.hip", "icp.hip", "icp_build.hip", "icp_single.hip", "grid.hip", "gseg.hip", "ccicp.hip",
            "mapper.hip", "mls.hip", "kf_edge.hip", "kf_gicp.hip", "csm.hip", "voxmap.hip", "kf_store.hip", "pgo.hip", "kf_sc.hip", "vmap_gicp.hip",
-           "vmap_search.hip", "grid_dist.hip", "pf.hip"]
+           "vmap_search.hip", "grid_dist.hip", "pf.hip", "grid_nav.hip"]
 RCCL_SOURCES = ["rccl.hip"]
 # -ffp-contract=off: the reference arithmetic (x86-64, no FMA) rounds every
 # product before the add; the kernels additionally spell the parity-critical
