@@ -339,31 +339,11 @@ private:
 //     ... per scan:  gm.update();  pf.predict(motion);  pf.update(T_GA, T_NGA, tGA, tNGA);  pf.state(s);   // s.x, s.y, s.theta
 //
 // A failure logs the library's error and answers false; a failed construction leaves ok() == false.
-// The C-ABI takes the parameters as plain arguments, the motion as 48 bytes and gives the state back as two arrays
-// (slam_mi355x.h); these three carry them by name.
-struct PfParams {
-    int      n_particles, n_angles, gauss_bits, weight_len, weight_shift;
-    double   weight_scale;
-    int      resample_num, resample_den;
-    uint64_t seed;
-    PfParams()
-    {
-        slam_pf_default_params(&n_particles, &n_angles, &gauss_bits, &weight_len, &weight_shift, &weight_scale, &resample_num, &resample_den, &seed);
-    }
+struct PfParams : slam_pf_params { // at the library's defaults
+    PfParams() { slam_pf_default_params(this); }
 };
-struct PfMotion { // the layout slam_pf_predict_dev reads on the device
-    double  dx, dy, sx, sy, sk;
-    int32_t dk, unused;
-};
-static_assert(sizeof(PfMotion) == SLAM_PF_MOTION_BYTES, "a motion is SLAM_PF_MOTION_BYTES on the device");
-struct PfState {
-    uint32_t t = 0;
-    int      n = 0, resampled = 0, degenerate = 0, best = -1, refused = 0;
-    int64_t  n_resamples = 0, A_max = 0;
-    uint64_t W = 0, S2 = 0;
-    int64_t  MX = 0, MY = 0, MC = 0, MS = 0;
-    double   x = 0.0, y = 0.0, theta = 0.0;
-};
+using PfMotion = slam_pf_motion;
+using PfState = slam_pf_state;
 
 class ParticleFilter {
 public:
@@ -375,8 +355,7 @@ public:
             std::fprintf(stderr, "ParticleFilter: the grid matcher is not usable\n");
             return;
         }
-        if (slam_pf_create(p_.n_particles, p_.n_angles, p_.gauss_bits, p_.weight_len, p_.weight_shift, p_.weight_scale, p_.resample_num,
-                           p_.resample_den, p_.seed, &h_) != SLAM_OK) {
+        if (slam_pf_create(&p_, &h_) != SLAM_OK) {
             detail::warn("ParticleFilter");
             h_ = nullptr;
         }
@@ -431,7 +410,7 @@ public:
     }
     bool initGaussian(double x, double y, int k, double sx, double sy, double sk) { return h_ && done(slam_pf_init_gaussian(h_, x, y, k, sx, sy, sk)); }
     // the motion model: host form (an invalid motion is refused, logged) and device form (the motion is read on the device)
-    bool predict(const PfMotion &m) { return h_ && done(slam_pf_predict(h_, m.dx, m.dy, m.sx, m.sy, m.sk, m.dk)); }
+    bool predict(const PfMotion &m) { return h_ && done(slam_pf_predict(h_, &m)); }
     bool predictDev(const PfMotion *d_motion, slam_stream_t stream = nullptr) { return h_ && done(slam_pf_predict_dev(h_, d_motion, stream)); }
     // the measurement step against the grid's plane as GridMatcher::update left it; the rolling centre is the matcher's
     bool update(const double *T_GA, const double *T_NGA, const int32_t T_GA_num, const int32_t T_NGA_num)
@@ -465,16 +444,7 @@ public:
                done(slam_memcpy_d2h(src.data(), d_src.p, d_src.cap, nullptr));
     }
     // the counter, the last update's sums and flags, and the estimate (x, y, theta); waits
-    bool state(PfState &s)
-    {
-        int64_t v[SLAM_PF_STATE_INTS];
-        double  e[3];
-        if (!h_ || !done(slam_pf_read_state(h_, v, e))) return false;
-        s.t = (uint32_t)v[0], s.n = (int)v[1], s.resampled = (int)v[2], s.degenerate = (int)v[3], s.best = (int)v[4], s.refused = (int)v[5];
-        s.n_resamples = v[6], s.A_max = v[7], s.W = (uint64_t)v[8], s.S2 = (uint64_t)v[9], s.MX = v[10], s.MY = v[11], s.MC = v[12], s.MS = v[13];
-        s.x = e[0], s.y = e[1], s.theta = e[2];
-        return true;
-    }
+    bool state(PfState &s) { return h_ && done(slam_pf_read_state(h_, &s)); }
 
 private:
     static bool done(int rc)

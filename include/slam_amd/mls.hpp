@@ -142,20 +142,26 @@ private:
 };
 
 // A path down a navigation field (slam_gnav_*, docs/GRID_NAV.md; the reference has no planner): window cells (x, y) from the
-// start to the goal, the same cells as world points at their centres, and the status of slam_mi355x.h: 0 reached a goal, 1 the
-// start is outside the plane, closed or unreachable, 2 cut at max_len, 3 the field is not converged.
+// start to the goal, the same cells as world points at their centres, and one of slam_mi355x.h's SLAM_GNAV_PATH_* statuses.
 struct NavPath {
-    int                  status = 3;
+    int                  status = SLAM_GNAV_PATH_NOT_CONVERGED;
     std::vector<int32_t> cells;  // 2 per cell
     std::vector<double>  points; // 2 per cell
+};
+
+// slam_gnav_params at the library's defaults, or with other move weights
+struct NavParams : slam_gnav_params {
+    NavParams() { slam_gnav_default_params(this); }
+    NavParams(int orth, int diag) : NavParams() { orth_w = orth, diag_w = diag; }
 };
 
 // RAII over slam_gnav_t.  A failed construction logs and leaves an unusable object (ok() == false), as the other adapters do.
 class NavField {
 public:
-    NavField(int size_x, int size_y, int orth_w = 12, int diag_w = 17)
+    NavField(int size_x, int size_y, int orth_w, int diag_w) : NavField(size_x, size_y, NavParams(orth_w, diag_w)) {}
+    NavField(int size_x, int size_y, const NavParams &p = NavParams())
     {
-        if (slam_gnav_create(size_x, size_y, orth_w, diag_w, &h_) != SLAM_OK) {
+        if (slam_gnav_create(size_x, size_y, &p, &h_) != SLAM_OK) {
             std::fprintf(stderr, "%s\n", slam_last_error());
             h_ = nullptr;
             return;
@@ -195,9 +201,9 @@ public:
         if (!good(slam_memcpy_h2d(d_goals_.p, goals.data(), sizeof(int32_t) * 2 * (size_t)n, nullptr))) return false;
         if (!good(slam_grid_nav_field(grid, df.handle(), h_, d_goals_.as<int32_t>(), n, batch, nullptr))) return false;
         for (size_t done = batch;; done += batch) {
-            int64_t st[SLAM_GNAV_STATE_INTS];
-            if (!good(slam_gnav_read_state(h_, st))) return false;
-            if (st[1]) return true;
+            slam_gnav_state st;
+            if (!state(st)) return false;
+            if (st.converged) return true;
             if (done > cells_) return false; // (cells + 1 rounds always suffice)
             uint8_t *d_cost = nullptr;
             if (!good(slam_gdist_planes_dev(df.handle(), nullptr, &d_cost)) || !d_cost) return false;
@@ -221,7 +227,7 @@ public:
         cells->resize(2 * (size_t)len);
         return true;
     }
-    bool state(int64_t ints[SLAM_GNAV_STATE_INTS]) { return h_ && good(slam_gnav_read_state(h_, ints)); }
+    bool state(slam_gnav_state &s) { return h_ && good(slam_gnav_read_state(h_, &s)); }
     slam_gnav_t *handle() { return h_; }
 
 private:
@@ -470,12 +476,12 @@ public:
     }
     // Opt-in planner over the costmap (not in the reference): needs enableCostmap first.  Moves cost orth_w / diag_w times the
     // sum of the two cells' steps; a cell's step is neutral + its cost byte, cells from lethal_from on are closed, unknown cells
-    // (255) take unknown_step (0: closed).  false (logged) when the arguments or the device refuse.
-    bool enablePlanner(int orth_w = 12, int diag_w = 17, int neutral = 50, int lethal_from = 253, int unknown_step = 0)
+    // (255) take unknown_step (0: closed).  false (logged) when the parameters or the device refuse.
+    bool enablePlanner(const NavParams &p = NavParams())
     {
         if (!h_ || !df_) return false;
-        std::unique_ptr<NavField> nav(new NavField((int)grid_.info.width, (int)grid_.info.height, orth_w, diag_w));
-        if (!nav->ok() || !nav->setSteps(neutral, lethal_from, unknown_step)) return false;
+        std::unique_ptr<NavField> nav(new NavField((int)grid_.info.width, (int)grid_.info.height, p));
+        if (!nav->ok()) return false;
         nav_ = std::move(nav);
         return true;
     }
@@ -502,19 +508,19 @@ public:
         *wy = ((double)(cy - (int)grid_.info.height / 2) + 0.5) * grid_.info.resolution + py;
     }
     // getCostmap()'s plane -> slam_grid_nav_field from the goal's cell, to convergence -> slam_gnav_path from the start's
-    // cell.  World points in, world points at cell centres out; status 1 with no cells when either point lies outside the
-    // window, 3 before enablePlanner or when the device refuses.
+    // cell.  World points in, world points at cell centres out; NO_START with no cells when either point lies outside the
+    // window, NOT_CONVERGED before enablePlanner or when the device refuses.
     NavPath planPath(double from_x, double from_y, double to_x, double to_y)
     {
         NavPath out;
         if (!(h_ && df_ && nav_)) return out;
         int sx, sy, gx, gy;
         if (!worldToCell(from_x, from_y, &sx, &sy) || !worldToCell(to_x, to_y, &gx, &gy)) {
-            out.status = 1;
+            out.status = SLAM_GNAV_PATH_NO_START;
             return out;
         }
         if (!(df_->computeFromGrid(h_) && nav_->computeFromGrid(h_, *df_, {gx, gy}) && nav_->path(sx, sy, &out.cells, &out.status))) {
-            out.status = 3;
+            out.status = SLAM_GNAV_PATH_NOT_CONVERGED;
             out.cells.clear();
             return out;
         }

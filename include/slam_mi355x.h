@@ -460,25 +460,34 @@ int  slam_grid_distance_field(slam_grid_t *g, slam_gdist_t *h, slam_stream_t str
  *               (saturated, never wrapped); 0 on goals, FAR on closed and unreachable cells
  *   goals       int32 pairs (x, y); one outside the plane or on a closed cell is skipped and counted
  *   path        from a start: the next cell is the allowed neighbour of lowest d with pot[v] + m(u, v) == pot[u]; int32 pairs,
- *               the start first, the goal last.  Status: 0 reached a goal; 1 the start is outside the plane, closed or FAR
- *               (length 0); 2 cut at max_len (max_len cells are valid); 3 the field is not converged (nothing walked)
- * The state read back is SLAM_GNAV_STATE_INTS int64:
- *   ints[0] rounds           rounds enqueued since the last restart
- *   ints[1] converged        a round has flagged nothing (or no goal was valid): the field is exact
- *   ints[2] goals_used       ints[3] goals_skipped
- *   ints[4] tiles_processed  tiles relaxed since the last restart
- *   ints[5] last_path_len    ints[6] last_path_status */
+ *               the start first, the goal last, with one of the SLAM_GNAV_PATH_* statuses below */
 typedef struct slam_gnav slam_gnav_t;
 #define SLAM_GNAV_FAR 0xFFFFFFFFu
-#define SLAM_GNAV_STATE_INTS 7
-/* the defaults: 12, 17, 50, 253, 0; each pointer nullable */
-void slam_gnav_default_params(int *orth_w, int *diag_w, int *neutral, int *lethal_from, int *unknown_step);
+#define SLAM_GNAV_PATH_REACHED       0  /* the path's last cell is a goal */
+#define SLAM_GNAV_PATH_NO_START      1  /* the start is outside the plane, closed or FAR (length 0) */
+#define SLAM_GNAV_PATH_CUT           2  /* cut at max_len (max_len cells are valid) */
+#define SLAM_GNAV_PATH_NOT_CONVERGED 3  /* the field is not converged (nothing walked) */
+typedef struct {
+    int orth_w, diag_w;     /* the move weights, 1 .. 255; default 12, 17 */
+    int neutral;            /* the step table slam_gnav_create installs, as slam_grid_step_table makes it; default 50 */
+    int lethal_from;        /* default 253 */
+    int unknown_step;       /* default 0 */
+} slam_gnav_params;
+typedef struct {
+    int64_t rounds;           /* rounds enqueued since the last restart */
+    int64_t converged;        /* a round has flagged nothing (or no goal was valid): the field is exact */
+    int64_t goals_used, goals_skipped;
+    int64_t tiles_processed;  /* tiles relaxed since the last restart */
+    int64_t last_path_len, last_path_status;
+} slam_gnav_state;
+void slam_gnav_default_params(slam_gnav_params *p);
 /* The step table, on the host (slam_amd/csrc/grid_nav_table.hpp; no device is touched): table[c] = neutral + c for
  * c < lethal_from, 0 from there on, table[255] = unknown_step (0 keeps unknown cells closed).  SLAM_E_INVALID and nothing
  * written: n != 256, neutral outside 1 .. 2^19, lethal_from outside 1 .. 256, unknown_step outside 0 .. 2^20, a null table. */
 int  slam_grid_step_table(int neutral, int lethal_from, int unknown_step, uint32_t *table, int n);
-/* Everything is allocated here, nothing later; the default table is installed.  Sizes 1 .. 32767, weights 1 .. 255. */
-int  slam_gnav_create(int size_x, int size_y, int orth_w, int diag_w, slam_gnav_t **out);
+/* Everything is allocated here, nothing later; the step table of p's neutral, lethal_from, unknown_step is installed (under
+ * slam_grid_step_table's rules).  Sizes 1 .. 32767, weights 1 .. 255. */
+int  slam_gnav_create(int size_x, int size_y, const slam_gnav_params *p /* NULL: the defaults */, slam_gnav_t **out);
 void slam_gnav_destroy(slam_gnav_t *h);
 /* any 256 entries of 0 .. 2^20.  Synchronous.  The field belongs to the table it was computed with: restart afterwards. */
 int  slam_gnav_set_table(slam_gnav_t *h, const uint32_t *table, int n);
@@ -499,7 +508,7 @@ int  slam_gnav_potential_dev(slam_gnav_t *h, uint32_t **d_pot);
  * status).  Bounded by max_len whatever the field holds.  Asynchronous on `stream`. */
 int  slam_gnav_path_dev(slam_gnav_t *h, int sx, int sy, int max_len, int32_t *d_path, int32_t *d_len_status, slam_stream_t stream);
 int  slam_gnav_path(slam_gnav_t *h, int sx, int sy, int max_len, int32_t *path, int *len, int *status); /* host twin; synchronous */
-int  slam_gnav_read_state(slam_gnav_t *h, int64_t ints[SLAM_GNAV_STATE_INTS]);  /* synchronous */
+int  slam_gnav_read_state(slam_gnav_t *h, slam_gnav_state *state);          /* synchronous */
 /* slam_gnav_compute_dev with restart over the cost plane slam_gdist_planes_dev hands out, as it lies at this point of the
  * stream.  Grid, distance field and navigation field must have the same size, and the distance field a table. */
 int  slam_grid_nav_field(slam_grid_t *g, slam_gdist_t *gdist, slam_gnav_t *gnav, const int32_t *d_goals, int n_goals, int rounds,
@@ -1093,40 +1102,41 @@ int  slam_csm_match_post(slam_csm_t *csm, const double *t_ga, int n_tga, const d
  * ---------------------------------------------------------------------- */
 typedef struct slam_pf slam_pf_t;
 
-/* The parameters are plain arguments, in this order wherever they appear (defaults in brackets):
- *   n_particles   1 .. 2^18 (1024)
- *   n_angles      A: headings per turn, a power of two from 2^6 to 2^16 (4096)
- *   gauss_bits    b: the Gaussian table has 2^b entries, 4 .. 16 (12)
- *   weight_len    L: entries of the weight table, 2 .. 65536 (1024)
- *   weight_shift  a weight is looked up at (A_max - acc) >> weight_shift, 0 .. 14 (4)
- *   weight_scale  the weight at deficit d is exp(-d / weight_scale); positive and finite (1024.0)
- *   resample_num  resample iff N_eff < (num / den) n; 0 never, num > den always; 0 .. 65535 (1)
- *   resample_den  1 .. 65535 (2)
- *   seed          the Philox key (1)
- * A motion on the device is 48 bytes: five f64 and one int32 (then four unused bytes),
- *   dx, dy        the odometry increment in the particle's own frame, metres
- *   sx, sy        standard deviations of its noise, metres; finite, >= 0
- *   sk            standard deviation of the heading noise in heading steps; finite, 0 <= sk < 2^20
- *   dk (int32)    the heading increment in heading steps, |dk| < 2^20
- * The state read back is SLAM_PF_STATE_INTS int64 and three f64:
- *   ints[0] t            the step counter: predicts done (mod 2^32)
- *   ints[1] n            n_particles
- *   ints[2] resampled    the last update resampled
- *   ints[3] degenerate   the last update found no finite particle: nothing moved, every sum is 0, best is -1
- *   ints[4] best         the lowest index whose acc reached A_max (before a resample zeroed it)
- *   ints[5] refused      motions slam_pf_predict_dev found invalid on the device and skipped (the step did not advance)
- *   ints[6] n_resamples  updates that resampled since creation
- *   ints[7] A_max        the largest acc among the finite particles
- *   ints[8] W, [9] S2    sum w, sum w^2
- *   ints[10] MX, [11] MY sum w q(x), sum w q(y); q(v) = llrint(65536 v) saturated to +-(2^29 - 1)
- *   ints[12] MC, [13] MS sum w llrint(2^24 cos), sum w llrint(2^24 sin) of the heading
- *   est[0..2]            the estimate x, y, theta, formed on the host: MX / (W 65536), MY / (W 65536), atan2(MS, MC); NaN when W = 0 */
-#define SLAM_PF_STATE_INTS 14
-#define SLAM_PF_MOTION_BYTES 48
+typedef struct {
+    int      n_particles;   /* 1 .. 2^18; default 1024 */
+    int      n_angles;      /* A: headings per turn, a power of two from 2^6 to 2^16; default 4096 */
+    int      gauss_bits;    /* b: the Gaussian table has 2^b entries, 4 .. 16; default 12 */
+    int      weight_len;    /* L: entries of the weight table, 2 .. 65536; default 1024 */
+    int      weight_shift;  /* a weight is looked up at (A_max - acc) >> weight_shift, 0 .. 14; default 4 */
+    double   weight_scale;  /* the weight at deficit d is exp(-d / weight_scale); positive and finite; default 1024.0 */
+    int      resample_num;  /* resample iff N_eff < (num / den) n; 0 never, num > den always; 0 .. 65535; default 1 */
+    int      resample_den;  /* 1 .. 65535; default 2 */
+    uint64_t seed;          /* the Philox key; default 1 */
+} slam_pf_params;
+/* A motion, on the host and as the predict kernel reads it on the device: 48 bytes */
+typedef struct {
+    double  dx, dy;         /* the odometry increment in the particle's own frame, metres */
+    double  sx, sy;         /* standard deviations of its noise, metres; finite, >= 0 */
+    double  sk;             /* standard deviation of the heading noise in heading steps; finite, 0 <= sk < 2^20 */
+    int32_t dk;             /* the heading increment in heading steps, |dk| < 2^20 */
+    int32_t reserved;       /* not read */
+} slam_pf_motion;
+typedef struct {
+    int64_t t;              /* the step counter: predicts done (mod 2^32) */
+    int64_t n;              /* n_particles */
+    int64_t resampled;      /* the last update resampled */
+    int64_t degenerate;     /* the last update found no finite particle: nothing moved, every sum is 0, best is -1 */
+    int64_t best;           /* the lowest index whose acc reached A_max (before a resample zeroed it) */
+    int64_t refused;        /* motions slam_pf_predict_dev found invalid on the device and skipped (the step did not advance) */
+    int64_t n_resamples;    /* updates that resampled since creation */
+    int64_t A_max;          /* the largest acc among the finite particles */
+    int64_t W, S2;          /* sum w, sum w^2 */
+    int64_t MX, MY;         /* sum w q(x), sum w q(y); q(v) = llrint(65536 v) saturated to +-(2^29 - 1) */
+    int64_t MC, MS;         /* sum w llrint(2^24 cos), sum w llrint(2^24 sin) of the heading */
+    double  x, y, theta;    /* the estimate, formed on the host: MX / (W 65536), MY / (W 65536), atan2(MS, MC); NaN when W = 0 */
+} slam_pf_state;
 
-/* the defaults above; each pointer nullable */
-void slam_pf_default_params(int *n_particles, int *n_angles, int *gauss_bits, int *weight_len, int *weight_shift, double *weight_scale,
-                            int *resample_num, int *resample_den, uint64_t *seed);
+void slam_pf_default_params(slam_pf_params *p);
 /* The table makers (slam_amd/csrc/pf_tables.hpp; host only, no device is touched).  SLAM_E_INVALID and nothing written:
  *   angle   n_angles not a power of two in 2^6 .. 2^16, n != 2 n_angles.  cs[2 k], cs[2 k + 1] = cos, sin(2 pi k / n_angles);
  *           the four quadrant entries are exactly (+-1, 0) and (0, +-1)
@@ -1139,8 +1149,7 @@ int  slam_pf_gauss_table(int bits, double *G, int n);
 int  slam_pf_weight_table(double scale, int shift, int L, uint32_t *wtab);
 /* A filter with the three tables made from its parameters; the particles are all at (0, 0, 0) with acc 0, t = 0.  Every
  * refusal of a parameter is SLAM_E_INVALID before a device is touched. */
-int  slam_pf_create(int n_particles, int n_angles, int gauss_bits, int weight_len, int weight_shift, double weight_scale, int resample_num,
-                    int resample_den, uint64_t seed, slam_pf_t **out);
+int  slam_pf_create(const slam_pf_params *p /* NULL: the defaults */, slam_pf_t **out);
 void slam_pf_destroy(slam_pf_t *pf);
 /* Other tables of the right lengths (2 n_angles, 2^gauss_bits, weight_len); a null table stays as it is.  cs and G must be
  * finite, wtab[0] == 65536 with no entry above it.  Synchronous. */
@@ -1152,7 +1161,7 @@ int  slam_pf_read_particles(slam_pf_t *pf, double *x, double *y, int32_t *k);
 /* acc (int64) and the weights w (uint32) of the last update, each nullable; synchronous */
 int  slam_pf_read_weights(slam_pf_t *pf, int64_t *acc, uint32_t *w);
 /* The step counter, the last update's sums and flags, and the estimate; synchronous */
-int  slam_pf_read_state(slam_pf_t *pf, int64_t ints[SLAM_PF_STATE_INTS], double est[3]);
+int  slam_pf_read_state(slam_pf_t *pf, slam_pf_state *state);
 /* Debug: d_words[4 i ..] = the four Philox words of counter (p0 + i, t, purpose, 0), i < n <= 2^20, under the filter's key.
  * Enqueued on the null stream. */
 int  slam_pf_random_words_dev(slam_pf_t *pf, uint32_t p0, int n, uint32_t t, uint32_t purpose, uint32_t *d_words);
@@ -1163,9 +1172,9 @@ int  slam_pf_random_words_dev(slam_pf_t *pf, uint32_t p0, int n, uint32_t t, uin
  * and t advances by one at the end.  The motion is read from the device, so that a graph can be fed new odometry; one that
  * breaks the motion's rules above is found on the device: nothing moves, t stays, and the state's `refused` counts it.
  * Asynchronous on `stream`; allocates, frees and waits for nothing.  One call at a time per handle. */
-int  slam_pf_predict_dev(slam_pf_t *pf, const void *d_motion, slam_stream_t stream);
+int  slam_pf_predict_dev(slam_pf_t *pf, const slam_pf_motion *d_motion, slam_stream_t stream);
 /* the same from the host: an invalid motion is SLAM_E_INVALID before a device is touched; stages and waits */
-int  slam_pf_predict(slam_pf_t *pf, double dx, double dy, double sx, double sy, double sk, int dk);
+int  slam_pf_predict(slam_pf_t *pf, const slam_pf_motion *motion);
 /* Every particle becomes the pose (x, y, k) moved by the motion {0, 0, sx, sy, sk, 0} drawn with purpose 1 at the current t
  * (the noise lies in the pose's own frame); acc = 0; t stays.  Synchronous. */
 int  slam_pf_init_gaussian(slam_pf_t *pf, double x, double y, int k, double sx, double sy, double sk);

@@ -59,6 +59,8 @@ STRUCTS = {
     "VmapGicpResult": "slam_vmap_gicp_result", "VmapSearchParams": "slam_vmap_search_params",
     "VmapSearchHit": "slam_vmap_search_hit", "PgoParams": "slam_pgo_params", "PgoTrial": "slam_pgo_trial",
     "PgoResult": "slam_pgo_result", "CommStats": "slam_comm_stats",
+    "PfParams": "slam_pf_params", "PfMotion": "slam_pf_motion", "PfState": "slam_pf_state",
+    "GnavParams": "slam_gnav_params", "GnavState": "slam_gnav_state",
 }
 globals().update((py, _H.structs[c]) for py, c in STRUCTS.items())
 
@@ -107,15 +109,13 @@ CSM_POST_DTYPE = np.dtype([(f, np.int32) for f, _ in CsmPosterior._fields_[:8]] 
                           [("m0", np.int64), ("m1", np.int64, (3,)), ("m2", np.int64, (6,)), ("mean", np.float64, (3,)),
                            ("cov", np.float64, (6,))])
 
-# one motion in a device buffer, as slam_pf_predict_dev reads it there: SLAM_PF_MOTION_BYTES
-PF_MOTION_DTYPE = np.dtype({"names": ["dx", "dy", "sx", "sy", "sk", "dk"], "formats": ["<f8"] * 5 + ["<i4"], "offsets": [0, 8, 16, 24, 32, 40],
-                            "itemsize": _D["SLAM_PF_MOTION_BYTES"]})
-PF_PARAMS = ("n_particles", "n_angles", "gauss_bits", "weight_len", "weight_shift", "weight_scale", "resample_num", "resample_den", "seed")
-PF_STATE_INTS = ("t", "n", "resampled", "degenerate", "best", "refused", "n_resamples", "A_max", "W", "S2", "MX", "MY", "MC", "MS")
-
-GNAV_PARAMS = ("orth_w", "diag_w", "neutral", "lethal_from", "unknown_step")
-GNAV_STATE_INTS = ("rounds", "converged", "goals_used", "goals_skipped", "tiles_processed", "last_path_len", "last_path_status")
-GNAV_REACHED, GNAV_NO_START, GNAV_CUT, GNAV_NOT_CONVERGED = 0, 1, 2, 3   # a path's status
+# one motion in a device buffer, as slam_pf_predict_dev reads it there: slam_pf_motion without its reserved word
+_m = np.dtype(PfMotion)
+_f = [n for n in _m.names if n != "reserved"]
+PF_MOTION_DTYPE = np.dtype({"names": _f, "formats": [_m.fields[n][0] for n in _f], "offsets": [_m.fields[n][1] for n in _f],
+                            "itemsize": _m.itemsize})
+GNAV_REACHED, GNAV_NO_START, GNAV_CUT, GNAV_NOT_CONVERGED = \
+    (_D["SLAM_GNAV_PATH_" + n] for n in ("REACHED", "NO_START", "CUT", "NOT_CONVERGED"))
 
 KF_LATTICE_MARGIN = 1.0 + 2.0 ** -16   # the search lattice's edge is cell_size (or the gate) times this
 
@@ -1372,11 +1372,8 @@ class DistanceField(_Handle):
         return d.value, c.value
 
 
-def gnav_default_params():
-    """the navigation field's defaults by name (GNAV_PARAMS)"""
-    c = [C.c_int() for _ in GNAV_PARAMS]
-    lib().slam_gnav_default_params(*(C.byref(v) for v in c))
-    return {n: v.value for n, v in zip(GNAV_PARAMS, c)}
+def gnav_default_params(**kw):
+    return _defaults(GnavParams, "slam_gnav_default_params", kw)
 
 
 def step_table(neutral=None, lethal_from=None, unknown_step=None):
@@ -1384,17 +1381,9 @@ def step_table(neutral=None, lethal_from=None, unknown_step=None):
     (slam_grid_step_table; host only).  None: the library's default."""
     d = gnav_default_params()
     t = np.zeros(256, np.uint32)
-    check(lib().slam_grid_step_table(int(d["neutral"] if neutral is None else neutral), int(d["lethal_from"] if lethal_from is None else lethal_from),
-                                     int(d["unknown_step"] if unknown_step is None else unknown_step), _ptr(t), len(t)))
+    check(lib().slam_grid_step_table(int(d.neutral if neutral is None else neutral), int(d.lethal_from if lethal_from is None else lethal_from),
+                                     int(d.unknown_step if unknown_step is None else unknown_step), _ptr(t), len(t)))
     return t
-
-
-class NavState:
-    """what slam_gnav_read_state returns, by name (GNAV_STATE_INTS)"""
-
-    def __init__(self, ints):
-        for n, v in zip(GNAV_STATE_INTS, ints):
-            setattr(self, n, int(v))
 
 
 class NavField(_Handle):
@@ -1402,13 +1391,18 @@ class NavField(_Handle):
     docs/GRID_NAV.md).  Planes are window order, data[x + size_x * y]; goals and paths are int32 (x, y) pairs."""
     _destroy = "slam_gnav_destroy"
 
-    def __init__(self, size_x, size_y, orth_w=None, diag_w=None):
-        d = gnav_default_params()
+    def __init__(self, size_x, size_y, orth_w=None, diag_w=None, params=None):
+        """params: a GnavParams (gnav_default_params(...)); orth_w, diag_w, where given, go over its weights"""
+        self.params = params or gnav_default_params()
         self.size_x, self.size_y = int(size_x), int(size_y)
-        self.orth_w, self.diag_w = int(d["orth_w"] if orth_w is None else orth_w), int(d["diag_w"] if diag_w is None else diag_w)
+        if orth_w is not None:
+            self.params.orth_w = int(orth_w)
+        if diag_w is not None:
+            self.params.diag_w = int(diag_w)
+        self.orth_w, self.diag_w = self.params.orth_w, self.params.diag_w
         self.cells = self.size_x * self.size_y
         h = _vp()
-        check(lib().slam_gnav_create(self.size_x, self.size_y, self.orth_w, self.diag_w, C.byref(h)))
+        check(lib().slam_gnav_create(self.size_x, self.size_y, C.byref(self.params), C.byref(h)))
         self.h = h.value
         self._d_goals = None
 
@@ -1460,9 +1454,9 @@ class NavField(_Handle):
                                        getattr(d_len_status, "ptr", d_len_status), _sp(stream)))
 
     def state(self):
-        ints = np.zeros(_D["SLAM_GNAV_STATE_INTS"], np.int64)
-        check(lib().slam_gnav_read_state(self.h, _ptr(ints)))
-        return NavState(ints)
+        s = GnavState()
+        check(lib().slam_gnav_read_state(self.h, C.byref(s)))
+        return s
 
 
 class GridMatcher:
@@ -1545,34 +1539,8 @@ class GridMatcher:
         self.matcher = self.field = None
 
 
-class PfParams:
-    """the particle filter's parameters by name, in the order the C-ABI takes them (PF_PARAMS)"""
-
-    def __init__(self, **kw):
-        c = [C.c_double() if n == "weight_scale" else C.c_uint64() if n == "seed" else C.c_int() for n in PF_PARAMS]
-        lib().slam_pf_default_params(*(C.byref(v) for v in c))
-        for n, v in zip(PF_PARAMS, c):
-            setattr(self, n, v.value)
-        for n, v in kw.items():
-            if n not in PF_PARAMS:
-                raise TypeError("no particle filter parameter %r" % n)
-            setattr(self, n, v)
-
-    def args(self):
-        return [float(self.weight_scale) if n == "weight_scale" else int(getattr(self, n)) for n in PF_PARAMS]
-
-
-class PfState:
-    """what slam_pf_read_state returns, by name: PF_STATE_INTS as int, and the estimate x, y, theta"""
-
-    def __init__(self, ints, est):
-        for n, v in zip(PF_STATE_INTS, ints):
-            setattr(self, n, int(v))
-        self.x, self.y, self.theta = (float(v) for v in est)
-
-
 def pf_default_params(**kw):
-    return PfParams(**kw)
+    return _defaults(PfParams, "slam_pf_default_params", kw)
 
 
 def pf_angle_table(n_angles):
@@ -1607,7 +1575,7 @@ class ParticleFilter(_Handle):
             self.params.n_particles = int(n)
         self.matcher = matcher
         h = _vp()
-        check(lib().slam_pf_create(*self.params.args(), C.byref(h)))
+        check(lib().slam_pf_create(C.byref(self.params), C.byref(h)))
         self.h = h.value
         self.n = self.params.n_particles
         self._motion = None
@@ -1641,9 +1609,9 @@ class ParticleFilter(_Handle):
         return acc, w
 
     def state(self):
-        ints, est = np.zeros(_D["SLAM_PF_STATE_INTS"], np.int64), np.zeros(3, np.float64)
-        check(lib().slam_pf_read_state(self.h, _ptr(ints), _ptr(est)))
-        return PfState(ints, est)
+        s = PfState()
+        check(lib().slam_pf_read_state(self.h, C.byref(s)))
+        return s
 
     def random_words(self, p0, n, t, purpose):
         """[n, 4] uint32: the device's Philox words of counters (p0 + i, t, purpose, 0)"""
@@ -1662,11 +1630,12 @@ class ParticleFilter(_Handle):
     def predict(self, motion):
         """motion: (dx, dy, sx, sy, sk, dk); synchronous"""
         dx, dy, sx, sy, sk, dk = motion
-        check(lib().slam_pf_predict(self.h, float(dx), float(dy), float(sx), float(sy), float(sk), int(dk)))
+        check(lib().slam_pf_predict(self.h, C.byref(PfMotion(float(dx), float(dy), float(sx), float(sy), float(sk), int(dk)))))
 
     def predict_dev(self, d_motion, stream=None):
         """d_motion: a device buffer holding one motion (PF_MOTION_DTYPE)"""
-        check(lib().slam_pf_predict_dev(self.h, getattr(d_motion, "ptr", d_motion), _sp(stream)))
+        at = getattr(d_motion, "ptr", d_motion)      # (a view of the device's bytes, never read here: cheaper per call than a cast)
+        check(lib().slam_pf_predict_dev(self.h, PfMotion.from_address(at) if at else None, _sp(stream)))
 
     def _centre(self, matcher, centre):
         """(the CorrelativeMatcher, the window's centre): a GridMatcher brings its own centre, anything else has (0, 0)

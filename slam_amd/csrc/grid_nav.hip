@@ -42,10 +42,9 @@ constexpr int      kStage = 1 << 16;    // int32 pairs of the host forms' stagin
 constexpr int      kBatch = 16;         // rounds per host wait of slam_gnav_compute
 
 struct NavState {
-    long long    ints[SLAM_GNAV_STATE_INTS]; // rounds, converged, goals_used, goals_skipped, tiles_processed, last_path_len, _status
-    unsigned int cur_count, next_count;      // tiles flagged for the round at hand, and for the one after it
+    slam_gnav_state s;                     // what slam_gnav_read_state hands out
+    unsigned int    cur_count, next_count; // tiles flagged for the round at hand, and for the one after it
 };
-enum { kRounds, kConverged, kGoalsUsed, kGoalsSkipped, kTilesProcessed, kPathLen, kPathStatus };
 
 struct Plane {
     const uint8_t  *cost;  // [sx * sy] the handle's copy of the cost plane
@@ -83,12 +82,12 @@ __global__ __launch_bounds__(256) void gnav_goals_kernel(const int32_t *goals, i
                     if (vx >= 0 && vx < P.sx && vy >= 0 && vy < P.sy) flag_tile(flags, (vy / kTile) * tiles_x + vx / kTile, &st->cur_count);
                 }
         }
-        atomicAdd((unsigned long long *)&st->ints[ok ? kGoalsUsed : kGoalsSkipped], 1ull);
+        atomicAdd((unsigned long long *)(ok ? &st->s.goals_used : &st->s.goals_skipped), 1ull);
     }
 }
 
 // behind the goals: with no valid goal nothing is flagged, everything is FAR and that is the field
-__global__ void gnav_seal_kernel(NavState *st) { st->ints[kConverged] = st->cur_count == 0 ? 1 : 0; }
+__global__ void gnav_seal_kernel(NavState *st) { st->s.converged = st->cur_count == 0 ? 1 : 0; }
 
 // One cell of the tile in LDS against its eight neighbours; true when it fell.  u = ly * kPitch + lx.
 __device__ __forceinline__ bool relax_cell(uint32_t *pot, const uint8_t *cb, const uint32_t *S, int u, uint32_t ow, uint32_t dw)
@@ -129,7 +128,7 @@ __global__ __launch_bounds__(256) void gnav_relax_kernel(Plane P, int *flags, in
     __shared__ uint8_t  s_cb[kHalo * kPitch];
     __shared__ unsigned s_mask;
     const int           tiles_x = gridDim.x, tile = blockIdx.y * tiles_x + blockIdx.x;
-    const int           parity = (int)(st->ints[kRounds] & 1);
+    const int           parity = (int)(st->s.rounds & 1);
     if (!flags[parity * n_tiles + tile]) return; // (uniform: the whole workgroup leaves)
     const int tid = threadIdx.x, x0 = blockIdx.x * kTile, y0 = blockIdx.y * kTile;
     const int sx = P.sx, sy = P.sy;
@@ -196,13 +195,13 @@ __global__ __launch_bounds__(256) void gnav_relax_kernel(Plane P, int *flags, in
 // behind every round: the round's flags go down, the counts move on, the two flag arrays change roles
 __global__ __launch_bounds__(256) void gnav_advance_kernel(int *flags, int n_tiles, NavState *st)
 {
-    int *cur = flags + (st->ints[kRounds] & 1) * n_tiles;
+    int *cur = flags + (st->s.rounds & 1) * n_tiles;
     for (int i = threadIdx.x; i < n_tiles; i += 256) cur[i] = 0;
     __syncthreads(); // (every thread has read the parity)
     if (threadIdx.x == 0) {
-        st->ints[kTilesProcessed] += st->cur_count;
-        st->ints[kRounds] += 1;
-        st->ints[kConverged] = st->next_count == 0 ? 1 : 0;
+        st->s.tiles_processed += st->cur_count;
+        st->s.rounds += 1;
+        st->s.converged = st->next_count == 0 ? 1 : 0;
         st->cur_count = st->next_count;
         st->next_count = 0;
     }
@@ -218,17 +217,17 @@ __global__ __launch_bounds__(64) void gnav_path_kernel(Plane P, int x, int y, in
                                                        NavState *st)
 {
     const int lane = threadIdx.x;
-    int       len = 0, status = 3;
-    if (st->ints[kConverged]) {
+    int       len = 0, status = SLAM_GNAV_PATH_NOT_CONVERGED;
+    if (st->s.converged) {
         const bool inside = x >= 0 && x < P.sx && y >= 0 && y < P.sy;
         uint32_t   su = inside ? P.S[P.cost[(size_t)y * P.sx + x]] : 0u;
         uint32_t   pu = su ? P.pot[(size_t)y * P.sx + x] : kFar;
-        status = pu == kFar ? 1 : 2;
-        while (status == 2 && len < max_len) {
+        status = pu == kFar ? SLAM_GNAV_PATH_NO_START : SLAM_GNAV_PATH_CUT;
+        while (status == SLAM_GNAV_PATH_CUT && len < max_len) {
             if (lane == 0) path[2 * len] = x, path[2 * len + 1] = y;
             ++len;
             if (pu == 0) { // only a goal has potential 0: every move costs at least 2
-                status = 0;
+                status = SLAM_GNAV_PATH_REACHED;
                 break;
             }
             if (len == max_len) break;
@@ -248,7 +247,7 @@ __global__ __launch_bounds__(64) void gnav_path_kernel(Plane P, int x, int y, in
             }
             const unsigned long long found = __ballot(ok);
             if (!found) { // not on an exact field; the caller's plane was not the one the field was computed on
-                status = 3;
+                status = SLAM_GNAV_PATH_NOT_CONVERGED;
                 len = 0;
                 break;
             }
@@ -262,8 +261,8 @@ __global__ __launch_bounds__(64) void gnav_path_kernel(Plane P, int x, int y, in
     if (lane == 0) {
         len_status[0] = len;
         len_status[1] = status;
-        st->ints[kPathLen] = (status == 0 || status == 2) ? prior + len : 0;
-        st->ints[kPathStatus] = status;
+        st->s.last_path_len = (status == SLAM_GNAV_PATH_REACHED || status == SLAM_GNAV_PATH_CUT) ? prior + len : 0;
+        st->s.last_path_status = status;
     }
 }
 
@@ -329,13 +328,11 @@ int compute_on(slam_gnav *h, const uint8_t *d_cost, const int32_t *d_goals, int 
 
 extern "C" {
 
-void slam_gnav_default_params(int *orth_w, int *diag_w, int *neutral, int *lethal_from, int *unknown_step)
+void slam_gnav_default_params(slam_gnav_params *p)
 {
-    if (orth_w) *orth_w = 12; // 12 : 17 is within 0.2 % of 1 : sqrt 2
-    if (diag_w) *diag_w = 17;
-    if (neutral) *neutral = 50;
-    if (lethal_from) *lethal_from = 253; // costmap_2d INSCRIBED_INFLATED_OBSTACLE
-    if (unknown_step) *unknown_step = 0;
+    if (!p) return;
+    p->orth_w = 12, p->diag_w = 17; // within 0.2 % of 1 : sqrt 2
+    p->neutral = 50, p->lethal_from = 253, p->unknown_step = 0; // 253: costmap_2d INSCRIBED_INFLATED_OBSTACLE
 }
 
 int slam_grid_step_table(int neutral, int lethal_from, int unknown_step, uint32_t *table, int n)
@@ -348,17 +345,24 @@ int slam_grid_step_table(int neutral, int lethal_from, int unknown_step, uint32_
     return SLAM_OK;
 }
 
-int slam_gnav_create(int size_x, int size_y, int orth_w, int diag_w, slam_gnav_t **out)
+int slam_gnav_create(int size_x, int size_y, const slam_gnav_params *params, slam_gnav_t **out)
 {
     SLAM_REQUIRE(out, SLAM_E_INVALID, "slam_gnav_create: null out pointer");
     *out = nullptr;
+    slam_gnav_params p;
+    slam_gnav_default_params(&p);
+    if (params) p = *params;
     SLAM_REQUIRE(size_x > 0 && size_y > 0 && size_x <= 32767 && size_y <= 32767, SLAM_E_INVALID, "slam_gnav_create: size must be 1..32767 cells");
-    SLAM_REQUIRE(orth_w >= 1 && orth_w <= kGnavMaxWeight && diag_w >= 1 && diag_w <= kGnavMaxWeight, SLAM_E_INVALID,
+    SLAM_REQUIRE(p.orth_w >= 1 && p.orth_w <= kGnavMaxWeight && p.diag_w >= 1 && p.diag_w <= kGnavMaxWeight, SLAM_E_INVALID,
                  "slam_gnav_create: orth_w and diag_w must be 1..255");
+    uint32_t    table[kGnavTableLen];
+    const char *why = "";
+    SLAM_REQUIRE(grid_step_table(p.neutral, p.lethal_from, p.unknown_step, table, kGnavTableLen, &why) == 0, SLAM_E_INVALID,
+                 "slam_gnav_create: %s", why);
     SLAM_TRY(require_device());
     std::unique_ptr<slam_gnav> h(new (std::nothrow) slam_gnav());
     SLAM_REQUIRE(h, SLAM_E_NOMEM, "slam_gnav_create: out of host memory");
-    h->sx = size_x, h->sy = size_y, h->orth_w = orth_w, h->diag_w = diag_w;
+    h->sx = size_x, h->sy = size_y, h->orth_w = p.orth_w, h->diag_w = p.diag_w;
     h->tiles_x = (size_x + kTile - 1) / kTile, h->tiles_y = (size_y + kTile - 1) / kTile;
     h->n_tiles = h->tiles_x * h->tiles_y;
     h->cells = (size_t)size_x * size_y;
@@ -369,10 +373,6 @@ int slam_gnav_create(int size_x, int size_y, int orth_w, int diag_w, slam_gnav_t
     SLAM_TRY(h->d_state.alloc(sizeof(NavState)));
     SLAM_TRY(h->d_stage.alloc(sizeof(int32_t) * (2 * (size_t)kStage + 2)));
     SLAM_TRY(h->h_word.alloc(sizeof(long long)));
-    uint32_t table[kGnavTableLen];
-    int      neutral, lethal_from, unknown_step;
-    slam_gnav_default_params(nullptr, nullptr, &neutral, &lethal_from, &unknown_step);
-    (void)grid_step_table(neutral, lethal_from, unknown_step, table, kGnavTableLen, nullptr);
     SLAM_HIP(hipMemcpy(h->d_table.get(), table, sizeof(table), hipMemcpyHostToDevice));
     SLAM_HIP(hipMemset(h->d_state.get(), 0, sizeof(NavState)));
     *out = h.release();
@@ -421,7 +421,7 @@ int slam_gnav_compute(slam_gnav_t *h, const uint8_t *cost, const int32_t *goals,
     for (long long done = 0; done < limit;) {
         const int b = (int)std::min<long long>(kBatch, limit - done);
         SLAM_TRY(enqueue_rounds(h, b, nullptr));
-        SLAM_HIP(hipMemcpyAsync(h->h_word.get(), &h->d_state.get()->ints[kConverged], sizeof(long long), hipMemcpyDeviceToHost, nullptr));
+        SLAM_HIP(hipMemcpyAsync(h->h_word.get(), &h->d_state.get()->s.converged, sizeof(long long), hipMemcpyDeviceToHost, nullptr));
         SLAM_HIP(hipStreamSynchronize(nullptr));
         done += b;
         if (*h->h_word.get()) return SLAM_OK;
@@ -466,7 +466,7 @@ int slam_gnav_path(slam_gnav_t *h, int sx, int sy, int max_len, int32_t *path, i
     // In pieces of at most kStage cells through the staging block; a piece that was cut before max_len is continued from its
     // last cell, which the next piece writes again.
     int32_t *d_piece = h->d_stage.get(), *d_ls = d_piece + 2 * (size_t)kStage;
-    int      total = 0, x = sx, y = sy, st = 2;
+    int      total = 0, x = sx, y = sy, st = SLAM_GNAV_PATH_CUT;
     for (;;) {
         const int prior = total ? total - 1 : 0, n = std::min(max_len - prior, kStage);
         int32_t   ls[2];
@@ -475,12 +475,12 @@ int slam_gnav_path(slam_gnav_t *h, int sx, int sy, int max_len, int32_t *path, i
         SLAM_HIP(hipMemcpy(ls, d_ls, sizeof(ls), hipMemcpyDeviceToHost));
         if (ls[0] > 0) SLAM_HIP(hipMemcpy(path + 2 * (size_t)prior, d_piece, sizeof(int32_t) * 2 * (size_t)ls[0], hipMemcpyDeviceToHost));
         st = ls[1];
-        if (st == 1 || st == 3) {
+        if (st == SLAM_GNAV_PATH_NO_START || st == SLAM_GNAV_PATH_NOT_CONVERGED) {
             total = 0;
             break;
         }
         total = prior + ls[0];
-        if (st == 0 || total >= max_len) break;
+        if (st == SLAM_GNAV_PATH_REACHED || total >= max_len) break;
         x = path[2 * (size_t)(total - 1)], y = path[2 * (size_t)(total - 1) + 1];
     }
     *len = total;
@@ -488,13 +488,11 @@ int slam_gnav_path(slam_gnav_t *h, int sx, int sy, int max_len, int32_t *path, i
     return SLAM_OK;
 }
 
-int slam_gnav_read_state(slam_gnav_t *h, int64_t ints[SLAM_GNAV_STATE_INTS])
+int slam_gnav_read_state(slam_gnav_t *h, slam_gnav_state *state)
 {
-    SLAM_REQUIRE(h && ints, SLAM_E_INVALID, "slam_gnav_read_state: bad arguments");
+    SLAM_REQUIRE(h && state, SLAM_E_INVALID, "slam_gnav_read_state: bad arguments");
     SLAM_HIP(hipDeviceSynchronize());
-    NavState s;
-    SLAM_HIP(hipMemcpy(&s, h->d_state.get(), sizeof(s), hipMemcpyDeviceToHost));
-    for (int i = 0; i < SLAM_GNAV_STATE_INTS; ++i) ints[i] = (int64_t)s.ints[i];
+    SLAM_HIP(hipMemcpy(state, &h->d_state.get()->s, sizeof(*state), hipMemcpyDeviceToHost)); // the record's first member
     return SLAM_OK;
 }
 

@@ -46,19 +46,8 @@ struct State {
     ScanHead           head, dbg;
 };
 
-// a motion as the device reads it (slam_mi355x.h): 48 bytes
-struct Motion {
-    double dx, dy, sx, sy, sk;
-    int    dk, pad;
-};
-static_assert(sizeof(Motion) == SLAM_PF_MOTION_BYTES, "the motion's layout is part of the C-ABI");
-
-// the parameters in force (slam_mi355x.h lists them)
-struct Params {
-    int      n_particles, n_angles, gauss_bits, weight_len, weight_shift, resample_num, resample_den;
-    double   weight_scale;
-    uint64_t seed;
-};
+using Motion = slam_pf_motion; // as the device reads it
+using Params = slam_pf_params;
 
 struct Tables {
     const double   *cs, *G;
@@ -393,18 +382,12 @@ struct slam_pf {
 
 extern "C" {
 
-void slam_pf_default_params(int *n_particles, int *n_angles, int *gauss_bits, int *weight_len, int *weight_shift, double *weight_scale,
-                            int *resample_num, int *resample_den, uint64_t *seed)
+void slam_pf_default_params(slam_pf_params *p)
 {
-    if (n_particles) *n_particles = 1024;
-    if (n_angles) *n_angles = 4096;
-    if (gauss_bits) *gauss_bits = 12;
-    if (weight_len) *weight_len = 1024;
-    if (weight_shift) *weight_shift = 4;
-    if (weight_scale) *weight_scale = 1024.0;
-    if (resample_num) *resample_num = 1;
-    if (resample_den) *resample_den = 2;
-    if (seed) *seed = 1;
+    if (!p) return;
+    p->n_particles = 1024, p->n_angles = 4096, p->gauss_bits = 12;
+    p->weight_len = 1024, p->weight_shift = 4, p->weight_scale = 1024.0;
+    p->resample_num = 1, p->resample_den = 2, p->seed = 1;
 }
 
 int slam_pf_angle_table(int n_angles, double *cs, int n)
@@ -494,12 +477,13 @@ static int create_filled(slam_pf *s)
     return slam_pf_set_tables(s, cs.data(), (int)cs.size(), G.data(), (int)G.size(), wtab.data(), (int)wtab.size());
 }
 
-int slam_pf_create(int n_particles, int n_angles, int gauss_bits, int weight_len, int weight_shift, double weight_scale, int resample_num,
-                   int resample_den, uint64_t seed, slam_pf_t **out)
+int slam_pf_create(const slam_pf_params *params, slam_pf_t **out)
 {
     SLAM_REQUIRE(out, SLAM_E_INVALID, "slam_pf_create: null out pointer");
     *out = nullptr;
-    const Params p = {n_particles, n_angles, gauss_bits, weight_len, weight_shift, resample_num, resample_den, weight_scale, seed};
+    Params p;
+    slam_pf_default_params(&p);
+    if (params) p = *params;
     SLAM_TRY(check_params(p));
     SLAM_TRY(require_device());
     slam_pf *s = new (std::nothrow) slam_pf();
@@ -553,20 +537,21 @@ int slam_pf_read_weights(slam_pf_t *pf, int64_t *acc, uint32_t *w)
     return SLAM_OK;
 }
 
-int slam_pf_read_state(slam_pf_t *pf, int64_t ints[SLAM_PF_STATE_INTS], double est[3])
+int slam_pf_read_state(slam_pf_t *pf, slam_pf_state *out)
 {
-    SLAM_REQUIRE(pf && ints && est, SLAM_E_INVALID, "slam_pf_read_state: null argument");
+    SLAM_REQUIRE(pf && out, SLAM_E_INVALID, "slam_pf_read_state: null argument");
     State s;
     SLAM_HIP(hipDeviceSynchronize()); // whatever stream the last update ran on
     SLAM_HIP(hipMemcpy(&s, pf->state.p, sizeof(State), hipMemcpyDeviceToHost));
-    const int64_t v[SLAM_PF_STATE_INTS] = {(int64_t)s.t, pf->n(), s.resampled, s.degenerate, s.W ? s.best : -1, s.refused, s.n_resamples,
-                                           s.W ? (int64_t)(s.amax_key ^ 0x8000000000000000ull) : 0, (int64_t)s.W, (int64_t)s.S2, s.MX, s.MY, s.MC, s.MS};
-    std::memcpy(ints, v, sizeof(v));
+    out->t = (int64_t)s.t, out->n = pf->n(), out->resampled = s.resampled, out->degenerate = s.degenerate;
+    out->best = s.W ? s.best : -1, out->refused = s.refused, out->n_resamples = s.n_resamples;
+    out->A_max = s.W ? (int64_t)(s.amax_key ^ 0x8000000000000000ull) : 0;
+    out->W = (int64_t)s.W, out->S2 = (int64_t)s.S2, out->MX = s.MX, out->MY = s.MY, out->MC = s.MC, out->MS = s.MS;
     if (s.W) {
         const double den = (double)s.W * 65536.0;
-        est[0] = (double)s.MX / den, est[1] = (double)s.MY / den, est[2] = std::atan2((double)s.MS, (double)s.MC);
+        out->x = (double)s.MX / den, out->y = (double)s.MY / den, out->theta = std::atan2((double)s.MS, (double)s.MC);
     } else {
-        est[0] = est[1] = est[2] = std::nan("");
+        out->x = out->y = out->theta = std::nan("");
     }
     return SLAM_OK;
 }
@@ -589,9 +574,8 @@ static int predict_launch(slam_pf_t *pf, const Motion *d_motion, bool init, doub
     return SLAM_OK;
 }
 
-int slam_pf_predict_dev(slam_pf_t *pf, const void *d_motion_bytes, slam_stream_t stream)
+int slam_pf_predict_dev(slam_pf_t *pf, const slam_pf_motion *d_motion, slam_stream_t stream)
 {
-    const Motion *d_motion = static_cast<const Motion *>(d_motion_bytes);
     SLAM_REQUIRE(pf && d_motion, SLAM_E_INVALID, "slam_pf_predict_dev: null argument");
     SLAM_TRY(predict_launch(pf, d_motion, false, 0.0, 0.0, 0, as_stream(stream)));
     hipLaunchKernelGGL(pf_advance_kernel, dim3(1), dim3(1), 0, as_stream(stream), pf->st(), d_motion);
@@ -599,14 +583,14 @@ int slam_pf_predict_dev(slam_pf_t *pf, const void *d_motion_bytes, slam_stream_t
     return SLAM_OK;
 }
 
-int slam_pf_predict(slam_pf_t *pf, double dx, double dy, double sx, double sy, double sk, int dk)
+int slam_pf_predict(slam_pf_t *pf, const slam_pf_motion *motion)
 {
     SLAM_REQUIRE(pf, SLAM_E_INVALID, "slam_pf_predict: null handle");
-    const Motion m = {dx, dy, sx, sy, sk, dk, 0};
-    const char  *why = motion_refusal(m);
+    SLAM_REQUIRE(motion, SLAM_E_INVALID, "slam_pf_predict: null motion");
+    const char *why = motion_refusal(*motion);
     SLAM_REQUIRE(!why, SLAM_E_INVALID, "slam_pf_predict: %s", why);
-    SLAM_HIP(hipMemcpy(pf->motion.p, &m, sizeof(m), hipMemcpyHostToDevice));
-    SLAM_TRY(slam_pf_predict_dev(pf, pf->motion.p, nullptr));
+    SLAM_HIP(hipMemcpy(pf->motion.p, motion, sizeof(Motion), hipMemcpyHostToDevice));
+    SLAM_TRY(slam_pf_predict_dev(pf, pf->motion.as<Motion>(), nullptr));
     SLAM_HIP(hipStreamSynchronize(nullptr));
     return SLAM_OK;
 }

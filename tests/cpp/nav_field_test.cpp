@@ -56,10 +56,10 @@ int main(int argc, char **argv)
         std::vector<uint32_t> pot;
         std::vector<int32_t>  cells;
         int                   status = -1;
-        int64_t               st[SLAM_GNAV_STATE_INTS];
+        slam_gnav_state       st;
         if (!(nf.read(&pot) && nf.path((int)pp[7], (int)pp[8], &cells, &status) && nf.state(st))) return 14;
-        std::vector<int64_t> state(st, st + SLAM_GNAV_STATE_INTS);
-        state.push_back(status);
+        const std::vector<int64_t> state = {st.rounds,          st.converged,     st.goals_used,       st.goals_skipped,
+                                            st.tiles_processed, st.last_path_len, st.last_path_status, status};
         if (!(save(d + "a_pot.u32", pot) && save(d + "a_path.i32", cells) && save(d + "a_state.i64", state))) return 15;
     }
     // ---- the map's planner
@@ -71,9 +71,9 @@ int main(int argc, char **argv)
     slam_amd::MLS            m((int)prm[0], (int)prm[1], prm[2], true);
     m.setMinClusterPoints(0);
     if (m.enablePlanner()) return 20;                                       // needs enableCostmap first
-    if (m.planPath(prm[9], prm[10], prm[11], prm[12]).status != 3) return 21; // nothing before enablePlanner
+    if (m.planPath(prm[9], prm[10], prm[11], prm[12]).status != SLAM_GNAV_PATH_NOT_CONVERGED) return 21; // nothing before enablePlanner
     if (!m.enableCostmap(prm[5], prm[6], prm[7], (int)prm[8])) return 22;
-    if (m.enablePlanner(0, 17)) return 23;                                  // a weight out of range: refused
+    if (m.enablePlanner(slam_amd::NavParams(0, 17))) return 23;             // a weight out of range: refused
     if (!m.enablePlanner()) return 24;
     for (int k = 0; k < 2; ++k)
         m.addToMap(obs[k].data(), (int)(obs[k].size() / 4), gnd[k].data(), (int)(gnd[k].size() / 4), pose[k][0], pose[k][1], 4);

@@ -49,8 +49,8 @@ static void print_step(const char *name, slam_amd::ParticleFilter &pf, bool ok)
     ok = pf.particles(x, y, k) && pf.weights(acc, w) && pf.state(s) && ok;
     std::printf("%s %d %u %d %d %d %d %d %" PRId64 " %" PRId64 " %" PRIu64 " %" PRIu64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64
                 " %a %a %a %016" PRIx64 " %016" PRIx64 " %016" PRIx64 " %016" PRIx64 " %016" PRIx64 "\n",
-                name, (int)ok, s.t, s.n, s.resampled, s.degenerate, s.best, s.refused, s.n_resamples, s.A_max, s.W, s.S2, s.MX, s.MY, s.MC, s.MS, s.x,
-                s.y, s.theta, digest(x), digest(y), digest(k), digest(acc), digest(w));
+                name, (int)ok, (uint32_t)s.t, (int)s.n, (int)s.resampled, (int)s.degenerate, (int)s.best, (int)s.refused, s.n_resamples, s.A_max,
+                (uint64_t)s.W, (uint64_t)s.S2, s.MX, s.MY, s.MC, s.MS, s.x, s.y, s.theta, digest(x), digest(y), digest(k), digest(acc), digest(w));
 }
 
 int main(int argc, char **argv)

@@ -188,7 +188,10 @@ def test_python_structs_mirror_the_header(tmp_path):
     import subprocess
     structs = {s: f for h in HEADERS for s, f in header_structs(h).items()}
     classes = dict({c: getattr(api, py) for py, c in api.STRUCTS.items()}, slam_csm_posterior=api.CsmPosterior)
-    assert sorted(structs) == sorted(classes) == sorted(api._H.structs) and len(structs) == 31
+    assert sorted(structs) == sorted(classes) == sorted(api._H.structs) and len(structs) == 36
+    assert {"slam_pf_params", "slam_pf_motion", "slam_pf_state", "slam_gnav_params", "slam_gnav_state"} <= set(structs)
+    # declarators that share a line (`int64_t W, S2;`) are read one by one
+    assert [f for f, _ in structs["slam_pf_state"]] == [f for f, _ in api.PfState._fields_] and len(structs["slam_pf_state"]) == 17
     for py, c in api.STRUCTS.items():
         assert getattr(api, py) is api._H.structs[c]
     assert issubclass(api.CsmPosterior, api._H.structs["slam_csm_posterior"])

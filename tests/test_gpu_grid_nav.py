@@ -75,6 +75,21 @@ def test_saturation_reads_far_and_never_a_wrapped_number():
     nf.close()
 
 
+def test_the_params_install_the_table_they_describe():
+    c = N.case("random_97x83_d2")
+    by_params = api.NavField(c["sx"], c["sy"], c["orth_w"], c["diag_w"], params=api.gnav_default_params(neutral=7))
+    by_table = api.NavField(c["sx"], c["sy"], c["orth_w"], c["diag_w"])
+    by_table.compute(c["cost"], c["goals"])
+    default = by_table.potential()
+    by_table.set_table(api.step_table(neutral=7))
+    pots = []
+    for nf in (by_params, by_table):
+        nf.compute(c["cost"], c["goals"])
+        pots.append(nf.potential())
+        nf.close()
+    assert np.array_equal(pots[0], pots[1]) and not np.array_equal(pots[0], default)
+
+
 def test_too_few_rounds_then_a_continued_call():
     c, want = N.case("130x70_maze"), N.expected("130x70_maze")
     nf = field_for(c)

@@ -104,6 +104,18 @@ def test_a_motion_that_breaks_the_rules_is_refused_on_the_device_too():
     pf.close()
 
 
+@gpu
+def test_a_filter_created_with_null_params_has_the_defaults():
+    import ctypes as C
+    L, h, s = api.lib(), C.c_void_p(), api.PfState()
+    api.check(L.slam_pf_create(None, C.byref(h)))
+    try:
+        api.check(L.slam_pf_read_state(h, C.byref(s)))
+        assert (s.n, s.t) == (F.DEFAULTS["n_particles"], 0) == (1024, 0)
+    finally:
+        L.slam_pf_destroy(h)
+
+
 # -------------------------------------------------------------------------------------------------------------- resampling
 @pytest.fixture(scope="module")
 def big_filter():

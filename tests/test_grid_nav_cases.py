@@ -115,7 +115,11 @@ def test_what_the_cases_are_there_for():
 # ------------------------------------------------------------------------------------------------------------ the step table
 def test_the_table_maker_against_its_formula(L):
     d = api.gnav_default_params()
-    assert d == dict(orth_w=12, diag_w=17, neutral=50, lethal_from=253, unknown_step=0)
+    assert [f for f, _ in d._fields_] == ["orth_w", "diag_w", "neutral", "lethal_from", "unknown_step"]
+    assert (d.orth_w, d.diag_w, d.neutral, d.lethal_from, d.unknown_step) == (12, 17, 50, 253, 0)
+    assert (api.GNAV_REACHED, api.GNAV_NO_START, api.GNAV_CUT, api.GNAV_NOT_CONVERGED) == (0, 1, 2, 3)
+    assert [f for f, _ in api.GnavState._fields_] == ["rounds", "converged", "goals_used", "goals_skipped", "tiles_processed", "last_path_len",
+                                                      "last_path_status"]
     assert (N.ORTH_W, N.DIAG_W, N.NEUTRAL, N.LETHAL_FROM, N.UNKNOWN_STEP) == (12, 17, 50, 253, 0)
     assert api.GNAV_FAR == N.FAR == 0xFFFFFFFF
     t = api.step_table()
@@ -189,11 +193,21 @@ def test_every_entry_point_refuses_before_a_device_is_touched(L):
         assert name.encode() in L.slam_last_error(), (name, L.slam_last_error())
 
     for sx, sy in ((0, 5), (5, 0), (-1, 5), (5, -1), (32768, 5), (5, 32768)):
-        refused("slam_gnav_create", sx, sy, 12, 17, C.byref(h))
-        assert not h.value
+        for params in (None, C.byref(api.gnav_default_params())):    # null params are the defaults
+            h.value = 5
+            refused("slam_gnav_create", sx, sy, params, C.byref(h))
+            assert not h.value                                       # the out pointer is nulled
     for ow, dw in ((0, 17), (12, 0), (256, 17), (12, 256), (-1, 17), (12, -5)):
-        refused("slam_gnav_create", 10, 10, ow, dw, C.byref(h))
-    refused("slam_gnav_create", 10, 10, 12, 17, None)
+        refused("slam_gnav_create", 10, 10, C.byref(api.gnav_default_params(orth_w=ow, diag_w=dw)), C.byref(h))
+    # the table's parameters, by the bounds of slam_grid_step_table (test_the_table_maker_refuses)
+    for neutral, lethal_from, unknown_step in ((0, 253, 0), (-1, 253, 0), ((1 << 19) + 1, 253, 0), (50, 0, 0), (50, 257, 0), (50, -3, 0),
+                                               (50, 253, -1), (50, 253, (1 << 20) + 1)):
+        h.value = 5
+        refused("slam_gnav_create", 10, 10, C.byref(api.gnav_default_params(neutral=neutral, lethal_from=lethal_from, unknown_step=unknown_step)),
+                C.byref(h))
+        assert not h.value
+    refused("slam_gnav_create", 10, 10, C.byref(api.gnav_default_params()), None)
+    refused("slam_gnav_create", 10, 10, None, None)
     L.slam_gnav_destroy(None)                                        # a null handle is nothing to free
     good = api.step_table()
     refused("slam_gnav_set_table", None, good.ctypes.data_as(vp), 256)
@@ -223,7 +237,7 @@ def test_every_entry_point_refuses_before_a_device_is_touched(L):
     refused("slam_gnav_read", fake, p)                               # nothing has been computed
     refused("slam_gnav_potential_dev", None, C.byref(h))
     refused("slam_gnav_potential_dev", fake, None)
-    refused("slam_gnav_read_state", None, p)
+    refused("slam_gnav_read_state", None, C.byref(api.GnavState()))
     refused("slam_gnav_read_state", fake, None)
     # the path
     n, st = C.c_int(), C.c_int()
@@ -245,7 +259,6 @@ def test_every_entry_point_refuses_before_a_device_is_touched(L):
     refused("slam_grid_nav_field", fake, fake, fake, None, 1, 0, None)
     refused("slam_grid_nav_field", fake, fake, fake, p, 0, 0, None)
     refused("slam_grid_nav_field", fake, fake, fake, p, 1, -1, None)
-    # defaults: every pointer nullable
-    L.slam_gnav_default_params(None, None, None, None, None)
+    L.slam_gnav_default_params(None)                                 # a null pointer: nothing to fill
     assert issubclass(api.NavField, api._Handle) and api.NavField._destroy in api.EXPORTS
     assert "close" not in vars(api.NavField) and "__del__" not in vars(api.NavField)

@@ -100,7 +100,12 @@ def test_the_entry_points_are_declared_and_exported(L):
     assert (p.n_particles, p.n_angles, p.gauss_bits, p.weight_len, p.weight_shift, p.resample_num, p.resample_den, p.weight_scale, p.seed) == \
         tuple(F.DEFAULTS[k] for k in ("n_particles", "n_angles", "gauss_bits", "weight_len", "weight_shift", "resample_num", "resample_den",
                                       "weight_scale", "seed"))
-    assert api.PF_MOTION_DTYPE.itemsize == 48 and api.PF_MOTION_DTYPE.fields["dk"][1] == 40 and len(api.PF_STATE_INTS) == 14
+    assert [f for f, _ in api.PfState._fields_] == ["t", "n", "resampled", "degenerate", "best", "refused", "n_resamples", "A_max", "W", "S2",
+                                                    "MX", "MY", "MC", "MS", "x", "y", "theta"]
+    assert C.sizeof(api.PfState) == 136
+    assert C.sizeof(api.PfMotion) == 48 and api.PfMotion.dk.offset == 40
+    assert api.PF_MOTION_DTYPE.itemsize == 48 and api.PF_MOTION_DTYPE.fields["dk"][1] == 40
+    assert api.PF_MOTION_DTYPE.names == ("dx", "dy", "sx", "sy", "sk", "dk")
 
 
 @pytest.mark.parametrize("A", (64, 4096, 65536))
@@ -180,9 +185,9 @@ BAD_PARAMS = [(dict(n_particles=0), "n_particles"), (dict(n_particles=-1), "n_pa
 def test_create_refuses_before_it_touches_a_device(L, kw, word):
     h = C.c_void_p(5)
     p = api.pf_default_params(**kw)
-    refused(L, L.slam_pf_create, word, *p.args(), C.byref(h))
+    refused(L, L.slam_pf_create, word, C.byref(p), C.byref(h))
     assert not h.value                                                                    # the out pointer is nulled, no handle leaks
-    refused(L, L.slam_pf_create, "null out", *p.args(), None)
+    refused(L, L.slam_pf_create, "null out", C.byref(p), None)
 
 
 BAD_MOTIONS = [((0.0, 0.0, float("nan"), 0.0, 0.0, 0), "sigma"), ((0.0, 0.0, 0.0, float("inf"), 0.0, 0), "sigma"),
@@ -198,19 +203,22 @@ def test_motion_arguments_are_refused_before_a_device_is_touched(L, m, word):
     refusal comes first (no filter can exist on a machine without a device)"""
     assert not F.motion_ok(m)
     fake = (C.c_char * 4096)()                                                            # never read: the motion is checked first
-    refused(L, L.slam_pf_predict, word, C.addressof(fake), *m)
+    refused(L, L.slam_pf_predict, word, C.addressof(fake), C.byref(api.PfMotion(*m)))
     ref = F.Filter(np.zeros(128), np.zeros(16), np.array([65536, 0]), n_particles=3, n_angles=64, gauss_bits=4, weight_len=2)
     ref.predict(m)
     assert (ref.t, ref.refused) == (0, 1)                                                 # the restatement counts and skips it
 
 
 def test_null_handles_are_refused(L):
-    one, ints = np.zeros(4), np.zeros(14, np.int64)
-    refused(L, L.slam_pf_predict, "slam_pf_predict", None, 0.0, 0.0, 0.0, 0.0, 0.0, 0)
+    one, fake = np.zeros(4), (C.c_char * 4096)()                                          # fake: a handle that is never read
+    refused(L, L.slam_pf_create, "null out", None, None)                                  # (null params are the defaults)
+    refused(L, L.slam_pf_predict, "slam_pf_predict", None, C.byref(api.PfMotion()))
+    refused(L, L.slam_pf_predict, "null motion", C.addressof(fake), None)
     refused(L, L.slam_pf_predict_dev, "slam_pf_predict_dev", None, None, None)
     refused(L, L.slam_pf_update, "slam_pf_update", None, None, vp(one), 2, 0, 0.0, 0.0)
     refused(L, L.slam_pf_update_dev, "slam_pf_update_dev", None, None, vp(one), 2, 0, 0.0, 0.0, None)
-    refused(L, L.slam_pf_read_state, "slam_pf_read_state", None, vp(ints), vp(one))
+    refused(L, L.slam_pf_read_state, "slam_pf_read_state", None, C.byref(api.PfState()))
+    refused(L, L.slam_pf_read_state, "slam_pf_read_state", C.addressof(fake), None)
     refused(L, L.slam_pf_set_particles, "slam_pf_set_particles", None, vp(one), vp(one), vp(one), 1)
     refused(L, L.slam_pf_read_particles, "slam_pf_read_particles", None, None, None, None)
     refused(L, L.slam_pf_read_weights, "slam_pf_read_weights", None, None, None)
@@ -219,6 +227,7 @@ def test_null_handles_are_refused(L):
     refused(L, L.slam_pf_random_words_dev, "slam_pf_random_words_dev", None, 0, 1, 0, 0, None)
     refused(L, L.slam_pf_resample_indices_dev, "slam_pf_resample_indices_dev", None, None, 1, 0, None, None)
     L.slam_pf_destroy(None)
+    L.slam_pf_default_params(None)
 
 
 @pytest.mark.skipif(api.device_count() != 0, reason="a GPU is present")
