@@ -9,6 +9,7 @@
 // cell per beam.  Each beam's cells inside a tile come from the closed form of
 // the integer Bresenham line, so clipping to the tile cannot change them.
 #pragma once
+#include "grid_clip.hpp"
 #include "grid_view.hpp"
 
 using namespace slam;
@@ -304,21 +305,6 @@ __global__ __launch_bounds__(kTileThreads) void tile_scan_kernel(const int *cnt,
     for (int i = threadIdx.x; i <= n_tiles; i += kTileThreads) cursor[i] = 0; // (behind the cursors: tile write-backs of the launch)
 }
 
-// floor(num / den) for 0 <= num < 2^31, 1 <= den < 2^16, when the quotient is
-// below 2^16 (larger quotients saturate to 65536: callers clamp against <= 32767).
-// One float multiply + an exact remainder fix instead of an integer division:
-// with rden within 1 ulp of 1/den the float quotient is off by < 2^16 * 2^-21,
-// so truncation lands on floor or floor +- 1 and the remainder test repairs it.
-__device__ inline int floor_div_small(int num, int den, float rden)
-{
-    const float qf = (float)num * rden;
-    if (qf >= 65536.0f) return 65536;
-    int       q = (int)qf;
-    const int r = (int)((unsigned)num - (unsigned)__mul24(q, den));
-    q += (r >= den) - (r < 0);
-    return q;
-}
-
 // Tiled raycast.  A persistent workgroup works on ONE tile at a time: it zeroes a 128x128 tile of packed
 // (hits<<16 | misses) counters in LDS, takes 64-beam blocks from the tile's work list a chunk at a time (the tile's
 // cursor: one global atomic per chunk), its 16 wavefronts pull the chunk's blocks from an LDS counter, and it keeps
@@ -509,45 +495,14 @@ __global__ __launch_bounds__(kTileThreads, 8) void raycast_tiled_kernel(GridView
             const int x0 = (short)(raw.x & 0xffff), y0 = raw.x >> 16;
             const int x1 = (short)(raw.y & 0xffff), y1 = raw.y >> 16;
             const bool maybe = x0 >= 0 && max(x0, x1) >= tx0 && min(x0, x1) <= tx1 && max(y0, y1) >= ty0 &&
-                               min(y0, y1) <= ty1;
+                               min(y0, y1) <= ty1; // (a live beam and clip_box_meets_tile)
             if (__any(maybe) && !(ablate & 16)) {
-                const int dx = abs(x1 - x0), dy = abs(y1 - y0);
-                // u = major axis, v = minor axis; step i in [0, du]; i == du is the end cell (hit)
-                const bool xm = dx >= dy;
-                const int  u0 = xm ? x0 : y0, v0 = xm ? y0 : x0, u1 = xm ? x1 : y1, v1 = xm ? y1 : x1;
-                const int  du = xm ? dx : dy, dv = xm ? dy : dx;
-                const int  tu0 = xm ? tx0 : ty0, tu1 = xm ? tx1 : ty1;
-                const int  tv0 = xm ? ty0 : tx0, tv1 = xm ? ty1 : tx1;
-                const bool up = u1 > u0, vp = v1 > v0;
-                int        i_lo = max(0, up ? tu0 - u0 : u0 - tu1);
-                int        i_hi = min(du, up ? tu1 - u0 : u0 - tu0);
-                den = max(2 * du, 1);
-                dv2 = 2 * dv;
-                const float rden = __builtin_amdgcn_rcpf((float)den); // 1 ulp is ample: see floor_div_small
-                // minor axis: v0 + sv*k in [tv0, tv1]  <=>  k in [k_lo, k_hi]
-                const int k_lo = vp ? tv0 - v0 : v0 - tv1;
-                const int k_hi = min(vp ? tv1 - v0 : v0 - tv0, dv);
-                bool      enters = maybe && k_hi >= 0 && k_lo <= dv;
-                if (enters && dv > 0 && !(ablate & 32)) {
-                    const float rdv2 = __builtin_amdgcn_rcpf((float)dv2);
-                    // k_i >= k_lo  <=>  i >= ceil((2*du*k_lo - du) / (2*dv))
-                    if (k_lo > 0) i_lo = max(i_lo, floor_div_small(__mul24(den, k_lo) - du + dv2 - 1, dv2, rdv2));
-                    // k_i <= k_hi  <=>  i <= floor((2*du*(k_hi+1) - du - 1) / (2*dv))
-                    i_hi = min(i_hi, floor_div_small(__mul24(den, k_hi + 1) - du - 1, dv2, rdv2));
-                }
-                enters = enters && i_lo <= i_hi;
-                if (enters && !(ablate & 64)) {
-                    const int num = __mul24(i_lo, dv2) + du; // < 2^31
-                    const int k = du ? floor_div_small(num, den, rden) : 0;
-                    e = num - __mul24(k, den); // running remainder in [0, den)
-                    const int ul = (up ? u0 + i_lo : u0 - i_lo) - tu0, vl = (vp ? v0 + k : v0 - k) - tv0;
-                    a = xm ? vl * kTileStride + ul : ul * kTileStride + vl;
-                    step_u = (up ? 1 : -1) * (xm ? 1 : kTileStride);
-                    step_v = (vp ? 1 : -1) * (xm ? kTileStride : 1);
-                    rem = i_hi - i_lo + 1;
-                    to_end = du - i_lo; // steps until the end cell
-                    did += (unsigned)rem;
-                }
+                // (grid_clip.hpp; the reciprocals are the device's own, 1 ulp is ample: see floor_div_small)
+                const float    rden = __builtin_amdgcn_rcpf((float)clip_den(x0, y0, x1, y1));
+                const float    rdv2 = __builtin_amdgcn_rcpf((float)clip_dv2(x0, y0, x1, y1));
+                const TileClip c = clip_beam_to_tile(x0, y0, x1, y1, tx0, ty0, tx1, ty1, kTileStride, rden, rdv2, maybe, ablate);
+                rem = c.rem, a = c.a, e = c.e, dv2 = c.dv2, den = c.den, step_u = c.step_u, step_v = c.step_v, to_end = c.to_end;
+                did += (unsigned)rem;
             }
             if (ablate & 1) rem = 0;
             // ---- the end cell's hit if the beam ends in this tile (its last step here is then the end cell),
