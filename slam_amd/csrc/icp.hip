@@ -1105,82 +1105,86 @@ __global__ __launch_bounds__(256) void icp_nearest_kernel(ModelView mv, int cls,
 
 namespace {
 
-template <int G, bool LDS, typename StartT, int MODE, int SWEEP = 0>
-int launch_fit_t(slam_icp *h, const FitArgs &fa, int n_scans, hipStream_t st)
+// One launch of a registration kernel: the kernel's limit of dynamic LDS raised where it needs more than the 48 KiB every
+// kernel may have, the launch, and what the launch itself reports.
+template <typename... Params, typename... Args>
+int launch_kernel(void (*kern)(Params...), dim3 grid, size_t lds, hipStream_t st, const Args &...args)
 {
-    auto kern = icp_fit_kernel<G, LDS, StartT, MODE, SWEEP>;
-    const size_t lds = h->lds_bytes;
     if (lds > 48 * 1024)
-        SLAM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(n_scans), dim3(kBlock), lds, st, h->mv, fa);
+        SLAM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, args...);
     SLAM_HIP(hipGetLastError());
     return SLAM_OK;
 }
 
-template <int MODE>
-int launch_fit_sweep(slam_icp *h, const FitArgs &fa, int n_scans, hipStream_t st)
+using FitKernel = void (*)(ModelView, FitArgs);
+enum class SearchForm { ring, lists }; // what every iteration of a launch of icp_fit_kernel searches with
+
+// the point-to-point ring kernel with G lanes per point (0: chosen per pass); null: no such width
+template <bool LDS, typename StartT>
+FitKernel ring_kernel_p2p(int G)
 {
-    if (h->sweep == 2 && h->have_lists) { // lists in LDS, cell index from HBM/L2
-        auto         kern = h->start32 ? icp_fit_kernel<1, false, uint32_t, MODE, 2> : icp_fit_kernel<1, false, uint16_t, MODE, 2>;
-        const size_t lds = h->list_lds_bytes;
-        SLAM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(n_scans), dim3(kBlock), lds, st, h->mv, fa);
-        SLAM_HIP(hipGetLastError());
+    switch (G) {
+    case 0: return icp_fit_kernel<0, LDS, StartT, SLAM_ICP_P2P, 0>;
+    case 1: return icp_fit_kernel<1, LDS, StartT, SLAM_ICP_P2P, 0>;
+    case 2: return icp_fit_kernel<2, LDS, StartT, SLAM_ICP_P2P, 0>;
+    case 4: return icp_fit_kernel<4, LDS, StartT, SLAM_ICP_P2P, 0>;
+    case 8: return icp_fit_kernel<8, LDS, StartT, SLAM_ICP_P2P, 0>;
+    case 16: return icp_fit_kernel<16, LDS, StartT, SLAM_ICP_P2P, 0>;
+    case 32: return icp_fit_kernel<32, LDS, StartT, SLAM_ICP_P2P, 0>;
+    case 64: return icp_fit_kernel<64, LDS, StartT, SLAM_ICP_P2P, 0>;
+    }
+    return nullptr;
+}
+
+// The instance of icp_fit_kernel, and its dynamic LDS, for one search form on this handle's model: by solver, lanes per
+// point, whether the index is in LDS, the width of its cell starts, and -- `phase` 0, a launch that runs every iteration --
+// wave tiles.
+int select_fit_kernel(const slam_icp *h, SearchForm form, int phase, FitKernel *kern, size_t *lds)
+{
+    // point-to-line (not what the reference builds) comes in the ring form of the default width only; the other widths and
+    // the list form for every iteration exist for the point-to-point measurements of DESIGN.md 4.1
+    const bool p2l = h->prm.mode == SLAM_ICP_P2L;
+    // (launch_fit asks for the lists of every iteration by lanes_per_point alone: a point-to-line handle with that setting
+    // runs its ring form, as it always has)
+    if (form == SearchForm::lists && !p2l) { // lists in LDS, cell index from HBM/L2
+        if (!h->have_lists) {
+            set_error("the list-sweep kernel needs halo lists, and they did not fit LDS for this model");
+            return SLAM_E_UNSUPPORTED;
+        }
+        *kern = h->start32 ? icp_fit_kernel<1, false, uint32_t, SLAM_ICP_P2P, 2> : icp_fit_kernel<1, false, uint16_t, SLAM_ICP_P2P, 2>;
+        *lds = h->list_lds_bytes;
         return SLAM_OK;
     }
-    set_error("the list-sweep kernel needs halo lists, and they did not fit LDS for this model");
-    return SLAM_E_UNSUPPORTED;
-}
-
-// the ring form on an index in HBM/L2 with the wavefronts' model tiles in the otherwise empty LDS (two lanes per point: a
-// wavefront's pass is 32 adjacent beams, whose 3 x 3 blocks one tile holds)
-template <typename StartT, int MODE>
-int launch_fit_tiled(slam_icp *h, const FitArgs &fa, int n_scans, hipStream_t st)
-{
-    auto         kern = icp_fit_kernel<2, false, StartT, MODE, 0, true>;
-    const size_t lds = kScratchBytes + (size_t)kWaves * kWaveTileBytes;
-    static_assert(kScratchBytes + kWaves * kWaveTileBytes <= kLdsTotal, "sixteen wave tiles beside the scratch");
-    SLAM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(n_scans), dim3(kBlock), lds, st, h->mv, fa);
-    SLAM_HIP(hipGetLastError());
+    const int G = p2l ? 2 : h->G;
+    *lds = h->lds_bytes;
+    if (h->in_lds) {
+        *kern = p2l ? icp_fit_kernel<2, true, uint16_t, SLAM_ICP_P2L, 0> : ring_kernel_p2p<true, uint16_t>(G);
+    } else if (G == 2 && h->prm.wave_tiles > 0 && phase == 0) {
+        // an index in HBM/L2 with the wavefronts' model tiles in the otherwise empty LDS (two lanes per point: a wavefront's
+        // pass is 32 adjacent beams, whose 3 x 3 blocks one tile holds)
+        static_assert(kScratchBytes + kWaves * kWaveTileBytes <= kLdsTotal, "sixteen wave tiles beside the scratch");
+        *kern = h->start32 ? (p2l ? icp_fit_kernel<2, false, uint32_t, SLAM_ICP_P2L, 0, true> : icp_fit_kernel<2, false, uint32_t, SLAM_ICP_P2P, 0, true>)
+                           : (p2l ? icp_fit_kernel<2, false, uint16_t, SLAM_ICP_P2L, 0, true> : icp_fit_kernel<2, false, uint16_t, SLAM_ICP_P2P, 0, true>);
+        *lds = kScratchBytes + (size_t)kWaves * kWaveTileBytes;
+    } else if (h->start32) {
+        *kern = p2l ? icp_fit_kernel<2, false, uint32_t, SLAM_ICP_P2L, 0> : ring_kernel_p2p<false, uint32_t>(G);
+    } else {
+        *kern = p2l ? icp_fit_kernel<2, false, uint16_t, SLAM_ICP_P2L, 0> : ring_kernel_p2p<false, uint16_t>(G);
+    }
+    if (!*kern) {
+        set_error("lanes_per_point must be 0 (per-pass choice) or one of 1,2,4,8,16,32,64 (got %d)", h->G);
+        return SLAM_E_INVALID;
+    }
     return SLAM_OK;
 }
 
-template <int G, int MODE>
-int launch_fit_g(slam_icp *h, const FitArgs &fa, int n_scans, hipStream_t st)
+int launch_fit_form(const slam_icp *h, SearchForm form, const FitArgs &fa, int n_scans, hipStream_t st)
 {
-    if (h->in_lds) return launch_fit_t<G, true, uint16_t, MODE>(h, fa, n_scans, st);
-    if constexpr (G == 2) {
-        if (h->prm.wave_tiles > 0 && fa.phase == 0)
-            return h->start32 ? launch_fit_tiled<uint32_t, MODE>(h, fa, n_scans, st) : launch_fit_tiled<uint16_t, MODE>(h, fa, n_scans, st);
-    }
-    if (h->start32) return launch_fit_t<G, false, uint32_t, MODE>(h, fa, n_scans, st);
-    return launch_fit_t<G, false, uint16_t, MODE>(h, fa, n_scans, st);
-}
-
-template <int MODE>
-int launch_fit_m(slam_icp *h, const FitArgs &fa, int n_scans, hipStream_t st)
-{
-    // point-to-line (not what the reference builds) comes in the default width only; the other widths
-    // exist for the point-to-point measurements of DESIGN.md 4.1
-    if constexpr (MODE == SLAM_ICP_P2L) {
-        return launch_fit_g<2, MODE>(h, fa, n_scans, st);
-    } else {
-        if (h->sweep) return launch_fit_sweep<SLAM_ICP_P2P>(h, fa, n_scans, st);
-        switch (h->G) {
-        case 0: return launch_fit_g<0, MODE>(h, fa, n_scans, st);
-        case 1: return launch_fit_g<1, MODE>(h, fa, n_scans, st);
-        case 2: return launch_fit_g<2, MODE>(h, fa, n_scans, st);
-        case 4: return launch_fit_g<4, MODE>(h, fa, n_scans, st);
-        case 8: return launch_fit_g<8, MODE>(h, fa, n_scans, st);
-        case 16: return launch_fit_g<16, MODE>(h, fa, n_scans, st);
-        case 32: return launch_fit_g<32, MODE>(h, fa, n_scans, st);
-        case 64: return launch_fit_g<64, MODE>(h, fa, n_scans, st);
-        }
-    }
-    set_error("lanes_per_point must be 0 (per-pass choice) or one of 1,2,4,8,16,32,64 (got %d)", h->G);
-    return SLAM_E_INVALID;
+    FitKernel kern = nullptr;
+    size_t    lds = 0;
+    SLAM_TRY(select_fit_kernel(h, form, fa.phase, &kern, &lds));
+    return launch_kernel(kern, dim3(n_scans), lds, st, h->mv, fa);
 }
 
 // lanes per scene point in the ring form of a pair: one is a measurement of the point-to-point kernel;
@@ -1197,27 +1201,63 @@ auto pair_kernel(int lanes) -> void (*)(ModelView, FitArgs, int)
 // The default schedule of a batch, either solver: first iterations by the ring search (index in LDS), the rest by the
 // list sweeps (halo lists in LDS), one launch -- every workgroup swaps its LDS contents when its own scan gets there.
 template <int MODE>
-int launch_fit_fused(slam_icp *h, FitArgs &fa, int n_scans, hipStream_t st)
+int launch_fit_fused(const slam_icp *h, FitArgs &fa, int n_scans, hipStream_t st)
 {
     fa.switch_iter = h->switch_iter;
     // two scans per workgroup where the batch leaves CUs to spare for it (slam_icp_params::pair_scans)
-    const size_t pair_lds = std::max(h->lds_bytes, h->list_lds_bytes) - kScratchBytes + 2 * TeamDims<kBlock / 2>::kScratch;
+    const size_t lds = std::max(h->lds_bytes, h->list_lds_bytes), pair_lds = lds - kScratchBytes + 2 * TeamDims<kBlock / 2>::kScratch;
     // Library default: from two scans per CU on.  Measured on config 2's scans (tools/pair_time.py): 256 scans on 256 CUs
     // 0.39 ms alone against 0.61 in pairs (half the CUs idle); 512 scans 0.72 against 0.61; 1024 scans 1.31 against 1.16.
     const int pair = h->pair > 0 ? h->pair : (h->pair == 0 && n_scans >= 2 * h->n_cu ? 2 : 0);
     if (pair && pair_lds + 64 <= kLdsTotal && n_scans >= 2) { // (+ the kernel's one static word, with its alignment)
         auto kern = h->start32 ? pair_kernel<uint32_t, MODE>(pair) : pair_kernel<uint16_t, MODE>(pair);
-        SLAM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pair_lds));
-        hipLaunchKernelGGL(kern, dim3((n_scans + 1) / 2), dim3(kBlock), pair_lds, st, h->mv, fa, n_scans);
-        SLAM_HIP(hipGetLastError());
-        return SLAM_OK;
+        return launch_kernel(kern, dim3((n_scans + 1) / 2), pair_lds, st, h->mv, fa, n_scans);
     }
-    auto         kern = h->start32 ? icp_fit_fused_kernel<uint32_t, MODE> : icp_fit_fused_kernel<uint16_t, MODE>;
-    const size_t lds = std::max(h->lds_bytes, h->list_lds_bytes);
-    SLAM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(n_scans), dim3(kBlock), lds, st, h->mv, fa);
-    SLAM_HIP(hipGetLastError());
+    auto kern = h->start32 ? icp_fit_fused_kernel<uint32_t, MODE> : icp_fit_fused_kernel<uint16_t, MODE>;
+    return launch_kernel(kern, dim3(n_scans), lds, st, h->mv, fa);
+}
+
+// phase events (a measurement build sets them): the times of the two launches of the call before, folded in before its
+// events are used again
+int fold_phase_events(slam_icp *h)
+{
+    if (!h->ev_pending) return SLAM_OK;
+    float a = 0, b = 0;
+    SLAM_HIP(hipEventSynchronize(h->ev[2]));
+    SLAM_HIP(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+    SLAM_HIP(hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
+    h->phase_ms[0] += a;
+    h->phase_ms[1] += b;
+    ++h->phase_calls;
+    h->ev_pending = false;
     return SLAM_OK;
+}
+
+// The same schedule as two launches (slam_icp_params::split_launch, or while a measurement build times the phases): the
+// second launch starts when the slowest scan of the first has handed over.
+int launch_fit_split(slam_icp *h, FitArgs &fa, int n_scans, hipStream_t st)
+{
+    SLAM_TRY(h->w_state.reserve(sizeof(int) * (size_t)n_scans));
+    fa.state = static_cast<int *>(h->w_state.p);
+    fa.switch_iter = h->switch_iter;
+    fa.phase = 1;
+    if (h->phase_events) {
+        SLAM_TRY(fold_phase_events(h));
+        for (auto &e : h->ev)
+            if (!e) SLAM_HIP(hipEventCreate(&e));
+        SLAM_HIP(hipEventRecord(h->ev[0], st));
+    }
+    int rc = launch_fit_form(h, SearchForm::ring, fa, n_scans, st);
+    if (h->phase_events) SLAM_HIP(hipEventRecord(h->ev[1], st));
+    fa.phase = 2;
+    fa.R0 = fa.R; // the second launch carries on from what the first left
+    fa.t0 = fa.t;
+    if (rc == SLAM_OK) rc = launch_fit_form(h, SearchForm::lists, fa, n_scans, st);
+    if (h->phase_events) {
+        SLAM_HIP(hipEventRecord(h->ev[2], st));
+        h->ev_pending = true;
+    }
+    return rc;
 }
 
 int launch_fit(slam_icp *h, const FitArgs &fa_in, int n_scans, hipStream_t st)
@@ -1228,54 +1268,70 @@ int launch_fit(slam_icp *h, const FitArgs &fa_in, int n_scans, hipStream_t st)
     fa.phase = 0;
     fa.switch_iter = 0;
     fa.far_div = h->far_div;
+    const bool both = h->two_phase && h->have_lists; // ring search first, list sweeps after the hand-over
     if (h->prm.mode == SLAM_ICP_P2L) {
         SLAM_REQUIRE(h->mv.normals, SLAM_E_INVALID, "point-to-line mode needs model normals");
         // the same schedule as point-to-point (the nine sums differ, nothing else); a model whose index or lists do not fit
         // LDS runs the ring search for every iteration
-        if (h->two_phase && h->have_lists && h->in_lds && h->mv.lnormals) return launch_fit_fused<SLAM_ICP_P2L>(h, fa, n_scans, st);
-        return launch_fit_m<SLAM_ICP_P2L>(h, fa, n_scans, st);
+        if (both && h->in_lds && h->mv.lnormals) return launch_fit_fused<SLAM_ICP_P2L>(h, fa, n_scans, st);
+        return launch_fit_form(h, SearchForm::ring, fa, n_scans, st);
     }
-    if (h->two_phase && h->have_lists && h->in_lds && !h->phase_events && !h->split_launch)
-        return launch_fit_fused<SLAM_ICP_P2P>(h, fa, n_scans, st);
-    if (h->two_phase && h->have_lists) {
-        // the same schedule as two launches (SLAM_ICP_SPLIT=1, or while the phases are being timed): the second
-        // launch starts when the slowest scan of the first has handed over
-        SLAM_TRY(h->w_state.reserve(sizeof(int) * (size_t)n_scans));
-        fa.state = static_cast<int *>(h->w_state.p);
-        fa.switch_iter = h->switch_iter;
-        fa.phase = 1;
-        const int keep = h->sweep;
-        if (h->phase_events) {
-            if (h->ev_pending) { // fold the previous call's times in before its events are reused
-                float a = 0, b = 0;
-                SLAM_HIP(hipEventSynchronize(h->ev[2]));
-                SLAM_HIP(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
-                SLAM_HIP(hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
-                h->phase_ms[0] += a;
-                h->phase_ms[1] += b;
-                ++h->phase_calls;
-                h->ev_pending = false;
-            }
-            for (auto &e : h->ev)
-                if (!e) SLAM_HIP(hipEventCreate(&e));
-            SLAM_HIP(hipEventRecord(h->ev[0], st));
-        }
-        h->sweep = 0;
-        int rc = launch_fit_m<SLAM_ICP_P2P>(h, fa, n_scans, st);
-        if (h->phase_events) SLAM_HIP(hipEventRecord(h->ev[1], st));
-        h->sweep = 2;
-        fa.phase = 2;
-        fa.R0 = fa.R; // the second launch carries on from what the first left
-        fa.t0 = fa.t;
-        if (rc == SLAM_OK) rc = launch_fit_m<SLAM_ICP_P2P>(h, fa, n_scans, st);
-        if (h->phase_events) {
-            SLAM_HIP(hipEventRecord(h->ev[2], st));
-            h->ev_pending = true;
-        }
-        h->sweep = keep;
-        return rc;
+    if (both && h->in_lds && !h->phase_events && !h->split_launch) return launch_fit_fused<SLAM_ICP_P2P>(h, fa, n_scans, st);
+    if (both) return launch_fit_split(h, fa, n_scans, st);
+    // one form for every iteration: what slam_icp_params::lanes_per_point asked for (icp_new)
+    return launch_fit_form(h, h->sweep ? SearchForm::lists : SearchForm::ring, fa, n_scans, st);
+}
+
+// what one call knows and the handle does not (slam_icp_fit; the C-ABI batch entry points pass the defaults)
+struct FitCall {
+    double *step_pose = nullptr;   // where every executed step leaves the pose it began with (slam_icp_get_edge_weight), or null
+    bool    skip_spread = false;   // not the spread form this time
+    int    *redo_mirror = nullptr; // where the spread launch leaves its redo flag for the host (pinned memory), or null
+    int     points_hint = 0;       // points of the batch when the caller knows them, else 0
+};
+
+// slam_icp_fit_batch_from_dev
+int fit_batch(slam_icp *icp, const double *d_pts, const int32_t *d_scan_off, const int32_t *d_scan_nga, int n_scans, const double *d_R0,
+              const double *d_t0, double *d_R, double *d_t, double indist, slam_icp_result *d_result, double *d_trace,
+              slam_stream_t stream, const FitCall &call)
+{
+    SLAM_REQUIRE(icp && d_scan_off && d_scan_nga && d_R0 && d_t0 && d_R && d_t && n_scans >= 0, SLAM_E_INVALID,
+                 "slam_icp_fit_batch_dev: bad arguments");
+    SLAM_TRY(require_device());
+    FitArgs fa;
+    fa.pts = reinterpret_cast<const double2 *>(d_pts);
+    fa.scan_off = d_scan_off;
+    fa.scan_nga = d_scan_nga;
+    fa.R = d_R;
+    fa.t = d_t;
+    fa.R0 = d_R0;
+    fa.t0 = d_t0;
+    fa.result = d_result;
+    fa.trace = d_trace;
+    fa.max_iter = icp->prm.max_iter;
+    fa.min_delta = icp->prm.min_delta;
+    fa.indist = indist;
+    fa.step_pose = call.step_pose;
+    fa.stamps = nullptr;
+#ifdef SLAM_MEASURE
+    if (getenv("SLAM_ICP_STAMPS")) {
+        SLAM_TRY(icp->w_stamps.reserve((size_t)n_scans * kWaves * kStampSlots * sizeof(long long)));
+        SLAM_HIP(hipMemsetAsync(icp->w_stamps.p, 0, (size_t)n_scans * kWaves * kStampSlots * sizeof(long long), as_stream(stream)));
+        fa.stamps = static_cast<long long *>(icp->w_stamps.p);
+        icp->n_stamps = n_scans * kWaves;
     }
-    return launch_fit_m<SLAM_ICP_P2P>(h, fa, n_scans, st);
+#endif
+    // few scans (one, in the reference's own usage): each scan spread over many workgroups of one persistent launch
+    fa.only = nullptr;
+    fa.spread_tag = 0;
+    fa.redo_mirror = call.redo_mirror;
+    if (takes_spread_form(icp, n_scans) && !call.skip_spread && !fa.stamps) {
+        // ... and behind it the workgroup-per-scan form for the scans whose workgroups did not all become resident together
+        // (another spread launch or a persistent kernel holding CUs: icp_single.hip): its workgroups find their scan's flag
+        // clear and exit -- a few microseconds -- unless the scan has to be redone.  A fit always completes (icp.cpp:80-114).
+        SLAM_TRY(launch_fit_spread(icp, fa, n_scans, as_stream(stream), &fa.only, call.points_hint));
+    }
+    return launch_fit(icp, fa, n_scans, as_stream(stream));
 }
 
 } // namespace
@@ -1298,13 +1354,15 @@ namespace slam {
 namespace icp {
 
 // Batches of so few scans run in the spread form (icp_single.hip): one persistent launch whose workgroups of a scan wait
-// for one another, with scratch that belongs to the handle -- a handle takes ONE such call at a time (batches in the
-// workgroup-per-scan forms may be in flight on several streams at once: they keep nothing in the handle).
+// for one another, with scratch that belongs to the handle -- a handle takes ONE such call at a time, and one slam_icp_fit
+// (its template, poses and result live in the handle's w_pts).  Batches in the workgroup-per-scan forms may be in flight
+// on several streams at once: what a call knows travels in its arguments, and they keep nothing in the handle (the
+// two-launch measurement schedule apart: its hand-over states are the handle's w_state).
 bool takes_spread_form(const slam_icp *h, int n_scans)
 {
     const int spread_max = h->prm.spread_scans > 0 ? std::min(h->prm.spread_scans, h->n_cu)
                                                    : (h->prm.spread_scans < 0 ? 0 : h->n_cu / kSpreadMinParts);
-    return n_scans >= 1 && n_scans <= spread_max && h->prm.lanes_per_point == 0 && !h->skip_spread;
+    return n_scans >= 1 && n_scans <= spread_max && h->prm.lanes_per_point == 0;
 }
 
 } // namespace icp
@@ -1561,44 +1619,7 @@ int slam_icp_fit_batch_from_dev(slam_icp_t *icp, const double *d_pts, const int3
                                 double *d_R, double *d_t, double indist, slam_icp_result *d_result, double *d_trace,
                                 slam_stream_t stream)
 {
-    SLAM_REQUIRE(icp && d_scan_off && d_scan_nga && d_R0 && d_t0 && d_R && d_t && n_scans >= 0, SLAM_E_INVALID,
-                 "slam_icp_fit_batch_dev: bad arguments");
-    SLAM_TRY(require_device());
-    FitArgs fa;
-    fa.pts = reinterpret_cast<const double2 *>(d_pts);
-    fa.scan_off = d_scan_off;
-    fa.scan_nga = d_scan_nga;
-    fa.R = d_R;
-    fa.t = d_t;
-    fa.R0 = d_R0;
-    fa.t0 = d_t0;
-    fa.result = d_result;
-    fa.trace = d_trace;
-    fa.max_iter = icp->prm.max_iter;
-    fa.min_delta = icp->prm.min_delta;
-    fa.indist = indist;
-    fa.step_pose = icp->want_step_pose ? reinterpret_cast<double *>(static_cast<unsigned char *>(icp->w_pts.p) + icp->step_pose_off) : nullptr;
-    fa.stamps = nullptr;
-#ifdef SLAM_MEASURE
-    if (getenv("SLAM_ICP_STAMPS")) {
-        SLAM_TRY(icp->w_stamps.reserve((size_t)n_scans * kWaves * kStampSlots * sizeof(long long)));
-        SLAM_HIP(hipMemsetAsync(icp->w_stamps.p, 0, (size_t)n_scans * kWaves * kStampSlots * sizeof(long long), as_stream(stream)));
-        fa.stamps = static_cast<long long *>(icp->w_stamps.p);
-        icp->n_stamps = n_scans * kWaves;
-    }
-#endif
-    // few scans (one, in the reference's own usage): each scan spread over many workgroups of one persistent launch
-    fa.only = nullptr;
-    fa.spread_tag = 0;
-    fa.redo_mirror = icp->redo_mirror;
-    if (takes_spread_form(icp, n_scans) && !fa.stamps) {
-        // ... and behind it the workgroup-per-scan form for the scans whose workgroups did not all become resident together
-        // (another spread launch or a persistent kernel holding CUs: icp_single.hip): its workgroups find their scan's flag
-        // clear and exit -- a few microseconds -- unless the scan has to be redone.  A fit always completes (icp.cpp:80-114).
-        SLAM_TRY(launch_fit_spread(icp, fa, n_scans, as_stream(stream), &fa.only));
-        return launch_fit(icp, fa, n_scans, as_stream(stream));
-    }
-    return launch_fit(icp, fa, n_scans, as_stream(stream));
+    return fit_batch(icp, d_pts, d_scan_off, d_scan_nga, n_scans, d_R0, d_t0, d_R, d_t, indist, d_result, d_trace, stream, FitCall());
 }
 
 int slam_icp_fit(slam_icp_t *icp, const double *t_ga, int n_tga, const double *t_nga, int n_tnga,
@@ -1643,21 +1664,17 @@ int slam_icp_fit(slam_icp_t *icp, const double *t_ga, int n_tga, const double *t
     *h_redo = 0;
     hipStream_t st = nullptr;
     SLAM_HIP(hipMemcpyAsync(dp, hp, o_res, hipMemcpyHostToDevice, st));
-    icp->want_step_pose = true;
     icp->step_pose_off = o_step;
-    icp->spread_points_hint = n;
-    icp->skip_spread = icp->spread_backoff > 0; // the spread form lost its CUs a moment ago: not again right away
-    if (icp->skip_spread) --icp->spread_backoff;
-    icp->redo_mirror = h_redo;
-    const int rc_fit = slam_icp_fit_batch_from_dev(icp, reinterpret_cast<double *>(dp), reinterpret_cast<int32_t *>(dp + hdr),
-                                                   reinterpret_cast<int32_t *>(dp + hdr + 8), 1,
-                                                   reinterpret_cast<double *>(dp + o_pose_in), reinterpret_cast<double *>(dp + o_pose_in + 32),
-                                                   reinterpret_cast<double *>(hp + o_pose_out), reinterpret_cast<double *>(hp + o_pose_out + 32),
-                                                   indist, h_res, nullptr, st);
-    icp->want_step_pose = false;
-    icp->skip_spread = false;
-    icp->redo_mirror = nullptr;
-    SLAM_TRY(rc_fit);
+    FitCall call;
+    call.step_pose = reinterpret_cast<double *>(dp + o_step);
+    call.points_hint = n;
+    call.skip_spread = icp->spread_backoff > 0; // the spread form lost its CUs a moment ago: not again right away
+    if (call.skip_spread) --icp->spread_backoff;
+    call.redo_mirror = h_redo;
+    SLAM_TRY(fit_batch(icp, reinterpret_cast<double *>(dp), reinterpret_cast<int32_t *>(dp + hdr), reinterpret_cast<int32_t *>(dp + hdr + 8), 1,
+                       reinterpret_cast<double *>(dp + o_pose_in), reinterpret_cast<double *>(dp + o_pose_in + 32),
+                       reinterpret_cast<double *>(hp + o_pose_out), reinterpret_cast<double *>(hp + o_pose_out + 32), indist, h_res, nullptr,
+                       st, call));
     icp->last_n = n;
     icp->last_nga = n_tga;
     icp->last_indist = indist;
@@ -1744,16 +1761,7 @@ int slam_icp_debug_phase_events(slam_icp_t *icp, int on)
 int slam_icp_debug_phase_ms(slam_icp_t *icp, double out[2], int *calls)
 {
     SLAM_REQUIRE(icp && out, SLAM_E_INVALID, "null argument");
-    if (icp->ev_pending) {
-        float a = 0, b = 0;
-        SLAM_HIP(hipEventSynchronize(icp->ev[2]));
-        SLAM_HIP(hipEventElapsedTime(&a, icp->ev[0], icp->ev[1]));
-        SLAM_HIP(hipEventElapsedTime(&b, icp->ev[1], icp->ev[2]));
-        icp->phase_ms[0] += a;
-        icp->phase_ms[1] += b;
-        ++icp->phase_calls;
-        icp->ev_pending = false;
-    }
+    SLAM_TRY(fold_phase_events(icp));
     const int n = icp->phase_calls > 0 ? icp->phase_calls : 1;
     out[0] = icp->phase_ms[0] / n;
     out[1] = icp->phase_ms[1] / n;

@@ -140,7 +140,6 @@ struct slam_icp {
     slam::PoolMem   d_normals;
     slam::PoolMem   d_lnormals; // normals per halo-list entry (P2L)
     slam::PoolMem   w_pts, w_stamps, w_ew, w_state, w_single; // w_pts: slam_icp_fit's block (points + header)
-    int             spread_points_hint = 0; // points of the batch when the caller knows them (slam_icp_fit), else 0
     size_t          step_pose_off = 0;   // where in w_pts the pose of the last executed step lies
     bool            two_phase = false;   // ring search, then list sweeps (the point-to-point default)
     int             pair = 0;             // two scans per workgroup in the fused schedule: lanes per point of its ring form; 0 = by batch size, -1 = never
@@ -154,7 +153,6 @@ struct slam_icp {
     int             switch_iter = 10;    // ring-search iterations before a scan may change to list sweeps (tools/switch_sweep.sh); point-to-line: 2 (icp_new)
     int             n_stamps = 0;
     int             spread_stamp_iters = 0; // measurement build: iterations per workgroup in the spread form's stamps (n_stamps < 0)
-    bool            want_step_pose = false; // set around slam_icp_fit()
     int             last_n = 0, last_nga = 0; // template of the last slam_icp_fit()
     double          last_indist = 0;
     bool            have_last = false;
@@ -166,8 +164,6 @@ struct slam_icp {
     // handle's next fits go straight to the one-workgroup form and try the spread form again later (icp_single.hip).
     unsigned        spread_tag = 1;             // tag base of the next spread launch (FitArgs::spread_tag)
     int             spread_backoff = 0;         // single fits still to be done without the spread form
-    bool            skip_spread = false;        // set around one slam_icp_fit_batch_dev call
-    int            *redo_mirror = nullptr;      // set around slam_icp_fit(): where the spread launch leaves its redo flag for the host (pinned)
     bool            build_beside = false;       // the index build's kernels must fit beside a resident registration workgroup (mapper)
     double          build_ms[4] = {0, 0, 0, 0}; // enqueueing the build, its one wait (the other two: unused since the plan moved to the device)
     slam_icp_pending *pending = nullptr;        // between build_index_begin and build_index_finish

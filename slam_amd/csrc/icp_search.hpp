@@ -1411,7 +1411,7 @@ constexpr int kSpreadMinParts = 16; // the spread form takes batches that leave 
 // persistent launch
 // *redo_flags: device array [n_scans], non-zero for a scan the launch could not finish (its R, t untouched): the caller
 // enqueues the workgroup-per-scan form behind it with FitArgs::only = that array
-int launch_fit_spread(slam_icp *h, const FitArgs &fa, int n_scans, hipStream_t st, const int **redo_flags);
+int launch_fit_spread(slam_icp *h, const FitArgs &fa, int n_scans, hipStream_t st, const int **redo_flags, int points_hint);
 bool takes_spread_form(const slam_icp *h, int n_scans); // icp.hip
 
 } // namespace icp

@@ -1305,7 +1305,7 @@ std::mutex  g_spread_mu;
 hipEvent_t  g_spread_done[16] = {};
 } // namespace
 
-int launch_fit_spread(slam_icp *h, const FitArgs &fa, int n_scans, hipStream_t st, const int **redo_flags)
+int launch_fit_spread(slam_icp *h, const FitArgs &fa, int n_scans, hipStream_t st, const int **redo_flags, int points_hint)
 {
     int dev = 0, n_cu = 0;
     SLAM_HIP(hipGetDevice(&dev));
@@ -1349,7 +1349,7 @@ int launch_fit_spread(slam_icp *h, const FitArgs &fa, int n_scans, hipStream_t s
     else if (ordered)
         SLAM_HIP(hipStreamWaitEvent(st, done, 0)); // behind the spread launch before this one, on whatever stream it went
     // per scene point, what its last search left for the next (positions beyond the buffer search unseeded)
-    const int qcap = std::max(h->spread_points_hint, 1 << 16);
+    const int qcap = std::max(points_hint, 1 << 16);
     SLAM_TRY(h->w_state.reserve(sizeof(float2) * (size_t)qcap));
     float2    *qstate = static_cast<float2 *>(h->w_state.p);
     const dim3 grid(parts, n_scans);

@@ -22,7 +22,10 @@ FORMS = {
     "fused": ONE_PER_WG,                                                       # the default schedule, one scan per workgroup
     "ring1": dict(spread_scans=-1, lanes_per_point=1),                         # the ring search for every iteration
     "ring2": dict(spread_scans=-1, lanes_per_point=2),
+    "ring4": dict(spread_scans=-1, lanes_per_point=4),
     "ring8": dict(spread_scans=-1, lanes_per_point=8),
+    "ring16": dict(spread_scans=-1, lanes_per_point=16),
+    "ring32": dict(spread_scans=-1, lanes_per_point=32),
     "ring64": dict(spread_scans=-1, lanes_per_point=64),
     "ring_per_pass": dict(spread_scans=-1, lanes_per_point=-1),
     "lists": dict(spread_scans=-1, lanes_per_point=-2),                        # the list sweeps for every iteration
